@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- LLK evaluations per second on the BASELINE.json workload.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 runs one process per GPU over RCCL.  Started under `python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N` the ranks come from the environment; started plainly
@@ -22,8 +22,17 @@ the N ranks by the library's own C++ group (vb2_shard_group_create_rank: launch 
 ncclAllReduce of the batch's partial LLKs per step, BASELINE.json configs[3]) -- its evals/s
 and its OptimizeLLK wall-clock.  `--mode marker` makes that the primary metric (strong scaling).
 
-Prints ONE JSON line on rank 0.  The oracle (oracle/) is used only as the checker of a small
-parity probe and as the cpu_baseline leg; it is never the thing timed as `value`.
+Prints ONE JSON line on rank 0.  A plain run does only what that line's headline needs: set up,
+warm up, time the K steps (`ms_per_step` = wall-clock of one), write the outputs if asked, print.
+`--dump-outputs DIR` writes what the last timed step computed -- the batch's LLKs, the array a
+caller of the launch receives -- as DIR/llk.npy (float64; rank 0's sample).  The inputs are seeded:
+the same arguments give the same inputs on every run and every build.
+
+`--full` adds everything else the line has carried: the roofline (with the issue ceiling measured
+on the device), the marker-sharded leg, search_point, create_ms, the wide and mid quality
+alphabets, OptimizeLLK, the cohort legs, the parity probe against the oracle and the CPU baseline.
+The oracle (oracle/) is used only as the checker of that parity probe and as the cpu_baseline leg;
+it is never the thing timed as `value`.
 """
 import argparse
 import json
@@ -60,10 +69,16 @@ def parse_args():
     ap.add_argument("--cohort-samples", type=int, default=32, help="samples of the single-GPU cohort leg (0 = skip)")
     ap.add_argument("--cohort-files", type=int, default=256,
                     help="samples of the cohort-from-text-files leg (BASELINE configs[4] per GPU; 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs beyond the headline: roofline, marker_sharded, search_point, create_ms, quality "
+                         "alphabets, optimize, cohort, parity probe, cpu_baseline (the --no-* options trim these)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the LLKs the last timed step computed to DIR/llk.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-optimize", action="store_true")
     ap.add_argument("--soft-exit", action="store_true",
-                    help="leave through the interpreter's normal exit (profilers flush their output there) instead of os._exit")
+                    help="(the default: the run leaves through the interpreter's normal exit, where profilers and exit "
+                         "handlers see the process whole; kept for existing command lines)")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip search_point / cohort / marker_sharded legs (profiling runs)")
     return ap.parse_args()
@@ -227,7 +242,7 @@ def main():
     if share_gpu and args.mode == "marker":
         raise SystemExit("VB2_BENCH_SHARE_GPU=1 cannot run --mode marker (RCCL needs one device per rank)")
     uid_error = None
-    if (world > 1 or not args.no_extras) and not share_gpu:
+    if (world > 1 or not args.no_extras) and (args.full or args.mode == "marker") and not share_gpu:
         # the library's own marker-shard group (C++: contexts + ncclAllReduce bound from librccl)
         box = [None, None]
         if rank == 0:
@@ -286,6 +301,9 @@ def main():
     evals_per_step = B * (world if args.mode == "sample" else 1)
     value = evals_per_step * args.steps / wall
     llk_dev = llk_host.copy() if args.mode == "marker" else out.cpu().numpy().copy()
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "llk.npy"), np.asarray(llk_dev, dtype=np.float64))
 
     if info is None:
         info = dict(num_read=shared.num_read, num_active_marker=shared.num_marker, num_code=-1, arch="gfx950",
@@ -314,7 +332,7 @@ def main():
         },
     }
 
-    if rank == 0 and args.mode == "sample":
+    if rank == 0 and args.mode == "sample" and args.full:
         # ---- roofline of the dominant kernel: frac = t_ideal / t_measured, t_ideal = the LONGEST of the three
         # times the launch would take if one resource alone ran at its peak --
         #   lds : bytes the read loops gather from the LDS tables (48 B per step and point: vb2_info.num_step, computed by the
@@ -423,7 +441,7 @@ def main():
     # Guarded: whatever happens in here (librccl missing, a communicator that does not come up, a
     # rank that dies and leaves the others in a collective) must not cost the run its main line --
     # an exception is recorded, and a watchdog prints what there is and ends every rank after 4 minutes.
-    if args.mode == "sample" and not args.no_extras and not share_gpu:
+    if args.full and args.mode == "sample" and not args.no_extras and not share_gpu:
         import threading
 
         def bail():
@@ -506,7 +524,7 @@ def main():
             result["marker_sharded"] = {"error": "%s: %s" % (type(exc).__name__, exc)}
         watchdog.cancel()
 
-    if rank == 0 and args.mode == "sample":
+    if rank == 0 and args.mode == "sample" and args.full:
         if world == 1 and not args.no_extras:
             # the operating points of the actual search: a 4-point launch (one Nelder-Mead
             # iteration: R, E, C_A, C_R) and a single point
@@ -830,15 +848,13 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     # RCCL prints a version banner through C stdio when its first communicator comes up; push that
-    # out first, so that the JSON line is the LAST line of stdout, and leave without running
-    # anything else that might print
+    # out first, so that the JSON line is the LAST line of stdout (whatever prints after it, on the way
+    # out of the interpreter, goes to file descriptor 1 = stderr)
     import ctypes
     ctypes.CDLL(None).fflush(None)
     if rank == 0:
         emit(result)
     sys.stdout.flush()
-    if not args.soft_exit:
-        os._exit(0)
 
 
 if __name__ == "__main__":

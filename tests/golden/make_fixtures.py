@@ -3,10 +3,11 @@
 
     python tests/golden/make_fixtures.py            # rewrite kat.json's LLK values + synthetic_c2/c3.json
     python tests/golden/make_fixtures.py --check    # recompute and compare with what is committed
+    python tests/golden/make_fixtures.py --gpu-reference tests/golden/reference_on_gpu.json   # on a gfx950 box
 
 Run in the BUILD container (it uses the oracle and, for the search half, oracle/_ref: the
-reference's own AmoebaMinimizer compiled in place from /root/reference).  Nothing here runs on
-the GPU box; the tests read the JSON files.
+reference's own AmoebaMinimizer compiled in place from /root/reference).  Only --gpu-reference
+runs on the GPU box (with the oracle/_ref built here); the tests read the JSON files.
 
 What pins what:
   * tests/golden/expected/* and the two pileups are byte-identical copies of the reference's own
@@ -25,6 +26,11 @@ What pins what:
     -- alpha, llk1, llk0, evaluation count, a digest of the whole evaluation trace -- computed
     twice: with the oracle's minimiser and with the reference's own (oracle/_ref); the two must
     agree exactly or nothing is written.
+  * reference_runs.json: the reference's own minimisers (oracle/_ref) on the cases the tests hold
+    the restated and the product's minimisers to; reference_on_gpu.json: the reference's
+    AmoebaMinimizer driving the product's GPU likelihood (oracle/ref_adapter.cpp).  Results,
+    evaluation counts and digests of the evaluation traces: the tests need no compiled reference,
+    and compare with the live one as well where oracle/_ref is built.
 """
 import argparse
 import hashlib
@@ -220,10 +226,88 @@ def norm_hex(h):
     return float.fromhex(h).hex()
 
 
+def run_record(r):
+    """An optimiser's estimate (hex-floats), its evaluation count and the digest of its whole evaluation trace."""
+    out = {key: float(r[key]).hex() for key in ("alpha", "llk1", "llk0")}
+    out.update(num_eval=r["num_eval"], trace_count=r["trace_count"], trace_sha256=trace_digest(r["trace"]))
+    return out
+
+
+def reference_runs():
+    """reference_runs.json: the reference's own minimisers (oracle/_ref) on the cases of tests/test_oracle_golden.py and
+    tests/test_abi_and_host.py -- results, evaluation counts, digests of the points evaluated in order."""
+    from oracle import binding, refio
+    if binding.ref_lib() is None:
+        raise SystemExit("reference_runs.json needs oracle/_ref (make -C oracle ref with the reference tree present)")
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_abi_and_host
+    import test_oracle_golden
+    flat, _, _ = refio.load_flat(HAPMAP, os.path.join(HERE, "test.LongRead.pileup"), 2, sanity_disabled=True)
+    od = binding.OracleData(flat)
+    search = {json.dumps(args, sort_keys=True): run_record(od.optimize(minimizer="reference", trace_capacity=4096, **args))
+              for args in test_oracle_golden.SEARCH_ARGS}
+    amoeba = []
+    for fn, start, tol in test_oracle_golden.amoeba_cases():
+        pts = []
+        ret, point = binding.amoeba(lambda v: (pts.append(v.copy()), fn(v))[1], start, tol, "reference")
+        amoeba.append(dict(ret=float(ret).hex(), point=[float(x).hex() for x in point], num_eval=len(pts),
+                           points_sha256=sha(np.array(pts))))
+    line = []
+    for fn, lo, hi, tol in test_abi_and_host.line_search_cases(HERE):
+        xs = []
+        want = binding.reference_scalar_minimize(lambda x: (xs.append(x), fn(x))[1], lo, hi, tol)
+        line.append(dict(want={key: float(v).hex() for key, v in want.items()}, num_eval=len(xs),
+                         x_sha256=sha(np.array(xs))))
+    return dict(_what="the reference's own AmoebaMinimizer and ScalarMinimizer (MathGenMin.cpp, MathGold.cpp; oracle/_ref) "
+                      "on the cases of tests/test_oracle_golden.py and tests/test_abi_and_host.py: results, evaluation "
+                      "counts, sha256 of the points evaluated (float64, in order); regenerate with "
+                      "tests/golden/make_fixtures.py",
+                amoeba_search=search, amoeba_functions=amoeba, line_search=line)
+
+
+def reference_on_gpu():
+    """reference_on_gpu.json (python tests/golden/make_fixtures.py --gpu-reference OUT, on a gfx950 box with oracle/_ref):
+    the reference's AmoebaMinimizer driving the product's GPU likelihood through the C-ABI (oracle/ref_adapter.cpp)."""
+    import verifybamid_amd as vb
+    from oracle import binding
+    from verifybamid_amd import _abi
+    if binding.ref_lib() is None:
+        raise SystemExit("reference_on_gpu.json needs oracle/_ref")
+    kat = json.load(open(os.path.join(HERE, "kat.json")))
+    models = {}
+    for name, spec in kat["models"].items():
+        if name.startswith("_"):
+            continue
+        d = vb.PileupData.from_files(HAPMAP, os.path.join(HERE, spec["pileup"]), 2, disable_sanity=True)
+        with vb.LikelihoodContext(d) as ctx:
+            recs = [binding.reference_optimiser_on_gpu(_abi.lib(), ctx._h, 2, bracket=b, **spec["args"]) for b in (True, False)]
+        recs = [dict(run_record(r), pc=[float(x).hex() for x in r["pc"]], pc2=[float(x).hex() for x in r["pc2"]])
+                for r in recs]
+        if recs[0] != recs[1]:
+            raise SystemExit("%s: the reference's search differs with and without the search bracket" % name)
+        models[name] = recs[0]
+    g = SHAPES["synthetic_c2.json"]
+    d = vb.synth.make_pileup(g["markers"], g["depth"], g["num_pc"], alpha_true=g["alpha_true"], seed=g["seed"])
+    with vb.LikelihoodContext(d) as ctx:
+        r = binding.reference_optimiser_on_gpu(_abi.lib(), ctx._h, d.num_pc)
+    c2 = dict(run_record(r), input_sha256=sha(d.ud, d.means, d.read_off, d.bases, d.quals, d.alt_base))
+    return dict(_what="the reference's own AmoebaMinimizer (oracle/_ref) driving the product's gfx950 likelihood through "
+                      "the C-ABI (oracle/ref_adapter.cpp; with and without the vb2_ctx_search_begin/end bracket: the same "
+                      "run) on the six models of kat.json and on the synthetic_c2.json input: results, evaluation counts, "
+                      "trace digests; regenerate with tests/golden/make_fixtures.py --gpu-reference",
+                models=models, synthetic_c2=c2)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--check", action="store_true")
+    ap.add_argument("--gpu-reference", metavar="OUT",
+                    help="on a gfx950 box with oracle/_ref: write only the reference-on-GPU runs, to OUT")
     args = ap.parse_args()
+    if args.gpu_reference:
+        json.dump(reference_on_gpu(), open(args.gpu_reference, "w"), indent=1)
+        print("wrote %s" % args.gpu_reference)
+        return
     bad = 0
     kat, got = kat_llk()
     for name, vals in got.items():
@@ -240,6 +324,16 @@ def main():
                           "tests/golden/make_fixtures.py from the oracle that tests/test_oracle_golden.py pins to "
                           "the reference's own fixtures. Hex-floats are the exact IEEE-754 doubles.")
         json.dump(kat, open(os.path.join(HERE, "kat.json"), "w"), indent=1)
+    runs = reference_runs()
+    path = os.path.join(HERE, "reference_runs.json")
+    if args.check:
+        if json.load(open(path)) != json.loads(json.dumps(runs)):
+            print("reference_runs.json differs from what the recipe produces now")
+            bad += 1
+    else:
+        json.dump(runs, open(path, "w"), indent=1)
+        print("wrote reference_runs.json (%d searches, %d plain functions, %d line searches)"
+              % (len(runs["amoeba_search"]), len(runs["amoeba_functions"]), len(runs["line_search"])))
     for fname, spec in SHAPES.items():
         fx = synthetic_fixture(spec)
         path = os.path.join(HERE, fname)

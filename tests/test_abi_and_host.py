@@ -190,40 +190,53 @@ def test_speculation_level_does_not_change_the_trajectory(golden_dir, level, kw,
         assert got["num_launch_point"] > got["num_eval"]
 
 
+def line_search_cases(golden_dir):
+    """(function, lo, hi, tol): plain test functions that take every branch of the bracket, and the real objective (the
+    LLK of the bundled input as a function of logit(alpha)).  The C library's functions (math), like the oracle's: the
+    abscissae do not depend on which vector code numpy picks on a machine."""
+    import math
+    flat, _, _ = refio.load_flat(os.path.join(golden_dir, HAPMAP), os.path.join(golden_dir, "expected/result.Pileup"), 2)
+    od = binding.OracleData(flat)
+    pc = [0.01, 0.01]
+
+    def neg_llk(x):
+        return -od.llk(pc, pc, 1.0 / (1.0 + math.exp(-x)), num_thread=1)
+
+    return [
+        (lambda x: (x - 2.0) ** 2 + 1.0, 0.0, 1.0, 1e-8),                  # downhill to the right
+        (lambda x: (x + 30.0) ** 2, 0.0, 1.0, 1e-10),                      # far: magnification limit
+        (lambda x: abs(x - 0.3) ** 1.5 + 0.1 * x, 5.0, 4.0, 1e-9),         # swapped ends, non-smooth
+        (lambda x: math.cosh(0.7 * x) + 0.05 * x ** 4 - x, -3.0, -2.9, 1e-12),
+        (lambda x: -math.exp(-(x - 1.0) ** 2 / 50.0), -40.0, -39.0, 1e-8),  # nearly flat start
+        (lambda x: float(math.floor(abs(x) * 3)), 2.2, 2.9, 1e-8),         # plateaus: the tie rules
+        (neg_llk, math.log(0.03 / 0.97), math.log(0.03 / 0.97) + 1.0, 1e-8),
+    ]
+
+
 def test_line_search_equals_the_references_scalar_minimizer(golden_dir):
     """csrc/line_search.cpp (bracket + Brent; the optimiser of the one-parameter models, SURVEY.md
-    8f row 4) against the reference's own compiled ScalarMinimizer (MathGold.cpp:27-195 in
-    oracle/_ref): the same abscissae evaluated in the same order, the same result, bit for bit --
-    on plain test functions that take every branch of the bracket, and on the real objective
-    (the LLK of the bundled input as a function of logit(alpha))."""
+    8f row 4) against the reference's own ScalarMinimizer (MathGold.cpp:27-195): the same abscissae
+    evaluated in the same order, the same result, bit for bit.  Against the reference's runs stored in
+    golden/reference_runs.json (sha256 of the abscissae), and against oracle/_ref live where it is built."""
     import ctypes as C
-    if binding.ref_lib() is None:
-        pytest.skip("oracle/_ref not built (reference tree absent)")
+    import hashlib
+    import json
     L = _abi.lib()
     FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_double)
     CM = C.CFUNCTYPE(None, C.c_void_p, C.c_double, C.c_double)
     L.vb2_debug_line_search.restype = C.c_int
     L.vb2_debug_line_search.argtypes = [FN, CM, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int,
                                         C.POINTER(C.c_double)]
-    flat, _, _ = refio.load_flat(os.path.join(golden_dir, HAPMAP), os.path.join(golden_dir, "expected/result.Pileup"), 2)
-    od = binding.OracleData(flat)
-    pc = [0.01, 0.01]
-
-    def neg_llk(x):
-        return -od.llk(pc, pc, 1.0 / (1.0 + np.exp(-x)), num_thread=1)
-
-    cases = [
-        (lambda x: (x - 2.0) ** 2 + 1.0, 0.0, 1.0, 1e-8),                  # downhill to the right
-        (lambda x: (x + 30.0) ** 2, 0.0, 1.0, 1e-10),                      # far: magnification limit
-        (lambda x: abs(x - 0.3) ** 1.5 + 0.1 * x, 5.0, 4.0, 1e-9),         # swapped ends, non-smooth
-        (lambda x: np.cosh(0.7 * x) + 0.05 * x ** 4 - x, -3.0, -2.9, 1e-12),
-        (lambda x: -np.exp(-(x - 1.0) ** 2 / 50.0), -40.0, -39.0, 1e-8),   # nearly flat start
-        (lambda x: float(np.floor(abs(x) * 3)), 2.2, 2.9, 1e-8),           # plateaus: the tie rules
-        (neg_llk, float(np.log(0.03 / 0.97)), float(np.log(0.03 / 0.97)) + 1.0, 1e-8),
-    ]
-    for fn, lo, hi, tol in cases:
-        ref_x = []
-        want = binding.reference_scalar_minimize(lambda x: (ref_x.append(x), fn(x))[1], lo, hi, tol)
+    digest = lambda xs: hashlib.sha256(np.array(xs, dtype=np.float64).tobytes()).hexdigest()   # noqa: E731
+    cases = line_search_cases(golden_dir)
+    stored = json.load(open(os.path.join(golden_dir, "reference_runs.json")))["line_search"]
+    assert len(stored) == len(cases)
+    for (fn, lo, hi, tol), rec in zip(cases, stored):
+        refs = [(rec["num_eval"], rec["x_sha256"], {key: float.fromhex(v) for key, v in rec["want"].items()})]
+        if binding.ref_lib() is not None:
+            ref_x = []
+            want = binding.reference_scalar_minimize(lambda x: (ref_x.append(x), fn(x))[1], lo, hi, tol)
+            refs.append((len(ref_x), digest(ref_x), want))
         for speculate in (0, 1):
             got_x, launched = [], []
             out = (C.c_double * 5)()
@@ -231,9 +244,10 @@ def test_line_search_equals_the_references_scalar_minimizer(golden_dir):
             c_cb = CM(lambda _u, x, y: got_x.append(x))
             rc = L.vb2_debug_line_search(f_cb, c_cb, None, lo, hi, tol, speculate, out)
             assert rc == 0
-            assert got_x == ref_x, (speculate, len(got_x), len(ref_x))
-            assert dict(zip(("min", "fmin", "a", "b", "c"), list(out))) == want
-            assert len(launched) == len(ref_x) + (1 if speculate else 0)   # the unused candidate for c
+            for n, x_sha, want in refs:
+                assert len(got_x) == n and digest(got_x) == x_sha, (speculate, len(got_x), n)
+                assert dict(zip(("min", "fmin", "a", "b", "c"), list(out))) == want
+                assert len(launched) == n + (1 if speculate else 0)   # the unused candidate for c
 
 
 def _capture_stderr(fn):

@@ -90,24 +90,47 @@ def test_golden_models(golden_dir, kat, model):
         assert est["num_eval"] == spec["num_eval"]
 
 
+@pytest.fixture(scope="module")
+def reference_on_gpu(golden_dir):
+    """The reference's AmoebaMinimizer driving this library's GPU likelihood through the C-ABI, recorded on a gfx950 box
+    with oracle/_ref (tests/golden/make_fixtures.py --gpu-reference): results, evaluation counts, trace digests."""
+    with open(os.path.join(golden_dir, "reference_on_gpu.json")) as fh:
+        return json.load(fh)
+
+
+def _trace_sha(tr):
+    import hashlib
+    h = hashlib.sha256()
+    for key in ("alpha", "pc1", "pc2", "llk"):
+        h.update(np.ascontiguousarray(tr[key], dtype=np.float64).tobytes())
+    return h.hexdigest()
+
+
 @pytest.mark.parametrize("model", ["result", "longread", "within", "within_fixpc", "fixalpha",
                                    "heter_fixpc"])
-def test_reference_optimiser_drives_the_gpu_through_the_c_abi(golden_dir, kat, model):
+def test_reference_optimiser_drives_the_gpu_through_the_c_abi(golden_dir, kat, model, reference_on_gpu):
     """INTEGRATION.md section A, executed: oracle/ref_adapter.cpp is the reference-side binding -- a
     subclass of the reference's VectorFunc whose ComputeMixLLKs is vb2_llk_eval_batch, installed in
     the reference's OWN AmoebaMinimizer (compiled in place from /root/reference into oracle/_ref),
     the search bracketed by vb2_ctx_search_begin/end.  With the reference's optimiser driving the
     GPU the six golden .Ancestry files come out byte for byte, and the evaluations are exactly those
-    of the library's own search (vb2_ctx_optimize_llk): same points, same values, same order."""
+    of the library's own search (vb2_ctx_optimize_llk): same points, same values, same order --
+    the run stored in golden/reference_on_gpu.json, and the live one where oracle/_ref is built."""
     from oracle import binding
-    if binding.ref_lib() is None:
-        pytest.skip("oracle/_ref/libvb2ref.so not built (needs the reference tree once)")
     spec = kat["models"][model]
     d = _golden(golden_dir, spec["pileup"])
     with vb.LikelihoodContext(d) as ctx:
         mine = ctx.optimize(trace_capacity=8192, **spec["args"])
-        for bracket in (True, False):
-            ref = binding.reference_optimiser_on_gpu(_abi.lib(), ctx._h, 2, bracket=bracket, **spec["args"])
+        rec = reference_on_gpu["models"][model]
+        stored = dict({key: float.fromhex(rec[key]) for key in ("alpha", "llk1", "llk0")},
+                      pc=np.array([float.fromhex(x) for x in rec["pc"]]), pc2=np.array([float.fromhex(x) for x in rec["pc2"]]),
+                      num_eval=rec["num_eval"], trace_count=rec["trace_count"], trace_sha256=rec["trace_sha256"])
+        runs = [("stored", stored)]
+        if binding.ref_lib() is not None:
+            for bracket in (True, False):
+                ref = binding.reference_optimiser_on_gpu(_abi.lib(), ctx._h, 2, bracket=bracket, **spec["args"])
+                runs.append((bracket, dict(ref, trace_sha256=_trace_sha(ref["trace"]))))
+        for bracket, ref in runs:
             assert abs(ref["alpha"] - spec["alpha"]) <= 1e-9
             with open(os.path.join(golden_dir, spec["ancestry"])) as fh:
                 assert ancestry_text(ref["pc"], ref["pc2"]) == fh.read()
@@ -117,23 +140,30 @@ def test_reference_optimiser_drives_the_gpu_through_the_c_abi(golden_dir, kat, m
                 assert ref[key] == mine[key], (key, bracket)
             assert np.array_equal(ref["pc"], mine["pc"]) and np.array_equal(ref["pc2"], mine["pc2"])
             assert ref["trace_count"] == mine["trace_count"]
-            for key in ("llk", "alpha", "pc1", "pc2"):
-                assert np.array_equal(ref["trace"][key], mine["trace"][key]), (key, bracket)
+            assert ref["trace_sha256"] == _trace_sha(mine["trace"]), bracket
 
 
-def test_reference_optimiser_on_gpu_at_c2_size(c2):
+def test_reference_optimiser_on_gpu_at_c2_size(c2, reference_on_gpu):
     """Same at 10 000 markers x depth 30 (BASELINE.json configs[1]): the reference's AmoebaMinimizer
-    over the C-ABI and the library's search agree evaluation by evaluation."""
+    over the C-ABI and the library's search agree evaluation by evaluation (stored run; live where built)."""
+    import hashlib
     from oracle import binding
-    if binding.ref_lib() is None:
-        pytest.skip("oracle/_ref/libvb2ref.so not built (needs the reference tree once)")
+    from conftest import fixture_input_must_match
     d, od = c2
+    rec = reference_on_gpu["synthetic_c2"]
+    h = hashlib.sha256()
+    for a in (d.ud, d.means, d.read_off, d.bases, d.quals, d.alt_base):
+        h.update(np.ascontiguousarray(a).tobytes())
+    fixture_input_must_match(h.hexdigest(), rec["input_sha256"], "reference_on_gpu.json synthetic_c2")
     with vb.LikelihoodContext(d) as ctx:
         mine = ctx.optimize(trace_capacity=8192)
-        ref = binding.reference_optimiser_on_gpu(_abi.lib(), ctx._h, d.num_pc)
-    assert ref["alpha"] == mine["alpha"] and ref["llk1"] == mine["llk1"] and ref["num_eval"] == mine["num_eval"]
-    assert np.array_equal(ref["trace"]["llk"], mine["trace"]["llk"])
-    assert abs(ref["alpha"] - od.optimize()["alpha"]) <= 1e-9
+        if binding.ref_lib() is not None:
+            ref = binding.reference_optimiser_on_gpu(_abi.lib(), ctx._h, d.num_pc)
+            assert ref["alpha"] == mine["alpha"] and ref["llk1"] == mine["llk1"] and ref["num_eval"] == mine["num_eval"]
+            assert np.array_equal(ref["trace"]["llk"], mine["trace"]["llk"])
+    assert mine["alpha"] == float.fromhex(rec["alpha"]) and mine["llk1"] == float.fromhex(rec["llk1"])
+    assert mine["num_eval"] == rec["num_eval"] and _trace_sha(mine["trace"]) == rec["trace_sha256"]
+    assert abs(mine["alpha"] - od.optimize()["alpha"]) <= 1e-9
 
 
 @pytest.mark.parametrize("case", [
@@ -1153,7 +1183,7 @@ def test_bench_two_ranks_sharing_the_gpu_plumbing():
     import sys
     env = dict(os.environ, VB2_BENCH_SHARE_GPU="1")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "50", "--warmup", "10",
-                        "--markers", "20000", "--no-cpu-baseline", "--no-optimize", "--no-extras"],
+                        "--markers", "20000", "--no-cpu-baseline", "--no-optimize", "--no-extras", "--full"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -1170,6 +1200,38 @@ def test_bench_two_ranks_sharing_the_gpu_plumbing():
     assert rf["kernel_src_hash"] == _abi.kernel_source_hash()
     for term in ("fp64", "hbm"):
         assert rf["terms"][term] is None or rf["terms"][term]["t_us"] > 0       # (20 000 markers: no committed PMC pass of this shape)
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_ones_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the headline line alone (none of the --full
+    legs), K timed steps, ms_per_step the wall-clock of one; DIR/llk.npy = the 48 LLKs of the last timed step, those of
+    the oracle at the seeded points, and bit for bit the same from a second run."""
+    import sys
+    got = []
+    for run in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "5",
+                            "--markers", "20000", "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        r = json.loads(lines[0])
+        assert r["metric"] == "llk_evals_per_sec" and r["unit"] == "evals/s" and r["higher_is_better"] is True
+        assert r["dtype"] == "f64" and r["steps"] == 30 and r["warmup"] == 5 and r["ms_per_step"] > 0
+        assert abs(r["value"] * r["ms_per_step"] / 1e3 - 48) < 1e-6                # evals per step / seconds per step
+        for leg in ("roofline", "marker_sharded", "search_point", "optimize", "cohort", "parity_probe_max_rel_err",
+                    "cpu_baseline"):
+            assert leg not in r, leg
+        llk = np.load(str(tmp_path / run / "llk.npy"))
+        assert llk.dtype == np.float64 and llk.shape == (48,)
+        got.append(llk)
+    assert np.array_equal(got[0], got[1])
+    d = vb.synth.make_pileup(20000, 30.0, 4, alpha_true=0.05, seed=2, q_lo=20, q_hi=40)      # bench.py's inputs
+    rng = np.random.default_rng(123)
+    pts = np.concatenate([rng.normal(0, 0.03, size=(48, 8)), rng.uniform(0.01, 0.3, size=(48, 1))], axis=1)
+    od = oracle_data(d)
+    want = [od.llk(pts[i, :4], pts[i, 4:8], pts[i, 8], num_thread=8) for i in range(48)]
+    assert rel_err(got[0], want) <= LLK_RTOL
 
 
 def test_shard_group_two_devices_rccl_all_reduce(c2):

@@ -4,11 +4,12 @@
   bit for bit;
 * the reference's own CTest fixtures: six expected .Ancestry files and two
   .selfSM files (CMakeLists.txt:86-147), byte for byte / field for field;
-* the reference's own AmoebaMinimizer (oracle/_ref, compiled in place from
-  /root/reference/MathGenMin.cpp): identical trajectories.
+* the reference's own AmoebaMinimizer (MathGenMin.cpp): identical trajectories -- against its runs
+  stored in golden/reference_runs.json, and against oracle/_ref (compiled in place) where built.
 
 CPU only.
 """
+import hashlib
 import json
 import os
 
@@ -83,31 +84,44 @@ def test_golden_ancestry_and_selfsm(golden_dir, kat, model):
         assert row[8] == cxx_default(-res["llk0"])
 
 
-def _need_ref():
-    if binding.ref_lib() is None:
-        pytest.skip("oracle/_ref not built (no /root/reference and no prebuilt library)")
+@pytest.fixture(scope="module")
+def reference_runs(golden_dir):
+    """The reference's own minimisers on these cases (tests/golden/make_fixtures.py): results, evaluation counts and
+    sha256 digests of the evaluations -- what the tests hold the restatement to without oracle/_ref."""
+    with open(os.path.join(golden_dir, "reference_runs.json")) as fh:
+        return json.load(fh)
 
 
-@pytest.mark.parametrize("args", [{}, {"within_ancestry": True}, {"fix_alpha": 0.1},
-                                  {"fix_pc": [0.034756, 0.0193]}])
-def test_search_matches_reference_amoeba(golden_dir, args):
+def _sha(*arrays):
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a, dtype=np.float64).tobytes())
+    return h.hexdigest()
+
+
+SEARCH_ARGS = [{}, {"within_ancestry": True}, {"fix_alpha": 0.1}, {"fix_pc": [0.034756, 0.0193]}]
+
+
+@pytest.mark.parametrize("args", SEARCH_ARGS)
+def test_search_matches_reference_amoeba(golden_dir, reference_runs, args):
     """Same objective, reference's AmoebaMinimizer vs the restatement: every
-    evaluation point and value identical, bit for bit."""
-    _need_ref()
+    evaluation point and value identical, bit for bit (the stored run; the live one too where oracle/_ref is built)."""
     od, _, _ = _data(golden_dir, "test.LongRead.pileup")
     a = od.optimize(minimizer="oracle", trace_capacity=4096, **args)
-    b = od.optimize(minimizer="reference", trace_capacity=4096, **args)
+    b = reference_runs["amoeba_search"][json.dumps(args, sort_keys=True)]
     assert a["num_eval"] == b["num_eval"] and a["trace_count"] == b["trace_count"]
-    for key in ("alpha", "pc1", "pc2", "llk"):
-        assert np.array_equal(a["trace"][key], b["trace"][key]), key
-    assert a["alpha"] == b["alpha"] and a["llk1"] == b["llk1"] and a["llk0"] == b["llk0"]
+    tr = a["trace"]
+    assert _sha(tr["alpha"], tr["pc1"], tr["pc2"], tr["llk"]) == b["trace_sha256"]
+    assert all(a[key] == float.fromhex(b[key]) for key in ("alpha", "llk1", "llk0"))
+    if binding.ref_lib() is not None:
+        b = od.optimize(minimizer="reference", trace_capacity=4096, **args)
+        assert a["num_eval"] == b["num_eval"] and a["trace_count"] == b["trace_count"]
+        for key in ("alpha", "pc1", "pc2", "llk"):
+            assert np.array_equal(a["trace"][key], b["trace"][key]), key
+        assert a["alpha"] == b["alpha"] and a["llk1"] == b["llk1"] and a["llk0"] == b["llk0"]
 
 
-def test_amoeba_generic_functions_match_reference():
-    """Nelder-Mead restatement vs reference on plain test functions, including
-    one that exhausts cycleMax (returns DBL_MAX and leaves the point alone)."""
-    _need_ref()
-
+def amoeba_cases():
     def rosen(v):
         return float(100.0 * (v[1] - v[0] ** 2) ** 2 + (1 - v[0]) ** 2)
 
@@ -117,15 +131,28 @@ def test_amoeba_generic_functions_match_reference():
     def plateau(v):   # exercises the tie rules (<= / >) and the shrink step
         return float(np.floor(abs(v[0]) * 4) + np.floor(abs(v[1]) * 4))
 
-    for fn, start, tol in [(rosen, [-1.2, 1.0], 1e-10), (quad5, [0.0] * 5, 1e-12),
-                           (plateau, [2.3, -1.7], 1e-8), (lambda v: float(v[0] ** 2), [3.0], 1e-14)]:
-        ev_a, ev_b = [], []
+    return [(rosen, [-1.2, 1.0], 1e-10), (quad5, [0.0] * 5, 1e-12),
+            (plateau, [2.3, -1.7], 1e-8), (lambda v: float(v[0] ** 2), [3.0], 1e-14)]
+
+
+def test_amoeba_generic_functions_match_reference(reference_runs):
+    """Nelder-Mead restatement vs reference on plain test functions, including
+    one that exhausts cycleMax (returns DBL_MAX and leaves the point alone)."""
+    stored = reference_runs["amoeba_functions"]
+    assert len(stored) == len(amoeba_cases())
+    for (fn, start, tol), rec in zip(amoeba_cases(), stored):
+        ev_a = []
         ra, pa = binding.amoeba(lambda v: (ev_a.append(v.copy()), fn(v))[1], start, tol, "oracle")
-        rb, pb = binding.amoeba(lambda v: (ev_b.append(v.copy()), fn(v))[1], start, tol, "reference")
-        assert ra == rb
-        assert np.array_equal(pa, pb)
-        assert len(ev_a) == len(ev_b)
-        assert all(np.array_equal(x, y) for x, y in zip(ev_a, ev_b))
+        assert ra == float.fromhex(rec["ret"])
+        assert np.array_equal(pa, [float.fromhex(x) for x in rec["point"]])
+        assert len(ev_a) == rec["num_eval"] and _sha(np.array(ev_a)) == rec["points_sha256"]
+        if binding.ref_lib() is not None:
+            ev_b = []
+            rb, pb = binding.amoeba(lambda v: (ev_b.append(v.copy()), fn(v))[1], start, tol, "reference")
+            assert ra == rb
+            assert np.array_equal(pa, pb)
+            assert len(ev_a) == len(ev_b)
+            assert all(np.array_equal(x, y) for x, y in zip(ev_a, ev_b))
 
 
 def test_sanity_filter_and_threads(golden_dir):

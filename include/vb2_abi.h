@@ -411,6 +411,73 @@ const vb2_input *vb2_flat_input(const vb2_flat *f);
 int vb2_flat_stats(const vb2_flat *f, vb2_run_result *out);
 void vb2_flat_free(vb2_flat *f);
 
+/* ------------------------------------------------------------------------- *
+ * 4. Reference-panel builder: --RefVCF (main.cpp:233-257, SVDcalculator::
+ *    ProcessRefVCF, SVDcalculator.cpp:363-400).  The kept markers' genotypes
+ *    (0/1/2, -1 = missing or no likelihood below 255) become an int8 slab on the
+ *    device; S = G^T G is exact (int8 MFMA, int32); mu, the centred Gram, its
+ *    eigenbasis (rocSOLVER dsyevd, bound at run time) and UD = (G - mu 1^T) V are
+ *    FP64.  Sign convention: each column of V is flipped so that its entry of
+ *    largest magnitude is positive (the lowest index on ties); UD follows.
+ * ------------------------------------------------------------------------- */
+typedef struct vb2_panel_args {
+    const char *vcf_path;      /* --RefVCF (vcf or vcf.gz); files go to <vcf_path>.UD/.mu/.bed/.V  */
+    const char *include_chr;   /* --IncludeChr a,b,...; NULL = the 44 autosome names (main.cpp:69-73);
+                                * "" = no chromosome filter                                      */
+    int32_t num_svd_pcs;       /* --NumSVDPCs (10); <= 0 = all min(M, N)                          */
+    int32_t skip_min_sample_count_check; /* --SkipMinSampleCountCheck                            */
+    int32_t check_minimums;    /* vb2_panel_build_genotypes only: enforce >= 5000 markers and
+                                * >= 1000 samples (unless skipped); the VCF entry always does   */
+    int32_t num_thread;        /* --NumThread: VCF parser threads; 0 = 4                          */
+    int32_t device;            /* HIP device ordinal, -1 = current                                */
+    int32_t notices;           /* print the reference's NOTICE / WARNING lines to stderr          */
+    int32_t chunk_markers;     /* markers per device chunk (a multiple of 128); 0 = 16384         */
+    int32_t reserved;
+} vb2_panel_args;
+
+/* The kept markers of a VCF, read on the host only (SVDcalculator::ReadVcf).  Library-owned. */
+typedef struct vb2_vcf vb2_vcf;
+typedef struct vb2_vcf_view {
+    int64_t num_marker;
+    int32_t num_sample;
+    int32_t num_chr;
+    const int8_t *genotypes;       /* marker-major [num_marker][num_sample]                     */
+    const int32_t *pos;            /* [num_marker] 1-based                                        */
+    const int32_t *chr_index;      /* [num_marker] into chr_names                                 */
+    const char *ref;               /* [num_marker] one base each                                  */
+    const char *alt;               /* [num_marker]                                                */
+    const char *const *chr_names;  /* [num_chr]                                                   */
+    const char *const *sample_ids; /* [num_sample]                                                */
+} vb2_vcf_view;
+int vb2_vcf_read(const vb2_panel_args *args, vb2_vcf **out);
+int vb2_vcf_get_view(const vb2_vcf *v, vb2_vcf_view *out);
+void vb2_vcf_free(vb2_vcf *v);
+
+typedef struct vb2_panel vb2_panel;
+typedef struct vb2_panel_view {
+    int64_t num_marker;            /* M                                                           */
+    int32_t num_sample;            /* N                                                           */
+    int32_t num_pc;                /* k: columns of ud and v                                      */
+    const double *ud;              /* [M][k]                                                      */
+    const double *v;               /* [N][k]                                                      */
+    const double *mu;              /* [M] binary32 means, widened                                 */
+    const double *sigma;           /* [N] descending: sqrt(max(lambda, 0)) of the centred Gram    */
+    const int32_t *gram;           /* [N][N] S = G^T G of the raw genotypes                       */
+    const int32_t *row_sum;        /* [M] sum_j g_mj                                              */
+    /* wall-clock seconds: parse (reading, with the device work it overlaps), upload, gram,
+     * centring, eigensolve, projection, write; device stages are event-timed */
+    double seconds[7];
+    double seconds_total;
+} vb2_panel_view;
+int vb2_panel_build(const vb2_panel_args *args, vb2_panel **out);
+int vb2_panel_build_genotypes(const vb2_panel_args *args, const int8_t *genotypes /* [M][N] marker-major */,
+                              int64_t num_marker, int32_t num_sample, vb2_panel **out);
+int vb2_panel_get_view(const vb2_panel *p, vb2_panel_view *out);
+/* <prefix>.UD, .mu, .bed, .V in the reference's format (WriteSVD, SVDcalculator.cpp:471-513);
+ * a panel built from genotypes has no marker names and is VB2_ERR_INVALID here. */
+int vb2_panel_write(vb2_panel *p, const char *prefix);
+void vb2_panel_destroy(vb2_panel *p);
+
 const char *vb2_last_error(void);
 int vb2_abi_version(void);
 /* Number of usable gfx950 devices (0 = none; compute calls will fail loudly). */

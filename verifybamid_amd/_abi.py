@@ -115,6 +115,30 @@ class ShardInfo(C.Structure):
     ]
 
 
+class PanelArgs(C.Structure):
+    _fields_ = [
+        ("vcf_path", C.c_char_p), ("include_chr", C.c_char_p), ("num_svd_pcs", C.c_int32),
+        ("skip_min_sample_count_check", C.c_int32), ("check_minimums", C.c_int32), ("num_thread", C.c_int32),
+        ("device", C.c_int32), ("notices", C.c_int32), ("chunk_markers", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class VcfView(C.Structure):
+    _fields_ = [
+        ("num_marker", C.c_int64), ("num_sample", C.c_int32), ("num_chr", C.c_int32),
+        ("genotypes", C.c_void_p), ("pos", C.c_void_p), ("chr_index", C.c_void_p), ("ref", C.c_void_p),
+        ("alt", C.c_void_p), ("chr_names", C.POINTER(C.c_char_p)), ("sample_ids", C.POINTER(C.c_char_p)),
+    ]
+
+
+class PanelView(C.Structure):
+    _fields_ = [
+        ("num_marker", C.c_int64), ("num_sample", C.c_int32), ("num_pc", C.c_int32),
+        ("ud", C.c_void_p), ("v", C.c_void_p), ("mu", C.c_void_p), ("sigma", C.c_void_p), ("gram", C.c_void_p),
+        ("row_sum", C.c_void_p), ("seconds", C.c_double * 7), ("seconds_total", C.c_double),
+    ]
+
+
 EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                       C.POINTER(C.c_double), C.POINTER(C.c_double))
 
@@ -127,6 +151,8 @@ SYMBOLS = [
     "vb2_batch_create", "vb2_batch_destroy", "vb2_batch_eval", "vb2_batch_optimize_llk",
     "vb2_shard_group_create", "vb2_rccl_unique_id", "vb2_shard_group_create_rank", "vb2_shard_group_eval",
     "vb2_shard_group_optimize_llk", "vb2_shard_group_info", "vb2_shard_group_destroy", "vb2_shard_range",
+    "vb2_vcf_read", "vb2_vcf_get_view", "vb2_vcf_free", "vb2_panel_build", "vb2_panel_build_genotypes",
+    "vb2_panel_get_view", "vb2_panel_write", "vb2_panel_destroy",
 ]
 
 _lib = None
@@ -195,6 +221,16 @@ def lib():
     L.vb2_shard_range.argtypes = [C.POINTER(Input), C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.vb2_shard_group_destroy.argtypes = [C.c_void_p]
     L.vb2_shard_group_destroy.restype = None
+    L.vb2_vcf_read.argtypes = [C.POINTER(PanelArgs), C.POINTER(C.c_void_p)]
+    L.vb2_vcf_get_view.argtypes = [C.c_void_p, C.POINTER(VcfView)]
+    L.vb2_vcf_free.argtypes = [C.c_void_p]
+    L.vb2_vcf_free.restype = None
+    L.vb2_panel_build.argtypes = [C.POINTER(PanelArgs), C.POINTER(C.c_void_p)]
+    L.vb2_panel_build_genotypes.argtypes = [C.POINTER(PanelArgs), C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]
+    L.vb2_panel_get_view.argtypes = [C.c_void_p, C.POINTER(PanelView)]
+    L.vb2_panel_write.argtypes = [C.c_void_p, C.c_char_p]
+    L.vb2_panel_destroy.argtypes = [C.c_void_p]
+    L.vb2_panel_destroy.restype = None
     L.vb2_debug_set_tunable.argtypes = [C.c_char_p, C.c_int]
     L.vb2_debug_get_tunable.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
     _lib = L

@@ -507,3 +507,113 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
                  seconds_load=res[s].seconds_load, seconds_optimize=res[s].seconds_optimize)
         out.append(d)
     return out
+
+
+# ---- reference-panel builder (--RefVCF): include/vb2_abi.h section 4 ----
+
+PANEL_STAGES = ("parse", "upload", "gram", "centre", "eigensolve", "project", "write")
+
+
+def _panel_args(vcf_path=None, num_svd_pcs=10, include_chr=None, skip_min_sample_count_check=False,
+                check_minimums=False, num_thread=0, device=-1, notices=False, chunk_markers=0):
+    a = _abi.PanelArgs()
+    keep = []
+    if vcf_path is not None:
+        keep.append(str(vcf_path).encode())
+        a.vcf_path = keep[-1]
+    if include_chr is not None:   # a list of names or one comma-separated string; [] / "" = no chromosome filter
+        s = include_chr if isinstance(include_chr, str) else ",".join(include_chr)
+        keep.append(s.encode())
+        a.include_chr = keep[-1]
+    a.num_svd_pcs = int(num_svd_pcs)
+    a.skip_min_sample_count_check = int(bool(skip_min_sample_count_check))
+    a.check_minimums = int(bool(check_minimums))
+    a.num_thread = int(num_thread)
+    a.device = int(device)
+    a.notices = int(bool(notices))
+    a.chunk_markers = int(chunk_markers)
+    return a, keep
+
+
+def read_vcf(vcf_path, include_chr=None, num_thread=0, notices=False):
+    """SVDcalculator::ReadVcf on the host (no device): the kept markers and their genotypes.
+
+    include_chr=None is the reference's default (the 44 autosome names), [] keeps every chromosome.
+    Returns a dict: genotypes (int8, markers x samples, -1 = missing), chr (list of str), pos (int32),
+    ref, alt (lists of one-character str), samples (list of str)."""
+    a, keep = _panel_args(vcf_path, include_chr=include_chr, num_thread=num_thread, notices=notices)
+    L = _abi.lib()
+    h = C.c_void_p()
+    _abi.check(L.vb2_vcf_read(C.byref(a), C.byref(h)), "vb2_vcf_read")
+    try:
+        v = _abi.VcfView()
+        _abi.check(L.vb2_vcf_get_view(h, C.byref(v)), "vb2_vcf_get_view")
+        M, N = int(v.num_marker), int(v.num_sample)
+
+        def arr(ptr, dtype, shape):
+            if M == 0 or not ptr:
+                return np.zeros(shape, dtype=dtype)
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), shape).copy()
+        geno = arr(v.genotypes, np.int8, (M, N))
+        pos = arr(v.pos, np.int32, (M,))
+        ci = arr(v.chr_index, np.int32, (M,))
+        ref = C.string_at(v.ref, M).decode("latin-1") if M else ""
+        alt = C.string_at(v.alt, M).decode("latin-1") if M else ""
+        names = [v.chr_names[i].decode() for i in range(v.num_chr)]
+        samples = [v.sample_ids[i].decode() for i in range(N)]
+    finally:
+        L.vb2_vcf_free(h)
+    return dict(genotypes=geno, chr=[names[i] for i in ci], pos=pos, ref=list(ref), alt=list(alt), samples=samples)
+
+
+def _panel_result(h):
+    L = _abi.lib()
+    v = _abi.PanelView()
+    _abi.check(L.vb2_panel_get_view(h, C.byref(v)), "vb2_panel_get_view")
+    M, N, k = int(v.num_marker), int(v.num_sample), int(v.num_pc)
+
+    def arr(ptr, ctype, shape):
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape).copy()
+    return dict(ud=arr(v.ud, C.c_double, (M, k)), v=arr(v.v, C.c_double, (N, k)), mu=arr(v.mu, C.c_double, (M,)),
+                sigma=arr(v.sigma, C.c_double, (N,)), gram=arr(v.gram, C.c_int32, (N, N)),
+                row_sum=arr(v.row_sum, C.c_int32, (M,)), num_pc=k,
+                seconds=dict(zip(PANEL_STAGES, list(v.seconds))), seconds_total=v.seconds_total)
+
+
+def build_panel(vcf_path, output_prefix=None, num_svd_pcs=10, include_chr=None, skip_min_sample_count_check=False,
+                device=0, num_thread=0, notices=False, chunk_markers=0):
+    """--RefVCF: read the VCF, decompose on the GPU, and (output_prefix given) write <prefix>.UD/.mu/.bed/.V in the
+    reference's format -- the command line writes them at prefix = vcf_path.  Returns the arrays of _panel_result:
+    ud (M x k), v (N x k), mu, sigma (full spectrum), gram (the exact int32 G^T G), row_sum, per-stage seconds."""
+    a, keep = _panel_args(vcf_path, num_svd_pcs, include_chr, skip_min_sample_count_check, True, num_thread, device,
+                          notices, chunk_markers)
+    L = _abi.lib()
+    h = C.c_void_p()
+    _abi.check(L.vb2_panel_build(C.byref(a), C.byref(h)), "vb2_panel_build")
+    try:
+        if output_prefix is not None:
+            _abi.check(L.vb2_panel_write(h, str(output_prefix).encode()), "vb2_panel_write")
+        out = _panel_result(h)
+    finally:
+        L.vb2_panel_destroy(h)
+    return out
+
+
+def build_panel_from_genotypes(geno, num_svd_pcs=10, check_minimums=False, skip_min_sample_count_check=False,
+                               device=0, notices=False, chunk_markers=0):
+    """The same decomposition from an in-memory markers x samples matrix of -1/0/1/2 (PLINK-style sources, tests).
+    The reference's minimums (5000 markers, 1000 samples) apply only with check_minimums=True."""
+    g = np.ascontiguousarray(geno, dtype=np.int8)
+    if g.ndim != 2:
+        raise ValueError("geno must be a markers x samples matrix")
+    a, keep = _panel_args(None, num_svd_pcs, None, skip_min_sample_count_check, check_minimums, 0, device, notices,
+                          chunk_markers)
+    L = _abi.lib()
+    h = C.c_void_p()
+    _abi.check(L.vb2_panel_build_genotypes(C.byref(a), g.ctypes.data, g.shape[0], g.shape[1], C.byref(h)),
+               "vb2_panel_build_genotypes")
+    try:
+        out = _panel_result(h)
+    finally:
+        L.vb2_panel_destroy(h)
+    return out

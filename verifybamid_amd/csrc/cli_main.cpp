@@ -10,6 +10,9 @@
 //
 // --BamFile needs a build with htslib (CMake finds it: bam_flatten.cpp); a build without it --
 // this image's -- reports that and suggests the reference's own --OutputPileup file with --PileupFile.
+// --RefVCF V [--NumSVDPCs k] [--SkipMinSampleCountCheck] [--IncludeChr a,b,..] [--GramSVD] builds a reference panel
+// (main.cpp:233-257): V.UD, V.mu, V.bed, V.V, decomposed on the GPU (vb2_panel_build), and returns before --Reference
+// is looked at.  --NumThread sizes the VCF parser pool there.
 // Extensions: --Device n selects the GPU; --Devices a,b,.. uses several -- one sample's markers
 // are sharded over them (partial log-likelihoods met in one RCCL all-reduce), a --PileupList
 // cohort is dealt to them group by group; --PileupList F runs many samples against one panel.
@@ -51,7 +54,14 @@ int main(int argc, char** argv)
     // defaults: main.cpp:58-79
     std::string UDPath("Empty"), MeanPath("Empty"), BedPath("Empty"), BamFile("Empty"),
         RefPath("Empty"), outputPrefix("result"), PileupFile("Empty"), SVDPrefix("Empty"),
-        knownAF("Empty"), fixPC("Empty"), PileupList("Empty"), Devices("Empty");
+        knownAF("Empty"), fixPC("Empty"), PileupList("Empty"), Devices("Empty"), RefVCF("Empty");
+    // --RefVCF mode (main.cpp:66-73): the default chromosome set is the 44 human autosome names
+    int numSVDPCs = 10;
+    bool skipMinSampleCountCheck = false, gramSVD = false;
+    std::string includeChrStr("1,2,3,4,5,6,7,8,9,10,11,12,13,14,15,16,17,18,19,20,21,22,"
+                              "chr1,chr2,chr3,chr4,chr5,chr6,chr7,chr8,chr9,chr10,"
+                              "chr11,chr12,chr13,chr14,chr15,chr16,chr17,chr18,chr19,"
+                              "chr20,chr21,chr22");
     double fixAlpha = -1., epsilon = 1e-8;
     bool withinAncestry = false, outputPileup = false, verbose = false, disableSanityCheck = false;
     int seed = 12345, nPC = 2, nthread = 4, device = -1, numStart = 1;
@@ -88,6 +98,11 @@ int main(int argc, char** argv)
         {"no-orphans", {Flag::kBool, &noOrphans, false}},
         {"incl-flags", {Flag::kInt, &inclFlags, false}},
         {"excl-flags", {Flag::kInt, &exclFlags, false}},
+        {"RefVCF", {Flag::kString, &RefVCF, false}},
+        {"NumSVDPCs", {Flag::kInt, &numSVDPCs, false}},
+        {"SkipMinSampleCountCheck", {Flag::kBool, &skipMinSampleCountCheck, false}},
+        {"IncludeChr", {Flag::kString, &includeChrStr, false}},
+        {"GramSVD", {Flag::kBool, &gramSVD, false}},
         {"Device", {Flag::kInt, &device, false}},
         {"Devices", {Flag::kString, &Devices, false}},
         // not in the reference: a cohort against one panel.  File of lines "<pileup>\t<output prefix>";
@@ -131,7 +146,35 @@ int main(int argc, char** argv)
         else *static_cast<std::string*>(f.dst) = v;
     }
     // --Seed: parsed and never used by the reference (main.cpp:137,286); here it seeds --NumStart's starting points
-    (void)nthread;  // the likelihood runs on the GPU; kept for command-line compatibility
+    // --NumThread: the likelihood runs on the GPU; the VCF parser pool of --RefVCF and the reader threads of --PileupList use it
+
+    if (RefVCF != "Empty") {                                            // main.cpp:233-257: SVD on the fly
+        std::fprintf(stderr, "NOTICE - Specified --RefVCF reference panel VCF file, doing SVD on the fly...\n");
+        std::fprintf(stderr, "NOTICE - This procedure will generate SVD matrices as [RefVCF path].UD and [RefVCF path].mu\n");
+        std::fprintf(stderr, "NOTICE - You may specify --SVDPrefix [RefVCF path](or --UDPath [RefVCF path].UD and "
+                             "--MeanPath [RefVCF path].mu) in future use\n");
+        if (gramSVD)
+            std::fprintf(stderr, "NOTICE - --GramSVD has no effect here: the one decomposition path is the exact Gram "
+                                 "matrix on the GPU with an FP64 eigensolver\n");
+        vb2_panel_args pa;
+        std::memset(&pa, 0, sizeof(pa));
+        pa.vcf_path = RefVCF.c_str();
+        pa.include_chr = includeChrStr.c_str();
+        pa.num_svd_pcs = numSVDPCs;
+        pa.skip_min_sample_count_check = skipMinSampleCountCheck ? 1 : 0;
+        pa.num_thread = nthread;
+        pa.device = device;
+        pa.notices = 1;
+        vb2_panel* panel = nullptr;
+        int rcp = vb2_panel_build(&pa, &panel);
+        if (rcp == VB2_OK) rcp = vb2_panel_write(panel, RefVCF.c_str());
+        vb2_panel_destroy(panel);
+        if (rcp != VB2_OK) fatal(vb2_last_error());
+        std::fprintf(stderr, "NOTICE - SVD output files written: %s.UD, %s.mu, %s.bed, %s.V\n", RefVCF.c_str(),
+                     RefVCF.c_str(), RefVCF.c_str(), RefVCF.c_str());
+        std::fprintf(stderr, "NOTICE - Success!\n");
+        return 0;
+    }
 
     // main.cpp:214-232
     if (SVDPrefix == "Empty") {

@@ -115,6 +115,11 @@ def reads_on_panel(means, ref_char, alt_char, mean_depth=30.0, alpha_true=0.05, 
     af = np.clip(mu / 2.0, 0.00005, 0.99995)
     g2 = rng.binomial(2, af)
     g1 = rng.binomial(2, af)
+    return _draw_reads(rng, g1, g2, ref_i, alt_i, mean_depth, alpha_true, q_lo, q_hi)
+
+
+def _draw_reads(rng, g1, g2, ref_i, alt_i, mean_depth, alpha_true, q_lo, q_hi):
+    M = g2.shape[0]
     depth = rng.poisson(mean_depth, size=M).astype(np.int64)
     read_off = np.zeros(M + 1, dtype=np.int64)
     np.cumsum(depth, out=read_off[1:])
@@ -130,6 +135,100 @@ def reads_on_panel(means, ref_char, alt_char, mean_depth=30.0, alpha_true=0.05, 
     ch = np.where(fwd, _BASES[obs_base], _LOWER[obs_base])
     ch = np.where(obs_base == ref_i[mk], np.where(fwd, ord("."), ord(",")), ch).astype(np.uint8)
     return read_off, ch, (q + 33).astype(np.uint8)
+
+
+def reads_from_genotypes(g_intended, g_contaminant, ref_char, alt_char, mean_depth=30.0, alpha_true=0.05, seed=1,
+                         q_lo=20, q_hi=40):
+    """reads_on_panel with EXPLICIT genotypes (0/1/2 per marker) for the intended sample and the contaminant, e.g.
+    individuals drawn from the populations of write_structured_vcf."""
+    rng = np.random.default_rng(seed)
+    code = {ord("A"): 0, ord("C"): 1, ord("G"): 2, ord("T"): 3}
+    ref_i = np.array([code.get(int(c), 0) for c in np.asarray(ref_char, dtype=np.uint8)])
+    alt_i = np.array([code.get(int(c), 1) for c in np.asarray(alt_char, dtype=np.uint8)])
+    return _draw_reads(rng, np.asarray(g_contaminant), np.asarray(g_intended), ref_i, alt_i, mean_depth, alpha_true,
+                       q_lo, q_hi)
+
+
+def write_structured_vcf(path, num_marker, num_sample, num_pop=3, fst=0.1, missing=0.02, seed=1, formats="mixed",
+                         skipped_every=0, chroms=("1", "2", "3")):
+    """A seeded reference-panel VCF with population structure (the Balding-Nichols model): ancestral allele
+    frequencies p ~ U(0.05, 0.95), population frequencies ~ Beta(p (1 - F) / F, (1 - p)(1 - F) / F), samples dealt to
+    the populations in turn, genotypes ~ Binom(2, p_pop).  formats="mixed" draws each marker's FORMAT from GT, PL, GL
+    and GT:PL (PL/GL: 0 at the true genotype, 10-99 elsewhere); "GT" writes hard calls only.  A fraction `missing` of
+    the values is "." (or "./." in GT).  skipped_every=k adds, after every k-th marker, a row the reader must skip
+    (FILTER q10, a second ALT, an indel, chromosome X, in turn).  Written gzip'd when path ends in .gz.
+
+    Returns dict(pop (population of each sample), freqs (num_pop x num_marker), ref, alt (uint8 per kept marker),
+    chr, pos (per kept marker))."""
+    import gzip
+    rng = np.random.default_rng(seed)
+    M, N = int(num_marker), int(num_sample)
+    p = rng.uniform(0.05, 0.95, size=M)
+    a = p * (1 - fst) / fst
+    b = (1 - p) * (1 - fst) / fst
+    freqs = np.clip(rng.beta(a[None, :].repeat(num_pop, 0), b[None, :].repeat(num_pop, 0)), 0.001, 0.999)
+    pop = np.arange(N) % num_pop
+    G = rng.binomial(2, freqs[pop].T)                       # M x N
+    miss = rng.random((M, N)) < missing
+    bases = np.frombuffer(b"ACGT", dtype=np.uint8)
+    ref = bases[rng.integers(0, 4, size=M)]
+    alt = bases[(np.searchsorted(bases, ref) + rng.integers(1, 4, size=M)) % 4]
+    other = rng.integers(10, 100, size=(M, N, 3))
+    fmt_names = ("GT", "PL", "GL", "GT:PL") if formats == "mixed" else (formats,)
+    fmt_pick = rng.integers(0, len(fmt_names), size=M)
+    gt_txt = np.array(["0/0", "0/1", "1/1"])
+    per_chr = (M + len(chroms) - 1) // len(chroms)
+    chr_of = [chroms[min(i // per_chr, len(chroms) - 1)] for i in range(M)]
+    pos_of = np.zeros(M, dtype=np.int64)
+    def opener(p, mode):
+        return gzip.open(p, mode, compresslevel=1) if str(p).endswith(".gz") else open(p, mode)
+    with opener(path, "wt") as f:
+        f.write("##fileformat=VCFv4.1\n")
+        f.write("##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n")
+        f.write("##FORMAT=<ID=PL,Number=G,Type=Integer,Description=\"Phred-scaled genotype likelihoods\">\n")
+        f.write("##FORMAT=<ID=GL,Number=G,Type=Float,Description=\"Log10-scaled genotype likelihoods\">\n")
+        f.write("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" +
+                "\t".join("S%05d" % j for j in range(N)) + "\n")
+        pos = 1000
+        prev_chr = None
+        nskip = 0
+        for i in range(M):
+            if chr_of[i] != prev_chr:
+                pos, prev_chr = 1000, chr_of[i]
+            pos += 10
+            pos_of[i] = pos
+            fmt = fmt_names[fmt_pick[i]]
+            g = G[i]
+            ph = other[i].copy()
+            ph[np.arange(N), g] = 0
+            pl = ["%d,%d,%d" % tuple(r) for r in ph]
+            if fmt == "GT":
+                vals = list(gt_txt[g])
+            elif fmt == "PL":
+                vals = pl
+            elif fmt == "GL":
+                vals = ["%.1f,%.1f,%.1f" % tuple(-r / 10.0) for r in ph]
+            else:
+                vals = ["%s:%s" % (gt_txt[g[j]], pl[j]) for j in range(N)]
+            for j in np.nonzero(miss[i])[0]:
+                vals[j] = "./." if fmt == "GT" else "."
+            f.write("%s\t%d\t.\t%s\t%s\t.\tPASS\t.\t%s\t%s\n" % (chr_of[i], pos, chr(ref[i]), chr(alt[i]), fmt,
+                                                               "\t".join(vals)))
+            if skipped_every and (i + 1) % skipped_every == 0:
+                pos += 5
+                kind = nskip % 4
+                nskip += 1
+                c, r_, a_, flt = chr_of[i], chr(ref[i]), chr(alt[i]), "PASS"
+                if kind == 0:
+                    flt = "q10"
+                elif kind == 1:
+                    a_ = a_ + ",T" if a_ != "T" else a_ + ",G"
+                elif kind == 2:
+                    r_ = r_ + "AC"
+                else:
+                    c = "X"
+                f.write("%s\t%d\t.\t%s\t%s\t.\t%s\t.\tGT\t%s\n" % (c, pos, r_, a_, flt, "\t".join(gt_txt[g])))
+    return dict(pop=pop, freqs=freqs, ref=ref, alt=alt, chr=chr_of, pos=pos_of, genotypes=np.where(miss, -1, G))
 
 
 def read_bed_rows(bed_path):

@@ -142,6 +142,16 @@ int vb2_ctx_info(const vb2_ctx *ctx, vb2_info *info);
 int vb2_llk_eval_batch(vb2_ctx *ctx, int32_t num_point, const double *pc1,
                        const double *pc2, const double *alpha, double *llk_out);
 
+/* Derivatives of  ComputeMixLLKs(pc1, pc2, alpha)  (ContaminationEstimator.h:194-314) at B points: llk_out[B] as
+ * vb2_llk_eval_batch returns it, grad_out[B][2k+1] and hess_out[B][2k+1][2k+1] (row-major, symmetric) with respect to
+ * (pc1[0..k), pc2[0..k), alpha).  It differentiates the table entries (h:223-224) in alpha, the genotype priors (h:186-192;
+ * 0 where the reference clamps the allele frequency) and the projection AF = (UD pc + mean) / 2 (h:251-267); a marker counts
+ * where its likelihood is > 0 (h:310).  --KnownAF: the PC entries are 0.  At alpha = 0 or 1 the LLK and the PC entries are
+ * exact; the alpha entries there are not defined (they may be NaN).  Synchronous; host pointers; not between
+ * vb2_ctx_search_begin and vb2_ctx_search_end. */
+int vb2_llk_derivs_batch(vb2_ctx *ctx, int32_t num_point, const double *pc1, const double *pc2,
+                         const double *alpha, double *llk_out, double *grad_out, double *hess_out);
+
 /* Same evaluation with DEVICE pointers, enqueued on `stream` (NULL = the
  * context's stream) without any host synchronisation:
  *   d_points : num_point x (2*num_pc+1) doubles, each row = pc1[0..k) pc2[0..k) alpha
@@ -244,6 +254,40 @@ typedef struct vb2_search_opts {
 } vb2_search_opts;
 int vb2_ctx_optimize_llk_ex(vb2_ctx *ctx, const vb2_model *model, const vb2_search_opts *opts,
                             vb2_estimate *best, vb2_estimate *all /* [num_start] or NULL */);
+
+/* A 95% confidence interval for FREEMIX and standard errors of the model's free parameters at an estimate
+ * (vb2_ctx_interval).  Rows are those of <Output>.CI: FREEMIX first, then one row per free PC; values and SEs as
+ * .selfSM / .Ancestry print them -- FREEMIX = alpha or 1 - alpha, the PCs with the reference's swap of indices 0 and 1
+ * between the two samples when alpha >= 0.5 (ContaminationEstimator.cpp:146-149), each SE following its value.
+ * NAN where a value does not exist. */
+#define VB2_CI_MAX_ROW (2 * VB2_MAX_PC + 1)
+typedef struct vb2_interval {
+    double freemix;            /* FREEMIX as .selfSM prints it                                            */
+    double freemix_se;         /* alpha(1-alpha) SE(logit alpha); NAN: alpha fixed or -H not pos. definite */
+    double lo, hi;             /* profile-likelihood interval (chi2_1(0.95)/2 below llk_max); NAN: fixed   */
+    double llk_max;            /* max(-llk1, every profile value)                                         */
+    double llk_lo, llk_hi;     /* profile LLK at lo and hi                                                */
+    int32_t alpha_free;        /* 0: --FixAlpha (no interval: METHOD fixed)                                */
+    int32_t num_free;          /* free parameters: the components of the model's simplex vector (h:339-433) */
+    int32_t pos_def;           /* 1: -H at the estimate is positive definite                              */
+    int32_t num_row;
+    int32_t row_kind[VB2_CI_MAX_ROW];   /* 0 FREEMIX, 1 ContaminatingSample.PC, 2 IntendedSample.PC, 3 PC (shared) */
+    int32_t row_pc[VB2_CI_MAX_ROW];     /* PC number (1-based); 0 for FREEMIX                                  */
+    double row_est[VB2_CI_MAX_ROW];
+    double row_se[VB2_CI_MAX_ROW];
+    double row_lo[VB2_CI_MAX_ROW];      /* FREEMIX: the profile interval; PCs: Wald, estimate -+ 1.96 SE       */
+    double row_hi[VB2_CI_MAX_ROW];
+    int64_t num_launch;        /* derivative launches (vb2_llk_derivs_batch calls) the interval used      */
+    int64_t num_profile;       /* profile points maximised                                                */
+} vb2_interval;
+
+/* The interval at `est` (the result of vb2_ctx_optimize_llk / _ex under `model`).  Standard errors from -H of the LLK in
+ * the free parameters of FullLLKFunc::Evaluate's packing (h:339-433; alpha as logit), from vb2_llk_derivs_batch at the
+ * reported point.  FREEMIX: the profile likelihood -- the LLK maximised over the other free parameters at alpha = f
+ * (1 - f when alpha >= 0.5: L(pc1, pc2, a) = L(pc2, pc1, 1 - a)) by damped Newton steps on the derivatives -- cut at
+ * llk_max - 1.9207294103470620; lo = 0 / hi = 0.5 where the profile stays above the cut there.  model->notices: NOTICE
+ * lines on stderr (a non-positive-definite Hessian, a profile value above -llk1, a search that did not converge). */
+int vb2_ctx_interval(vb2_ctx *ctx, const vb2_model *model, const vb2_estimate *est, vb2_interval *out);
 
 /* ------------------------------------------------------------------------- *
  * 2b. Cohorts: several samples (contexts on one device, same --NumPC) advancing in
@@ -377,6 +421,10 @@ typedef struct vb2_run_result {
 } vb2_run_result;
 
 int vb2_run(const vb2_run_args *args, vb2_run_result *out);
+/* vb2_run, then vb2_ctx_interval on the winning estimate, then <output_prefix>.CI (tab-separated: #PARAM ESTIMATE STDERR
+ * CI_LOW CI_HIGH METHOD) and one NOTICE line with the FREEMIX interval on stderr.  stdout, .selfSM and .Ancestry are what
+ * vb2_run writes.  One device only (VB2_ERR_INVALID for marker shards over several devices, before any file is read). */
+int vb2_run_interval(const vb2_run_args *args, vb2_run_result *out, vb2_interval *ci);
 
 /* Cohort form of vb2_run (BASELINE configs[4]: many samples against one panel).  The reference
  * runs one process per sample; here the panel (.UD/.mu/.bed, optional AF file) is read once, the

@@ -68,6 +68,21 @@ class Estimate(C.Structure):
     ]
 
 
+VB2_CI_MAX_ROW = 2 * VB2_MAX_PC + 1
+
+
+class Interval(C.Structure):
+    _fields_ = [
+        ("freemix", C.c_double), ("freemix_se", C.c_double), ("lo", C.c_double), ("hi", C.c_double),
+        ("llk_max", C.c_double), ("llk_lo", C.c_double), ("llk_hi", C.c_double),
+        ("alpha_free", C.c_int32), ("num_free", C.c_int32), ("pos_def", C.c_int32), ("num_row", C.c_int32),
+        ("row_kind", C.c_int32 * VB2_CI_MAX_ROW), ("row_pc", C.c_int32 * VB2_CI_MAX_ROW),
+        ("row_est", C.c_double * VB2_CI_MAX_ROW), ("row_se", C.c_double * VB2_CI_MAX_ROW),
+        ("row_lo", C.c_double * VB2_CI_MAX_ROW), ("row_hi", C.c_double * VB2_CI_MAX_ROW),
+        ("num_launch", C.c_int64), ("num_profile", C.c_int64),
+    ]
+
+
 class Trace(C.Structure):
     _fields_ = [
         ("capacity", C.c_int64), ("count", C.c_int64),
@@ -144,7 +159,7 @@ EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.P
 
 # every symbol include/vb2_abi.h declares
 SYMBOLS = [
-    "vb2_ctx_create", "vb2_ctx_destroy", "vb2_ctx_info", "vb2_llk_eval_batch",
+    "vb2_ctx_create", "vb2_ctx_destroy", "vb2_ctx_info", "vb2_llk_eval_batch", "vb2_llk_derivs_batch", "vb2_ctx_interval", "vb2_run_interval",
     "vb2_llk_eval_batch_device", "vb2_ctx_search_begin", "vb2_ctx_search_end", "vb2_optimize_llk", "vb2_ctx_optimize_llk", "vb2_ctx_optimize_llk_ex", "vb2_run", "vb2_cohort_run",
     "vb2_flat_load", "vb2_flat_input", "vb2_flat_stats", "vb2_flat_free", "vb2_last_error",
     "vb2_abi_version", "vb2_device_count",
@@ -187,6 +202,8 @@ def lib():
     L.vb2_ctx_info.argtypes = [C.c_void_p, C.POINTER(Info)]
     L.vb2_llk_eval_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]
+    L.vb2_llk_derivs_batch.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6
+    L.vb2_ctx_interval.argtypes = [C.c_void_p, C.POINTER(Model), C.POINTER(Estimate), C.POINTER(Interval)]
     L.vb2_llk_eval_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                             C.c_void_p]
     L.vb2_cohort_run.argtypes = [C.POINTER(CohortArgs), C.POINTER(RunResult), C.POINTER(C.c_int32)]
@@ -200,6 +217,7 @@ def lib():
     L.vb2_ctx_optimize_llk.argtypes = [C.c_void_p, C.POINTER(Model), C.POINTER(Estimate),
                                        C.POINTER(Trace)]
     L.vb2_run.argtypes = [C.POINTER(RunArgs), C.POINTER(RunResult)]
+    L.vb2_run_interval.argtypes = [C.POINTER(RunArgs), C.POINTER(RunResult), C.POINTER(Interval)]
     L.vb2_flat_load.argtypes = [C.POINTER(RunArgs), C.POINTER(C.c_void_p)]
     L.vb2_flat_input.argtypes = [C.c_void_p]
     L.vb2_flat_input.restype = C.POINTER(Input)

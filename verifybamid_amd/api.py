@@ -139,6 +139,22 @@ def _run_args(svd_prefix, pileup_path, num_pc, disable_sanity, known_af_path, ou
     return args, (keep, devs)
 
 
+_CI_NAMES = {1: "ContaminatingSample.PC", 2: "IntendedSample.PC", 3: "PC"}
+
+
+def _interval_dict(ci):
+    rows = []
+    for r in range(ci.num_row):
+        kind = ci.row_kind[r]
+        name = "FREEMIX" if kind == 0 else _CI_NAMES[kind] + str(ci.row_pc[r])
+        method = ("profile" if ci.alpha_free else "fixed") if kind == 0 else "wald"
+        rows.append(dict(param=name, estimate=ci.row_est[r], stderr=ci.row_se[r], lo=ci.row_lo[r], hi=ci.row_hi[r],
+                         method=method))
+    return dict(freemix=ci.freemix, freemix_se=ci.freemix_se, lo=ci.lo, hi=ci.hi, llk_max=ci.llk_max,
+                llk_lo=ci.llk_lo, llk_hi=ci.llk_hi, alpha_free=bool(ci.alpha_free), num_free=int(ci.num_free),
+                pos_def=bool(ci.pos_def), rows=rows, num_launch=int(ci.num_launch), num_profile=int(ci.num_profile))
+
+
 def _estimate_dict(est, k):
     return dict(alpha=est.alpha, llk1=est.llk1, llk0=est.llk0,
                 pc=np.array(est.pc[:k]), pc2=np.array(est.pc2[:k]),
@@ -205,6 +221,34 @@ class LikelihoodContext:
         _abi.check(self._lib.vb2_llk_eval_batch(self._h, B, _p(pc1), _p(pc2), _p(alpha), _p(out)),
                    "vb2_llk_eval_batch")
         return out
+
+    def derivatives(self, pc1, pc2, alpha):
+        """LLK, gradient and Hessian at B points (vb2_llk_derivs_batch), with respect to (pc1[0..k), pc2[0..k), alpha).
+        Returns (llk [B], grad [B, 2k+1], hess [B, 2k+1, 2k+1]).  At alpha 0 or 1 the alpha entries are not defined."""
+        pc1 = np.ascontiguousarray(np.atleast_2d(np.asarray(pc1, dtype=np.float64)))
+        pc2 = np.ascontiguousarray(np.atleast_2d(np.asarray(pc2, dtype=np.float64)))
+        alpha = np.ascontiguousarray(np.atleast_1d(np.asarray(alpha, dtype=np.float64)))
+        B = alpha.shape[0]
+        assert pc1.shape == (B, self.num_pc) and pc2.shape == (B, self.num_pc)
+        n = 2 * self.num_pc + 1
+        llk, grad, hess = np.zeros(B), np.zeros((B, n)), np.zeros((B, n, n))
+        _abi.check(self._lib.vb2_llk_derivs_batch(self._h, B, _p(pc1), _p(pc2), _p(alpha), _p(llk), _p(grad), _p(hess)),
+                   "vb2_llk_derivs_batch")
+        return llk, grad, hess
+
+    def interval(self, estimate, **model_kw):
+        """95% confidence interval for FREEMIX and standard errors at an estimate of optimize(**model_kw) on this context
+        (vb2_ctx_interval): a dict with freemix, freemix_se, lo, hi, llk_max, llk_lo, llk_hi, pos_def and the .CI rows."""
+        m, keep = _model(known_af=self.data.known_af is not None, **model_kw)
+        est = _abi.Estimate()
+        est.alpha, est.llk1, est.llk0 = estimate["alpha"], estimate["llk1"], estimate.get("llk0", 0.0)
+        for j in range(self.num_pc):
+            est.pc[j] = float(estimate["pc"][j])
+            est.pc2[j] = float(estimate["pc2"][j])
+        est.converged = int(bool(estimate.get("converged", True)))
+        ci = _abi.Interval()
+        _abi.check(self._lib.vb2_ctx_interval(self._h, C.byref(m), C.byref(est), C.byref(ci)), "vb2_ctx_interval")
+        return _interval_dict(ci)
 
     def llk_device(self, points_ptr, out_ptr, num_point, stream=None):
         """Enqueue an evaluation on device pointers (rows = pc1|pc2|alpha); no host sync."""
@@ -462,14 +506,21 @@ def optimize_with_evaluator(evaluate, num_pc, trace_capacity=0, known_af=False, 
 
 
 def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_sanity=False,
-              known_af_path=None, device=-1, output_pileup=False, devices=None, **model_kw):
+              known_af_path=None, device=-1, output_pileup=False, devices=None, confidence_interval=False, **model_kw):
     """The --SVDPrefix/--PileupFile flow of execute() (vb2_run); devices=[a, b, ...] shards the
-    sample's markers over those GPUs."""
+    sample's markers over those GPUs.  confidence_interval: vb2_run_interval (<output_prefix>.CI, and an
+    `interval` entry in the result)."""
     args, keep = _run_args(svd_prefix, pileup_path, num_pc, disable_sanity, known_af_path,
                            output_prefix, device, output_pileup, devices=devices, **model_kw)
     res = _abi.RunResult()
-    _abi.check(_abi.lib().vb2_run(C.byref(args), C.byref(res)), "vb2_run")
+    ci = _abi.Interval() if confidence_interval else None
+    if ci is not None:
+        _abi.check(_abi.lib().vb2_run_interval(C.byref(args), C.byref(res), C.byref(ci)), "vb2_run_interval")
+    else:
+        _abi.check(_abi.lib().vb2_run(C.byref(args), C.byref(res)), "vb2_run")
     out = _estimate_dict(res.est, num_pc)
+    if ci is not None:
+        out["interval"] = _interval_dict(ci)
     out.update(num_marker=res.num_marker, num_site=res.num_site, num_bases=int(res.num_bases),
                avg_depth=res.avg_depth, sd_depth=res.sd_depth, seconds_load=res.seconds_load,
                seconds_optimize=res.seconds_optimize)

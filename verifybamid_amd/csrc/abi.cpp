@@ -161,6 +161,13 @@ int vb2_llk_eval_batch(vb2_ctx* ctx, int32_t num_point, const double* pc1, const
     return ctx->impl->eval_host(num_point, pc1, pc2, alpha, llk_out);
 }
 
+int vb2_llk_derivs_batch(vb2_ctx* ctx, int32_t num_point, const double* pc1, const double* pc2, const double* alpha,
+                         double* llk_out, double* grad_out, double* hess_out)
+{
+    if (int rc = guard_ctx(ctx)) return rc;
+    return ctx->impl->derivs_host(num_point, pc1, pc2, alpha, llk_out, grad_out, hess_out);
+}
+
 int vb2_llk_eval_batch_device(vb2_ctx* ctx, int32_t num_point, const double* d_points,
                               double* d_llk_out, void* stream)
 {
@@ -782,10 +789,29 @@ int vb2_flat_stats(const vb2_flat* f, vb2_run_result* out)
 
 void vb2_flat_free(vb2_flat* f) { delete f; }
 
-int vb2_run(const vb2_run_args* a, vb2_run_result* out)
+int vb2_ctx_interval(vb2_ctx* ctx, const vb2_model* model, const vb2_estimate* est, vb2_interval* out)
+{
+    if (int rc = guard_ctx(ctx)) return rc;
+    if (!model || !est || !out) {
+        set_error("vb2_ctx_interval: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    return vb2::ctx_interval(ctx->impl, *model, *est, out);
+}
+
+}  // extern "C"
+
+namespace {
+
+// vb2_run, and with ci != nullptr vb2_run_interval
+int run_impl(const vb2_run_args* a, vb2_run_result* out, vb2_interval* ci)
 {
     if (!a || !out) {
         set_error("vb2_run: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    if (ci && a->devices && a->num_device > 1) {
+        set_error("--ConfidenceInterval takes one device: it cannot be combined with marker shards over several --Devices");
         return VB2_ERR_INVALID;
     }
     const double t0 = now_s();
@@ -862,6 +888,14 @@ int vb2_run(const vb2_run_args* a, vb2_run_result* out)
         out->seconds_optimize = now_s() - t1;
         if (notices)
             std::fprintf(stderr, "NOTICE - Finished phase: Optimize likelihood  [%.3f seconds]\n", out->seconds_optimize);
+        if (!rc && ci) {
+            const double t2 = now_s();
+            if (notices) std::fprintf(stderr, "NOTICE - Starting phase: Confidence interval\n");
+            rc = vb2_ctx_interval(ctx, &model, &out->est, ci);
+            if (notices)
+                std::fprintf(stderr, "NOTICE - Finished phase: Confidence interval  [%.3f seconds, %lld derivative launches]\n",
+                             now_s() - t2, (long long)ci->num_launch);
+        }
         vb2_ctx_destroy(ctx);
         if (rc) return rc;
     }
@@ -871,8 +905,25 @@ int vb2_run(const vb2_run_args* a, vb2_run_result* out)
         if ((rc = vb2::write_ancestry(a->output_prefix, a->num_pc, out->est.pc, out->est.pc2))) return rc;
         // main.cpp:398-400: #READS is viewer.numBases for BAM input, "NA" for pileup input
         if ((rc = vb2::write_selfsm(a->output_prefix, *flat, out->est, a->pileup_path != nullptr))) return rc;
+        if (ci && (rc = vb2::write_ci(a->output_prefix, *ci))) return rc;
     }
+    if (ci) std::fprintf(stderr, "NOTICE - FREEMIX 95%% CI (profile likelihood): [%g, %g]\n", ci->lo, ci->hi);
     return VB2_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vb2_run(const vb2_run_args* a, vb2_run_result* out) { return run_impl(a, out, nullptr); }
+
+int vb2_run_interval(const vb2_run_args* a, vb2_run_result* out, vb2_interval* ci)
+{
+    if (!ci) {
+        set_error("vb2_run_interval: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    return run_impl(a, out, ci);
 }
 
 }  // extern "C"

@@ -66,6 +66,7 @@ int main(int argc, char** argv)
     bool withinAncestry = false, outputPileup = false, verbose = false, disableSanityCheck = false;
     int seed = 12345, nPC = 2, nthread = 4, device = -1, numStart = 1;
     bool lineSearch = false;
+    bool confidenceInterval = false;
     // "Pileup Options" (main.cpp:176-187), defaults main.cpp:81-96 (MPLP_REALN | MPLP_SMART_OVERLAPS; UNMAP | SECONDARY |
     // QCFAIL | DUP): they shape what --BamFile input becomes and, as in the reference, do nothing to --PileupFile input
     int minBQ = 13, minMQ = 2, adjustMQ = 40, maxDepth = 8000, inclFlags = (1 << 4) | (1 << 10), exclFlags = 0x4 | 0x100 | 0x200 | 0x400;
@@ -114,6 +115,9 @@ int main(int argc, char** argv)
         // MathGold) for the one-parameter models (--FixPC / --KnownAF).
         {"NumStart", {Flag::kInt, &numStart, false}},
         {"LineSearch", {Flag::kBool, &lineSearch, false}},
+        // not in the reference: a 95% confidence interval for FREEMIX (profile likelihood) and standard errors of the free
+        // parameters, written to <Output>.CI (vb2_run_interval)
+        {"ConfidenceInterval", {Flag::kBool, &confidenceInterval, false}},
     };
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
@@ -144,6 +148,12 @@ int main(int argc, char** argv)
         if (f.kind == Flag::kInt) *static_cast<int*>(f.dst) = std::atoi(v);
         else if (f.kind == Flag::kDouble) *static_cast<double*>(f.dst) = std::atof(v);
         else *static_cast<std::string*>(f.dst) = v;
+    }
+    if (confidenceInterval) {                                           // single-sample, single-device runs only
+        if (PileupList != "Empty")
+            fatal("--ConfidenceInterval cannot be combined with --PileupList: intervals are computed for one sample per run");
+        if (Devices != "Empty" && Devices.find(',') != std::string::npos)
+            fatal("--ConfidenceInterval cannot be combined with more than one --Devices: intervals are computed on one device");
     }
     // --Seed: parsed and never used by the reference (main.cpp:137,286); here it seeds --NumStart's starting points
     // --NumThread: the likelihood runs on the GPU; the VCF parser pool of --RefVCF and the reader threads of --PileupList use it
@@ -299,7 +309,8 @@ int main(int argc, char** argv)
     }
 
     vb2_run_result res;
-    const int rc = vb2_run(&args, &res);
+    vb2_interval ci;
+    const int rc = confidenceInterval ? vb2_run_interval(&args, &res, &ci) : vb2_run(&args, &res);
     if (rc != VB2_OK) {
         if (rc == VB2_ERR_SANITY) std::fprintf(stderr, "WARNING - %s\n", vb2_last_error());
         else std::fprintf(stderr, "\nFATAL ERROR - \n%s\n\n", vb2_last_error());

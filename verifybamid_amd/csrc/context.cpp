@@ -196,6 +196,7 @@ Context::~Context()
     if (h_slab && !slab_cache().give(slab_cache().pin, h_slab, h_slab_bytes, device)) (void)hipHostFree(h_slab);
     if (h_trace_stage) (void)hipHostFree(h_trace_stage);
     if (d_codes16_own) (void)hipFree(d_codes16_own);
+    if (d_deriv && !slab_cache().give(slab_cache().dev, d_deriv, d_deriv_bytes, device)) (void)hipFree(d_deriv);
     for (CohortSched& e : cohort_sched_)
         if (e.d_mem && !slab_cache().give(slab_cache().dev, e.d_mem, e.bytes, device)) (void)hipFree(e.d_mem);
     if (own_stream && stream && !slab_cache().give_stream(stream, device)) (void)hipStreamDestroy(stream);

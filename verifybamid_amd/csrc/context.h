@@ -146,6 +146,13 @@ public:
     void* d_codes16_own = nullptr;
     int64_t cohort_bytes = 0;                 // device bytes one cohort step streams for this sample
     int num_code_seen = 0;                    // distinct (class, quality) codes of the data (vb2_info::num_code)
+    // Gradient and Hessian of the LLK at B points (deriv_kernels.hip; host pointers, synchronous): llk[B], grad[B][2k+1],
+    // hess[B][2k+1][2k+1] in the order pc1[0..k) pc2[0..k) alpha.  Scratch from the slab cache on the first call (d_deriv),
+    // kept for the context's lifetime.  Not between resident_begin and resident_end.  Defined in derivs.cpp.
+    int derivs_host(int num_point, const double* pc1, const double* pc2, const double* alpha, double* llk, double* grad,
+                    double* hess);
+    double* d_deriv = nullptr;
+    size_t d_deriv_bytes = 0;
 
     int device = -1;
     int num_marker = 0;
@@ -201,6 +208,12 @@ namespace vb2 {
 // words to NaN before a step and, once the flag is seen, wait here a few microseconds for NaNs still on their way.
 // false: a NaN stayed (the kernels' own "a workgroup never reported", or the input's).
 bool settle_results(const double* out, int n);
+}  // namespace vb2
+
+namespace vb2 {
+// vb2_ctx_interval / <prefix>.CI (interval.cpp)
+int ctx_interval(Context* ctx, const vb2_model& model, const vb2_estimate& est, vb2_interval* out);
+int write_ci(const std::string& prefix, const vb2_interval& ci);
 }  // namespace vb2
 
 struct vb2_ctx {

@@ -1,0 +1,34 @@
+// deriv_kernels.h -- derivatives of the genotype-mixture log-likelihood on the device (deriv_kernels.hip).
+#ifndef VB2_DERIV_KERNELS_H_
+#define VB2_DERIV_KERNELS_H_
+
+#include <hip/hip_runtime_api.h>
+
+#include "llk_kernels.h"
+
+namespace vb2 {
+
+// Per marker and point, the read-loop kernel writes these ten scalars (0 for a marker whose likelihood L is not > 0, h:310):
+// log L, then with x, y in {1 = AF of pc1 (contaminant), 2 = AF of pc2 (intended), a = alpha}:
+//   l_1, l_2, l_a, l_11, l_22, l_12, l_1a, l_2a, l_aa    (l_x = L_x / L, l_xy = L_xy / L - l_x l_y)
+constexpr int kDerivVals = 10;
+// Points per pass of the two kernels: the scratch of a context holds kDerivChunk x kDerivVals x m_pad doubles
+constexpr int kDerivChunk = 4;
+
+// Outputs per point of the reduction: the LLK, the gradient (n = 2k + 1 entries, order pc1[0..k) pc2[0..k) alpha) and the upper
+// triangle of the Hessian, row by row
+__host__ __device__ inline int deriv_out_count(int k) { const int n = 2 * k + 1; return 1 + n + n * (n + 1) / 2; }
+// doubles of device scratch a context needs (per-marker scalars, parameter rows, outputs of one chunk)
+inline size_t deriv_scratch_doubles(const DeviceLayout& L)
+{
+    return (size_t)kDerivChunk * ((size_t)kDerivVals * (size_t)L.m_pad + (size_t)(2 * L.num_pc + 1) + (size_t)deriv_out_count(L.num_pc));
+}
+
+// Enqueue the derivatives of num_point <= kDerivChunk rows (pc1 | pc2 | alpha, device memory) on stream: d_out receives
+// deriv_out_count(k) doubles per point.  d_marker: kDerivChunk x kDerivVals x m_pad doubles of scratch.
+hipError_t launch_llk_derivs(const DeviceLayout& L, int num_point, const double* d_points, double* d_marker, double* d_out,
+                             hipStream_t stream);
+
+}  // namespace vb2
+
+#endif

@@ -1,0 +1,390 @@
+// deriv_kernels.hip -- gfx950 kernels for the gradient and Hessian of the genotype-mixture log-likelihood
+// (FullLLKFunc::ComputeMixLLKs, ContaminationEstimator.h:194-314) with respect to (pc1[0..k), pc2[0..k), alpha).
+// DESIGN.md section 10 has the math; this file walks the layouts the context already holds (llk_kernels.h: DeviceLayout),
+// in both forms, and makes no second copy of the reads.
+//
+//   * llk_derivs_marker_kernel: one workgroup per (stripe of micro-tiles, point).  It builds the point's derivative table
+//     in LDS -- per table row and off-diagonal genotype pair {value, d, d^2} with d = dp/dalpha / p -- and one thread per
+//     marker walks the marker's runs (log domain: value = log p, a run of n reads adds n x each entry) or steps
+//     (probability domain: value = P^n, the row carries n d and n d^2; window rows the sums of their factors').  The
+//     epilogue forms the marker's nine derivatives of L = GF1' W GF2 and writes them with log L to the scratch
+//     [point][kDerivVals][m_pad].
+//   * llk_derivs_reduce_kernel: one workgroup per (output, point) sums a scalar over the markers with the sorted panel
+//     rows (AF = (UD pc + mu) / 2: the chain rule), in a fixed order -- thread t takes positions t, t + 256, ..., then a
+//     fixed tree.  A point's results are the same bits whatever else the batch holds and from one call to the next.
+#include "deriv_kernels.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace vb2 {
+namespace {
+
+constexpr int kThreads = 256;                     // 16 micro-tiles of 16 markers per pass of a workgroup
+constexpr int kEntry = 3;                         // {value, d, d^2} per (row, pair)
+constexpr int kRowDoubles = 6 * kEntry;
+constexpr double kMinAf = 0.00005, kMaxAf = 0.99995;   // h:94-95
+
+// off-diagonal genotype pairs, in the reference's (g1 outer, g2 inner) order (as llk_kernels.hip numbers them)
+__device__ __forceinline__ void pair_g(int p, int& g1, int& g2)
+{
+    g1 = p >> 1;
+    const int lo = p & 1;
+    g2 = lo + (lo >= g1 ? 1 : 0);
+}
+
+// h:223-224 for one class / quality / pair: p = alpha u_g1 + (1 - alpha) u_g2 (the reference's expression order) and
+// d = (u_g1 - u_g2) / p = dp/dalpha / p, 0 where p = 0; a negative p (alpha outside [0, 1]) is NaN.  The class is ref; alt
+// reads the pair mirrored (g -> 2 - g, h:164-177).
+__device__ __forceinline__ void entry_of(double alpha, double p_err, int g1, int g2, double& p, double& d)
+{
+    const double p_ok = 1.0 - p_err;
+    const double e1 = (double)g1 * (1.0 / 6.0), e2 = (double)g2 * (1.0 / 6.0);
+    const double n1 = 1.0 - 0.5 * (double)g1, n2 = 1.0 - 0.5 * (double)g2;
+    const double one_minus_alpha = 1.0 - alpha;
+    p = (alpha * e1 + one_minus_alpha * e2) * p_err + (alpha * n1 + one_minus_alpha * n2) * p_ok;
+    p = p >= 0.0 ? p : __builtin_nan("");          // alpha outside [0, 1]: NaN, the marker is left out (as prob_entry)
+    const double u1 = e1 * p_err + n1 * p_ok, u2 = e2 * p_err + n2 * p_ok;
+    d = p != 0.0 ? (u1 - u2) / p : 0.0;
+}
+
+// GF (h:186-192) and its first two derivatives in AF; both 0 where the reference clamps AF (the branch it takes)
+__device__ __forceinline__ void gf_derivs(double af, bool fixed, double* gf, double* d1, double* d2)
+{
+    const bool clamped = af < kMinAf || af > kMaxAf || fixed;
+    if (af < kMinAf) af = kMinAf;
+    if (af > kMaxAf) af = kMaxAf;
+    gf[0] = (1 - af) * (1 - af);
+    gf[1] = 2 * (af) * (1 - af);
+    gf[2] = af * af;
+    d1[0] = clamped ? 0.0 : -2.0 * (1.0 - af);
+    d1[1] = clamped ? 0.0 : 2.0 - 4.0 * af;
+    d1[2] = clamped ? 0.0 : 2.0 * af;
+    d2[0] = clamped ? 0.0 : 2.0;
+    d2[1] = clamped ? 0.0 : -4.0;
+    d2[2] = clamped ? 0.0 : 2.0;
+}
+
+template <bool PD>
+__global__ void __launch_bounds__(kThreads)
+llk_derivs_marker_kernel(const DeviceLayout L, const double* __restrict__ points, double* __restrict__ out)
+{
+    extern __shared__ __attribute__((aligned(16))) double tab[];      // [nrow][6 pairs][kEntry]
+    const int tid = threadIdx.x;
+    const int pt = blockIdx.y;
+    const int k = L.num_pc, stride = 2 * k + 1;
+    const double* prow = points + (size_t)pt * stride;
+    const double alpha = prow[2 * k];
+    const int nrow = L.num_code + 1;
+    const size_t mp = (size_t)L.m_pad;
+
+    // ---- the point's table ----
+    const int num_single = PD ? L.num_prim - L.num_pair : L.num_prim;
+    for (int e = tid; e < num_single * 6; e += kThreads) {
+        const int pi = e / 6, p = e - pi * 6;
+        const double2 rec = L.prim[pi];
+        const uint32_t pr = (uint32_t)__double_as_longlong(rec.y);
+        const int first = (int)(pr & 0xffffu), twin = (int)(pr >> 16);
+        int g1, g2;
+        pair_g(p, g1, g2);
+        double v, d;
+        if constexpr (PD) {
+            // record = a quality, class ref: {pErr, first row | K << 16 | rows from P^n to P^(n+1), a signed byte, << 24}
+            entry_of(alpha, rec.x, g1, g2, v, d);
+            const int kq = twin & 0xff, rstep = (int)(int8_t)(twin >> 8);
+            double r = v;
+            for (int n = 1; n <= kq; ++n) {
+                const int row = first + (n - 1) * rstep;
+                if (row >= 0 && row < nrow) {
+                    double* c = tab + (size_t)row * kRowDoubles + p * kEntry;
+                    c[0] = r;
+                    c[1] = (double)n * d;
+                    c[2] = (double)n * (d * d);
+                }
+                r *= v;
+            }
+        } else {
+            // record = a code: {signed pErr (alt < 0), code | twin << 16}; the alt twin's row is this one mirrored (pair 5 - p)
+            if (rec.x < 0.0) { g1 = 2 - g1; g2 = 2 - g2; }
+            entry_of(alpha, fabs(rec.x), g1, g2, v, d);
+            const double lv = log(v);
+            if (first < nrow) {
+                double* c = tab + (size_t)first * kRowDoubles + p * kEntry;
+                c[0] = lv; c[1] = d; c[2] = d * d;
+            }
+            if (twin != 0xffff && twin < nrow) {
+                double* c = tab + (size_t)twin * kRowDoubles + (5 - p) * kEntry;
+                c[0] = lv; c[1] = d; c[2] = d * d;
+            }
+        }
+    }
+    for (int e = tid; e < kRowDoubles; e += kThreads)           // padding row: P = 1 (log domain: 0), no derivative
+        tab[(size_t)L.num_code * kRowDoubles + e] = (PD && e % kEntry == 0) ? 1.0 : 0.0;
+    if constexpr (PD) {
+        // window rows: the product of two rows -- the value multiplies, d and d^2 add (level 1 uses rows of level 0)
+        for (int level = 0; level < 2; ++level) {
+            const int nrec = level == 0 ? L.num_pair - L.num_pair2 : L.num_pair2;
+            const int base = num_single + (level == 0 ? 0 : L.num_pair - L.num_pair2);
+            __syncthreads();
+            for (int e = tid; e < nrec * 6; e += kThreads) {
+                const int pi = e / 6, p = e - pi * 6;
+                const double2 rec = L.prim[base + pi];
+                const uint32_t ab = (uint32_t)__double_as_longlong(rec.x), dst = (uint32_t)__double_as_longlong(rec.y);
+                const uint32_t ra = ab & 0xffffu, rb = ab >> 16;
+                if (ra >= (uint32_t)nrow || rb >= (uint32_t)nrow || dst >= (uint32_t)nrow) continue;
+                const double* a = tab + (size_t)ra * kRowDoubles + p * kEntry;
+                const double* b = tab + (size_t)rb * kRowDoubles + p * kEntry;
+                double* c = tab + (size_t)dst * kRowDoubles + p * kEntry;
+                c[0] = a[0] * b[0];
+                c[1] = a[1] + b[1];
+                c[2] = a[2] + b[2];
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- one thread per marker of the sorted order ----
+    const int m = tid & 15;
+    const int ntile_grp = (L.num_mt + 15) / 16;
+    for (int tg = blockIdx.x; tg < ntile_grp; tg += gridDim.x) {
+        const int mt = tg * 16 + (tid >> 4);
+        if (mt >= L.num_mt) continue;
+        const size_t pos = (size_t)mt * 16 + (size_t)m;
+        double* o = out + (size_t)pt * kDerivVals * mp + pos;
+        if (pos >= (size_t)L.num_active) {
+            for (int j = 0; j < kDerivVals; ++j) o[(size_t)j * mp] = 0.0;
+            continue;
+        }
+        const uint2 rec = L.mt_rec[mt];
+        double acc[6], a1[6], a2[6];
+        for (int p = 0; p < 6; ++p) { acc[p] = PD ? 1.0 : L.ediag[pos]; a1[p] = 0.0; a2[p] = 0.0; }
+        if constexpr (PD) {
+            // {ref steps | all steps << 16}; a step = a 16-bit byte offset of its row (+ kPdAltOffset for class alt), two per word
+            const uint32_t s1 = rec.y & 0xffffu, s2 = rec.y >> 16;
+            const uint16_t* c16 = reinterpret_cast<const uint16_t*>(L.codes);
+            for (uint32_t s = 0; s < s2; ++s) {
+                const bool alt = s >= s1;
+                uint32_t off = c16[(((size_t)rec.x + (s >> 1)) * 16 + (size_t)m) * 2 + (s & 1u)];
+                if (alt) off -= (uint32_t)kPdAltOffset;
+                uint32_t row = off / (uint32_t)L.row_bytes;
+                row = row < (uint32_t)nrow ? row : (uint32_t)L.num_code;
+                const double* t = tab + (size_t)row * kRowDoubles;
+#pragma unroll
+                for (int p = 0; p < 6; ++p) {
+                    const double* c = t + (alt ? 5 - p : p) * kEntry;
+                    acc[p] *= c[0];
+                    a1[p] += c[1];
+                    a2[p] += c[2];
+                }
+            }
+        } else {
+            // {first row, rows}; a row = two run words, run = row byte offset | top 16 bits of double(count) << 16
+            for (uint32_t r = 0; r < rec.y; ++r) {
+                const uint2 w = L.codes[((size_t)rec.x + r) * 16 + (size_t)m];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const uint32_t rw = j ? w.y : w.x;
+                    const double n = __hiloint2double((int)(rw & 0xffff0000u), 0);
+                    uint32_t row = (rw & 0xffffu) / (uint32_t)L.row_bytes;
+                    row = row < (uint32_t)nrow ? row : (uint32_t)L.num_code;
+                    const double* t = tab + (size_t)row * kRowDoubles;
+#pragma unroll
+                    for (int p = 0; p < 6; ++p) {
+                        acc[p] = fma(n, t[p * kEntry], acc[p]);
+                        a1[p] = fma(n, t[p * kEntry + 1], a1[p]);
+                        a2[p] = fma(n, t[p * kEntry + 2], a2[p]);
+                    }
+                }
+            }
+        }
+        // ---- epilogue: W[g1][g2] (diagonal: the context's constants), A' and A'' + A'^2 off the diagonal ----
+        double af1, af2;
+        const bool kaf = L.known_af != nullptr;
+        if (kaf) {
+            af1 = af2 = L.known_af[pos];
+        } else {
+            af1 = 0.0; af2 = 0.0;
+            for (int kk = 0; kk < k; ++kk) {
+                const double u = L.ud[(size_t)kk * mp + pos];
+                af1 = fma(u, prow[kk], af1);
+                af2 = fma(u, prow[k + kk], af2);
+            }
+            const double mu = L.mu[pos];
+            af1 += mu; af1 /= 2.0;
+            af2 += mu; af2 /= 2.0;
+        }
+        double G1[3], G1d[3], G1dd[3], G2[3], G2d[3], G2dd[3];
+        gf_derivs(af1, kaf, G1, G1d, G1dd);
+        gf_derivs(af2, kaf, G2, G2d, G2dd);
+        double W[3][3], WA[3][3], WB[3][3];
+        const double cst = PD ? L.ediag[pos] : 0.0;
+        for (int g = 0; g < 3; ++g) { W[g][g] = L.ediag[(size_t)(1 + g) * mp + pos]; WA[g][g] = 0.0; WB[g][g] = 0.0; }
+        double lk = 0.0;         // L itself, in the reference's order (h:307-309): what decides whether the marker counts
+        double scale = 0.0;      // log domain: W relative to exp(scale), so that the ratios survive deep markers
+        if constexpr (!PD) {
+            double amax = -__builtin_huge_val();
+            for (int p = 0; p < 6; ++p) amax = acc[p] > amax ? acc[p] : amax;
+            for (int g = 0; g < 3; ++g)
+                if (W[g][g] > 0.0) { const double lw = log(W[g][g]); amax = lw > amax ? lw : amax; }
+            scale = amax > -__builtin_huge_val() && amax < __builtin_huge_val() ? amax : 0.0;
+        }
+        double Wu[3][3];
+        for (int g = 0; g < 3; ++g) Wu[g][g] = W[g][g];
+#pragma unroll
+        for (int p = 0; p < 6; ++p) {
+            int g1, g2;
+            pair_g(p, g1, g2);
+            double wu, ws;
+            if constexpr (PD) {
+                wu = ws = cst * acc[p];
+            } else {
+                wu = exp(acc[p]);
+                ws = exp(acc[p] - scale);
+            }
+            Wu[g1][g2] = wu;
+            W[g1][g2] = ws;
+            WA[g1][g2] = ws * a1[p];
+            WB[g1][g2] = ws * (a1[p] * a1[p] - a2[p]);
+        }
+        if constexpr (!PD)
+            for (int g = 0; g < 3; ++g) W[g][g] = W[g][g] > 0.0 ? exp(log(W[g][g]) - scale) : 0.0;
+        for (int g1 = 0; g1 < 3; ++g1)
+            for (int g2 = 0; g2 < 3; ++g2) lk += Wu[g1][g2] * G1[g1] * G2[g2];
+        double v[kDerivVals];
+        for (int j = 0; j < kDerivVals; ++j) v[j] = 0.0;
+        if (lk > 0) {
+            // rows weighted by GF2 and its derivatives, then the GF1 side
+            double r0[3], r1[3], r2[3], s0[3], s1v[3], t0[3];
+            for (int a = 0; a < 3; ++a) {
+                r0[a] = r1[a] = r2[a] = s0[a] = s1v[a] = t0[a] = 0.0;
+                for (int b = 0; b < 3; ++b) {
+                    r0[a] += W[a][b] * G2[b];
+                    r1[a] += W[a][b] * G2d[b];
+                    r2[a] += W[a][b] * G2dd[b];
+                    s0[a] += WA[a][b] * G2[b];
+                    s1v[a] += WA[a][b] * G2d[b];
+                    t0[a] += WB[a][b] * G2[b];
+                }
+            }
+            double Ls = 0, L1 = 0, L2 = 0, L11 = 0, L22 = 0, L12 = 0, La = 0, L1a = 0, L2a = 0, Laa = 0;
+            for (int a = 0; a < 3; ++a) {
+                Ls += G1[a] * r0[a];
+                L1 += G1d[a] * r0[a];
+                L11 += G1dd[a] * r0[a];
+                L2 += G1[a] * r1[a];
+                L12 += G1d[a] * r1[a];
+                L22 += G1[a] * r2[a];
+                La += G1[a] * s0[a];
+                L1a += G1d[a] * s0[a];
+                L2a += G1[a] * s1v[a];
+                Laa += G1[a] * t0[a];
+            }
+            if (Ls > 0) {
+                const double inv = 1.0 / Ls;
+                const double l1 = L1 * inv, l2 = L2 * inv, la = La * inv;
+                v[1] = l1;
+                v[2] = l2;
+                v[3] = la;
+                v[4] = L11 * inv - l1 * l1;
+                v[5] = L22 * inv - l2 * l2;
+                v[6] = L12 * inv - l1 * l2;
+                v[7] = L1a * inv - l1 * la;
+                v[8] = L2a * inv - l2 * la;
+                v[9] = Laa * inv - la * la;
+            }
+            v[0] = log(lk);
+        }
+        for (int j = 0; j < kDerivVals; ++j) o[(size_t)j * mp] = v[j];
+    }
+}
+
+// Output e of a point (deriv_out_count): 0 = LLK, then the gradient, then the Hessian's upper triangle row by row.
+// Returns the marker scalar it sums and the UD columns (-1: none) and power-of-two factor that weight it.
+__device__ __forceinline__ void output_terms(int e, int k, int& val, int& ca, int& cb, double& f)
+{
+    const int n = 2 * k + 1;
+    ca = cb = -1;
+    f = 1.0;
+    if (e == 0) { val = 0; return; }
+    e -= 1;
+    if (e < n) {                                   // gradient
+        if (e < k) { val = 1; ca = e; f = 0.5; }
+        else if (e < 2 * k) { val = 2; ca = e - k; f = 0.5; }
+        else val = 3;
+        return;
+    }
+    e -= n;
+    int r = 0;
+    while (e >= n - r) { e -= n - r; ++r; }
+    const int c = r + e;                           // r <= c
+    const int tr = r < k ? 1 : r < 2 * k ? 2 : 0, tc = c < k ? 1 : c < 2 * k ? 2 : 0;   // 1 pc1, 2 pc2, 0 alpha
+    const int ir = tr == 2 ? r - k : r, ic = tc == 2 ? c - k : c;
+    if (tr == 1 && tc == 1) { val = 4; ca = ir; cb = ic; f = 0.25; }
+    else if (tr == 2 && tc == 2) { val = 5; ca = ir; cb = ic; f = 0.25; }
+    else if (tr == 1 && tc == 2) { val = 6; ca = ir; cb = ic; f = 0.25; }
+    else if (tr == 1 && tc == 0) { val = 7; ca = ir; f = 0.5; }
+    else if (tr == 2 && tc == 0) { val = 8; ca = ir; f = 0.5; }
+    else val = 9;
+}
+
+__global__ void __launch_bounds__(kThreads)
+llk_derivs_reduce_kernel(const DeviceLayout L, const double* __restrict__ marker, double* __restrict__ out)
+{
+    __shared__ double part[kThreads];
+    const int tid = threadIdx.x;
+    const int e = blockIdx.x, pt = blockIdx.y;
+    const int k = L.num_pc;
+    int val, ca, cb;
+    double f;
+    output_terms(e, k, val, ca, cb, f);
+    const size_t mp = (size_t)L.m_pad, na = (size_t)L.num_active;
+    const double* s = marker + ((size_t)pt * kDerivVals + (size_t)val) * mp;
+    // known allele frequencies: no PC dependence (the PC entries are 0 and there are no panel rows to read)
+    const bool pc_free = L.known_af == nullptr;
+    const double* ua = (ca >= 0 && pc_free) ? L.ud + (size_t)ca * mp : nullptr;
+    const double* ub = (cb >= 0 && pc_free) ? L.ud + (size_t)cb * mp : nullptr;
+    double sum = 0.0;
+    if (ca < 0 || pc_free)
+        for (size_t i = (size_t)tid; i < na; i += kThreads) {
+            double w = s[i];
+            if (ua) w *= ua[i];
+            if (ub) w *= ub[i];
+            sum += w;
+        }
+    part[tid] = sum;
+    __syncthreads();
+    for (int h = kThreads / 2; h > 0; h >>= 1) {
+        if (tid < h) part[tid] += part[tid + h];
+        __syncthreads();
+    }
+    if (tid == 0) out[(size_t)pt * deriv_out_count(k) + e] = part[0] * f;
+}
+
+}  // namespace
+
+hipError_t launch_llk_derivs(const DeviceLayout& L, int num_point, const double* d_points, double* d_marker, double* d_out,
+                             hipStream_t stream)
+{
+    if (num_point <= 0) return hipSuccess;
+    if (num_point > kDerivChunk) return hipErrorInvalidValue;
+    const int nrow = L.num_code + 1;
+    const size_t shmem = (size_t)nrow * kRowDoubles * sizeof(double);
+    const int ntile_grp = (L.num_mt + 15) / 16;
+    // about four workgroups per CU over the whole launch; each walks a stripe of 16-tile groups with one table
+    int gx = (4 * (L.num_cu > 0 ? L.num_cu : 1) + num_point - 1) / num_point;
+    gx = gx < ntile_grp ? gx : ntile_grp;
+    gx = gx > 0 ? gx : 1;
+    const dim3 grid((unsigned)gx, (unsigned)num_point), block(kThreads);
+    if (L.pd)
+        hipLaunchKernelGGL(llk_derivs_marker_kernel<true>, grid, block, shmem, stream, L, d_points, d_marker);
+    else
+        hipLaunchKernelGGL(llk_derivs_marker_kernel<false>, grid, block, shmem, stream, L, d_points, d_marker);
+    hipError_t rc = hipGetLastError();
+    if (rc != hipSuccess) return rc;
+    const dim3 rgrid((unsigned)deriv_out_count(L.num_pc), (unsigned)num_point);
+    hipLaunchKernelGGL(llk_derivs_reduce_kernel, rgrid, block, 0, stream, L, d_marker, d_out);
+    return hipGetLastError();
+}
+
+}  // namespace vb2

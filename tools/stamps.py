@@ -32,6 +32,26 @@ if os.environ.get("VB2_STAMPS_DETAIL"):
     print("last wave done, median by workgroup index mod 8 (XCD): " + " ".join("%.2f" % np.median(t4[x::8]) for x in range(8)))
     print("   by index mod 16: " + " ".join("%.1f" % np.median(t4[x::16]) for x in range(16)))
     print("   by index // 32:  " + " ".join("%.2f" % np.median(t4[32 * x:32 * x + 32]) for x in range(8)))
+    # (a split launch's workgroups leave 1 + their XCC id in word 7 -- not the workgroups 0, 20, 21: by the XCD itself, and
+    # by the depth of a workgroup's tiles -- its index among the workgroups of its XCD, the tiles being dealt deepest first)
+    xcc = s[:, 7].astype(np.int64) - 1
+    has = (xcc >= 0) & (xcc < 8)
+    has[[i for i in (0, 20, 21) if i < len(has)]] = False
+    if has.sum() > 8:
+        t5 = us[:, 5]
+        print("by XCC id (workgroups, last wave done median / max, block reduced median): " +
+              "  ".join("%d: %d %.2f / %.2f %.2f" % (x, (has & (xcc == x)).sum(), np.median(t4[has & (xcc == x)]), t4[has & (xcc == x)].max(),
+                                                  np.median(t5[has & (xcc == x)])) for x in range(8) if (has & (xcc == x)).any()))
+        idx = np.arange(len(t4))
+        print("   workgroups whose XCC id is that of their index mod 8's majority: %d of %d"
+              % (sum((xcc[i] == np.bincount(xcc[has & (idx % 8 == i % 8)]).argmax()) for i in idx[has]), has.sum()))
+        resid = t4 - np.array([np.median(t4[has & (xcc == xcc[i])]) if has[i] else 0.0 for i in idx])
+        q = len(t4) // 4
+        print("   last wave done minus its XCD's median, by quarter of the workgroup index (first quarter = deepest tiles): " +
+              " ".join("%.2f" % np.median(resid[has & (idx >= a) & (idx < a + q)]) for a in range(0, 4 * q, q)))
+        print("   spread (max - min) of last wave done: all %.2f us; within an XCD, median over XCDs %.2f us; between the XCDs' medians %.2f us"
+              % (t4[has].max() - t4[has].min(), np.median([t4[has & (xcc == x)].max() - t4[has & (xcc == x)].min() for x in range(8) if (has & (xcc == x)).any()]),
+                 np.ptp([np.median(t4[has & (xcc == x)]) for x in range(8) if (has & (xcc == x)).any()])))
     order = np.argsort(-t4)
     print("   slowest: " + ", ".join("%d: %.1f" % (i, t4[i]) for i in order[:16]))
     print("   fastest: " + ", ".join("%d: %.1f" % (i, t4[i]) for i in order[-16:]))

@@ -20,6 +20,9 @@
 //                        32 kAblNoSignal  no hand-off to the host
 //                        64 kAblNoMul     probability domain: the table rows are read, the products not multiplied
 //                       128 kAblNoRowLoads  probability domain: the steps are made up in registers, no loads of the lists
+//   VB2_SPLIT_FAST=mask the short head and tail of a split launch (eval_body, SPLIT), each part on its own for A/B builds (default: all):
+//                         1 the tables are built from records and alphas requested at kernel entry, not from the staged copies
+//                         2 one arrival ticket per share of the point groups: each share's last workgroup adds up that share's points
 #ifndef VB2_KERNEL_DEBUG_H_
 #define VB2_KERNEL_DEBUG_H_
 
@@ -35,6 +38,9 @@
 #ifndef VB2_CTRL_PRIO
 #define VB2_CTRL_PRIO 3         // the control wave's priority during its tile-phase work
 #endif
+#ifndef VB2_SPLIT_FAST
+#define VB2_SPLIT_FAST 3
+#endif
 #ifndef VB2_STAMP_ROUND
 #define VB2_STAMP_ROUND 0
 #endif
@@ -42,6 +48,7 @@
 namespace vb2 {
 constexpr int kAblNoMap = 1, kAblNoTable = 2, kAblNoItems = 4, kAblNoReads = 8, kAblNoEpi = 16, kAblNoSignal = 32, kAblNoMul = 64, kAblNoRowLoads = 128;
 constexpr int kAblate = VB2_ABLATE;
+constexpr int kSplitFast = VB2_SPLIT_FAST;
 }  // namespace vb2
 
 #ifdef VB2_WITH_STAMPS

@@ -39,7 +39,8 @@ constexpr int kPdPairSample = 128;         // markers of the sample on which the
 constexpr double kPdMaxBound = 900.0;      // binary orders of magnitude a marker's likelihood may lie below 1 at most (context.cpp:
                                            // its (het, het) term's, a lower bound of the likelihood that no alpha or PC changes)
 // d_ticket of launch_llk_eval: kTicketWords zero-initialised unsigned ints -- [0, kTicketScratchWord) the arrival tickets of a
-// launch's passes (llk_eval_passes_kernel; a plain launch uses [0]), two words from kTicketScratchWord on a scratch flag
+// launch's passes (llk_eval_passes_kernel; a plain launch uses [0]; a split launch of `ways` shares uses [0, ways) for the
+// shares and [ways] to count the shares that are added up), two words from kTicketScratchWord on a scratch flag
 constexpr int kTicketScratchWord = 8, kTicketWords = 16;
 constexpr int kInlinePointDoubles = 96;    // parameter rows that travel as kernel arguments (768 B)
 

@@ -594,6 +594,15 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
     unsigned long long* stamps = (VB2_STAMPS_OF(L) && stamp_this) ? VB2_STAMPS_OF(L) + (size_t)blk * 8 : nullptr;
 #endif
     if (stamps && tid == 0) { stamps[0] = wall_clock64(); stamps[4] = 0; }
+    if constexpr (SPLIT != 0) {
+        // (word 7 = 1 + the id of the XCD this workgroup runs on, for the finishing spread by XCD -- tools/stamps.py; not in the
+        // workgroups 0, 20 and 21, whose word 7 the search rounds' accumulated figures use)
+        if (stamps && tid == 0 && blk != 0u && blk != 20u && blk != 21u) {
+            unsigned int xcc;
+            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+            stamps[7] = 1ull + (xcc & 15u);
+        }
+    }
 
     // A workgroup that owns no tiles (the resident kernel's extra workgroup for the control wave: Hook::collect_only): nothing of
     // the evaluation -- its hook wave does its work, then all of it collects the tile workgroups' sums below.
@@ -620,6 +629,29 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
         while (__hip_atomic_load(soft_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < soft_gen) __builtin_amdgcn_s_sleep(1);
         asm volatile("" ::: "memory");
     };
+    // SPLIT: a thread's table entries need its record and the alphas of its groups, nothing else -- requested straight from
+    // global memory here, in one burst with the staging loads below, so that the table is built from registers and does not
+    // wait at a barrier for the staged rows and records to be read back (the resident kernel's early_table, for launches of
+    // many groups; kSplitFast & 1).  The same numbers into the same expressions.
+    constexpr bool SPLIT_EARLY = SPLIT != 0 && (kSplitFast & 1) != 0;
+    constexpr int kTabSide = 3;                       // groups whose entries a thread builds side by side (see the table loop)
+    const int ntab_split = (kAblate & kAblNoTable) ? 0 : (PD ? L.num_prim - L.num_pair : L.num_prim) * 6 * NP;
+    auto table_inputs = [&](int e, int g0, double2& rec_o, double* al_o) {
+        const int pi = e / (6 * NP);
+        const int bb = (e - pi * (6 * NP)) / 6;
+        rec_o = L.prim[pi];
+#pragma unroll
+        for (int u = 0; u < kTabSide; ++u) {
+            const int ge = g0 + u < ngrp ? g0 + u : ngrp - 1;
+            const int b = ge * NP + bb;
+            const int idx = (p_off + b < num_valid ? p_off + b : num_valid - 1) * stride + 2 * k;
+            al_o[u] = (kAblate & kAblNoMap) ? 0.01 * (double)(1 + idx % 7) : points[idx];
+        }
+    };
+    double2 tin_rec = make_double2(0.0, 0.0);
+    double tin_al[kTabSide] = {0.0, 0.0, 0.0};
+    if constexpr (SPLIT_EARLY)
+        if (ptid < ntab_split) table_inputs(ptid, 0, tin_rec, tin_al);
     if (ptid == 0) *queue = (unsigned int)(nwave - (hook_blk ? 1 : 0));      // waves start on tiles 0..nwave-1
     // parameter rows -> LDS with one coalesced load (they may live in mapped host memory)
     for (int e = ptid; e < NPT * stride; e += pnthread) {
@@ -660,8 +692,8 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
     // for the copies above: the table needs the alphas only, and takes them from the staged rows (-0.6 us per
     // round; the same for launches whose rows come with the kernel arguments: no gain, not kept).
     const bool early_table = lds_rows != nullptr && !staged;
-    if (!early_table) prologue_sync();
-    if (stamps && (soft ? ptid : tid) == 0) stamps[1] = wall_clock64();
+    if (!early_table && !SPLIT_EARLY) prologue_sync();
+    if (stamps && (soft ? ptid : tid) == 0) stamps[1] = wall_clock64();      // (SPLIT_EARLY: the staging stores are issued, nothing waited for)
 
     // ---- per-alpha table, off-diagonal pairs only (h:213-229) ----
     // Class alt is class ref with the genotypes mirrored (g -> 2-g, h:164-177): the entry of
@@ -673,6 +705,52 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
     // that their long dependent logarithm chains overlap)
     const uint32_t ltab_addr = lds_byte_addr(ltab);
     const int num_single = PD ? L.num_prim - L.num_pair : L.num_prim;
+    if constexpr (SPLIT_EARLY) {
+        // (the loop below on inputs that are in registers: the next step's are requested before this step's entries are computed)
+        int e = ptid, g0 = 0;
+        while (e < ntab_split) {
+            int e_n = e, g0_n = g0 + kTabSide;
+            if (g0_n >= ngrp) {
+                g0_n = 0;
+                e_n = e + pnthread;
+            }
+            double2 rec_n = tin_rec;
+            double al_n[kTabSide] = {tin_al[0], tin_al[1], tin_al[2]};
+            if (e_n < ntab_split) table_inputs(e_n, g0_n, rec_n, al_n);
+            const int pi = e / (6 * NP);
+            const int bp = e - pi * (6 * NP);
+            const int bb = bp / 6, p = bp - bb * 6;
+            (void)bb;
+            const uint32_t pr = (uint32_t)__double_as_longlong(tin_rec.y);
+            const int dc = (int)(pr & 0xffffu), twin = (int)(pr >> 16);
+            int g1, g2;
+            pair_of(p, g1, g2);
+            double v3[kTabSide], r3[kTabSide];
+            double* cell3[kTabSide];
+#pragma unroll
+            for (int u = 0; u < kTabSide; ++u) {
+                const int ge = g0 + u < ngrp ? g0 + u : ngrp - 1;      // (past the last group: the last one again, the same values)
+                v3[u] = prob_entry(tin_al[u], tin_rec.x, g1, g2);
+                r3[u] = v3[u];
+                cell3[u] = tab + (size_t)ge * nrow * RS + dc * RS + bp;
+                *cell3[u] = r3[u];
+            }
+            const int kq = twin & 0xff, pstride = RS * (int)(int8_t)(twin >> 8);
+            for (int n = 1; n < kq; ++n) {
+#pragma unroll
+                for (int u = 0; u < kTabSide; ++u) {
+                    r3[u] *= v3[u];
+                    cell3[u] += pstride;
+                    *cell3[u] = r3[u];
+                }
+            }
+            tin_rec = rec_n;
+#pragma unroll
+            for (int u = 0; u < kTabSide; ++u) tin_al[u] = al_n[u];
+            e = e_n;
+            g0 = g0_n;
+        }
+    } else
     for (int e = ptid; e < ((kAblate & kAblNoTable) ? 0 : num_single * 6 * NP); e += pnthread) {
         const int pi = e / (6 * NP);
         const int bp = e - pi * (6 * NP);
@@ -1626,6 +1704,14 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
         if (tid < NPT) partials[(size_t)tid * nblk + blk] = red[tid];
         return;
     }
+    // SPLIT: one arrival ticket per share of the point groups, d_ticket[0 .. NVS) -- see below; the host's flag goes up behind the
+    // LAST share's results: the shares' finalising workgroups are counted at d_ticket[NVS] the way a cohort step's samples are
+    constexpr bool SPLIT_CLASS = SPLIT != 0 && (kSplitFast & 2) != 0;
+    unsigned int* const my_ticket = SPLIT_CLASS && ticket ? ticket + blk % (uint32_t)NVS : ticket;
+    if constexpr (SPLIT_CLASS) {
+        batch_done = ticket ? ticket + NVS : nullptr;
+        batch_active = (unsigned int)NVS;
+    }
     if (tag == 0) {
         // ---- single-launch mode A (large batches): the last workgroup to arrive sums all partials ----
         // Hand-off through 8-byte agent-scope atomics on both sides (write-through stores,
@@ -1636,13 +1722,37 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
             __hip_atomic_store(&partials[(size_t)(p_off + bl) * nblk + (vb0 + (uint32_t)vsb * vstep)], red[tid],
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
+        unsigned int* last_flag = queue;                                    // the queue is drained
+        if constexpr (SPLIT_CLASS) {
+            // One ticket per share j = blk % NVS of the point groups: the nblk / NVS workgroups of a share hold, between them, every
+            // virtual block's sum of that share's points, so the share's last arriver adds up ITS points the moment its share is
+            // complete -- a third of the arrivals on each counter, a third of the reload for each of three workgroups side by side.
+            // A share's sums are all stored by wave 0 when they fit a wave (48 of a 48-point launch): that wave waits for its own
+            // stores, draws the ticket behind them, and the workgroup meets at ONE barrier.
+            if (NVS * NPT <= 64) {
+                if (wave == 0) {
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    if (lane == 0) {
+                        const unsigned int t = __hip_atomic_fetch_add(my_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        *last_flag = (t == nblk / (uint32_t)NVS - 1) ? 1u : 0u;
+                    }
+                }
+            } else {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+                if (tid == 0) {
+                    const unsigned int t = __hip_atomic_fetch_add(my_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    *last_flag = (t == nblk / (uint32_t)NVS - 1) ? 1u : 0u;
+                }
+            }
+        } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        unsigned int* last_flag = queue;                                    // the queue is drained
         if (tid == 0) {
             const unsigned int t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED,
                                                           __HIP_MEMORY_SCOPE_AGENT);
             *last_flag = (t == nblk - 1) ? 1u : 0u;
+        }
         }
         __syncthreads();
         if (*last_flag == 0u) return;
@@ -1650,8 +1760,11 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
         const int nbt = (int)nblk;
         // (a wave's points side by side -- three of a 48-point launch: their loads, each a trip to memory, are in flight
         // together, and so are their butterflies; every point's sum in the order it always had)
-        constexpr int kSide = 3;
-        for (int b0 = wave; b0 < num_valid; b0 += kSide * nwave) {
+        // (SPLIT_CLASS: the points [pt_lo, pt_hi) of this workgroup's share, one per wave of a 48-point launch)
+        constexpr int kSide = SPLIT_CLASS ? 1 : 3;
+        const int pt_lo = SPLIT_CLASS ? p_off : 0;
+        const int pt_hi = SPLIT_CLASS ? (p_off + NPT < num_valid ? p_off + NPT : num_valid) : num_valid;
+        for (int b0 = pt_lo + wave; b0 < pt_hi; b0 += kSide * nwave) {
             double s[kSide];
 #pragma unroll
             for (int u = 0; u < kSide; ++u) s[u] = 0;
@@ -1660,7 +1773,7 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
 #pragma unroll
                 for (int u = 0; u < kSide; ++u) {
                     const int b = b0 + u * nwave;
-                    const double* p = partials + (size_t)(b < num_valid ? b : b0) * nbt;
+                    const double* p = partials + (size_t)(b < pt_hi ? b : b0) * nbt;
 #pragma unroll
                     for (int q = 0; q < 8; ++q) {
                         const int i = base + q * 64 + lane;
@@ -1677,10 +1790,10 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
             for (int u = 0; u < kSide; ++u) {
                 const int b = b0 + u * nwave;
                 const double t = wave_sum(s[u]);
-                if (lane == 0 && b < num_valid) put_result(b, t);
+                if (lane == 0 && b < pt_hi) put_result(b, t);
             }
         }
-        if (tid == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) __hip_atomic_store(my_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     } else {
     // ---- single-launch mode B (small batches, resident search): workgroup 0 collects all partials ----
     // Every workgroup publishes its NPT sums plus a check word (XOR of position-dependent word

@@ -125,3 +125,52 @@ def test_derivs_entry_is_declared_and_exported():
     assert "vb2_llk_derivs_batch" in _abi.SYMBOLS
     assert hasattr(_abi.lib(), "vb2_llk_derivs_batch")
     assert _abi.lib().vb2_abi_version() == 7
+
+
+@pytest.mark.parametrize("shape", [(3000, 30, 4, {}), (800, 650, 2, {}), (1500, 30, 2, dict(q_lo=0, q_hi=93)),
+                                   (1500, 30, 2, dict(missing_frac=0.3))])
+def test_restatement_in_80_bits_agrees_with_float64(shape):
+    """The same code in np.longdouble and in float64: outputs of the precision asked for (no silent drop to double), the
+    LLK to 1e-14, every entry to (1e-12 + 1e-15 / min(alpha, 1 - alpha)) of its condition sum -- double rounding, times
+    the cancellation inside a marker (G1' W: terms of order 1 that cancel to order alpha) that S_e does not count."""
+    assert np.finfo(np.longdouble).eps < 2e-19              # the x87 80-bit format: 64 bits of mantissa
+    M, depth, k, kw = shape
+    d = vb.synth.make_pileup(M, mean_depth=depth, num_pc=k, alpha_true=0.05, seed=44, **kw)
+    c64, c80 = deriv_ref.Counts(d), deriv_ref.Counts(d, np.longdouble)
+    assert c80.N.dtype == np.longdouble and c80.ud.dtype == np.longdouble and c64.N.dtype == np.float64
+    rng = np.random.default_rng(4)
+    for a in (1e-6, 0.03, 0.3, 0.5, 0.97):
+        pc1, pc2 = rng.normal(0, 0.01, k), rng.normal(0, 0.01, k)
+        for c, T in ((c64, np.float64), (c80, np.longdouble)):
+            out = deriv_ref.derivs_cond(c, pc1, pc2, a)
+            assert all(np.asarray(x).dtype == np.dtype(T) for x in out)
+            assert deriv_ref.marker_terms(c, pc1, pc2, a).dtype == np.dtype(T)
+        ref = deriv_ref.reference(c64, c80, pc1, pc2, a)
+        assert abs(float(ref["l64"] - ref["l80"])) <= 1e-14 * abs(float(ref["l80"]))
+        bound = 1e-12 + 1e-15 / min(a, 1 - a)
+        for name, (dev, dev64, tol) in deriv_ref.block_devs(ref, ref["g64"], ref["h64"]).items():
+            assert dev == dev64 <= bound, (name, a, dev64, bound)
+            assert tol == max(32 * dev64, 1e-13)
+        # a condition sum is never below the entry it belongs to
+        assert np.all(ref["sg"] >= np.abs(ref["g80"]) * (1 - 1e-15)) and np.all(ref["sh"] >= np.abs(ref["h80"]) * (1 - 1e-15))
+
+
+def test_condition_sums_at_alpha_zero_and_one():
+    """At alpha = 0 nothing depends on pc1 (at alpha = 1: on pc2): those entries are 0 up to rounding, S_e with them, and
+    the reference measures those blocks in the sums taken inside the markers -- which are never below S_e."""
+    k = 2
+    d = vb.synth.make_pileup(2000, mean_depth=30, num_pc=k, alpha_true=0.05, seed=10)
+    c64, c80 = deriv_ref.Counts(d), deriv_ref.Counts(d, np.longdouble)
+    pc1, pc2 = np.array([0.01, -0.02]), np.array([0.03, 0.01])
+    for a, dead in ((0.0, slice(0, k)), (1.0, slice(k, 2 * k))):
+        ref = deriv_ref.reference(c64, c80, pc1, pc2, a)
+        _, _, _, sg, sh = deriv_ref.derivs_cond(c80, pc1, pc2, a)
+        gi, hi = deriv_ref.derivs_cond(c80, pc1, pc2, a, inner=True)
+        assert np.all(gi[:2 * k] >= sg[:2 * k]) and np.all(hi[:2 * k, :2 * k] >= sh[:2 * k, :2 * k])
+        assert np.max(np.abs(ref["g80"][dead])) <= 1e-12 * np.max(gi[dead])          # 0 up to rounding
+        assert np.array_equal(ref["sg"][dead], gi[dead]) and np.array_equal(ref["sh"][dead, dead], hi[dead, dead])
+        for name, (_, dev64, _) in deriv_ref.block_devs(ref, ref["g64"], ref["h64"], alpha_entries=False).items():
+            assert dev64 <= 1e-12, (name, a, dev64)
+    gi, hi = deriv_ref.derivs_cond(c80, pc1, pc2, 0.3, inner=True)
+    _, _, _, sg, sh = deriv_ref.derivs_cond(c80, pc1, pc2, 0.3)
+    assert np.all(gi >= sg) and np.all(hi >= sh)

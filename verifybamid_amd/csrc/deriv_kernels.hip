@@ -6,7 +6,10 @@
 //   * llk_derivs_marker_kernel: one workgroup per (stripe of micro-tiles, point).  It builds the point's derivative table
 //     in LDS -- per table row and off-diagonal genotype pair {value, d, d^2} with d = dp/dalpha / p -- and one thread per
 //     marker walks the marker's runs (log domain: value = log p, a run of n reads adds n x each entry) or steps
-//     (probability domain: value = P^n, the row carries n d and n d^2; window rows the sums of their factors').  The
+//     (probability domain: value = P^n, the row carries n d and n d^2; window rows the sums of their factors').  In the
+//     log domain a row also carries log u_g of the three diagonal pairs: the context's diagonal constants are
+//     probabilities, exp(c_other + D[g]), which past ~1 000 reads are subnormal doubles with few bits left (or 0) --
+//     good enough for L itself, whose value the reference defines that way, but not for the ratios W / L.  The
 //     epilogue forms the marker's nine derivatives of L = GF1' W GF2 and writes them with log L to the scratch
 //     [point][kDerivVals][m_pad].
 //   * llk_derivs_reduce_kernel: one workgroup per (output, point) sums a scalar over the markers with the sorted panel
@@ -23,7 +26,9 @@ namespace {
 
 constexpr int kThreads = 256;                     // 16 micro-tiles of 16 markers per pass of a workgroup
 constexpr int kEntry = 3;                         // {value, d, d^2} per (row, pair)
-constexpr int kRowDoubles = 6 * kEntry;
+constexpr int kPairDoubles = 6 * kEntry;
+constexpr int kRowDoublesPd = kPairDoubles;       // probability domain: the six off-diagonal pairs
+constexpr int kRowDoublesLog = kPairDoubles + 3;  // log domain: and log u_g of the diagonal pairs (g, g)
 constexpr double kMinAf = 0.00005, kMaxAf = 0.99995;   // h:94-95
 
 // off-diagonal genotype pairs, in the reference's (g1 outer, g2 inner) order (as llk_kernels.hip numbers them)
@@ -70,7 +75,8 @@ template <bool PD>
 __global__ void __launch_bounds__(kThreads)
 llk_derivs_marker_kernel(const DeviceLayout L, const double* __restrict__ points, double* __restrict__ out)
 {
-    extern __shared__ __attribute__((aligned(16))) double tab[];      // [nrow][6 pairs][kEntry]
+    extern __shared__ __attribute__((aligned(16))) double tab[];      // [nrow][6 pairs][kEntry] (+ [3] in the log domain)
+    constexpr int kRowDoubles = PD ? kRowDoublesPd : kRowDoublesLog;
     const int tid = threadIdx.x;
     const int pt = blockIdx.y;
     const int k = L.num_pc, stride = 2 * k + 1;
@@ -119,6 +125,19 @@ llk_derivs_marker_kernel(const DeviceLayout L, const double* __restrict__ points
             }
         }
     }
+    if constexpr (!PD) {
+        // the diagonal pairs: p = alpha u_g + (1 - alpha) u_g = u_g whatever alpha; an alt code reads the genotype mirrored
+        for (int e = tid; e < num_single * 3; e += kThreads) {
+            const int pi = e / 3, g = e - pi * 3;
+            const double2 rec = L.prim[pi];
+            const uint32_t pr = (uint32_t)__double_as_longlong(rec.y);
+            const int first = (int)(pr & 0xffffu), twin = (int)(pr >> 16);
+            const double p_err = fabs(rec.x), p_ok = 1.0 - p_err;
+            const double lu = log((double)g * (1.0 / 6.0) * p_err + (1.0 - 0.5 * (double)g) * p_ok);
+            if (first < nrow) tab[(size_t)first * kRowDoubles + kPairDoubles + (rec.x < 0.0 ? 2 - g : g)] = lu;
+            if (twin != 0xffff && twin < nrow) tab[(size_t)twin * kRowDoubles + kPairDoubles + (2 - g)] = lu;
+        }
+    }
     for (int e = tid; e < kRowDoubles; e += kThreads)           // padding row: P = 1 (log domain: 0), no derivative
         tab[(size_t)L.num_code * kRowDoubles + e] = (PD && e % kEntry == 0) ? 1.0 : 0.0;
     if constexpr (PD) {
@@ -157,8 +176,9 @@ llk_derivs_marker_kernel(const DeviceLayout L, const double* __restrict__ points
             continue;
         }
         const uint2 rec = L.mt_rec[mt];
-        double acc[6], a1[6], a2[6];
+        double acc[6], a1[6], a2[6], dacc[3];
         for (int p = 0; p < 6; ++p) { acc[p] = PD ? 1.0 : L.ediag[pos]; a1[p] = 0.0; a2[p] = 0.0; }
+        for (int g = 0; g < 3; ++g) dacc[g] = PD ? 0.0 : L.ediag[pos];     // log domain: c_other + D[g], summed here
         if constexpr (PD) {
             // {ref steps | all steps << 16}; a step = a 16-bit byte offset of its row (+ kPdAltOffset for class alt), two per word
             const uint32_t s1 = rec.y & 0xffffu, s2 = rec.y >> 16;
@@ -195,6 +215,8 @@ llk_derivs_marker_kernel(const DeviceLayout L, const double* __restrict__ points
                         a1[p] = fma(n, t[p * kEntry + 1], a1[p]);
                         a2[p] = fma(n, t[p * kEntry + 2], a2[p]);
                     }
+#pragma unroll
+                    for (int g = 0; g < 3; ++g) dacc[g] = fma(n, t[kPairDoubles + g], dacc[g]);
                 }
             }
         }
@@ -225,8 +247,7 @@ llk_derivs_marker_kernel(const DeviceLayout L, const double* __restrict__ points
         if constexpr (!PD) {
             double amax = -__builtin_huge_val();
             for (int p = 0; p < 6; ++p) amax = acc[p] > amax ? acc[p] : amax;
-            for (int g = 0; g < 3; ++g)
-                if (W[g][g] > 0.0) { const double lw = log(W[g][g]); amax = lw > amax ? lw : amax; }
+            for (int g = 0; g < 3; ++g) amax = dacc[g] > amax ? dacc[g] : amax;
             scale = amax > -__builtin_huge_val() && amax < __builtin_huge_val() ? amax : 0.0;
         }
         double Wu[3][3];
@@ -248,7 +269,7 @@ llk_derivs_marker_kernel(const DeviceLayout L, const double* __restrict__ points
             WB[g1][g2] = ws * (a1[p] * a1[p] - a2[p]);
         }
         if constexpr (!PD)
-            for (int g = 0; g < 3; ++g) W[g][g] = W[g][g] > 0.0 ? exp(log(W[g][g]) - scale) : 0.0;
+            for (int g = 0; g < 3; ++g) W[g][g] = exp(dacc[g] - scale);     // (Wu keeps the context's constant: L as evaluated)
         for (int g1 = 0; g1 < 3; ++g1)
             for (int g2 = 0; g2 < 3; ++g2) lk += Wu[g1][g2] * G1[g1] * G2[g2];
         double v[kDerivVals];
@@ -369,7 +390,7 @@ hipError_t launch_llk_derivs(const DeviceLayout& L, int num_point, const double*
     if (num_point <= 0) return hipSuccess;
     if (num_point > kDerivChunk) return hipErrorInvalidValue;
     const int nrow = L.num_code + 1;
-    const size_t shmem = (size_t)nrow * kRowDoubles * sizeof(double);
+    const size_t shmem = (size_t)nrow * (L.pd ? kRowDoublesPd : kRowDoublesLog) * sizeof(double);
     const int ntile_grp = (L.num_mt + 15) / 16;
     // about four workgroups per CU over the whole launch; each walks a stripe of 16-tile groups with one table
     int gx = (4 * (L.num_cu > 0 ? L.num_cu : 1) + num_point - 1) / num_point;

@@ -238,7 +238,21 @@ int ctx_interval(Context* ctx, const vb2_model& model_in, const vb2_estimate& es
             for (const Pt& p : pts)
                 if (std::fabs(p.f - f) < dist) { dist = std::fabs(p.f - f); u = p.u; }
             double best = 0;
-            if (int rc = prof.maximise(side ? 1 - f : f, &u, &best)) return rc;
+            const double a = side ? 1 - f : f;
+            if (int rc = prof.maximise(a, &u, &best)) return rc;
+            // The LLK has several local maxima in the contaminant's PCs (the AF clamps; hardly identified near alpha = 0),
+            // and a chain of warm starts can end on a lower one than the estimate's own PCs give at this alpha: then the
+            // climb starts from those as well, and the better end counts.
+            if (!pts.empty() && fr.nu > 0) {
+                Eval e0;
+                if (int rc = prof.eval(u0, a, &e0)) return rc;
+                if (e0.f > best) {
+                    std::vector<double> v = u0;
+                    double b2 = 0;
+                    if (int rc = prof.maximise(a, &v, &b2)) return rc;
+                    if (b2 > best) { best = b2; u = v; }
+                }
+            }
             pts.push_back(Pt{f, best, u});
             ++out->num_profile;
             if (best > llk_max) llk_max = best;
@@ -314,7 +328,13 @@ int ctx_interval(Context* ctx, const vb2_model& model_in, const vb2_estimate& es
         for (int j = 0; j < k; ++j) wald(3, j, v1[j], se1[j]);
     } else if (heter) {
         for (int j = 0; j < k; ++j) wald(1, j, v1[j], se1[j]);
-        if (fr.pc2_free) for (int j = 0; j < k; ++j) wald(2, j, v2[j], se2[j]);
+        if (fr.pc2_free) {
+            for (int j = 0; j < k; ++j) wald(2, j, v2[j], se2[j]);
+        } else if (swapped) {
+            // --FixPC at alpha >= 0.5: the swap prints the fixed values as the contaminant's PC1, PC2 (NA above) and the
+            // free ones as the intended sample's -- those get their rows, so that no free parameter's SE is dropped
+            for (int j = 0; j < std::min(k, 2); ++j) wald(2, j, v2[j], se2[j]);
+        }
     }
     out->num_row = r;
     out->num_launch = prof.launches;

@@ -608,14 +608,17 @@ kaf = np.clip(rng.uniform(0, 1, size=M), 0.01, 0.99)
 out.append(_flatten_digest(vb.PileupData(2, dd.ud, dd.means, off, bases, quals, alt, kaf, 30.0, 0.0, True, {})))
 print(json.dumps(out))
 """ % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__)))
-    res = []
-    for env_extra in ({"VB2_FLATTEN_THREADS": "1"}, {"VB2_FLATTEN_THREADS": "3"}, {"VB2_FLATTEN_THREADS": "8"}):
-        p = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env_extra), capture_output=True, text=True,
-                           timeout=600)
-        assert p.returncode == 0, p.stderr[-2000:]
-        res.append(json.loads(p.stdout.strip().splitlines()[-1]))
-    assert res[0] == res[1] == res[2]
-    assert len(set(res[0])) == len(res[0])                 # (six different inputs, six different digests)
+    # ... in the default layout, in the run-word layout (VB2_PD=0: its multi-threaded pack and schedule_tile pass) and in the
+    # probability domain without the pair windows
+    for layout in ({}, {"VB2_PD": "0"}, {"VB2_PD_PAIRS": "0"}):
+        res = []
+        for env_extra in ({"VB2_FLATTEN_THREADS": "1"}, {"VB2_FLATTEN_THREADS": "3"}, {"VB2_FLATTEN_THREADS": "8"}):
+            p = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **layout, **env_extra), capture_output=True,
+                               text=True, timeout=600)
+            assert p.returncode == 0, p.stderr[-2000:]
+            res.append(json.loads(p.stdout.strip().splitlines()[-1]))
+        assert res[0] == res[1] == res[2], layout
+        assert len(set(res[0])) == len(res[0]), layout     # (six different inputs, six different digests)
 
 
 def test_run_scheduling_only_reorders_the_runs_of_a_marker():

@@ -30,6 +30,10 @@ int flatten_dry_run(const vb2_input* in, double* ms);
 // ... and a digest of what it produced (run words, tile records, panel rows, per-marker constants, dictionary): lets a
 // test hold two ways of flattening -- the AVX2 classification and the scalar statements -- to the same bytes without a device.
 int flatten_digest(const vb2_input* in, unsigned long long* digest);
+// A dry run of vb2_ctx_create: the host half only, no device, no context; digest (may be null) gets flatten_digest's value.
+struct DryRun {
+    unsigned long long* digest;
+};
 // The process-wide recycling of device slabs, pinned device-mapped slabs and streams (context.cpp):
 // allocation and release calls cost milliseconds and serialise in the driver.  take: nullptr = none
 // cached, allocate yourself; give: false = cache full, release it yourself.
@@ -90,7 +94,7 @@ public:
     std::vector<uint32_t> h_mt_rows;         // rows per micro-tile (host copy: the schedules are built from it)
     std::vector<uint32_t> h_mt_rec_y;        // probability domain: a tile's {ref steps | all steps << 16} (ensure_codes16: the 8-bit lists)
     static int create(const vb2_input* in, const vb2_options* opt, Context** out);
-    static int create_impl(const vb2_input* in, const vb2_options* opt, Context** out, bool dry);
+    static int create_impl(const vb2_input* in, const vb2_options* opt, Context** out, const DryRun* dry_run);   // null: a real create
     // device pointers, asynchronous on s (nullptr = own stream)
     int eval_device(int num_point, const double* d_points, double* d_llk, hipStream_t s,
                     unsigned long long* done_flag = nullptr, unsigned long long done_seq = 0,

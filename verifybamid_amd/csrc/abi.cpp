@@ -264,39 +264,15 @@ int vb2_debug_lockstep_optimize(vb2_eval_fn eval, void* user, int32_t num_pc, co
     try {
         vb2::FiberGang gang(runs, 4);
         std::vector<int> rcs(runs, 0);
-        std::vector<double> p1, p2, al, vals;
         auto body = [&](int i) {
-            try {
-                vb2::Estimator est(num_pc, vb2::FiberGang::eval_cb, gang.user(i));
-                vb2::apply_model(est, *model);
-                est.speculate = speculate;
-                est.start_index = i;
-                est.start_seed = 1;
-                rcs[i] = est.OptimizeLLK();
-                vb2::fill_estimate(est, &out[i]);
-            } catch (...) {
-                rcs[i] = VB2_ERR_INVALID;
-            }
+            vb2::FiberGang::Search cfg;
+            cfg.model = model;
+            cfg.speculate = speculate;
+            cfg.start_index = i;
+            cfg.start_seed = 1;
+            rcs[i] = gang.search(i, cfg, "vb2_debug_lockstep_optimize", &out[i]);
         };
-        auto step = [&](std::vector<vb2::FiberGang::Request>& req) {
-            p1.clear(); p2.clear(); al.clear();
-            for (const auto& r : req) {
-                if (r.n <= 0) continue;
-                p1.insert(p1.end(), r.p1, r.p1 + (size_t)r.n * num_pc);
-                p2.insert(p2.end(), r.p2, r.p2 + (size_t)r.n * num_pc);
-                al.insert(al.end(), r.a, r.a + r.n);
-            }
-            vals.resize(al.size());
-            if (const int rc = eval(user, (int32_t)al.size(), p1.data(), p2.data(), al.data(), vals.data())) return rc;
-            size_t o = 0;
-            for (auto& r : req) {
-                if (r.n <= 0) continue;
-                std::memcpy(r.out, &vals[o], sizeof(double) * r.n);
-                o += (size_t)r.n;
-            }
-            return 0;
-        };
-        const int rc = gang.run(num_pc, body, step);
+        const int rc = gang.run(num_pc, body, vb2::FiberGang::concat_step(num_pc, eval, user));
         if (num_step) *num_step = gang.steps;
         if (rc) return rc < 0 ? VB2_ERR_INVALID : rc;
         for (int i = 0; i < runs; ++i)
@@ -438,20 +414,15 @@ int vb2_ctx_optimize_llk_ex(vb2_ctx* ctx, const vb2_model* model, const vb2_sear
     }
     vb2::Context* c = ctx->impl;
     const int k = c->num_pc;
-    auto configure = [&](vb2::Estimator& est, int index) {
-        vb2::apply_model(est, *model, c->L.known_af != nullptr);
-        est.line_search = line;
-        est.start_index = index;
-        est.start_seed = opts ? opts->seed : 0u;
-        if (opts && opts->start_sd > 0) est.start_sd = opts->start_sd;
-        if (index > 0) est.notices = false;  // (the reference's phase lines once, for its own start)
-    };
     try {
         if (S == 1) {
             // one run, Brent's single-point evaluations served by the resident kernel
             const bool resident = c->resident_begin();
             vb2::Estimator est(k, ctx_eval_cb, c);
-            configure(est, 0);
+            vb2::apply_model(est, *model, c->L.known_af != nullptr);
+            est.line_search = line;
+            est.start_seed = opts ? opts->seed : 0u;
+            if (opts && opts->start_sd > 0) est.start_sd = opts->start_sd;
             const int rc = est.OptimizeLLK();
             if (resident) c->resident_end();
             if (rc) return rc;
@@ -463,43 +434,20 @@ int vb2_ctx_optimize_llk_ex(vb2_ctx* ctx, const vb2_model* model, const vb2_sear
         vb2::FiberGang gang(S, 4);
         std::vector<vb2_estimate> ests(S);
         std::vector<int> rcs(S, 0);
-        std::vector<double> p1, p2, al, out;
+        vb2_model quiet = *model;              // (the reference's phase lines once, for its own start)
+        quiet.notices = 0;
         auto body = [&](int i) {
-            try {
-                vb2::Estimator est(k, vb2::FiberGang::eval_cb, gang.user(i));
-                configure(est, i);
-                est.speculate = S * 4 <= vb2::kMaxPointsPerLaunch ? 4 : 2;     // the whole step in one launch
-                rcs[i] = est.OptimizeLLK();
-                vb2::fill_estimate(est, &ests[i]);
-            } catch (const std::bad_alloc&) {
-                rcs[i] = VB2_ERR_NOMEM;
-            } catch (const std::exception& e) {
-                set_error(e.what());
-                rcs[i] = VB2_ERR_INVALID;
-            } catch (...) {
-                set_error("vb2_ctx_optimize_llk_ex: unknown exception in a search");
-                rcs[i] = VB2_ERR_INVALID;
-            }
+            vb2::FiberGang::Search cfg;
+            cfg.model = i > 0 ? &quiet : model;
+            cfg.data_has_known_af = c->L.known_af != nullptr;
+            cfg.speculate = S * 4 <= vb2::kMaxPointsPerLaunch ? 4 : 2;         // the whole step in one launch
+            cfg.line_search = line;
+            cfg.start_index = i;
+            cfg.start_seed = opts ? opts->seed : 0u;
+            cfg.start_sd = opts ? opts->start_sd : 0;
+            rcs[i] = gang.search(i, cfg, "vb2_ctx_optimize_llk_ex", &ests[i]);
         };
-        auto step = [&](std::vector<vb2::FiberGang::Request>& req) {
-            p1.clear(); p2.clear(); al.clear();
-            for (const auto& r : req) {
-                if (r.n <= 0) continue;
-                p1.insert(p1.end(), r.p1, r.p1 + (size_t)r.n * k);
-                p2.insert(p2.end(), r.p2, r.p2 + (size_t)r.n * k);
-                al.insert(al.end(), r.a, r.a + r.n);
-            }
-            out.resize(al.size());
-            if (const int rc = c->eval_host((int)al.size(), p1.data(), p2.data(), al.data(), out.data())) return rc;
-            size_t o = 0;
-            for (auto& r : req) {
-                if (r.n <= 0) continue;
-                std::memcpy(r.out, &out[o], sizeof(double) * r.n);
-                o += (size_t)r.n;
-            }
-            return 0;
-        };
-        const int rc = gang.run(k, body, step);
+        const int rc = gang.run(k, body, vb2::FiberGang::concat_step(k, ctx_eval_cb, c));
         if (rc < 0) {
             set_error("vb2_ctx_optimize_llk_ex: getcontext failed");
             return VB2_ERR_INVALID;

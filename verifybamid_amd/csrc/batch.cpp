@@ -29,6 +29,19 @@ namespace vb2 {
 
 namespace {
 constexpr int kSlot = 8;                     // point slots per sample and step (VB2_BATCH_SLOTS)
+// launch shapes of a step: 0 = up to 4 points per sample, 1 = 8 points, 2 = one point, 3 = two
+constexpr int kShapeNp[Batch::kShapes] = {4, 8, 1, 2};
+
+// the layout of a slot that holds no sample (its workgroups leave before they read it)
+DeviceLayout empty_layout(int num_pc, int num_cu)
+{
+    DeviceLayout none;
+    std::memset(&none, 0, sizeof(none));
+    none.num_pc = num_pc;
+    none.row_bytes = kRowBytesWide;
+    none.num_cu = num_cu;
+    return none;
+}
 }
 
 Batch::~Batch()
@@ -99,19 +112,39 @@ int Batch::regroup_bps(int num_cu, int active)
     return b;
 }
 
-namespace {
-constexpr int kSplitFrom = 16;               // a cohort of this many samples is searched as two half-cohorts taking turns
+int search_speculate(int n)
+{
+    // Speculation (amoeba.h) trades device work for fewer dependent steps.  A small cohort's step is
+    // latency-bound and {R, E, C_A, C_R} per iteration pays (2.5 points evaluated per point the
+    // search needs).  A big cohort's step is throughput-bound -- its cost grows with the points in
+    // it, down to the floor of streaming every sample's pileup from HBM once per step (5.7 TB/s
+    // measured: a 1-point step of 32 C3 samples takes 131 us against 236 us with 4 points) -- and
+    // {R, C_R} is the better trade: 1.2 steps per iteration at about half the points.  Same
+    // decisions, same trajectory either way.  Tunables::cohort_speculate = 1|2|4 forces one.
+    constexpr int kPairFrom = 8;
+    const int forced = tunables().cohort_speculate;
+    return forced > 0 ? forced : n < kPairFrom ? 4 : 2;
+}
+
+int search_lanes(int n, bool tuned, int* sizes)
+{
+    constexpr int kSplitFrom = 16;           // a cohort of this many samples is searched as two half-cohorts taking turns
+    const Tunables& tn = tunables();
+    bool split = n >= kSplitFrom;
+    if (tuned && tn.cohort_split >= 0) split = tn.cohort_split != 0 && n >= 2;
+    const int nlane = !split ? 1 : !tuned ? 2 : std::max(2, std::min(std::min(kMaxLanes, tn.cohort_lanes), n));
+    for (int l = 0; l < nlane; ++l) sizes[l] = (int)((long)n * (l + 1) / nlane) - (int)((long)n * l / nlane);
+    return nlane;
 }
 
 int Batch::prepare_for_cohort(Context* c, int group)
 {
     if (group < 1 || c->L.num_mt == 0) return VB2_OK;
-    int lanes[2] = {group, 0};
-    if (group >= kSplitFrom) { lanes[0] = group / 2; lanes[1] = group - group / 2; }
+    int lanes[kMaxLanes];
+    const int nlane = search_lanes(group, false, lanes);
     Schedule sc[kShapes];
     int first_bps = 0;
-    for (int l = 0; l < 2; ++l) {
-        if (lanes[l] <= 0) continue;
+    for (int l = 0; l < nlane; ++l) {
         int bps, bw;
         geometry(c->L.num_cu, lanes[l], c->L.num_mt, c->num_pc, 0, &bps, &bw);
         if (bps == first_bps) continue;
@@ -154,22 +187,18 @@ int Batch::create(const std::vector<Context*>& ctxs, Batch** out, int bps_in)
         b->ctx_.push_back(c);
         // cohort steps stream every sample's run lists from HBM once per step: the 16-bit copy halves
         // those bytes (VB2_COHORT_W16=0: the 32-bit lists, A/B)
-        const bool w16_on = cohort_w16_enabled();
-        if (w16_on && c->L.num_mt > 0)
+        if (cohort_w16_enabled() && c->L.num_mt > 0)
             if (const int rc16 = c->ensure_codes16()) return rc16;
-        if (!w16_on || (c->L.num_mt > 0 && !c->L.codes16)) b->w16_ = false;
         layouts[s] = c->L;
         layouts[s].stamps = nullptr;
-        if (c->L.row_bytes != kRowBytesWide) b->wide_rows_ = false;
         max_mt = std::max(max_mt, c->L.num_mt);
     }
+    b->scan_samples();
     VB2_HIP(hipSetDevice(b->device));
 
     int bps = 1;
     geometry(num_cu, num_sample, max_mt, b->num_pc, bps_in, &bps, &b->block_waves_);
     b->bps_ = bps;
-    // launch shapes of a step: 0 = up to 4 points per sample, 1 = 8 points, 2 = one point, 3 = two
-    static const int kShapeNp[kShapes] = {4, 8, 1, 2};
     for (int sh = 0; sh < kShapes; ++sh) {
         size_t need = 0;
         for (int s = 0; s < num_sample; ++s)
@@ -200,16 +229,22 @@ int Batch::create_slots(int capacity, int device, int num_pc, int num_cu, Batch*
     b->slots_ = true;
     b->strict_shapes = true;
     b->ctx_.assign(capacity, nullptr);
-    DeviceLayout none;
-    std::memset(&none, 0, sizeof(none));
-    none.num_pc = num_pc;
-    none.row_bytes = kRowBytesWide;
-    none.num_cu = num_cu;
-    b->layouts_.assign(capacity, none);
+    b->layouts_.assign(capacity, empty_layout(num_pc, num_cu));
     b->bps_ = std::max(1, num_cu * (kMaxBlockWaves / cohort_waves()) / capacity);
     b->block_waves_ = cohort_waves();         // whatever the samples: a sample's sums must not depend on its neighbours
     *out = b.release();
     return VB2_OK;
+}
+
+void Batch::scan_samples()
+{
+    w16_ = cohort_w16_enabled();
+    wide_rows_ = true;
+    for (const Context* c : ctx_) {
+        if (!c) continue;                                    // (an empty slot)
+        if (c->L.num_mt > 0 && !c->L.codes16) w16_ = false;
+        if (c->L.row_bytes != kRowBytesWide) wide_rows_ = false;
+    }
 }
 
 int Batch::set_slot(int i, Context* c)
@@ -218,7 +253,7 @@ int Batch::set_slot(int i, Context* c)
         set_error("streaming batch: set_slot out of place");
         return VB2_ERR_INVALID;
     }
-    DeviceLayout lay = layouts_[i];
+    DeviceLayout lay = empty_layout(num_pc, layouts_[i].num_cu);
     Schedule sc[kShapes];
     for (int sh = 0; sh < kShapes; ++sh) sc[sh] = Schedule{nullptr, nullptr};
     if (c) {
@@ -230,7 +265,6 @@ int Batch::set_slot(int i, Context* c)
             if (const int rc16 = c->ensure_codes16()) return rc16;
         lay = c->L;
         lay.stamps = nullptr;
-        static const int kShapeNp[kShapes] = {4, 8, 1, 2};
         size_t need[kShapes];
         for (int sh = 0; sh < kShapes; ++sh) need[sh] = std::max(shmem_[sh], eval_shmem_np(lay, kShapeNp[sh], bps_, block_waves_, 1));
         if (need[1] > (size_t)kLdsLimitBytes) {
@@ -239,21 +273,10 @@ int Batch::set_slot(int i, Context* c)
         }
         for (int sh = 0; sh < kShapes; ++sh) shmem_[sh] = need[sh];
         if (const int rc = c->cohort_schedules(bps_, block_waves_, sc, false)) return rc;
-    } else {
-        std::memset(&lay, 0, sizeof(lay));
-        lay.num_pc = num_pc;
-        lay.row_bytes = kRowBytesWide;
-        lay.num_cu = layouts_[i].num_cu;
     }
     ctx_[i] = c;
     layouts_[i] = lay;
-    w16_ = cohort_w16_enabled();
-    wide_rows_ = true;
-    for (int s = 0; s < num_sample; ++s) {
-        if (!ctx_[s]) continue;
-        if (ctx_[s]->L.num_mt > 0 && !ctx_[s]->L.codes16) w16_ = false;
-        if (ctx_[s]->L.row_bytes != kRowBytesWide) wide_rows_ = false;
-    }
+    scan_samples();
     if (!ready_ || !c) return VB2_OK;           // (ensure_resources uploads everything at the first step; an empty slot's
                                                 //  workgroups leave before they read its layout)
     VB2_HIP(hipSetDevice(device));
@@ -368,6 +391,86 @@ int Batch::eval(const int32_t* num_point, const double* pc1, const double* pc2, 
     return eval_end();
 }
 
+// The launches of a step, in order.  A launch runs ONE kind of kernel in ONE wave shape: three rules, one inside the other.
+// 1. Samples of both layouts (a probability-domain context next to one that could not take that layout: deep markers,
+//    quality 0): the probability-domain samples first, then the others.  A sample's values do not depend on its launch.
+// 2. strict_shapes: a step's wave shape follows from the LARGEST request in it, and under the static deal the shape decides
+//    which tiles a wave multiplies together -- so a sample's sums would move in their last bits with what its neighbours
+//    happen to ask for (a new sample's initial simplex, a shrink).  Strict: the requests of 1-2, of 3-4 and of 5-8 points
+//    leave as separate launches (the one- and two-point shapes deal and multiply alike: bit-identical, tested), so a
+//    sample's values depend on its own requests only.  Mixed steps are rare (a sample starts or shrinks in 1-2 % of them):
+//    the most populous class goes last, which is the launch left in flight.  A 5-8 point request of a sample with narrow
+//    table rows is a class of its own, or one such neighbour would change everybody's wave shape.
+// 3. A sample with a very wide dictionary (more than kMaxWideCodes codes) has narrow table rows: 4 points per launch at
+//    most, so a launch of 5-8 points with such a sample in it becomes two of 4, both waited for.  (Where rule 2 applies and
+//    left the launch's group whole, it takes each of the two apart: their requests are of 4 and of 1-4 points.)
+void Batch::plan_step(const int32_t* num_point, std::vector<SubStep>* plan) const
+{
+    typedef std::vector<int32_t> Counts;
+    const size_t S = (size_t)num_sample;
+    auto narrow = [&](size_t s) { return ctx_[s] && ctx_[s]->L.row_bytes != kRowBytesWide; };
+    auto cls_of = [&](int n, size_t s) { return n <= 0 ? -1 : n <= 2 ? 0 : n <= 4 ? 1 : narrow(s) ? 3 : 2; };
+    auto several = [](const int* pop) { return (pop[0] > 0) + (pop[1] > 0) + (pop[2] > 0) + (pop[3] > 0) > 1; };
+    // nearly every step is one launch of num_point as it is: *plan stays empty and nothing is allocated
+    bool any_pd = false, any_log = false, narrow_in = false;
+    int all_pop[4] = {0, 0, 0, 0}, max_n = 0;
+    for (size_t s = 0; s < S; ++s) {
+        if (num_point[s] <= 0) continue;
+        max_n = std::max(max_n, (int)num_point[s]);
+        narrow_in |= narrow(s);
+        ++all_pop[cls_of(num_point[s], s)];
+        if (ctx_[s] && ctx_[s]->L.num_mt > 0) (ctx_[s]->L.pd ? any_pd : any_log) = true;
+    }
+    if (!(any_pd && any_log) && !(strict_shapes && several(all_pop)) && !(max_n > 4 && !wide_rows_ && narrow_in)) return;
+    // rule 2: appends np's classes to *out, the most populous last, and says whether there was more than one
+    auto by_class = [&](Counts np, std::vector<Counts>* out) {
+        int pop[4] = {0, 0, 0, 0}, keep = 0;
+        for (size_t s = 0; s < S; ++s)
+            if (np[s] > 0) ++pop[cls_of(np[s], s)];
+        if (!strict_shapes || !several(pop)) {
+            out->push_back(std::move(np));
+            return false;
+        }
+        for (int c = 1; c < 4; ++c)
+            if (pop[c] > pop[keep]) keep = c;
+        for (int i = 0; i < 4; ++i) {
+            const int c = i < 3 ? (i < keep ? i : i + 1) : keep;
+            if (pop[c] == 0) continue;
+            Counts part(S);
+            for (size_t s = 0; s < S; ++s) part[s] = cls_of(np[s], s) == c ? np[s] : 0;
+            out->push_back(std::move(part));
+        }
+        return true;
+    };
+    std::vector<Counts> groups;                    // rule 1
+    groups.emplace_back(num_point, num_point + S);
+    if (any_pd && any_log) {
+        groups.push_back(groups[0]);
+        for (size_t s = 0; s < S; ++s) groups[ctx_[s] && ctx_[s]->L.pd ? 1 : 0][s] = 0;
+    }
+    for (Counts& g : groups) {
+        std::vector<Counts> classes;
+        const bool apart = by_class(std::move(g), &classes);
+        for (Counts& c : classes) {
+            bool halves = false;                   // rule 3 (of the samples that take part in THIS launch)
+            if (!wide_rows_ && *std::max_element(c.begin(), c.end()) > 4)
+                for (size_t s = 0; s < S; ++s) halves |= c[s] > 0 && narrow(s);
+            if (!halves) {
+                plan->push_back(SubStep{std::move(c), 0, false});
+                continue;
+            }
+            for (int first = 0; first < kSlot; first += 4) {
+                Counts h(S);
+                for (size_t s = 0; s < S; ++s) h[s] = std::max(0, std::min(4, (int)c[s] - first));
+                std::vector<Counts> parts;
+                if (apart) parts.push_back(std::move(h));
+                else by_class(std::move(h), &parts);
+                for (Counts& p : parts) plan->push_back(SubStep{std::move(p), first, true});
+            }
+        }
+    }
+}
+
 int Batch::eval_begin(const int32_t* num_point, const double* pc1, const double* pc2, const double* alpha,
                       double* llk_out)
 {
@@ -376,9 +479,7 @@ int Batch::eval_begin(const int32_t* num_point, const double* pc1, const double*
         return VB2_ERR_INVALID;
     }
     VB2_HIP(hipSetDevice(device));
-    const int k = num_pc, stride = 2 * k + 1;
     int max_n = 0;
-    unsigned int active = 0;
     for (int s = 0; s < num_sample; ++s) {
         if (num_point[s] < 0 || num_point[s] > kSlot) {
             set_error("vb2_batch_eval: num_point out of range");
@@ -388,106 +489,50 @@ int Batch::eval_begin(const int32_t* num_point, const double* pc1, const double*
     }
     if (max_n == 0) return VB2_OK;
     if (const int rc = ensure_resources()) return rc;
-    {
-        // Samples of both layouts in one step (a probability-domain context next to one that could not take that layout: deep
-        // markers, quality 0): a launch runs ONE kind of kernel, so the probability-domain samples are evaluated first, on their
-        // own, and the others go on as this step.  A sample's values do not depend on which launch carries it.
-        bool any_pd = false, any_log = false;
-        for (int s = 0; s < num_sample; ++s)
-            if (num_point[s] > 0 && ctx_[s] && ctx_[s]->L.num_mt > 0) (ctx_[s]->L.pd ? any_pd : any_log) = true;
-        if (any_pd && any_log) {
-            std::vector<int32_t> np((size_t)num_sample);
-            const bool was_split = in_split_;
-            for (int s = 0; s < num_sample; ++s) np[s] = (ctx_[s] && ctx_[s]->L.pd) ? num_point[s] : 0;
-            if (const int rc = eval(np.data(), pc1, pc2, alpha, llk_out)) return rc;
-            for (int s = 0; s < num_sample; ++s) np[s] = (ctx_[s] && ctx_[s]->L.pd) ? 0 : num_point[s];
-            const int rc = eval_begin(np.data(), pc1, pc2, alpha, llk_out);
-            in_split_ = was_split;
-            return rc;
-        }
+    std::vector<SubStep> plan;
+    plan_step(num_point, &plan);
+    if (plan.empty()) return launch_step(num_point, 0, pc1, pc2, alpha, llk_out);
+    for (size_t i = 0; i < plan.size(); ++i) {
+        if (const int rc = launch_step(plan[i].np.data(), plan[i].first, pc1, pc2, alpha, llk_out)) return rc;
+        if (plan[i].wait || i + 1 < plan.size())
+            if (const int rc = eval_end()) return rc;
     }
-    if (strict_shapes && !in_split_) {
-        // A step's wave shape follows from the LARGEST request in it, and under the static deal the shape decides which tiles a
-        // wave multiplies together -- so a sample's sums would move in their last bits with what its neighbours happen to ask
-        // for (a new sample's initial simplex, a shrink).  Strict: the requests of 1-2, of 3-4 and of 5-8 points are evaluated
-        // as separate launches (the one- and two-point shapes deal and multiply alike: bit-identical, tested), so a sample's
-        // values depend on its own requests only.  Mixed steps are rare (a sample starts or shrinks in 1-2 % of them): all
-        // classes but the most populous are evaluated synchronously first.
-        // (a 5-8 point request of a sample with narrow table rows -- more than kMaxWideCodes codes -- is evaluated as two
-        // 4-point launches, below: a class of its own, or one such neighbour would change everybody's wave shape: ADVICE r4)
-        auto cls = [&](int s) {
-            const int n = num_point[s];
-            if (n <= 0) return -1;
-            if (n <= 2) return 0;
-            if (n <= 4) return 1;
-            return (ctx_[s] && ctx_[s]->L.row_bytes != kRowBytesWide) ? 3 : 2;
-        };
-        int pop[4] = {0, 0, 0, 0};
-        for (int s = 0; s < num_sample; ++s)
-            if (num_point[s] > 0) ++pop[cls(s)];
-        if ((pop[0] > 0) + (pop[1] > 0) + (pop[2] > 0) + (pop[3] > 0) > 1) {
-            int keep = 0;
-            for (int c = 1; c < 4; ++c)
-                if (pop[c] > pop[keep]) keep = c;
-            std::vector<int32_t> np((size_t)num_sample);
-            in_split_ = true;
-            int rc = VB2_OK;
-            for (int c = 0; c < 4 && !rc; ++c) {
-                if (c == keep || pop[c] == 0) continue;
-                for (int s = 0; s < num_sample; ++s) np[s] = cls(s) == c ? num_point[s] : 0;
-                rc = eval(np.data(), pc1, pc2, alpha, llk_out);
-            }
-            if (!rc) {
-                for (int s = 0; s < num_sample; ++s) np[s] = cls(s) == keep ? num_point[s] : 0;
-                rc = eval_begin(np.data(), pc1, pc2, alpha, llk_out);
-            }
-            in_split_ = false;
-            return rc;
-        }
-    }
-    bool narrow_in_step = false;               // (of the samples that take part in THIS step)
-    for (int s = 0; s < num_sample && !wide_rows_; ++s)
-        narrow_in_step |= num_point[s] > 0 && ctx_[s] && ctx_[s]->L.row_bytes != kRowBytesWide;
-    if (max_n > 4 && narrow_in_step) {
-        // a sample with a very wide dictionary has narrow table rows: 4 points per launch at most
-        const size_t S = (size_t)num_sample;
-        std::vector<int32_t> np(S);
-        std::vector<double> p1(S * kSlot * k), p2(S * kSlot * k), al(S * kSlot), lo(S * kSlot);
-        for (int half = 0; half < 2; ++half) {
-            for (size_t s = 0; s < S; ++s) {
-                np[s] = std::max(0, std::min(4, (int)num_point[s] - 4 * half));
-                for (int j = 0; j < np[s]; ++j) {
-                    const size_t src = s * kSlot + 4 * half + j, dst = s * kSlot + j;
-                    std::memcpy(&p1[dst * k], pc1 + src * k, sizeof(double) * k);
-                    std::memcpy(&p2[dst * k], pc2 + src * k, sizeof(double) * k);
-                    al[dst] = alpha[src];
-                }
-            }
-            if (int rc = eval(np.data(), p1.data(), p2.data(), al.data(), lo.data())) return rc;
-            for (size_t s = 0; s < S; ++s)
-                for (int j = 0; j < np[s]; ++j) llk_out[s * kSlot + 4 * half + j] = lo[s * kSlot + j];
-        }
-        return VB2_OK;
-    }
+    return VB2_OK;
+}
+
+void Batch::prefill_nan()
+{
+    // (results come back as relaxed stores behind a relaxed flag: NaN first, so that a store still on its way when the
+    // flag is seen is noticed -- Context::eval_host, settle_results)
+    for (int s = 0; s < num_sample; ++s)
+        for (int j = 0; j < h_nv_[s]; ++j) h_out_[(size_t)s * flight_np_ + j] = std::numeric_limits<double>::quiet_NaN();
+}
+
+int Batch::launch_step(const int32_t* np, int first, const double* pc1, const double* pc2, const double* alpha, double* llk_out)
+{
+    const int k = num_pc, stride = 2 * k + 1;
+    const int max_n = *std::max_element(np, np + num_sample);
+    unsigned int active = 0;
     // one or two points per sample (a search that speculates little or not at all): the wave takes
     // four micro-tiles, and the step costs a quarter / half of a 4-point step whose other slots
     // would replicate the last point
     const bool small = max_n <= 2;
     const int NP = max_n > 4 ? 8 : small ? max_n : 4, shape = max_n > 4 ? 1 : small ? (max_n == 1 ? 2 : 3) : 0;
     for (int s = 0; s < num_sample; ++s) {
-        int n = num_point[s];
+        int n = np[s];
+        const size_t at = (size_t)s * kSlot + first;
         // a sample without active markers has LLK 0 for every point: answer it here
         if (n > 0 && (!ctx_[s] || ctx_[s]->L.num_mt == 0)) {
-            for (int j = 0; j < n; ++j) llk_out[(size_t)s * kSlot + j] = 0.0;
+            for (int j = 0; j < n; ++j) llk_out[at + j] = 0.0;
             n = 0;
         }
         h_nv_[s] = n;
         if (n > 0) ++active;
         for (int j = 0; j < n; ++j) {
             double* row = h_points_ + ((size_t)s * NP + j) * stride;
-            std::memcpy(row, pc1 + ((size_t)s * kSlot + j) * k, sizeof(double) * k);
-            std::memcpy(row + k, pc2 + ((size_t)s * kSlot + j) * k, sizeof(double) * k);
-            row[2 * k] = alpha[(size_t)s * kSlot + j];
+            std::memcpy(row, pc1 + (at + j) * k, sizeof(double) * k);
+            std::memcpy(row + k, pc2 + (at + j) * k, sizeof(double) * k);
+            row[2 * k] = alpha[at + j];
         }
     }
     if (active == 0) return VB2_OK;
@@ -512,15 +557,15 @@ int Batch::eval_begin(const int32_t* num_point, const double* pc1, const double*
     ml.force_ticket = false;
     ml.w16 = w16_;
     for (int s2 = 0; s2 < num_sample; ++s2)
-        if (h_nv_[s2] > 0 && ctx_[s2] && ctx_[s2]->L.pd) ml.pd = true;      // (the step's samples are of one layout: see the top)
+        if (h_nv_[s2] > 0 && ctx_[s2] && ctx_[s2]->L.pd) ml.pd = true;      // (the launch's samples are of one layout: plan_step)
     // (probability domain: the short copy is the 8-bit step lists -- they pay where a step is bound by what it streams: 32 C3
     // samples x 1 point 62.4 -> 58.0 us, x 2 points 77.4 -> 76.0, x 4 points 124.6 -> 126.3: the one- and two-point shapes only)
     if (ml.pd && NP > 2) ml.w16 = false;
     {   // (the pipelined item loop is compiled for the static deal: every sample of the cohort must run it)
-        bool st = true;
-        for (int s2 = 0; s2 < num_sample && st; ++s2)
-            st = !ctx_[s2] || ctx_[s2]->L.num_mt == 0 || !eval_takes_the_queue(ctx_[s2]->L, bps_, block_waves_, 1);
-        ml.all_static = st;
+        bool st_all = true;
+        for (int s2 = 0; s2 < num_sample && st_all; ++s2)
+            st_all = !ctx_[s2] || ctx_[s2]->L.num_mt == 0 || !eval_takes_the_queue(ctx_[s2]->L, bps_, block_waves_, 1);
+        ml.all_static = st_all;
     }
     {   // (the cohort kernels compiled for --NumPC 2 / 4 without a known-AF column)
         bool plain = num_pc == 2 || num_pc == 4;
@@ -534,15 +579,13 @@ int Batch::eval_begin(const int32_t* num_point, const double* pc1, const double*
         for (int s2 = 0; s2 < num_sample; ++s2) ml.inl.nv[s2] = (unsigned char)h_nv_[s2];
         std::memcpy(ml.inl.v, h_points_, sizeof(double) * (size_t)ml.inl.count);
     }
-    // (results come back as relaxed stores behind a relaxed flag: NaN first, so that a store still on its way when the
-    // flag is seen is noticed -- Context::eval_host, settle_results)
-    for (int s = 0; s < num_sample; ++s)
-        for (int j = 0; j < h_nv_[s]; ++j) h_out_[(size_t)s * NP + j] = std::numeric_limits<double>::quiet_NaN();
+    flight_np_ = NP;
+    flight_first_ = first;
+    flight_out_ = llk_out;
+    prefill_nan();
     VB2_HIP(launch_llk_eval_multi(ml, stream_));
     ++num_launch;
     in_flight_ = true;
-    flight_np_ = NP;
-    flight_out_ = llk_out;
     return VB2_OK;
 }
 
@@ -559,8 +602,7 @@ int Batch::eval_end()
         if (attempt > 0) {
             ml.force_ticket = true;
             ml.done_seq = ++seq_;
-            for (int s = 0; s < num_sample; ++s)
-                for (int j = 0; j < h_nv_[s]; ++j) h_out_[(size_t)s * NP + j] = std::numeric_limits<double>::quiet_NaN();
+            prefill_nan();
             VB2_HIP(launch_llk_eval_multi(ml, stream_));
             ++num_launch;
         }
@@ -584,7 +626,7 @@ int Batch::eval_end()
         if (!any_nan) break;
     }
     for (int s = 0; s < num_sample; ++s)
-        for (int j = 0; j < h_nv_[s]; ++j) flight_out_[(size_t)s * kSlot + j] = h_out_[(size_t)s * NP + j];
+        for (int j = 0; j < h_nv_[s]; ++j) flight_out_[(size_t)s * kSlot + flight_first_ + j] = h_out_[(size_t)s * NP + j];
     return VB2_OK;
 }
 
@@ -593,26 +635,135 @@ int Batch::eval_end()
 // the reference-exact simplex) as a fiber of the calling thread (lockstep.h); the parked
 // requests of a step leave as ONE launch of the multi-sample kernel.
 //
-// A cohort of kSplitFrom samples or more is searched as TWO half-cohorts taking turns: while one
+// A cohort of 16 samples or more (search_lanes) is searched as TWO half-cohorts taking turns: while one
 // half's step is on the device, the other half's fibers run on the host (64 fiber switches and
 // simplex updates are ~60 us, a quarter of the step they would otherwise be added to), and the
 // next launch is already queued behind the running one, so the device never waits for the host.
+//
+// SearchLane is one of those halves: a gang of fibers, the batch their requests are launched on, the staging in between.
+// take_turns is the loop; what a search does around a step (regrouping; refilling and retiring slots) it is given as hooks.
 // ---------------------------------------------------------------------------
 namespace {
 
-struct Lane {
-    Batch* batch = nullptr;                 // the lane's samples, all of them
+double wall_s()
+{
+    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+struct SearchLane;
+struct LaneTeam {                           // the lanes of one search and its first device-level error
+    SearchLane* lanes = nullptr;
+    int nlane = 0, error = 0;
+    bool dbg = tunables().debug_lockstep != 0;       // what the lanes then count and time for the searches' diagnostic lines
+    long steps = 0, active = 0, points = 0, by_eighths[9] = {0}, steps_by_slots[65] = {0};
+    double s_launch = 0, s_wait = 0, s_resume = 0, s_flight_by_slots[65] = {0};
+};
+
+struct SearchLane {
+    LaneTeam* team = nullptr;
     std::unique_ptr<FiberGang> gang;
-    int base = 0, count = 0;                // samples [base, base + count) of the whole cohort
+    Batch* batch = nullptr;                 // where the next step is launched (not owned)
+    std::vector<int> slot_fiber;            // slot j of `batch` carries fiber slot_fiber[j]: the identity until a lane regroups
     std::vector<int32_t> npts;
     std::vector<double> pc1, pc2, alpha, llk;
     bool flying = false;
-    std::chrono::steady_clock::time_point t_launch;
-    // the samples still searching, regrouped (see Batch::optimize): slot j of `cur` is fiber slot_fiber[j]
-    Batch* cur = nullptr;
-    std::unique_ptr<Batch> regrouped;
-    std::vector<int> slot_fiber;
+    double t_launch = 0;
+
+    void init(LaneTeam* t, Batch* b, int num_fiber, int max_points_per_request)
+    {
+        team = t;
+        batch = b;
+        gang.reset(new FiberGang(num_fiber, max_points_per_request));
+        slot_fiber.resize(num_fiber);
+        for (int i = 0; i < num_fiber; ++i) slot_fiber[i] = i;
+        const size_t n = (size_t)num_fiber, k = (size_t)b->num_pc;
+        npts.assign(n, 0);
+        pc1.resize(n * kSlot * k); pc2.resize(n * kSlot * k); alpha.resize(n * kSlot); llk.resize(n * kSlot);
+    }
+    bool busy() const { return flying || gang->pending(); }
+    void fail(int rc)
+    {
+        if (!team->error) team->error = rc;
+        for (int l = 0; l < team->nlane; ++l) team->lanes[l].gang->fail(rc);
+    }
+    // the parked requests of the lane -> one step of its batch
+    void launch()
+    {
+        if (team->error || !gang->pending()) return;
+        const std::vector<FiberGang::Request>& req = gang->requests();
+        const int nslot = (int)slot_fiber.size(), k = batch->num_pc;
+        int act = 0, pts = 0;
+        for (int i = 0; i < nslot; ++i) {
+            const FiberGang::Request& r = req[slot_fiber[i]];
+            npts[i] = gang->idle(slot_fiber[i]) ? 0 : r.n;
+            if (npts[i] <= 0) continue;
+            ++act; pts += r.n;
+            std::memcpy(&pc1[(size_t)i * kSlot * k], r.p1, sizeof(double) * r.n * k);
+            std::memcpy(&pc2[(size_t)i * kSlot * k], r.p2, sizeof(double) * r.n * k);
+            std::memcpy(&alpha[(size_t)i * kSlot], r.a, sizeof(double) * r.n);
+        }
+        if (team->dbg) {
+            ++team->steps; team->active += act; team->points += pts;
+            team->by_eighths[std::min(8, (8 * act + nslot - 1) / nslot)]++;
+        }
+        const double tl = team->dbg ? wall_s() : 0.0;
+        if (const int rc = batch->eval_begin(npts.data(), pc1.data(), pc2.data(), alpha.data(), llk.data())) {
+            fail(rc);
+            return;
+        }
+        if (team->dbg) team->s_launch += (t_launch = wall_s()) - tl;
+        flying = true;
+    }
+    // wait for the lane's step, hand the values out, run its fibers up to their next requests
+    void land()
+    {
+        if (flying) {
+            flying = false;
+            const double tw = team->dbg ? wall_s() : 0.0;
+            if (const int rc = batch->eval_end()) fail(rc);
+            if (team->dbg) {
+                const int ns = std::min(64, (int)slot_fiber.size());
+                const double now = wall_s();
+                team->s_wait += now - tw;
+                team->s_flight_by_slots[ns] += now - t_launch;
+                ++team->steps_by_slots[ns];
+            }
+            if (!team->error) {
+                std::vector<FiberGang::Request>& req = gang->requests();
+                for (size_t i = 0; i < slot_fiber.size(); ++i)
+                    if (npts[i] > 0) std::memcpy(req[slot_fiber[i]].out, &llk[i * kSlot], sizeof(double) * npts[i]);
+            }
+        }
+        const double tr = team->dbg ? wall_s() : 0.0;
+        if (gang->pending()) gang->resume_parked();           // (after an error: the fibers unwind)
+        if (team->dbg) team->s_resume += wall_s() - tr;
+    }
 };
+
+// The lanes take turns until none has a step in flight or a request parked: a lane's step is queued behind the other's step
+// in flight, then that one is landed and launched again.  The hooks run ahead of every launch and behind every landing.
+template <class Before, class After>
+void take_turns(LaneTeam& team, Before before_launch, After after_land)
+{
+    for (bool busy = true; busy;) {
+        busy = false;
+        for (int l = 0; l < team.nlane; ++l) {
+            SearchLane& next = team.lanes[(l + 1) % team.nlane];
+            if (team.nlane > 1 && !next.flying) {              // queued behind the step in flight
+                before_launch(next);
+                next.launch();
+            }
+            SearchLane& cur = team.lanes[l];
+            if (cur.busy()) {
+                cur.land();
+                after_land(cur);
+            }
+            before_launch(cur);
+            cur.launch();
+            busy |= cur.busy();
+        }
+    }
+}
 
 }  // namespace
 
@@ -622,25 +773,15 @@ int Batch::optimize(const vb2_model* models, int num_model, vb2_estimate* out)
         set_error("vb2_batch_optimize_llk: pass 1 model or one per sample");
         return VB2_ERR_INVALID;
     }
-    // Speculation (amoeba.h) trades device work for fewer dependent steps.  A small cohort's step is
-    // latency-bound and {R, E, C_A, C_R} per iteration pays (2.5 points evaluated per point the
-    // search needs).  A big cohort's step is throughput-bound -- its cost grows with the points in
-    // it, down to the floor of streaming every sample's pileup from HBM once per step (5.7 TB/s
-    // measured: a 1-point step of 32 C3 samples takes 131 us against 236 us with 4 points) -- and
-    // {R, C_R} is the better trade: 1.2 steps per iteration at about half the points.  Same
-    // decisions, same trajectory either way.  Tunables::cohort_speculate = 1|2|4 forces one.
     const Tunables& tn = tunables();
-    constexpr int kPairFrom = 8;
-    speculate_ = num_sample < kPairFrom ? 4 : 2;
-    if (tn.cohort_speculate > 0) speculate_ = tn.cohort_speculate;
-    bool split = num_sample >= kSplitFrom;
-    if (tn.cohort_split >= 0) split = tn.cohort_split != 0 && num_sample >= 2;
-
-    const int S = num_sample, k = num_pc;
-    Lane lanes[kMaxLanes];
-    int nlane = 1;
-    if (split) {
-        nlane = std::max(2, std::min(std::min(kMaxLanes, tn.cohort_lanes), S));
+    const int S = num_sample, k = num_pc, speculate = search_speculate(S);
+    SearchLane lanes[kMaxLanes];
+    LaneTeam team{lanes};
+    int base[kMaxLanes] = {0}, count[kMaxLanes];               // lane l searches samples [base[l], base[l] + count[l])
+    std::unique_ptr<Batch> regrouped[kMaxLanes];
+    const int nlane = team.nlane = search_lanes(S, true, count);
+    for (int l = 1; l < nlane; ++l) base[l] = base[l - 1] + count[l - 1];
+    if (nlane > 1) {
         if (tn.cohort_own_queues && !lane_streams_[0]) {
             VB2_HIP(hipSetDevice(device));
             for (int h = 0; h < nlane; ++h)
@@ -650,19 +791,16 @@ int Batch::optimize(const vb2_model* models, int num_model, vb2_estimate* out)
                 }
         }
         for (int h = 0; h < nlane; ++h) {
-            const int lo = (int)((long)S * h / nlane), hi = (int)((long)S * (h + 1) / nlane);
-            if (!half_[h] || half_[h]->num_sample != hi - lo) {
-                std::vector<Context*> part(ctx_.begin() + lo, ctx_.begin() + hi);
+            if (!half_[h] || half_[h]->num_sample != count[h]) {
+                std::vector<Context*> part(ctx_.begin() + base[h], ctx_.begin() + base[h] + count[h]);
                 Batch* hb = nullptr;
                 if (const int rc = Batch::create(part, &hb)) return rc;
                 if (lane_streams_[h]) hb->borrow_stream(lane_streams_[h]);
                 half_[h].reset(hb);
             }
-            lanes[h].batch = half_[h].get(); lanes[h].base = lo; lanes[h].count = hi - lo;
         }
-    } else {
-        lanes[0].batch = this; lanes[0].base = 0; lanes[0].count = S;
     }
+    for (int l = 0; l < nlane; ++l) lanes[l].init(&team, nlane > 1 ? half_[l].get() : this, count[l], kSlot);
     // Samples finish at different iterations (C3-shaped cohort of 32: the shortest search is over after ~60 % of the
     // longest's steps), and a step gives every sample of its batch 256 / num_sample workgroups whether it still takes part
     // or not: in round 3 a third of all steps served one or two samples on an eighth of the device.  So when half of a
@@ -672,121 +810,50 @@ int Batch::optimize(const vb2_model* models, int num_model, vb2_estimate* out)
     // an eighth ...
     // Tunables::cohort_regroup = 0: the fixed batch to the end (A/B).
     const bool regroup = tn.cohort_regroup != 0;
-    std::vector<int> rcs(S, 0);
-    for (int l = 0; l < nlane; ++l) {
-        Lane& L = lanes[l];
-        L.cur = L.batch;
-        L.slot_fiber.resize(L.count);
-        for (int i = 0; i < L.count; ++i) L.slot_fiber[i] = i;
-        const size_t n = (size_t)L.count;
-        L.gang.reset(new FiberGang(L.count, kSlot));
-        L.npts.assign(n, 0);
-        L.pc1.resize(n * kSlot * k); L.pc2.resize(n * kSlot * k); L.alpha.resize(n * kSlot); L.llk.resize(n * kSlot);
-    }
-    auto body_of = [&](Lane& L) {
-        return [&, this](int i) {
-            const int s = L.base + i;
-            try {
-                const vb2_model& m = models[num_model == 1 ? 0 : s];
-                Estimator est(num_pc, FiberGang::eval_cb, L.gang->user(i));
-                apply_model(est, m, ctx_[s]->L.known_af != nullptr);
-                est.speculate = speculate_;
-                rcs[s] = est.OptimizeLLK();
-                fill_estimate(est, &out[s]);
-            } catch (const std::bad_alloc&) {
-                rcs[s] = VB2_ERR_NOMEM;
-            } catch (const std::exception& e) {
-                set_error(e.what());
-                rcs[s] = VB2_ERR_INVALID;
-            } catch (...) {                      // nothing may unwind past the fiber's entry frame
-                set_error("vb2_batch_optimize_llk: unknown exception in a sample's search");
-                rcs[s] = VB2_ERR_INVALID;
+    double regroup_s = 0;
+    num_regroup = 0;
+    auto regroup_lane = [&](SearchLane& L) {
+        if (!regroup || team.error) return;
+        const int l = (int)(&L - lanes);
+        const std::vector<FiberGang::Request>& req = L.gang->requests();
+        int act = 0;
+        for (int j : L.slot_fiber) act += req[j].n > 0;
+        if (act < 1 || 2 * act > (int)L.slot_fiber.size()) return;
+        std::vector<int> keep;
+        std::vector<Context*> part;
+        for (int j : L.slot_fiber)
+            if (req[j].n > 0) {
+                keep.push_back(j);
+                part.push_back(ctx_[base[l] + j]);
             }
-        };
-    };
-    const bool dbg = tn.debug_lockstep != 0;
-    double dbg_regroup_s = 0, dbg_wall_by_slots[65] = {0}; long dbg_steps_by_slots[65] = {0};
-    long dbg_steps = 0, dbg_active = 0, dbg_points = 0, dbg_regroups = 0, dbg_hist[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    int error = 0;
-    auto fail = [&](int rc) {
-        if (!error) error = rc;
-        for (int l = 0; l < nlane; ++l) lanes[l].gang->fail(rc);
-    };
-    // the parked requests of a lane -> one launch
-    auto launch = [&](Lane& L) {
-        if (error || !L.gang->pending()) return;
-        std::vector<FiberGang::Request>& req = L.gang->requests();
-        if (regroup) {
-            int act = 0;
-            for (int j : L.slot_fiber) act += req[j].n > 0;
-            if (act >= 1 && 2 * act <= (int)L.slot_fiber.size()) {
-                std::vector<int> keep;
-                std::vector<Context*> part;
-                for (int j : L.slot_fiber)
-                    if (req[j].n > 0) {
-                        keep.push_back(j);
-                        part.push_back(ctx_[L.base + j]);
-                    }
-                Batch* nb = nullptr;
-                const auto tr0 = std::chrono::steady_clock::now();
-                int rc = Batch::create(part, &nb, regroup_bps(ctx_[0]->L.num_cu, (int)part.size()));
-                if (!rc && nlane > 1 && lane_streams_[&L - lanes]) nb->borrow_stream(lane_streams_[&L - lanes]);
-                if (!rc) rc = nb->ensure_resources();
-                if (rc) {
-                    delete nb;
-                    fail(rc);
-                    return;
-                }
-                dbg_regroup_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tr0).count();
-                L.regrouped.reset(nb);             // (the batch it replaces has no step in flight: its slabs go back to the caches)
-                L.cur = nb;
-                L.slot_fiber.swap(keep);
-                ++dbg_regroups;
-            }
-        }
-        const int nslot = (int)L.slot_fiber.size();
-        for (int i = 0; i < nslot; ++i) {
-            const FiberGang::Request& r = req[L.slot_fiber[i]];
-            L.npts[i] = r.n;
-            if (r.n <= 0) continue;
-            std::memcpy(&L.pc1[(size_t)i * kSlot * k], r.p1, sizeof(double) * r.n * k);
-            std::memcpy(&L.pc2[(size_t)i * kSlot * k], r.p2, sizeof(double) * r.n * k);
-            std::memcpy(&L.alpha[(size_t)i * kSlot], r.a, sizeof(double) * r.n);
-        }
-        if (dbg) {
-            int act = 0, pts = 0;
-            for (int i = 0; i < nslot; ++i) { act += L.npts[i] > 0; pts += std::max(0, L.npts[i]); }
-            ++dbg_steps; dbg_active += act; dbg_points += pts;
-            dbg_hist[std::min(8, (8 * act + nslot - 1) / nslot)]++;
-        }
-        if (const int rc = L.cur->eval_begin(L.npts.data(), L.pc1.data(), L.pc2.data(), L.alpha.data(), L.llk.data())) {
-            fail(rc);
+        Batch* nb = nullptr;
+        const double tr0 = wall_s();
+        int rc = Batch::create(part, &nb, regroup_bps(ctx_[0]->L.num_cu, (int)part.size()));
+        if (!rc && nlane > 1 && lane_streams_[l]) nb->borrow_stream(lane_streams_[l]);
+        if (!rc) rc = nb->ensure_resources();
+        if (rc) {
+            delete nb;
+            L.fail(rc);
             return;
         }
-        L.flying = true;
-        L.t_launch = std::chrono::steady_clock::now();
+        regroup_s += wall_s() - tr0;
+        regrouped[l].reset(nb);                // (the batch it replaces has no step in flight: its slabs go back to the caches)
+        L.batch = nb;
+        L.slot_fiber.swap(keep);
+        ++num_regroup;
     };
-    // wait for the lane's step, hand the values out, run its fibers up to their next requests
-    auto land = [&](Lane& L) {
-        if (L.flying) {
-            L.flying = false;
-            if (const int rc = L.cur->eval_end()) fail(rc);
-            if (dbg) {
-                const int ns = std::min(64, (int)L.slot_fiber.size());
-                dbg_wall_by_slots[ns] += std::chrono::duration<double>(std::chrono::steady_clock::now() - L.t_launch).count();
-                ++dbg_steps_by_slots[ns];
-            }
-            if (!error) {
-                std::vector<FiberGang::Request>& req = L.gang->requests();
-                for (int i = 0; i < (int)L.slot_fiber.size(); ++i)
-                    if (L.npts[i] > 0)
-                        std::memcpy(req[L.slot_fiber[i]].out, &L.llk[(size_t)i * kSlot], sizeof(double) * L.npts[i]);
-            }
-        }
-        if (L.gang->pending()) L.gang->resume_parked();       // (after an error: the fibers unwind)
-    };
-    for (int l = 0; l < nlane; ++l)
-        if (lanes[l].gang->start(k, body_of(lanes[l])) < 0) {
+    std::vector<int> rcs(S, 0);
+    for (int l = 0; l < nlane; ++l) {
+        SearchLane& L = lanes[l];
+        auto body = [&, l](int i) {
+            const int s = base[l] + i;
+            FiberGang::Search cfg;
+            cfg.model = &models[num_model == 1 ? 0 : s];
+            cfg.data_has_known_af = ctx_[s]->L.known_af != nullptr;
+            cfg.speculate = speculate;
+            rcs[s] = L.gang->search(i, cfg, "vb2_batch_optimize_llk", &out[s]);
+        };
+        if (L.gang->start(k, body) < 0) {
             // the lanes started so far have fibers parked in the middle of OptimizeLLK: tell them, and
             // run them until they have unwound (their Estimators and vectors live on the fiber stacks,
             // which the gang unmaps) before giving up
@@ -797,37 +864,24 @@ int Batch::optimize(const vb2_model* models, int num_model, vb2_estimate* out)
             set_error("vb2_batch_optimize_llk: could not start the search fibers (mmap / getcontext failed)");
             return VB2_ERR_INVALID;
         }
-    const auto t_loop0 = std::chrono::steady_clock::now();
-    launch(lanes[0]);
-    for (;;) {
-        bool busy = false;
-        for (int l = 0; l < nlane; ++l) {
-            Lane& next = lanes[(l + 1) % nlane];
-            if (nlane > 1 && !next.flying) launch(next);       // queued behind the step in flight
-            Lane& cur = lanes[l];
-            if (cur.flying || cur.gang->pending()) {
-                land(cur);
-                launch(cur);
-            }
-            busy |= cur.flying || cur.gang->pending();
-        }
-        if (!busy) break;
     }
-    if (dbg) {
-        std::fprintf(stderr, "lock-step loop %.2f ms, of which regrouping %.2f ms\n",
-                     1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop0).count(), 1e3 * dbg_regroup_s);
+    const double t_loop0 = wall_s();
+    regroup_lane(lanes[0]);
+    lanes[0].launch();
+    take_turns(team, regroup_lane, [](SearchLane&) {});
+    if (team.dbg) {
+        std::fprintf(stderr, "lock-step loop %.2f ms, of which regrouping %.2f ms\n", 1e3 * (wall_s() - t_loop0), 1e3 * regroup_s);
         for (int n = 1; n <= 64; ++n)
-            if (dbg_steps_by_slots[n])
-                std::fprintf(stderr, "  batches of %d: %ld steps, %.1f us from launch to landing each\n", n, dbg_steps_by_slots[n],
-                             1e6 * dbg_wall_by_slots[n] / dbg_steps_by_slots[n]);
-    }
-    if (dbg)
+            if (team.steps_by_slots[n])
+                std::fprintf(stderr, "  batches of %d: %ld steps, %.1f us from launch to landing each\n", n, team.steps_by_slots[n],
+                             1e6 * team.s_flight_by_slots[n] / team.steps_by_slots[n]);
+        const long* e = team.by_eighths;
         std::fprintf(stderr, "lock-step search of %d samples in %d lane(s): %ld steps, %.1f active samples and %.1f points per step "
                              "(a lane holds %d, %ld regroupings); steps by eighths of the batch active: %ld %ld %ld %ld %ld %ld %ld %ld\n",
-                     S, nlane, dbg_steps, (double)dbg_active / std::max(1L, dbg_steps), (double)dbg_points / std::max(1L, dbg_steps),
-                     lanes[0].count, dbg_regroups, dbg_hist[1], dbg_hist[2], dbg_hist[3], dbg_hist[4], dbg_hist[5], dbg_hist[6], dbg_hist[7], dbg_hist[8]);
-    num_regroup = dbg_regroups;
-    if (error) return error;
+                     S, nlane, team.steps, (double)team.active / std::max(1L, team.steps), (double)team.points / std::max(1L, team.steps),
+                     count[0], (long)num_regroup, e[1], e[2], e[3], e[4], e[5], e[6], e[7], e[8]);
+    }
+    if (team.error) return team.error;
     for (int s = 0; s < S; ++s)
         if (rcs[s]) return rcs[s];
     return VB2_OK;
@@ -836,46 +890,14 @@ int Batch::optimize(const vb2_model* models, int num_model, vb2_estimate* out)
 // ---------------------------------------------------------------------------
 // stream_search.h: slots that change hands
 // ---------------------------------------------------------------------------
-namespace {
-
-struct StreamLane {
-    std::unique_ptr<Batch> batch;
-    std::unique_ptr<FiberGang> gang;
-    int count = 0;
-    std::vector<int> id;                    // [slot] the sample in it, or -1
-    std::vector<int> rc;
-    std::vector<vb2_estimate> est;
-    std::vector<double> t0;
-    std::vector<int32_t> npts;
-    std::vector<double> pc1, pc2, alpha, llk;
-    bool flying = false;
-};
-
-double wall_s()
-{
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-void stream_lanes(int capacity, int* n0, int* n1)
-{
-    *n0 = capacity;
-    *n1 = 0;
-    if (capacity >= kSplitFrom) {
-        *n0 = capacity / 2;
-        *n1 = capacity - capacity / 2;
-    }
-}
-
-}  // namespace
-
 int prepare_for_stream(Context* c, int capacity)
 {
-    if (!c || c->L.num_mt == 0) return VB2_OK;
-    int n[2];
-    stream_lanes(capacity, &n[0], &n[1]);
+    if (!c || capacity < 1 || c->L.num_mt == 0) return VB2_OK;
+    int n[kMaxLanes];
+    const int nlane = search_lanes(capacity, false, n);
     Schedule sc[Batch::kShapes];
-    for (int l = 0; l < 2; ++l) {
-        if (n[l] <= 0 || (l == 1 && n[1] == n[0])) continue;
+    for (int l = 0; l < nlane; ++l) {
+        if (l == 1 && n[1] == n[0]) continue;
         if (const int rc = c->cohort_schedules(std::max(1, c->L.num_cu * (kMaxBlockWaves / cohort_waves()) / n[l]), cohort_waves(), sc, false)) return rc;
     }
     return VB2_OK;
@@ -884,74 +906,61 @@ int prepare_for_stream(Context* c, int capacity)
 int stream_search(int device, int num_pc, int num_cu, int capacity, StreamSource& src, const hipStream_t* lane_streams)
 {
     capacity = std::max(1, std::min(capacity, 128));
-    const int k = num_pc;
-    int speculate = capacity < 8 ? 4 : 2;                      // (Batch::optimize: kPairFrom)
-    if (tunables().cohort_speculate > 0) speculate = tunables().cohort_speculate;
-    StreamLane lanes[2];
-    int cnt[2];
-    stream_lanes(capacity, &cnt[0], &cnt[1]);
-    const int nlane = cnt[1] > 0 ? 2 : 1;
-    int error = 0;
+    const int k = num_pc, speculate = search_speculate(capacity);
+    struct Slots {                          // of a lane: [slot] the sample in it (or -1) and what its search leaves
+        std::unique_ptr<Batch> batch;
+        std::vector<int> id, rc;
+        std::vector<vb2_estimate> est;
+        std::vector<double> t0;
+    } slots[kMaxLanes];
+    SearchLane lanes[kMaxLanes];
+    LaneTeam team{lanes};
+    int cnt[kMaxLanes];
+    const int nlane = team.nlane = search_lanes(capacity, false, cnt);
     for (int l = 0; l < nlane; ++l) {
-        StreamLane& L = lanes[l];
-        L.count = cnt[l];
         Batch* b = nullptr;
-        if (const int rc = Batch::create_slots(L.count, device, k, num_cu, &b)) return rc;
-        L.batch.reset(b);
+        if (const int rc = Batch::create_slots(cnt[l], device, k, num_cu, &b)) return rc;
+        slots[l].batch.reset(b);
         if (lane_streams && lane_streams[l]) b->borrow_stream(lane_streams[l]);
         // A streamed sample starts whenever a slot falls free, alone.  The ten vertices of its fresh simplex as ONE request would be
-        // a class of their own in that step (strict shapes: eval_begin evaluates the minority classes synchronously first): an
-        // eight-point launch on that sample's sixteenth of the device, ~120 us during which the pipeline thread serves neither
-        // lane.  In pieces of two they ride along with the other slots' steps.
-        L.gang.reset(new FiberGang(L.count, std::max(1, std::min(kSlot, tunables().cohort_stream_points))));
-        const size_t n = (size_t)L.count;
-        L.id.assign(n, -1);
-        L.rc.assign(n, 0);
-        L.est.resize(n);
-        L.t0.assign(n, 0.0);
-        L.npts.assign(n, 0);
-        L.pc1.resize(n * kSlot * k); L.pc2.resize(n * kSlot * k); L.alpha.resize(n * kSlot); L.llk.resize(n * kSlot);
+        // a class of their own in that step (strict shapes: plan_step leaves the most populous class in flight and waits for the
+        // others): an eight-point launch on that sample's sixteenth of the device, ~120 us during which the pipeline thread serves
+        // neither lane.  In pieces of two they ride along with the other slots' steps.
+        lanes[l].init(&team, b, cnt[l], std::max(1, std::min(kSlot, tunables().cohort_stream_points)));
+        slots[l].id.assign(cnt[l], -1);
+        slots[l].rc.assign(cnt[l], 0);
+        slots[l].est.resize(cnt[l]);
+        slots[l].t0.assign(cnt[l], 0.0);
     }
     for (int l = 0; l < nlane; ++l) {
-        StreamLane& L = lanes[l];
-        L.gang->open(k, [&L, &src, k, speculate](int i) {
-            try {
-                Estimator est(k, FiberGang::eval_cb, L.gang->user(i));
-                apply_model(est, src.model(L.id[i]), L.batch->slot(i)->L.known_af != nullptr);
-                est.speculate = speculate;
-                L.rc[i] = est.OptimizeLLK();
-                fill_estimate(est, &L.est[i]);
-            } catch (const std::bad_alloc&) {
-                L.rc[i] = VB2_ERR_NOMEM;
-            } catch (const std::exception& e) {
-                set_error(e.what());
-                L.rc[i] = VB2_ERR_INVALID;
-            } catch (...) {                      // nothing may unwind past the fiber's entry frame
-                set_error("stream_search: unknown exception in a sample's search");
-                L.rc[i] = VB2_ERR_INVALID;
-            }
+        SearchLane& L = lanes[l];
+        Slots& sl = slots[l];
+        L.gang->open(k, [&L, &sl, &src, speculate](int i) {
+            FiberGang::Search cfg;
+            cfg.model = &src.model(sl.id[i]);
+            cfg.data_has_known_af = sl.batch->slot(i)->L.known_af != nullptr;
+            cfg.speculate = speculate;
+            sl.rc[i] = L.gang->search(i, cfg, "stream_search", &sl.est[i]);
         });
     }
     bool ended = false;
-    const bool dbg = tunables().debug_lockstep != 0;
-    long dbg_steps = 0, dbg_active = 0, dbg_points = 0, dbg_samples = 0;
-    double dbg_blocked = 0, dbg_refill = 0, dbg_wait = 0, dbg_resume = 0, dbg_launch = 0, dbg_retire = 0;
+    const bool dbg = team.dbg;
+    long dbg_samples = 0;
+    double dbg_blocked = 0, dbg_refill = 0, dbg_retire = 0;
     const double dbg_t0 = wall_s();
-    auto fail = [&](int rc) {
-        if (!error) error = rc;
-        for (int l = 0; l < nlane; ++l) lanes[l].gang->fail(rc);
-    };
-    auto retire = [&](StreamLane& L, int i) {
-        const int rc = error ? error : L.rc[i];
-        src.done(L.id[i], rc, L.est[i], wall_s() - L.t0[i]);
-        L.id[i] = -1;
-        (void)L.batch->set_slot(i, nullptr);
+    auto retire = [&](SearchLane& L, int i) {
+        Slots& sl = slots[&L - lanes];
+        const int rc = team.error ? team.error : sl.rc[i];
+        src.done(sl.id[i], rc, sl.est[i], wall_s() - sl.t0[i]);
+        sl.id[i] = -1;
+        (void)sl.batch->set_slot(i, nullptr);
     };
     // free slots of a lane <- samples that are ready; block: wait for the first one (nothing is running anywhere)
-    auto refill = [&](StreamLane& L, bool block) {
-        if (error) return;
-        for (int i = 0; i < L.count && !ended; ++i) {
-            if (L.id[i] >= 0) continue;
+    auto refill = [&](SearchLane& L, bool block) {
+        if (team.error) return;
+        Slots& sl = slots[&L - lanes];
+        for (int i = 0; i < L.gang->size() && !ended; ++i) {
+            if (sl.id[i] >= 0) continue;
             Context* c = nullptr;
             const double tb = dbg ? wall_s() : 0.0;
             const int id = src.next(block, &c);
@@ -959,23 +968,23 @@ int stream_search(int device, int num_pc, int num_cu, int capacity, StreamSource
             block = false;
             if (id == StreamSource::kEnd) ended = true;
             if (id < 0) break;
-            L.id[i] = id;
-            L.rc[i] = 0;
-            std::memset(&L.est[i], 0, sizeof(vb2_estimate));
-            L.t0[i] = wall_s();
+            sl.id[i] = id;
+            sl.rc[i] = 0;
+            std::memset(&sl.est[i], 0, sizeof(vb2_estimate));
+            sl.t0[i] = wall_s();
             ++dbg_samples;
             // (Tunables::cohort_fail_sample: a test's way to send one sample down this error path)
             const int rc_slot = id == tunables().cohort_fail_sample ? (set_error("streaming batch: sample refused (test hook)"), VB2_ERR_INVALID)
-                                                                   : L.batch->set_slot(i, c);
+                                                                   : sl.batch->set_slot(i, c);
             if (const int rc = rc_slot) {                       // this sample cannot be searched here: the others can
-                L.rc[i] = rc;
+                sl.rc[i] = rc;
                 retire(L, i);
                 --i;
                 continue;
             }
             if (L.gang->spawn(i) < 0) {
                 set_error("stream_search: could not start a search fiber (mmap / getcontext failed)");
-                L.rc[i] = VB2_ERR_INVALID;
+                sl.rc[i] = VB2_ERR_INVALID;
                 retire(L, i);
                 continue;
             }
@@ -983,81 +992,34 @@ int stream_search(int device, int num_pc, int num_cu, int capacity, StreamSource
                 retire(L, i);
                 --i;
             }
-            if (dbg) dbg_refill += wall_s() - L.t0[i < 0 ? 0 : i];
+            if (dbg) dbg_refill += wall_s() - sl.t0[i < 0 ? 0 : i];
         }
     };
-    auto launch = [&](StreamLane& L) {
-        if (error || !L.gang->pending()) return;
-        std::vector<FiberGang::Request>& req = L.gang->requests();
-        for (int i = 0; i < L.count; ++i) {
-            const FiberGang::Request& r = req[i];
-            L.npts[i] = (L.id[i] >= 0 && !L.gang->idle(i)) ? r.n : 0;
-            if (L.npts[i] <= 0) continue;
-            std::memcpy(&L.pc1[(size_t)i * kSlot * k], r.p1, sizeof(double) * r.n * k);
-            std::memcpy(&L.pc2[(size_t)i * kSlot * k], r.p2, sizeof(double) * r.n * k);
-            std::memcpy(&L.alpha[(size_t)i * kSlot], r.a, sizeof(double) * r.n);
-        }
-        if (dbg) {
-            ++dbg_steps;
-            for (int i = 0; i < L.count; ++i) { dbg_active += L.npts[i] > 0; dbg_points += std::max(0, L.npts[i]); }
-        }
-        const double tl = dbg ? wall_s() : 0.0;
-        if (const int rc = L.batch->eval_begin(L.npts.data(), L.pc1.data(), L.pc2.data(), L.alpha.data(), L.llk.data())) {
-            fail(rc);
-            return;
-        }
-        if (dbg) dbg_launch += wall_s() - tl;
-        L.flying = true;
-    };
-    auto land = [&](StreamLane& L) {
-        if (L.flying) {
-            L.flying = false;
-            const double tw = dbg ? wall_s() : 0.0;
-            const int rc_end = L.batch->eval_end();
-            if (dbg) dbg_wait += wall_s() - tw;
-            if (const int rc = rc_end) fail(rc);
-            if (!error) {
-                std::vector<FiberGang::Request>& req = L.gang->requests();
-                for (int i = 0; i < L.count; ++i)
-                    if (L.npts[i] > 0) std::memcpy(req[i].out, &L.llk[(size_t)i * kSlot], sizeof(double) * L.npts[i]);
-            }
-        }
+    // the slots whose searches are over are reported and fall free
+    auto retire_idle = [&](SearchLane& L) {
+        const Slots& sl = slots[&L - lanes];
         const double tr = dbg ? wall_s() : 0.0;
-        if (L.gang->pending()) L.gang->resume_parked();       // (after an error: the fibers unwind)
-        const double tr2 = dbg ? wall_s() : 0.0;
-        for (int i = 0; i < L.count; ++i)
-            if (L.id[i] >= 0 && L.gang->idle(i)) retire(L, i);
-        if (dbg) { dbg_resume += tr2 - tr; dbg_retire += wall_s() - tr2; }
+        for (int i = 0; i < L.gang->size(); ++i)
+            if (sl.id[i] >= 0 && L.gang->idle(i)) retire(L, i);
+        if (dbg) dbg_retire += wall_s() - tr;
     };
     for (;;) {
-        bool busy = false;
-        for (int l = 0; l < nlane; ++l) {
-            StreamLane& next = lanes[(l + 1) % nlane];
-            if (nlane > 1 && !next.flying) {                   // queued behind the step in flight
-                refill(next, false);
-                launch(next);
-            }
-            StreamLane& cur = lanes[l];
-            if (cur.flying || cur.gang->pending()) land(cur);
-            refill(cur, false);
-            launch(cur);
-            busy |= cur.flying || cur.gang->pending();
-        }
-        if (busy) continue;
-        if (error || ended) break;
+        take_turns(team, [&](SearchLane& L) { refill(L, false); }, retire_idle);
+        if (team.error || ended) break;
         refill(lanes[0], true);                                 // nothing in flight, nothing ready: wait for a sample
-        launch(lanes[0]);
-        if (!lanes[0].flying && !lanes[0].gang->pending() && ended) break;
+        lanes[0].launch();
+        if (!lanes[0].busy() && ended) break;
     }
-    if (dbg)
+    if (dbg) {
+        const long per = std::max(1L, team.steps);
         std::fprintf(stderr, "stream search: %ld samples through %d slots in %.1f ms: %ld steps, %.1f active samples and %.1f points "
                              "per step (a lane holds %d); waited %.1f ms with nothing to do, %.1f ms taking samples in; the pipeline thread per step: "
                              "%.1f us waiting for a step to land, %.1f us in the samples' optimisers, %.1f us retiring, %.1f us launching\n",
-                     dbg_samples, capacity, 1e3 * (wall_s() - dbg_t0), dbg_steps, (double)dbg_active / std::max(1L, dbg_steps),
-                     (double)dbg_points / std::max(1L, dbg_steps), lanes[0].count, 1e3 * dbg_blocked, 1e3 * dbg_refill,
-                     1e6 * dbg_wait / std::max(1L, dbg_steps), 1e6 * dbg_resume / std::max(1L, dbg_steps),
-                     1e6 * dbg_retire / std::max(1L, dbg_steps), 1e6 * dbg_launch / std::max(1L, dbg_steps));
-    return error;
+                     dbg_samples, capacity, 1e3 * (wall_s() - dbg_t0), team.steps, (double)team.active / per, (double)team.points / per, cnt[0],
+                     1e3 * dbg_blocked, 1e3 * dbg_refill, 1e6 * team.s_wait / per, 1e6 * team.s_resume / per, 1e6 * dbg_retire / per,
+                     1e6 * team.s_launch / per);
+    }
+    return team.error;
 }
 
 }  // namespace vb2

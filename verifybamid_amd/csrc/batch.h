@@ -15,6 +15,14 @@ namespace vb2 {
 int cohort_waves();                   // waves per workgroup of a cohort step: 8 (VB2_COHORT_BW=16|8|4)
 bool cohort_w16_enabled();            // cohort steps stream the 16-bit run lists (default; VB2_COHORT_W16=0 turns it off)
 
+// The lane policy of the lock-step searches (Batch::optimize, stream_search.h, what the reader threads prepare for them):
+constexpr int kMaxLanes = 4;
+// points a search of n samples (or n slots) evaluates per iteration: 4 or 2 (Tunables::cohort_speculate forces one)
+int search_speculate(int n);
+// The lanes that take turns in a search of n samples: their number (<= kMaxLanes) and sizes[l].  tuned: Tunables::cohort_split
+// and cohort_lanes apply -- only Batch::optimize listens to them (HISTORY.md has the finding).
+int search_lanes(int n, bool tuned, int* sizes);
+
 class Batch {
 public:
     ~Batch();
@@ -40,7 +48,7 @@ public:
     int eval(const int32_t* num_point, const double* pc1, const double* pc2, const double* alpha,
              double* llk_out);
     // the same in two halves: begin launches and returns, end waits and delivers (into the llk_out
-    // given to begin).  One step may be in flight per Batch.
+    // given to begin).  One step may be in flight per Batch (of a step of several launches, plan_step, the last one).
     int eval_begin(const int32_t* num_point, const double* pc1, const double* pc2, const double* alpha,
                    double* llk_out);
     int eval_end();
@@ -87,20 +95,26 @@ private:
     bool w16_ = true;                       // every sample has the 16-bit run lists: the steps stream those
     bool wide_rows_ = true;                 // every sample has kRowBytesWide table rows (8-point launches allowed)
     size_t shmem_[kShapes] = {0, 0, 0, 0};  // [shape]
-    int speculate_ = 4;                     // points a lock-step search evaluates per iteration (amoeba.h)
-    // the step in flight (eval_begin .. eval_end)
+    void scan_samples();                    // w16_ and wide_rows_ from ctx_
+    // One launch of a step: points [first, first + np[s]) of every sample s; wait: waited for even if it is the step's last
+    struct SubStep {
+        std::vector<int32_t> np;
+        int first;
+        bool wait;
+    };
+    void plan_step(const int32_t* num_point, std::vector<SubStep>* plan) const;    // (empty: num_point as it is, one launch)
+    int launch_step(const int32_t* np, int first, const double* pc1, const double* pc2, const double* alpha, double* llk_out);
+    void prefill_nan();
+    // the launch in flight (launch_step .. eval_end)
     bool in_flight_ = false;
-    bool in_split_ = false;                 // eval_begin is evaluating one request class of a mixed step
     MultiLaunch ml_{};
-    int flight_np_ = 0;
+    int flight_np_ = 0, flight_first_ = 0;
     double* flight_out_ = nullptr;
     // optimize() of a big cohort: two half-cohorts taking turns on the device (see batch.cpp)
-    static constexpr int kMaxLanes = 4;
     std::unique_ptr<Batch> half_[kMaxLanes];
     // the lanes' streams of optimize(): made back to back (different hardware queues: see cohort.cpp), lent to the lanes'
     // batches and to the batches their unfinished samples are regrouped into; they outlive half_
     hipStream_t lane_streams_[kMaxLanes] = {};
-    int optimize_range(const vb2_model* models, int num_model, vb2_estimate* out);
 };
 
 }  // namespace vb2

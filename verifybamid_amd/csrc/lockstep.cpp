@@ -5,8 +5,15 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cstring>
+#include <new>
+#include <string>
+
+#include "estimator.h"
 
 namespace vb2 {
+
+void set_error(const std::string& msg);         // (context.h, which this file stays clear of: it brings HIP in)
 
 namespace {
 constexpr size_t kFiberStack = 256 * 1024;      // the optimiser's frames are a few KB deep
@@ -145,6 +152,53 @@ int FiberGang::run(int num_pc, const std::function<void(int)>& body, const StepF
         resume_parked();
     }
     return error_;
+}
+
+int FiberGang::search(int i, const Search& cfg, const char* caller, vb2_estimate* out) noexcept
+{
+    try {
+        Estimator est(num_pc_, eval_cb, user(i));
+        apply_model(est, *cfg.model, cfg.data_has_known_af);
+        est.speculate = cfg.speculate;
+        est.line_search = cfg.line_search;
+        est.start_index = cfg.start_index;
+        est.start_seed = cfg.start_seed;
+        if (cfg.start_sd > 0) est.start_sd = cfg.start_sd;
+        const int rc = est.OptimizeLLK();
+        fill_estimate(est, out);
+        return rc;
+    } catch (const std::bad_alloc&) {
+        return VB2_ERR_NOMEM;
+    } catch (const std::exception& e) {
+        set_error(e.what());
+        return VB2_ERR_INVALID;
+    } catch (...) {                              // nothing may unwind past the fiber's entry frame
+        set_error(std::string(caller) + ": unknown exception in a search");
+        return VB2_ERR_INVALID;
+    }
+}
+
+FiberGang::StepFn FiberGang::concat_step(int num_pc, vb2_eval_fn eval, void* user)
+{
+    std::vector<double> p1, p2, al, vals;
+    return [=](std::vector<Request>& req) mutable {
+        p1.clear(); p2.clear(); al.clear();
+        for (const Request& r : req) {
+            if (r.n <= 0) continue;
+            p1.insert(p1.end(), r.p1, r.p1 + (size_t)r.n * num_pc);
+            p2.insert(p2.end(), r.p2, r.p2 + (size_t)r.n * num_pc);
+            al.insert(al.end(), r.a, r.a + r.n);
+        }
+        vals.resize(al.size());
+        if (const int rc = eval(user, (int32_t)al.size(), p1.data(), p2.data(), al.data(), vals.data())) return rc;
+        size_t o = 0;
+        for (Request& r : req) {
+            if (r.n <= 0) continue;
+            std::memcpy(r.out, &vals[o], sizeof(double) * r.n);
+            o += (size_t)r.n;
+        }
+        return 0;
+    };
 }
 
 }  // namespace vb2

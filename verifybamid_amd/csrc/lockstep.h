@@ -8,6 +8,9 @@
 // threads, no locks, no wake-ups: a step costs the host ~0.3 us per run where one thread per run
 // cost a futex round trip each (9 ms of CPU per sample and search at C3 size, and under a
 // container's CPU quota it throttled the readers and the search alike).
+//
+// Two helpers every user of a gang shares, no device in either: FiberGang::search, the body of a search fiber (one configured
+// OptimizeLLK to its rc and vb2_estimate), and FiberGang::concat_step, a step that answers all requests with ONE evaluator call.
 #ifndef VB2_LOCKSTEP_H_
 #define VB2_LOCKSTEP_H_
 
@@ -17,6 +20,8 @@
 #include <functional>
 #include <memory>
 #include <vector>
+
+#include "../../include/vb2_abi.h"
 
 namespace vb2 {
 
@@ -56,6 +61,22 @@ public:
     int spawn(int i);                                               // < 0: no context / stack
     bool idle(int i) const { return fibers_[i].done; }
     int size() const { return (int)fibers_.size(); }
+
+    // What the search of one fiber is configured with (estimator.h has the meaning of each field).
+    struct Search {
+        const vb2_model* model = nullptr;
+        bool data_has_known_af = false;     // (Context::L.known_af: apply_model)
+        int speculate = 4;
+        bool line_search = false;
+        int start_index = 0;
+        uint32_t start_seed = 0;
+        double start_sd = 0;                // <= 0: the Estimator's own
+    };
+    // For body(i): that search on fiber i's evaluator.  Fills *out when the optimiser returned and gives its code, or
+    // VB2_ERR_NOMEM / VB2_ERR_INVALID with the last error set (`caller` goes into the message for an unknown exception).
+    int search(int i, const Search& cfg, const char* caller, vb2_estimate* out) noexcept;
+    // a StepFn that evaluates the points of all requests with one call of eval(user, ...) and hands the values back
+    static StepFn concat_step(int num_pc, vb2_eval_fn eval, void* user);
 
 private:
     struct Fiber {

@@ -450,6 +450,52 @@ typedef struct vb2_cohort_args {
 int vb2_cohort_run(const vb2_cohort_args *args, vb2_run_result *out /* [num_sample] */,
                    int32_t *status /* [num_sample] */);
 
+/* ------------------------------------------------------------------------- *
+ * 3b. The source of a contamination within a cohort (--FindSource).  Not in the reference: it
+ *     follows its model (ContaminationEstimator.h:186-192, 285-311).  With W[g1][g2] = prod_reads P(read | g1, g2, alpha)
+ *     of a marker (g1 the alpha-fraction, contaminating genotype, g2 the intended one) and GF1, GF2 the genotype priors
+ *     at the two samples' allele frequencies:
+ *         L     = sum GF1[g1] GF2[g2] W[g1][g2]                 (h:307-309; the marker counts where L > 0, h:310)
+ *         c[g1] = (sum_g2 W[g1][g2] GF2[g2]) / L                contaminant-genotype likelihood relative to a random one
+ *         q[g2] = GF2[g2] (sum_g1 GF1[g1] W[g1][g2]) / L        posterior of the sample's own genotype
+ *     and for target i, candidate j:  S(i, j) = sum_m log max(c_i[m] . q_j[m], VB2_SOURCE_DOT_FLOOR)  over the markers
+ *     both count: the log-likelihood ratio of "i's contaminant carries j's genotypes" against "a random individual of
+ *     i's fitted contaminant ancestry".  S -> 0 as alpha_i -> 0 (c -> 1): a clean sample has no source.
+ * ------------------------------------------------------------------------- */
+#define VB2_SOURCE_DOT_FLOOR 1e-30     /* bounds what one marker can veto at -69 nats; part of the definition (the device
+                                        * compares float32 dots against its float32 rounding) */
+
+/* c, q and log L at ONE point, per marker in panel order: contam_lik [M][3], geno_post [M][3], log_l [M]; host pointers,
+ * any may be NULL; zeros for the markers the sample does not count.  sum_m log_l = vb2_llk_eval_batch at the point.
+ * Synchronous; not between vb2_ctx_search_begin and vb2_ctx_search_end. */
+int vb2_ctx_marginals(vb2_ctx *ctx, const double *pc1, const double *pc2, double alpha, double *contam_lik,
+                      double *geno_post, double *log_l);
+
+/* A set of samples of ONE panel on ONE device: per sample its c and q as float32, 24 bytes per marker, in device memory
+ * (capacity x num_marker x 24 bytes, reserved at creation: VB2_ERR_NOMEM with the bytes needed when they do not fit). */
+typedef struct vb2_source_set vb2_source_set;
+int vb2_source_set_create(int32_t num_marker, int32_t capacity, int32_t device, vb2_source_set **out);
+/* Adds the sample of `ctx` at the search's own point of `est` (the result of vb2_ctx_optimize_llk under `model`): the
+ * reported PCs with the swap of indices 0 and 1 undone, and -- when alpha >= 0.5 -- mirrored, pc1 <-> pc2 and alpha ->
+ * 1 - alpha (L(pc1, pc2, a) = L(pc2, pc1, 1 - a)), so that g1 is always the minor component.  The context may be destroyed
+ * afterwards.  *index: the sample's row and column in the score matrix.  Thread-safe. */
+int vb2_source_set_add(vb2_source_set *set, vb2_ctx *ctx, const vb2_model *model, const vb2_estimate *est, int32_t *index);
+/* score [n][n] (row = target, column = candidate; NAN on the diagonal) and shared [n][n] (markers both count), n = samples
+ * added; either may be NULL.  A pair's score is the same bits from call to call and whatever else the set holds. */
+int vb2_source_set_scores(vb2_source_set *set, double *score, int32_t *shared);
+/* n: the slots taken so far (a sample whose add failed after it took its slot keeps it, as a row and column of NAN). */
+int vb2_source_set_size(vb2_source_set *set, int32_t *n);
+void vb2_source_set_destroy(vb2_source_set *set);
+
+/* vb2_cohort_run that also adds every searched sample to a source set before its context is released (one device only:
+ * VB2_ERR_INVALID otherwise, before any file is read).  score / shared: [num_sample][num_sample] in the order of the
+ * samples, or NULL; a sample that failed has a row and a column of NAN.  With output prefixes it writes
+ * <output_prefix of base>.Sources -- tab-separated "#SAMPLE FREEMIX RANK CANDIDATE LLR MARKERS", per sample its `top`
+ * best candidates by descending LLR, samples and candidates named by their output prefixes.  Everything else is what
+ * vb2_cohort_run does and writes. */
+int vb2_cohort_run_sources(const vb2_cohort_args *args, int32_t top, vb2_run_result *out /* [num_sample] */,
+                           int32_t *status /* [num_sample] */, double *score, int32_t *shared);
+
 /* Host-side flattening only (no device): reads panel + pileup, resolves markers
  * and returns the arrays of vb2_input in library-owned memory; free with
  * vb2_flat_free.  Lets callers (tests, shard planners) inspect or slice them. */

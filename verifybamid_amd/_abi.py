@@ -168,6 +168,8 @@ SYMBOLS = [
     "vb2_shard_group_optimize_llk", "vb2_shard_group_info", "vb2_shard_group_destroy", "vb2_shard_range",
     "vb2_vcf_read", "vb2_vcf_get_view", "vb2_vcf_free", "vb2_panel_build", "vb2_panel_build_genotypes",
     "vb2_panel_get_view", "vb2_panel_write", "vb2_panel_destroy",
+    "vb2_ctx_marginals", "vb2_source_set_create", "vb2_source_set_add", "vb2_source_set_scores",
+    "vb2_source_set_destroy", "vb2_source_set_size", "vb2_cohort_run_sources",
 ]
 
 _lib = None
@@ -249,6 +251,15 @@ def lib():
     L.vb2_panel_write.argtypes = [C.c_void_p, C.c_char_p]
     L.vb2_panel_destroy.argtypes = [C.c_void_p]
     L.vb2_panel_destroy.restype = None
+    L.vb2_ctx_marginals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.vb2_source_set_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    L.vb2_source_set_add.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Model), C.POINTER(Estimate), C.POINTER(C.c_int32)]
+    L.vb2_source_set_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.vb2_source_set_size.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    L.vb2_source_set_destroy.argtypes = [C.c_void_p]
+    L.vb2_source_set_destroy.restype = None
+    L.vb2_cohort_run_sources.argtypes = [C.POINTER(CohortArgs), C.c_int32, C.POINTER(RunResult), C.POINTER(C.c_int32),
+                                         C.c_void_p, C.c_void_p]
     L.vb2_debug_set_tunable.argtypes = [C.c_char_p, C.c_int]
     L.vb2_debug_get_tunable.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
     _lib = L

@@ -236,6 +236,19 @@ class LikelihoodContext:
                    "vb2_llk_derivs_batch")
         return llk, grad, hess
 
+    def marginals(self, pc1, pc2, alpha):
+        """Per marker, in panel order, at ONE point (vb2_ctx_marginals): the contaminant-genotype likelihood relative to a
+        random contaminant c [M, 3], the posterior of the sample's own genotype q [M, 3] and log L [M]; zeros for the
+        markers the sample does not count.  g1 (c) is the alpha-fraction component, g2 (q) the other."""
+        pc1 = np.ascontiguousarray(np.asarray(pc1, dtype=np.float64).reshape(-1))
+        pc2 = np.ascontiguousarray(np.asarray(pc2, dtype=np.float64).reshape(-1))
+        assert pc1.shape == (self.num_pc,) and pc2.shape == (self.num_pc,)
+        M = self.data.num_marker
+        c, q, ll = np.zeros((M, 3)), np.zeros((M, 3)), np.zeros(M)
+        _abi.check(self._lib.vb2_ctx_marginals(self._h, _p(pc1), _p(pc2), float(alpha), _p(c), _p(q), _p(ll)),
+                   "vb2_ctx_marginals")
+        return c, q, ll
+
     def interval(self, estimate, **model_kw):
         """95% confidence interval for FREEMIX and standard errors at an estimate of optimize(**model_kw) on this context
         (vb2_ctx_interval): a dict with freemix, freemix_se, lo, hi, llk_max, llk_lo, llk_hi, pos_def and the .CI rows."""
@@ -302,6 +315,65 @@ class LikelihoodContext:
         out = _estimate_dict(best, self.num_pc)
         out["start"] = int(best.reserved)
         return out, [_estimate_dict(every[i], self.num_pc) for i in range(n)]
+
+
+def _estimate_struct(estimate, k):
+    est = _abi.Estimate()
+    est.alpha, est.llk1, est.llk0 = estimate["alpha"], estimate.get("llk1", 0.0), estimate.get("llk0", 0.0)
+    for j in range(k):
+        est.pc[j] = float(estimate["pc"][j])
+        est.pc2[j] = float(estimate["pc2"][j])
+    est.converged = int(bool(estimate.get("converged", True)))
+    return est
+
+
+class SourceSet:
+    """vb2_source_set: the genotype marginals of a cohort's samples (float32, 24 bytes per marker and sample, on one
+    device) and every pair's source score S(target, candidate): the log-likelihood ratio of "the target's contaminant
+    carries the candidate's genotypes" against "a random individual of the target's fitted contaminant ancestry"."""
+
+    def __init__(self, num_marker, capacity, device=-1):
+        self._lib = _abi.lib()
+        h = C.c_void_p()
+        _abi.check(self._lib.vb2_source_set_create(int(num_marker), int(capacity), int(device), C.byref(h)),
+                   "vb2_source_set_create")
+        self._h = h
+
+    @property
+    def count(self):
+        """Slots taken so far, as the library counts them (vb2_source_set_size)."""
+        n = C.c_int32(0)
+        _abi.check(self._lib.vb2_source_set_size(self._h, C.byref(n)), "vb2_source_set_size")
+        return n.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.vb2_source_set_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def add(self, ctx, estimate, **model_kw):
+        """Adds the sample of a LikelihoodContext at an estimate of its optimize(**model_kw); returns its index."""
+        m, keep = _model(known_af=ctx.data.known_af is not None, **model_kw)
+        est = _estimate_struct(estimate, ctx.num_pc)
+        idx = C.c_int32(-1)
+        _abi.check(self._lib.vb2_source_set_add(self._h, ctx._h, C.byref(m), C.byref(est), C.byref(idx)),
+                   "vb2_source_set_add")
+        return idx.value
+
+    def scores(self):
+        """(score [n, n] float64, NaN on the diagonal; shared [n, n] int32): row = target, column = candidate."""
+        n = self.count
+        score, shared = np.zeros((n, n)), np.zeros((n, n), dtype=np.int32)
+        _abi.check(self._lib.vb2_source_set_scores(self._h, _p(score), _p(shared)), "vb2_source_set_scores")
+        return score, shared
 
 
 class CohortBatch:
@@ -529,12 +601,16 @@ def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_san
 
 def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, disable_sanity=False,
                      known_af_path=None, device=-1, output_pileup=False, group_size=0, num_host_thread=0,
-                     devices=None, **model_kw):
+                     devices=None, find_source=False, source_top=3, sources_prefix=None, **model_kw):
     """Many pileups against one panel (vb2_cohort_run): the panel is read once, the pileups are read
     and flattened by host threads while the device searches the previous group in lock-step.
-    Returns one dict per sample (with its own "status" code)."""
+    Returns one dict per sample (with its own "status" code).
+    find_source (vb2_cohort_run_sources; one device): returns (samples, sources), sources = dict(score [S, S] -- row =
+    target, column = candidate, NaN on the diagonal and for failed samples --, shared [S, S]); with output_prefixes and
+    sources_prefix it writes <sources_prefix>.Sources, source_top candidates per sample."""
     S = len(pileup_paths)
-    args, keep = _run_args(svd_prefix, pileup_paths[0], num_pc, disable_sanity, known_af_path, None,
+    args, keep = _run_args(svd_prefix, pileup_paths[0], num_pc, disable_sanity, known_af_path,
+                           sources_prefix if find_source else None,
                            device, output_pileup, devices=devices, **model_kw)
     ca = _abi.CohortArgs()
     ca.base = args
@@ -549,7 +625,13 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
     ca.num_host_thread = int(num_host_thread)
     res = (_abi.RunResult * S)()
     status = (C.c_int32 * S)()
-    _abi.check(_abi.lib().vb2_cohort_run(C.byref(ca), res, status), "vb2_cohort_run")
+    score = shared = None
+    if find_source:
+        score, shared = np.zeros((S, S)), np.zeros((S, S), dtype=np.int32)
+        _abi.check(_abi.lib().vb2_cohort_run_sources(C.byref(ca), int(source_top), res, status, _p(score), _p(shared)),
+                   "vb2_cohort_run_sources")
+    else:
+        _abi.check(_abi.lib().vb2_cohort_run(C.byref(ca), res, status), "vb2_cohort_run")
     out = []
     for s in range(S):
         d = _estimate_dict(res[s].est, num_pc)
@@ -557,6 +639,8 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
                  num_bases=int(res[s].num_bases), avg_depth=res[s].avg_depth, sd_depth=res[s].sd_depth,
                  seconds_load=res[s].seconds_load, seconds_optimize=res[s].seconds_optimize)
         out.append(d)
+    if find_source:
+        return out, dict(score=score, shared=shared)
     return out
 
 

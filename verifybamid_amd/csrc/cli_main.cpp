@@ -67,6 +67,8 @@ int main(int argc, char** argv)
     int seed = 12345, nPC = 2, nthread = 4, device = -1, numStart = 1;
     bool lineSearch = false;
     bool confidenceInterval = false;
+    bool findSource = false;
+    int sourceTop = 3;
     // "Pileup Options" (main.cpp:176-187), defaults main.cpp:81-96 (MPLP_REALN | MPLP_SMART_OVERLAPS; UNMAP | SECONDARY |
     // QCFAIL | DUP): they shape what --BamFile input becomes and, as in the reference, do nothing to --PileupFile input
     int minBQ = 13, minMQ = 2, adjustMQ = 40, maxDepth = 8000, inclFlags = (1 << 4) | (1 << 10), exclFlags = 0x4 | 0x100 | 0x200 | 0x400;
@@ -118,6 +120,10 @@ int main(int argc, char** argv)
         // not in the reference: a 95% confidence interval for FREEMIX (profile likelihood) and standard errors of the free
         // parameters, written to <Output>.CI (vb2_run_interval)
         {"ConfidenceInterval", {Flag::kBool, &confidenceInterval, false}},
+        // not in the reference: which sample of the --PileupList cohort does each sample's contamination come from?  Every
+        // pair's log-likelihood ratio (vb2_cohort_run_sources); the --SourceTop best candidates per sample go to <Output>.Sources
+        {"FindSource", {Flag::kBool, &findSource, false}},
+        {"SourceTop", {Flag::kInt, &sourceTop, false}},
     };
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
@@ -154,6 +160,13 @@ int main(int argc, char** argv)
             fatal("--ConfidenceInterval cannot be combined with --PileupList: intervals are computed for one sample per run");
         if (Devices != "Empty" && Devices.find(',') != std::string::npos)
             fatal("--ConfidenceInterval cannot be combined with more than one --Devices: intervals are computed on one device");
+    }
+    if (findSource) {                                                   // a cohort on one device
+        if (PileupList == "Empty")
+            fatal("--FindSource needs --PileupList: the source of a contamination is looked for among the samples of one cohort run");
+        if (Devices != "Empty" && Devices.find(',') != std::string::npos)
+            fatal("--FindSource cannot be combined with more than one --Devices: a source set lives on one device");
+        if (sourceTop < 1) fatal("--SourceTop takes a positive number of candidates");
     }
     // --Seed: parsed and never used by the reference (main.cpp:137,286); here it seeds --NumStart's starting points
     // --NumThread: the likelihood runs on the GPU; the VCF parser pool of --RefVCF and the reader threads of --PileupList use it
@@ -291,7 +304,8 @@ int main(int argc, char** argv)
         ca.num_host_thread = nthread > 4 ? nthread : 0;               // --NumThread above its default: reader threads
         std::vector<vb2_run_result> cres(pile.size());
         std::vector<int32_t> cst(pile.size());
-        const int rcc = vb2_cohort_run(&ca, cres.data(), cst.data());
+        const int rcc = findSource ? vb2_cohort_run_sources(&ca, sourceTop, cres.data(), cst.data(), nullptr, nullptr)
+                                   : vb2_cohort_run(&ca, cres.data(), cst.data());
         if (rcc != VB2_OK) {
             std::fprintf(stderr, "\nFATAL ERROR - \n%s\n\n", vb2_last_error());
             return EXIT_FAILURE;

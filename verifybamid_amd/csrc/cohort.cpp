@@ -28,6 +28,7 @@
 #include "context.h"
 #include "estimator.h"
 #include "hostio.h"
+#include "source.h"
 #include "stream_search.h"
 #include "tunables.h"
 
@@ -49,8 +50,12 @@ struct Slot {
 
 class CohortRunner {
 public:
-    CohortRunner(const vb2_cohort_args* a, vb2_run_result* out, int32_t* status)
-        : a_(a), out_(out), status_(status), S_(a->num_sample)
+    // find_source: every searched sample also goes into a source set (vb2_cohort_run_sources) -- on the releaser thread,
+    // before its context is destroyed; score / shared ([S][S], may be null) and <Output>.Sources after the last sample
+    CohortRunner(const vb2_cohort_args* a, vb2_run_result* out, int32_t* status, bool find_source = false, int top = 0,
+                 double* score = nullptr, int32_t* shared = nullptr)
+        : a_(a), out_(out), status_(status), S_(a->num_sample), find_source_(find_source), top_(top), score_(score),
+          shared_(shared)
     {
         if (a->base.devices && a->base.num_device > 0) devices_.assign(a->base.devices, a->base.devices + a->base.num_device);
         else devices_.push_back(a->base.device);
@@ -129,6 +134,14 @@ public:
         const double t_warm = now_s();
         model_ = a_->base.model;
         if (panel_->isAFknown) model_.is_af_known = 1;
+        if (find_source_) {
+            vb2::SourceSet* set = nullptr;
+            if (const int rcs = vb2::SourceSet::create((int)panel_->NumMarker, S_, devices_[0], &set)) {
+                err_all_ = vb2::g_last_error;
+                return rcs;
+            }
+            sources_.reset(set);
+        }
         vb2::g_flatten_thread_cap.store(std::max(1, 16 / T_));
 
         // HIP maps a process's streams onto FOUR hardware queues per device, each in order.  A context's creation (uploads, the
@@ -159,6 +172,7 @@ public:
         dev_threads_.clear();
         const double t_dev = now_s();
         shutdown();
+        if (sources_ && !rc_all_) rc_all_ = finish_sources();
         if (timing)
             std::fprintf(stderr, "vb2_cohort_run: panel %.1f ms, HIP start-up beyond that %.1f ms, pipelines %.1f ms, "
                                  "shutdown (release contexts, join) %.1f ms; releaser: %.2f ms per context, %.2f ms per sample's host arrays\n",
@@ -205,7 +219,32 @@ private:
     std::vector<int> inflight_;            // [device] samples handed to a reader and not yet done
     std::vector<int> remaining_;           // [device] samples not yet delivered to the search (or failed before it)
     std::vector<std::deque<int>> ready_q_; // [device] prepared samples, in the order they became ready
-    struct Done { int s; vb2_ctx* ctx; std::unique_ptr<vb2_flat> flat; bool write; vb2_estimate est; };
+    struct Done { int s; vb2_ctx* ctx; std::unique_ptr<vb2_flat> flat; bool write; vb2_estimate est; bool add = false; };
+    // --FindSource (null without it: nothing below then differs from a plain run)
+    bool find_source_ = false;
+    int top_ = 0;
+    double* score_ = nullptr;
+    int32_t* shared_ = nullptr;
+    std::unique_ptr<vb2::SourceSet> sources_;
+
+    // after the last context is gone: the matrix, and <Output>.Sources next to the samples' own files
+    int finish_sources()
+    {
+        sources_->set_count(S_);
+        const size_t nn = (size_t)S_ * (size_t)S_;
+        std::vector<double> sc;
+        std::vector<int32_t> sh;
+        const bool file = a_->output_prefixes && a_->base.output_prefix;
+        double* score = score_;
+        int32_t* shared = shared_;
+        if (file && !score) { sc.resize(nn); score = sc.data(); }
+        if (file && !shared) { sh.resize(nn); shared = sh.data(); }
+        if (!score && !shared) return VB2_OK;
+        int rc = sources_->scores(score, shared);
+        if (!rc && file) rc = vb2::write_sources(a_->base.output_prefix, S_, top_, a_->output_prefixes, out_, status_, score, shared);
+        if (rc) err_all_ = vb2::g_last_error;
+        return rc;
+    }
     std::deque<Done> done_queue_;          // (rel_mu_) searched samples: outputs to write, context and arrays to free
 
     int device_of_group(int gi) const { return gi % ndev_; }
@@ -348,6 +387,7 @@ private:
             std::lock_guard<std::mutex> lk(rel_mu_);
             Done d{s, slots_[s].ctx, std::move(slots_[s].flat), write, vb2_estimate{}};
             if (est) d.est = *est;
+            d.add = write && est;
             slots_[s].ctx = nullptr;
             done_queue_.push_back(std::move(d));
         }
@@ -448,6 +488,13 @@ private:
                         if (!rw) rw = vb2::write_selfsm(prefix, *d.flat, d.est, true);   // (cohort input is text pileups: #READS = NA)
                         if (rw) status_[d.s] = rw;
                     }
+                    if (sources_ && d.add && d.ctx && d.ctx->impl && status_[d.s] == VB2_OK) {
+                        // (a sample whose row cannot be made keeps its files and its status -- it was searched and written as
+                        // the plain run does it --; its row and column of the matrix are NaN and a NOTICE says why)
+                        if (sources_->put(d.s, d.ctx->impl, model_, d.est))
+                            std::fprintf(stderr, "NOTICE - --FindSource: sample %d has no row in the source set: %s\n", d.s,
+                                         vb2::g_last_error.c_str());
+                    }
                     item.first = d.ctx;
                     item.second = std::move(d.flat);
                 } else {
@@ -526,7 +573,13 @@ private:
                 // per context: hand the group to the releaser thread and move on
                 std::lock_guard<std::mutex> lk(rel_mu_);
                 for (int s = g0; s < g1; ++s) {
-                    rel_queue_.emplace_back(slots_[s].ctx, std::move(slots_[s].flat));
+                    if (sources_) {              // (the releaser adds the sample to the source set first; its files are written)
+                        Done d{s, slots_[s].ctx, std::move(slots_[s].flat), false, out_[s].est};
+                        d.add = !rcb && status_[s] == VB2_OK && slots_[s].ctx != nullptr;
+                        done_queue_.push_back(std::move(d));
+                    } else {
+                        rel_queue_.emplace_back(slots_[s].ctx, std::move(slots_[s].flat));
+                    }
                     slots_[s].ctx = nullptr;
                 }
             }
@@ -578,6 +631,32 @@ extern "C" int vb2_cohort_run(const vb2_cohort_args* a, vb2_run_result* out, int
             }
     try {
         CohortRunner runner(a, out, status);
+        const int rc = runner.run();
+        if (rc && !runner.error().empty()) set_error(runner.error());
+        return rc;
+    } catch (const std::bad_alloc&) {
+        set_error("out of host memory");
+        return VB2_ERR_NOMEM;
+    } catch (const std::exception& e) {
+        set_error(e.what());
+        return VB2_ERR_INVALID;
+    }
+}
+
+extern "C" int vb2_cohort_run_sources(const vb2_cohort_args* a, int32_t top, vb2_run_result* out, int32_t* status, double* score,
+                                      int32_t* shared)
+{
+    if (!a || !out || !status || a->num_sample < 1 || !a->pileup_paths || !a->base.ud_path || !a->base.mean_path ||
+        !a->base.bed_path || a->base.num_pc < 1 || a->base.num_pc > VB2_MAX_PC || top < 0) {
+        set_error("vb2_cohort_run_sources: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    if (a->base.num_device > 1 || a->base.num_device < 0) {
+        set_error("--FindSource takes one device: a source set is not spread over several --Devices");
+        return VB2_ERR_INVALID;
+    }
+    try {
+        CohortRunner runner(a, out, status, true, top, score, shared);
         const int rc = runner.run();
         if (rc && !runner.error().empty()) set_error(runner.error());
         return rc;

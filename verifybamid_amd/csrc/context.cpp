@@ -197,6 +197,8 @@ Context::~Context()
     if (h_trace_stage) (void)hipHostFree(h_trace_stage);
     if (d_codes16_own) (void)hipFree(d_codes16_own);
     if (d_deriv && !slab_cache().give(slab_cache().dev, d_deriv, d_deriv_bytes, device)) (void)hipFree(d_deriv);
+    if (d_marg && !slab_cache().give(slab_cache().dev, d_marg, d_marg_bytes, device)) (void)hipFree(d_marg);
+    if (d_pidx && !slab_cache().give(slab_cache().dev, d_pidx, d_pidx_bytes, device)) (void)hipFree(d_pidx);
     for (CohortSched& e : cohort_sched_)
         if (e.d_mem && !slab_cache().give(slab_cache().dev, e.d_mem, e.bytes, device)) (void)hipFree(e.d_mem);
     if (own_stream && stream && !slab_cache().give_stream(stream, device)) (void)hipStreamDestroy(stream);
@@ -1945,7 +1947,7 @@ int Context::create_impl(const vb2_input* in, const vb2_options* opt, Context** 
         pass_a_host(in, rd, *tables, dict, nthr, md.pd_wanted, &a);
     }
     tm.pass1 = Clock::now();
-    const ActiveList al = active_list(a.eff_all, M);
+    ActiveList al = active_list(a.eff_all, M);
     const int64_t m_active = (int64_t)al.active.size();
     tm.act = Clock::now();
 
@@ -2021,6 +2023,9 @@ int Context::create_impl(const vb2_input* in, const vb2_options* opt, Context** 
                      md.device_pack ? "+pack kernels" : "", ms_between(tm.flat, Clock::now()));
         if (md.device_flatten) std::fprintf(stderr, "  upload + classify_kernel + read-back: %.2f ms\n", ms_between(a.staged, tm.pass1));
     }
+    // (what vb2_ctx_marginals needs to write in panel order: kept, not copied -- Context::ensure_pidx)
+    c->h_active = std::move(al.active);
+    c->h_perm = std::move(tl.perm);
     *out = c.release();
     return VB2_OK;
 }

@@ -157,6 +157,21 @@ public:
                     double* hess);
     double* d_deriv = nullptr;
     size_t d_deriv_bytes = 0;
+    // Genotype marginals at one point (source_kernels.hip; defined in source.cpp): the contaminant's genotype likelihood
+    // c [M][3], the posterior of the sample's own genotype q [M][3] and log L [M], in panel order, zeros for markers the
+    // sample does not count.  Host pointers (any may be null), synchronous; d_row: a device row of a source set (float32
+    // planes c | q, kSourceRowFloats * M floats) written on the context's stream, or null.  Not inside a resident search.
+    int marginals(const double* pc1, const double* pc2, double alpha, double* contam_lik, double* geno_post, double* log_l,
+                  float* d_row);
+    // sorted position -> panel marker on the device, uploaded on first use (the flatten keeps only the two host vectors it
+    // sorted with: h_perm[position] indexes h_active, the counted markers' panel rows)
+    int ensure_pidx();
+    std::vector<int32_t> h_active;
+    std::vector<int64_t> h_perm;
+    int32_t* d_pidx = nullptr;
+    size_t d_pidx_bytes = 0;
+    void* d_marg = nullptr;                   // scratch of marginals(): the point's row and the three double outputs
+    size_t d_marg_bytes = 0;
 
     int device = -1;
     int num_marker = 0;

@@ -1,0 +1,51 @@
+// source.h -- vb2_source_set internals (source.cpp): the float32 marginals of a cohort's samples on one device and
+// their pairwise source scores (source_kernels.hip).
+#ifndef VB2_SOURCE_H_
+#define VB2_SOURCE_H_
+
+#include <hip/hip_runtime_api.h>
+
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "context.h"
+
+namespace vb2 {
+
+class SourceSet {
+public:
+    static int create(int num_marker, int capacity, int device, SourceSet** out);
+    ~SourceSet();
+    // the next free slot (add) or a given one (put: a cohort's samples retire in any order); thread-safe
+    int add(Context* ctx, const vb2_model& model, const vb2_estimate& est, int* index);
+    int put(int slot, Context* ctx, const vb2_model& model, const vb2_estimate& est);
+    // slots [0, n) count as added, with or without a row (a cohort's failed samples: NaN)
+    void set_count(int n);
+    int count();
+    int scores(double* score, int32_t* shared);
+    // Measurement aids (tools/source_time.py; event-timed, milliseconds per repetition into ms[reps]): the pair kernels
+    // over n synthetic rows (seeded non-negative triples; what was in the set is overwritten), and the marginal kernel of
+    // a context into slot 0 (the row's memset included, as an add pays it).
+    int time_pairs(int n, uint32_t seed, int warmup, int reps, double* ms);
+    int time_marginals(Context* ctx, double alpha, int warmup, int reps, double* ms);
+
+private:
+    int device_ = -1, num_marker_ = 0, capacity_ = 0, n_ = 0;
+    float* d_slab_ = nullptr;
+    hipStream_t stream_ = nullptr;
+    std::vector<const float*> rows_;         // [capacity] device rows, nullptr = none
+    std::mutex mu_;
+};
+
+// <prefix>.Sources (vb2_cohort_run_sources): per sample its `top` best candidates by descending score
+int write_sources(const std::string& prefix, int n, int top, const char* const* names, const vb2_run_result* res,
+                  const int32_t* status, const double* score, const int32_t* shared);
+
+}  // namespace vb2
+
+struct vb2_source_set {
+    vb2::SourceSet* impl;
+};
+
+#endif

@@ -23,6 +23,15 @@
 //   VB2_SPLIT_FAST=mask the short head and tail of a split launch (eval_body, SPLIT), each part on its own for A/B builds (default: all):
 //                         1 the tables are built from records and alphas requested at kernel entry, not from the staged copies
 //                         2 one arrival ticket per share of the point groups: each share's last workgroup adds up that share's points
+//   VB2_READS_AHEAD=0xRNPS how a row word of the probability-domain walk (eval_body, walk_pd) orders its table reads and its multiplies, one
+//                       hex digit per kernel family -- S llk_eval_split_kernel, P the plain 8-point launch llk_eval_kernel<2, ...>, N the
+//                       4-point and narrower launches llk_eval_kernel<3..5, ...>, R the resident search kernel (default 0x0111):
+//                         0 as the scheduler likes it: four landing quads, a step's six reads in three dependent round trips
+//                         1 a row at a time: both steps' twelve reads, then their multiplies (a drain per two rows of the loop)
+//                         2 a step at a time: a step's six reads, then its multiplies (a drain per step)
+//                         3 as 1, and a tile's last row also requests the epilogue's 2 k projection coefficients before it multiplies (KSEL 2, 4)
+//                         4 as 3 with the coefficients of the first two components only (four quads)
+//                       (the cohort kernels and the pass-per-group kernel keep 0: with 1 some of them spill; R: see HISTORY.md)
 #ifndef VB2_KERNEL_DEBUG_H_
 #define VB2_KERNEL_DEBUG_H_
 
@@ -41,6 +50,9 @@
 #ifndef VB2_SPLIT_FAST
 #define VB2_SPLIT_FAST 3
 #endif
+#ifndef VB2_READS_AHEAD
+#define VB2_READS_AHEAD 0x0111
+#endif
 #ifndef VB2_STAMP_ROUND
 #define VB2_STAMP_ROUND 0
 #endif
@@ -49,6 +61,8 @@ namespace vb2 {
 constexpr int kAblNoMap = 1, kAblNoTable = 2, kAblNoItems = 4, kAblNoReads = 8, kAblNoEpi = 16, kAblNoSignal = 32, kAblNoMul = 64, kAblNoRowLoads = 128;
 constexpr int kAblate = VB2_ABLATE;
 constexpr int kSplitFast = VB2_SPLIT_FAST;
+constexpr int kReadsAheadMask = VB2_READS_AHEAD;
+constexpr int reads_ahead(int family) { return (kReadsAheadMask >> (4 * family)) & 0xf; }      // family: 0 S, 1 P, 2 N, 3 R
 }  // namespace vb2
 
 #ifdef VB2_WITH_STAMPS

@@ -502,12 +502,17 @@ __host__ __device__ __forceinline__ bool eval_is_dynamic(const DeviceLayout& L, 
 // started (a workgroup owns the same micro-tiles in every round), so a round's read loops begin without the two dependent
 // trips to L2 (tile record, then its first rows) and never wait for a row again.
 // ESH: log2 of the byte stride between the entries of exp_nonpos's table (8: conflict-free; 6: the compact copy).
-// (Measured and dropped over the rounds, all bit-identical: a software-pipelined item loop, a run-ahead ring of table reads,
-// the next item drawn a whole item early, two half-sized workgroups per CU -- HISTORY.md.)
+// (Measured and dropped over the rounds, all bit-identical: a software-pipelined item loop, the next item drawn a whole item
+// early, two half-sized workgroups per CU; of table reads that run ahead of their multiplies: a ring that carries reads ACROSS
+// the steps of the run-word kernel -- rounds 3 and 4: 128 registers and spills, slower -- and eight to ten reads in flight in
+// the search round's single item per wave -- round 5: equal, that regime is bound by the deepest wave's latency.  Kept: the
+// probability-domain walk requests a row word's twelve reads before it multiplies, RAHEAD below -- HISTORY.md.)
 // PD: a probability-domain context (DeviceLayout::pd; llk_kernels.h, kMaxPow): the table holds P^n rows of class ref only,
 // a marker's list is one 16-bit row offset per step, ref steps first and alt steps behind them; the six sums are PRODUCTS,
 // class alt multiplies them with the row read the other way round (g -> 2 - g, h:164-177: T[alt][q][g1][g2] is T[ref][q][2-g1][2-g2]),
 // and the epilogue needs no exponential.  Only for contexts whose markers cannot underflow that way (Context::create).
+// RAHEAD: how a row word of the probability-domain walk orders its table reads and its multiplies (walk_pd; reads_ahead() below
+// gives every kernel its digit of VB2_READS_AHEAD): 0 as the scheduler likes it, 1 a row's reads first, 2 a step's reads first.
 // SPLIT (a probability-domain launch of more points than a workgroup's LDS holds tables for -- a dictionary of ~100 rows and 48
 // points): the workgroups come in PAIRS that share their tiles and split the point groups -- workgroup 2v takes the first
 // half of the groups, 2v + 1 the second, both over the tiles of the VIRTUAL blocks v and v + grid / 2, i.e. over exactly the
@@ -515,7 +520,7 @@ __host__ __device__ __forceinline__ bool eval_is_dynamic(const DeviceLayout& L, 
 // multiplied in the same order and its sum goes to the same word of the partial sums as in a plain launch of this grid:
 // the same bits, and no second pass over the tiles (llk_eval_passes_kernel: +4 us per pass at C3).
 template <int MODE, bool W16 = false, class Hook = NoHook, bool STREAM = false, int QUEUE = -1, int KSEL = 0,
-          bool LCACHE = false, int ESH = 8, bool PD = false, int SPLIT = 0>
+          bool LCACHE = false, int ESH = 8, bool PD = false, int SPLIT = 0, int RAHEAD = 0>
 __device__ __forceinline__ void
 eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const double* __restrict__ points, int num_valid,
           double* __restrict__ partials, double* __restrict__ llk_out,
@@ -540,9 +545,24 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
     constexpr int TPW = MODE == 3 ? 2 : (MODE == 4 || MODE == 5) ? 4 : 1;   // micro-tiles per wave
     constexpr int SLOTS = 4 / TPW;                           // candidate slots per wave
     constexpr int NP = SLOTS * BTL;
-    const int row_bytes = MODE == 2 ? kRowBytesWide : L.row_bytes;      // (the 8-point shape needs the wide rows: the launcher sees to it)
+    constexpr int kReadsAhead = PD ? RAHEAD : 0;    // how far walk_pd's table reads run ahead of its multiplies (reads_ahead)
+    // (the run-word kernels of the static deal in the paired shapes: the layout's four sizes in scalar registers of their own.
+    // Under those kernels' scalar pressure the register allocator gave up the {num_code, row_bytes, num_prim, num_mt} quad of the
+    // kernel arguments, loaded it again at each of six uses and left the quad's spill slot behind: scratch memory set up for
+    // every launch that no instruction touches)
+    constexpr bool kOwnSizes = QUEUE == 0 && KSEL == 0 && !PD && !STREAM && (MODE == 3 || MODE == 4) && std::is_same<Hook, NoHook>::value;    // llk_eval_kernel<3, 0, 0, false>, <4, 0, 0, false>: no others
+    int own_num_code = 0, own_row_bytes = 0, own_num_prim = 0, own_num_mt = 0;
+    if constexpr (kOwnSizes) {
+        own_num_code = L.num_code; own_row_bytes = L.row_bytes; own_num_prim = L.num_prim; own_num_mt = L.num_mt;
+        asm volatile("" : "+s"(own_num_code), "+s"(own_row_bytes), "+s"(own_num_prim), "+s"(own_num_mt));
+    }
+    const auto l_num_code = [&] { if constexpr (kOwnSizes) return own_num_code; else return L.num_code; };
+    const auto l_row_bytes = [&] { if constexpr (kOwnSizes) return own_row_bytes; else return L.row_bytes; };
+    const auto l_num_prim = [&] { if constexpr (kOwnSizes) return own_num_prim; else return L.num_prim; };
+    const auto l_num_mt = [&] { if constexpr (kOwnSizes) return own_num_mt; else return L.num_mt; };
+    const int row_bytes = MODE == 2 ? kRowBytesWide : l_row_bytes();      // (the 8-point shape needs the wide rows: the launcher sees to it)
     const int RS = row_bytes >> 3;              // doubles per table row (>= 6 * NP + 2)
-    const int nrow = L.num_code + 1;
+    const int nrow = l_num_code() + 1;
     const int nthread = blockDim.x;
     const int nwave = nthread >> 6;
     const int k = KSEL > 0 ? KSEL : L.num_pc;
@@ -574,7 +594,7 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
     double* ptq = pts + (size_t)NPT * stride + ((NPT * stride) & 1);
     const size_t prim_off = (size_t)(ptq - lds) + (size_t)NPT * 2 * k;
     double2* prim_lds = reinterpret_cast<double2*>(lds + prim_off + (prim_off & 1));   // [num_prim], 16-B aligned
-    double* tile_llk = reinterpret_cast<double*>(prim_lds + L.num_prim);   // [work items or waves][NP] {mantissa, exponent}
+    double* tile_llk = reinterpret_cast<double*>(prim_lds + l_num_prim());   // [work items or waves][NP] {mantissa, exponent}
 
     // (tid_in: the resident kernel passes its thread index through an opaque register each round,
     // so that nothing derived from it is hoisted out of the round loop and kept alive across it)
@@ -635,7 +655,7 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
     // many groups; kSplitFast & 1).  The same numbers into the same expressions.
     constexpr bool SPLIT_EARLY = SPLIT != 0 && (kSplitFast & 1) != 0;
     constexpr int kTabSide = 3;                       // groups whose entries a thread builds side by side (see the table loop)
-    const int ntab_split = (kAblate & kAblNoTable) ? 0 : (PD ? L.num_prim - L.num_pair : L.num_prim) * 6 * NP;
+    const int ntab_split = (kAblate & kAblNoTable) ? 0 : (PD ? l_num_prim() - L.num_pair : l_num_prim()) * 6 * NP;
     auto table_inputs = [&](int e, int g0, double2& rec_o, double* al_o) {
         const int pi = e / (6 * NP);
         const int bb = (e - pi * (6 * NP)) / 6;
@@ -687,7 +707,7 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
     const bool prim_kept = hook.prim_in_lds() && hook.keep_prim();
     const bool staged = ngrp > 1 || (hook.prim_in_lds() && !prim_kept) || (PD && L.num_pair > 0 && !prim_kept);      // (pair rows: their records from LDS)
     if (staged)
-        for (int e = ptid; e < L.num_prim; e += pnthread) prim_lds[e] = L.prim[e];
+        for (int e = ptid; e < l_num_prim(); e += pnthread) prim_lds[e] = L.prim[e];
     // A search round (its rows are in LDS since the round's staging barrier) builds its one table without waiting
     // for the copies above: the table needs the alphas only, and takes them from the staged rows (-0.6 us per
     // round; the same for launches whose rows come with the kernel arguments: no gain, not kept).
@@ -704,7 +724,7 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
     // (a thread's entries for the different groups are independent: computed side by side so
     // that their long dependent logarithm chains overlap)
     const uint32_t ltab_addr = lds_byte_addr(ltab);
-    const int num_single = PD ? L.num_prim - L.num_pair : L.num_prim;
+    const int num_single = PD ? l_num_prim() - L.num_pair : l_num_prim();
     if constexpr (SPLIT_EARLY) {
         // (the loop below on inputs that are in registers: the next step's are requested before this step's entries are computed)
         int e = ptid, g0 = 0;
@@ -828,7 +848,7 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
     }
     for (int e = ptid; e < ngrp * RS; e += pnthread) {                // padding code: zero rows (PD: ones)
         const int grp_e = e / RS;
-        tab[((size_t)grp_e * nrow + L.num_code) * RS + (e - grp_e * RS)] = PD ? 1.0 : 0.0;
+        tab[((size_t)grp_e * nrow + l_num_code()) * RS + (e - grp_e * RS)] = PD ? 1.0 : 0.0;
     }
     if constexpr (PD) {
         // ---- pair rows (PdDict): the product of two of the rows above, entry by entry -- one record per row
@@ -869,9 +889,9 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
     // an A/B knob -- pulled longest-first through an LDS counter, each item's product going to its
     // own LDS slot.  Either way the multiplication order is fixed, so the schedule does not
     // change a single bit of the result.
-    const uint32_t nt_v0 = owned_count(OSH, (uint32_t)L.num_mt, vb0, nblk);
-    const uint32_t nt_v1 = SPLIT ? owned_count(OSH, (uint32_t)L.num_mt, vb0 + vstep, nblk) : 0u;
-    const uint32_t nt_v2 = SPLIT > 2 ? owned_count(OSH, (uint32_t)L.num_mt, vb0 + 2u * vstep, nblk) : 0u;
+    const uint32_t nt_v0 = owned_count(OSH, (uint32_t)l_num_mt(), vb0, nblk);
+    const uint32_t nt_v1 = SPLIT ? owned_count(OSH, (uint32_t)l_num_mt(), vb0 + vstep, nblk) : 0u;
+    const uint32_t nt_v2 = SPLIT > 2 ? owned_count(OSH, (uint32_t)l_num_mt(), vb0 + 2u * vstep, nblk) : 0u;
     auto nt_of = [&](uint32_t vs) { return vs == 0u ? nt_v0 : vs == 1u ? nt_v1 : nt_v2; };
     // (SPLIT: per virtual block, the largest -- virtual block vb0 has it: owned_count does not grow with the block index)
     const uint32_t ntile_blk = nt_v0;
@@ -1066,10 +1086,67 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
     // ---- PD: one word of the list = two steps.  A step multiplies the six products of every point by ONE table row; class alt
     // (the rows behind the tile's ref rows: alt_tag) by the same row read the other way round, pair p <-> 5 - p.  No count, no
     // conversion: one SDWA add per step and the multiplies ----
-    auto walk_pd = [&](const uint32_t w_cur, double* acc, const uint32_t my_tab, auto alt0_tag, auto alt1_tag, auto first_tag) {
+    // (kEpiAhead, VB2_READS_AHEAD digits 3 and 4: a tile's LAST row also requests the epilogue's projection coefficients at cq_addr
+    // behind its own twelve reads and before its multiplies -- pre_tag -- and marker_lk finds them in registers: all 2 k quads
+    // [3], or those of the first kCqK <= 2 components [4], the rest at the epilogue's head as before)
+    constexpr bool kEpiAhead = (kReadsAhead == 3 || kReadsAhead == 4) && KSEL > 0 && BTL == 2;
+    constexpr int kCqK = !kEpiAhead ? 0 : (kReadsAhead == 3 || KSEL < 2) ? KSEL : 2;
+    constexpr int kCq = kEpiAhead ? 2 * kCqK : 1;
+    vdouble2 cq[kCq];                           // {first sample's, second sample's} coefficient of component j at [2 j], [2 j + 1]
+    uint32_t cq_addr = 0;
+    auto request_cq = [&]() {
+#pragma unroll
+        for (int i = 0; i < kCq; ++i) cq[i] = *reinterpret_cast<lds_cdouble2*>(cq_addr + (uint32_t)((i & 1) * KSEL + (i >> 1)) * 16u);
+    };
+    auto walk_pd = [&](const uint32_t w_cur, double* acc, const uint32_t my_tab, auto alt0_tag, auto alt1_tag, auto first_tag, auto pre_tag) {
         constexpr bool kAlt0 = decltype(alt0_tag)::value, kAlt1 = decltype(alt1_tag)::value, kFirst = decltype(first_tag)::value;
+        constexpr bool kPre = decltype(pre_tag)::value;
         if constexpr ((kAblate & kAblNoReads) != 0) {        // (ablation build: the steps are consumed, the table is not read)
             acc[0] = (kFirst ? 1.0 : acc[0]) * __hiloint2double((int)((w_cur ^ (w_cur >> 16)) & 0x000fu) | 0x3ff00000, 0);
+            return;
+        }
+        // (kReadsAhead: the word's rows are REQUESTED before they are multiplied -- both steps' 6 * BTL reads, then the
+        // 12 * BTL multiplies [1], or a step's reads, then its multiplies [2] -- and the order is pinned behind them.  Left to
+        // itself the scheduler takes the low-pressure order: four landing quads, three dependent LDS round trips per step,
+        // every step drained.  The same multiplies in the same order on the same products: no bit moves.  The first row
+        // already has all its reads in flight -- its first step has nothing to multiply.)
+        if constexpr (kReadsAhead != 0 && !kFirst && (kAblate & kAblNoMul) == 0) {
+            vdouble2 t[6 * BTL];
+            auto request = [&](const int j) {
+                const bool kAlt = j ? kAlt1 : kAlt0;
+                const uint32_t row_addr = (kAlt ? my_tab - (uint32_t)kPdAltOffset : my_tab) + (j ? (w_cur >> 16) : (w_cur & 0xffffu));
+                lds_cdouble2* row = reinterpret_cast<lds_cdouble2*>(row_addr);
+#pragma unroll
+                for (int i = 0; i < 3 * BTL; ++i) t[j * 3 * BTL + i] = row[i];
+            };
+            auto multiply = [&](const int j) {
+                const bool kAlt = j ? kAlt1 : kAlt0;
+#pragma unroll
+                for (int i = 0; i < 3 * BTL; ++i) {
+                    const int pt = i / 3, q2 = 2 * (i - 3 * pt);
+                    const int a0 = pt * 6 + (kAlt ? 5 - q2 : q2), a1 = pt * 6 + (kAlt ? 4 - q2 : q2 + 1);
+                    acc[a0] = acc[a0] * t[j * 3 * BTL + i].x;
+                    acc[a1] = acc[a1] * t[j * 3 * BTL + i].y;
+                }
+            };
+            // (0x100: LDS reads, 0x002: vector ALU; the groups of one id follow each other in this order)
+            if constexpr (kReadsAhead == 1 || kReadsAhead == 3 || kReadsAhead == 4) {
+                request(0); request(1);
+                if constexpr (kPre) request_cq();
+                multiply(0); multiply(1);
+                __builtin_amdgcn_sched_group_barrier(0x100, 6 * BTL + (kPre ? kCq : 0), 0);
+                __builtin_amdgcn_sched_group_barrier(0x002, 12 * BTL, 0);
+            } else {
+                // (each step a scheduling region of its own: with four groups in one region the scheduler mixed the steps)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    request(j);
+                    multiply(j);
+                    __builtin_amdgcn_sched_group_barrier(0x100, 3 * BTL, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x002, 6 * BTL, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
             return;
         }
 #pragma unroll
@@ -1155,8 +1232,12 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
                 for (int t = 0; t < BTL; ++t) af1[t] = af2[t] = 0.;
                 auto project = [&](int kk, double uu) {
                     if constexpr (BTL == 2) {              // both points' coefficient in one ds_read_b128
-                        const vdouble2 c1 = *reinterpret_cast<lds_cdouble2*>(my_ptq + (uint32_t)kk * 16u);
-                        const vdouble2 c2 = *reinterpret_cast<lds_cdouble2*>(my_ptq + (uint32_t)(k + kk) * 16u);
+                        vdouble2 c1, c2;
+                        if (kEpiAhead && kk < kCqK) { c1 = cq[kCq > 1 ? 2 * kk : 0]; c2 = cq[kCq > 1 ? 2 * kk + 1 : 0]; }   // (requested under the tile's last row)
+                        else {
+                            c1 = *reinterpret_cast<lds_cdouble2*>(my_ptq + (uint32_t)kk * 16u);
+                            c2 = *reinterpret_cast<lds_cdouble2*>(my_ptq + (uint32_t)(k + kk) * 16u);
+                        }
                         af1[0] = fma(uu, c1.x, af1[0]); af1[1] = fma(uu, c1.y, af1[1]);
                         af2[0] = fma(uu, c2.x, af2[0]); af2[1] = fma(uu, c2.y, af2[1]);
                     } else {
@@ -1500,12 +1581,15 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
             // lists' loads hide behind the table reads either way -- with made-up steps and no loads at all, VB2_ABLATE = 128,
             // the launch is no shorter; profiles/r06/ab_ablations.txt.)
             static_assert(kPf == 2, "the ring below has two slots");
-            auto row_step = [&](auto slot_tag, auto alt0_tag, auto alt1_tag, auto first_tag) {
+            auto row_step_pre = [&](auto slot_tag, auto alt0_tag, auto alt1_tag, auto first_tag, auto pre_tag) {
                 constexpr int kSlot = decltype(slot_tag)::value;
                 const uint32_t cur = w[kSlot];
                 w[kSlot] = load_row(r + kPf);
-                walk_pd(cur, acc, my_tab, alt0_tag, alt1_tag, first_tag);
+                walk_pd(cur, acc, my_tab, alt0_tag, alt1_tag, first_tag, pre_tag);
                 ++r;
+            };
+            auto row_step = [&](auto slot_tag, auto alt0_tag, auto alt1_tag, auto first_tag) {
+                row_step_pre(slot_tag, alt0_tag, alt1_tag, first_tag, std::false_type());
             };
             const std::integral_constant<int, 0> kS0;
             const std::integral_constant<int, 1> kS1;
@@ -1532,12 +1616,38 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
                 }
                 if (r < end) row_step(kS0, alt_tag, alt_tag, kNotFirst);
             };
+            if constexpr (kEpiAhead) {
+                // the tile's last row on its own, whichever kind it is (ref, the mixed row, alt) and whichever slot it has
+                cq_addr = my_ptq;
+                const int last = rows - 1;
+                rows_of_kind(rows_ra < last ? rows_ra : last, kRef);
+                if ((steps_ref & 1) && r == rows_ra && r < last) {
+                    if (r & 1) row_step(kS1, kRef, kAltT, kNotFirst);
+                    else row_step(kS0, kRef, kAltT, kNotFirst);
+                }
+                rows_of_kind(last, kAltT);
+                const std::true_type kPreT;
+                if (r < rows) {                           // (r == last >= 1: never the first row)
+                    if (r < rows_ra) {
+                        if (r & 1) row_step_pre(kS1, kRef, kRef, kNotFirst, kPreT);
+                        else row_step_pre(kS0, kRef, kRef, kNotFirst, kPreT);
+                    } else if ((steps_ref & 1) && r == rows_ra) {
+                        if (r & 1) row_step_pre(kS1, kRef, kAltT, kNotFirst, kPreT);
+                        else row_step_pre(kS0, kRef, kAltT, kNotFirst, kPreT);
+                    } else {
+                        if (r & 1) row_step_pre(kS1, kAltT, kAltT, kNotFirst, kPreT);
+                        else row_step_pre(kS0, kAltT, kAltT, kNotFirst, kPreT);
+                    }
+                } else
+                    request_cq();                         // (a tile of one row or none: at the epilogue's head, as before)
+            } else {
             rows_of_kind(rows_ra, kRef);
             if ((steps_ref & 1) && r == rows_ra && r < rows) {
                 if (r & 1) row_step(kS1, kRef, kAltT, kNotFirst);
                 else row_step(kS0, kRef, kAltT, kNotFirst);
             }
             rows_of_kind(rows, kAltT);
+            }
             if constexpr (PIPE) {
                 issue_rows(rec_n2, have_next);
                 cst_nx = other_const(mt_next, have_next);
@@ -1910,7 +2020,7 @@ llk_eval_kernel(const DeviceLayout L, const InlinePoints ip, const double* __res
                 unsigned int* __restrict__ ticket, unsigned long long* __restrict__ done_flag,
                 unsigned long long done_seq, int ngrp, unsigned long long tag, const Schedule sch)
 {
-    eval_body<MODE, false, NoHook, false, QUEUE, KSEL, false, 8, PD>(L, ip.v, ip.count, points, num_valid, partials, llk_out, ticket,
+    eval_body<MODE, false, NoHook, false, QUEUE, KSEL, false, 8, PD, 0, reads_ahead(MODE == 2 ? 1 : 2)>(L, ip.v, ip.count, points, num_valid, partials, llk_out, ticket,
                                                                      done_flag, done_seq, blockIdx.x, gridDim.x, nullptr, 0u, ngrp, tag, sch);
 }
 
@@ -1921,7 +2031,7 @@ llk_eval_split_kernel(const DeviceLayout L, const double* __restrict__ points, i
                       double* __restrict__ llk_out, unsigned int* __restrict__ ticket, unsigned long long* __restrict__ done_flag,
                       unsigned long long done_seq, int ngrp)
 {
-    eval_body<2, false, NoHook, false, 1, KSEL, false, 8, true, S>(L, nullptr, 0, points, num_valid, partials, llk_out, ticket, done_flag,
+    eval_body<2, false, NoHook, false, 1, KSEL, false, 8, true, S, reads_ahead(0)>(L, nullptr, 0, points, num_valid, partials, llk_out, ticket, done_flag,
                                                                      done_seq, blockIdx.x, gridDim.x, nullptr, 0u, ngrp, 0ull,
                                                                      Schedule{nullptr, nullptr});
 }

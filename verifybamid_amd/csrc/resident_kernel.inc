@@ -1413,7 +1413,7 @@ llk_resident_kernel(const DeviceLayout L, const ResidentArgs ra, double* __restr
         // ONE instance of the evaluation body (a single point goes through the four-point shape too,
         // replicated: results do not depend on the wave shape, and a second inlined body would push
         // the kernel past the instruction cache -- every round would refetch its code)
-        eval_body<3, false, ControlHook, false, QUEUE, KSEL, LCACHE, 8, PD>(Lr, nullptr, 0, nullptr, nv, partials, dst, ticket, dflag, dseq, blockIdx.x,
+        eval_body<3, false, ControlHook, false, QUEUE, KSEL, LCACHE, 8, PD, 0, reads_ahead(3)>(Lr, nullptr, 0, nullptr, nv, partials, dst, ticket, dflag, dseq, blockIdx.x,
                                                    nblk_eval, nullptr, 0u, 1, tag, ra.sched_multi, false, tid_r, lds_rows,
                                                    hook);
     }

@@ -18,6 +18,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 LIB = os.path.join(ROOT, "verifybamid_amd", "libvb2.so")
+STAMPS_LIB = os.path.join(ROOT, "verifybamid_amd", "libvb2_stamps.so")
 
 VGPR_LIMIT = 128
 
@@ -71,3 +72,26 @@ def test_evaluation_kernels_fit_128_vgprs_without_scratch():
     assert len(plain) >= 12, plain
     over = {(k[0], k[1].split("(")[0]): v for k, v in mine.items() if v["vgpr_count"] > VGPR_LIMIT or v["private_segment_fixed_size"] != 0}
     assert not over, over
+
+
+def test_each_evaluation_kernel_is_compiled_once_and_the_stamps_build_has_the_same_units():
+    """Every vb2::llk_* kernel belongs to one translation unit -- the one with its launcher and its scheduler (csrc/Makefile) --
+    so its name shows in one code object of libvb2.so only; and the profiling library libvb2_stamps.so is made of the same
+    units: the same kernel names at the same code-object positions.  Names from the notes only."""
+    import isa_diff
+    if not os.path.exists(LIB):
+        pytest.skip("libvb2.so is not built")
+    if not all(os.path.exists(isa_diff.LLVM + t) for t in ("llvm-objdump", "llvm-readelf")):
+        pytest.skip("the ROCm binutils are not installed")
+    ship = set(all_kernel_notes(LIB))
+    homes = {}
+    for co, name in ship:
+        if re.search(r"\bvb2::llk_", name):
+            homes.setdefault(name, []).append(co)
+    assert len(homes) >= 85, len(homes)                 # 12+ plain, 6 split, 6 pass-per-group, 72 cohort kernels, the resident ones
+    twice = {n.split("(")[0]: sorted(c) for n, c in homes.items() if len(c) > 1}
+    assert not twice, twice
+    if not os.path.exists(STAMPS_LIB):
+        return
+    stamps = set(all_kernel_notes(STAMPS_LIB))
+    assert stamps == ship, sorted((co, n.split("(")[0]) for co, n in stamps ^ ship)

@@ -297,7 +297,7 @@ def kernel_source_hash():
     import hashlib
     h = hashlib.sha256()
     d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-    for name in ("llk_kernels.hip", "resident_kernel.inc", "llk_kernels.h", "kernel_debug.h", "log_table.inc", "Makefile"):
+    for name in ("eval_body.h", "llk_kernels.hip", "llk_passes.hip", "resident_kernel.inc", "llk_kernels.h", "kernel_debug.h", "log_table.inc", "Makefile"):
         with open(os.path.join(d, name), "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]

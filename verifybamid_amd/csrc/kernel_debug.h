@@ -1,4 +1,4 @@
-// kernel_debug.h -- every compile-time switch of the kernels (llk_kernels.hip, resident_kernel.inc).  A shipping build
+// kernel_debug.h -- every compile-time switch of the kernels (eval_body.h, llk_kernels.hip, llk_passes.hip, resident_kernel.inc).  A shipping build
 // defines none of them; the profiling builds are made by csrc/Makefile (libvb2_stamps.so, `make stamps_round`) and
 // tools/build_variant.sh.
 //
@@ -23,6 +23,7 @@
 //   VB2_SPLIT_FAST=mask the short head and tail of a split launch (eval_body, SPLIT), each part on its own for A/B builds (default: all):
 //                         1 the tables are built from records and alphas requested at kernel entry, not from the staged copies
 //                         2 one arrival ticket per share of the point groups: each share's last workgroup adds up that share's points
+//   VB2_SIMD_DEAL=0     wave w of a search round takes item w instead of the SIMD-balanced first deal (eval_body)
 //   VB2_READS_AHEAD=0xRNPS how a row word of the probability-domain walk (eval_body, walk_pd) orders its table reads and its multiplies, one
 //                       hex digit per kernel family -- S llk_eval_split_kernel, P the plain 8-point launch llk_eval_kernel<2, ...>, N the
 //                       4-point and narrower launches llk_eval_kernel<3..5, ...>, R the resident search kernel (default 0x0111):
@@ -52,6 +53,9 @@
 #endif
 #ifndef VB2_READS_AHEAD
 #define VB2_READS_AHEAD 0x0111
+#endif
+#ifndef VB2_SIMD_DEAL
+#define VB2_SIMD_DEAL 1     // (0: wave w takes item w -- the A/B of the SIMD-balanced first deal, see eval_body)
 #endif
 #ifndef VB2_STAMP_ROUND
 #define VB2_STAMP_ROUND 0

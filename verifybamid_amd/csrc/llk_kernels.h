@@ -255,6 +255,14 @@ int max_groups(const DeviceLayout& L, int btl, int nblk, int block_waves);
 // table rows of a probability-domain context of ~M markers that leave a 48-point launch (six point groups) its LDS
 int pd_row_budget(int num_marker, int num_pc, int num_cu);
 hipError_t launch_llk_eval_multi(const MultiLaunch& ml, hipStream_t stream);
+// llk_passes.hip: the passes of one launch for more points than the LDS holds tables for (see llk_eval_passes_kernel).
+// *taken = false: the geometry does not allow it, or it would save no launch (launch_llk_eval goes on with a launch per `cap` points)
+hipError_t launch_passes(const DeviceLayout& L, const double* d_points, int num_valid, int groups_per_launch,
+                         double* d_partials, double* d_out, unsigned int* d_tickets,
+                         unsigned long long* done_flag, unsigned long long done_seq, hipStream_t stream, bool* taken);
+// lets kernel function fn take up to kLdsLimitBytes of dynamic LDS on the current device (once per function and device);
+// defined in llk_kernels.hip, used by the launchers of both kernel units
+hipError_t raise_lds_limit(const void* fn);
 hipError_t launch_fill_zero(double* d_out, int n, hipStream_t stream);
 // codes / mt_rec -> codes16 / mt_rec16 on the device (rec16 already holds the tiles' {first row, rows};
 // rows16_total + kCodeSlackRows rows are written, the slack as padding words)

@@ -1,4 +1,4 @@
-// resident_kernel.inc -- included by llk_kernels.hip (needs eval_body).
+// resident_kernel.inc -- included by llk_kernels.hip, behind eval_body.h (needs eval_body).
 // ---------------------------------------------------------------------------------------------
 // Resident search kernel.  A Nelder-Mead search is ~480 DEPENDENT evaluations of <= 4 points; with
 // a launch per evaluation a third of the wall-clock is launch submission and dispatch.  This kernel

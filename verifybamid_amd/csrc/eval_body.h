@@ -503,6 +503,13 @@ __host__ __device__ __forceinline__ bool eval_is_dynamic(const DeviceLayout& L, 
 // the steps of the run-word kernel -- rounds 3 and 4: 128 registers and spills, slower -- and eight to ten reads in flight in
 // the search round's single item per wave -- round 5: equal, that regime is bound by the deepest wave's latency.  Kept: the
 // probability-domain walk requests a row word's twelve reads before it multiplies, RAHEAD below -- HISTORY.md.)
+// AHEAD (VB2_ITEM_AHEAD; the 8-point probability-domain shape on the queue, i.e. the split launch and the plain 8-point launch):
+// where a wave gets its NEXT item from.  0: at the item's head -- the draw, the tile's record, the list's first rows: three
+// dependent trips before the first table read.  1: the draw and the record's request behind the present item's last row, the
+// rows 0, 1, 2 of the list behind its epilogue; the next iteration starts from those registers (see the item loop).  2: as 1,
+// and the ring of row words has FIXED registers: a row's two table addresses are taken from its word before the refill is
+// loaded into the same register, so no loop of the walk begins or ends with a copy of a register that is being loaded.
+// (The item drawn a WHOLE item early -- round 4, above -- cost balance; this draw is one epilogue early.)
 // PD: a probability-domain context (DeviceLayout::pd; llk_kernels.h, kMaxPow): the table holds P^n rows of class ref only,
 // a marker's list is one 16-bit row offset per step, ref steps first and alt steps behind them; the six sums are PRODUCTS,
 // class alt multiplies them with the row read the other way round (g -> 2 - g, h:164-177: T[alt][q][g1][g2] is T[ref][q][2-g1][2-g2]),
@@ -516,7 +523,7 @@ __host__ __device__ __forceinline__ bool eval_is_dynamic(const DeviceLayout& L, 
 // multiplied in the same order and its sum goes to the same word of the partial sums as in a plain launch of this grid:
 // the same bits, and no second pass over the tiles (llk_eval_passes_kernel: +4 us per pass at C3).
 template <int MODE, bool W16 = false, class Hook = NoHook, bool STREAM = false, int QUEUE = -1, int KSEL = 0,
-          bool LCACHE = false, int ESH = 8, bool PD = false, int SPLIT = 0, int RAHEAD = 0>
+          bool LCACHE = false, int ESH = 8, bool PD = false, int SPLIT = 0, int RAHEAD = 0, int AHEAD = 0>
 __device__ __forceinline__ void
 eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const double* __restrict__ points, int num_valid,
           double* __restrict__ partials, double* __restrict__ llk_out,
@@ -542,6 +549,9 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
     constexpr int SLOTS = 4 / TPW;                           // candidate slots per wave
     constexpr int NP = SLOTS * BTL;
     constexpr int kReadsAhead = PD ? RAHEAD : 0;    // how far walk_pd's table reads run ahead of its multiplies (reads_ahead)
+    static_assert(AHEAD == 0 || (PD && MODE == 2 && QUEUE == 1 && !STREAM && !LCACHE && !W16 && std::is_same<Hook, NoHook>::value),
+                  "items requested ahead: the 8-point probability-domain shape on the queue");
+    constexpr bool kAhead = AHEAD != 0 && (kAblate & (kAblNoReads | kAblNoRowLoads)) == 0;      // (item_ahead; see the item loop)
     // (the run-word kernels of the static deal in the paired shapes: the layout's four sizes in scalar registers of their own.
     // Under those kernels' scalar pressure the register allocator gave up the {num_code, row_bytes, num_prim, num_mt} quad of the
     // kernel arguments, loaded it again at each of six uses and left the quad's spill slot behind: scratch memory set up for
@@ -1094,9 +1104,10 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
 #pragma unroll
         for (int i = 0; i < kCq; ++i) cq[i] = *reinterpret_cast<lds_cdouble2*>(cq_addr + (uint32_t)((i & 1) * KSEL + (i >> 1)) * 16u);
     };
+    // (pre_tag's bit 1, AHEAD 2: the caller has taken the word's two row addresses from it and passes THEM as w_cur and my_tab)
     auto walk_pd = [&](const uint32_t w_cur, double* acc, const uint32_t my_tab, auto alt0_tag, auto alt1_tag, auto first_tag, auto pre_tag) {
         constexpr bool kAlt0 = decltype(alt0_tag)::value, kAlt1 = decltype(alt1_tag)::value, kFirst = decltype(first_tag)::value;
-        constexpr bool kPre = decltype(pre_tag)::value;
+        constexpr bool kPre = ((int)decltype(pre_tag)::value & 1) != 0, kAt = ((int)decltype(pre_tag)::value & 2) != 0;
         if constexpr ((kAblate & kAblNoReads) != 0) {        // (ablation build: the steps are consumed, the table is not read)
             acc[0] = (kFirst ? 1.0 : acc[0]) * __hiloint2double((int)((w_cur ^ (w_cur >> 16)) & 0x000fu) | 0x3ff00000, 0);
             return;
@@ -1110,7 +1121,9 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
             vdouble2 t[6 * BTL];
             auto request = [&](const int j) {
                 const bool kAlt = j ? kAlt1 : kAlt0;
-                const uint32_t row_addr = (kAlt ? my_tab - (uint32_t)kPdAltOffset : my_tab) + (j ? (w_cur >> 16) : (w_cur & 0xffffu));
+                uint32_t row_addr;
+                if constexpr (kAt) row_addr = j ? my_tab : w_cur;
+                else row_addr = (kAlt ? my_tab - (uint32_t)kPdAltOffset : my_tab) + (j ? (w_cur >> 16) : (w_cur & 0xffffu));
                 lds_cdouble2* row = reinterpret_cast<lds_cdouble2*>(row_addr);
 #pragma unroll
                 for (int i = 0; i < 3 * BTL; ++i) t[j * 3 * BTL + i] = row[i];
@@ -1376,6 +1389,41 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
 #ifdef VB2_ITEM_PROF     // (profiling build, with VB2_WITH_STAMPS: where a wave's time per work item goes -- tools/item_prof.py)
     unsigned long long ip_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
+    // AHEAD (VB2_ITEM_AHEAD; the 8-point probability-domain shape on the queue: several items per wave, lists in L2): an item used
+    // to begin with three DEPENDENT trips -- the draw from the queue, the tile's record from L2, the list's first rows from L2 --
+    // during which the wave feeds neither the LDS nor the VALU, and the depth-sorted items keep a workgroup's waves so close to
+    // lock-step that these holes coincide.  Now a wave draws its next item when its last row's multiplies are issued, requests that
+    // item's record at once and -- behind marker_lk, when the record is there -- the rows 0, 1 and 2 of its list: they land under
+    // the epilogue, the 16-lane exchange and the slot write, and the next iteration starts from these registers.  The item's nine
+    // per-marker constants stay where they were: requested at its top, awaited behind its read loop.  Each word is consumed in the
+    // register it was loaded into -- row 0 and row 1 ARE the ring's two slots, row 2 is the first row's refill, so the three kinds
+    // of first row request nothing and meet without a copy of a register that is being loaded (such a copy drains every load).
+    // A tile's product still goes to its own slot: the same bits whichever wave drew it, and when.
+    vuint2 rec_ah;                                        // the record of the item about to be processed ...
+    rec_ah.x = rec_ah.y = 0u;
+    uint32_t w_ah[3] = {0u, 0u, 0u};                      // ... and this lane's words of its rows 0, 1, 2
+    auto request_rec_ahead = [&](const uint32_t idx_) {
+        // (item -> tile as the loop's head does it; an item past the queue's end: tile 0's record, never used)
+        const uint32_t unit_ = ngrp > 1 ? __umulhi(idx_, ngrp_magic) : idx_;
+        const uint32_t vs_ = SPLIT ? unit_ % (uint32_t)NVS : 0u;
+        const uint32_t it_ = SPLIT ? unit_ / (uint32_t)NVS : unit_;
+        const bool have_ = idx_ < nitem && (SPLIT ? it_ < nt_of(vs_) : true);
+        const uint32_t mt_ = have_ ? owned_tile(OSH, vb0 + vs_ * vstep, nblk, it_) : 0u;
+        rec_ah = g_rec[mt_];
+    };
+    auto request_rows_ahead = [&]() {
+        // (a tile shorter than three rows: the rows behind it, never consumed -- the array ends in padding rows)
+        const uint32_t cb_ = rec_ah.x * kRowBytes + (uint32_t)m * kLaneBytes;
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            w_ah[j] = *reinterpret_cast<g_cuint*>(reinterpret_cast<g_cchar*>(g_codes) + (cb_ + (uint32_t)j * kRowBytes));
+    };
+    if constexpr (kAhead) {
+        if (idx_first < nitem) {
+            request_rec_ahead(idx_first);
+            request_rows_ahead();
+        }
+    }
     for (uint32_t idx = idx_first; idx < nitem;) {
         VB2_IP_T(ip_t0);
         // grp = idx / nunit without the ~25-instruction integer division: float estimate (exact for
@@ -1416,6 +1464,7 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
         vuint2 rec;
         if constexpr (LCACHE) rec = *reinterpret_cast<lds_cuint2v*>(hook.cache_rec() + (have_tile ? it : 0u) * 8u);
         else if (PIPE) rec = rec_nx;
+        else if (kAhead) rec = rec_ah;
         else rec = g_rec[mt];
         VB2_IP_USE(rec.x);
         VB2_IP_T(ip_t1);
@@ -1516,7 +1565,9 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
                 else return *reinterpret_cast<g_cuint2*>(a_);
             }
         };
-        if (!PIPE) {
+        if constexpr (kAhead) {
+            if constexpr (PD) { w[0] = w_ah[0]; w[1] = w_ah[1]; }
+        } else if (!PIPE) {
 #pragma unroll
             for (int j = 0; j < kPf; ++j) w[j] = load_row(j);
         }
@@ -1580,8 +1631,19 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
             auto row_step_pre = [&](auto slot_tag, auto alt0_tag, auto alt1_tag, auto first_tag, auto pre_tag) {
                 constexpr int kSlot = decltype(slot_tag)::value;
                 const uint32_t cur = w[kSlot];
-                w[kSlot] = load_row(r + kPf);
-                walk_pd(cur, acc, my_tab, alt0_tag, alt1_tag, first_tag, pre_tag);
+                // (AHEAD 2: the ring's slots are FIXED registers -- the row's two table addresses are taken from the word first, and
+                // the refill is loaded into the register that held it: no copy of a loading register at the loops' heads and exits)
+                constexpr bool kAt = kAhead && AHEAD >= 2 && kReadsAhead != 0 && !decltype(first_tag)::value && (kAblate & kAblNoMul) == 0;
+                uint32_t row_a0 = cur, row_a1 = my_tab;
+                if constexpr (kAt) {
+                    row_a0 = (decltype(alt0_tag)::value ? my_tab - (uint32_t)kPdAltOffset : my_tab) + (cur & 0xffffu);
+                    row_a1 = (decltype(alt1_tag)::value ? my_tab - (uint32_t)kPdAltOffset : my_tab) + (cur >> 16);
+                    asm volatile("" : "+v"(row_a0), "+v"(row_a1));
+                }
+                if constexpr (kAhead && decltype(first_tag)::value) w[kSlot] = w_ah[2];      // (row 2: requested with rows 0 and 1)
+                else w[kSlot] = load_row(r + kPf);
+                if constexpr (kAt) walk_pd(row_a0, acc, row_a1, alt0_tag, alt1_tag, first_tag, std::integral_constant<int, 2 + (decltype(pre_tag)::value ? 1 : 0)>());
+                else walk_pd(cur, acc, my_tab, alt0_tag, alt1_tag, first_tag, pre_tag);
                 ++r;
             };
             auto row_step = [&](auto slot_tag, auto alt0_tag, auto alt1_tag, auto first_tag) {
@@ -1672,6 +1734,12 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
             for (int s0 = 0; s0 < rows; s0 += kPf) walk_block(s0, true, std::false_type());
         }
 
+        // AHEAD: the last row's multiplies are issued -- the next item is drawn and its record requested
+        uint32_t idx_ah = nitem;
+        if constexpr (kAhead) {
+            idx_ah = draw_item();
+            request_rec_ahead(idx_ah);
+        }
         __builtin_amdgcn_s_setprio(0);
 #ifdef VB2_STAMP_CTRL
         if (stamps && lane == 0 && wave == 1 && !hook_blk) stamps[3] = wall_clock64();
@@ -1686,6 +1754,7 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
         double lk_m[BTL];
         int lk_e[BTL];
         marker_lk(live, pos, acc, e0, e1, e2, udr, mur, my_ptq, lk_m, lk_e, cst);
+        if constexpr (kAhead) request_rows_ahead();           // (the record has had the epilogue to arrive)
         VB2_IP_USE(lk_m[0]); VB2_IP_USE(lk_m[BTL - 1]);
         VB2_IP_T(ip_t5);
         if (!dyn) {
@@ -1730,7 +1799,8 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
         }
         VB2_IP_T(ip_t6);
         // next work item of this workgroup, whichever wave gets there first
-        idx = draw_item();
+        if constexpr (kAhead) idx = idx_ah;
+        else idx = draw_item();
 #ifdef VB2_ITEM_PROF
         {
             const unsigned long long ip_t7 = __builtin_readcyclecounter();

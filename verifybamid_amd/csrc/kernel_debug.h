@@ -33,6 +33,14 @@
 //                         3 as 1, and a tile's last row also requests the epilogue's 2 k projection coefficients before it multiplies (KSEL 2, 4)
 //                         4 as 3 with the coefficients of the first two components only (four quads)
 //                       (the cohort kernels and the pass-per-group kernel keep 0: with 1 some of them spill; R: see HISTORY.md)
+//   VB2_ITEM_AHEAD=0xPS where a wave of the 8-point probability-domain shape on the work queue gets its NEXT item from (eval_body, AHEAD),
+//                       one hex digit per kernel family -- S llk_eval_split_kernel, P the plain 8-point launch llk_eval_kernel<2, 1, *, true>:
+//                         0 at the item's head: the draw, the tile's record, its first rows -- three dependent trips before the first table read
+//                         1 the draw and the record's request behind the present item's last row, the list's rows 0, 1, 2 behind its
+//                           epilogue; the first row's refill is row 2, so its three kinds meet without a copy of a loading register
+//                         2 as 1, and the ring of row words has fixed registers: a row's two table addresses are taken from its word
+//                           before the refill is loaded into the same register -- no copy of a ring word in any loop of the walk
+//                       (default 0x02: -2.6 % on the 48-point launch; P measured faster, but not by three times the spread: HISTORY.md)
 #ifndef VB2_KERNEL_DEBUG_H_
 #define VB2_KERNEL_DEBUG_H_
 
@@ -54,6 +62,9 @@
 #ifndef VB2_READS_AHEAD
 #define VB2_READS_AHEAD 0x0111
 #endif
+#ifndef VB2_ITEM_AHEAD
+#define VB2_ITEM_AHEAD 0x02     // (profiles/r10/ab_item_head.txt)
+#endif
 #ifndef VB2_SIMD_DEAL
 #define VB2_SIMD_DEAL 1     // (0: wave w takes item w -- the A/B of the SIMD-balanced first deal, see eval_body)
 #endif
@@ -67,6 +78,8 @@ constexpr int kAblate = VB2_ABLATE;
 constexpr int kSplitFast = VB2_SPLIT_FAST;
 constexpr int kReadsAheadMask = VB2_READS_AHEAD;
 constexpr int reads_ahead(int family) { return (kReadsAheadMask >> (4 * family)) & 0xf; }      // family: 0 S, 1 P, 2 N, 3 R
+constexpr int kItemAheadMask = VB2_ITEM_AHEAD;
+constexpr int item_ahead(int family) { return (kItemAheadMask >> (4 * family)) & 0xf; }        // family: 0 S, 1 P
 }  // namespace vb2
 
 #ifdef VB2_WITH_STAMPS

@@ -1,15 +1,21 @@
 """--RefVCF without a device: the VCF reader (SVDcalculator::ReadVcf, SVDcalculator.cpp:22-228, restated rule by rule
-below), the command line's checks that come before any device call, and the layouts of the new ABI structs."""
+below), the command line's checks that come before any device call, the layouts of the new ABI structs, and the
+a-posteriori checker of the decomposition (tests/panel_ref.py) on a float64 numpy restatement with and without planted
+faults."""
 import ctypes as C
 import gzip
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
 
 import verifybamid_amd as vb
 from verifybamid_amd import _abi
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import panel_ref as pr  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "verifybamid_amd", "bin", "VerifyBamID")
@@ -225,3 +231,147 @@ def test_panel_abi_structs_match_the_binding(tmp_path):
         assert int(got[n]) == C.sizeof(cls), n
         for f, _ in cls._fields_:
             assert int(got["%s.%s" % (n, f)]) == getattr(cls, f).offset, (n, f)
+
+
+# ---- the a-posteriori checker (tests/panel_ref.py): inside every bound on the float64 restatement alone, and each planted
+# ---- fault caught by the quantity that points at its stage
+
+PANEL_SHAPES = [(300, 80, 33), (257, 129, 17)]
+
+
+@pytest.fixture(scope="module", params=PANEL_SHAPES, ids=lambda p: "%dx%d_k%d" % p)
+def restated(request):
+    M, N, k = request.param
+    G = pr.structured_geno(M, N, seed=M + N)
+    mu, S, c, tau = pr.restate_gram(G)
+    sigma, V, raw = pr.restate_eig(pr.centre(S, c, tau), k)
+    r = pr.restate(G, k)
+    assert np.array_equal(r["v"], V) and np.array_equal(r["sigma"], sigma)
+    return dict(G=G, k=k, r=r, mu=mu, S=S, c=c, tau=tau, sigma=sigma, V=V, raw=raw)
+
+
+def test_checker_is_longdouble():
+    G = pr.structured_geno(40, 9, seed=1)
+    mu, C, S = pr.exact_centred_gram(G)
+    assert C.dtype == np.longdouble and S.dtype == np.int64 and mu.dtype == np.float64
+    assert np.array_equal(mu, mu.astype(np.float32).astype(np.float64))            # binary32 values
+    assert np.array_equal(mu.astype(np.float32), G.sum(axis=1).astype(np.float32) / np.float32(9))
+    # C against exact rationals (mu is a dyadic rational): within the 80-bit rounding of sums of M terms of <= 4 M in all,
+    # M 4M 2^-64, which is below half a binary64 ulp of the entries here
+    from fractions import Fraction
+    muq = [Fraction(float(m)) for m in mu]
+    Gi = G.astype(np.int64)
+
+    def exact(x):                                   # a longdouble as a Fraction: two binary64 pieces
+        hi = float(x)
+        return Fraction(hi) + Fraction(float(x - np.longdouble(hi)))
+    for i, j in ((0, 0), (3, 7), (8, 2)):
+        want = sum(int(Gi[m, i] * Gi[m, j]) - muq[m] * int(Gi[m, i]) - muq[m] * int(Gi[m, j]) + muq[m] * muq[m]
+                   for m in range(40))
+        assert abs(exact(C[i, j]) - want) <= Fraction(40 * 160, 2 ** 64), (i, j)
+        assert Fraction(40 * 160, 2 ** 64) < Fraction(float(np.spacing(np.float64(abs(C[i, j]))))) / 2
+    ref, cond = pr.projection_reference(G, mu, np.eye(9)[:, :2])
+    assert ref.dtype == np.longdouble and cond.dtype == np.longdouble
+
+
+def test_checker_passes_the_restatement(restated):
+    rec = pr.check_panel(restated["G"], restated["r"], restated["k"])
+    print(pr.ratios_line(rec))
+    pr.assert_inside(rec)
+    assert all(rec[n] <= 1.0 for n in pr.RATIOS)
+    # by construction: the restatement is its own yardstick
+    for n in ("resid", "ortho", "trace", "spec"):
+        assert rec["value"][n] == rec["ref"][n] and rec[n] <= 1.0 / pr.MARGIN + 1e-12, n
+
+
+def _with(restated, **kw):
+    r = dict(restated["r"])
+    r.update(kw)
+    return r
+
+
+def _caught_by(restated, r, quantity):
+    """The quantity named raises, or its ratio is above 1; the exact checks come first, so a raise names the first."""
+    try:
+        rec = pr.check_panel(restated["G"], r, restated["k"])
+    except pr.PanelMismatch as e:
+        assert e.quantity == quantity, str(e)
+        return None
+    assert quantity in pr.RATIOS and rec[quantity] > 1.0, (quantity, pr.ratios_line(rec))
+    with pytest.raises(pr.PanelMismatch):
+        pr.assert_inside(rec)
+    return rec
+
+
+def test_fault_last_sample_left_out_of_the_projection(restated):
+    G, V, mu = restated["G"], restated["V"], restated["mu"]
+    ud = pr.project_in_kernel_order(G, mu, V, samples=G.shape[1] - 1)
+    _caught_by(restated, _with(restated, ud=ud), "proj")
+
+
+def test_fault_col0_offset_lost(restated):
+    G, V, mu, k = restated["G"], restated["V"], restated["mu"], restated["k"]
+    vsum = pr.column_sums(V)
+    ud = restated["r"]["ud"].copy()
+    for col0 in range(16, k, 16):
+        kc = min(16, k - col0)
+        ud[:, col0:col0 + kc] = pr.project_in_kernel_order(G, mu, V[:, :kc], vsum=vsum[col0:col0 + kc])
+    rec = _caught_by(restated, _with(restated, ud=ud), "proj")
+    assert rec["where"]["proj"][1] >= 16          # the first pass is right
+
+
+def test_fault_vsum_before_the_sign_flip(restated):
+    G, V, mu, raw = restated["G"], restated["V"], restated["mu"], restated["raw"]
+    assert (np.sign(raw[0]) != np.sign(V[0])).any()             # some column was flipped
+    ud = pr.project_in_kernel_order(G, mu, V, vsum=pr.column_sums(raw))
+    _caught_by(restated, _with(restated, ud=ud), "proj")
+
+
+def test_fault_float32_accumulation(restated):
+    ud = pr.project_in_kernel_order(restated["G"], restated["mu"], restated["V"], dtype=np.float32)
+    _caught_by(restated, _with(restated, ud=ud), "proj")
+
+
+def test_fault_float64_mean(restated):
+    G, k = restated["G"], restated["k"]
+    mu = G.astype(np.int64).sum(axis=1) / np.float64(G.shape[1])
+    _, S, c, tau = pr.restate_gram(G, mu=mu)
+    sigma, V, _ = pr.restate_eig(pr.centre(S, c, tau), k)
+    r = _with(restated, mu=mu, sigma=sigma, v=V, ud=pr.project_in_kernel_order(G, mu, V))
+    _caught_by(restated, r, "mu")
+
+
+def test_fault_one_column_sign_reversed(restated):
+    V = restated["V"].copy()
+    V[:, 3] = -V[:, 3]
+    _caught_by(restated, _with(restated, v=V), "sign")
+
+
+def test_fault_ascending_eigenpairs(restated):
+    G, mu, k = restated["G"], restated["mu"], restated["k"]
+    w, Uu = np.linalg.eigh(pr.centre(restated["S"], restated["c"], restated["tau"]))
+    sigma = np.sqrt(np.maximum(w, 0.0))
+    V = Uu[:, :k].copy()
+    for q in range(k):
+        if V[int(np.argmax(np.abs(V[:, q]))), q] < 0:
+            V[:, q] = -V[:, q]
+    _caught_by(restated, _with(restated, sigma=sigma, v=V, ud=pr.project_in_kernel_order(G, mu, V)), "sigma")
+    # ... and with a sigma that looks right, the columns are still not those of the k largest eigenvalues
+    _caught_by(restated, _with(restated, v=V, ud=pr.project_in_kernel_order(G, mu, V)), "order")
+
+
+def test_fault_unmirrored_upper_tile(restated):
+    G, mu, k = restated["G"], restated["mu"], restated["k"]
+    S = restated["S"].copy()
+    S[0:64, 64:128] = 0.0                    # the device writes lower tiles only: an upper tile read as it is ...
+    sigma, V, _ = pr.restate_eig(pr.centre(S, restated["c"], restated["tau"]), k, uplo="U")    # ... by a solver that reads it
+    r = _with(restated, sigma=sigma, v=V, ud=pr.project_in_kernel_order(G, mu, V))
+    _caught_by(restated, r, "resid")
+
+
+def test_fault_neighbours_eigenvector(restated):
+    G, mu = restated["G"], restated["mu"]
+    V = restated["V"].copy()
+    V[:, 4] = V[:, 5]
+    rec = _caught_by(restated, _with(restated, v=V, ud=pr.project_in_kernel_order(G, mu, V)), "resid")
+    assert rec["where"]["resid"] == (4,) and rec["proj"] <= 1.0        # the projection of that V is still right

@@ -139,6 +139,14 @@ def test_panel_against_the_restatement(structured):
         assert open(pre_a + ext, "rb").read() == open(pre_b + ext, "rb").read(), ext
     ud_lines = open(pre_a + ".UD").read().splitlines()
     assert len(ud_lines) == 6000 and ud_lines[0].count("\t") == k and ud_lines[0].endswith("\t")
+    # .UD and .V line by line against the struct's numbers (a transposed or shifted column would pass the two-builds
+    # comparison above both ways)
+    for m, (line, row) in enumerate(zip(ud_lines, r["ud"])):
+        assert line == "".join("%g\t" % x for x in row), (".UD", m)
+    v_lines = open(pre_a + ".V").read().splitlines()
+    assert len(v_lines) == 1200 == len(d["samples"])
+    for j, (line, name, row) in enumerate(zip(v_lines, d["samples"], r["v"])):
+        assert line == name + "\t" + "".join("%g\t" % x for x in row), (".V", j)
     # the populations separate on the first two PCs
     pop = info["pop"]
     cent = np.array([r["v"][pop == p, :2].mean(axis=0) for p in range(3)])

@@ -7,6 +7,8 @@ decided once per process) with VB2_RCCL_LIB=tests/stub_rccl/librccl_stub.so.
                                                                  ncclCommInitAll + the grouped all-reduce loop
     python tests/stub_rccl/run_case.py ranks <c2|c3> <nranks>   nranks threads, each a rank-mode group
                                                                  (ncclCommInitRank with nranks > 1)
+
+    <c2|c3> may also be `known-af`: a seeded 3 000-marker sample with a known-AF column, checked against the C oracle.
 """
 import json
 import os
@@ -20,7 +22,25 @@ import verifybamid_amd as vb  # noqa: E402
 from verifybamid_amd import _abi  # noqa: E402
 
 
+def known_af_case():
+    """The seeded known-AF sample of tests/test_model_paths_gpu.py (base sample 0 and its uniform, clipped column); the wanted
+    values are the C oracle's, computed here."""
+    from oracle.bridge import oracle_data
+    d = vb.synth.make_pileup(3000, 25, 3, alpha_true=0.02, seed=61)
+    af = np.clip(np.random.default_rng(1061).uniform(0, 1, d.num_marker), 0.01, 0.99)
+    d = vb.PileupData(d.num_pc, d.ud, d.means, d.read_off, d.bases, d.quals, d.alt_base, af, d.avg_depth, d.sd_depth, True, {})
+    od = oracle_data(d)
+    rng = np.random.default_rng(24)
+    pc1, pc2, al = rng.normal(0, 0.03, (8, 3)), rng.normal(0, 0.03, (8, 3)), rng.uniform(0, 0.5, 8)
+    want = np.array([od.llk(pc1[i], pc2[i], al[i]) for i in range(8)])
+    ref = od.optimize()
+    m = {"alpha_hex": float(ref["alpha"]).hex(), "llk1_hex": float(ref["llk1"]).hex(), "num_eval": int(ref["num_eval"])}
+    return d, pc1, pc2, al, want, m
+
+
 def fixture(size):
+    if size == "known-af":
+        return known_af_case()
     fx = json.load(open(os.path.join(ROOT, "tests", "golden", "synthetic_%s.json" % size)))
     g = fx["generator"]
     d = vb.synth.make_pileup(g["markers"], g["mean_depth"], g["num_pc"], alpha_true=g["alpha_true"], seed=g["seed"])

@@ -291,13 +291,21 @@ def test_verbose_notices_are_the_references_per_evaluation_lines(golden_dir, kw)
     assert len(lines_p) == got["num_eval"] - 2 and got["num_eval"] == want["num_eval"]
 
 
+LOCKSTEP_MODELS = [("heter", {}), ("homo", dict(within_ancestry=True)), ("heter-fixalpha", dict(fix_alpha=0.07)),
+                   ("homo-fixalpha", dict(within_ancestry=True, fix_alpha=0.07)), ("heter-fixpc", dict(fix_pc=[0.01, -0.02])),
+                   ("homo-fixpc", dict(within_ancestry=True, fix_pc=[0.01, -0.02]))]
+
+
 @pytest.mark.parametrize("speculate", [4, 2])
-def test_lockstep_fibers_give_each_run_its_own_search(golden_dir, speculate):
+@pytest.mark.parametrize("kw", [m for _, m in LOCKSTEP_MODELS], ids=[n for n, _ in LOCKSTEP_MODELS])
+def test_lockstep_fibers_give_each_run_its_own_search(golden_dir, speculate, kw):
     """lockstep.h -- what cohorts and multi-start searches run on: several OptimizeLLK searches as
     fibers of one thread, every step's requests answered by ONE evaluator call.  Here without a
     device: the oracle evaluates, run 0 must equal the plain search (evaluation count, alpha, LLKs
     bit for bit), the jittered runs must equal themselves done alone, and the steps must indeed
-    carry several runs' points each."""
+    carry several runs' points each.  Under each of the six models: simplexes of 2k+1 = 5 (Heter), k+1 = 3 (Homo,
+    HeterFixedPC), 2k = 4 and k = 2 (--FixAlpha) and ONE parameter (HomoFixedPC); run 0 is held to the oracle's own
+    search under the same model, PCs included."""
     import ctypes as C
     flat, _, _ = refio.load_flat(os.path.join(golden_dir, HAPMAP), os.path.join(golden_dir, "expected/result.Pileup"), 2)
     od = binding.OracleData(flat)
@@ -315,22 +323,27 @@ def test_lockstep_fibers_give_each_run_its_own_search(golden_dir, speculate):
     L.vb2_debug_lockstep_optimize.restype = C.c_int
     L.vb2_debug_lockstep_optimize.argtypes = [_abi.EVAL_FN, C.c_void_p, C.c_int32, C.POINTER(_abi.Model), C.c_int32,
                                               C.c_int32, C.POINTER(_abi.Estimate), C.POINTER(C.c_int64)]
-    m = _abi.Model(1, 0, 0, 0, 0.0, None, 1e-8, 0, 0)
+    m, _keep_fix_pc = vb.api._model(**kw)
+    if not kw:
+        m = _abi.Model(1, 0, 0, 0, 0.0, None, 1e-8, 0, 0)
     ests = (_abi.Estimate * runs)()
     steps = C.c_int64(0)
     assert L.vb2_debug_lockstep_optimize(fn, None, k, C.byref(m), runs, speculate, ests, C.byref(steps)) == 0
     together = list(sizes)
     assert steps.value == len(together) and max(together) > speculate        # steps carry several runs
-    plain = od.optimize()
+    plain = od.optimize(**kw)
     assert ests[0].alpha == plain["alpha"] and ests[0].llk1 == plain["llk1"] and ests[0].llk0 == plain["llk0"]
     assert ests[0].num_eval == plain["num_eval"]
+    assert all(e.converged for e in ests)
+    assert np.array_equal(np.array(ests[0].pc[:k]), plain["pc"]) and np.array_equal(np.array(ests[0].pc2[:k]), plain["pc2"])
     # each run alone (a gang of i + 1 runs whose last member is run i) gives the same answer
     for i in (1, 4):
         alone = (_abi.Estimate * (i + 1))()
         assert L.vb2_debug_lockstep_optimize(fn, None, k, C.byref(m), i + 1, speculate, alone, None) == 0
         for key in ("alpha", "llk1", "llk0", "num_eval"):
             assert getattr(alone[i], key) == getattr(ests[i], key), (i, key)
-    assert len({e.alpha for e in ests}) > 1                                   # the starts do differ
+    # the starts do differ (alpha is not searched under --FixAlpha: the likelihoods then)
+    assert len({e.llk1 if "fix_alpha" in kw and "fix_pc" not in kw else e.alpha for e in ests}) > 1
 
 
 def test_cpp_optimiser_other_dimensions():

@@ -434,11 +434,21 @@ class CohortBatch:
                 _abi.check(rc, "vb2_batch_eval")
         return step, out
 
-    def optimize(self, **model_kw):
+    def optimize(self, models=None, **model_kw):
+        """Every sample's OptimizeLLK in lock-step (vb2_batch_optimize_llk).  model_kw: one model for all samples;
+        models: a list of one keyword dict per sample instead (the library refuses any other length).  A sample with
+        a known-AF column is searched over alpha alone whatever its model says (estimator.h: apply_model)."""
         S = len(self.contexts)
-        m, keep = _model(**model_kw)
+        if models is None:
+            m, keep = _model(**model_kw)
+            arr, n = C.byref(m), 1
+        else:
+            built = [_model(**dict(model_kw, **kw)) for kw in models]
+            keep = [fpc for _, fpc in built]              # (the fix_pc arrays the structs point into)
+            n = len(built)
+            arr = (_abi.Model * max(1, n))(*[m for m, _ in built])
         est = (_abi.Estimate * S)()
-        _abi.check(self._lib.vb2_batch_optimize_llk(self._h, C.byref(m), 1, est),
+        _abi.check(self._lib.vb2_batch_optimize_llk(self._h, arr, n, est),
                    "vb2_batch_optimize_llk")
         return [_estimate_dict(est[s], self.num_pc) for s in range(S)]
 

@@ -519,6 +519,13 @@ long long vb2_debug_batch_regroups(vb2_batch* b)
     return b && b->impl ? (long long)b->impl->num_regroup : -1;
 }
 
+// Test aid (not part of the public header): kernel launches the batch has made so far (a step that is launched again,
+// Batch::eval_end, counts twice).
+long long vb2_debug_batch_launches(vb2_batch* b)
+{
+    return b && b->impl ? (long long)b->impl->num_launch : -1;
+}
+
 int vb2_batch_optimize_llk(vb2_batch* b, const vb2_model* models, int32_t num_model, vb2_estimate* out)
 {
     if (!b || !b->impl) {

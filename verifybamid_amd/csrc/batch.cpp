@@ -518,6 +518,7 @@ int Batch::launch_step(const int32_t* np, int first, const double* pc1, const do
     // would replicate the last point
     const bool small = max_n <= 2;
     const int NP = max_n > 4 ? 8 : small ? max_n : 4, shape = max_n > 4 ? 1 : small ? (max_n == 1 ? 2 : 3) : 0;
+    flight_nan_.resize((size_t)num_sample);
     for (int s = 0; s < num_sample; ++s) {
         int n = np[s];
         const size_t at = (size_t)s * kSlot + first;
@@ -528,8 +529,19 @@ int Batch::launch_step(const int32_t* np, int first, const double* pc1, const do
         }
         h_nv_[s] = n;
         if (n > 0) ++active;
+        flight_nan_[s] = 0;
+        const bool kaf = n > 0 && ctx_[s]->L.known_af != nullptr;
         for (int j = 0; j < n; ++j) {
             double* row = h_points_ + ((size_t)s * NP + j) * stride;
+            // NaN parameters (context.h: params_hold_nan, with this sample's own known-AF flag): the answer is 0, given in
+            // eval_end; the kernel evaluates a finite stand-in in the point's place, so that the step keeps its shape and a
+            // caller's NaN is never taken for the hand-off's "a workgroup never reported" marker
+            if (params_hold_nan(pc1 + (at + j) * k, pc2 + (at + j) * k, alpha[at + j], k, kaf)) {
+                flight_nan_[s] |= (unsigned char)(1u << j);
+                std::memset(row, 0, sizeof(double) * 2 * k);
+                row[2 * k] = 0.5;
+                continue;
+            }
             std::memcpy(row, pc1 + (at + j) * k, sizeof(double) * k);
             std::memcpy(row + k, pc2 + (at + j) * k, sizeof(double) * k);
             row[2 * k] = alpha[at + j];
@@ -626,7 +638,8 @@ int Batch::eval_end()
         if (!any_nan) break;
     }
     for (int s = 0; s < num_sample; ++s)
-        for (int j = 0; j < h_nv_[s]; ++j) flight_out_[(size_t)s * kSlot + flight_first_ + j] = h_out_[(size_t)s * NP + j];
+        for (int j = 0; j < h_nv_[s]; ++j)
+            flight_out_[(size_t)s * kSlot + flight_first_ + j] = (flight_nan_[s] >> j & 1) ? 0.0 : h_out_[(size_t)s * NP + j];
     return VB2_OK;
 }
 

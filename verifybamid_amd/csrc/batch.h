@@ -110,6 +110,7 @@ private:
     MultiLaunch ml_{};
     int flight_np_ = 0, flight_first_ = 0;
     double* flight_out_ = nullptr;
+    std::vector<unsigned char> flight_nan_;                // [sample] bit j: point j of the launch held NaN parameters -> 0
     // optimize() of a big cohort: two half-cohorts taking turns on the device (see batch.cpp)
     std::unique_ptr<Batch> half_[kMaxLanes];
     // the lanes' streams of optimize(): made back to back (different hardware queues: see cohort.cpp), lent to the lanes'

@@ -43,6 +43,25 @@ void fatal(const char* msg)
     std::exit(EXIT_FAILURE);
 }
 
+// One sample of a --PileupList cohort: the stdout block the reference prints for its sample (ContaminationEstimator.cpp:98-166,
+// the "Estimation from Optimize..." title its model selects, then the PCs and FREEMIX in default ostream formatting) -- what
+// vb2_run prints for the sample of a --PileupFile run.
+void print_sample_summary(const vb2_model& m, int k, const vb2_estimate& est)
+{
+    const bool heter = m.is_heter && !m.is_af_known;
+    const bool pcfix = (m.is_pc_fixed && m.fix_pc) || m.is_af_known;
+    const bool afix = !pcfix && m.is_alpha_fixed;
+    const char* title = !heter ? (pcfix ? "Estimation from OptimizeHomoFixedPC:" : afix ? nullptr : "Estimation from OptimizeHomo:")
+                               : (pcfix ? "Estimation from OptimizeHeterFixedPC:"
+                                        : afix ? "Estimation from OptimizeHeterFixedAlpha:" : "Estimation from OptimizeHeter:");
+    if (title) std::printf("%s\n", title);
+    std::printf("Contaminating Sample ");
+    for (int i = 0; i < k; ++i) std::printf("PC%d:%g\t", i + 1, est.pc[i]);
+    std::printf("\nIntended Sample ");
+    for (int i = 0; i < k; ++i) std::printf("PC%d:%g\t", i + 1, est.pc2[i]);
+    std::printf("\nFREEMIX(Alpha):%g\n", est.alpha < 0.5 ? est.alpha : 1 - est.alpha);
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
@@ -311,6 +330,8 @@ int main(int argc, char** argv)
             return EXIT_FAILURE;
         }
         int bad = 0;
+        for (size_t i = 0; i < pile.size(); ++i)
+            if (cst[i] == VB2_OK) print_sample_summary(args.model, args.num_pc, cres[i].est);
         std::printf("#PILEUP\tOUTPUT\tSTATUS\tFREEMIX\tFREELK1\tFREELK0\tAVG_DP\n");
         for (size_t i = 0; i < pile.size(); ++i) {
             const double al = cres[i].est.alpha;

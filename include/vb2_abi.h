@@ -307,6 +307,28 @@ int vb2_batch_eval(vb2_batch *b, const int32_t *num_point, const double *pc1, co
 int vb2_batch_optimize_llk(vb2_batch *b, const vb2_model *models, int32_t num_model,
                            vb2_estimate *out);
 
+/* Gradient and Hessian of several samples' LLK in one launch pair: sample s has num_point[s] >= 0 points, the rows of all
+ * samples concatenated in sample order -- pc1 / pc2 [sum][num_pc], alpha [sum] -> llk [sum], grad [sum][2k+1],
+ * hess [sum][2k+1][2k+1].  Every point's results are the bits vb2_llk_derivs_batch returns on that sample's context alone,
+ * whatever else the call holds.  Synchronous; not while a sample is inside vb2_ctx_search_begin / vb2_ctx_search_end. */
+int vb2_batch_derivs(vb2_batch *b, const int32_t *num_point, const double *pc1, const double *pc2, const double *alpha,
+                     double *llk_out, double *grad_out, double *hess_out);
+/* vb2_ctx_interval for every sample of the batch at est[s] (models: 1 entry or num_sample), the intervals advancing in
+ * lock-step: every step's one derivative point per unfinished sample goes into one vb2_batch_derivs call.  out[s] is what
+ * vb2_ctx_interval gives for the sample alone, bit for bit; status[s] the sample's own code; *num_step (may be NULL) the
+ * batched derivative steps taken: the largest num_launch among the samples, not their sum. */
+int vb2_batch_interval(vb2_batch *b, const vb2_model *models, int32_t num_model, const vb2_estimate *est,
+                       vb2_interval *out /* [num_sample] */, int32_t *status /* [num_sample] */, int64_t *num_step);
+/* The same driver over a caller's evaluator (the seam vb2_optimize_llk is for the search): no device needed.  A step calls
+ * fn once, on the calling thread's own stack, with num_point[s] = 1 for every sample whose interval is still running and 0
+ * for the others; rows and results concatenated in sample order as for vb2_batch_derivs.  Non-zero from fn ends every
+ * interval and is returned.  data_has_known_af: [num_sample] or NULL (none). */
+typedef int (*vb2_batch_derivs_fn)(void *user, int32_t num_sample, const int32_t *num_point, const double *pc1,
+                                   const double *pc2, const double *alpha, double *llk, double *grad, double *hess);
+int vb2_intervals_lockstep(vb2_batch_derivs_fn fn, void *user, int32_t num_sample, int32_t num_pc,
+                           const int32_t *data_has_known_af, const vb2_model *models, int32_t num_model,
+                           const vb2_estimate *est, vb2_interval *out, int32_t *status, int64_t *num_step);
+
 /* ------------------------------------------------------------------------- *
  * 2c. Marker shards: ONE sample's markers spread over several GPUs (BASELINE.json configs[3]).
  *     LLK is a sum of independent per-marker terms -- the reference's OpenMP
@@ -495,6 +517,13 @@ void vb2_source_set_destroy(vb2_source_set *set);
  * vb2_cohort_run does and writes. */
 int vb2_cohort_run_sources(const vb2_cohort_args *args, int32_t top, vb2_run_result *out /* [num_sample] */,
                            int32_t *status /* [num_sample] */, double *score, int32_t *shared);
+
+/* vb2_cohort_run that also computes every searched sample's interval (vb2_batch_interval: in lock-step, on a stage of its own
+ * next to the search) and writes <prefix>.CI per sample; ci: [num_sample] or NULL.  A sample that failed its search or its
+ * sanity check has no .CI (and a zeroed ci entry).  source_top > 0: --FindSource as well, what vb2_cohort_run_sources does
+ * with top = source_top (score and shared NULL).  One device only: VB2_ERR_INVALID otherwise, before any file is read. */
+int vb2_cohort_run_intervals(const vb2_cohort_args *args, int32_t source_top, vb2_run_result *out /* [num_sample] */,
+                             int32_t *status /* [num_sample] */, vb2_interval *ci);
 
 /* Host-side flattening only (no device): reads panel + pileup, resolves markers
  * and returns the arrays of vb2_input in library-owned memory; free with

@@ -157,6 +157,11 @@ class PanelView(C.Structure):
 EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                       C.POINTER(C.c_double), C.POINTER(C.c_double))
 
+# vb2_batch_derivs_fn: (user, num_sample, num_point, pc1, pc2, alpha, llk, grad, hess)
+BATCH_DERIVS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                              C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                              C.POINTER(C.c_double))
+
 # every symbol include/vb2_abi.h declares
 SYMBOLS = [
     "vb2_ctx_create", "vb2_ctx_destroy", "vb2_ctx_info", "vb2_llk_eval_batch", "vb2_llk_derivs_batch", "vb2_ctx_interval", "vb2_run_interval",
@@ -170,6 +175,7 @@ SYMBOLS = [
     "vb2_panel_get_view", "vb2_panel_write", "vb2_panel_destroy",
     "vb2_ctx_marginals", "vb2_source_set_create", "vb2_source_set_add", "vb2_source_set_scores",
     "vb2_source_set_destroy", "vb2_source_set_size", "vb2_cohort_run_sources",
+    "vb2_batch_derivs", "vb2_batch_interval", "vb2_intervals_lockstep", "vb2_cohort_run_intervals",
 ]
 
 _lib = None
@@ -260,6 +266,14 @@ def lib():
     L.vb2_source_set_destroy.restype = None
     L.vb2_cohort_run_sources.argtypes = [C.POINTER(CohortArgs), C.c_int32, C.POINTER(RunResult), C.POINTER(C.c_int32),
                                          C.c_void_p, C.c_void_p]
+    L.vb2_batch_derivs.argtypes = [C.c_void_p] + [C.c_void_p] * 7
+    L.vb2_batch_interval.argtypes = [C.c_void_p, C.POINTER(Model), C.c_int32, C.POINTER(Estimate), C.POINTER(Interval),
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    L.vb2_intervals_lockstep.argtypes = [BATCH_DERIVS_FN, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                         C.POINTER(Model), C.c_int32, C.POINTER(Estimate), C.POINTER(Interval),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    L.vb2_cohort_run_intervals.argtypes = [C.POINTER(CohortArgs), C.c_int32, C.POINTER(RunResult), C.POINTER(C.c_int32),
+                                           C.POINTER(Interval)]
     L.vb2_debug_set_tunable.argtypes = [C.c_char_p, C.c_int]
     L.vb2_debug_get_tunable.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
     _lib = L

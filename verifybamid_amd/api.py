@@ -453,6 +453,83 @@ class CohortBatch:
         return [_estimate_dict(est[s], self.num_pc) for s in range(S)]
 
 
+    def derivatives(self, num_point, pc1, pc2, alpha):
+        """LLK, gradient and Hessian of every sample at its own points in one launch pair per step (vb2_batch_derivs):
+        num_point [S] ints >= 0; pc1 / pc2 [P, k] and alpha [P] with P = sum(num_point), the samples' rows one after the
+        other.  Returns (llk [P], grad [P, 2k+1], hess [P, 2k+1, 2k+1]): every row is the bits of
+        LikelihoodContext.derivatives on that sample alone."""
+        S, k = len(self.contexts), self.num_pc
+        npt = np.ascontiguousarray(num_point, dtype=np.int32).reshape(S)
+        P = int(npt.sum())
+        pc1 = np.ascontiguousarray(np.asarray(pc1, dtype=np.float64).reshape(P, k))
+        pc2 = np.ascontiguousarray(np.asarray(pc2, dtype=np.float64).reshape(P, k))
+        alpha = np.ascontiguousarray(np.asarray(alpha, dtype=np.float64).reshape(P))
+        n = 2 * k + 1
+        llk, grad, hess = np.zeros(P), np.zeros((P, n)), np.zeros((P, n, n))
+        _abi.check(self._lib.vb2_batch_derivs(self._h, _p(npt), _p(pc1), _p(pc2), _p(alpha), _p(llk), _p(grad), _p(hess)),
+                   "vb2_batch_derivs")
+        return llk, grad, hess
+
+    def intervals(self, estimates, **model_kw):
+        """LikelihoodContext.interval for every sample at estimates[s] (of optimize(**model_kw)), advancing in lock-step
+        (vb2_batch_interval): one dict per sample, with its own "status"; every number is what the sample's context gives
+        alone, bit for bit.  self.num_interval_step: the batched derivative steps the call took."""
+        S = len(self.contexts)
+        built = [_model(known_af=c.data.known_af is not None, **model_kw) for c in self.contexts]
+        keep = [fpc for _, fpc in built]                  # (the fix_pc arrays the structs point into)
+        models = (_abi.Model * S)(*[m for m, _ in built])
+        est = (_abi.Estimate * S)(*[_estimate_struct(e, self.num_pc) for e in estimates])
+        ci = (_abi.Interval * S)()
+        status = (C.c_int32 * S)()
+        steps = C.c_int64(0)
+        _abi.check(self._lib.vb2_batch_interval(self._h, models, S, est, ci, status, C.byref(steps)), "vb2_batch_interval")
+        del keep
+        self.num_interval_step = int(steps.value)
+        return [dict(_interval_dict(ci[s]), status=int(status[s])) for s in range(S)]
+
+
+def intervals_with_evaluator(evaluate, num_pc, estimates, known_af=None, **model_kw):
+    """The lock-step interval driver over a Python evaluator (vb2_intervals_lockstep): no device.
+    evaluate(num_point [S] int32, pc1 [P, k], pc2 [P, k], alpha [P]) -> (llk [P], grad [P, 2k+1], hess [P, 2k+1, 2k+1]),
+    P = sum(num_point), called once per step -- on the calling thread's own stack -- with one point of every sample whose
+    interval is still running.  known_af: None or one flag per sample.  Returns (intervals, num_step): one dict per sample
+    (with "status") and the calls made."""
+    L = _abi.lib()
+    k, S = int(num_pc), len(estimates)
+    n = 2 * k + 1
+    err = []
+
+    def cb(_user, ns, npt, p1, p2, a, llk, grad, hess):
+        try:
+            num_point = np.ctypeslib.as_array(npt, (ns,)).copy()
+            P = int(num_point.sum())
+            res = evaluate(num_point, np.ctypeslib.as_array(p1, (P, k)).copy(), np.ctypeslib.as_array(p2, (P, k)).copy(),
+                           np.ctypeslib.as_array(a, (P,)).copy())
+            np.ctypeslib.as_array(llk, (P,))[:] = np.asarray(res[0], dtype=np.float64).reshape(P)
+            np.ctypeslib.as_array(grad, (P, n))[:] = np.asarray(res[1], dtype=np.float64).reshape(P, n)
+            np.ctypeslib.as_array(hess, (P, n, n))[:] = np.asarray(res[2], dtype=np.float64).reshape(P, n, n)
+            return 0
+        except Exception as exc:   # never let an exception cross the C boundary
+            err.append(exc)
+            return _abi.VB2_ERR_INVALID
+    fn = _abi.BATCH_DERIVS_FN(cb)
+    flags = [bool(f) for f in known_af] if known_af is not None else [False] * S
+    built = [_model(known_af=f, **model_kw) for f in flags]
+    keep = [fpc for _, fpc in built]
+    models = (_abi.Model * S)(*[m for m, _ in built])
+    kaf = (C.c_int32 * S)(*[int(f) for f in flags])
+    est = (_abi.Estimate * S)(*[_estimate_struct(e, k) for e in estimates])
+    ci = (_abi.Interval * S)()
+    status = (C.c_int32 * S)()
+    steps = C.c_int64(0)
+    rc = L.vb2_intervals_lockstep(fn, None, S, k, kaf, models, S, est, ci, status, C.byref(steps))
+    del keep
+    if err:
+        raise err[0]
+    _abi.check(rc, "vb2_intervals_lockstep")
+    return [dict(_interval_dict(ci[s]), status=int(status[s])) for s in range(S)], int(steps.value)
+
+
 class ShardGroup:
     """vb2_shard_group: ONE sample's markers sharded over several GPUs, partial LLKs met in one
     RCCL all-reduce per batch (BASELINE.json configs[3]).
@@ -611,13 +688,17 @@ def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_san
 
 def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, disable_sanity=False,
                      known_af_path=None, device=-1, output_pileup=False, group_size=0, num_host_thread=0,
-                     devices=None, find_source=False, source_top=3, sources_prefix=None, **model_kw):
+                     devices=None, find_source=False, source_top=3, sources_prefix=None, confidence_interval=False,
+                     **model_kw):
     """Many pileups against one panel (vb2_cohort_run): the panel is read once, the pileups are read
     and flattened by host threads while the device searches the previous group in lock-step.
     Returns one dict per sample (with its own "status" code).
     find_source (vb2_cohort_run_sources; one device): returns (samples, sources), sources = dict(score [S, S] -- row =
     target, column = candidate, NaN on the diagonal and for failed samples --, shared [S, S]); with output_prefixes and
-    sources_prefix it writes <sources_prefix>.Sources, source_top candidates per sample."""
+    sources_prefix it writes <sources_prefix>.Sources, source_top candidates per sample.
+    confidence_interval (vb2_cohort_run_intervals; one device; may be combined with find_source, which then returns no
+    matrices: sources = None): every searched sample's dict has an `interval` entry, and with output_prefixes its
+    <prefix>.CI is written."""
     S = len(pileup_paths)
     args, keep = _run_args(svd_prefix, pileup_paths[0], num_pc, disable_sanity, known_af_path,
                            sources_prefix if find_source else None,
@@ -636,7 +717,12 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
     res = (_abi.RunResult * S)()
     status = (C.c_int32 * S)()
     score = shared = None
-    if find_source:
+    civ = None
+    if confidence_interval:
+        civ = (_abi.Interval * S)()
+        _abi.check(_abi.lib().vb2_cohort_run_intervals(C.byref(ca), int(source_top) if find_source else 0, res, status, civ),
+                   "vb2_cohort_run_intervals")
+    elif find_source:
         score, shared = np.zeros((S, S)), np.zeros((S, S), dtype=np.int32)
         _abi.check(_abi.lib().vb2_cohort_run_sources(C.byref(ca), int(source_top), res, status, _p(score), _p(shared)),
                    "vb2_cohort_run_sources")
@@ -648,9 +734,11 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
         d.update(status=int(status[s]), num_marker=res[s].num_marker, num_site=res[s].num_site,
                  num_bases=int(res[s].num_bases), avg_depth=res[s].avg_depth, sd_depth=res[s].sd_depth,
                  seconds_load=res[s].seconds_load, seconds_optimize=res[s].seconds_optimize)
+        if civ is not None and status[s] == _abi.VB2_OK:
+            d["interval"] = _interval_dict(civ[s])
         out.append(d)
     if find_source:
-        return out, dict(score=score, shared=shared)
+        return out, (None if civ is not None else dict(score=score, shared=shared))
     return out
 
 

@@ -540,6 +540,70 @@ int vb2_batch_optimize_llk(vb2_batch* b, const vb2_model* models, int32_t num_mo
     }
 }
 
+int vb2_batch_derivs(vb2_batch* b, const int32_t* num_point, const double* pc1, const double* pc2, const double* alpha,
+                     double* llk_out, double* grad_out, double* hess_out)
+{
+    if (!b || !b->impl || !num_point) {
+        set_error("vb2_batch_derivs: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    try {
+        return b->impl->derivs(num_point, pc1, pc2, alpha, llk_out, grad_out, hess_out);
+    } catch (const std::bad_alloc&) {
+        set_error("out of host memory");
+        return VB2_ERR_NOMEM;
+    } catch (const std::exception& e) {
+        set_error(e.what());
+        return VB2_ERR_INVALID;
+    }
+}
+
+int vb2_batch_interval(vb2_batch* b, const vb2_model* models, int32_t num_model, const vb2_estimate* est, vb2_interval* out,
+                       int32_t* status, int64_t* num_step)
+{
+    if (num_step) *num_step = 0;
+    if (!b || !b->impl || !models || !est || !out || !status) {
+        set_error("vb2_batch_interval: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    try {
+        return vb2::batch_interval(b->impl, models, num_model, est, out, status, num_step, nullptr);
+    } catch (const std::bad_alloc&) {
+        set_error("out of host memory");
+        return VB2_ERR_NOMEM;
+    } catch (const std::exception& e) {
+        set_error(e.what());
+        return VB2_ERR_INVALID;
+    }
+}
+
+int vb2_intervals_lockstep(vb2_batch_derivs_fn fn, void* user, int32_t num_sample, int32_t num_pc, const int32_t* data_has_known_af,
+                           const vb2_model* models, int32_t num_model, const vb2_estimate* est, vb2_interval* out,
+                           int32_t* status, int64_t* num_step)
+{
+    if (num_step) *num_step = 0;
+    if (!fn) {
+        set_error("vb2_intervals_lockstep: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    try {
+        const vb2::BatchDerivsFn call = [fn, user](int32_t ns, const int32_t* np, const double* p1, const double* p2,
+                                                   const double* a, double* llk, double* grad, double* hess) {
+            const int rc = fn(user, ns, np, p1, p2, a, llk, grad, hess);
+            if (rc) set_error("vb2_intervals_lockstep: the evaluator failed");
+            return rc;
+        };
+        return vb2::intervals_lockstep(num_sample, num_pc, data_has_known_af, models, num_model, est, call, out, status, num_step,
+                                       nullptr);
+    } catch (const std::bad_alloc&) {
+        set_error("out of host memory");
+        return VB2_ERR_NOMEM;
+    } catch (const std::exception& e) {
+        set_error(e.what());
+        return VB2_ERR_INVALID;
+    }
+}
+
 int vb2_shard_group_create(const vb2_input* in, const int32_t* devices, int32_t num_device, vb2_shard_group** out)
 {
     if (!out) return VB2_ERR_INVALID;

@@ -57,6 +57,8 @@ Batch::~Batch()
     if (stream_) (void)hipStreamSynchronize(stream_);          // nothing of this batch is in flight any more
     if (d_slab_ && !recycle_device_slab(d_slab_, d_slab_bytes_, device)) (void)hipFree(d_slab_);
     if (h_slab_ && !recycle_pinned_slab(h_slab_, h_slab_bytes_, device)) (void)hipHostFree(h_slab_);
+    if (dv_dev_ && !recycle_device_slab(dv_dev_, dv_dev_bytes_, device)) (void)hipFree(dv_dev_);
+    if (dv_pin_ && !recycle_pinned_slab(dv_pin_, dv_pin_bytes_, device)) (void)hipHostFree(dv_pin_);
     if (stream_ && own_stream_ && !recycle_stream(stream_, device)) (void)hipStreamDestroy(stream_);
 }
 

@@ -55,6 +55,18 @@ public:
     // OptimizeLLK for every sample, searches advancing in lock-step; models: 1 or S entries
     int optimize(const vb2_model* models, int num_model, vb2_estimate* out);
 
+    // Gradient and Hessian of every sample's LLK (derivs.cpp; deriv_kernels.hip: the multi-sample kernels): sample s has
+    // num_point[s] >= 0 points, the rows of all samples concatenated in sample order -- pc1 / pc2 [sum][k], alpha [sum] ->
+    // llk [sum], grad [sum][2k+1], hess [sum][2k+1][2k+1].  Per step (kDerivChunk points of every sample that has any left)
+    // one pinned H2D copy of the job table and the rows, one marker launch per layout class, one reduction launch, one D2H
+    // copy and one synchronisation.  Every point's results are Context::derivs_host's bits on that sample alone.
+    int derivs(const int32_t* num_point, const double* pc1, const double* pc2, const double* alpha, double* llk, double* grad,
+               double* hess);
+    int64_t num_deriv_step = 0;             // steps derivs() has taken so far
+    // every sample's derivative scratch and the batch's staging, before the first step (derivs() calls it; a caller whose
+    // requests come from fibers calls it first, on its own stack)
+    int ensure_deriv_resources();
+
     static constexpr int kShapes = 4;       // launch shapes of a step: <= 4, 8, 1, 2 points per sample
     int num_sample = 0, num_pc = 0, device = -1;
     int64_t num_launch = 0;
@@ -111,6 +123,12 @@ private:
     int flight_np_ = 0, flight_first_ = 0;
     double* flight_out_ = nullptr;
     std::vector<unsigned char> flight_nan_;                // [sample] bit j: point j of the launch held NaN parameters -> 0
+    // derivs(): the job table and parameter rows on their way to the device, the results on their way back (pinned), and
+    // their device side; allocated at the first call
+    void* dv_pin_ = nullptr;
+    size_t dv_pin_bytes_ = 0;
+    void* dv_dev_ = nullptr;
+    size_t dv_dev_bytes_ = 0;
     // optimize() of a big cohort: two half-cohorts taking turns on the device (see batch.cpp)
     std::unique_ptr<Batch> half_[kMaxLanes];
     // the lanes' streams of optimize(): made back to back (different hardware queues: see cohort.cpp), lent to the lanes'

@@ -16,6 +16,9 @@
 // Extensions: --Device n selects the GPU; --Devices a,b,.. uses several -- one sample's markers
 // are sharded over them (partial log-likelihoods met in one RCCL all-reduce), a --PileupList
 // cohort is dealt to them group by group; --PileupList F runs many samples against one panel.
+// --ConfidenceInterval writes <Output>.CI for the sample of a --PileupFile / --BamFile run; --PileupList F --CohortInterval
+// writes <output prefix>.CI for every sample of the cohort, the intervals computed in lock-step next to the search (one
+// device; may be combined with --FindSource).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -86,6 +89,7 @@ int main(int argc, char** argv)
     int seed = 12345, nPC = 2, nthread = 4, device = -1, numStart = 1;
     bool lineSearch = false;
     bool confidenceInterval = false;
+    bool cohortInterval = false;
     bool findSource = false;
     int sourceTop = 3;
     // "Pileup Options" (main.cpp:176-187), defaults main.cpp:81-96 (MPLP_REALN | MPLP_SMART_OVERLAPS; UNMAP | SECONDARY |
@@ -139,6 +143,9 @@ int main(int argc, char** argv)
         // not in the reference: a 95% confidence interval for FREEMIX (profile likelihood) and standard errors of the free
         // parameters, written to <Output>.CI (vb2_run_interval)
         {"ConfidenceInterval", {Flag::kBool, &confidenceInterval, false}},
+        // not in the reference: the same interval for every sample of a --PileupList cohort, <output prefix>.CI each, computed
+        // in lock-step (vb2_cohort_run_intervals)
+        {"CohortInterval", {Flag::kBool, &cohortInterval, false}},
         // not in the reference: which sample of the --PileupList cohort does each sample's contamination come from?  Every
         // pair's log-likelihood ratio (vb2_cohort_run_sources); the --SourceTop best candidates per sample go to <Output>.Sources
         {"FindSource", {Flag::kBool, &findSource, false}},
@@ -176,9 +183,17 @@ int main(int argc, char** argv)
     }
     if (confidenceInterval) {                                           // single-sample, single-device runs only
         if (PileupList != "Empty")
-            fatal("--ConfidenceInterval cannot be combined with --PileupList: intervals are computed for one sample per run");
+            fatal("--ConfidenceInterval cannot be combined with --PileupList: intervals are computed for one sample per run "
+                  "(--CohortInterval computes them for every sample of a --PileupList cohort)");
         if (Devices != "Empty" && Devices.find(',') != std::string::npos)
             fatal("--ConfidenceInterval cannot be combined with more than one --Devices: intervals are computed on one device");
+    }
+    if (cohortInterval) {                                               // a cohort on one device
+        if (PileupList == "Empty")
+            fatal("--CohortInterval needs --PileupList: it computes the interval of every sample of a cohort run "
+                  "(--ConfidenceInterval is the flag for one sample)");
+        if (Devices != "Empty" && Devices.find(',') != std::string::npos)
+            fatal("--CohortInterval cannot be combined with more than one --Devices: the intervals of a cohort are computed on one device");
     }
     if (findSource) {                                                   // a cohort on one device
         if (PileupList == "Empty")
@@ -323,8 +338,9 @@ int main(int argc, char** argv)
         ca.num_host_thread = nthread > 4 ? nthread : 0;               // --NumThread above its default: reader threads
         std::vector<vb2_run_result> cres(pile.size());
         std::vector<int32_t> cst(pile.size());
-        const int rcc = findSource ? vb2_cohort_run_sources(&ca, sourceTop, cres.data(), cst.data(), nullptr, nullptr)
-                                   : vb2_cohort_run(&ca, cres.data(), cst.data());
+        const int rcc = cohortInterval ? vb2_cohort_run_intervals(&ca, findSource ? sourceTop : 0, cres.data(), cst.data(), nullptr)
+                        : findSource ? vb2_cohort_run_sources(&ca, sourceTop, cres.data(), cst.data(), nullptr, nullptr)
+                                     : vb2_cohort_run(&ca, cres.data(), cst.data());
         if (rcc != VB2_OK) {
             std::fprintf(stderr, "\nFATAL ERROR - \n%s\n\n", vb2_last_error());
             return EXIT_FAILURE;

@@ -9,6 +9,9 @@
 // (vb2_batch_*; still there as VB2_COHORT_STREAM=0).  Samples are independent, so several devices
 // need no collective: sample s runs on devices[s % n] (--Devices a,b,...; groups: group g on
 // devices[g % n]), which is the sample-parallel sharding of SURVEY.md 8e(2) inside one process.
+// vb2_cohort_run_intervals (--CohortInterval; one device): every searched sample's confidence interval as well, computed in
+// lock-step (interval.h) -- on the group's batch after its search, or, streaming, on an interval stage with a thread and a
+// stream of its own that takes the samples the search is done with.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -28,6 +31,7 @@
 #include "context.h"
 #include "estimator.h"
 #include "hostio.h"
+#include "interval.h"
 #include "source.h"
 #include "stream_search.h"
 #include "tunables.h"
@@ -52,10 +56,12 @@ class CohortRunner {
 public:
     // find_source: every searched sample also goes into a source set (vb2_cohort_run_sources) -- on the releaser thread,
     // before its context is destroyed; score / shared ([S][S], may be null) and <Output>.Sources after the last sample
+    // intervals: every searched sample's vb2_interval as well (vb2_cohort_run_intervals; one device) -- <prefix>.CI, and
+    // ci[s] when ci is not null -- before the sample goes to the releaser
     CohortRunner(const vb2_cohort_args* a, vb2_run_result* out, int32_t* status, bool find_source = false, int top = 0,
-                 double* score = nullptr, int32_t* shared = nullptr)
+                 double* score = nullptr, int32_t* shared = nullptr, bool intervals = false, vb2_interval* ci = nullptr)
         : a_(a), out_(out), status_(status), S_(a->num_sample), find_source_(find_source), top_(top), score_(score),
-          shared_(shared)
+          shared_(shared), intervals_(intervals), ci_(ci)
     {
         if (a->base.devices && a->base.num_device > 0) devices_.assign(a->base.devices, a->base.devices + a->base.num_device);
         else devices_.push_back(a->base.device);
@@ -108,6 +114,7 @@ public:
         for (int s = 0; s < S_; ++s) {
             std::memset(&out_[s], 0, sizeof(out_[s]));
             status_[s] = VB2_ERR_INVALID;
+            if (ci_) std::memset(&ci_[s], 0, sizeof(ci_[s]));
         }
         const bool timing = vb2::tunables().debug_timing != 0;
         const double t_run0 = now_s();
@@ -226,6 +233,15 @@ private:
     double* score_ = nullptr;
     int32_t* shared_ = nullptr;
     std::unique_ptr<vb2::SourceSet> sources_;
+    // --CohortInterval (false without it: nothing below then differs from a plain run).  Streaming: a searched sample waits
+    // in iv_queue_ for a fiber of the interval stage (interval_loop), which has a thread and a stream of its own.
+    bool intervals_ = false;
+    vb2_interval* ci_ = nullptr;
+    struct IvItem { int s = -1; vb2_estimate est{}; };
+    std::mutex iv_mu_;
+    std::condition_variable iv_cv_;
+    std::deque<IvItem> iv_queue_;
+    bool iv_closed_ = false;
 
     // after the last context is gone: the matrix, and <Output>.Sources next to the samples' own files
     int finish_sources()
@@ -431,9 +447,136 @@ private:
                 r->out_[s].est = est;
                 r->out_[s].seconds_optimize = seconds;
             }
+            if (r->intervals_ && rc == VB2_OK) {             // its interval first: the stage finishes the sample
+                {
+                    std::lock_guard<std::mutex> lk(r->iv_mu_);
+                    IvItem it;
+                    it.s = s;
+                    it.est = est;
+                    r->iv_queue_.push_back(it);
+                }
+                r->iv_cv_.notify_one();
+                return;
+            }
             r->finish_sample(s, rc == VB2_OK, &est, /*delivered=*/true);
         }
     };
+
+    // 1: *it is the next searched sample; 0: none right now (only when block is false); -1: none will come any more
+    int take_searched(bool block, IvItem* it)
+    {
+        std::unique_lock<std::mutex> lk(iv_mu_);
+        for (;;) {
+            if (!iv_queue_.empty()) {
+                *it = iv_queue_.front();
+                iv_queue_.pop_front();
+                return 1;
+            }
+            if (iv_closed_) return -1;
+            if (!block) return 0;
+            iv_cv_.wait(lk);
+        }
+    }
+
+    // sample s's interval is over (rc != 0: it has none): <prefix>.CI, the caller's array, then the sample leaves as it does
+    // without intervals -- its other files are the search's
+    void complete_interval(int s, int rc, const vb2_estimate& est, const vb2_interval& ci)
+    {
+        const char* prefix = a_->output_prefixes ? a_->output_prefixes[s] : nullptr;
+        if (!rc && prefix) rc = vb2::write_ci(prefix, ci);
+        if (!rc && ci_) ci_[s] = ci;
+        if (rc) status_[s] = rc;
+        finish_sample(s, true, &est, /*delivered=*/true);
+    }
+
+    // The interval stage of a streaming run: as many fibers as the search has slots, each running one sample's interval
+    // (interval.h).  At a step boundary an idle fiber takes the next searched sample; a step -- one Batch::derivs call for
+    // every live fiber's point -- goes out as soon as all live fibers have parked, however few they are.  The search of later
+    // samples goes on meanwhile on its own thread and streams.
+    void interval_loop(int d)
+    {
+        int dev = devices_[d];
+        if (dev < 0) (void)hipGetDevice(&dev);
+        int fail = hipSetDevice(dev) == hipSuccess ? VB2_OK : VB2_ERR_HIP;
+        if (fail) set_error("--CohortInterval: hipSetDevice failed");
+        int num_cu = 256;
+        {
+            hipDeviceProp_t prop;
+            if (!fail && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) num_cu = prop.multiProcessorCount;
+        }
+        const int k = a_->base.num_pc;
+        std::unique_ptr<vb2::Batch> batch;
+        if (!fail) {
+            vb2::Batch* bp = nullptr;
+            fail = vb2::Batch::create_slots(G_, dev, k, num_cu, &bp);
+            batch.reset(bp);
+        }
+        auto device_failure = [&](int rc) {          // concerns every sample: the run stops, what is queued leaves with rc
+            fail = rc;
+            std::lock_guard<std::mutex> lk(mu_);
+            if (!rc_all_) {
+                rc_all_ = rc;
+                err_all_ = vb2::g_last_error;
+            }
+            stop_ = true;
+        };
+        if (fail) device_failure(fail);
+        vb2::IntervalGang gang(G_, k);
+        std::vector<IvItem> cur(G_);
+        std::vector<vb2_interval> civ(G_);
+        std::vector<char> live(G_, 0);
+        int nlive = 0;
+        const vb2::BatchDerivsFn fn = [&](int32_t, const int32_t* np, const double* p1, const double* p2, const double* al,
+                                          double* llk, double* grad, double* hess) {
+            return batch->derivs(np, p1, p2, al, llk, grad, hess);
+        };
+        auto retire = [&](int i) {
+            live[i] = 0;
+            --nlive;
+            if (batch) (void)batch->set_slot(i, nullptr);
+            complete_interval(cur[i].s, fail ? fail : gang.result(i), cur[i].est, civ[i]);
+        };
+        for (;;) {
+            bool end = false;
+            for (int i = 0; i < G_; ++i) {
+                if (live[i]) continue;
+                IvItem it;
+                const int got = take_searched(nlive == 0, &it);
+                if (got < 0) end = true;
+                if (got <= 0) break;
+                cur[i] = it;
+                vb2::Context* c = slots_[it.s].ctx->impl;
+                int rcs = fail;
+                if (!rcs) rcs = batch->set_slot(i, c);
+                // (the sample's scratch and the batch's staging here, on this thread's own stack: the fibers only park)
+                if (!rcs) rcs = batch->ensure_deriv_resources();
+                if (rcs) {
+                    if (batch) (void)batch->set_slot(i, nullptr);
+                    complete_interval(it.s, rcs, it.est, civ[i]);
+                    continue;
+                }
+                vb2::IntervalGang::Task t;
+                t.model = &model_;
+                t.est = &cur[i].est;
+                t.out = &civ[i];
+                t.data_has_known_af = c->L.known_af != nullptr;
+                t.label = a_->output_prefixes ? a_->output_prefixes[it.s] : nullptr;
+                live[i] = 1;
+                ++nlive;
+                (void)gang.spawn(i, t);
+                if (gang.idle(i)) retire(i);
+            }
+            if (nlive == 0) {
+                if (end) break;
+                continue;
+            }
+            if (const int rc = gang.step(fn))
+                if (!fail) device_failure(rc);
+            for (int i = 0; i < G_; ++i)
+                if (live[i] && gang.idle(i)) retire(i);
+        }
+        cv_.notify_all();
+    }
 
     void stream_loop(int d)
     {
@@ -449,7 +592,24 @@ private:
             if (dev < 0) (void)hipGetDevice(&cur);
             if (hipGetDeviceProperties(&prop, cur) == hipSuccess && prop.multiProcessorCount > 0) num_cu = prop.multiProcessorCount;
         }
+        std::thread iv;
+        if (intervals_) iv = std::thread([this, d] { interval_loop(d); });
+        struct IvJoin {                              // the stage ends when the search has handed over its last sample
+            CohortRunner* r;
+            std::thread* t;
+            ~IvJoin()
+            {
+                if (!t->joinable()) return;
+                {
+                    std::lock_guard<std::mutex> lk(r->iv_mu_);
+                    r->iv_closed_ = true;
+                }
+                r->iv_cv_.notify_all();
+                t->join();
+            }
+        };
         try {
+            IvJoin join{this, &iv};
             int dev = devices_[d];
             if (dev < 0) (void)hipGetDevice(&dev);
             rc = vb2::stream_search(dev, a_->base.num_pc, num_cu, G_, src, own_streams_.empty() ? nullptr : &own_streams_[(size_t)d * 4]);
@@ -542,10 +702,19 @@ private:
             if (!ctxs.empty()) {
                 const double t1 = now_s();
                 std::vector<vb2_estimate> est(ctxs.size());
+                std::vector<vb2_interval> civ;
+                std::vector<int32_t> ist;
                 vb2_batch* batch = nullptr;
                 try {
                     rcb = vb2_batch_create(ctxs.data(), (int32_t)ctxs.size(), &batch);
                     if (!rcb) rcb = vb2_batch_optimize_llk(batch, &model_, 1, est.data());
+                    if (!rcb && intervals_) {        // on the same batch, before it goes
+                        civ.resize(ctxs.size());
+                        ist.assign(ctxs.size(), VB2_ERR_INVALID);
+                        std::vector<const char*> labels;
+                        for (const int s : who) labels.push_back(a_->output_prefixes ? a_->output_prefixes[s] : nullptr);
+                        rcb = vb2::batch_interval(batch->impl, &model_, 1, est.data(), civ.data(), ist.data(), nullptr, labels.data());
+                    }
                 } catch (const std::exception& e) {
                     set_error(e.what());
                     rcb = VB2_ERR_INVALID;
@@ -564,6 +733,12 @@ private:
                             int rw = vb2::write_ancestry(prefix, a_->base.num_pc, est[i].pc, est[i].pc2);
                             if (!rw) rw = vb2::write_selfsm(prefix, *slots_[s].flat, est[i], true);   // (cohort input is text pileups: #READS = NA)
                             if (rw) status_[s] = rw;
+                        }
+                        if (intervals_) {
+                            int ri = ist[i];
+                            if (!ri && prefix) ri = vb2::write_ci(prefix, civ[i]);
+                            if (!ri && ci_) ci_[s] = civ[i];
+                            if (ri) status_[s] = ri;
                         }
                     }
                 }
@@ -657,6 +832,32 @@ extern "C" int vb2_cohort_run_sources(const vb2_cohort_args* a, int32_t top, vb2
     }
     try {
         CohortRunner runner(a, out, status, true, top, score, shared);
+        const int rc = runner.run();
+        if (rc && !runner.error().empty()) set_error(runner.error());
+        return rc;
+    } catch (const std::bad_alloc&) {
+        set_error("out of host memory");
+        return VB2_ERR_NOMEM;
+    } catch (const std::exception& e) {
+        set_error(e.what());
+        return VB2_ERR_INVALID;
+    }
+}
+
+extern "C" int vb2_cohort_run_intervals(const vb2_cohort_args* a, int32_t source_top, vb2_run_result* out, int32_t* status,
+                                        vb2_interval* ci)
+{
+    if (!a || !out || !status || a->num_sample < 1 || !a->pileup_paths || !a->base.ud_path || !a->base.mean_path ||
+        !a->base.bed_path || a->base.num_pc < 1 || a->base.num_pc > VB2_MAX_PC || source_top < 0) {
+        set_error("vb2_cohort_run_intervals: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    if (a->base.num_device > 1 || a->base.num_device < 0) {
+        set_error("--CohortInterval takes one device: the intervals of a cohort are not spread over several --Devices");
+        return VB2_ERR_INVALID;
+    }
+    try {
+        CohortRunner runner(a, out, status, source_top > 0, source_top, nullptr, nullptr, true, ci);
         const int rc = runner.run();
         if (rc && !runner.error().empty()) set_error(runner.error());
         return rc;

@@ -7,6 +7,7 @@
 #include <atomic>
 #include <chrono>
 #include <cstdio>
+#include <functional>
 #include <memory>
 #include <string>
 #include <mutex>
@@ -156,6 +157,7 @@ public:
     // kept for the context's lifetime.  Not between resident_begin and resident_end.  Defined in derivs.cpp.
     int derivs_host(int num_point, const double* pc1, const double* pc2, const double* alpha, double* llk, double* grad,
                     double* hess);
+    int ensure_deriv_scratch();               // d_deriv, on the first call (the calling thread's device is set to this context's)
     double* d_deriv = nullptr;
     size_t d_deriv_bytes = 0;
     // Genotype marginals at one point (source_kernels.hip; defined in source.cpp): the contaminant's genotype likelihood
@@ -234,6 +236,24 @@ namespace vb2 {
 // vb2_ctx_interval / <prefix>.CI (interval.cpp)
 int ctx_interval(Context* ctx, const vb2_model& model, const vb2_estimate& est, vb2_interval* out);
 int write_ci(const std::string& prefix, const vb2_interval& ci);
+// The same interval over any evaluator of ONE point's LLK, gradient [2k+1] and Hessian [2k+1][2k+1] (order pc1 pc2 alpha):
+// the same points in the same order whatever answers them.  label (may be null) starts the NOTICE lines.
+typedef std::function<int(const double* pc1, const double* pc2, double alpha, double* llk, double* grad, double* hess)> DerivFn;
+int interval_at(int num_pc, bool data_has_known_af, const vb2_model& model, const vb2_estimate& est, const DerivFn& fn,
+                vb2_interval* out, const char* label);
+// A batched evaluator: slot s has num_point[s] (0 or 1 here) points, the rows of all slots concatenated in slot order.
+typedef std::function<int(int32_t num_slot, const int32_t* num_point, const double* pc1, const double* pc2, const double* alpha,
+                          double* llk, double* grad, double* hess)> BatchDerivsFn;
+// interval_at for every sample, advancing in lock-step (lockstep.h: one fiber per sample, parked at every request; a step =
+// ONE call of fn with every live sample's point, made on the caller's own stack).  A sample whose interval ends early stops
+// contributing.  status[s]: the sample's own code; the return value: a failure of fn (it ends every interval).
+// models: 1 or num_sample entries; labels: null or [num_sample]; *num_step (may be null): calls of fn.
+int intervals_lockstep(int num_sample, int num_pc, const int32_t* data_has_known_af, const vb2_model* models, int num_model,
+                       const vb2_estimate* est, const BatchDerivsFn& fn, vb2_interval* out, int32_t* status, int64_t* num_step,
+                       const char* const* labels);
+class Batch;
+int batch_interval(Batch* b, const vb2_model* models, int num_model, const vb2_estimate* est, vb2_interval* out, int32_t* status,
+                   int64_t* num_step, const char* const* labels);
 }  // namespace vb2
 
 struct vb2_ctx {

@@ -29,6 +29,21 @@ inline size_t deriv_scratch_doubles(const DeviceLayout& L)
 hipError_t launch_llk_derivs(const DeviceLayout& L, int num_point, const double* d_points, double* d_marker, double* d_out,
                              hipStream_t stream);
 
+// One sample's share of a launch pair that serves several samples: its layout, num_point <= kDerivChunk parameter rows, its own
+// scratch (kDerivChunk x kDerivVals x m_pad doubles) and where its deriv_out_count(k) doubles per point go.  All device memory.
+struct DerivJob {
+    DeviceLayout L;
+    const double* points;
+    double* marker;
+    double* out;
+    int32_t num_point;
+    int32_t reserved;
+};
+// Enqueue the derivatives of num_job jobs on stream as one launch of the marker kernel per layout class present and one of
+// the reduction.  h_jobs: the table as the host wrote it (probability-domain jobs first), d_jobs: where it is -- or will be,
+// stream-ordered before this call -- on the device.  Every point's results are launch_llk_derivs' bits.
+hipError_t launch_llk_derivs_multi(const DerivJob* h_jobs, const DerivJob* d_jobs, int num_job, hipStream_t stream);
+
 }  // namespace vb2
 
 #endif

@@ -15,6 +15,9 @@
 //   * llk_derivs_reduce_kernel: one workgroup per (output, point) sums a scalar over the markers with the sorted panel
 //     rows (AF = (UD pc + mu) / 2: the chain rule), in a fixed order -- thread t takes positions t, t + 256, ..., then a
 //     fixed tree.  A point's results are the same bits whatever else the batch holds and from one call to the next.
+//   * llk_derivs_marker_multi_kernel / llk_derivs_reduce_multi_kernel: the same two bodies for the points of SEVERAL samples
+//     in one launch pair (Batch::derivs), each workgroup reading its sample's layout through a job table in device memory.
+//     A point's results are the single-sample kernels' bits.
 #include "deriv_kernels.h"
 
 #include <hip/hip_runtime.h>
@@ -71,14 +74,14 @@ __device__ __forceinline__ void gf_derivs(double af, bool fixed, double* gf, dou
     d2[2] = clamped ? 0.0 : 2.0;
 }
 
+// The body of the marker kernels: point pt of `points`, as workgroup bx of the nbx that share the point's 16-tile groups.
+// What a marker's ten scalars are does not depend on bx / nbx, nor on where L was read from.
 template <bool PD>
-__global__ void __launch_bounds__(kThreads)
-llk_derivs_marker_kernel(const DeviceLayout L, const double* __restrict__ points, double* __restrict__ out)
+__device__ __forceinline__ void derivs_marker_body(const DeviceLayout& L, const double* __restrict__ points,
+                                                   double* __restrict__ out, double* tab, int pt, int bx, int nbx)
 {
-    extern __shared__ __attribute__((aligned(16))) double tab[];      // [nrow][6 pairs][kEntry] (+ [3] in the log domain)
     constexpr int kRowDoubles = PD ? kRowDoublesPd : kRowDoublesLog;
     const int tid = threadIdx.x;
-    const int pt = blockIdx.y;
     const int k = L.num_pc, stride = 2 * k + 1;
     const double* prow = points + (size_t)pt * stride;
     const double alpha = prow[2 * k];
@@ -166,7 +169,7 @@ llk_derivs_marker_kernel(const DeviceLayout L, const double* __restrict__ points
     // ---- one thread per marker of the sorted order ----
     const int m = tid & 15;
     const int ntile_grp = (L.num_mt + 15) / 16;
-    for (int tg = blockIdx.x; tg < ntile_grp; tg += gridDim.x) {
+    for (int tg = bx; tg < ntile_grp; tg += nbx) {
         const int mt = tg * 16 + (tid >> 4);
         if (mt >= L.num_mt) continue;
         const size_t pos = (size_t)mt * 16 + (size_t)m;
@@ -320,6 +323,28 @@ llk_derivs_marker_kernel(const DeviceLayout L, const double* __restrict__ points
     }
 }
 
+template <bool PD>
+__global__ void __launch_bounds__(kThreads)
+llk_derivs_marker_kernel(const DeviceLayout L, const double* __restrict__ points, double* __restrict__ out)
+{
+    extern __shared__ __attribute__((aligned(16))) double tab[];      // [nrow][6 pairs][kEntry] (+ [3] in the log domain)
+    derivs_marker_body<PD>(L, points, out, tab, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// The same for several samples: workgroup (x, y, z) is stripe x of point y of job z.  The job -- its layout included -- is
+// read at a workgroup-uniform address (scalar loads); a point the job does not have, or a stripe beyond the job's 16-tile
+// groups, leaves before it builds a table.
+template <bool PD>
+__global__ void __launch_bounds__(kThreads)
+llk_derivs_marker_multi_kernel(const DerivJob* __restrict__ jobs)
+{
+    extern __shared__ __attribute__((aligned(16))) double tab[];      // sized for the widest dictionary of the launch
+    const DerivJob& job = jobs[blockIdx.z];
+    if ((int)blockIdx.y >= job.num_point) return;
+    if ((int)blockIdx.x >= (job.L.num_mt + 15) / 16) return;
+    derivs_marker_body<PD>(job.L, job.points, job.marker, tab, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x);
+}
+
 // Output e of a point (deriv_out_count): 0 = LLK, then the gradient, then the Hessian's upper triangle row by row.
 // Returns the marker scalar it sums and the UD columns (-1: none) and power-of-two factor that weight it.
 __device__ __forceinline__ void output_terms(int e, int k, int& val, int& ca, int& cb, double& f)
@@ -349,12 +374,11 @@ __device__ __forceinline__ void output_terms(int e, int k, int& val, int& ca, in
     else val = 9;
 }
 
-__global__ void __launch_bounds__(kThreads)
-llk_derivs_reduce_kernel(const DeviceLayout L, const double* __restrict__ marker, double* __restrict__ out)
+// The body of the reduction kernels: output e of point pt.
+__device__ __forceinline__ void derivs_reduce_body(const DeviceLayout& L, const double* __restrict__ marker,
+                                                   double* __restrict__ out, double* part, int e, int pt)
 {
-    __shared__ double part[kThreads];
     const int tid = threadIdx.x;
-    const int e = blockIdx.x, pt = blockIdx.y;
     const int k = L.num_pc;
     int val, ca, cb;
     double f;
@@ -382,6 +406,23 @@ llk_derivs_reduce_kernel(const DeviceLayout L, const double* __restrict__ marker
     if (tid == 0) out[(size_t)pt * deriv_out_count(k) + e] = part[0] * f;
 }
 
+__global__ void __launch_bounds__(kThreads)
+llk_derivs_reduce_kernel(const DeviceLayout L, const double* __restrict__ marker, double* __restrict__ out)
+{
+    __shared__ double part[kThreads];
+    derivs_reduce_body(L, marker, out, part, (int)blockIdx.x, (int)blockIdx.y);
+}
+
+// workgroup (x, y, z): output x of point y of job z
+__global__ void __launch_bounds__(kThreads)
+llk_derivs_reduce_multi_kernel(const DerivJob* __restrict__ jobs)
+{
+    __shared__ double part[kThreads];
+    const DerivJob& job = jobs[blockIdx.z];
+    if ((int)blockIdx.y >= job.num_point || (int)blockIdx.x >= deriv_out_count(job.L.num_pc)) return;
+    derivs_reduce_body(job.L, job.marker, job.out, part, (int)blockIdx.x, (int)blockIdx.y);
+}
+
 }  // namespace
 
 hipError_t launch_llk_derivs(const DeviceLayout& L, int num_point, const double* d_points, double* d_marker, double* d_out,
@@ -405,6 +446,52 @@ hipError_t launch_llk_derivs(const DeviceLayout& L, int num_point, const double*
     if (rc != hipSuccess) return rc;
     const dim3 rgrid((unsigned)deriv_out_count(L.num_pc), (unsigned)num_point);
     hipLaunchKernelGGL(llk_derivs_reduce_kernel, rgrid, block, 0, stream, L, d_marker, d_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_llk_derivs_multi(const DerivJob* h_jobs, const DerivJob* d_jobs, int num_job, hipStream_t stream)
+{
+    if (num_job <= 0) return hipSuccess;
+    // the jobs come sorted: probability domain first.  Per class one launch of the marker kernel.
+    int num_pd = 0, total_points = 0, nout = 0, num_cu = 1;
+    for (int j = 0; j < num_job; ++j) {
+        const DerivJob& job = h_jobs[j];
+        if (job.num_point < 1 || job.num_point > kDerivChunk) return hipErrorInvalidValue;
+        if (job.L.pd) {
+            if (num_pd != j) return hipErrorInvalidValue;
+            ++num_pd;
+        }
+        total_points += job.num_point;
+        nout = nout > deriv_out_count(job.L.num_pc) ? nout : deriv_out_count(job.L.num_pc);
+        num_cu = job.L.num_cu > num_cu ? job.L.num_cu : num_cu;
+    }
+    // about four workgroups per CU over the whole launch pair, at least one per (job, point)
+    int gx_all = (4 * num_cu + total_points - 1) / total_points;
+    gx_all = gx_all > 0 ? gx_all : 1;
+    const dim3 block(kThreads);
+    for (int cls = 0; cls < 2; ++cls) {
+        const int first = cls == 0 ? 0 : num_pd, count = cls == 0 ? num_pd : num_job - num_pd;
+        if (count == 0) continue;
+        size_t shmem = 0;
+        int max_grp = 1;
+        for (int j = first; j < first + count; ++j) {
+            const DeviceLayout& L = h_jobs[j].L;
+            const size_t need = (size_t)(L.num_code + 1) * (L.pd ? kRowDoublesPd : kRowDoublesLog) * sizeof(double);
+            shmem = need > shmem ? need : shmem;
+            const int grp = (L.num_mt + 15) / 16;
+            max_grp = grp > max_grp ? grp : max_grp;
+        }
+        const int gx = gx_all < max_grp ? gx_all : max_grp;
+        const dim3 grid((unsigned)gx, (unsigned)kDerivChunk, (unsigned)count);
+        if (cls == 0)
+            hipLaunchKernelGGL(llk_derivs_marker_multi_kernel<true>, grid, block, shmem, stream, d_jobs + first);
+        else
+            hipLaunchKernelGGL(llk_derivs_marker_multi_kernel<false>, grid, block, shmem, stream, d_jobs + first);
+        const hipError_t rc = hipGetLastError();
+        if (rc != hipSuccess) return rc;
+    }
+    const dim3 rgrid((unsigned)nout, (unsigned)kDerivChunk, (unsigned)num_job);
+    hipLaunchKernelGGL(llk_derivs_reduce_multi_kernel, rgrid, block, 0, stream, d_jobs);
     return hipGetLastError();
 }
 

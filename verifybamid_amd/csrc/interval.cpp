@@ -1,5 +1,8 @@
 // interval.cpp -- standard errors and the profile-likelihood interval for FREEMIX (vb2_ctx_interval), on the derivatives
 // of the LLK the device returns (Context::derivs_host, deriv_kernels.hip).  DESIGN.md section 10.
+// The interval is blocking code over an evaluator of one point's derivatives: ctx_interval hands it the context's, and
+// intervals_lockstep runs one such body per sample as the fibers of a FiberGang (lockstep.h), every step's parked requests
+// answered by ONE call of a batched evaluator (Batch::derivs: vb2_batch_interval; a caller's: vb2_intervals_lockstep).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -10,7 +13,9 @@
 #include <string>
 #include <vector>
 
+#include "batch.h"
 #include "context.h"
+#include "interval.h"
 
 namespace vb2 {
 namespace {
@@ -79,14 +84,14 @@ bool solve_spd(std::vector<double> A, const std::vector<double>& b, std::vector<
 
 class Profiler {
 public:
-    Profiler(Context* c, const Free& fr) : ctx_(c), fr_(fr) {}
+    Profiler(const DerivFn& fn, const Free& fr) : fn_(fn), fr_(fr) {}
     int eval(const std::vector<double>& u, double a, Eval* e)
     {
         const int k = fr_.k, n = 2 * k + 1, nu = fr_.nu;
         std::vector<double> pc1(k > 0 ? k : 1), pc2(k > 0 ? k : 1), grad(n), hess((size_t)n * n);
         fr_.unpack(u.data(), pc1.data(), pc2.data());
         double llk = 0;
-        if (int rc = ctx_->derivs_host(1, pc1.data(), pc2.data(), &a, &llk, grad.data(), hess.data())) return rc;
+        if (int rc = fn_(pc1.data(), pc2.data(), a, &llk, grad.data(), hess.data())) return rc;
         ++launches;
         e->f = llk;
         e->ga = grad[2 * k];
@@ -150,7 +155,7 @@ public:
     int64_t launches = 0;
 
 private:
-    Context* ctx_;
+    const DerivFn& fn_;
     const Free& fr_;
 };
 
@@ -158,9 +163,18 @@ private:
 
 int ctx_interval(Context* ctx, const vb2_model& model_in, const vb2_estimate& est, vb2_interval* out)
 {
+    const DerivFn fn = [ctx](const double* pc1, const double* pc2, double a, double* llk, double* grad, double* hess) {
+        return ctx->derivs_host(1, pc1, pc2, &a, llk, grad, hess);
+    };
+    return interval_at(ctx->num_pc, ctx->L.known_af != nullptr, model_in, est, fn, out, nullptr);
+}
+
+int interval_at(int k, bool data_has_known_af, const vb2_model& model_in, const vb2_estimate& est, const DerivFn& fn,
+                vb2_interval* out, const char* label)
+{
     std::memset(out, 0, sizeof(*out));
-    const int k = ctx->num_pc;
-    const bool kaf = model_in.is_af_known != 0 || ctx->L.known_af != nullptr;
+    const bool kaf = model_in.is_af_known != 0 || data_has_known_af;
+    const std::string who = label ? std::string(label) + ": " : std::string();       // (a cohort run: whose NOTICE it is)
     const bool heter = model_in.is_heter && !kaf;                                  // apply_model (estimator.cpp)
     const bool pcfix = (model_in.is_pc_fixed && model_in.fix_pc) || kaf;
     const bool afix = !pcfix && model_in.is_alpha_fixed;
@@ -183,9 +197,10 @@ int ctx_interval(Context* ctx, const vb2_model& model_in, const vb2_estimate& es
     std::vector<double> u0(fr.nu);
     for (int j = 0; j < fr.nu; ++j) u0[j] = j < k ? fr.base1[j] : fr.base2[j - k];
     if (!est.converged && notices)
-        std::fprintf(stderr, "NOTICE - the search did not converge: the interval is computed at its best point all the same\n");
+        std::fprintf(stderr, "NOTICE - %sthe search did not converge: the interval is computed at its best point all the same\n",
+                     who.c_str());
 
-    Profiler prof(ctx, fr);
+    Profiler prof(fn, fr);
     const double a_hat = est.alpha;
     out->alpha_free = fr.alpha_free ? 1 : 0;
     out->num_free = fr.nu + (fr.alpha_free ? 1 : 0);
@@ -216,8 +231,8 @@ int ctx_interval(Context* ctx, const vb2_model& model_in, const vb2_estimate& es
         if (!pd) {
             std::fill(se.begin(), se.end(), kNaN);
             if (notices && nf > 0)
-                std::fprintf(stderr, "NOTICE - the Hessian of the log-likelihood at the estimate is not negative definite "
-                                     "(typical for FREEMIX near 0): standard errors are NA\n");
+                std::fprintf(stderr, "NOTICE - %sthe Hessian of the log-likelihood at the estimate is not negative definite "
+                                     "(typical for FREEMIX near 0): standard errors are NA\n", who.c_str());
         }
     }
     out->freemix_se = fr.alpha_free ? a_hat * (1 - a_hat) * se[nu] : kNaN;
@@ -296,8 +311,8 @@ int ctx_interval(Context* ctx, const vb2_model& model_in, const vb2_estimate& es
         if (v5 >= llk_max - kHalfChi2) { out->hi = 0.5; out->llk_hi = v5; }
         else if (int rc = root(f_hat, v_hat, 0.5, v5, &out->hi, &out->llk_hi)) return rc;
         if (llk_max > -est.llk1 + 1e-9 * std::fabs(est.llk1) && notices)
-            std::fprintf(stderr, "NOTICE - a profile point has a higher log-likelihood (%.10g) than the search's estimate "
-                                 "(%.10g): the search stopped short of the maximum\n", llk_max, -est.llk1);
+            std::fprintf(stderr, "NOTICE - %sa profile point has a higher log-likelihood (%.10g) than the search's estimate "
+                                 "(%.10g): the search stopped short of the maximum\n", who.c_str(), llk_max, -est.llk1);
         out->llk_max = llk_max;
     }
 
@@ -339,6 +354,126 @@ int ctx_interval(Context* ctx, const vb2_model& model_in, const vb2_estimate& es
     out->num_row = r;
     out->num_launch = prof.launches;
     return VB2_OK;
+}
+
+// One interval_at per sample as the fibers of a gang: see context.h.
+IntervalGang::IntervalGang(int num_fiber, int num_pc) : gang_(num_fiber, 1), k_(num_pc), task_(num_fiber), rc_(num_fiber, VB2_OK)
+{
+    gang_.open(num_pc, [this](int i) {
+        const Task& t = task_[i];
+        int rc = VB2_ERR_INVALID;
+        try {
+            FiberGang* g = &gang_;
+            void* user = g->user(i);
+            const DerivFn fn = [user](const double* pc1, const double* pc2, double a, double* llk, double* grad, double* hess) {
+                return FiberGang::derivs_cb(user, pc1, pc2, a, llk, grad, hess);      // (parks: no device call on this stack)
+            };
+            rc = interval_at(k_, t.data_has_known_af, *t.model, *t.est, fn, t.out, t.label);
+        } catch (const std::bad_alloc&) {
+            rc = VB2_ERR_NOMEM;
+        } catch (const std::exception& e) {
+            set_error(e.what());
+            rc = VB2_ERR_INVALID;
+        } catch (...) {                              // nothing may unwind past the fiber's entry frame
+            set_error("interval: unknown exception");
+            rc = VB2_ERR_INVALID;
+        }
+        rc_[i] = rc;
+    });
+}
+
+int IntervalGang::spawn(int i, const Task& t)
+{
+    task_[i] = t;
+    rc_[i] = VB2_OK;
+    if (gang_.spawn(i) < 0) {
+        set_error("interval: no stack for a fiber");
+        rc_[i] = VB2_ERR_NOMEM;
+        return VB2_ERR_NOMEM;
+    }
+    return VB2_OK;
+}
+
+int IntervalGang::step(const BatchDerivsFn& fn)
+{
+    const int F = gang_.size(), k = k_, n = 2 * k + 1;
+    std::vector<FiberGang::Request>& req = gang_.requests();
+    np_.assign(F, 0);
+    p1_.clear(); p2_.clear(); al_.clear();
+    for (int i = 0; i < F; ++i) {
+        if (gang_.idle(i) || req[i].n <= 0) continue;
+        np_[i] = 1;
+        p1_.insert(p1_.end(), req[i].p1, req[i].p1 + k);
+        p2_.insert(p2_.end(), req[i].p2, req[i].p2 + k);
+        al_.push_back(req[i].a[0]);
+    }
+    const size_t P = al_.size();
+    if (P == 0) return VB2_OK;
+    llk_.assign(P, 0.0);
+    grad_.assign(P * n, 0.0);
+    hess_.assign(P * n * n, 0.0);
+    int rc = gang_.error();
+    if (!rc) {
+        rc = fn(F, np_.data(), p1_.data(), p2_.data(), al_.data(), llk_.data(), grad_.data(), hess_.data());
+        ++steps;
+        if (rc) gang_.fail(rc);                      // the fibers see it at resume and unwind
+    }
+    size_t o = 0;
+    for (int i = 0; i < F && !rc; ++i) {
+        if (np_[i] == 0) continue;
+        req[i].out[0] = llk_[o];
+        std::memcpy(req[i].grad, &grad_[o * n], sizeof(double) * n);
+        std::memcpy(req[i].hess, &hess_[o * n * n], sizeof(double) * n * n);
+        ++o;
+    }
+    gang_.resume_parked();
+    return rc;
+}
+
+int intervals_lockstep(int num_sample, int num_pc, const int32_t* data_has_known_af, const vb2_model* models, int num_model,
+                       const vb2_estimate* est, const BatchDerivsFn& fn, vb2_interval* out, int32_t* status, int64_t* num_step,
+                       const char* const* labels)
+{
+    if (num_step) *num_step = 0;
+    if (num_sample < 1 || num_pc < 1 || num_pc > VB2_MAX_PC || !models || (num_model != 1 && num_model != num_sample) || !est ||
+        !out || !status) {
+        set_error("intervals in lock-step: invalid argument (models: one entry or one per sample)");
+        return VB2_ERR_INVALID;
+    }
+    IntervalGang g(num_sample, num_pc);
+    for (int s = 0; s < num_sample; ++s) {
+        IntervalGang::Task t;
+        t.model = &models[num_model == 1 ? 0 : s];
+        t.est = &est[s];
+        t.out = &out[s];
+        t.data_has_known_af = data_has_known_af && data_has_known_af[s];
+        t.label = labels ? labels[s] : nullptr;
+        (void)g.spawn(s, t);                         // (up to its first request; a failure is the sample's own)
+    }
+    int rc = VB2_OK;
+    while (g.pending())
+        if (const int r = g.step(fn)) rc = rc ? rc : r;
+    for (int s = 0; s < num_sample; ++s) status[s] = g.result(s);
+    if (num_step) *num_step = g.steps;
+    return rc;
+}
+
+int batch_interval(Batch* b, const vb2_model* models, int num_model, const vb2_estimate* est, vb2_interval* out, int32_t* status,
+                   int64_t* num_step, const char* const* labels)
+{
+    std::vector<int32_t> kaf(b->num_sample, 0);
+    for (int s = 0; s < b->num_sample; ++s) {
+        if (!b->slot(s)) {
+            set_error("vb2_batch_interval: the batch has an empty slot");
+            return VB2_ERR_INVALID;
+        }
+        kaf[s] = b->slot(s)->L.known_af != nullptr;
+    }
+    // (scratch and staging before the first fiber runs: the fibers only park)
+    if (const int rc = b->ensure_deriv_resources()) return rc;
+    const BatchDerivsFn fn = [b](int32_t, const int32_t* np, const double* p1, const double* p2, const double* a, double* llk,
+                                 double* grad, double* hess) { return b->derivs(np, p1, p2, a, llk, grad, hess); };
+    return intervals_lockstep(b->num_sample, b->num_pc, kaf.data(), models, num_model, est, fn, out, status, num_step, labels);
 }
 
 // <prefix>.CI: the rows of vb2_interval, numbers in the default ostream format (as .Ancestry), NA where there is none

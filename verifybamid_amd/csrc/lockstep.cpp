@@ -57,10 +57,27 @@ int FiberGang::eval_cb(void* user, int32_t n, const double* p1, const double* p2
         r.p2 = p2 + (size_t)done * k;
         r.a = a + done;
         r.out = o + done;
+        r.grad = r.hess = nullptr;
         swapcontext(&g->fibers_[cb->index].ctx, &g->main_);      // parked until the step has been evaluated
         if (g->error_) return g->error_;
     }
     return 0;
+}
+
+int FiberGang::derivs_cb(void* user, const double* p1, const double* p2, double a, double* llk, double* grad, double* hess)
+{
+    Cb* cb = static_cast<Cb*>(user);
+    FiberGang* g = cb->gang;
+    Request& r = g->req_[cb->index];
+    r.n = 1;
+    r.p1 = p1;
+    r.p2 = p2;
+    r.a = &a;
+    r.out = llk;
+    r.grad = grad;
+    r.hess = hess;
+    swapcontext(&g->fibers_[cb->index].ctx, &g->main_);          // parked until the step has been evaluated
+    return g->error_;
 }
 
 int FiberGang::prepare(int i)

@@ -33,6 +33,9 @@ public:
         int n = 0;
         const double *p1 = nullptr, *p2 = nullptr, *a = nullptr;
         double* out = nullptr;
+        // a derivative request (derivs_cb; n = 1) also wants the gradient [2k+1] and the Hessian [2k+1][2k+1] of its point;
+        // null for the searches' requests, whose steps never look at them
+        double *grad = nullptr, *hess = nullptr;
     };
     // evaluates every request with n > 0 (writes req[i].out[0..n)); non-zero = error for all
     typedef std::function<int(std::vector<Request>& req)> StepFn;
@@ -42,6 +45,8 @@ public:
     // the evaluator to hand to run i's Estimator (vb2_eval_fn signature) and its user pointer
     static int eval_cb(void* user, int32_t n, const double* p1, const double* p2, const double* a, double* o);
     void* user(int i) { return &cb_[i]; }
+    // the same for code that asks for ONE point's LLK, gradient and Hessian (the interval's Profiler, interval.cpp)
+    static int derivs_cb(void* user, const double* p1, const double* p2, double a, double* llk, double* grad, double* hess);
     // body(i) runs as fiber i; it must not let an exception escape
     int run(int num_pc, const std::function<void(int)>& body, const StepFn& step);
     int64_t steps = 0;

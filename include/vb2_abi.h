@@ -525,6 +525,84 @@ int vb2_cohort_run_sources(const vb2_cohort_args *args, int32_t top, vb2_run_res
 int vb2_cohort_run_intervals(const vb2_cohort_args *args, int32_t source_top, vb2_run_result *out /* [num_sample] */,
                              int32_t *status /* [num_sample] */, vb2_interval *ci);
 
+/* ------------------------------------------------------------------------- *
+ * 3c. Weighted-marker replicates (--PerChromosome, --Bootstrap).  Not in the reference: its model
+ *     with integer marker weights,  LLK_w(theta) = sum_i w_i log L_i(theta)  (L_i as in h:285-311; a marker counts where
+ *     L_i > 0, h:310), for many weight vectors ("replicates") over the ONE resident copy of a sample.  LLK_w is what
+ *     ComputeMixLLKs returns on the input with marker i repeated w_i times (depth statistics unchanged).
+ * ------------------------------------------------------------------------- */
+typedef struct vb2_replicates vb2_replicates;
+
+/* weight: [num_rep][num_marker] counts 0..255 in panel order (num_marker = the context's).  The rows are uploaded once and
+ * permuted on the device into the context's marker order; device memory comes from the library's slab cache.  The context
+ * must outlive the set and must not be inside vb2_ctx_search_begin / vb2_ctx_search_end when the set is used. */
+int vb2_replicates_create(vb2_ctx *ctx, int32_t num_rep, const uint8_t *weight, vb2_replicates **out);
+void vb2_replicates_destroy(vb2_replicates *rep);
+/* One step: replicate r evaluates num_point[r] (0..VB2_BATCH_SLOTS) points under its weights; the rows of all replicates
+ * are concatenated in replicate order -- pc1 / pc2 [sum][num_pc], alpha [sum] -> llk_out [sum] -- as in vb2_batch_derivs.
+ * A point's value is the same bits whatever else the step holds and from call to call; a replicate whose weights select no
+ * counted marker evaluates to 0.0; an alpha outside [0, 1] leaves every marker out, as in vb2_llk_eval_batch. */
+int vb2_replicates_eval(vb2_replicates *rep, const int32_t *num_point, const double *pc1, const double *pc2,
+                        const double *alpha, double *llk_out);
+/* OptimizeLLK for every replicate under `model` (the reference-exact simplex from the reference's start), all advancing in
+ * lock-step, each step one vb2_replicates_eval.  status[r]: VB2_OK, or VB2_ERR_INVALID for a replicate with no counted
+ * marker (the others finish); the return value: an error that concerns all. */
+int vb2_replicates_optimize_llk(vb2_replicates *rep, const vb2_model *model, vb2_estimate *est_out /* [num_rep] */,
+                                int32_t *status /* [num_rep] */);
+typedef struct vb2_replicates_info {
+    int32_t num_rep;
+    int32_t num_marker;
+    int64_t device_bytes;      /* device memory the set holds beyond the context's                   */
+    int64_t num_step;          /* vb2_replicates_eval calls so far (the searches' steps included)     */
+    int64_t num_launch;        /* marker-kernel launches of those steps                               */
+} vb2_replicates_info;
+int vb2_replicates_info_get(const vb2_replicates *rep, vb2_replicates_info *info, int64_t *counted /* [num_rep] or NULL */);
+/* The same driver over a caller's evaluator (the seam vb2_optimize_llk is for one search): no device needed.  A step calls
+ * fn once, on the calling thread's own stack; num_point[r] = 0 for a replicate that has finished.  A replicate whose first
+ * evaluation is exactly 0.0 at every point has no counted marker.  Non-zero from fn ends every search and is returned. */
+typedef int (*vb2_replicates_eval_fn)(void *user, int32_t num_rep, const int32_t *num_point, const double *pc1,
+                                      const double *pc2, const double *alpha, double *llk);
+int vb2_replicates_lockstep(vb2_replicates_eval_fn fn, void *user, int32_t num_rep, int32_t num_pc, const vb2_model *model,
+                            vb2_estimate *est_out, int32_t *status);
+
+/* Host-only helpers.
+ * vb2_chromosome_weights: the blocks of a panel's .bed are its chromosomes in order of first appearance.  *num_block: their
+ * number; block_of [num_marker]: the block of each of the first num_marker rows; block_size [max_block]: DISTINCT positions
+ * of the block among those rows (a position listed twice is one); names [max_block][VB2_CHROM_NAME_LEN]; only / without
+ * [num_block][num_marker]: the 0/1 indicator of the block's rows and its complement.  Any output may be NULL; more than
+ * max_block blocks with a non-NULL per-block output, or fewer rows than num_marker, is VB2_ERR_INVALID (*num_block is set). */
+#define VB2_CHROM_NAME_LEN 32
+int vb2_chromosome_weights(const char *bed_path, int32_t num_marker, int32_t max_block, int32_t *num_block, int32_t *block_of,
+                           int32_t *block_size, char *names, uint8_t *only, uint8_t *without);
+/* out [num_rep][num_marker]: replicate r counts num_marker uniform draws of a marker index,
+ * index = floor(x * num_marker / 2^64) for the 64-bit outputs x of splitmix64 started at
+ * ((uint64_t)seed << 32) ^ (0x5851f42d4c957f2d * (r + 1)) -- the stream of the multi-start searches; counts saturate at 255. */
+int vb2_bootstrap_weights(int32_t num_marker, int32_t num_rep, uint32_t seed, uint8_t *out);
+/* Delete-m_j jackknife (Busing, Meijer and van der Leeden 1999): block j has m[j] counted markers and the estimate
+ * theta_without[j] with it left out; n = sum m_j over the g blocks with m_j > 0 (the others are skipped), h_j = n / m_j,
+ *   estimate = g theta_hat - sum_j (1 - m_j / n) theta_without[j],  tau_j = h_j theta_hat - (h_j - 1) theta_without[j],
+ *   se^2 = (1 / g) sum_j (tau_j - estimate)^2 / (h_j - 1).   Fewer than two blocks with markers: VB2_ERR_INVALID. */
+int vb2_jackknife(int32_t num_block, const int64_t *m, double theta_hat, const double *theta_without, double *estimate,
+                  double *se);
+
+/* vb2_run, then on the same context: per_chromosome != 0 -- every chromosome of the .bed alone and left out, refitted under
+ * the run's model, <output_prefix>.Chrom (tab-separated: #CHROM MARKERS FREEMIX_ONLY FREELK1_ONLY FREELK0_ONLY
+ * FREEMIX_WITHOUT DELTA, NA for a chromosome without counted markers, then "#JACKKNIFE FREEMIX <est> SE <se> LO <lo> HI
+ * <hi>", the bounds FREEMIX -+ 1.96 se clipped to [0, 0.5]); bootstrap = N in 1..1000 -- N marker resamples seeded by
+ * args->search.seed, <output_prefix>.Boot (#REPLICATE FREEMIX FREELK1, then "#BOOTSTRAP MEAN .. SD .. P2.5 .. P97.5 ..",
+ * percentile q = the sorted value of index floor(q (N - 1) + 0.5)).  All searches form ONE replicate set.  stdout, .selfSM
+ * and .Ancestry are what vb2_run writes.  One device only (VB2_ERR_INVALID otherwise, before any file is read). */
+typedef struct vb2_replicate_summary {
+    int32_t num_chrom;         /* rows of .Chrom (0: not asked for)                                  */
+    int32_t num_boot;          /* bootstrap replicates that finished                                 */
+    double jack_estimate, jack_se, jack_lo, jack_hi;
+    double boot_mean, boot_sd, boot_p025, boot_p975;
+    int64_t num_step;          /* lock-step steps of the replicate set                               */
+    double seconds;            /* wall-clock of the replicate stage                                  */
+} vb2_replicate_summary;
+int vb2_run_replicates(const vb2_run_args *args, int32_t per_chromosome, int32_t bootstrap, vb2_run_result *out,
+                       vb2_replicate_summary *summary /* or NULL */);
+
 /* Host-side flattening only (no device): reads panel + pileup, resolves markers
  * and returns the arrays of vb2_input in library-owned memory; free with
  * vb2_flat_free.  Lets callers (tests, shard planners) inspect or slice them. */

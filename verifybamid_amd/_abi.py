@@ -162,6 +162,25 @@ BATCH_DERIVS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int3
                               C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                               C.POINTER(C.c_double))
 
+# vb2_replicates_eval_fn: (user, num_rep, num_point, pc1, pc2, alpha, llk)
+REPLICATES_EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                 C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double))
+VB2_BATCH_SLOTS = 8
+VB2_CHROM_NAME_LEN = 32
+
+
+class ReplicatesInfo(C.Structure):
+    _fields_ = [("num_rep", C.c_int32), ("num_marker", C.c_int32), ("device_bytes", C.c_int64), ("num_step", C.c_int64),
+                ("num_launch", C.c_int64)]
+
+
+class ReplicateSummary(C.Structure):
+    _fields_ = [("num_chrom", C.c_int32), ("num_boot", C.c_int32)] + \
+               [(n, C.c_double) for n in ("jack_estimate", "jack_se", "jack_lo", "jack_hi", "boot_mean", "boot_sd",
+                                          "boot_p025", "boot_p975")] + \
+               [("num_step", C.c_int64), ("seconds", C.c_double)]
+
+
 # every symbol include/vb2_abi.h declares
 SYMBOLS = [
     "vb2_ctx_create", "vb2_ctx_destroy", "vb2_ctx_info", "vb2_llk_eval_batch", "vb2_llk_derivs_batch", "vb2_ctx_interval", "vb2_run_interval",
@@ -176,6 +195,9 @@ SYMBOLS = [
     "vb2_ctx_marginals", "vb2_source_set_create", "vb2_source_set_add", "vb2_source_set_scores",
     "vb2_source_set_destroy", "vb2_source_set_size", "vb2_cohort_run_sources",
     "vb2_batch_derivs", "vb2_batch_interval", "vb2_intervals_lockstep", "vb2_cohort_run_intervals",
+    "vb2_replicates_create", "vb2_replicates_destroy", "vb2_replicates_eval", "vb2_replicates_optimize_llk",
+    "vb2_replicates_info_get", "vb2_replicates_lockstep", "vb2_chromosome_weights", "vb2_bootstrap_weights", "vb2_jackknife",
+    "vb2_run_replicates",
 ]
 
 _lib = None
@@ -274,6 +296,19 @@ def lib():
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     L.vb2_cohort_run_intervals.argtypes = [C.POINTER(CohortArgs), C.c_int32, C.POINTER(RunResult), C.POINTER(C.c_int32),
                                            C.POINTER(Interval)]
+    L.vb2_replicates_create.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]
+    L.vb2_replicates_destroy.argtypes = [C.c_void_p]
+    L.vb2_replicates_destroy.restype = None
+    L.vb2_replicates_eval.argtypes = [C.c_void_p] * 6
+    L.vb2_replicates_optimize_llk.argtypes = [C.c_void_p, C.POINTER(Model), C.POINTER(Estimate), C.POINTER(C.c_int32)]
+    L.vb2_replicates_info_get.argtypes = [C.c_void_p, C.POINTER(ReplicatesInfo), C.c_void_p]
+    L.vb2_replicates_lockstep.argtypes = [REPLICATES_EVAL_FN, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Model),
+                                          C.POINTER(Estimate), C.POINTER(C.c_int32)]
+    L.vb2_chromosome_weights.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)] + [C.c_void_p] * 5
+    L.vb2_bootstrap_weights.argtypes = [C.c_int32, C.c_int32, C.c_uint32, C.c_void_p]
+    L.vb2_jackknife.argtypes = [C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.vb2_run_replicates.argtypes = [C.POINTER(RunArgs), C.c_int32, C.c_int32, C.POINTER(RunResult),
+                                     C.POINTER(ReplicateSummary)]
     L.vb2_debug_set_tunable.argtypes = [C.c_char_p, C.c_int]
     L.vb2_debug_get_tunable.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
     _lib = L

@@ -530,6 +530,143 @@ def intervals_with_evaluator(evaluate, num_pc, estimates, known_af=None, **model
     return [dict(_interval_dict(ci[s]), status=int(status[s])) for s in range(S)], int(steps.value)
 
 
+class Replicates:
+    """vb2_replicates: many integer weight vectors ("replicates") over the ONE resident copy of a sample -- the
+    log-likelihood under marker weights, LLK_w = sum_i w_i log L_i, evaluated for all of them together and searched in
+    lock-step.  weights: [R, M] counts 0..255 in panel order (chromosome_weights, bootstrap_weights, or the caller's)."""
+    SLOTS = _abi.VB2_BATCH_SLOTS
+
+    def __init__(self, ctx: LikelihoodContext, weights):
+        self._lib = _abi.lib()
+        self.ctx = ctx
+        self.num_pc = ctx.num_pc
+        w = np.ascontiguousarray(np.atleast_2d(np.asarray(weights)))
+        if w.shape[1] != ctx.data.num_marker:
+            raise ValueError("weights must be [replicates, %d markers]" % ctx.data.num_marker)
+        if w.min() < 0 or w.max() > 255:
+            raise ValueError("weights are counts 0..255")
+        w = np.ascontiguousarray(w, dtype=np.uint8)
+        self.num_rep = int(w.shape[0])
+        h = C.c_void_p()
+        _abi.check(self._lib.vb2_replicates_create(ctx._h, self.num_rep, _p(w), C.byref(h)), "vb2_replicates_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.vb2_replicates_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def info(self):
+        i = _abi.ReplicatesInfo()
+        counted = np.zeros(self.num_rep, dtype=np.int64)
+        _abi.check(self._lib.vb2_replicates_info_get(self._h, C.byref(i), _p(counted)), "vb2_replicates_info_get")
+        return dict(num_rep=i.num_rep, num_marker=i.num_marker, device_bytes=int(i.device_bytes), num_step=int(i.num_step),
+                    num_launch=int(i.num_launch), counted=counted)
+
+    def eval(self, num_point, pc1, pc2, alpha):
+        """One step (vb2_replicates_eval): num_point [R] ints 0..8; pc1 / pc2 [P, k] and alpha [P] with P = sum(num_point),
+        the replicates' rows one after the other.  Returns llk [P]."""
+        k = self.num_pc
+        npt = np.ascontiguousarray(num_point, dtype=np.int32).reshape(self.num_rep)
+        P = int(npt.sum())
+        pc1 = np.ascontiguousarray(np.asarray(pc1, dtype=np.float64).reshape(P, k))
+        pc2 = np.ascontiguousarray(np.asarray(pc2, dtype=np.float64).reshape(P, k))
+        alpha = np.ascontiguousarray(np.asarray(alpha, dtype=np.float64).reshape(P))
+        out = np.zeros(P)
+        _abi.check(self._lib.vb2_replicates_eval(self._h, _p(npt), _p(pc1), _p(pc2), _p(alpha), _p(out)), "vb2_replicates_eval")
+        return out
+
+    def optimize(self, **model_kw):
+        """OptimizeLLK of every replicate in lock-step (vb2_replicates_optimize_llk): one dict per replicate with its own
+        "status" (VB2_ERR_INVALID: the replicate's weights select no counted marker)."""
+        m, keep = _model(known_af=self.ctx.data.known_af is not None, **model_kw)
+        est = (_abi.Estimate * self.num_rep)()
+        status = (C.c_int32 * self.num_rep)()
+        _abi.check(self._lib.vb2_replicates_optimize_llk(self._h, C.byref(m), est, status), "vb2_replicates_optimize_llk")
+        del keep
+        return [dict(_estimate_dict(est[r], self.num_pc), status=int(status[r])) for r in range(self.num_rep)]
+
+
+def replicates_with_evaluator(evaluate, num_rep, num_pc, known_af=False, **model_kw):
+    """The replicates' lock-step driver over a Python evaluator (vb2_replicates_lockstep): no device.
+    evaluate(num_point [R] int32, pc1 [P, k], pc2 [P, k], alpha [P]) -> llk [P], P = sum(num_point), called once per step
+    with the points of every replicate still searching.  Returns one dict per replicate (with "status")."""
+    L = _abi.lib()
+    k, R = int(num_pc), int(num_rep)
+    err = []
+
+    def cb(_user, nr, npt, p1, p2, a, out):
+        try:
+            num_point = np.ctypeslib.as_array(npt, (nr,)).copy()
+            P = int(num_point.sum())
+            res = evaluate(num_point, np.ctypeslib.as_array(p1, (P, k)).copy(), np.ctypeslib.as_array(p2, (P, k)).copy(),
+                           np.ctypeslib.as_array(a, (P,)).copy())
+            np.ctypeslib.as_array(out, (P,))[:] = np.asarray(res, dtype=np.float64).reshape(P)
+            return 0
+        except Exception as exc:   # never let an exception cross the C boundary
+            err.append(exc)
+            return _abi.VB2_ERR_INVALID
+    fn = _abi.REPLICATES_EVAL_FN(cb)
+    m, keep = _model(known_af=known_af, **model_kw)
+    est = (_abi.Estimate * R)()
+    status = (C.c_int32 * R)()
+    rc = L.vb2_replicates_lockstep(fn, None, R, k, C.byref(m), est, status)
+    del keep
+    if err:
+        raise err[0]
+    _abi.check(rc, "vb2_replicates_lockstep")
+    return [dict(_estimate_dict(est[r], k), status=int(status[r])) for r in range(R)]
+
+
+def chromosome_weights(bed_path, num_marker=None):
+    """The chromosomes of a panel's .bed as blocks, in order of first appearance (vb2_chromosome_weights): a dict with
+    names, block_of [M], block_size (distinct positions per block) and the weight rows only / without [C, M] uint8.
+    num_marker: the panel's markers (rows of .UD); None = every row of the .bed."""
+    L = _abi.lib()
+    if num_marker is None:
+        with open(bed_path, "rb") as f:
+            num_marker = sum(1 for line in f if line.strip())
+    M = int(num_marker)
+    nb = C.c_int32(0)
+    path = str(bed_path).encode()
+    _abi.check(L.vb2_chromosome_weights(path, M, 0, C.byref(nb), None, None, None, None, None), "vb2_chromosome_weights")
+    B = nb.value
+    block_of, size = np.zeros(M, dtype=np.int32), np.zeros(B, dtype=np.int32)
+    names = C.create_string_buffer(B * _abi.VB2_CHROM_NAME_LEN)
+    only, without = np.zeros((B, M), dtype=np.uint8), np.zeros((B, M), dtype=np.uint8)
+    _abi.check(L.vb2_chromosome_weights(path, M, B, C.byref(nb), _p(block_of), _p(size), C.cast(names, C.c_void_p), _p(only),
+                                        _p(without)), "vb2_chromosome_weights")
+    n = _abi.VB2_CHROM_NAME_LEN
+    return dict(names=[names.raw[j * n:(j + 1) * n].split(b"\0")[0].decode() for j in range(B)], block_of=block_of,
+                block_size=size, only=only, without=without)
+
+
+def bootstrap_weights(num_marker, num_rep, seed):
+    """[num_rep, num_marker] uint8 multinomial counts of num_marker uniform draws per replicate (vb2_bootstrap_weights)."""
+    out = np.zeros((int(num_rep), int(num_marker)), dtype=np.uint8)
+    _abi.check(_abi.lib().vb2_bootstrap_weights(int(num_marker), int(num_rep), int(seed), _p(out)), "vb2_bootstrap_weights")
+    return out
+
+
+def jackknife(m, theta_hat, theta_without):
+    """Delete-m_j jackknife (vb2_jackknife): block sizes m, the whole-sample estimate and the estimates with each block left
+    out -> (estimate, standard error).  Blocks with m = 0 are skipped."""
+    m = np.ascontiguousarray(m, dtype=np.int64)
+    tw = np.ascontiguousarray(theta_without, dtype=np.float64)
+    assert m.shape == tw.shape and m.ndim == 1
+    est, se = C.c_double(0), C.c_double(0)
+    _abi.check(_abi.lib().vb2_jackknife(len(m), _p(m), float(theta_hat), _p(tw), C.byref(est), C.byref(se)), "vb2_jackknife")
+    return est.value, se.value
+
+
 class ShardGroup:
     """vb2_shard_group: ONE sample's markers sharded over several GPUs, partial LLKs met in one
     RCCL all-reduce per batch (BASELINE.json configs[3]).
@@ -665,21 +802,32 @@ def optimize_with_evaluator(evaluate, num_pc, trace_capacity=0, known_af=False, 
 
 
 def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_sanity=False,
-              known_af_path=None, device=-1, output_pileup=False, devices=None, confidence_interval=False, **model_kw):
+              known_af_path=None, device=-1, output_pileup=False, devices=None, confidence_interval=False,
+              per_chromosome=False, bootstrap=0, **model_kw):
     """The --SVDPrefix/--PileupFile flow of execute() (vb2_run); devices=[a, b, ...] shards the
     sample's markers over those GPUs.  confidence_interval: vb2_run_interval (<output_prefix>.CI, and an
-    `interval` entry in the result)."""
+    `interval` entry in the result).  per_chromosome / bootstrap=N (seeded by seed=): vb2_run_replicates
+    (<output_prefix>.Chrom / .Boot, and a `replicates` entry with the jackknife and bootstrap summaries)."""
     args, keep = _run_args(svd_prefix, pileup_path, num_pc, disable_sanity, known_af_path,
                            output_prefix, device, output_pileup, devices=devices, **model_kw)
     res = _abi.RunResult()
     ci = _abi.Interval() if confidence_interval else None
-    if ci is not None:
+    summary = None
+    if per_chromosome or bootstrap:
+        if confidence_interval:
+            raise ValueError("per_chromosome / bootstrap cannot be combined with confidence_interval")
+        summary = _abi.ReplicateSummary()
+        _abi.check(_abi.lib().vb2_run_replicates(C.byref(args), int(bool(per_chromosome)), int(bootstrap), C.byref(res),
+                                                 C.byref(summary)), "vb2_run_replicates")
+    elif ci is not None:
         _abi.check(_abi.lib().vb2_run_interval(C.byref(args), C.byref(res), C.byref(ci)), "vb2_run_interval")
     else:
         _abi.check(_abi.lib().vb2_run(C.byref(args), C.byref(res)), "vb2_run")
     out = _estimate_dict(res.est, num_pc)
     if ci is not None:
         out["interval"] = _interval_dict(ci)
+    if summary is not None:
+        out["replicates"] = {name: getattr(summary, name) for name, _ in _abi.ReplicateSummary._fields_}
     out.update(num_marker=res.num_marker, num_site=res.num_site, num_bases=int(res.num_bases),
                avg_depth=res.avg_depth, sd_depth=res.sd_depth, seconds_load=res.seconds_load,
                seconds_optimize=res.seconds_optimize)

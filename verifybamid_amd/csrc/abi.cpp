@@ -25,6 +25,7 @@
 #include "lockstep.h"
 #include "hostio.h"
 #include "shard.h"
+#include "replicates.h"
 
 using vb2::set_error;
 
@@ -822,8 +823,8 @@ int vb2_ctx_interval(vb2_ctx* ctx, const vb2_model* model, const vb2_estimate* e
 
 namespace {
 
-// vb2_run, and with ci != nullptr vb2_run_interval
-int run_impl(const vb2_run_args* a, vb2_run_result* out, vb2_interval* ci)
+// vb2_run, and with ci != nullptr vb2_run_interval; hook (may be null): a stage on the run's context after the search
+int run_impl(const vb2_run_args* a, vb2_run_result* out, vb2_interval* ci, const vb2::RunHook* hook)
 {
     if (!a || !out) {
         set_error("vb2_run: invalid argument");
@@ -915,6 +916,7 @@ int run_impl(const vb2_run_args* a, vb2_run_result* out, vb2_interval* ci)
                 std::fprintf(stderr, "NOTICE - Finished phase: Confidence interval  [%.3f seconds, %lld derivative launches]\n",
                              now_s() - t2, (long long)ci->num_launch);
         }
+        if (!rc && hook) rc = (*hook)(ctx, *flat, model, out->est);
         vb2_ctx_destroy(ctx);
         if (rc) return rc;
     }
@@ -932,9 +934,13 @@ int run_impl(const vb2_run_args* a, vb2_run_result* out, vb2_interval* ci)
 
 }  // namespace
 
+namespace vb2 {
+int run_with_hook(const vb2_run_args* args, vb2_run_result* out, const RunHook& hook) { return run_impl(args, out, nullptr, &hook); }
+}  // namespace vb2
+
 extern "C" {
 
-int vb2_run(const vb2_run_args* a, vb2_run_result* out) { return run_impl(a, out, nullptr); }
+int vb2_run(const vb2_run_args* a, vb2_run_result* out) { return run_impl(a, out, nullptr, nullptr); }
 
 int vb2_run_interval(const vb2_run_args* a, vb2_run_result* out, vb2_interval* ci)
 {
@@ -942,7 +948,7 @@ int vb2_run_interval(const vb2_run_args* a, vb2_run_result* out, vb2_interval* c
         set_error("vb2_run_interval: invalid argument");
         return VB2_ERR_INVALID;
     }
-    return run_impl(a, out, ci);
+    return run_impl(a, out, ci, nullptr);
 }
 
 }  // extern "C"

@@ -19,6 +19,9 @@
 // --ConfidenceInterval writes <Output>.CI for the sample of a --PileupFile / --BamFile run; --PileupList F --CohortInterval
 // writes <output prefix>.CI for every sample of the cohort, the intervals computed in lock-step next to the search (one
 // device; may be combined with --FindSource).
+// --PerChromosome writes <Output>.Chrom -- FREEMIX refitted on every chromosome of the .bed alone and with it left out, and a
+// delete-one-chromosome jackknife --, --Bootstrap N (1..1000, seeded by --Seed) <Output>.Boot: weighted-marker replicates of
+// the one resident sample searched in lock-step (vb2_run_replicates; one sample, one device).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -92,6 +95,8 @@ int main(int argc, char** argv)
     bool cohortInterval = false;
     bool findSource = false;
     int sourceTop = 3;
+    bool perChromosome = false;
+    int bootstrap = 0;
     // "Pileup Options" (main.cpp:176-187), defaults main.cpp:81-96 (MPLP_REALN | MPLP_SMART_OVERLAPS; UNMAP | SECONDARY |
     // QCFAIL | DUP): they shape what --BamFile input becomes and, as in the reference, do nothing to --PileupFile input
     int minBQ = 13, minMQ = 2, adjustMQ = 40, maxDepth = 8000, inclFlags = (1 << 4) | (1 << 10), exclFlags = 0x4 | 0x100 | 0x200 | 0x400;
@@ -150,6 +155,11 @@ int main(int argc, char** argv)
         // pair's log-likelihood ratio (vb2_cohort_run_sources); the --SourceTop best candidates per sample go to <Output>.Sources
         {"FindSource", {Flag::kBool, &findSource, false}},
         {"SourceTop", {Flag::kInt, &sourceTop, false}},
+        // not in the reference: FREEMIX refitted on every chromosome alone and with every chromosome left out, with a
+        // delete-one-chromosome jackknife (<Output>.Chrom), and over --Bootstrap N marker resamples seeded by --Seed
+        // (<Output>.Boot): weighted-marker replicates of the one resident sample, searched in lock-step (vb2_run_replicates)
+        {"PerChromosome", {Flag::kBool, &perChromosome, false}},
+        {"Bootstrap", {Flag::kInt, &bootstrap, false}},
     };
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
@@ -201,6 +211,19 @@ int main(int argc, char** argv)
         if (Devices != "Empty" && Devices.find(',') != std::string::npos)
             fatal("--FindSource cannot be combined with more than one --Devices: a source set lives on one device");
         if (sourceTop < 1) fatal("--SourceTop takes a positive number of candidates");
+    }
+    if (perChromosome || flags["Bootstrap"].seen) {                     // single-sample, single-device runs only
+        const char* which = perChromosome ? "--PerChromosome" : "--Bootstrap";
+        if (PileupList != "Empty") {
+            const std::string m = std::string(which) + " cannot be combined with --PileupList: replicates are refitted for one sample per run";
+            fatal(m.c_str());
+        }
+        if (Devices != "Empty" && Devices.find(',') != std::string::npos) {
+            const std::string m = std::string(which) + " cannot be combined with more than one --Devices: replicates read one resident sample on one device";
+            fatal(m.c_str());
+        }
+        if (flags["Bootstrap"].seen && (bootstrap < 1 || bootstrap > 1000)) fatal("--Bootstrap takes 1 to 1000 replicates");
+        if (confidenceInterval) fatal("--PerChromosome / --Bootstrap cannot be combined with --ConfidenceInterval: run them separately");
     }
     // --Seed: parsed and never used by the reference (main.cpp:137,286); here it seeds --NumStart's starting points
     // --NumThread: the likelihood runs on the GPU; the VCF parser pool of --RefVCF and the reader threads of --PileupList use it
@@ -361,7 +384,9 @@ int main(int argc, char** argv)
 
     vb2_run_result res;
     vb2_interval ci;
-    const int rc = confidenceInterval ? vb2_run_interval(&args, &res, &ci) : vb2_run(&args, &res);
+    const int rc = (perChromosome || bootstrap > 0) ? vb2_run_replicates(&args, perChromosome ? 1 : 0, bootstrap, &res, nullptr)
+                   : confidenceInterval             ? vb2_run_interval(&args, &res, &ci)
+                                                    : vb2_run(&args, &res);
     if (rc != VB2_OK) {
         if (rc == VB2_ERR_SANITY) std::fprintf(stderr, "WARNING - %s\n", vb2_last_error());
         else std::fprintf(stderr, "\nFATAL ERROR - \n%s\n\n", vb2_last_error());

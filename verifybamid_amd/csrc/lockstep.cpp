@@ -174,7 +174,7 @@ int FiberGang::run(int num_pc, const std::function<void(int)>& body, const StepF
 int FiberGang::search(int i, const Search& cfg, const char* caller, vb2_estimate* out) noexcept
 {
     try {
-        Estimator est(num_pc_, eval_cb, user(i));
+        Estimator est(num_pc_, cfg.eval ? cfg.eval : eval_cb, cfg.eval ? cfg.eval_user : user(i));
         apply_model(est, *cfg.model, cfg.data_has_known_af);
         est.speculate = cfg.speculate;
         est.line_search = cfg.line_search;

@@ -76,6 +76,10 @@ public:
         int start_index = 0;
         uint32_t start_seed = 0;
         double start_sd = 0;                // <= 0: the Estimator's own
+        // what the Estimator calls for its values instead of eval_cb on user(i) (null: that); it must end up in eval_cb on
+        // user(i) itself -- a wrapper that looks at the values on their way (replicates.cpp)
+        vb2_eval_fn eval = nullptr;
+        void* eval_user = nullptr;
     };
     // For body(i): that search on fiber i's evaluator.  Fills *out when the optimiser returned and gives its code, or
     // VB2_ERR_NOMEM / VB2_ERR_INVALID with the last error set (`caller` goes into the message for an unknown exception).

@@ -1,0 +1,684 @@
+// replicates.cpp -- host side of the weighted-marker replicates (weighted_kernels.hip): the replicate
+// set on a context, its lock-step searches, the host-only helpers (chromosome and bootstrap weights, the delete-m_j
+// jackknife) and the file flow behind --PerChromosome / --Bootstrap.
+#include "replicates.h"
+
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <memory>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "context.h"
+#include "hostio.h"
+#include "lockstep.h"
+#include "weighted_kernels.h"
+
+namespace vb2 {
+
+#define VB2_HIP_R(call)                                                                \
+    do {                                                                               \
+        hipError_t e_ = (call);                                                        \
+        if (e_ != hipSuccess) {                                                        \
+            set_error(std::string(#call) + " failed: " + hipGetErrorString(e_));       \
+            return VB2_ERR_HIP;                                                        \
+        }                                                                              \
+    } while (0)
+
+namespace {
+size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// a device slab from the cache, or a fresh one
+int take_device(size_t bytes, int device, void** p, size_t* got)
+{
+    *p = cached_device_slab(bytes, device, got);
+    if (!*p) {
+        VB2_HIP_R(hipMalloc(p, bytes));
+        *got = bytes;
+    }
+    return VB2_OK;
+}
+void give_device(void* p, size_t bytes, int device)
+{
+    if (p && !recycle_device_slab(p, bytes, device)) (void)hipFree(p);
+}
+}  // namespace
+
+int Replicates::create(Context* ctx, int num_rep, const uint8_t* weight, Replicates** out)
+{
+    *out = nullptr;
+    if (!ctx || num_rep < 1 || num_rep > 65535 || !weight) {
+        set_error("vb2_replicates_create: invalid argument (1..65535 replicates)");
+        return VB2_ERR_INVALID;
+    }
+    if (ctx->resident_active) {
+        set_error("vb2_replicates_create: not inside vb2_ctx_search_begin / vb2_ctx_search_end");
+        return VB2_ERR_INVALID;
+    }
+    std::unique_ptr<Replicates> r(new Replicates());
+    r->ctx = ctx;
+    r->num_rep = num_rep;
+    const DeviceLayout& L = ctx->L;
+    const size_t M = (size_t)ctx->num_marker, mp = (size_t)L.m_pad, na = (size_t)L.num_active;
+    // counted markers per replicate, on the host: the sorted positions' panel rows are h_active[h_perm[position]]
+    r->counted.assign(num_rep, 0);
+    if (na > 0 && ctx->h_perm.size() < na) {
+        set_error("vb2_replicates_create: the context holds no marker order");
+        return VB2_ERR_INVALID;
+    }
+    for (size_t pos = 0; pos < na; ++pos) {
+        const int64_t a = ctx->h_perm[pos];
+        if (a < 0 || (size_t)a >= ctx->h_active.size()) continue;
+        const size_t i = (size_t)ctx->h_active[(size_t)a];
+        if (i >= M) continue;
+        for (int q = 0; q < num_rep; ++q) r->counted[q] += weight[(size_t)q * M + i] != 0;
+    }
+    VB2_HIP_R(hipSetDevice(ctx->device));
+    if (const int rc = ctx->ensure_pidx()) return rc;
+    const int k = ctx->num_pc;
+    r->cap_ = num_rep * VB2_BATCH_SLOTS;
+    const size_t cap = (size_t)r->cap_;
+    // stage: rows [cap][2k+1] | weight-row indices [cap] | results [cap]; on the device also a launch's partial sums
+    r->o_row_ = up256(sizeof(double) * cap * (size_t)(2 * k + 1));
+    r->o_res_ = up256(r->o_row_ + sizeof(int32_t) * cap);
+    r->o_part_ = up256(r->o_res_ + sizeof(double) * cap);
+    const size_t part_bytes = sizeof(double) * (size_t)kMaxPointsPerLaunch * (size_t)std::max(1, weighted_tile_groups(L));
+    if (const int rc = take_device(std::max<size_t>(mp * (size_t)num_rep, 256), ctx->device, reinterpret_cast<void**>(&r->d_weights_),
+                                   &r->d_weights_bytes_))
+        return rc;
+    if (const int rc = take_device(r->o_part_ + part_bytes, ctx->device, &r->d_stage_, &r->d_stage_bytes_)) return rc;
+    r->h_stage_ = cached_pinned_slab(r->o_part_, ctx->device, &r->h_stage_bytes_);
+    if (!r->h_stage_) {
+        VB2_HIP_R(hipHostMalloc(&r->h_stage_, r->o_part_, hipHostMallocMapped));
+        r->h_stage_bytes_ = r->o_part_;
+    }
+    r->device_bytes = (int64_t)(r->d_weights_bytes_ + r->d_stage_bytes_);
+    // the panel-order rows go up once, into a slab that goes back to the cache when the permutation is done
+    void* d_panel = nullptr;
+    size_t d_panel_bytes = 0;
+    if (const int rc = take_device(std::max<size_t>(M * (size_t)num_rep, 256), ctx->device, &d_panel, &d_panel_bytes)) return rc;
+    hipError_t e = hipMemcpyAsync(d_panel, weight, M * (size_t)num_rep, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess)
+        e = launch_weights_permute(L, ctx->num_marker, num_rep, static_cast<const uint8_t*>(d_panel), ctx->d_pidx, r->d_weights_,
+                                   ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    give_device(d_panel, d_panel_bytes, ctx->device);
+    if (e != hipSuccess) {
+        set_error(std::string("vb2_replicates_create: weight upload failed: ") + hipGetErrorString(e));
+        return VB2_ERR_HIP;
+    }
+    *out = r.release();
+    return VB2_OK;
+}
+
+Replicates::~Replicates()
+{
+    if (!ctx) return;
+    (void)hipSetDevice(ctx->device);
+    give_device(d_weights_, d_weights_bytes_, ctx->device);
+    give_device(d_stage_, d_stage_bytes_, ctx->device);
+    if (h_stage_ && !recycle_pinned_slab(h_stage_, h_stage_bytes_, ctx->device)) (void)hipHostFree(h_stage_);
+}
+
+int Replicates::eval(const int32_t* num_point, const double* pc1, const double* pc2, const double* alpha, double* llk)
+{
+    if (!num_point) {
+        set_error("vb2_replicates_eval: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    size_t total = 0;
+    for (int r = 0; r < num_rep; ++r) {
+        if (num_point[r] < 0 || num_point[r] > VB2_BATCH_SLOTS) {
+            set_error("vb2_replicates_eval: a replicate's point count outside 0..VB2_BATCH_SLOTS");
+            return VB2_ERR_INVALID;
+        }
+        total += (size_t)num_point[r];
+    }
+    if (total == 0) return VB2_OK;
+    if (!pc1 || !pc2 || !alpha || !llk) {
+        set_error("vb2_replicates_eval: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    if (ctx->resident_active) {
+        set_error("vb2_replicates_eval: not inside vb2_ctx_search_begin / vb2_ctx_search_end");
+        return VB2_ERR_INVALID;
+    }
+    VB2_HIP_R(hipSetDevice(ctx->device));
+    const int k = ctx->num_pc, n = 2 * k + 1;
+    char* const hp = static_cast<char*>(h_stage_);
+    char* const dp = static_cast<char*>(d_stage_);
+    double* const h_rows = reinterpret_cast<double*>(hp);
+    int32_t* const h_row_of = reinterpret_cast<int32_t*>(hp + o_row_);
+    const double* const h_res = reinterpret_cast<const double*>(hp + o_res_);
+    size_t p = 0;
+    for (int r = 0; r < num_rep; ++r)
+        for (int b = 0; b < num_point[r]; ++b, ++p) {
+            double* row = h_rows + p * n;
+            std::memcpy(row, pc1 + p * k, sizeof(double) * k);
+            std::memcpy(row + k, pc2 + p * k, sizeof(double) * k);
+            row[2 * k] = alpha[p];
+            h_row_of[p] = r;
+        }
+    // one upload, a launch pair per kMaxPointsPerLaunch points on the stream (the partial sums are stream-ordered), one
+    // download, one synchronisation
+    hipStream_t s = ctx->stream;
+    VB2_HIP_R(hipMemcpyAsync(dp, hp, sizeof(double) * total * n, hipMemcpyHostToDevice, s));
+    VB2_HIP_R(hipMemcpyAsync(dp + o_row_, hp + o_row_, sizeof(int32_t) * total, hipMemcpyHostToDevice, s));
+    for (size_t done = 0; done < total; done += kMaxPointsPerLaunch) {
+        const int c = (int)std::min<size_t>(kMaxPointsPerLaunch, total - done);
+        VB2_HIP_R(launch_llk_weighted(ctx->L, c, reinterpret_cast<const double*>(dp) + done * n,
+                                      reinterpret_cast<const int32_t*>(dp + o_row_) + done, d_weights_,
+                                      reinterpret_cast<double*>(dp + o_part_), reinterpret_cast<double*>(dp + o_res_) + done, s));
+        ++num_launch;
+    }
+    VB2_HIP_R(hipMemcpyAsync(hp + o_res_, dp + o_res_, sizeof(double) * total, hipMemcpyDeviceToHost, s));
+    VB2_HIP_R(hipStreamSynchronize(s));
+    ++num_step;
+    std::memcpy(llk, h_res, sizeof(double) * total);
+    return VB2_OK;
+}
+
+namespace {
+// what a replicate's Estimator calls: the gang's evaluator, and a look at the first values it returns
+struct Probe {
+    void* gang_user = nullptr;
+    bool first = true, empty = false;
+};
+int probe_eval(void* user, int32_t n, const double* p1, const double* p2, const double* a, double* o)
+{
+    Probe* pr = static_cast<Probe*>(user);
+    if (const int rc = FiberGang::eval_cb(pr->gang_user, n, p1, p2, a, o)) return rc;
+    if (pr->first) {
+        pr->first = false;
+        bool all_zero = n > 0;
+        for (int i = 0; i < n; ++i) all_zero = all_zero && o[i] == 0.0;
+        if (all_zero) {
+            pr->empty = true;
+            return VB2_ERR_INVALID;
+        }
+    }
+    return 0;
+}
+}  // namespace
+
+int replicates_lockstep(vb2_replicates_eval_fn fn, void* user, int num_rep, int num_pc, bool data_has_known_af,
+                        const vb2_model& model, vb2_estimate* est, int32_t* status, int64_t* num_step)
+{
+    const int R = num_rep, k = num_pc;
+    FiberGang gang(R, VB2_BATCH_SLOTS);
+    std::vector<Probe> probes(R);
+    vb2_model quiet = model;                   // (the reference's phase lines belong to the run's own search)
+    quiet.notices = 0;
+    quiet.verbose = 0;
+    auto body = [&](int i) {
+        probes[i].gang_user = gang.user(i);
+        FiberGang::Search cfg;
+        cfg.model = &quiet;
+        cfg.data_has_known_af = data_has_known_af;
+        cfg.eval = probe_eval;
+        cfg.eval_user = &probes[i];
+        std::memset(&est[i], 0, sizeof(est[i]));
+        status[i] = gang.search(i, cfg, "vb2_replicates_optimize_llk", &est[i]);
+    };
+    std::vector<int32_t> npt(R);
+    std::vector<double> p1, p2, al, vals;
+    auto step = [&](std::vector<FiberGang::Request>& req) {
+        p1.clear(); p2.clear(); al.clear();
+        for (int r = 0; r < R; ++r) {
+            const FiberGang::Request& q = req[r];
+            npt[r] = q.n > 0 ? q.n : 0;
+            if (q.n <= 0) continue;
+            p1.insert(p1.end(), q.p1, q.p1 + (size_t)q.n * k);
+            p2.insert(p2.end(), q.p2, q.p2 + (size_t)q.n * k);
+            al.insert(al.end(), q.a, q.a + q.n);
+        }
+        vals.assign(al.size(), 0.0);
+        if (const int rc = fn(user, R, npt.data(), p1.data(), p2.data(), al.data(), vals.data())) return rc;
+        size_t o = 0;
+        for (int r = 0; r < R; ++r) {
+            if (req[r].n <= 0) continue;
+            std::memcpy(req[r].out, &vals[o], sizeof(double) * req[r].n);
+            o += (size_t)req[r].n;
+        }
+        return 0;
+    };
+    const int rc = gang.run(k, body, step);
+    if (num_step) *num_step = gang.steps;
+    if (rc) return rc;
+    for (int r = 0; r < R; ++r)
+        if (probes[r].empty) {
+            status[r] = VB2_ERR_INVALID;
+            set_error("vb2_replicates_optimize_llk: a replicate's weights select no counted marker");
+        }
+    return VB2_OK;
+}
+
+namespace {
+int replicates_eval_cb(void* user, int32_t, const int32_t* num_point, const double* pc1, const double* pc2, const double* alpha,
+                       double* llk)
+{
+    return static_cast<Replicates*>(user)->eval(num_point, pc1, pc2, alpha, llk);
+}
+}  // namespace
+
+int Replicates::optimize(const vb2_model& model, vb2_estimate* est, int32_t* status)
+{
+    if (!est || !status) {
+        set_error("vb2_replicates_optimize_llk: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    if (ctx->resident_active) {
+        set_error("vb2_replicates_optimize_llk: not inside vb2_ctx_search_begin / vb2_ctx_search_end");
+        return VB2_ERR_INVALID;
+    }
+    return replicates_lockstep(replicates_eval_cb, this, num_rep, ctx->num_pc, ctx->L.known_af != nullptr, model, est, status,
+                               nullptr);
+}
+
+// ---------------------------------------------------------------------------
+// host-only helpers
+// ---------------------------------------------------------------------------
+namespace {
+struct Blocks {
+    std::vector<std::string> names;
+    std::vector<int32_t> block_of;           // per row
+    std::vector<int32_t> size;               // distinct positions per block
+};
+
+// the chromosomes of a panel's rows in order of first appearance (rows beyond `rows` are not looked at)
+void blocks_of_panel(const Panel& p, size_t rows, Blocks* b)
+{
+    rows = std::min(rows, p.rowSlot.size());
+    std::vector<int32_t> block_of_chr(p.chrNames.size(), -1);
+    std::vector<char> seen(p.num_slot(), 0);
+    b->block_of.assign(rows, -1);
+    for (size_t i = 0; i < rows; ++i) {
+        const int32_t slot = p.rowSlot[i], chr = p.slotChr[slot];
+        if (block_of_chr[chr] < 0) {
+            block_of_chr[chr] = (int32_t)b->names.size();
+            b->names.push_back(p.chrNames[chr]);
+            b->size.push_back(0);
+        }
+        b->block_of[i] = block_of_chr[chr];
+        if (!seen[slot]) {
+            seen[slot] = 1;
+            ++b->size[block_of_chr[chr]];
+        }
+    }
+}
+
+double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+inline uint64_t splitmix64(uint64_t& s)
+{
+    uint64_t z = (s += 0x9e3779b97f4a7c15ull);
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
+double freemix_of(const vb2_estimate& e) { return e.alpha < 0.5 ? e.alpha : 1 - e.alpha; }
+}  // namespace
+
+}  // namespace vb2
+
+using vb2::set_error;
+
+extern "C" {
+
+int vb2_replicates_create(vb2_ctx* ctx, int32_t num_rep, const uint8_t* weight, vb2_replicates** out)
+{
+    if (!out) {
+        set_error("vb2_replicates_create: out is NULL");
+        return VB2_ERR_INVALID;
+    }
+    *out = nullptr;
+    if (!ctx || !ctx->impl) {
+        set_error("null vb2_ctx");
+        return VB2_ERR_INVALID;
+    }
+    try {
+        vb2::Replicates* r = nullptr;
+        if (const int rc = vb2::Replicates::create(ctx->impl, num_rep, weight, &r)) return rc;
+        *out = new vb2_replicates{r};
+        return VB2_OK;
+    } catch (const std::bad_alloc&) {
+        set_error("out of host memory");
+        return VB2_ERR_NOMEM;
+    } catch (const std::exception& e) {
+        set_error(e.what());
+        return VB2_ERR_INVALID;
+    }
+}
+
+void vb2_replicates_destroy(vb2_replicates* rep)
+{
+    if (!rep) return;
+    delete rep->impl;
+    delete rep;
+}
+
+int vb2_replicates_eval(vb2_replicates* rep, const int32_t* num_point, const double* pc1, const double* pc2, const double* alpha,
+                        double* llk_out)
+{
+    if (!rep || !rep->impl) {
+        set_error("null vb2_replicates");
+        return VB2_ERR_INVALID;
+    }
+    return rep->impl->eval(num_point, pc1, pc2, alpha, llk_out);
+}
+
+int vb2_replicates_optimize_llk(vb2_replicates* rep, const vb2_model* model, vb2_estimate* est_out, int32_t* status)
+{
+    if (!rep || !rep->impl || !model) {
+        set_error("vb2_replicates_optimize_llk: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    try {
+        return rep->impl->optimize(*model, est_out, status);
+    } catch (const std::bad_alloc&) {
+        set_error("out of host memory");
+        return VB2_ERR_NOMEM;
+    } catch (const std::exception& e) {
+        set_error(e.what());
+        return VB2_ERR_INVALID;
+    }
+}
+
+int vb2_replicates_info_get(const vb2_replicates* rep, vb2_replicates_info* info, int64_t* counted)
+{
+    if (!rep || !rep->impl || !info) return VB2_ERR_INVALID;
+    const vb2::Replicates& r = *rep->impl;
+    info->num_rep = r.num_rep;
+    info->num_marker = r.ctx->num_marker;
+    info->device_bytes = r.device_bytes;
+    info->num_step = r.num_step;
+    info->num_launch = r.num_launch;
+    if (counted) std::memcpy(counted, r.counted.data(), sizeof(int64_t) * (size_t)r.num_rep);
+    return VB2_OK;
+}
+
+int vb2_replicates_lockstep(vb2_replicates_eval_fn fn, void* user, int32_t num_rep, int32_t num_pc, const vb2_model* model,
+                            vb2_estimate* est_out, int32_t* status)
+{
+    if (!fn || !model || !est_out || !status || num_rep < 1 || num_pc < 1 || num_pc > VB2_MAX_PC) {
+        set_error("vb2_replicates_lockstep: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    try {
+        return vb2::replicates_lockstep(fn, user, num_rep, num_pc, false, *model, est_out, status, nullptr);
+    } catch (const std::bad_alloc&) {
+        set_error("out of host memory");
+        return VB2_ERR_NOMEM;
+    } catch (const std::exception& e) {
+        set_error(e.what());
+        return VB2_ERR_INVALID;
+    }
+}
+
+int vb2_chromosome_weights(const char* bed_path, int32_t num_marker, int32_t max_block, int32_t* num_block, int32_t* block_of,
+                           int32_t* block_size, char* names, uint8_t* only, uint8_t* without)
+{
+    if (!bed_path || num_marker < 1 || !num_block) {
+        set_error("vb2_chromosome_weights: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    try {
+        vb2::Panel panel;
+        if (const int rc = vb2::read_bed(bed_path, &panel)) return rc;
+        vb2::Blocks b;
+        vb2::blocks_of_panel(panel, (size_t)num_marker, &b);
+        const int32_t nb = (int32_t)b.names.size();
+        *num_block = nb;
+        if (b.block_of.size() < (size_t)num_marker) {
+            set_error("vb2_chromosome_weights: the .bed has fewer rows than num_marker");
+            return VB2_ERR_INVALID;
+        }
+        if ((block_size || names || only || without) && nb > max_block) {
+            set_error("vb2_chromosome_weights: more chromosomes than max_block");
+            return VB2_ERR_INVALID;
+        }
+        const size_t M = (size_t)num_marker;
+        if (block_of) std::memcpy(block_of, b.block_of.data(), sizeof(int32_t) * M);
+        for (int32_t j = 0; j < nb; ++j) {
+            if (block_size) block_size[j] = b.size[j];
+            if (names) {
+                char* dst = names + (size_t)j * VB2_CHROM_NAME_LEN;
+                std::memset(dst, 0, VB2_CHROM_NAME_LEN);
+                std::strncpy(dst, b.names[j].c_str(), VB2_CHROM_NAME_LEN - 1);
+            }
+            for (size_t i = 0; i < M && (only || without); ++i) {
+                const uint8_t in = b.block_of[i] == j ? 1 : 0;
+                if (only) only[(size_t)j * M + i] = in;
+                if (without) without[(size_t)j * M + i] = (uint8_t)(1 - in);
+            }
+        }
+        return VB2_OK;
+    } catch (const std::bad_alloc&) {
+        set_error("out of host memory");
+        return VB2_ERR_NOMEM;
+    } catch (const std::exception& e) {
+        set_error(e.what());
+        return VB2_ERR_INVALID;
+    }
+}
+
+int vb2_bootstrap_weights(int32_t num_marker, int32_t num_rep, uint32_t seed, uint8_t* out)
+{
+    if (num_marker < 1 || num_rep < 1 || !out) {
+        set_error("vb2_bootstrap_weights: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    const size_t M = (size_t)num_marker;
+    std::memset(out, 0, M * (size_t)num_rep);
+    for (int32_t r = 0; r < num_rep; ++r) {
+        uint64_t s = ((uint64_t)seed << 32) ^ (0x5851f42d4c957f2dull * (uint64_t)(r + 1));
+        uint8_t* row = out + (size_t)r * M;
+        for (size_t d = 0; d < M; ++d) {
+            const uint64_t x = vb2::splitmix64(s);
+            const size_t i = (size_t)(((unsigned __int128)x * (unsigned __int128)M) >> 64);
+            if (row[i] != 255) ++row[i];
+        }
+    }
+    return VB2_OK;
+}
+
+int vb2_jackknife(int32_t num_block, const int64_t* m, double theta_hat, const double* theta_without, double* estimate, double* se)
+{
+    if (num_block < 1 || !m || !theta_without || !estimate || !se) {
+        set_error("vb2_jackknife: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    double n = 0;
+    int g = 0;
+    for (int32_t j = 0; j < num_block; ++j)
+        if (m[j] > 0) {
+            n += (double)m[j];
+            ++g;
+        }
+    if (g < 2) {
+        set_error("vb2_jackknife: fewer than two blocks with counted markers");
+        return VB2_ERR_INVALID;
+    }
+    // the formulas of vb2_abi.h in the differences d_j = theta_hat - theta_without[j] (sum_j (1 - m_j / n) = g - 1):
+    //   estimate = theta_hat + S,  S = sum_j (1 - m_j / n) d_j;   tau_j - estimate = (h_j - 1) d_j - S
+    // -- the same numbers without the cancellation of g theta_hat against the sum: equal estimates give se = 0 exactly
+    double S = 0;
+    for (int32_t j = 0; j < num_block; ++j)
+        if (m[j] > 0) S += (1.0 - (double)m[j] / n) * (theta_hat - theta_without[j]);
+    const double est = theta_hat + S;
+    double var = 0;
+    for (int32_t j = 0; j < num_block; ++j) {
+        if (m[j] <= 0) continue;
+        const double h = n / (double)m[j];
+        const double dev = (h - 1.0) * (theta_hat - theta_without[j]) - S;
+        var += dev * dev / (h - 1.0);
+    }
+    *estimate = est;
+    *se = std::sqrt(var / (double)g);
+    return VB2_OK;
+}
+
+int vb2_run_replicates(const vb2_run_args* args, int32_t per_chromosome, int32_t bootstrap, vb2_run_result* out,
+                       vb2_replicate_summary* summary)
+{
+    if (!args || !out || bootstrap < 0 || bootstrap > 1000 || (!per_chromosome && bootstrap == 0)) {
+        set_error("vb2_run_replicates: invalid argument (--Bootstrap takes 1..1000 replicates)");
+        return VB2_ERR_INVALID;
+    }
+    if (args->devices && args->num_device > 1) {
+        set_error("--PerChromosome / --Bootstrap take one device: they cannot be combined with marker shards over several "
+                  "--Devices");
+        return VB2_ERR_INVALID;
+    }
+    vb2_replicate_summary sum;
+    std::memset(&sum, 0, sizeof(sum));
+    sum.jack_estimate = sum.jack_se = sum.jack_lo = sum.jack_hi = NAN;
+    sum.boot_mean = sum.boot_sd = sum.boot_p025 = sum.boot_p975 = NAN;
+    const vb2::RunHook hook = [&](vb2_ctx* ctx, const vb2_flat& flat, const vb2_model& model, const vb2_estimate& whole) -> int {
+        const double t0 = vb2::now_s();
+        vb2::Context* c = ctx->impl;
+        const size_t M = (size_t)c->num_marker;
+        vb2::Blocks b;
+        if (per_chromosome) vb2::blocks_of_panel(flat.panel, M, &b);
+        const int C = (int)b.names.size(), N = bootstrap, R = 2 * C + N;
+        if (R < 1) {
+            set_error("vb2_run_replicates: the panel names no chromosome");
+            return VB2_ERR_INVALID;
+        }
+        // rows: C "only", C "without", N bootstrap resamples
+        std::vector<uint8_t> w((size_t)R * M, 0);
+        for (size_t i = 0; i < M && C > 0; ++i) {
+            const int32_t j = i < b.block_of.size() ? b.block_of[i] : -1;
+            for (int q = 0; q < C; ++q) {
+                w[(size_t)q * M + i] = q == j ? 1 : 0;
+                w[(size_t)(C + q) * M + i] = q == j ? 0 : 1;
+            }
+        }
+        if (N > 0)
+            if (const int rc = vb2_bootstrap_weights((int32_t)M, N, args->search.seed, w.data() + (size_t)2 * C * M)) return rc;
+        const bool notices = model.notices != 0;
+        if (notices) std::fprintf(stderr, "NOTICE - Starting phase: Likelihood replicates (%d searches in lock-step)\n", R);
+        vb2::Replicates* rep = nullptr;
+        if (const int rc = vb2::Replicates::create(c, R, w.data(), &rep)) return rc;
+        std::unique_ptr<vb2::Replicates> holder(rep);
+        std::vector<vb2_estimate> est(R);
+        std::vector<int32_t> status(R, 0);
+        if (const int rc = rep->optimize(model, est.data(), status.data())) return rc;
+        sum.num_step = rep->num_step;
+        const double theta = vb2::freemix_of(whole);
+        if (C > 0) {
+            std::vector<int64_t> m(C);
+            std::vector<double> without(C, 0.0);
+            for (int j = 0; j < C; ++j) {
+                m[j] = status[j] == VB2_OK ? rep->counted[j] : 0;
+                if (status[C + j] != VB2_OK) m[j] = 0;
+                without[j] = vb2::freemix_of(est[C + j]);
+            }
+            double je = NAN, jse = NAN;
+            if (vb2_jackknife(C, m.data(), theta, without.data(), &je, &jse) == VB2_OK) {
+                sum.jack_estimate = je;
+                sum.jack_se = jse;
+                sum.jack_lo = std::min(0.5, std::max(0.0, theta - 1.96 * jse));
+                sum.jack_hi = std::min(0.5, std::max(0.0, theta + 1.96 * jse));
+            }
+            sum.num_chrom = C;
+            if (args->output_prefix) {
+                const std::string name(std::string(args->output_prefix) + ".Chrom");
+                std::ofstream fout(name);
+                if (!fout.is_open()) {
+                    set_error("Open file " + name + " failed!");
+                    return VB2_ERR_IO;
+                }
+                fout << "#CHROM\tMARKERS\tFREEMIX_ONLY\tFREELK1_ONLY\tFREELK0_ONLY\tFREEMIX_WITHOUT\tDELTA\n";
+                for (int j = 0; j < C; ++j) {
+                    fout << b.names[j] << "\t" << rep->counted[j];
+                    if (m[j] > 0) {
+                        fout << "\t" << vb2::freemix_of(est[j]) << "\t" << -est[j].llk1 << "\t" << -est[j].llk0 << "\t" << without[j]
+                             << "\t" << without[j] - theta << "\n";
+                    } else {
+                        fout << "\tNA\tNA\tNA\tNA\tNA\n";
+                    }
+                }
+                fout << "#JACKKNIFE\tFREEMIX\t" << sum.jack_estimate << "\tSE\t" << sum.jack_se << "\tLO\t" << sum.jack_lo << "\tHI\t"
+                     << sum.jack_hi << "\n";
+                fout.close();
+                if (!fout) {
+                    set_error("Errors detected when writing to file " + name + " !");
+                    return VB2_ERR_IO;
+                }
+            }
+        }
+        if (N > 0) {
+            std::vector<double> v;
+            for (int q = 0; q < N; ++q)
+                if (status[2 * C + q] == VB2_OK) v.push_back(vb2::freemix_of(est[2 * C + q]));
+            sum.num_boot = (int32_t)v.size();
+            if (!v.empty()) {
+                double mean = 0, ss = 0;
+                for (double x : v) mean += x;
+                mean /= (double)v.size();
+                for (double x : v) ss += (x - mean) * (x - mean);
+                std::vector<double> sorted(v);
+                std::sort(sorted.begin(), sorted.end());
+                const double last = (double)(sorted.size() - 1);
+                sum.boot_mean = mean;
+                sum.boot_sd = v.size() > 1 ? std::sqrt(ss / (double)(v.size() - 1)) : 0.0;
+                sum.boot_p025 = sorted[(size_t)std::floor(0.025 * last + 0.5)];
+                sum.boot_p975 = sorted[(size_t)std::floor(0.975 * last + 0.5)];
+            }
+            if (args->output_prefix) {
+                const std::string name(std::string(args->output_prefix) + ".Boot");
+                std::ofstream fout(name);
+                if (!fout.is_open()) {
+                    set_error("Open file " + name + " failed!");
+                    return VB2_ERR_IO;
+                }
+                fout << "#REPLICATE\tFREEMIX\tFREELK1\n";
+                for (int q = 0; q < N; ++q) {
+                    const vb2_estimate& e = est[2 * C + q];
+                    if (status[2 * C + q] == VB2_OK) fout << q + 1 << "\t" << vb2::freemix_of(e) << "\t" << -e.llk1 << "\n";
+                    else fout << q + 1 << "\tNA\tNA\n";
+                }
+                fout << "#BOOTSTRAP\tMEAN\t" << sum.boot_mean << "\tSD\t" << sum.boot_sd << "\tP2.5\t" << sum.boot_p025 << "\tP97.5\t"
+                     << sum.boot_p975 << "\n";
+                fout.close();
+                if (!fout) {
+                    set_error("Errors detected when writing to file " + name + " !");
+                    return VB2_ERR_IO;
+                }
+            }
+        }
+        sum.seconds = vb2::now_s() - t0;
+        if (notices)
+            std::fprintf(stderr, "NOTICE - Finished phase: Likelihood replicates  [%.3f seconds, %lld lock-step steps]\n", sum.seconds,
+                         (long long)sum.num_step);
+        if (C > 0)
+            std::fprintf(stderr, "NOTICE - FREEMIX jackknife over %d chromosomes: %g, SE %g, [%g, %g]\n", C, sum.jack_estimate,
+                         sum.jack_se, sum.jack_lo, sum.jack_hi);
+        if (N > 0)
+            std::fprintf(stderr, "NOTICE - FREEMIX bootstrap over %d resamples: mean %g, SD %g, [%g, %g]\n", (int)sum.num_boot,
+                         sum.boot_mean, sum.boot_sd, sum.boot_p025, sum.boot_p975);
+        return VB2_OK;
+    };
+    try {
+        const int rc = vb2::run_with_hook(args, out, hook);
+        if (summary) *summary = sum;
+        return rc;
+    } catch (const std::bad_alloc&) {
+        set_error("out of host memory");
+        return VB2_ERR_NOMEM;
+    } catch (const std::exception& e) {
+        set_error(e.what());
+        return VB2_ERR_INVALID;
+    }
+}
+
+}  // extern "C"

@@ -518,6 +518,34 @@ void vb2_source_set_destroy(vb2_source_set *set);
 int vb2_cohort_run_sources(const vb2_cohort_args *args, int32_t top, vb2_run_result *out /* [num_sample] */,
                            int32_t *status /* [num_sample] */, double *score, int32_t *shared);
 
+/* vb2_cohort_run_sources plus a stage after the score matrix (--FindSource --RefitSource; section 3d):
+ * the contexts of the samples that got a row in the source set are not destroyed when their files are written but parked --
+ * the one cost of the call, their device bytes go into a NOTICE -- and after the matrix every sample is refitted GIVEN its best
+ * candidate, where that candidate's score is finite and > 0: a one-hypothesis vb2_conditioned set on the sample's own
+ * context, pc1 held at the sample's search point (vb2_source_set_add), all refits in ONE vb2_conditioned_optimize_llk.
+ * fit: [num_sample] or NULL.  With output prefixes it writes <output_prefix of base>.SourceFit, tab-separated with %g:
+ *     #SAMPLE CANDIDATE LLR MARKERS FREEMIX FREELK1 ALPHA_GIVEN LK1_GIVEN LK0_GIVEN DELTA_LK
+ * one row per searched sample with a first candidate in .Sources (a sample that failed is absent), NA in the last four
+ * columns where no refit ran.  FREELK1, LK1_GIVEN and LK0_GIVEN are minus log-likelihoods as the cohort's stdout table
+ * prints FREELK1 (vb2_estimate.llk1 / llk0); DELTA_LK = (-LK1_GIVEN) - (-FREELK1): positive = the likelihood at the
+ * conditioned maximum exceeds the anonymous model's at its own maximum -- with num_pc fewer free parameters.  LLR is the
+ * floored score of .Sources; DELTA_LK has no floor.  A refit that fails leaves its row NA, gives a NOTICE and does not fail
+ * the run.  is_alpha_fixed and more than one device are VB2_ERR_INVALID before any file is read.  stdout, .selfSM, .Ancestry
+ * and .Sources are what vb2_cohort_run_sources writes. */
+#define VB2_SOURCE_FIT_NONE 1          /* vb2_source_fit.status: no refit was asked of this sample */
+typedef struct vb2_source_fit {
+    int32_t candidate;         /* the best candidate's sample index; -1: none (the sample failed, or stands alone)   */
+    int32_t markers;           /* markers both count                                                                  */
+    int32_t status;            /* VB2_OK: refitted; VB2_SOURCE_FIT_NONE; or the refit's error                         */
+    int32_t reserved;
+    double llr;                /* the candidate's score in the matrix                                                 */
+    double freemix, freelk1;   /* the anonymous fit: min(alpha, 1 - alpha), llk1                                      */
+    double alpha_given, lk1_given, lk0_given, delta_lk;    /* NAN where no refit ran                                  */
+} vb2_source_fit;
+int vb2_cohort_run_source_fits(const vb2_cohort_args *args, int32_t top, vb2_run_result *out /* [num_sample] */,
+                               int32_t *status /* [num_sample] */, double *score, int32_t *shared,
+                               vb2_source_fit *fit /* [num_sample] or NULL */);
+
 /* vb2_cohort_run that also computes every searched sample's interval (vb2_batch_interval: in lock-step, on a stage of its own
  * next to the search) and writes <prefix>.CI per sample; ci: [num_sample] or NULL.  A sample that failed its search or its
  * sanity check has no .CI (and a zeroed ci entry).  source_top > 0: --FindSource as well, what vb2_cohort_run_sources does
@@ -602,6 +630,68 @@ typedef struct vb2_replicate_summary {
 } vb2_replicate_summary;
 int vb2_run_replicates(const vb2_run_args *args, int32_t per_chromosome, int32_t bootstrap, vb2_run_result *out,
                        vb2_replicate_summary *summary /* or NULL */);
+
+/* ------------------------------------------------------------------------- *
+ * 3d. The likelihood given a hypothesised contaminant.  Not in the reference: its model with a
+ *     per-marker genotype prior on the alpha-fraction component in place of the Hardy-Weinberg prior GF1.  In the notation
+ *     of 3b, a hypothesis h carries one triple pi_h[m][3] per panel marker (float32, panel order):
+ *         L_m(pc1, pc2, alpha | h) = sum_g1 P[g1] sum_g2 GF2[g2] W[g1][g2]
+ *             P = pi_h[m]          where the triple is not all zero
+ *             P = GF1(pc1)[m]      where it is (no information: the anonymous model's term)
+ *         LLK(. | h) = sum_m log L_m  over the markers with L_m > 0  (h:310)
+ *     An all-zero hypothesis is vb2_llk_eval_batch; at alpha = 0 a normalised prior drops out; with pi = q_j (3b) on the
+ *     markers j counts, LLK(theta | j) - LLK(theta) = sum_shared log(c_i . q_j): 3b's score without its floor -- ONE
+ *     discordant marker can cost more than 3b's -69 nats.  There is no mirror symmetry: alpha is the share of the
+ *     hypothesised individual and is reported as fitted, never folded at 0.5.
+ *     The refit (vb2_conditioned_optimize_llk) holds pc1 -- it only feeds the fallback markers -- and searches alpha and
+ *     the intended sample's PCs: the conditioned model has num_pc FEWER free parameters than the default two-ancestry
+ *     model, which a comparison of the two maxima has to bear in mind.
+ * ------------------------------------------------------------------------- */
+typedef struct vb2_conditioned vb2_conditioned;
+
+/* prior: [num_hyp][num_marker][3] float32 in panel order (num_marker = the context's), host memory.  The rows are uploaded
+ * once and permuted on the device into the context's marker order (three planes per hypothesis); device memory comes from
+ * the library's slab cache.  The context must outlive the set and must not be inside vb2_ctx_search_begin /
+ * vb2_ctx_search_end when the set is used. */
+int vb2_conditioned_create(vb2_ctx *ctx, int32_t num_hyp, const float *prior, vb2_conditioned **out);
+/* The same with hypothesis h = the genotype posterior q of sample candidate[h] of a source set (3b), copied device to
+ * device.  The set must be of the context's panel size and on the context's device, and the candidate must have a row:
+ * VB2_ERR_INVALID otherwise. */
+int vb2_conditioned_create_from_set(vb2_ctx *ctx, vb2_source_set *set, int32_t num_hyp, const int32_t *candidate,
+                                    vb2_conditioned **out);
+void vb2_conditioned_destroy(vb2_conditioned *cond);
+/* One step: hypothesis h evaluates num_point[h] (0..VB2_BATCH_SLOTS) points; the rows of all hypotheses are concatenated in
+ * hypothesis order -- pc1 / pc2 [sum][num_pc], alpha [sum] -> llk_out [sum] -- as in vb2_replicates_eval.  A point's value
+ * is the same bits whatever else the step holds and from call to call; an alpha outside [0, 1] leaves every marker out. */
+int vb2_conditioned_eval(vb2_conditioned *cond, const int32_t *num_point, const double *pc1, const double *pc2,
+                         const double *alpha, double *llk_out);
+/* The refit of every hypothesis of every set, all in lock-step: the reference-exact OptimizeLLK under a copy of `model` with
+ * is_heter = 0 (it packs pc1 = pc2 = v, starts where the reference starts and takes llk0 at alpha = 0), whose pc1 rows are
+ * overwritten with pc1_fixed on their way to the device -- alpha and the intended sample's PCs are searched (alpha alone
+ * with is_pc_fixed or known allele frequencies); is_alpha_fixed is VB2_ERR_INVALID.  pc1_fixed: [num_set][num_pc], one row
+ * per set (the target's search point).  A step begins the evaluation of every set with live points, then collects them:
+ * sets on different contexts overlap on the device.  est_out / status: [sum of num_hyp] in set order; est_out has alpha,
+ * pc2 (also in pc), llk1 and llk0.  status: VB2_OK, or VB2_ERR_INVALID for a hypothesis whose first evaluation is exactly
+ * 0.0 everywhere (no counted marker; the others finish).  All sets must share num_pc.  The return value: an error that
+ * concerns all. */
+int vb2_conditioned_optimize_llk(vb2_conditioned *const *sets, int32_t num_set, const vb2_model *model,
+                                 const double *pc1_fixed, vb2_estimate *est_out, int32_t *status);
+typedef struct vb2_conditioned_info {
+    int32_t num_hyp;
+    int32_t num_marker;
+    int64_t device_bytes;      /* device memory the set holds beyond the context's                   */
+    int64_t num_step;          /* evaluations that reached the device (the searches' steps included)  */
+    int64_t num_launch;        /* marker-kernel launches of those steps                               */
+} vb2_conditioned_info;
+int vb2_conditioned_info_get(const vb2_conditioned *cond, vb2_conditioned_info *info);
+/* The same driver over a caller's evaluator (the seam vb2_replicates_lockstep is for the replicates): no device needed.  A
+ * step calls fn once, on the calling thread's own stack; num_point[h] = 0 for a hypothesis that has finished.  The pc1 rows
+ * fn sees are pc1_fixed [num_hyp][num_pc] at every call, the llk0 call included.  Non-zero from fn ends every search and is
+ * returned. */
+typedef int (*vb2_conditioned_eval_fn)(void *user, int32_t num_hyp, const int32_t *num_point, const double *pc1,
+                                       const double *pc2, const double *alpha, double *llk);
+int vb2_conditioned_lockstep(vb2_conditioned_eval_fn fn, void *user, int32_t num_hyp, int32_t num_pc, const vb2_model *model,
+                             const double *pc1_fixed, vb2_estimate *est_out, int32_t *status);
 
 /* Host-side flattening only (no device): reads panel + pileup, resolves markers
  * and returns the arrays of vb2_input in library-owned memory; free with

@@ -165,12 +165,27 @@ BATCH_DERIVS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int3
 # vb2_replicates_eval_fn: (user, num_rep, num_point, pc1, pc2, alpha, llk)
 REPLICATES_EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double),
                                  C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double))
+# vb2_conditioned_eval_fn: (user, num_hyp, num_point, pc1, pc2, alpha, llk)
+CONDITIONED_EVAL_FN = REPLICATES_EVAL_FN
 VB2_BATCH_SLOTS = 8
 VB2_CHROM_NAME_LEN = 32
 
 
 class ReplicatesInfo(C.Structure):
     _fields_ = [("num_rep", C.c_int32), ("num_marker", C.c_int32), ("device_bytes", C.c_int64), ("num_step", C.c_int64),
+                ("num_launch", C.c_int64)]
+
+
+VB2_SOURCE_FIT_NONE = 1
+
+
+class SourceFit(C.Structure):
+    _fields_ = [("candidate", C.c_int32), ("markers", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)] + \
+               [(n, C.c_double) for n in ("llr", "freemix", "freelk1", "alpha_given", "lk1_given", "lk0_given", "delta_lk")]
+
+
+class ConditionedInfo(C.Structure):
+    _fields_ = [("num_hyp", C.c_int32), ("num_marker", C.c_int32), ("device_bytes", C.c_int64), ("num_step", C.c_int64),
                 ("num_launch", C.c_int64)]
 
 
@@ -198,6 +213,8 @@ SYMBOLS = [
     "vb2_replicates_create", "vb2_replicates_destroy", "vb2_replicates_eval", "vb2_replicates_optimize_llk",
     "vb2_replicates_info_get", "vb2_replicates_lockstep", "vb2_chromosome_weights", "vb2_bootstrap_weights", "vb2_jackknife",
     "vb2_run_replicates",
+    "vb2_conditioned_create", "vb2_conditioned_create_from_set", "vb2_conditioned_destroy", "vb2_conditioned_eval",
+    "vb2_conditioned_optimize_llk", "vb2_conditioned_info_get", "vb2_conditioned_lockstep", "vb2_cohort_run_source_fits",
 ]
 
 _lib = None
@@ -309,6 +326,20 @@ def lib():
     L.vb2_jackknife.argtypes = [C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.vb2_run_replicates.argtypes = [C.POINTER(RunArgs), C.c_int32, C.c_int32, C.POINTER(RunResult),
                                      C.POINTER(ReplicateSummary)]
+    L.vb2_cohort_run_source_fits.argtypes = [C.POINTER(CohortArgs), C.c_int32, C.POINTER(RunResult), C.POINTER(C.c_int32),
+                                             C.c_void_p, C.c_void_p, C.POINTER(SourceFit)]
+    L.vb2_conditioned_create.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]
+    L.vb2_conditioned_create_from_set.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]
+    L.vb2_conditioned_destroy.argtypes = [C.c_void_p]
+    L.vb2_conditioned_destroy.restype = None
+    L.vb2_conditioned_eval.argtypes = [C.c_void_p] * 6
+    L.vb2_conditioned_optimize_llk.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(Model), C.c_void_p,
+                                               C.POINTER(Estimate), C.POINTER(C.c_int32)]
+    L.vb2_conditioned_info_get.argtypes = [C.c_void_p, C.POINTER(ConditionedInfo)]
+    L.vb2_conditioned_lockstep.argtypes = [CONDITIONED_EVAL_FN, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Model), C.c_void_p,
+                                           C.POINTER(Estimate), C.POINTER(C.c_int32)]
+    L.vb2_debug_conditioned_time.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+    L.vb2_debug_replicates_time.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     L.vb2_debug_set_tunable.argtypes = [C.c_char_p, C.c_int]
     L.vb2_debug_get_tunable.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
     _lib = L

@@ -626,6 +626,126 @@ def replicates_with_evaluator(evaluate, num_rep, num_pc, known_af=False, **model
     return [dict(_estimate_dict(est[r], k), status=int(status[r])) for r in range(R)]
 
 
+class Conditioned:
+    """vb2_conditioned: the likelihood of the ONE resident sample given a hypothesised contaminant -- per hypothesis one
+    genotype triple per panel marker (float32, panel order) in place of the Hardy-Weinberg prior of the alpha-fraction
+    component; an all-zero triple falls back to that prior.  prior: [H, M, 3]; or source_set= and candidates= (indices
+    into a SourceSet on the context's device): hypothesis h is the genotype posterior of that sample, copied on the device."""
+    SLOTS = _abi.VB2_BATCH_SLOTS
+
+    def __init__(self, ctx: LikelihoodContext, prior=None, source_set=None, candidates=None):
+        self._lib = _abi.lib()
+        self.ctx = ctx
+        self.num_pc = ctx.num_pc
+        h = C.c_void_p()
+        if source_set is not None:
+            cand = np.ascontiguousarray(np.atleast_1d(np.asarray(candidates)), dtype=np.int32)
+            self.num_hyp = int(cand.shape[0])
+            _abi.check(self._lib.vb2_conditioned_create_from_set(ctx._h, source_set._h, self.num_hyp, _p(cand), C.byref(h)),
+                       "vb2_conditioned_create_from_set")
+        else:
+            pr = np.asarray(prior)
+            if pr.ndim == 2:
+                pr = pr[None]
+            if pr.ndim != 3 or pr.shape[1:] != (ctx.data.num_marker, 3):
+                raise ValueError("prior must be [hypotheses, %d markers, 3]" % ctx.data.num_marker)
+            pr = np.ascontiguousarray(pr, dtype=np.float32)
+            self.num_hyp = int(pr.shape[0])
+            _abi.check(self._lib.vb2_conditioned_create(ctx._h, self.num_hyp, _p(pr), C.byref(h)), "vb2_conditioned_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.vb2_conditioned_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def info(self):
+        i = _abi.ConditionedInfo()
+        _abi.check(self._lib.vb2_conditioned_info_get(self._h, C.byref(i)), "vb2_conditioned_info_get")
+        return dict(num_hyp=i.num_hyp, num_marker=i.num_marker, device_bytes=int(i.device_bytes), num_step=int(i.num_step),
+                    num_launch=int(i.num_launch))
+
+    def eval(self, num_point, pc1, pc2, alpha):
+        """One step (vb2_conditioned_eval): num_point [H] ints 0..8; pc1 / pc2 [P, k] and alpha [P] with P = sum(num_point),
+        the hypotheses' rows one after the other.  Returns llk [P]."""
+        k = self.num_pc
+        npt = np.ascontiguousarray(num_point, dtype=np.int32).reshape(self.num_hyp)
+        P = int(npt.sum())
+        pc1 = np.ascontiguousarray(np.asarray(pc1, dtype=np.float64).reshape(P, k))
+        pc2 = np.ascontiguousarray(np.asarray(pc2, dtype=np.float64).reshape(P, k))
+        alpha = np.ascontiguousarray(np.asarray(alpha, dtype=np.float64).reshape(P))
+        out = np.zeros(P)
+        _abi.check(self._lib.vb2_conditioned_eval(self._h, _p(npt), _p(pc1), _p(pc2), _p(alpha), _p(out)), "vb2_conditioned_eval")
+        return out
+
+    def optimize(self, pc1_fixed, **model_kw):
+        """The refit of every hypothesis in lock-step (Conditioned.optimize_sets on this set alone)."""
+        return Conditioned.optimize_sets([self], [pc1_fixed], **model_kw)[0]
+
+    @staticmethod
+    def optimize_sets(sets, pc1_fixed, **model_kw):
+        """vb2_conditioned_optimize_llk: the refits of every hypothesis of every set in ONE lock-step gang -- alpha and the
+        intended sample's PCs (alpha alone with fix_pc= or known allele frequencies), the contaminant's PCs held at
+        pc1_fixed[s] ([num_set, k]).  Returns per set a list of dicts (alpha, pc2 -- also in pc --, llk1, llk0, "status")."""
+        L = _abi.lib()
+        k = sets[0].num_pc
+        S = len(sets)
+        fixed = np.ascontiguousarray(np.asarray(pc1_fixed, dtype=np.float64).reshape(S, k))
+        m, keep = _model(**model_kw)
+        H = sum(c.num_hyp for c in sets)
+        handles = (C.c_void_p * S)(*[c._h for c in sets])
+        est = (_abi.Estimate * H)()
+        status = (C.c_int32 * H)()
+        _abi.check(L.vb2_conditioned_optimize_llk(handles, S, C.byref(m), _p(fixed), est, status), "vb2_conditioned_optimize_llk")
+        del keep
+        out, at = [], 0
+        for c in sets:
+            out.append([dict(_estimate_dict(est[at + h], k), status=int(status[at + h])) for h in range(c.num_hyp)])
+            at += c.num_hyp
+        return out
+
+
+def conditioned_with_evaluator(evaluate, num_hyp, num_pc, pc1_fixed, known_af=False, **model_kw):
+    """The refits' lock-step driver over a Python evaluator (vb2_conditioned_lockstep): no device.
+    evaluate(num_point [H] int32, pc1 [P, k], pc2 [P, k], alpha [P]) -> llk [P], P = sum(num_point), called once per step
+    with the points of every hypothesis still searching; the pc1 rows are pc1_fixed [H, k] at every call.  Returns one dict
+    per hypothesis (with "status")."""
+    L = _abi.lib()
+    k, H = int(num_pc), int(num_hyp)
+    err = []
+
+    def cb(_user, nh, npt, p1, p2, a, out):
+        try:
+            num_point = np.ctypeslib.as_array(npt, (nh,)).copy()
+            P = int(num_point.sum())
+            res = evaluate(num_point, np.ctypeslib.as_array(p1, (P, k)).copy(), np.ctypeslib.as_array(p2, (P, k)).copy(),
+                           np.ctypeslib.as_array(a, (P,)).copy())
+            np.ctypeslib.as_array(out, (P,))[:] = np.asarray(res, dtype=np.float64).reshape(P)
+            return 0
+        except Exception as exc:   # never let an exception cross the C boundary
+            err.append(exc)
+            return _abi.VB2_ERR_INVALID
+    fn = _abi.CONDITIONED_EVAL_FN(cb)
+    fixed = np.ascontiguousarray(np.asarray(pc1_fixed, dtype=np.float64).reshape(H, k))
+    m, keep = _model(known_af=known_af, **model_kw)
+    est = (_abi.Estimate * H)()
+    status = (C.c_int32 * H)()
+    rc = L.vb2_conditioned_lockstep(fn, None, H, k, C.byref(m), _p(fixed), est, status)
+    del keep
+    if err:
+        raise err[0]
+    _abi.check(rc, "vb2_conditioned_lockstep")
+    return [dict(_estimate_dict(est[h], k), status=int(status[h])) for h in range(H)]
+
+
 def chromosome_weights(bed_path, num_marker=None):
     """The chromosomes of a panel's .bed as blocks, in order of first appearance (vb2_chromosome_weights): a dict with
     names, block_of [M], block_size (distinct positions per block) and the weight rows only / without [C, M] uint8.
@@ -837,7 +957,7 @@ def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_san
 def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, disable_sanity=False,
                      known_af_path=None, device=-1, output_pileup=False, group_size=0, num_host_thread=0,
                      devices=None, find_source=False, source_top=3, sources_prefix=None, confidence_interval=False,
-                     **model_kw):
+                     refit_source=False, **model_kw):
     """Many pileups against one panel (vb2_cohort_run): the panel is read once, the pileups are read
     and flattened by host threads while the device searches the previous group in lock-step.
     Returns one dict per sample (with its own "status" code).
@@ -846,8 +966,13 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
     sources_prefix it writes <sources_prefix>.Sources, source_top candidates per sample.
     confidence_interval (vb2_cohort_run_intervals; one device; may be combined with find_source, which then returns no
     matrices: sources = None): every searched sample's dict has an `interval` entry, and with output_prefixes its
-    <prefix>.CI is written."""
+    <prefix>.CI is written.
+    refit_source (with find_source; vb2_cohort_run_source_fits): sources also has `fit`, one dict per sample -- candidate
+    (-1: none), markers, status (0: refitted, 1: no refit asked, < 0: the refit's error), llr, freemix, freelk1,
+    alpha_given, lk1_given, lk0_given, delta_lk -- and <sources_prefix>.SourceFit is written."""
     S = len(pileup_paths)
+    if refit_source and (not find_source or confidence_interval):
+        raise ValueError("refit_source needs find_source and cannot be combined with confidence_interval")
     args, keep = _run_args(svd_prefix, pileup_paths[0], num_pc, disable_sanity, known_af_path,
                            sources_prefix if find_source else None,
                            device, output_pileup, devices=devices, **model_kw)
@@ -870,6 +995,11 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
         civ = (_abi.Interval * S)()
         _abi.check(_abi.lib().vb2_cohort_run_intervals(C.byref(ca), int(source_top) if find_source else 0, res, status, civ),
                    "vb2_cohort_run_intervals")
+    elif refit_source:
+        score, shared = np.zeros((S, S)), np.zeros((S, S), dtype=np.int32)
+        fits = (_abi.SourceFit * S)()
+        _abi.check(_abi.lib().vb2_cohort_run_source_fits(C.byref(ca), int(source_top), res, status, _p(score), _p(shared), fits),
+                   "vb2_cohort_run_source_fits")
     elif find_source:
         score, shared = np.zeros((S, S)), np.zeros((S, S), dtype=np.int32)
         _abi.check(_abi.lib().vb2_cohort_run_sources(C.byref(ca), int(source_top), res, status, _p(score), _p(shared)),
@@ -885,6 +1015,9 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
         if civ is not None and status[s] == _abi.VB2_OK:
             d["interval"] = _interval_dict(civ[s])
         out.append(d)
+    if refit_source:
+        fit = [{name: getattr(fits[s], name) for name, _ in _abi.SourceFit._fields_ if name != "reserved"} for s in range(S)]
+        return out, dict(score=score, shared=shared, fit=fit)
     if find_source:
         return out, (None if civ is not None else dict(score=score, shared=shared))
     return out

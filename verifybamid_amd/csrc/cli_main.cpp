@@ -22,6 +22,9 @@
 // --PerChromosome writes <Output>.Chrom -- FREEMIX refitted on every chromosome of the .bed alone and with it left out, and a
 // delete-one-chromosome jackknife --, --Bootstrap N (1..1000, seeded by --Seed) <Output>.Boot: weighted-marker replicates of
 // the one resident sample searched in lock-step (vb2_run_replicates; one sample, one device).
+// --FindSource --RefitSource also writes <Output>.SourceFit: every sample's FREEMIX refitted GIVEN the genotypes of its best
+// candidate, and the likelihood difference to the anonymous fit (vb2_cohort_run_source_fits; not with --FixAlpha,
+// --CohortInterval or several --Devices).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -95,6 +98,7 @@ int main(int argc, char** argv)
     bool cohortInterval = false;
     bool findSource = false;
     int sourceTop = 3;
+    bool refitSource = false;
     bool perChromosome = false;
     int bootstrap = 0;
     // "Pileup Options" (main.cpp:176-187), defaults main.cpp:81-96 (MPLP_REALN | MPLP_SMART_OVERLAPS; UNMAP | SECONDARY |
@@ -155,6 +159,9 @@ int main(int argc, char** argv)
         // pair's log-likelihood ratio (vb2_cohort_run_sources); the --SourceTop best candidates per sample go to <Output>.Sources
         {"FindSource", {Flag::kBool, &findSource, false}},
         {"SourceTop", {Flag::kInt, &sourceTop, false}},
+        // not in the reference: after --FindSource, every sample's FREEMIX refitted given its best candidate's genotypes
+        // (vb2_cohort_run_source_fits), to <Output>.SourceFit
+        {"RefitSource", {Flag::kBool, &refitSource, false}},
         // not in the reference: FREEMIX refitted on every chromosome alone and with every chromosome left out, with a
         // delete-one-chromosome jackknife (<Output>.Chrom), and over --Bootstrap N marker resamples seeded by --Seed
         // (<Output>.Boot): weighted-marker replicates of the one resident sample, searched in lock-step (vb2_run_replicates)
@@ -204,6 +211,16 @@ int main(int argc, char** argv)
                   "(--ConfidenceInterval is the flag for one sample)");
         if (Devices != "Empty" && Devices.find(',') != std::string::npos)
             fatal("--CohortInterval cannot be combined with more than one --Devices: the intervals of a cohort are computed on one device");
+    }
+    if (refitSource) {                                                  // a --FindSource cohort on one device
+        if (!findSource)
+            fatal("--RefitSource needs --FindSource: the refit is given the best candidate of the cohort's source scores");
+        if (flags["FixAlpha"].seen)
+            fatal("--RefitSource cannot be combined with --FixAlpha: a fixed alpha leaves the refit nothing to estimate");
+        if (cohortInterval)
+            fatal("--RefitSource cannot be combined with --CohortInterval: run the intervals and the refits separately");
+        if (Devices != "Empty" && Devices.find(',') != std::string::npos)
+            fatal("--RefitSource cannot be combined with more than one --Devices: the refits read a source set on one device");
     }
     if (findSource) {                                                   // a cohort on one device
         if (PileupList == "Empty")
@@ -362,6 +379,7 @@ int main(int argc, char** argv)
         std::vector<vb2_run_result> cres(pile.size());
         std::vector<int32_t> cst(pile.size());
         const int rcc = cohortInterval ? vb2_cohort_run_intervals(&ca, findSource ? sourceTop : 0, cres.data(), cst.data(), nullptr)
+                        : refitSource ? vb2_cohort_run_source_fits(&ca, sourceTop, cres.data(), cst.data(), nullptr, nullptr, nullptr)
                         : findSource ? vb2_cohort_run_sources(&ca, sourceTop, cres.data(), cst.data(), nullptr, nullptr)
                                      : vb2_cohort_run(&ca, cres.data(), cst.data());
         if (rcc != VB2_OK) {

@@ -20,7 +20,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <cmath>
 #include <deque>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -28,6 +30,7 @@
 #include <vector>
 
 #include "batch.h"
+#include "conditioned.h"
 #include "context.h"
 #include "estimator.h"
 #include "hostio.h"
@@ -58,10 +61,14 @@ public:
     // before its context is destroyed; score / shared ([S][S], may be null) and <Output>.Sources after the last sample
     // intervals: every searched sample's vb2_interval as well (vb2_cohort_run_intervals; one device) -- <prefix>.CI, and
     // ci[s] when ci is not null -- before the sample goes to the releaser
+    // refit (with find_source; vb2_cohort_run_source_fits): the contexts of the samples that got a row in the source set are
+    // parked instead of destroyed, and after the score matrix every sample's FREEMIX is refitted given its best candidate
+    // (conditioned.h) -- <Output>.SourceFit, and fit[s] when fit is not null
     CohortRunner(const vb2_cohort_args* a, vb2_run_result* out, int32_t* status, bool find_source = false, int top = 0,
-                 double* score = nullptr, int32_t* shared = nullptr, bool intervals = false, vb2_interval* ci = nullptr)
+                 double* score = nullptr, int32_t* shared = nullptr, bool intervals = false, vb2_interval* ci = nullptr,
+                 bool refit = false, vb2_source_fit* fit = nullptr)
         : a_(a), out_(out), status_(status), S_(a->num_sample), find_source_(find_source), top_(top), score_(score),
-          shared_(shared), intervals_(intervals), ci_(ci)
+          shared_(shared), intervals_(intervals), ci_(ci), refit_(refit && find_source), fit_(fit)
     {
         if (a->base.devices && a->base.num_device > 0) devices_.assign(a->base.devices, a->base.devices + a->base.num_device);
         else devices_.push_back(a->base.device);
@@ -107,7 +114,12 @@ public:
         ngroup_ = (int)group_begin_.size() - 1;
     }
 
-    ~CohortRunner() { shutdown(); }
+    ~CohortRunner()
+    {
+        shutdown();
+        release_parked();
+        drop_streams();
+    }
 
     int run()
     {
@@ -180,6 +192,11 @@ public:
         const double t_dev = now_s();
         shutdown();
         if (sources_ && !rc_all_) rc_all_ = finish_sources();
+        if (refit_) {
+            if (!rc_all_) rc_all_ = refit_sources();
+            release_parked();
+            drop_streams();
+        }
         if (timing)
             std::fprintf(stderr, "vb2_cohort_run: panel %.1f ms, HIP start-up beyond that %.1f ms, pipelines %.1f ms, "
                                  "shutdown (release contexts, join) %.1f ms; releaser: %.2f ms per context, %.2f ms per sample's host arrays\n",
@@ -243,18 +260,30 @@ private:
     std::deque<IvItem> iv_queue_;
     bool iv_closed_ = false;
 
+    // --RefitSource (false without it: nothing else then differs from a --FindSource run)
+    bool refit_ = false;
+    vb2_source_fit* fit_ = nullptr;
+    std::vector<vb2_ctx*> parked_;         // [sample] the context of a sample with a row in the source set (releaser thread)
+    int64_t parked_bytes_ = 0;
+    std::vector<double> sc_;               // the matrix, where the caller gave no room for it
+    std::vector<int32_t> sh_;
+    const double* fit_score_ = nullptr;
+    const int32_t* fit_shared_ = nullptr;
+
     // after the last context is gone: the matrix, and <Output>.Sources next to the samples' own files
     int finish_sources()
     {
         sources_->set_count(S_);
         const size_t nn = (size_t)S_ * (size_t)S_;
-        std::vector<double> sc;
-        std::vector<int32_t> sh;
+        std::vector<double>& sc = sc_;
+        std::vector<int32_t>& sh = sh_;
         const bool file = a_->output_prefixes && a_->base.output_prefix;
         double* score = score_;
         int32_t* shared = shared_;
-        if (file && !score) { sc.resize(nn); score = sc.data(); }
-        if (file && !shared) { sh.resize(nn); shared = sh.data(); }
+        if ((file || refit_) && !score) { sc.resize(nn); score = sc.data(); }
+        if ((file || refit_) && !shared) { sh.resize(nn); shared = sh.data(); }
+        fit_score_ = score;
+        fit_shared_ = shared;
         if (!score && !shared) return VB2_OK;
         int rc = sources_->scores(score, shared);
         if (!rc && file) rc = vb2::write_sources(a_->base.output_prefix, S_, top_, a_->output_prefixes, out_, status_, score, shared);
@@ -293,12 +322,121 @@ private:
                 sl.ctx = nullptr;
             }
         vb2::g_flatten_thread_cap.store(0);
+        if (!refit_) drop_streams();                     // (--RefitSource: the parked contexts still run on them)
+    }
+
+    void drop_streams()
+    {
         for (hipStream_t& st : own_streams_)             // (every context and batch that used them is gone)
             if (st) {
                 (void)hipStreamSynchronize(st);
                 (void)hipStreamDestroy(st);
                 st = nullptr;
             }
+    }
+
+    void release_parked()
+    {
+        for (vb2_ctx*& c : parked_)
+            if (c) {
+                vb2_ctx_destroy(c);
+                c = nullptr;
+            }
+    }
+
+    // --RefitSource, after the matrix: one refit per sample -- its best candidate, where that candidate's score is finite
+    // and > 0 --, each a one-hypothesis set on the sample's parked context, ALL in one lock-step call; fit[] and
+    // <Output>.SourceFit.  A refit that fails leaves its row NA, gives a NOTICE and does not fail the run.
+    int refit_sources()
+    {
+        const int k = a_->base.num_pc;
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        std::vector<vb2_source_fit> fit((size_t)S_);
+        std::vector<std::unique_ptr<vb2::Conditioned>> sets;
+        std::vector<int> who;
+        std::vector<double> fixed;
+        if (parked_bytes_ > 0)
+            std::fprintf(stderr, "NOTICE - --RefitSource: the contexts of %d samples stayed on the device for the refit (%lld bytes)\n",
+                         (int)std::count_if(parked_.begin(), parked_.end(), [](vb2_ctx* c) { return c != nullptr; }),
+                         (long long)parked_bytes_);
+        for (int i = 0; i < S_; ++i) {
+            vb2_source_fit& f = fit[(size_t)i];
+            std::memset(&f, 0, sizeof(f));
+            f.candidate = -1;
+            f.status = VB2_SOURCE_FIT_NONE;
+            f.llr = f.freemix = f.freelk1 = f.alpha_given = f.lk1_given = f.lk0_given = f.delta_lk = nan;
+            if (status_[i] != VB2_OK || !fit_score_ || top_ < 1) continue;
+            const vb2_estimate& e = out_[i].est;
+            f.freemix = e.alpha < 0.5 ? e.alpha : 1 - e.alpha;
+            f.freelk1 = e.llk1;
+            // the first row of the sample in .Sources: the first of the largest scores (write_sources: a stable sort)
+            int best = -1;
+            for (int j = 0; j < S_; ++j) {
+                const double v = fit_score_[(size_t)i * S_ + j];
+                if (j == i || std::isnan(v)) continue;
+                if (best < 0 || v > fit_score_[(size_t)i * S_ + best]) best = j;
+            }
+            if (best < 0) continue;
+            f.candidate = best;
+            f.llr = fit_score_[(size_t)i * S_ + best];
+            f.markers = fit_shared_ ? fit_shared_[(size_t)i * S_ + best] : 0;
+            if (!(std::isfinite(f.llr) && f.llr > 0) || (size_t)i >= parked_.size() || !parked_[(size_t)i]) continue;
+            // the target's search point, as the source set took it (SourceSet::put): the swap of indices 0 and 1 undone,
+            // mirrored when alpha >= 0.5; its pc1 is what the refit holds
+            vb2::Context* c = parked_[(size_t)i]->impl;
+            const bool kaf = model_.is_af_known != 0 || c->L.known_af != nullptr;
+            const bool heter = model_.is_heter && !kaf;
+            std::vector<double> p1(e.pc, e.pc + k), p2(e.pc2, e.pc2 + k);
+            if (heter && e.alpha >= 0.5 && k >= 1) {
+                std::swap(p1[0], p2[0]);
+                if (k >= 2) std::swap(p1[1], p2[1]);
+            }
+            if (e.alpha >= 0.5) p1.swap(p2);
+            vb2::Conditioned* set = nullptr;
+            const int32_t cand = best;
+            if (const int rc = vb2::Conditioned::create_from_set(c, sources_.get(), 1, &cand, &set)) {
+                f.status = rc;
+                std::fprintf(stderr, "NOTICE - --RefitSource: sample %d is not refitted: %s\n", i, vb2::g_last_error.c_str());
+                continue;
+            }
+            sets.emplace_back(set);
+            who.push_back(i);
+            fixed.insert(fixed.end(), p1.begin(), p1.end());
+        }
+        if (!sets.empty()) {
+            std::vector<vb2::Conditioned*> raw;
+            for (auto& p : sets) raw.push_back(p.get());
+            std::vector<vb2_estimate> est(sets.size());
+            std::vector<int32_t> st(sets.size(), VB2_ERR_INVALID);
+            const double t0 = now_s();
+            if (model_.notices)
+                std::fprintf(stderr, "NOTICE - Starting phase: Refit given the source (%d searches in lock-step)\n", (int)sets.size());
+            const int rc = vb2::conditioned_optimize(raw.data(), (int)raw.size(), model_, fixed.data(), est.data(), st.data());
+            if (model_.notices)
+                std::fprintf(stderr, "NOTICE - Finished phase: Refit given the source  [%.3f seconds]\n", now_s() - t0);
+            for (size_t n = 0; n < who.size(); ++n) {
+                vb2_source_fit& f = fit[(size_t)who[n]];
+                f.status = rc ? rc : st[n];
+                if (f.status != VB2_OK) {
+                    std::fprintf(stderr, "NOTICE - --RefitSource: the refit of sample %d failed: %s\n", who[n], vb2::g_last_error.c_str());
+                    continue;
+                }
+                f.alpha_given = est[n].alpha;
+                f.lk1_given = est[n].llk1;
+                f.lk0_given = est[n].llk0;
+                f.delta_lk = (-f.lk1_given) - (-f.freelk1);
+            }
+            sets.clear();                               // before their contexts go
+        }
+        if (fit_) std::memcpy(fit_, fit.data(), sizeof(vb2_source_fit) * (size_t)S_);
+        if (a_->output_prefixes && a_->base.output_prefix) {
+            const int rc = vb2::write_source_fit(a_->base.output_prefix, S_, a_->output_prefixes, fit.data());
+            if (rc) {
+                err_all_ = vb2::g_last_error;
+                return rc;
+            }
+        }
+        return VB2_OK;
     }
 
     void prepare(int s)
@@ -654,6 +792,12 @@ private:
                         if (sources_->put(d.s, d.ctx->impl, model_, d.est))
                             std::fprintf(stderr, "NOTICE - --FindSource: sample %d has no row in the source set: %s\n", d.s,
                                          vb2::g_last_error.c_str());
+                        else if (refit_) {               // searched, written, in the set: parked for the refit, not destroyed
+                            if (parked_.empty()) parked_.assign((size_t)S_, nullptr);
+                            parked_[(size_t)d.s] = d.ctx;
+                            parked_bytes_ += d.ctx->impl->device_bytes;
+                            d.ctx = nullptr;
+                        }
                     }
                     item.first = d.ctx;
                     item.second = std::move(d.flat);
@@ -832,6 +976,36 @@ extern "C" int vb2_cohort_run_sources(const vb2_cohort_args* a, int32_t top, vb2
     }
     try {
         CohortRunner runner(a, out, status, true, top, score, shared);
+        const int rc = runner.run();
+        if (rc && !runner.error().empty()) set_error(runner.error());
+        return rc;
+    } catch (const std::bad_alloc&) {
+        set_error("out of host memory");
+        return VB2_ERR_NOMEM;
+    } catch (const std::exception& e) {
+        set_error(e.what());
+        return VB2_ERR_INVALID;
+    }
+}
+
+extern "C" int vb2_cohort_run_source_fits(const vb2_cohort_args* a, int32_t top, vb2_run_result* out, int32_t* status, double* score,
+                                          int32_t* shared, vb2_source_fit* fit)
+{
+    if (!a || !out || !status || a->num_sample < 1 || !a->pileup_paths || !a->base.ud_path || !a->base.mean_path ||
+        !a->base.bed_path || a->base.num_pc < 1 || a->base.num_pc > VB2_MAX_PC || top < 0) {
+        set_error("vb2_cohort_run_source_fits: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    if (a->base.num_device > 1 || a->base.num_device < 0) {
+        set_error("--RefitSource takes one device: a source set and the refits given it are not spread over several --Devices");
+        return VB2_ERR_INVALID;
+    }
+    if (a->base.model.is_alpha_fixed) {
+        set_error("--RefitSource cannot be combined with --FixAlpha: a fixed alpha leaves the refit nothing to estimate");
+        return VB2_ERR_INVALID;
+    }
+    try {
+        CohortRunner runner(a, out, status, true, top, score, shared, false, nullptr, true, fit);
         const int rc = runner.run();
         if (rc && !runner.error().empty()) set_error(runner.error());
         return rc;

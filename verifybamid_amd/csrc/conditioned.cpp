@@ -1,0 +1,600 @@
+// conditioned.cpp -- host side of the likelihood given a hypothesised contaminant (conditioned_kernels.hip; DESIGN.md section
+// 13): the set of hypotheses on a context, its evaluation in two halves, and the refits in lock-step.
+#include "conditioned.h"
+
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <cstring>
+#include <memory>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "conditioned_kernels.h"
+#include "context.h"
+#include "lockstep.h"
+#include "source.h"
+
+namespace vb2 {
+
+#define VB2_HIP_C(call)                                                                \
+    do {                                                                               \
+        hipError_t e_ = (call);                                                        \
+        if (e_ != hipSuccess) {                                                        \
+            set_error(std::string(#call) + " failed: " + hipGetErrorString(e_));       \
+            return VB2_ERR_HIP;                                                        \
+        }                                                                              \
+    } while (0)
+
+namespace {
+size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// a device slab from the cache, or a fresh one
+int take_device(size_t bytes, int device, void** p, size_t* got)
+{
+    *p = cached_device_slab(bytes, device, got);
+    if (!*p) {
+        if (hipMalloc(p, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            *p = nullptr;
+            set_error("vb2_conditioned_create: " + std::to_string(bytes) + " bytes of device memory do not fit");
+            return VB2_ERR_NOMEM;
+        }
+        *got = bytes;
+    }
+    return VB2_OK;
+}
+void give_device(void* p, size_t bytes, int device)
+{
+    if (p && !recycle_device_slab(p, bytes, device)) (void)hipFree(p);
+}
+}  // namespace
+
+int Conditioned::make(Context* ctx, int num_hyp, const char* who, Conditioned** out)
+{
+    *out = nullptr;
+    if (!ctx || num_hyp < 1 || num_hyp > 65535) {
+        set_error(std::string(who) + ": invalid argument (1..65535 hypotheses)");
+        return VB2_ERR_INVALID;
+    }
+    if (ctx->resident_active) {
+        set_error(std::string(who) + ": not inside vb2_ctx_search_begin / vb2_ctx_search_end");
+        return VB2_ERR_INVALID;
+    }
+    std::unique_ptr<Conditioned> c(new Conditioned());
+    c->ctx = ctx;
+    c->num_hyp = num_hyp;
+    const DeviceLayout& L = ctx->L;
+    VB2_HIP_C(hipSetDevice(ctx->device));
+    if (const int rc = ctx->ensure_pidx()) return rc;
+    const int k = ctx->num_pc;
+    const size_t cap = (size_t)num_hyp * VB2_BATCH_SLOTS;
+    // stage: rows [cap][2k+1] | hypothesis indices [cap] | results [cap]; on the device also a launch's partial sums
+    c->o_hyp_ = up256(sizeof(double) * cap * (size_t)(2 * k + 1));
+    c->o_res_ = up256(c->o_hyp_ + sizeof(int32_t) * cap);
+    c->o_part_ = up256(c->o_res_ + sizeof(double) * cap);
+    const size_t part_bytes = sizeof(double) * (size_t)kMaxPointsPerLaunch * (size_t)std::max(1, conditioned_tile_groups(L));
+    const size_t plane_bytes = std::max<size_t>(sizeof(float) * conditioned_hyp_floats(L) * (size_t)num_hyp, 256);
+    if (const int rc = take_device(plane_bytes, ctx->device, reinterpret_cast<void**>(&c->d_planes_), &c->d_planes_bytes_)) return rc;
+    if (const int rc = take_device(c->o_part_ + part_bytes, ctx->device, &c->d_stage_, &c->d_stage_bytes_)) return rc;
+    c->h_stage_ = cached_pinned_slab(c->o_part_, ctx->device, &c->h_stage_bytes_);
+    if (!c->h_stage_) {
+        VB2_HIP_C(hipHostMalloc(&c->h_stage_, c->o_part_, hipHostMallocMapped));
+        c->h_stage_bytes_ = c->o_part_;
+    }
+    c->device_bytes = (int64_t)(c->d_planes_bytes_ + c->d_stage_bytes_);
+    *out = c.release();
+    return VB2_OK;
+}
+
+int Conditioned::create(Context* ctx, int num_hyp, const float* prior, Conditioned** out)
+{
+    *out = nullptr;
+    if (!prior) {
+        set_error("vb2_conditioned_create: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    Conditioned* raw = nullptr;
+    if (const int rc = make(ctx, num_hyp, "vb2_conditioned_create", &raw)) return rc;
+    std::unique_ptr<Conditioned> c(raw);
+    // the panel-order rows go up once, into a slab that goes back to the cache when the permutation is done
+    const size_t bytes = sizeof(float) * 3 * (size_t)ctx->num_marker * (size_t)num_hyp;
+    void* d_panel = nullptr;
+    size_t d_panel_bytes = 0;
+    if (const int rc = take_device(std::max<size_t>(bytes, 256), ctx->device, &d_panel, &d_panel_bytes)) return rc;
+    hipError_t e = hipMemcpyAsync(d_panel, prior, bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess)
+        e = launch_prior_permute(ctx->L, ctx->num_marker, num_hyp, static_cast<const float*>(d_panel), ctx->d_pidx, c->d_planes_,
+                                 ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = es;
+    give_device(d_panel, d_panel_bytes, ctx->device);
+    if (e != hipSuccess) {
+        set_error(std::string("vb2_conditioned_create: prior upload failed: ") + hipGetErrorString(e));
+        return VB2_ERR_HIP;
+    }
+    *out = c.release();
+    return VB2_OK;
+}
+
+int Conditioned::create_from_set(Context* ctx, SourceSet* set, int num_hyp, const int32_t* candidate, Conditioned** out)
+{
+    *out = nullptr;
+    if (!ctx || !set || !candidate) {
+        set_error("vb2_conditioned_create_from_set: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    if (set->num_marker() != ctx->num_marker || set->device() != ctx->device) {
+        set_error("vb2_conditioned_create_from_set: the context is of another panel size or on another device than the set");
+        return VB2_ERR_INVALID;
+    }
+    std::vector<const float*> rows((size_t)std::max(num_hyp, 0));
+    for (int h = 0; h < num_hyp; ++h) {
+        rows[(size_t)h] = set->q_row(candidate[h]);
+        if (!rows[(size_t)h]) {
+            set_error("vb2_conditioned_create_from_set: candidate " + std::to_string(candidate[h]) + " has no row in the set");
+            return VB2_ERR_INVALID;
+        }
+    }
+    Conditioned* raw = nullptr;
+    if (const int rc = make(ctx, num_hyp, "vb2_conditioned_create_from_set", &raw)) return rc;
+    std::unique_ptr<Conditioned> c(raw);
+    // (the set's rows were written by contexts' streams that have been synchronised since: source.cpp, Context::marginals)
+    hipError_t e = hipSuccess;
+    for (int h = 0; h < num_hyp && e == hipSuccess; ++h)
+        e = launch_prior_permute(ctx->L, ctx->num_marker, 1, rows[(size_t)h], ctx->d_pidx,
+                                 c->d_planes_ + (size_t)h * conditioned_hyp_floats(ctx->L), ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) {
+        set_error(std::string("vb2_conditioned_create_from_set: the copy of the rows failed: ") + hipGetErrorString(e));
+        return VB2_ERR_HIP;
+    }
+    *out = c.release();
+    return VB2_OK;
+}
+
+Conditioned::~Conditioned()
+{
+    if (!ctx) return;
+    (void)hipSetDevice(ctx->device);
+    if (pending_) (void)hipStreamSynchronize(ctx->stream);
+    give_device(d_planes_, d_planes_bytes_, ctx->device);
+    give_device(d_stage_, d_stage_bytes_, ctx->device);
+    if (h_stage_ && !recycle_pinned_slab(h_stage_, h_stage_bytes_, ctx->device)) (void)hipHostFree(h_stage_);
+}
+
+int Conditioned::eval_begin(const int32_t* num_point, const double* pc1, const double* pc2, const double* alpha)
+{
+    if (!num_point || pending_) {
+        set_error("vb2_conditioned_eval: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    size_t total = 0;
+    for (int h = 0; h < num_hyp; ++h) {
+        if (num_point[h] < 0 || num_point[h] > VB2_BATCH_SLOTS) {
+            set_error("vb2_conditioned_eval: a hypothesis's point count outside 0..VB2_BATCH_SLOTS");
+            return VB2_ERR_INVALID;
+        }
+        total += (size_t)num_point[h];
+    }
+    if (total == 0) return VB2_OK;
+    if (!pc1 || !pc2 || !alpha) {
+        set_error("vb2_conditioned_eval: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    if (ctx->resident_active) {
+        set_error("vb2_conditioned_eval: not inside vb2_ctx_search_begin / vb2_ctx_search_end");
+        return VB2_ERR_INVALID;
+    }
+    VB2_HIP_C(hipSetDevice(ctx->device));
+    const int k = ctx->num_pc, n = 2 * k + 1;
+    char* const hp = static_cast<char*>(h_stage_);
+    char* const dp = static_cast<char*>(d_stage_);
+    double* const h_rows = reinterpret_cast<double*>(hp);
+    int32_t* const h_hyp = reinterpret_cast<int32_t*>(hp + o_hyp_);
+    size_t p = 0;
+    for (int h = 0; h < num_hyp; ++h)
+        for (int b = 0; b < num_point[h]; ++b, ++p) {
+            double* row = h_rows + p * n;
+            std::memcpy(row, pc1 + p * k, sizeof(double) * k);
+            std::memcpy(row + k, pc2 + p * k, sizeof(double) * k);
+            row[2 * k] = alpha[p];
+            h_hyp[p] = h;
+        }
+    // one upload, a launch pair per kMaxPointsPerLaunch points on the stream (the partial sums are stream-ordered), one
+    // download; the synchronisation is eval_end's
+    hipStream_t s = ctx->stream;
+    pending_ = total;                      // (from here on the stream may hold work on the stages)
+    VB2_HIP_C(hipMemcpyAsync(dp, hp, sizeof(double) * total * n, hipMemcpyHostToDevice, s));
+    VB2_HIP_C(hipMemcpyAsync(dp + o_hyp_, hp + o_hyp_, sizeof(int32_t) * total, hipMemcpyHostToDevice, s));
+    for (size_t done = 0; done < total; done += kMaxPointsPerLaunch) {
+        const int c = (int)std::min<size_t>(kMaxPointsPerLaunch, total - done);
+        VB2_HIP_C(launch_llk_conditioned(ctx->L, c, reinterpret_cast<const double*>(dp) + done * n,
+                                         reinterpret_cast<const int32_t*>(dp + o_hyp_) + done, d_planes_,
+                                         reinterpret_cast<double*>(dp + o_part_), reinterpret_cast<double*>(dp + o_res_) + done, s));
+        ++num_launch;
+    }
+    VB2_HIP_C(hipMemcpyAsync(hp + o_res_, dp + o_res_, sizeof(double) * total, hipMemcpyDeviceToHost, s));
+    return VB2_OK;
+}
+
+int Conditioned::eval_end(double* llk)
+{
+    if (!pending_) return VB2_OK;
+    const size_t total = pending_;
+    pending_ = 0;
+    VB2_HIP_C(hipSetDevice(ctx->device));
+    VB2_HIP_C(hipStreamSynchronize(ctx->stream));
+    ++num_step;
+    if (llk) std::memcpy(llk, static_cast<const char*>(h_stage_) + o_res_, sizeof(double) * total);
+    return VB2_OK;
+}
+
+int Conditioned::eval(const int32_t* num_point, const double* pc1, const double* pc2, const double* alpha, double* llk)
+{
+    const int rc = eval_begin(num_point, pc1, pc2, alpha);
+    if (rc) {
+        (void)eval_end(nullptr);           // whatever reached the stream has left the stages when this returns
+        return rc;
+    }
+    if (pending_ && !llk) {
+        (void)eval_end(nullptr);
+        set_error("vb2_conditioned_eval: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    return eval_end(llk);
+}
+
+namespace {
+struct TimerEvents {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~TimerEvents()
+    {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+};
+}  // namespace
+
+int Conditioned::time_launch(int num_point, int warmup, int reps, double* ms)
+{
+    if (num_point < 1 || num_point > kMaxPointsPerLaunch || num_point > num_hyp * VB2_BATCH_SLOTS || warmup < 0 || reps < 1 || !ms ||
+        ctx->resident_active || pending_) {
+        set_error("time_launch: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    VB2_HIP_C(hipSetDevice(ctx->device));
+    const int k = ctx->num_pc, n = 2 * k + 1;
+    char* const hp = static_cast<char*>(h_stage_);
+    char* const dp = static_cast<char*>(d_stage_);
+    double* const h_rows = reinterpret_cast<double*>(hp);
+    int32_t* const h_idx = reinterpret_cast<int32_t*>(hp + o_hyp_);
+    for (int p = 0; p < num_point; ++p) {
+        for (int j = 0; j < 2 * k; ++j) h_rows[(size_t)p * n + j] = 0.01;
+        h_rows[(size_t)p * n + 2 * k] = 0.03;
+        h_idx[p] = p % num_hyp;
+    }
+    hipStream_t s = ctx->stream;
+    VB2_HIP_C(hipMemcpyAsync(dp, hp, sizeof(double) * (size_t)num_point * n, hipMemcpyHostToDevice, s));
+    VB2_HIP_C(hipMemcpyAsync(dp + o_hyp_, hp + o_hyp_, sizeof(int32_t) * (size_t)num_point, hipMemcpyHostToDevice, s));
+    TimerEvents ev;
+    VB2_HIP_C(hipEventCreate(&ev.a));
+    VB2_HIP_C(hipEventCreate(&ev.b));
+    for (int r = -warmup; r < reps; ++r) {
+        VB2_HIP_C(hipEventRecord(ev.a, s));
+        VB2_HIP_C(launch_llk_conditioned(ctx->L, num_point, reinterpret_cast<const double*>(dp), reinterpret_cast<const int32_t*>(dp + o_hyp_), d_planes_,
+                     reinterpret_cast<double*>(dp + o_part_), reinterpret_cast<double*>(dp + o_res_), s));
+        VB2_HIP_C(hipEventRecord(ev.b, s));
+        VB2_HIP_C(hipEventSynchronize(ev.b));
+        float t = 0.0f;
+        VB2_HIP_C(hipEventElapsedTime(&t, ev.a, ev.b));
+        if (r >= 0) ms[r] = (double)t;
+    }
+    return VB2_OK;
+}
+
+namespace {
+// what a hypothesis's Estimator calls: pc1 replaced by the fixed row, the gang's evaluator, and a look at the first values
+struct Wrap {
+    void* gang_user = nullptr;
+    const double* fixed = nullptr;
+    int k = 0;
+    bool first = true, empty = false;
+    std::vector<double> p1;                // (not on the fiber's stack: alive while the request is parked)
+};
+int wrap_eval(void* user, int32_t n, const double*, const double* p2, const double* a, double* o)
+{
+    Wrap* w = static_cast<Wrap*>(user);
+    w->p1.resize((size_t)std::max(n, 0) * (size_t)w->k);
+    for (int i = 0; i < n; ++i) std::memcpy(&w->p1[(size_t)i * w->k], w->fixed, sizeof(double) * w->k);
+    if (const int rc = FiberGang::eval_cb(w->gang_user, n, w->p1.data(), p2, a, o)) return rc;
+    if (w->first) {
+        w->first = false;
+        bool all_zero = n > 0;
+        for (int i = 0; i < n; ++i) all_zero = all_zero && o[i] == 0.0;
+        if (all_zero) {
+            w->empty = true;
+            return VB2_ERR_INVALID;
+        }
+    }
+    return 0;
+}
+}  // namespace
+
+int conditioned_lockstep(ConditionedStep fn, void* user, int num_hyp, int num_pc, const uint8_t* known_af, const vb2_model& model,
+                         const double* pc1_fixed, const int32_t* fixed_row, vb2_estimate* est, int32_t* status)
+{
+    const int H = num_hyp, k = num_pc;
+    if (model.is_alpha_fixed) {
+        set_error("vb2_conditioned_optimize_llk: a fixed alpha leaves the refit nothing to estimate (--FixAlpha)");
+        return VB2_ERR_INVALID;
+    }
+    FiberGang gang(H, VB2_BATCH_SLOTS);
+    std::vector<Wrap> wraps(H);
+    vb2_model homo = model;                    // pc1 = pc2 = v, the reference's start, llk0 at alpha = 0
+    homo.is_heter = 0;
+    homo.notices = 0;                          // (the reference's phase lines belong to the run's own search)
+    homo.verbose = 0;
+    auto body = [&](int i) {
+        wraps[i].gang_user = gang.user(i);
+        wraps[i].fixed = pc1_fixed + (size_t)(fixed_row ? fixed_row[i] : i) * k;
+        wraps[i].k = k;
+        FiberGang::Search cfg;
+        cfg.model = &homo;
+        cfg.data_has_known_af = known_af && known_af[i];
+        cfg.eval = wrap_eval;
+        cfg.eval_user = &wraps[i];
+        std::memset(&est[i], 0, sizeof(est[i]));
+        status[i] = gang.search(i, cfg, "vb2_conditioned_optimize_llk", &est[i]);
+    };
+    std::vector<int32_t> npt(H);
+    std::vector<double> p1, p2, al, vals;
+    auto step = [&](std::vector<FiberGang::Request>& req) {
+        p1.clear(); p2.clear(); al.clear();
+        for (int h = 0; h < H; ++h) {
+            const FiberGang::Request& q = req[h];
+            npt[h] = q.n > 0 ? q.n : 0;
+            if (q.n <= 0) continue;
+            p1.insert(p1.end(), q.p1, q.p1 + (size_t)q.n * k);
+            p2.insert(p2.end(), q.p2, q.p2 + (size_t)q.n * k);
+            al.insert(al.end(), q.a, q.a + q.n);
+        }
+        vals.assign(al.size(), 0.0);
+        if (const int rc = fn(user, npt.data(), p1.data(), p2.data(), al.data(), vals.data())) return rc;
+        size_t o = 0;
+        for (int h = 0; h < H; ++h) {
+            if (req[h].n <= 0) continue;
+            std::memcpy(req[h].out, &vals[o], sizeof(double) * req[h].n);
+            o += (size_t)req[h].n;
+        }
+        return 0;
+    };
+    const int rc = gang.run(k, body, step);
+    if (rc) return rc;
+    for (int h = 0; h < H; ++h) {
+        if (wraps[h].empty) {
+            status[h] = VB2_ERR_INVALID;
+            set_error("vb2_conditioned_optimize_llk: the sample counts no marker under a hypothesis");
+        }
+    }
+    return VB2_OK;
+}
+
+namespace {
+struct SetsStep {
+    Conditioned* const* sets;
+    int num_set, k;
+};
+int sets_step(void* user, const int32_t* num_point, const double* pc1, const double* pc2, const double* alpha, double* llk)
+{
+    const SetsStep* S = static_cast<const SetsStep*>(user);
+    const int k = S->k;
+    // begin every set with live points, then collect: sets on different contexts overlap on the device
+    std::vector<size_t> at((size_t)S->num_set + 1, 0);
+    int rc = VB2_OK, hyp = 0, begun = 0;
+    for (int s = 0; s < S->num_set; ++s) {
+        size_t n = 0;
+        for (int h = 0; h < S->sets[s]->num_hyp; ++h) n += (size_t)num_point[hyp + h];
+        at[(size_t)s + 1] = at[(size_t)s] + n;
+        hyp += S->sets[s]->num_hyp;
+    }
+    hyp = 0;
+    for (int s = 0; s < S->num_set && !rc; ++s) {
+        const size_t o = at[(size_t)s];
+        if (at[(size_t)s + 1] > o) rc = S->sets[s]->eval_begin(num_point + hyp, pc1 + o * k, pc2 + o * k, alpha + o);
+        hyp += S->sets[s]->num_hyp;
+        begun = s + 1;
+    }
+    for (int s = 0; s < begun; ++s) {
+        const int re = S->sets[s]->eval_end(rc ? nullptr : llk + at[(size_t)s]);
+        if (!rc) rc = re;
+    }
+    return rc;
+}
+}  // namespace
+
+int conditioned_optimize(Conditioned* const* sets, int num_set, const vb2_model& model, const double* pc1_fixed,
+                         vb2_estimate* est, int32_t* status)
+{
+    if (!sets || num_set < 1 || !pc1_fixed || !est || !status) {
+        set_error("vb2_conditioned_optimize_llk: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    int H = 0;
+    for (int s = 0; s < num_set; ++s) {
+        if (!sets[s] || !sets[s]->ctx) {
+            set_error("vb2_conditioned_optimize_llk: invalid argument");
+            return VB2_ERR_INVALID;
+        }
+        if (sets[s]->ctx->num_pc != sets[0]->ctx->num_pc) {
+            set_error("vb2_conditioned_optimize_llk: the sets' contexts differ in the number of PCs");
+            return VB2_ERR_INVALID;
+        }
+        if (sets[s]->ctx->resident_active) {
+            set_error("vb2_conditioned_optimize_llk: not inside vb2_ctx_search_begin / vb2_ctx_search_end");
+            return VB2_ERR_INVALID;
+        }
+        for (int t = 0; t < s; ++t)
+            if (sets[t] == sets[s]) {
+                set_error("vb2_conditioned_optimize_llk: a set is listed twice");
+                return VB2_ERR_INVALID;
+            }
+        H += sets[s]->num_hyp;
+    }
+    std::vector<uint8_t> kaf((size_t)H);
+    std::vector<int32_t> row((size_t)H);
+    int h = 0;
+    for (int s = 0; s < num_set; ++s)
+        for (int j = 0; j < sets[s]->num_hyp; ++j, ++h) {
+            kaf[(size_t)h] = sets[s]->ctx->L.known_af != nullptr;
+            row[(size_t)h] = s;
+        }
+    SetsStep S{sets, num_set, sets[0]->ctx->num_pc};
+    return conditioned_lockstep(sets_step, &S, H, S.k, kaf.data(), model, pc1_fixed, row.data(), est, status);
+}
+
+}  // namespace vb2
+
+using vb2::set_error;
+
+namespace {
+template <class F>
+int guarded(F&& f)
+{
+    try {
+        return f();
+    } catch (const std::bad_alloc&) {
+        set_error("out of host memory");
+        return VB2_ERR_NOMEM;
+    } catch (const std::exception& e) {
+        set_error(e.what());
+        return VB2_ERR_INVALID;
+    }
+}
+}  // namespace
+
+extern "C" {
+
+int vb2_conditioned_create(vb2_ctx* ctx, int32_t num_hyp, const float* prior, vb2_conditioned** out)
+{
+    if (!out) {
+        set_error("vb2_conditioned_create: out is NULL");
+        return VB2_ERR_INVALID;
+    }
+    *out = nullptr;
+    if (!ctx || !ctx->impl) {
+        set_error("null vb2_ctx");
+        return VB2_ERR_INVALID;
+    }
+    return guarded([&]() -> int {
+        vb2::Conditioned* c = nullptr;
+        if (const int rc = vb2::Conditioned::create(ctx->impl, num_hyp, prior, &c)) return rc;
+        *out = new vb2_conditioned{c};
+        return VB2_OK;
+    });
+}
+
+int vb2_conditioned_create_from_set(vb2_ctx* ctx, vb2_source_set* set, int32_t num_hyp, const int32_t* candidate,
+                                    vb2_conditioned** out)
+{
+    if (!out) {
+        set_error("vb2_conditioned_create_from_set: out is NULL");
+        return VB2_ERR_INVALID;
+    }
+    *out = nullptr;
+    if (!ctx || !ctx->impl || !set || !set->impl) {
+        set_error("vb2_conditioned_create_from_set: null vb2_ctx or vb2_source_set");
+        return VB2_ERR_INVALID;
+    }
+    return guarded([&]() -> int {
+        vb2::Conditioned* c = nullptr;
+        if (const int rc = vb2::Conditioned::create_from_set(ctx->impl, set->impl, num_hyp, candidate, &c)) return rc;
+        *out = new vb2_conditioned{c};
+        return VB2_OK;
+    });
+}
+
+void vb2_conditioned_destroy(vb2_conditioned* cond)
+{
+    if (!cond) return;
+    delete cond->impl;
+    delete cond;
+}
+
+int vb2_conditioned_eval(vb2_conditioned* cond, const int32_t* num_point, const double* pc1, const double* pc2, const double* alpha,
+                         double* llk_out)
+{
+    if (!cond || !cond->impl) {
+        set_error("null vb2_conditioned");
+        return VB2_ERR_INVALID;
+    }
+    return cond->impl->eval(num_point, pc1, pc2, alpha, llk_out);
+}
+
+int vb2_conditioned_optimize_llk(vb2_conditioned* const* sets, int32_t num_set, const vb2_model* model, const double* pc1_fixed,
+                                 vb2_estimate* est_out, int32_t* status)
+{
+    if (!sets || num_set < 1 || !model) {
+        set_error("vb2_conditioned_optimize_llk: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    return guarded([&]() -> int {
+        std::vector<vb2::Conditioned*> impl((size_t)num_set);
+        for (int s = 0; s < num_set; ++s) {
+            if (!sets[s] || !sets[s]->impl) {
+                set_error("null vb2_conditioned");
+                return VB2_ERR_INVALID;
+            }
+            impl[(size_t)s] = sets[s]->impl;
+        }
+        return vb2::conditioned_optimize(impl.data(), num_set, *model, pc1_fixed, est_out, status);
+    });
+}
+
+int vb2_debug_conditioned_time(vb2_conditioned* cond, int32_t num_point, int32_t warmup, int32_t reps, double* ms)
+{
+    if (!cond || !cond->impl) return VB2_ERR_INVALID;
+    return cond->impl->time_launch(num_point, warmup, reps, ms);
+}
+
+int vb2_conditioned_info_get(const vb2_conditioned* cond, vb2_conditioned_info* info)
+{
+    if (!cond || !cond->impl || !info) return VB2_ERR_INVALID;
+    const vb2::Conditioned& c = *cond->impl;
+    info->num_hyp = c.num_hyp;
+    info->num_marker = c.ctx->num_marker;
+    info->device_bytes = c.device_bytes;
+    info->num_step = c.num_step;
+    info->num_launch = c.num_launch;
+    return VB2_OK;
+}
+
+namespace {
+struct SeamStep {
+    vb2_conditioned_eval_fn fn;
+    void* user;
+    int num_hyp;
+};
+int seam_step(void* user, const int32_t* num_point, const double* pc1, const double* pc2, const double* alpha, double* llk)
+{
+    const SeamStep* s = static_cast<const SeamStep*>(user);
+    return s->fn(s->user, s->num_hyp, num_point, pc1, pc2, alpha, llk);
+}
+}  // namespace
+
+int vb2_conditioned_lockstep(vb2_conditioned_eval_fn fn, void* user, int32_t num_hyp, int32_t num_pc, const vb2_model* model,
+                             const double* pc1_fixed, vb2_estimate* est_out, int32_t* status)
+{
+    if (!fn || !model || !pc1_fixed || !est_out || !status || num_hyp < 1 || num_pc < 1 || num_pc > VB2_MAX_PC) {
+        set_error("vb2_conditioned_lockstep: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    return guarded([&]() -> int {
+        SeamStep s{fn, user, num_hyp};
+        return vb2::conditioned_lockstep(seam_step, &s, num_hyp, num_pc, nullptr, *model, pc1_fixed, nullptr, est_out, status);
+    });
+}
+
+}  // extern "C"

@@ -186,6 +186,54 @@ int Replicates::eval(const int32_t* num_point, const double* pc1, const double* 
 }
 
 namespace {
+struct TimerEvents {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~TimerEvents()
+    {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+};
+}  // namespace
+
+int Replicates::time_launch(int num_point, int warmup, int reps, double* ms)
+{
+    if (num_point < 1 || num_point > kMaxPointsPerLaunch || num_point > cap_ || warmup < 0 || reps < 1 || !ms ||
+        ctx->resident_active) {
+        set_error("time_launch: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    VB2_HIP_R(hipSetDevice(ctx->device));
+    const int k = ctx->num_pc, n = 2 * k + 1;
+    char* const hp = static_cast<char*>(h_stage_);
+    char* const dp = static_cast<char*>(d_stage_);
+    double* const h_rows = reinterpret_cast<double*>(hp);
+    int32_t* const h_idx = reinterpret_cast<int32_t*>(hp + o_row_);
+    for (int p = 0; p < num_point; ++p) {
+        for (int j = 0; j < 2 * k; ++j) h_rows[(size_t)p * n + j] = 0.01;
+        h_rows[(size_t)p * n + 2 * k] = 0.03;
+        h_idx[p] = p % num_rep;
+    }
+    hipStream_t s = ctx->stream;
+    VB2_HIP_R(hipMemcpyAsync(dp, hp, sizeof(double) * (size_t)num_point * n, hipMemcpyHostToDevice, s));
+    VB2_HIP_R(hipMemcpyAsync(dp + o_row_, hp + o_row_, sizeof(int32_t) * (size_t)num_point, hipMemcpyHostToDevice, s));
+    TimerEvents ev;
+    VB2_HIP_R(hipEventCreate(&ev.a));
+    VB2_HIP_R(hipEventCreate(&ev.b));
+    for (int r = -warmup; r < reps; ++r) {
+        VB2_HIP_R(hipEventRecord(ev.a, s));
+        VB2_HIP_R(launch_llk_weighted(ctx->L, num_point, reinterpret_cast<const double*>(dp), reinterpret_cast<const int32_t*>(dp + o_row_), d_weights_,
+                     reinterpret_cast<double*>(dp + o_part_), reinterpret_cast<double*>(dp + o_res_), s));
+        VB2_HIP_R(hipEventRecord(ev.b, s));
+        VB2_HIP_R(hipEventSynchronize(ev.b));
+        float t = 0.0f;
+        VB2_HIP_R(hipEventElapsedTime(&t, ev.a, ev.b));
+        if (r >= 0) ms[r] = (double)t;
+    }
+    return VB2_OK;
+}
+
+namespace {
 // what a replicate's Estimator calls: the gang's evaluator, and a look at the first values it returns
 struct Probe {
     void* gang_user = nullptr;
@@ -390,6 +438,12 @@ int vb2_replicates_optimize_llk(vb2_replicates* rep, const vb2_model* model, vb2
         set_error(e.what());
         return VB2_ERR_INVALID;
     }
+}
+
+int vb2_debug_replicates_time(vb2_replicates* rep, int32_t num_point, int32_t warmup, int32_t reps, double* ms)
+{
+    if (!rep || !rep->impl) return VB2_ERR_INVALID;
+    return rep->impl->time_launch(num_point, warmup, reps, ms);
 }
 
 int vb2_replicates_info_get(const vb2_replicates* rep, vb2_replicates_info* info, int64_t* counted)

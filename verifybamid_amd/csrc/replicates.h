@@ -27,6 +27,9 @@ public:
     int eval(const int32_t* num_point, const double* pc1, const double* pc2, const double* alpha, double* llk);
     // one OptimizeLLK per replicate under `model`, all advancing in lock-step, each step one eval()
     int optimize(const vb2_model& model, vb2_estimate* est, int32_t* status);
+    // Measurement aid (tools/conditioned_time.py; event-timed, milliseconds per repetition into ms[reps]): ONE launch pair
+    // of num_point <= kMaxPointsPerLaunch points (pc = 0.01, alpha = 0.03), point p under weight row p % num_rep.
+    int time_launch(int num_point, int warmup, int reps, double* ms);
 
     Context* ctx = nullptr;
     int num_rep = 0;

@@ -383,6 +383,29 @@ int write_sources(const std::string& prefix, int n, int top, const char* const* 
     return VB2_OK;
 }
 
+int write_source_fit(const std::string& prefix, int n, const char* const* names, const vb2_source_fit* fit)
+{
+    const std::string name(prefix + ".SourceFit");
+    std::FILE* f = std::fopen(name.c_str(), "w");
+    if (!f) {
+        set_error("cannot write " + name);
+        return VB2_ERR_IO;
+    }
+    std::fprintf(f, "#SAMPLE\tCANDIDATE\tLLR\tMARKERS\tFREEMIX\tFREELK1\tALPHA_GIVEN\tLK1_GIVEN\tLK0_GIVEN\tDELTA_LK\n");
+    for (int i = 0; i < n; ++i) {
+        const vb2_source_fit& s = fit[i];
+        if (s.candidate < 0 || s.candidate >= n) continue;
+        std::fprintf(f, "%s\t%s\t%g\t%d\t%g\t%g", names[i], names[s.candidate], s.llr, (int)s.markers, s.freemix, s.freelk1);
+        if (s.status == VB2_OK) std::fprintf(f, "\t%g\t%g\t%g\t%g\n", s.alpha_given, s.lk1_given, s.lk0_given, s.delta_lk);
+        else std::fprintf(f, "\tNA\tNA\tNA\tNA\n");
+    }
+    if (std::fclose(f) != 0) {
+        set_error("cannot write " + name);
+        return VB2_ERR_IO;
+    }
+    return VB2_OK;
+}
+
 }  // namespace vb2
 
 using vb2::set_error;

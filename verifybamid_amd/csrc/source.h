@@ -24,6 +24,16 @@ public:
     void set_count(int n);
     int count();
     int scores(double* score, int32_t* shared);
+    // what a set of hypotheses reads of a sample (conditioned.cpp): the q plane [num_marker][3] of the slot's device row,
+    // nullptr = the slot holds none
+    int device() const { return device_; }
+    int num_marker() const { return num_marker_; }
+    const float* q_row(int slot)
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        if (slot < 0 || slot >= capacity_ || !rows_[(size_t)slot]) return nullptr;
+        return rows_[(size_t)slot] + 3 * (size_t)num_marker_;
+    }
     // Measurement aids (tools/source_time.py; event-timed, milliseconds per repetition into ms[reps]): the pair kernels
     // over n synthetic rows (seeded non-negative triples; what was in the set is overwritten), and the marginal kernel of
     // a context into slot 0 (the row's memset included, as an add pays it).
@@ -41,6 +51,9 @@ private:
 // <prefix>.Sources (vb2_cohort_run_sources): per sample its `top` best candidates by descending score
 int write_sources(const std::string& prefix, int n, int top, const char* const* names, const vb2_run_result* res,
                   const int32_t* status, const double* score, const int32_t* shared);
+
+// <prefix>.SourceFit (vb2_cohort_run_source_fits): per searched sample with a first candidate the refit given it
+int write_source_fit(const std::string& prefix, int n, const char* const* names, const vb2_source_fit* fit);
 
 }  // namespace vb2
 

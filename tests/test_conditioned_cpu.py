@@ -255,9 +255,10 @@ def test_the_seeded_cohort_gives_what_the_gpu_suite_asserts():
 
 
 def test_conditioned_kernels_fit_the_weighted_kernels_budget():
-    """Note-only, like tests/test_replicates_cpu.py: the six llk_conditioned_marker_kernel instantiations, the reduction and
-    the permutation live in one code object, use no scratch memory, the weighted kernels' LDS, and each
-    marker kernel at most 8 VGPRs more than the weighted kernel of the same layout and --NumPC selection."""
+    """Note-only, like tests/test_replicates_cpu.py: the six prior-term instantiations of llk_sum_marker_kernel
+    (marker_sum_kernels.hip), the reduction and the permutation live in one code object -- the weight term's --, use no
+    scratch memory, the weight term's LDS, and each marker kernel at most 8 VGPRs more than the weight-term kernel of the
+    same layout and --NumPC selection."""
     import test_kernel_resources_cpu as res
     import isa_diff
     if not os.path.exists(res.LIB):
@@ -267,25 +268,28 @@ def test_conditioned_kernels_fit_the_weighted_kernels_budget():
     notes = res.all_kernel_notes(res.LIB)
     short = lambda name: re.search(r"(\w+_kernel(<[^>]*>)?)\(", name).group(1)
     mine = {short(k[1]): (k[0], v) for k, v in notes.items()
-            if re.search(r"llk_conditioned_(marker|reduce)_kernel|prior_permute_kernel", k[1])}
-    theirs = {short(k[1]): v for k, v in notes.items() if re.search(r"llk_weighted_(marker|reduce)_kernel", k[1])}
+            if re.search(r"llk_sum_marker_kernel<[^>]*PriorTerm|llk_sum_reduce_kernel|prior_permute_kernel", k[1])}
+    theirs = {short(k[1]): (k[0], v) for k, v in notes.items() if re.search(r"llk_sum_marker_kernel<[^>]*WeightTerm", k[1])}
+    twin_of = lambda name: theirs.get(name.replace("PriorTerm", "WeightTerm"), (None, None))
     for name, (obj, v) in sorted(mine.items()):
-        twin = theirs.get(name.replace("llk_conditioned_", "llk_weighted_"), {}).get("vgpr_count", -1)
+        twin = (twin_of(name)[1] or {}).get("vgpr_count", -1)
         print("%4d VGPRs (weighted: %4d) %5d B scratch  %s  [%s]" % (v["vgpr_count"], twin, v["private_segment_fixed_size"], name, obj))
-    marker = sorted(n for n in mine if n.startswith("llk_conditioned_marker_kernel<"))
+    marker = sorted(n for n in mine if n.startswith("llk_sum_marker_kernel<"))
     assert len(marker) == 6, marker                      # PD x KSEL 0, 2, 4
-    assert len(mine) == 8 and len({obj for obj, _ in mine.values()}) == 1, sorted(mine)
+    assert len(mine) == 8 and len({obj for obj, _ in mine.values()} | {obj for obj, _ in theirs.values()}) == 1, sorted(mine)
     for name, (_, v) in mine.items():
         assert v["private_segment_fixed_size"] == 0, name
-        twin = theirs.get(name.replace("llk_conditioned_", "llk_weighted_"))
+        twin = twin_of(name)[1]
         if twin is None:
             continue
         assert v["vgpr_count"] <= twin["vgpr_count"] + 8, (name, v["vgpr_count"], twin["vgpr_count"])
-    assert sum(1 for n in marker if n.replace("llk_conditioned_", "llk_weighted_") in theirs) == 6
-    # LDS: the table and the tree are dynamic, sized by the launcher with the weighted kernel's own expression (at most 189
-    # rows x 48 B + 2 KB = 11 KB); the marker kernel declares no other shared memory, and nothing in the unit is atomic
+    assert sum(1 for n in marker if twin_of(n)[1] is not None) == 6
+    # LDS: the table and the tree are dynamic, sized by the one launcher of both terms (at most 189 rows x 48 B + 2 KB =
+    # 11 KB); the marker kernel declares no other shared memory, and nothing in the unit or the walk it includes is atomic
     csrc = os.path.join(ROOT, "verifybamid_amd", "csrc")
-    src, ref = (open(os.path.join(csrc, n + "_kernels.hip")).read() for n in ("conditioned", "weighted"))
+    src, walk = (open(os.path.join(csrc, n)).read() for n in ("marker_sum_kernels.hip", "marker_walk.h"))
     size = "const size_t shmem = ((size_t)nrow * kRowDoubles + kThreads) * sizeof(double);"
-    assert size in src and size in ref and "constexpr int kRowDoubles = 6;" in src and "constexpr int kThreads = 256;" in src
-    assert src.count("__shared__") == 2 and ref.count("__shared__") == 2 and "atomic" not in src.lower()
+    assert src.count(size) == 1 and src.count("constexpr int kRowDoubles = 6;") == 1
+    assert walk.count("constexpr int kThreads = 256;") == 1 and "kThreads =" not in src
+    assert src.count("__shared__") == 2 and "__shared__" not in walk            # the marker kernel's table, the reduction's tree
+    assert "atomic" not in src.lower() and "atomic" not in walk.lower()

@@ -1,4 +1,4 @@
-"""The likelihood given a hypothesised contaminant on the MI355X (conditioned_kernels.hip, conditioned.cpp; DESIGN.md section
+"""The likelihood given a hypothesised contaminant on the MI355X (marker_sum_kernels.hip, conditioned.cpp; DESIGN.md section
 13): vb2_conditioned_eval against the np.longdouble restatement (tests/conditioned_ref.py) in both layouts, the KSEL-compiled
 and the general --NumPC, a known-AF column, every kind of hypothesis row and of step; the bits of a point whatever the step
 holds; create_from_set against create; the lock-step refits against the same searches on the float64 restatement through

@@ -184,8 +184,9 @@ def test_the_planted_chromosome_stands_out_for_the_oracle():
 
 
 def test_weighted_kernels_use_no_scratch():
-    """Note-only, like tests/test_kernel_resources_cpu.py: the six llk_weighted_marker_kernel instantiations, the reduction
-    and the permutation of libvb2.so live in one code object, use no scratch memory and fit 128 VGPRs."""
+    """Note-only, like tests/test_kernel_resources_cpu.py: the six weight-term instantiations of llk_sum_marker_kernel
+    (marker_sum_kernels.hip), the reduction and the permutation of libvb2.so live in one code object, use no scratch memory
+    and fit 128 VGPRs."""
     import test_kernel_resources_cpu as res
     import isa_diff
     if not os.path.exists(res.LIB):
@@ -193,11 +194,12 @@ def test_weighted_kernels_use_no_scratch():
     if not all(os.path.exists(isa_diff.LLVM + t) for t in ("llvm-objdump", "llvm-readelf")):
         pytest.skip("the ROCm binutils are not installed")
     notes = res.all_kernel_notes(res.LIB)
-    mine = {k: v for k, v in notes.items() if re.search(r"llk_weighted_(marker|reduce)_kernel|weights_permute_kernel", k[1])}
+    mine = {k: v for k, v in notes.items()
+            if re.search(r"llk_sum_marker_kernel<[^>]*WeightTerm|llk_sum_reduce_kernel|weights_permute_kernel", k[1])}
     short = lambda name: re.search(r"(\w+_kernel(<[^>]*>)?)\(", name).group(1)
     for k, v in sorted(mine.items()):
         print("%4d VGPRs %5d B scratch  %s  [%s]" % (v["vgpr_count"], v["private_segment_fixed_size"], short(k[1]), k[0]))
-    marker = {short(k[1]) for k in mine if "llk_weighted_marker_kernel<" in k[1]}
+    marker = {short(k[1]) for k in mine if "llk_sum_marker_kernel<" in k[1]}
     assert len(marker) == 6, marker                      # PD x KSEL 0, 2, 4
     assert len(mine) == 8 and len({k[0] for k in mine}) == 1, sorted(mine)
     over = {short(k[1]): v for k, v in mine.items() if v["private_segment_fixed_size"] != 0 or v["vgpr_count"] > 128}

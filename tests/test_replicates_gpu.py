@@ -1,4 +1,4 @@
-"""Weighted-marker replicates on the MI355X (weighted_kernels.hip, replicates.cpp): vb2_replicates_eval against the pinned
+"""Weighted-marker replicates on the MI355X (marker_sum_kernels.hip, replicates.cpp): vb2_replicates_eval against the pinned
 oracle on EXPANDED inputs (tests/replicate_ref.py) in both layouts, the KSEL-compiled and the general --NumPC, a known-AF
 column, every kind of weight row and of step; the bits of a point whatever the step holds; the lock-step searches against
 the oracle's under three models; and --PerChromosome / --Bootstrap through the files.

@@ -1,7 +1,7 @@
 """What the likelihood given a hypothesised contaminant costs on one MI355X:
-  (1) a 48-point launch pair of llk_conditioned_marker_kernel + its reduction at 100 000 x 30, k = 4, in both layouts, beside
-      the yardstick: llk_weighted_marker_kernel (weighted_kernels.hip) on the SAME context with all-ones weight rows -- the
-      two bodies differ by three float loads and a select.  HIP events around the launches (vb2_debug_conditioned_time /
+  (1) a 48-point launch pair of llk_sum_marker_kernel under the prior term (marker_sum_kernels.hip) + its reduction at
+      100 000 x 30, k = 4, in both layouts, beside the yardstick: the same kernel under the weight term on the SAME context
+      with all-ones weight rows -- the two terms differ by three float loads and a select.  HIP events around the launches (vb2_debug_conditioned_time /
       vb2_debug_replicates_time), after a warm-up; the two are timed in alternating rounds and medians reported, with the
       spread of the rounds' medians.
   (2) the wall-clock --RefitSource adds to a cohort run (32 samples x 100 000 x 30, k = 4, 8 of them contaminated at 5 % by

@@ -11,21 +11,13 @@
 #include <limits>
 #include <memory>
 
+#include "device_util.h"
 #include "estimator.h"
 #include "lockstep.h"
 #include "stream_search.h"
 #include "tunables.h"
 
 namespace vb2 {
-
-#define VB2_HIP(call)                                                                  \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            set_error(std::string(#call) + " failed: " + hipGetErrorString(e_));       \
-            return VB2_ERR_HIP;                                                        \
-        }                                                                              \
-    } while (0)
 
 namespace {
 constexpr int kSlot = 8;                     // point slots per sample and step (VB2_BATCH_SLOTS)

@@ -1,4 +1,4 @@
-// conditioned.cpp -- host side of the likelihood given a hypothesised contaminant (conditioned_kernels.hip; DESIGN.md section
+// conditioned.cpp -- host side of the likelihood given a hypothesised contaminant (marker_sum_kernels.hip; DESIGN.md section
 // 13): the set of hypotheses on a context, its evaluation in two halves, and the refits in lock-step.
 #include "conditioned.h"
 
@@ -11,45 +11,17 @@
 #include <string>
 #include <vector>
 
-#include "conditioned_kernels.h"
 #include "context.h"
+#include "device_util.h"
 #include "lockstep.h"
+#include "marker_sum_kernels.h"
 #include "source.h"
 
 namespace vb2 {
 
-#define VB2_HIP_C(call)                                                                \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            set_error(std::string(#call) + " failed: " + hipGetErrorString(e_));       \
-            return VB2_ERR_HIP;                                                        \
-        }                                                                              \
-    } while (0)
-
 namespace {
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// a device slab from the cache, or a fresh one
-int take_device(size_t bytes, int device, void** p, size_t* got)
-{
-    *p = cached_device_slab(bytes, device, got);
-    if (!*p) {
-        if (hipMalloc(p, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            *p = nullptr;
-            set_error("vb2_conditioned_create: " + std::to_string(bytes) + " bytes of device memory do not fit");
-            return VB2_ERR_NOMEM;
-        }
-        *got = bytes;
-    }
-    return VB2_OK;
+const char* const kNoMemWho = "vb2_conditioned_create";   // (whichever way the set is made)
 }
-void give_device(void* p, size_t bytes, int device)
-{
-    if (p && !recycle_device_slab(p, bytes, device)) (void)hipFree(p);
-}
-}  // namespace
 
 int Conditioned::make(Context* ctx, int num_hyp, const char* who, Conditioned** out)
 {
@@ -66,24 +38,15 @@ int Conditioned::make(Context* ctx, int num_hyp, const char* who, Conditioned** 
     c->ctx = ctx;
     c->num_hyp = num_hyp;
     const DeviceLayout& L = ctx->L;
-    VB2_HIP_C(hipSetDevice(ctx->device));
+    VB2_HIP(hipSetDevice(ctx->device));
     if (const int rc = ctx->ensure_pidx()) return rc;
-    const int k = ctx->num_pc;
-    const size_t cap = (size_t)num_hyp * VB2_BATCH_SLOTS;
-    // stage: rows [cap][2k+1] | hypothesis indices [cap] | results [cap]; on the device also a launch's partial sums
-    c->o_hyp_ = up256(sizeof(double) * cap * (size_t)(2 * k + 1));
-    c->o_res_ = up256(c->o_hyp_ + sizeof(int32_t) * cap);
-    c->o_part_ = up256(c->o_res_ + sizeof(double) * cap);
-    const size_t part_bytes = sizeof(double) * (size_t)kMaxPointsPerLaunch * (size_t)std::max(1, conditioned_tile_groups(L));
     const size_t plane_bytes = std::max<size_t>(sizeof(float) * conditioned_hyp_floats(L) * (size_t)num_hyp, 256);
-    if (const int rc = take_device(plane_bytes, ctx->device, reinterpret_cast<void**>(&c->d_planes_), &c->d_planes_bytes_)) return rc;
-    if (const int rc = take_device(c->o_part_ + part_bytes, ctx->device, &c->d_stage_, &c->d_stage_bytes_)) return rc;
-    c->h_stage_ = cached_pinned_slab(c->o_part_, ctx->device, &c->h_stage_bytes_);
-    if (!c->h_stage_) {
-        VB2_HIP_C(hipHostMalloc(&c->h_stage_, c->o_part_, hipHostMallocMapped));
-        c->h_stage_bytes_ = c->o_part_;
-    }
-    c->device_bytes = (int64_t)(c->d_planes_bytes_ + c->d_stage_bytes_);
+    if (const int rc = take_device(plane_bytes, ctx->device, reinterpret_cast<void**>(&c->d_planes_), &c->d_planes_bytes_, kNoMemWho))
+        return rc;
+    if (const int rc = c->stage_.create(ctx, (size_t)num_hyp * VB2_BATCH_SLOTS,
+                                        (size_t)kMaxPointsPerLaunch * (size_t)std::max(1, marker_sum_tile_groups(L)), kNoMemWho))
+        return rc;
+    c->device_bytes = (int64_t)(c->d_planes_bytes_ + c->stage_.device_bytes());
     *out = c.release();
     return VB2_OK;
 }
@@ -102,7 +65,7 @@ int Conditioned::create(Context* ctx, int num_hyp, const float* prior, Condition
     const size_t bytes = sizeof(float) * 3 * (size_t)ctx->num_marker * (size_t)num_hyp;
     void* d_panel = nullptr;
     size_t d_panel_bytes = 0;
-    if (const int rc = take_device(std::max<size_t>(bytes, 256), ctx->device, &d_panel, &d_panel_bytes)) return rc;
+    if (const int rc = take_device(std::max<size_t>(bytes, 256), ctx->device, &d_panel, &d_panel_bytes, kNoMemWho)) return rc;
     hipError_t e = hipMemcpyAsync(d_panel, prior, bytes, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess)
         e = launch_prior_permute(ctx->L, ctx->num_marker, num_hyp, static_cast<const float*>(d_panel), ctx->d_pidx, c->d_planes_,
@@ -159,25 +122,29 @@ Conditioned::~Conditioned()
 {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
-    if (pending_) (void)hipStreamSynchronize(ctx->stream);
+    // a begun evaluation reads the planes: it has to be over before they are given back, and the stage's own destructor,
+    // which would wait for it as well, runs after this body
+    (void)stage_.end(nullptr);
     give_device(d_planes_, d_planes_bytes_, ctx->device);
-    give_device(d_stage_, d_stage_bytes_, ctx->device);
-    if (h_stage_ && !recycle_pinned_slab(h_stage_, h_stage_bytes_, ctx->device)) (void)hipHostFree(h_stage_);
+}
+
+PointStage::Launch Conditioned::launcher() const
+{
+    return [this](int c, const double* d_rows, const int32_t* d_hyp, double* d_partial, double* d_out, hipStream_t s) {
+        return launch_llk_conditioned(ctx->L, c, d_rows, d_hyp, d_planes_, d_partial, d_out, s);
+    };
 }
 
 int Conditioned::eval_begin(const int32_t* num_point, const double* pc1, const double* pc2, const double* alpha)
 {
-    if (!num_point || pending_) {
+    if (!num_point || stage_.pending()) {
         set_error("vb2_conditioned_eval: invalid argument");
         return VB2_ERR_INVALID;
     }
     size_t total = 0;
-    for (int h = 0; h < num_hyp; ++h) {
-        if (num_point[h] < 0 || num_point[h] > VB2_BATCH_SLOTS) {
-            set_error("vb2_conditioned_eval: a hypothesis's point count outside 0..VB2_BATCH_SLOTS");
-            return VB2_ERR_INVALID;
-        }
-        total += (size_t)num_point[h];
+    if (!PointStage::count(num_hyp, num_point, &total)) {
+        set_error("vb2_conditioned_eval: a hypothesis's point count outside 0..VB2_BATCH_SLOTS");
+        return VB2_ERR_INVALID;
     }
     if (total == 0) return VB2_OK;
     if (!pc1 || !pc2 || !alpha) {
@@ -188,49 +155,11 @@ int Conditioned::eval_begin(const int32_t* num_point, const double* pc1, const d
         set_error("vb2_conditioned_eval: not inside vb2_ctx_search_begin / vb2_ctx_search_end");
         return VB2_ERR_INVALID;
     }
-    VB2_HIP_C(hipSetDevice(ctx->device));
-    const int k = ctx->num_pc, n = 2 * k + 1;
-    char* const hp = static_cast<char*>(h_stage_);
-    char* const dp = static_cast<char*>(d_stage_);
-    double* const h_rows = reinterpret_cast<double*>(hp);
-    int32_t* const h_hyp = reinterpret_cast<int32_t*>(hp + o_hyp_);
-    size_t p = 0;
-    for (int h = 0; h < num_hyp; ++h)
-        for (int b = 0; b < num_point[h]; ++b, ++p) {
-            double* row = h_rows + p * n;
-            std::memcpy(row, pc1 + p * k, sizeof(double) * k);
-            std::memcpy(row + k, pc2 + p * k, sizeof(double) * k);
-            row[2 * k] = alpha[p];
-            h_hyp[p] = h;
-        }
-    // one upload, a launch pair per kMaxPointsPerLaunch points on the stream (the partial sums are stream-ordered), one
-    // download; the synchronisation is eval_end's
-    hipStream_t s = ctx->stream;
-    pending_ = total;                      // (from here on the stream may hold work on the stages)
-    VB2_HIP_C(hipMemcpyAsync(dp, hp, sizeof(double) * total * n, hipMemcpyHostToDevice, s));
-    VB2_HIP_C(hipMemcpyAsync(dp + o_hyp_, hp + o_hyp_, sizeof(int32_t) * total, hipMemcpyHostToDevice, s));
-    for (size_t done = 0; done < total; done += kMaxPointsPerLaunch) {
-        const int c = (int)std::min<size_t>(kMaxPointsPerLaunch, total - done);
-        VB2_HIP_C(launch_llk_conditioned(ctx->L, c, reinterpret_cast<const double*>(dp) + done * n,
-                                         reinterpret_cast<const int32_t*>(dp + o_hyp_) + done, d_planes_,
-                                         reinterpret_cast<double*>(dp + o_part_), reinterpret_cast<double*>(dp + o_res_) + done, s));
-        ++num_launch;
-    }
-    VB2_HIP_C(hipMemcpyAsync(hp + o_res_, dp + o_res_, sizeof(double) * total, hipMemcpyDeviceToHost, s));
-    return VB2_OK;
+    // the synchronisation is eval_end's
+    return stage_.begin(num_hyp, num_point, total, pc1, pc2, alpha, launcher());
 }
 
-int Conditioned::eval_end(double* llk)
-{
-    if (!pending_) return VB2_OK;
-    const size_t total = pending_;
-    pending_ = 0;
-    VB2_HIP_C(hipSetDevice(ctx->device));
-    VB2_HIP_C(hipStreamSynchronize(ctx->stream));
-    ++num_step;
-    if (llk) std::memcpy(llk, static_cast<const char*>(h_stage_) + o_res_, sizeof(double) * total);
-    return VB2_OK;
-}
+int Conditioned::eval_end(double* llk) { return stage_.end(llk); }
 
 int Conditioned::eval(const int32_t* num_point, const double* pc1, const double* pc2, const double* alpha, double* llk)
 {
@@ -239,7 +168,7 @@ int Conditioned::eval(const int32_t* num_point, const double* pc1, const double*
         (void)eval_end(nullptr);           // whatever reached the stream has left the stages when this returns
         return rc;
     }
-    if (pending_ && !llk) {
+    if (stage_.pending() && !llk) {
         (void)eval_end(nullptr);
         set_error("vb2_conditioned_eval: invalid argument");
         return VB2_ERR_INVALID;
@@ -247,52 +176,9 @@ int Conditioned::eval(const int32_t* num_point, const double* pc1, const double*
     return eval_end(llk);
 }
 
-namespace {
-struct TimerEvents {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~TimerEvents()
-    {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-    }
-};
-}  // namespace
-
 int Conditioned::time_launch(int num_point, int warmup, int reps, double* ms)
 {
-    if (num_point < 1 || num_point > kMaxPointsPerLaunch || num_point > num_hyp * VB2_BATCH_SLOTS || warmup < 0 || reps < 1 || !ms ||
-        ctx->resident_active || pending_) {
-        set_error("time_launch: invalid argument");
-        return VB2_ERR_INVALID;
-    }
-    VB2_HIP_C(hipSetDevice(ctx->device));
-    const int k = ctx->num_pc, n = 2 * k + 1;
-    char* const hp = static_cast<char*>(h_stage_);
-    char* const dp = static_cast<char*>(d_stage_);
-    double* const h_rows = reinterpret_cast<double*>(hp);
-    int32_t* const h_idx = reinterpret_cast<int32_t*>(hp + o_hyp_);
-    for (int p = 0; p < num_point; ++p) {
-        for (int j = 0; j < 2 * k; ++j) h_rows[(size_t)p * n + j] = 0.01;
-        h_rows[(size_t)p * n + 2 * k] = 0.03;
-        h_idx[p] = p % num_hyp;
-    }
-    hipStream_t s = ctx->stream;
-    VB2_HIP_C(hipMemcpyAsync(dp, hp, sizeof(double) * (size_t)num_point * n, hipMemcpyHostToDevice, s));
-    VB2_HIP_C(hipMemcpyAsync(dp + o_hyp_, hp + o_hyp_, sizeof(int32_t) * (size_t)num_point, hipMemcpyHostToDevice, s));
-    TimerEvents ev;
-    VB2_HIP_C(hipEventCreate(&ev.a));
-    VB2_HIP_C(hipEventCreate(&ev.b));
-    for (int r = -warmup; r < reps; ++r) {
-        VB2_HIP_C(hipEventRecord(ev.a, s));
-        VB2_HIP_C(launch_llk_conditioned(ctx->L, num_point, reinterpret_cast<const double*>(dp), reinterpret_cast<const int32_t*>(dp + o_hyp_), d_planes_,
-                     reinterpret_cast<double*>(dp + o_part_), reinterpret_cast<double*>(dp + o_res_), s));
-        VB2_HIP_C(hipEventRecord(ev.b, s));
-        VB2_HIP_C(hipEventSynchronize(ev.b));
-        float t = 0.0f;
-        VB2_HIP_C(hipEventElapsedTime(&t, ev.a, ev.b));
-        if (r >= 0) ms[r] = (double)t;
-    }
-    return VB2_OK;
+    return stage_.time_launch(num_point, num_hyp, warmup, reps, ms, launcher());
 }
 
 namespace {
@@ -566,8 +452,8 @@ int vb2_conditioned_info_get(const vb2_conditioned* cond, vb2_conditioned_info* 
     info->num_hyp = c.num_hyp;
     info->num_marker = c.ctx->num_marker;
     info->device_bytes = c.device_bytes;
-    info->num_step = c.num_step;
-    info->num_launch = c.num_launch;
+    info->num_step = c.num_step();
+    info->num_launch = c.num_launch();
     return VB2_OK;
 }
 

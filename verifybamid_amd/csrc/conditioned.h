@@ -1,5 +1,5 @@
 // conditioned.h -- the likelihood given a hypothesised contaminant: per-marker genotype priors
-// ("hypotheses") over ONE resident sample, evaluated together (conditioned_kernels.hip) and refitted in lock-step
+// ("hypotheses") over ONE resident sample, evaluated together (marker_sum_kernels.hip) and refitted in lock-step
 // (lockstep.h).  vb2_conditioned_* of the C-ABI.
 #ifndef VB2_CONDITIONED_H_
 #define VB2_CONDITIONED_H_
@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/vb2_abi.h"
+#include "point_stage.h"
 
 namespace vb2 {
 
@@ -38,19 +39,17 @@ public:
     Context* ctx = nullptr;
     int num_hyp = 0;
     int64_t device_bytes = 0;              // what the set holds in device memory
-    int64_t num_step = 0, num_launch = 0;  // evaluations that reached the device, and their marker launches
+    // evaluations that reached the device, and their marker launches
+    int64_t num_step() const { return stage_.num_step; }
+    int64_t num_launch() const { return stage_.num_launch; }
 
 private:
     Conditioned() {}
     static int make(Context* ctx, int num_hyp, const char* who, Conditioned** out);   // everything but the planes' content
+    PointStage::Launch launcher() const;
     float* d_planes_ = nullptr;
     size_t d_planes_bytes_ = 0;
-    void* d_stage_ = nullptr;
-    size_t d_stage_bytes_ = 0;
-    void* h_stage_ = nullptr;              // pinned: rows | hypothesis indices | results
-    size_t h_stage_bytes_ = 0;
-    size_t o_hyp_ = 0, o_res_ = 0, o_part_ = 0;   // offsets into the stages (o_part_: device only)
-    size_t pending_ = 0;                   // points of a begun evaluation
+    PointStage stage_;                     // num_hyp * VB2_BATCH_SLOTS points; the indices: hypotheses
 };
 
 // The refits of every hypothesis of every set in ONE gang (vb2_conditioned_optimize_llk).

@@ -20,52 +20,31 @@
 //     A point's results are the single-sample kernels' bits.
 #include "deriv_kernels.h"
 
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "marker_walk.h"
 
 namespace vb2 {
 namespace {
 
-constexpr int kThreads = 256;                     // 16 micro-tiles of 16 markers per pass of a workgroup
+using namespace walk;
+
 constexpr int kEntry = 3;                         // {value, d, d^2} per (row, pair)
 constexpr int kPairDoubles = 6 * kEntry;
 constexpr int kRowDoublesPd = kPairDoubles;       // probability domain: the six off-diagonal pairs
 constexpr int kRowDoublesLog = kPairDoubles + 3;  // log domain: and log u_g of the diagonal pairs (g, g)
-constexpr double kMinAf = 0.00005, kMaxAf = 0.99995;   // h:94-95
 
-// off-diagonal genotype pairs, in the reference's (g1 outer, g2 inner) order (as llk_kernels.hip numbers them)
-__device__ __forceinline__ void pair_g(int p, int& g1, int& g2)
+// entry_of and d = (u_g1 - u_g2) / p = dp/dalpha / p, 0 where p = 0
+__device__ __forceinline__ void entry_d_of(double alpha, double p_err, int g1, int g2, double& p, double& d)
 {
-    g1 = p >> 1;
-    const int lo = p & 1;
-    g2 = lo + (lo >= g1 ? 1 : 0);
-}
-
-// h:223-224 for one class / quality / pair: p = alpha u_g1 + (1 - alpha) u_g2 (the reference's expression order) and
-// d = (u_g1 - u_g2) / p = dp/dalpha / p, 0 where p = 0; a negative p (alpha outside [0, 1]) is NaN.  The class is ref; alt
-// reads the pair mirrored (g -> 2 - g, h:164-177).
-__device__ __forceinline__ void entry_of(double alpha, double p_err, int g1, int g2, double& p, double& d)
-{
-    const double p_ok = 1.0 - p_err;
-    const double e1 = (double)g1 * (1.0 / 6.0), e2 = (double)g2 * (1.0 / 6.0);
-    const double n1 = 1.0 - 0.5 * (double)g1, n2 = 1.0 - 0.5 * (double)g2;
-    const double one_minus_alpha = 1.0 - alpha;
-    p = (alpha * e1 + one_minus_alpha * e2) * p_err + (alpha * n1 + one_minus_alpha * n2) * p_ok;
-    p = p >= 0.0 ? p : __builtin_nan("");          // alpha outside [0, 1]: NaN, the marker is left out (as prob_entry)
-    const double u1 = e1 * p_err + n1 * p_ok, u2 = e2 * p_err + n2 * p_ok;
-    d = p != 0.0 ? (u1 - u2) / p : 0.0;
+    p = entry_of(alpha, p_err, g1, g2);
+    d = p != 0.0 ? (diag_entry_of(p_err, g1) - diag_entry_of(p_err, g2)) / p : 0.0;
 }
 
 // GF (h:186-192) and its first two derivatives in AF; both 0 where the reference clamps AF (the branch it takes)
 __device__ __forceinline__ void gf_derivs(double af, bool fixed, double* gf, double* d1, double* d2)
 {
     const bool clamped = af < kMinAf || af > kMaxAf || fixed;
-    if (af < kMinAf) af = kMinAf;
-    if (af > kMaxAf) af = kMaxAf;
-    gf[0] = (1 - af) * (1 - af);
-    gf[1] = 2 * (af) * (1 - af);
-    gf[2] = af * af;
+    af = clamp_af(af);
+    gf_of(af, gf);
     d1[0] = clamped ? 0.0 : -2.0 * (1.0 - af);
     d1[1] = clamped ? 0.0 : 2.0 - 4.0 * af;
     d1[2] = clamped ? 0.0 : 2.0 * af;
@@ -89,22 +68,18 @@ __device__ __forceinline__ void derivs_marker_body(const DeviceLayout& L, const 
     const size_t mp = (size_t)L.m_pad;
 
     // ---- the point's table ----
-    const int num_single = PD ? L.num_prim - L.num_pair : L.num_prim;
-    for (int e = tid; e < num_single * 6; e += kThreads) {
+    for (int e = tid; e < num_single<PD>(L) * 6; e += kThreads) {
         const int pi = e / 6, p = e - pi * 6;
-        const double2 rec = L.prim[pi];
-        const uint32_t pr = (uint32_t)__double_as_longlong(rec.y);
-        const int first = (int)(pr & 0xffffu), twin = (int)(pr >> 16);
+        const SingleRec rec = single_rec(L, pi);
         int g1, g2;
         pair_g(p, g1, g2);
         double v, d;
         if constexpr (PD) {
-            // record = a quality, class ref: {pErr, first row | K << 16 | rows from P^n to P^(n+1), a signed byte, << 24}
-            entry_of(alpha, rec.x, g1, g2, v, d);
-            const int kq = twin & 0xff, rstep = (int)(int8_t)(twin >> 8);
+            entry_d_of(alpha, rec.p_err, g1, g2, v, d);
+            const int kq = rec.kq(), rstep = rec.rstep();
             double r = v;
             for (int n = 1; n <= kq; ++n) {
-                const int row = first + (n - 1) * rstep;
+                const int row = rec.first + (n - 1) * rstep;
                 if (row >= 0 && row < nrow) {
                     double* c = tab + (size_t)row * kRowDoubles + p * kEntry;
                     c[0] = r;
@@ -114,61 +89,46 @@ __device__ __forceinline__ void derivs_marker_body(const DeviceLayout& L, const 
                 r *= v;
             }
         } else {
-            // record = a code: {signed pErr (alt < 0), code | twin << 16}; the alt twin's row is this one mirrored (pair 5 - p)
-            if (rec.x < 0.0) { g1 = 2 - g1; g2 = 2 - g2; }
-            entry_of(alpha, fabs(rec.x), g1, g2, v, d);
+            if (rec.alt()) { g1 = 2 - g1; g2 = 2 - g2; }
+            entry_d_of(alpha, fabs(rec.p_err), g1, g2, v, d);
             const double lv = log(v);
-            if (first < nrow) {
-                double* c = tab + (size_t)first * kRowDoubles + p * kEntry;
+            if (rec.first < nrow) {
+                double* c = tab + (size_t)rec.first * kRowDoubles + p * kEntry;
                 c[0] = lv; c[1] = d; c[2] = d * d;
             }
-            if (twin != 0xffff && twin < nrow) {
-                double* c = tab + (size_t)twin * kRowDoubles + (5 - p) * kEntry;
+            if (rec.has_twin() && rec.twin < nrow) {
+                double* c = tab + (size_t)rec.twin * kRowDoubles + (5 - p) * kEntry;
                 c[0] = lv; c[1] = d; c[2] = d * d;
             }
         }
     }
     if constexpr (!PD) {
         // the diagonal pairs: p = alpha u_g + (1 - alpha) u_g = u_g whatever alpha; an alt code reads the genotype mirrored
-        for (int e = tid; e < num_single * 3; e += kThreads) {
+        for (int e = tid; e < num_single<PD>(L) * 3; e += kThreads) {
             const int pi = e / 3, g = e - pi * 3;
-            const double2 rec = L.prim[pi];
-            const uint32_t pr = (uint32_t)__double_as_longlong(rec.y);
-            const int first = (int)(pr & 0xffffu), twin = (int)(pr >> 16);
-            const double p_err = fabs(rec.x), p_ok = 1.0 - p_err;
-            const double lu = log((double)g * (1.0 / 6.0) * p_err + (1.0 - 0.5 * (double)g) * p_ok);
-            if (first < nrow) tab[(size_t)first * kRowDoubles + kPairDoubles + (rec.x < 0.0 ? 2 - g : g)] = lu;
-            if (twin != 0xffff && twin < nrow) tab[(size_t)twin * kRowDoubles + kPairDoubles + (2 - g)] = lu;
+            const SingleRec rec = single_rec(L, pi);
+            const double lu = log(diag_entry_of(fabs(rec.p_err), g));
+            if (rec.first < nrow) tab[(size_t)rec.first * kRowDoubles + kPairDoubles + (rec.alt() ? 2 - g : g)] = lu;
+            if (rec.has_twin() && rec.twin < nrow) tab[(size_t)rec.twin * kRowDoubles + kPairDoubles + (2 - g)] = lu;
         }
     }
     for (int e = tid; e < kRowDoubles; e += kThreads)           // padding row: P = 1 (log domain: 0), no derivative
         tab[(size_t)L.num_code * kRowDoubles + e] = (PD && e % kEntry == 0) ? 1.0 : 0.0;
-    if constexpr (PD) {
-        // window rows: the product of two rows -- the value multiplies, d and d^2 add (level 1 uses rows of level 0)
-        for (int level = 0; level < 2; ++level) {
-            const int nrec = level == 0 ? L.num_pair - L.num_pair2 : L.num_pair2;
-            const int base = num_single + (level == 0 ? 0 : L.num_pair - L.num_pair2);
-            __syncthreads();
-            for (int e = tid; e < nrec * 6; e += kThreads) {
-                const int pi = e / 6, p = e - pi * 6;
-                const double2 rec = L.prim[base + pi];
-                const uint32_t ab = (uint32_t)__double_as_longlong(rec.x), dst = (uint32_t)__double_as_longlong(rec.y);
-                const uint32_t ra = ab & 0xffffu, rb = ab >> 16;
-                if (ra >= (uint32_t)nrow || rb >= (uint32_t)nrow || dst >= (uint32_t)nrow) continue;
-                const double* a = tab + (size_t)ra * kRowDoubles + p * kEntry;
-                const double* b = tab + (size_t)rb * kRowDoubles + p * kEntry;
-                double* c = tab + (size_t)dst * kRowDoubles + p * kEntry;
-                c[0] = a[0] * b[0];
-                c[1] = a[1] + b[1];
-                c[2] = a[2] + b[2];
-            }
-        }
-    }
+    if constexpr (PD)
+        // window rows: the value multiplies, d and d^2 add
+        for_each_window<6>(L, nrow, tid, [&](uint32_t ra, uint32_t rb, uint32_t dst, int p) {
+            const double* a = tab + (size_t)ra * kRowDoubles + p * kEntry;
+            const double* b = tab + (size_t)rb * kRowDoubles + p * kEntry;
+            double* c = tab + (size_t)dst * kRowDoubles + p * kEntry;
+            c[0] = a[0] * b[0];
+            c[1] = a[1] + b[1];
+            c[2] = a[2] + b[2];
+        });
     __syncthreads();
 
     // ---- one thread per marker of the sorted order ----
     const int m = tid & 15;
-    const int ntile_grp = (L.num_mt + 15) / 16;
+    const int ntile_grp = tile_groups(L);
     for (int tg = bx; tg < ntile_grp; tg += nbx) {
         const int mt = tg * 16 + (tid >> 4);
         if (mt >= L.num_mt) continue;
@@ -182,6 +142,9 @@ __device__ __forceinline__ void derivs_marker_body(const DeviceLayout& L, const 
         double acc[6], a1[6], a2[6], dacc[3];
         for (int p = 0; p < 6; ++p) { acc[p] = PD ? 1.0 : L.ediag[pos]; a1[p] = 0.0; a2[p] = 0.0; }
         for (int g = 0; g < 3; ++g) dacc[g] = PD ? 0.0 : L.ediag[pos];     // log domain: c_other + D[g], summed here
+        // The walk is written out here, not for_each_step of marker_walk.h: through it the scheduler issues a step's 18 LDS
+        // reads in fewer groups and the probability-domain kernels take 8 more VGPRs (156 -> 164 and 154 -> 162: the last
+        // granule that still gives three waves per SIMD).
         if constexpr (PD) {
             // {ref steps | all steps << 16}; a step = a 16-bit byte offset of its row (+ kPdAltOffset for class alt), two per word
             const uint32_t s1 = rec.y & 0xffffu, s2 = rec.y >> 16;
@@ -245,7 +208,7 @@ __device__ __forceinline__ void derivs_marker_body(const DeviceLayout& L, const 
         double W[3][3], WA[3][3], WB[3][3];
         const double cst = PD ? L.ediag[pos] : 0.0;
         for (int g = 0; g < 3; ++g) { W[g][g] = L.ediag[(size_t)(1 + g) * mp + pos]; WA[g][g] = 0.0; WB[g][g] = 0.0; }
-        double lk = 0.0;         // L itself, in the reference's order (h:307-309): what decides whether the marker counts
+        double lk;               // L itself, in the reference's order (h:307-309): what decides whether the marker counts
         double scale = 0.0;      // log domain: W relative to exp(scale), so that the ratios survive deep markers
         if constexpr (!PD) {
             double amax = -__builtin_huge_val();
@@ -273,8 +236,7 @@ __device__ __forceinline__ void derivs_marker_body(const DeviceLayout& L, const 
         }
         if constexpr (!PD)
             for (int g = 0; g < 3; ++g) W[g][g] = exp(dacc[g] - scale);     // (Wu keeps the context's constant: L as evaluated)
-        for (int g1 = 0; g1 < 3; ++g1)
-            for (int g2 = 0; g2 < 3; ++g2) lk += Wu[g1][g2] * G1[g1] * G2[g2];
+        lk = mix_of(Wu, G1, G2);
         double v[kDerivVals];
         for (int j = 0; j < kDerivVals; ++j) v[j] = 0.0;
         if (lk > 0) {
@@ -341,7 +303,7 @@ llk_derivs_marker_multi_kernel(const DerivJob* __restrict__ jobs)
     extern __shared__ __attribute__((aligned(16))) double tab[];      // sized for the widest dictionary of the launch
     const DerivJob& job = jobs[blockIdx.z];
     if ((int)blockIdx.y >= job.num_point) return;
-    if ((int)blockIdx.x >= (job.L.num_mt + 15) / 16) return;
+    if ((int)blockIdx.x >= tile_groups(job.L)) return;
     derivs_marker_body<PD>(job.L, job.points, job.marker, tab, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x);
 }
 
@@ -398,11 +360,7 @@ __device__ __forceinline__ void derivs_reduce_body(const DeviceLayout& L, const 
             sum += w;
         }
     part[tid] = sum;
-    __syncthreads();
-    for (int h = kThreads / 2; h > 0; h >>= 1) {
-        if (tid < h) part[tid] += part[tid + h];
-        __syncthreads();
-    }
+    tree_sum(part, tid);
     if (tid == 0) out[(size_t)pt * deriv_out_count(k) + e] = part[0] * f;
 }
 
@@ -432,12 +390,7 @@ hipError_t launch_llk_derivs(const DeviceLayout& L, int num_point, const double*
     if (num_point > kDerivChunk) return hipErrorInvalidValue;
     const int nrow = L.num_code + 1;
     const size_t shmem = (size_t)nrow * (L.pd ? kRowDoublesPd : kRowDoublesLog) * sizeof(double);
-    const int ntile_grp = (L.num_mt + 15) / 16;
-    // about four workgroups per CU over the whole launch; each walks a stripe of 16-tile groups with one table
-    int gx = (4 * (L.num_cu > 0 ? L.num_cu : 1) + num_point - 1) / num_point;
-    gx = gx < ntile_grp ? gx : ntile_grp;
-    gx = gx > 0 ? gx : 1;
-    const dim3 grid((unsigned)gx, (unsigned)num_point), block(kThreads);
+    const dim3 grid((unsigned)stripe_grid(L, num_point), (unsigned)num_point), block(kThreads);
     if (L.pd)
         hipLaunchKernelGGL(llk_derivs_marker_kernel<true>, grid, block, shmem, stream, L, d_points, d_marker);
     else
@@ -478,7 +431,7 @@ hipError_t launch_llk_derivs_multi(const DerivJob* h_jobs, const DerivJob* d_job
             const DeviceLayout& L = h_jobs[j].L;
             const size_t need = (size_t)(L.num_code + 1) * (L.pd ? kRowDoublesPd : kRowDoublesLog) * sizeof(double);
             shmem = need > shmem ? need : shmem;
-            const int grp = (L.num_mt + 15) / 16;
+            const int grp = tile_groups(L);
             max_grp = grp > max_grp ? grp : max_grp;
         }
         const int gx = gx_all < max_grp ? gx_all : max_grp;

@@ -10,28 +10,20 @@
 #include "batch.h"
 #include "context.h"
 #include "deriv_kernels.h"
+#include "device_util.h"
 
 namespace vb2 {
-
-#define VB2_HIP_D(call)                                                                \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            set_error(std::string(#call) + " failed: " + hipGetErrorString(e_));       \
-            return VB2_ERR_HIP;                                                        \
-        }                                                                              \
-    } while (0)
 
 // scratch: once per context, through the slab cache ([chunk][kDerivVals][m_pad] | [chunk][2k+1] | [chunk][nout])
 int Context::ensure_deriv_scratch()
 {
-    VB2_HIP_D(hipSetDevice(device));
+    VB2_HIP(hipSetDevice(device));
     if (d_deriv) return VB2_OK;
     const size_t bytes = deriv_scratch_doubles(L) * sizeof(double);
     size_t got = 0;
     void* p = cached_device_slab(bytes, device, &got);
     if (!p) {
-        VB2_HIP_D(hipMalloc(&p, bytes));
+        VB2_HIP(hipMalloc(&p, bytes));
         got = bytes;
     }
     d_deriv = static_cast<double*>(p);
@@ -67,13 +59,13 @@ int Context::derivs_host(int num_point, const double* pc1, const double* pc2, co
     }
     for (int done = 0; done < num_point; done += kDerivChunk) {
         const int c = std::min(kDerivChunk, num_point - done);
-        VB2_HIP_D(hipMemcpyAsync(d_rows, rows.data() + (size_t)done * n, sizeof(double) * (size_t)c * n, hipMemcpyHostToDevice,
+        VB2_HIP(hipMemcpyAsync(d_rows, rows.data() + (size_t)done * n, sizeof(double) * (size_t)c * n, hipMemcpyHostToDevice,
                                  stream));
-        VB2_HIP_D(launch_llk_derivs(L, c, d_rows, d_marker, d_res, stream));
-        VB2_HIP_D(hipMemcpyAsync(res.data() + (size_t)done * nout, d_res, sizeof(double) * (size_t)c * nout,
+        VB2_HIP(launch_llk_derivs(L, c, d_rows, d_marker, d_res, stream));
+        VB2_HIP(hipMemcpyAsync(res.data() + (size_t)done * nout, d_res, sizeof(double) * (size_t)c * nout,
                                  hipMemcpyDeviceToHost, stream));
     }
-    VB2_HIP_D(hipStreamSynchronize(stream));
+    VB2_HIP(hipStreamSynchronize(stream));
     for (int pb = 0; pb < num_point; ++pb) {
         const double* r = res.data() + (size_t)pb * nout;
         llk[pb] = r[0];
@@ -104,7 +96,7 @@ struct DerivStage {
 
 int Batch::ensure_deriv_resources()
 {
-    VB2_HIP_D(hipSetDevice(device));
+    VB2_HIP(hipSetDevice(device));
     for (Context* c : ctx_)
         if (c)
             if (const int rc = c->ensure_deriv_scratch()) return rc;
@@ -112,16 +104,16 @@ int Batch::ensure_deriv_resources()
     const DerivStage st(num_sample, num_pc);
     if (!stream_) {
         stream_ = cached_stream(device);
-        if (!stream_) VB2_HIP_D(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+        if (!stream_) VB2_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     }
     dv_dev_ = cached_device_slab(st.total, device, &dv_dev_bytes_);
     if (!dv_dev_) {
-        VB2_HIP_D(hipMalloc(&dv_dev_, st.total));
+        VB2_HIP(hipMalloc(&dv_dev_, st.total));
         dv_dev_bytes_ = st.total;
     }
     void* pin = cached_pinned_slab(st.total, device, &dv_pin_bytes_);
     if (!pin) {
-        VB2_HIP_D(hipHostMalloc(&pin, st.total, hipHostMallocMapped));
+        VB2_HIP(hipHostMalloc(&pin, st.total, hipHostMallocMapped));
         dv_pin_bytes_ = st.total;
     }
     dv_pin_ = pin;
@@ -194,11 +186,11 @@ int Batch::derivs(const int32_t* num_point, const double* pc1, const double* pc2
             }
         }
         const size_t up = st.o_rows + sizeof(double) * (size_t)nj * kDerivChunk * n;
-        VB2_HIP_D(hipMemcpyAsync(dp, hp, up, hipMemcpyHostToDevice, stream_));
-        VB2_HIP_D(launch_llk_derivs_multi(h_jobs, reinterpret_cast<const DerivJob*>(dp + st.o_jobs), nj, stream_));
-        VB2_HIP_D(hipMemcpyAsync(hp + st.o_res, dp + st.o_res, sizeof(double) * (size_t)nj * kDerivChunk * nout,
+        VB2_HIP(hipMemcpyAsync(dp, hp, up, hipMemcpyHostToDevice, stream_));
+        VB2_HIP(launch_llk_derivs_multi(h_jobs, reinterpret_cast<const DerivJob*>(dp + st.o_jobs), nj, stream_));
+        VB2_HIP(hipMemcpyAsync(hp + st.o_res, dp + st.o_res, sizeof(double) * (size_t)nj * kDerivChunk * nout,
                                  hipMemcpyDeviceToHost, stream_));
-        VB2_HIP_D(hipStreamSynchronize(stream_));
+        VB2_HIP(hipStreamSynchronize(stream_));
         ++num_deriv_step;
         for (int j = 0; j < nj; ++j) {
             const int s = who[j];

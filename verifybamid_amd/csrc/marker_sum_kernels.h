@@ -1,0 +1,38 @@
+// marker_sum_kernels.h -- launchers of the two per-marker sums over one resident sample (marker_sum_kernels.hip): the
+// weighted-marker evaluation and the likelihood conditioned on a hypothesised contaminant (section 13).
+#ifndef VB2_MARKER_SUM_KERNELS_H_
+#define VB2_MARKER_SUM_KERNELS_H_
+
+#include "llk_kernels.h"
+
+namespace vb2 {
+
+// tile groups (256 markers of the sorted order) of a layout: a point's partial sums, one per group
+int marker_sum_tile_groups(const DeviceLayout& L);
+// floats of one hypothesis in the sorted order: three planes of m_pad
+inline size_t conditioned_hyp_floats(const DeviceLayout& L) { return 3 * (size_t)L.m_pad; }
+
+// panel-order weight rows [num_rep][num_marker] -> the context's sorted order [num_rep][m_pad]; positions past the counted
+// markers (the tiles' padding) get 0.  pidx: sorted position -> panel marker (Context::ensure_pidx), [num_active].
+hipError_t launch_weights_permute(const DeviceLayout& L, int num_marker, int num_rep, const uint8_t* d_panel,
+                                  const int32_t* d_pidx, uint8_t* d_sorted, hipStream_t stream);
+
+// panel-order prior rows d_panel [num_hyp][num_marker][3] -> the context's sorted order as planes d_planes
+// [num_hyp][3][m_pad]; positions past the counted markers (the tiles' padding) and positions whose panel marker is out of
+// range get 0.  d_panel is an upload or the q plane of a source set's row (one hypothesis per call then).
+hipError_t launch_prior_permute(const DeviceLayout& L, int num_marker, int num_hyp, const float* d_panel, const int32_t* d_pidx,
+                                float* d_planes, hipStream_t stream);
+
+// LLK_w at num_point <= kMaxPointsPerLaunch points: rows d_points [num_point][2k+1] (pc1 | pc2 | alpha), d_row[p] the weight
+// row of point p in d_weights [..][m_pad].  d_partial: num_point * marker_sum_tile_groups(L) doubles of scratch; d_out
+// [num_point].  A point's value is the same bits whatever else the launch holds (one partial sum per tile group, then one
+// fixed-order sum).
+hipError_t launch_llk_weighted(const DeviceLayout& L, int num_point, const double* d_points, const int32_t* d_row,
+                               const uint8_t* d_weights, double* d_partial, double* d_out, hipStream_t stream);
+
+// LLK(. | h) the same way: d_hyp[p] the hypothesis of point p in d_planes [..][3][m_pad].
+hipError_t launch_llk_conditioned(const DeviceLayout& L, int num_point, const double* d_points, const int32_t* d_hyp,
+                                  const float* d_planes, double* d_partial, double* d_out, hipStream_t stream);
+
+}  // namespace vb2
+#endif

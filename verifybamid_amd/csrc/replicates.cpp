@@ -1,4 +1,4 @@
-// replicates.cpp -- host side of the weighted-marker replicates (weighted_kernels.hip): the replicate
+// replicates.cpp -- host side of the weighted-marker replicates (marker_sum_kernels.hip): the replicate
 // set on a context, its lock-step searches, the host-only helpers (chromosome and bootstrap weights, the delete-m_j
 // jackknife) and the file flow behind --PerChromosome / --Bootstrap.
 #include "replicates.h"
@@ -17,39 +17,12 @@
 #include <vector>
 
 #include "context.h"
+#include "device_util.h"
 #include "hostio.h"
 #include "lockstep.h"
-#include "weighted_kernels.h"
+#include "marker_sum_kernels.h"
 
 namespace vb2 {
-
-#define VB2_HIP_R(call)                                                                \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            set_error(std::string(#call) + " failed: " + hipGetErrorString(e_));       \
-            return VB2_ERR_HIP;                                                        \
-        }                                                                              \
-    } while (0)
-
-namespace {
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// a device slab from the cache, or a fresh one
-int take_device(size_t bytes, int device, void** p, size_t* got)
-{
-    *p = cached_device_slab(bytes, device, got);
-    if (!*p) {
-        VB2_HIP_R(hipMalloc(p, bytes));
-        *got = bytes;
-    }
-    return VB2_OK;
-}
-void give_device(void* p, size_t bytes, int device)
-{
-    if (p && !recycle_device_slab(p, bytes, device)) (void)hipFree(p);
-}
-}  // namespace
 
 int Replicates::create(Context* ctx, int num_rep, const uint8_t* weight, Replicates** out)
 {
@@ -80,26 +53,15 @@ int Replicates::create(Context* ctx, int num_rep, const uint8_t* weight, Replica
         if (i >= M) continue;
         for (int q = 0; q < num_rep; ++q) r->counted[q] += weight[(size_t)q * M + i] != 0;
     }
-    VB2_HIP_R(hipSetDevice(ctx->device));
+    VB2_HIP(hipSetDevice(ctx->device));
     if (const int rc = ctx->ensure_pidx()) return rc;
-    const int k = ctx->num_pc;
-    r->cap_ = num_rep * VB2_BATCH_SLOTS;
-    const size_t cap = (size_t)r->cap_;
-    // stage: rows [cap][2k+1] | weight-row indices [cap] | results [cap]; on the device also a launch's partial sums
-    r->o_row_ = up256(sizeof(double) * cap * (size_t)(2 * k + 1));
-    r->o_res_ = up256(r->o_row_ + sizeof(int32_t) * cap);
-    r->o_part_ = up256(r->o_res_ + sizeof(double) * cap);
-    const size_t part_bytes = sizeof(double) * (size_t)kMaxPointsPerLaunch * (size_t)std::max(1, weighted_tile_groups(L));
     if (const int rc = take_device(std::max<size_t>(mp * (size_t)num_rep, 256), ctx->device, reinterpret_cast<void**>(&r->d_weights_),
                                    &r->d_weights_bytes_))
         return rc;
-    if (const int rc = take_device(r->o_part_ + part_bytes, ctx->device, &r->d_stage_, &r->d_stage_bytes_)) return rc;
-    r->h_stage_ = cached_pinned_slab(r->o_part_, ctx->device, &r->h_stage_bytes_);
-    if (!r->h_stage_) {
-        VB2_HIP_R(hipHostMalloc(&r->h_stage_, r->o_part_, hipHostMallocMapped));
-        r->h_stage_bytes_ = r->o_part_;
-    }
-    r->device_bytes = (int64_t)(r->d_weights_bytes_ + r->d_stage_bytes_);
+    if (const int rc = r->stage_.create(ctx, (size_t)num_rep * VB2_BATCH_SLOTS,
+                                        (size_t)kMaxPointsPerLaunch * (size_t)std::max(1, marker_sum_tile_groups(L)), nullptr))
+        return rc;
+    r->device_bytes = (int64_t)(r->d_weights_bytes_ + r->stage_.device_bytes());
     // the panel-order rows go up once, into a slab that goes back to the cache when the permutation is done
     void* d_panel = nullptr;
     size_t d_panel_bytes = 0;
@@ -123,8 +85,13 @@ Replicates::~Replicates()
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     give_device(d_weights_, d_weights_bytes_, ctx->device);
-    give_device(d_stage_, d_stage_bytes_, ctx->device);
-    if (h_stage_ && !recycle_pinned_slab(h_stage_, h_stage_bytes_, ctx->device)) (void)hipHostFree(h_stage_);
+}
+
+PointStage::Launch Replicates::launcher() const
+{
+    return [this](int c, const double* d_rows, const int32_t* d_row_of, double* d_partial, double* d_out, hipStream_t s) {
+        return launch_llk_weighted(ctx->L, c, d_rows, d_row_of, d_weights_, d_partial, d_out, s);
+    };
 }
 
 int Replicates::eval(const int32_t* num_point, const double* pc1, const double* pc2, const double* alpha, double* llk)
@@ -134,12 +101,9 @@ int Replicates::eval(const int32_t* num_point, const double* pc1, const double* 
         return VB2_ERR_INVALID;
     }
     size_t total = 0;
-    for (int r = 0; r < num_rep; ++r) {
-        if (num_point[r] < 0 || num_point[r] > VB2_BATCH_SLOTS) {
-            set_error("vb2_replicates_eval: a replicate's point count outside 0..VB2_BATCH_SLOTS");
-            return VB2_ERR_INVALID;
-        }
-        total += (size_t)num_point[r];
+    if (!PointStage::count(num_rep, num_point, &total)) {
+        set_error("vb2_replicates_eval: a replicate's point count outside 0..VB2_BATCH_SLOTS");
+        return VB2_ERR_INVALID;
     }
     if (total == 0) return VB2_OK;
     if (!pc1 || !pc2 || !alpha || !llk) {
@@ -150,87 +114,16 @@ int Replicates::eval(const int32_t* num_point, const double* pc1, const double* 
         set_error("vb2_replicates_eval: not inside vb2_ctx_search_begin / vb2_ctx_search_end");
         return VB2_ERR_INVALID;
     }
-    VB2_HIP_R(hipSetDevice(ctx->device));
-    const int k = ctx->num_pc, n = 2 * k + 1;
-    char* const hp = static_cast<char*>(h_stage_);
-    char* const dp = static_cast<char*>(d_stage_);
-    double* const h_rows = reinterpret_cast<double*>(hp);
-    int32_t* const h_row_of = reinterpret_cast<int32_t*>(hp + o_row_);
-    const double* const h_res = reinterpret_cast<const double*>(hp + o_res_);
-    size_t p = 0;
-    for (int r = 0; r < num_rep; ++r)
-        for (int b = 0; b < num_point[r]; ++b, ++p) {
-            double* row = h_rows + p * n;
-            std::memcpy(row, pc1 + p * k, sizeof(double) * k);
-            std::memcpy(row + k, pc2 + p * k, sizeof(double) * k);
-            row[2 * k] = alpha[p];
-            h_row_of[p] = r;
-        }
-    // one upload, a launch pair per kMaxPointsPerLaunch points on the stream (the partial sums are stream-ordered), one
-    // download, one synchronisation
-    hipStream_t s = ctx->stream;
-    VB2_HIP_R(hipMemcpyAsync(dp, hp, sizeof(double) * total * n, hipMemcpyHostToDevice, s));
-    VB2_HIP_R(hipMemcpyAsync(dp + o_row_, hp + o_row_, sizeof(int32_t) * total, hipMemcpyHostToDevice, s));
-    for (size_t done = 0; done < total; done += kMaxPointsPerLaunch) {
-        const int c = (int)std::min<size_t>(kMaxPointsPerLaunch, total - done);
-        VB2_HIP_R(launch_llk_weighted(ctx->L, c, reinterpret_cast<const double*>(dp) + done * n,
-                                      reinterpret_cast<const int32_t*>(dp + o_row_) + done, d_weights_,
-                                      reinterpret_cast<double*>(dp + o_part_), reinterpret_cast<double*>(dp + o_res_) + done, s));
-        ++num_launch;
+    if (const int rc = stage_.begin(num_rep, num_point, total, pc1, pc2, alpha, launcher())) {
+        (void)stage_.end(nullptr);         // whatever reached the stream has left the stages when this returns
+        return rc;
     }
-    VB2_HIP_R(hipMemcpyAsync(hp + o_res_, dp + o_res_, sizeof(double) * total, hipMemcpyDeviceToHost, s));
-    VB2_HIP_R(hipStreamSynchronize(s));
-    ++num_step;
-    std::memcpy(llk, h_res, sizeof(double) * total);
-    return VB2_OK;
+    return stage_.end(llk);
 }
-
-namespace {
-struct TimerEvents {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~TimerEvents()
-    {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-    }
-};
-}  // namespace
 
 int Replicates::time_launch(int num_point, int warmup, int reps, double* ms)
 {
-    if (num_point < 1 || num_point > kMaxPointsPerLaunch || num_point > cap_ || warmup < 0 || reps < 1 || !ms ||
-        ctx->resident_active) {
-        set_error("time_launch: invalid argument");
-        return VB2_ERR_INVALID;
-    }
-    VB2_HIP_R(hipSetDevice(ctx->device));
-    const int k = ctx->num_pc, n = 2 * k + 1;
-    char* const hp = static_cast<char*>(h_stage_);
-    char* const dp = static_cast<char*>(d_stage_);
-    double* const h_rows = reinterpret_cast<double*>(hp);
-    int32_t* const h_idx = reinterpret_cast<int32_t*>(hp + o_row_);
-    for (int p = 0; p < num_point; ++p) {
-        for (int j = 0; j < 2 * k; ++j) h_rows[(size_t)p * n + j] = 0.01;
-        h_rows[(size_t)p * n + 2 * k] = 0.03;
-        h_idx[p] = p % num_rep;
-    }
-    hipStream_t s = ctx->stream;
-    VB2_HIP_R(hipMemcpyAsync(dp, hp, sizeof(double) * (size_t)num_point * n, hipMemcpyHostToDevice, s));
-    VB2_HIP_R(hipMemcpyAsync(dp + o_row_, hp + o_row_, sizeof(int32_t) * (size_t)num_point, hipMemcpyHostToDevice, s));
-    TimerEvents ev;
-    VB2_HIP_R(hipEventCreate(&ev.a));
-    VB2_HIP_R(hipEventCreate(&ev.b));
-    for (int r = -warmup; r < reps; ++r) {
-        VB2_HIP_R(hipEventRecord(ev.a, s));
-        VB2_HIP_R(launch_llk_weighted(ctx->L, num_point, reinterpret_cast<const double*>(dp), reinterpret_cast<const int32_t*>(dp + o_row_), d_weights_,
-                     reinterpret_cast<double*>(dp + o_part_), reinterpret_cast<double*>(dp + o_res_), s));
-        VB2_HIP_R(hipEventRecord(ev.b, s));
-        VB2_HIP_R(hipEventSynchronize(ev.b));
-        float t = 0.0f;
-        VB2_HIP_R(hipEventElapsedTime(&t, ev.a, ev.b));
-        if (r >= 0) ms[r] = (double)t;
-    }
-    return VB2_OK;
+    return stage_.time_launch(num_point, num_rep, warmup, reps, ms, launcher());
 }
 
 namespace {
@@ -453,8 +346,8 @@ int vb2_replicates_info_get(const vb2_replicates* rep, vb2_replicates_info* info
     info->num_rep = r.num_rep;
     info->num_marker = r.ctx->num_marker;
     info->device_bytes = r.device_bytes;
-    info->num_step = r.num_step;
-    info->num_launch = r.num_launch;
+    info->num_step = r.num_step();
+    info->num_launch = r.num_launch();
     if (counted) std::memcpy(counted, r.counted.data(), sizeof(int64_t) * (size_t)r.num_rep);
     return VB2_OK;
 }
@@ -626,7 +519,7 @@ int vb2_run_replicates(const vb2_run_args* args, int32_t per_chromosome, int32_t
         std::vector<vb2_estimate> est(R);
         std::vector<int32_t> status(R, 0);
         if (const int rc = rep->optimize(model, est.data(), status.data())) return rc;
-        sum.num_step = rep->num_step;
+        sum.num_step = rep->num_step();
         const double theta = vb2::freemix_of(whole);
         if (C > 0) {
             std::vector<int64_t> m(C);

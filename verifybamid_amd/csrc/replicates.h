@@ -1,5 +1,5 @@
 // replicates.h -- weighted-marker likelihood replicates: many integer weight vectors over ONE resident
-// sample, evaluated together (weighted_kernels.hip) and searched in lock-step (lockstep.h).  vb2_replicates_* of the C-ABI.
+// sample, evaluated together (marker_sum_kernels.hip) and searched in lock-step (lockstep.h).  vb2_replicates_* of the C-ABI.
 #ifndef VB2_REPLICATES_H_
 #define VB2_REPLICATES_H_
 
@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/vb2_abi.h"
+#include "point_stage.h"
 
 struct vb2_flat;
 
@@ -35,18 +36,16 @@ public:
     int num_rep = 0;
     std::vector<int64_t> counted;          // [num_rep] counted markers of the sample with a weight > 0
     int64_t device_bytes = 0;              // what the set holds in device memory
-    int64_t num_step = 0, num_launch = 0;  // eval() calls that reached the device, and their marker launches
+    // eval() calls that reached the device, and their marker launches
+    int64_t num_step() const { return stage_.num_step; }
+    int64_t num_launch() const { return stage_.num_launch; }
 
 private:
     Replicates() {}
+    PointStage::Launch launcher() const;
     uint8_t* d_weights_ = nullptr;
     size_t d_weights_bytes_ = 0;
-    void* d_stage_ = nullptr;
-    size_t d_stage_bytes_ = 0;
-    void* h_stage_ = nullptr;              // pinned: rows | weight-row indices | results
-    size_t h_stage_bytes_ = 0;
-    size_t o_row_ = 0, o_res_ = 0, o_part_ = 0;   // offsets into the stages (o_part_: device only)
-    int cap_ = 0;                          // points a step can hold: num_rep * VB2_BATCH_SLOTS
+    PointStage stage_;                     // num_rep * VB2_BATCH_SLOTS points; the indices: weight rows
 };
 
 // The lock-step driver over any evaluator of a step (vb2_replicates_lockstep; no device): replicate r's search is the

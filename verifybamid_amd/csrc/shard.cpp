@@ -14,18 +14,10 @@
 
 #include <rccl/rccl.h>       // types and prototypes only: the library is bound with dlopen below
 
+#include "device_util.h"
 #include "estimator.h"
 
 namespace vb2 {
-
-#define VB2_HIP(call)                                                                  \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            set_error(std::string(#call) + " failed: " + hipGetErrorString(e_));       \
-            return VB2_ERR_HIP;                                                        \
-        }                                                                              \
-    } while (0)
 
 namespace {
 

@@ -12,18 +12,10 @@
 #include <limits>
 #include <new>
 
+#include "device_util.h"
 #include "source_kernels.h"
 
 namespace vb2 {
-
-#define VB2_HIP_S(call)                                                                \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            set_error(std::string(#call) + " failed: " + hipGetErrorString(e_));       \
-            return VB2_ERR_HIP;                                                        \
-        }                                                                              \
-    } while (0)
 
 int Context::ensure_pidx()
 {
@@ -38,18 +30,18 @@ int Context::ensure_pidx()
         const int64_t a = h_perm[m];
         pidx[m] = a >= 0 && (size_t)a < h_active.size() ? h_active[(size_t)a] : -1;
     }
-    VB2_HIP_S(hipSetDevice(device));
+    VB2_HIP(hipSetDevice(device));
     const size_t bytes = na * sizeof(int32_t);
     size_t got = 0;
     void* p = cached_device_slab(bytes, device, &got);
     if (!p) {
-        VB2_HIP_S(hipMalloc(&p, bytes));
+        VB2_HIP(hipMalloc(&p, bytes));
         got = bytes;
     }
     d_pidx = static_cast<int32_t*>(p);
     d_pidx_bytes = got;
-    VB2_HIP_S(hipMemcpyAsync(d_pidx, pidx.data(), bytes, hipMemcpyHostToDevice, stream));
-    VB2_HIP_S(hipStreamSynchronize(stream));          // (a pageable source: gone when this returns)
+    VB2_HIP(hipMemcpyAsync(d_pidx, pidx.data(), bytes, hipMemcpyHostToDevice, stream));
+    VB2_HIP(hipStreamSynchronize(stream));          // (a pageable source: gone when this returns)
     return VB2_OK;
 }
 
@@ -64,11 +56,11 @@ int Context::marginals(const double* pc1, const double* pc2, double alpha, doubl
         set_error("vb2_ctx_marginals: not inside vb2_ctx_search_begin / vb2_ctx_search_end");
         return VB2_ERR_INVALID;
     }
-    VB2_HIP_S(hipSetDevice(device));
+    VB2_HIP(hipSetDevice(device));
     const int k = num_pc;
     const size_t M = (size_t)num_marker;
     const bool want_host = contam_lik || geno_post || log_l;
-    if (d_row) VB2_HIP_S(hipMemsetAsync(d_row, 0, sizeof(float) * kSourceRowFloats * M, stream));
+    if (d_row) VB2_HIP(hipMemsetAsync(d_row, 0, sizeof(float) * kSourceRowFloats * M, stream));
     // NaN parameters: no marker counts (context.h: params_hold_nan)
     const bool none = params_hold_nan(pc1, pc2, alpha, k, L.known_af != nullptr) || L.num_active == 0;
     double* d_c = nullptr;
@@ -78,14 +70,14 @@ int Context::marginals(const double* pc1, const double* pc2, double alpha, doubl
             size_t got = 0;
             void* p = cached_device_slab(bytes, device, &got);
             if (!p) {
-                VB2_HIP_S(hipMalloc(&p, bytes));
+                VB2_HIP(hipMalloc(&p, bytes));
                 got = bytes;
             }
             d_marg = p;
             d_marg_bytes = got;
         }
         d_c = static_cast<double*>(d_marg);
-        VB2_HIP_S(hipMemsetAsync(d_c, 0, 7 * M * sizeof(double), stream));
+        VB2_HIP(hipMemsetAsync(d_c, 0, 7 * M * sizeof(double), stream));
     }
     if (!none) {
         if (const int rc = ensure_pidx()) return rc;
@@ -93,19 +85,19 @@ int Context::marginals(const double* pc1, const double* pc2, double alpha, doubl
         std::memcpy(h_points, pc1, sizeof(double) * k);
         std::memcpy(h_points + k, pc2, sizeof(double) * k);
         h_points[2 * k] = alpha;
-        VB2_HIP_S(launch_source_marginals(L, num_marker, d_points, d_pidx, d_c, d_c ? d_c + 3 * M : nullptr,
+        VB2_HIP(launch_source_marginals(L, num_marker, d_points, d_pidx, d_c, d_c ? d_c + 3 * M : nullptr,
                                           d_c ? d_c + 6 * M : nullptr, d_row, stream));
     }
     if (want_host && !none) {
-        if (contam_lik) VB2_HIP_S(hipMemcpyAsync(contam_lik, d_c, 3 * M * sizeof(double), hipMemcpyDeviceToHost, stream));
-        if (geno_post) VB2_HIP_S(hipMemcpyAsync(geno_post, d_c + 3 * M, 3 * M * sizeof(double), hipMemcpyDeviceToHost, stream));
-        if (log_l) VB2_HIP_S(hipMemcpyAsync(log_l, d_c + 6 * M, M * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (contam_lik) VB2_HIP(hipMemcpyAsync(contam_lik, d_c, 3 * M * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (geno_post) VB2_HIP(hipMemcpyAsync(geno_post, d_c + 3 * M, 3 * M * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (log_l) VB2_HIP(hipMemcpyAsync(log_l, d_c + 6 * M, M * sizeof(double), hipMemcpyDeviceToHost, stream));
     } else if (want_host) {
         if (contam_lik) std::memset(contam_lik, 0, 3 * M * sizeof(double));
         if (geno_post) std::memset(geno_post, 0, 3 * M * sizeof(double));
         if (log_l) std::memset(log_l, 0, M * sizeof(double));
     }
-    VB2_HIP_S(hipStreamSynchronize(stream));
+    VB2_HIP(hipStreamSynchronize(stream));
     return VB2_OK;
 }
 
@@ -121,8 +113,8 @@ int SourceSet::create(int num_marker, int capacity, int device, SourceSet** out)
         return VB2_ERR_NO_DEVICE;
     }
     std::unique_ptr<SourceSet> s(new SourceSet());
-    if (device < 0) VB2_HIP_S(hipGetDevice(&device));
-    VB2_HIP_S(hipSetDevice(device));
+    if (device < 0) VB2_HIP(hipGetDevice(&device));
+    VB2_HIP(hipSetDevice(device));
     s->device_ = device;
     s->num_marker_ = num_marker;
     s->capacity_ = capacity;
@@ -141,7 +133,7 @@ int SourceSet::create(int num_marker, int capacity, int device, SourceSet** out)
         return VB2_ERR_NOMEM;
     }
     s->d_slab_ = static_cast<float*>(p);
-    VB2_HIP_S(hipStreamCreateWithFlags(&s->stream_, hipStreamNonBlocking));
+    VB2_HIP(hipStreamCreateWithFlags(&s->stream_, hipStreamNonBlocking));
     *out = s.release();
     return VB2_OK;
 }
@@ -221,7 +213,7 @@ int SourceSet::scores(double* score, int32_t* shared)
     std::lock_guard<std::mutex> lk(mu_);
     const int n = n_;
     if (n == 0) return VB2_OK;
-    VB2_HIP_S(hipSetDevice(device_));
+    VB2_HIP(hipSetDevice(device_));
     const size_t nn = (size_t)n * (size_t)n, np = source_partial_count(n, num_marker_);
     // [rows: n pointers][score: nn doubles][partial sums: np doubles][shared: nn ints][partial counts: np ints]
     const size_t ptr_bytes = ((size_t)n * sizeof(float*) + 15) / 16 * 16;
@@ -269,7 +261,7 @@ int SourceSet::time_pairs(int n, uint32_t seed, int warmup, int reps, double* ms
         return VB2_ERR_INVALID;
     }
     std::lock_guard<std::mutex> lk(mu_);
-    VB2_HIP_S(hipSetDevice(device_));
+    VB2_HIP(hipSetDevice(device_));
     const size_t row_floats = (size_t)num_marker_ * kSourceRowFloats;
     // eight distinct rows, dealt to the slots in turn (the kernels' time does not depend on the values)
     std::vector<float> host(row_floats);
@@ -279,10 +271,10 @@ int SourceSet::time_pairs(int n, uint32_t seed, int warmup, int reps, double* ms
             x = x * 1664525u + 1013904223u;
             host[e] = (float)((x >> 8) & 0xffff) * (1.0f / 65536.0f) + 1e-3f;
         }
-        VB2_HIP_S(hipMemcpy(d_slab_ + (size_t)v * row_floats, host.data(), row_floats * sizeof(float), hipMemcpyHostToDevice));
+        VB2_HIP(hipMemcpy(d_slab_ + (size_t)v * row_floats, host.data(), row_floats * sizeof(float), hipMemcpyHostToDevice));
     }
     for (int sl = 8; sl < n; ++sl)
-        VB2_HIP_S(hipMemcpy(d_slab_ + (size_t)sl * row_floats, d_slab_ + (size_t)(sl % 8) * row_floats, row_floats * sizeof(float),
+        VB2_HIP(hipMemcpy(d_slab_ + (size_t)sl * row_floats, d_slab_ + (size_t)(sl % 8) * row_floats, row_floats * sizeof(float),
                             hipMemcpyDeviceToDevice));
     for (int sl = 0; sl < n; ++sl) rows_[(size_t)sl] = d_slab_ + (size_t)sl * row_floats;
     n_ = std::max(n_, n);
@@ -290,7 +282,7 @@ int SourceSet::time_pairs(int n, uint32_t seed, int warmup, int reps, double* ms
     const size_t ptr_bytes = ((size_t)n * sizeof(float*) + 15) / 16 * 16;
     const size_t bytes = ptr_bytes + (nn + np) * sizeof(double) + (nn + np) * sizeof(int32_t);
     char* d = nullptr;
-    VB2_HIP_S(hipMalloc(reinterpret_cast<void**>(&d), bytes));
+    VB2_HIP(hipMalloc(reinterpret_cast<void**>(&d), bytes));
     const float** d_rows = reinterpret_cast<const float**>(d);
     double* d_score = reinterpret_cast<double*>(d + ptr_bytes);
     double* d_ps = d_score + nn;
@@ -324,23 +316,23 @@ int SourceSet::time_marginals(Context* ctx, double alpha, int warmup, int reps, 
         return VB2_ERR_INVALID;
     }
     std::lock_guard<std::mutex> lk(mu_);      // (slot 0 is written: no add, no scores meanwhile; the row is not registered)
-    VB2_HIP_S(hipSetDevice(device_));
+    VB2_HIP(hipSetDevice(device_));
     if (const int rc = ctx->ensure_pidx()) return rc;
     const int k = ctx->num_pc;
     for (int j = 0; j < 2 * k; ++j) ctx->h_points[j] = 0.01;
     ctx->h_points[2 * k] = alpha;
     EventPair ev;
-    VB2_HIP_S(hipEventCreate(&ev.a));
-    VB2_HIP_S(hipEventCreate(&ev.b));
+    VB2_HIP(hipEventCreate(&ev.a));
+    VB2_HIP(hipEventCreate(&ev.b));
     for (int r = -warmup; r < reps; ++r) {
-        VB2_HIP_S(hipEventRecord(ev.a, ctx->stream));
-        VB2_HIP_S(hipMemsetAsync(d_slab_, 0, sizeof(float) * kSourceRowFloats * (size_t)num_marker_, ctx->stream));
-        VB2_HIP_S(launch_source_marginals(ctx->L, num_marker_, ctx->d_points, ctx->d_pidx, nullptr, nullptr, nullptr, d_slab_,
+        VB2_HIP(hipEventRecord(ev.a, ctx->stream));
+        VB2_HIP(hipMemsetAsync(d_slab_, 0, sizeof(float) * kSourceRowFloats * (size_t)num_marker_, ctx->stream));
+        VB2_HIP(launch_source_marginals(ctx->L, num_marker_, ctx->d_points, ctx->d_pidx, nullptr, nullptr, nullptr, d_slab_,
                                           ctx->stream));
-        VB2_HIP_S(hipEventRecord(ev.b, ctx->stream));
-        VB2_HIP_S(hipEventSynchronize(ev.b));
+        VB2_HIP(hipEventRecord(ev.b, ctx->stream));
+        VB2_HIP(hipEventSynchronize(ev.b));
         float t = 0.0f;
-        VB2_HIP_S(hipEventElapsedTime(&t, ev.a, ev.b));
+        VB2_HIP(hipEventElapsedTime(&t, ev.a, ev.b));
         if (r >= 0) ms[r] = (double)t;
     }
     return VB2_OK;

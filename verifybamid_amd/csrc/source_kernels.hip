@@ -18,14 +18,13 @@
 //     No atomics: a pair's score is the same bits from call to call and whatever else the set holds.
 #include "source_kernels.h"
 
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "marker_walk.h"
 
 namespace vb2 {
 namespace {
 
-constexpr int kThreads = 256;
+using namespace walk;
+
 // a table row: the six off-diagonal pairs, then the three diagonal pairs (g, g), whose p = u_g whatever alpha -- P^n in the
 // probability domain, log p in the log domain.  The context's own diagonal constants exp(c_other + D[g]) are good enough
 // for L itself but are subnormal or 0 on deep markers: no basis for the ratios W / L.
@@ -35,35 +34,6 @@ constexpr int kRowDoubles = 9;
 // >= 1 and a product 2^-1000 of it is still a normal double; started at 1, such entries are subnormal and their few bits
 // reach q (measured: 1.2e-4 relative on a marker 400 reads deep).  c_other, common to the nine, cancels in the ratios.
 constexpr double kPdScale = 0x1p900, kPdUnscale = 0x1p-900;
-constexpr double kMinAf = 0.00005, kMaxAf = 0.99995;   // h:94-95
-
-// off-diagonal genotype pairs, in the reference's (g1 outer, g2 inner) order (as llk_kernels.hip numbers them)
-__device__ __forceinline__ void pair_g(int p, int& g1, int& g2)
-{
-    g1 = p >> 1;
-    const int lo = p & 1;
-    g2 = lo + (lo >= g1 ? 1 : 0);
-}
-
-// h:223-224 for one class / quality / pair, class ref (alt reads the pair mirrored): the reference's expression order
-__device__ __forceinline__ double entry_of(double alpha, double p_err, int g1, int g2)
-{
-    const double p_ok = 1.0 - p_err;
-    const double e1 = (double)g1 * (1.0 / 6.0), e2 = (double)g2 * (1.0 / 6.0);
-    const double n1 = 1.0 - 0.5 * (double)g1, n2 = 1.0 - 0.5 * (double)g2;
-    const double one_minus_alpha = 1.0 - alpha;
-    const double p = (alpha * e1 + one_minus_alpha * e2) * p_err + (alpha * n1 + one_minus_alpha * n2) * p_ok;
-    return p >= 0.0 ? p : __builtin_nan("");      // alpha outside [0, 1]: NaN, the marker is left out
-}
-
-__device__ __forceinline__ void gf_of(double af, double* gf)      // h:186-192
-{
-    if (af < kMinAf) af = kMinAf;
-    if (af > kMaxAf) af = kMaxAf;
-    gf[0] = (1 - af) * (1 - af);
-    gf[1] = 2 * (af) * (1 - af);
-    gf[2] = af * af;
-}
 
 template <bool PD>
 __global__ void __launch_bounds__(kThreads)
@@ -79,77 +49,57 @@ source_marginal_kernel(const DeviceLayout L, const int num_marker, const double*
     const size_t mp = (size_t)L.m_pad;
 
     // ---- the point's table (deriv_kernels.hip, values only) ----
-    const int num_single = PD ? L.num_prim - L.num_pair : L.num_prim;
-    for (int e = tid; e < num_single * 6; e += kThreads) {
+    for (int e = tid; e < num_single<PD>(L) * 6; e += kThreads) {
         const int pi = e / 6, p = e - pi * 6;
-        const double2 rec = L.prim[pi];
-        const uint32_t pr = (uint32_t)__double_as_longlong(rec.y);
-        const int first = (int)(pr & 0xffffu), twin = (int)(pr >> 16);
+        const SingleRec rec = single_rec(L, pi);
         int g1, g2;
         pair_g(p, g1, g2);
         if constexpr (PD) {
-            // record = a quality, class ref: {pErr, first row | K << 16 | rows from P^n to P^(n+1), a signed byte, << 24}
-            const double v = entry_of(alpha, rec.x, g1, g2);
-            const int kq = twin & 0xff, rstep = (int)(int8_t)(twin >> 8);
+            const double v = entry_of(alpha, rec.p_err, g1, g2);
+            const int kq = rec.kq(), rstep = rec.rstep();
             double r = v;
             for (int n = 1; n <= kq; ++n) {
-                const int rw = first + (n - 1) * rstep;
+                const int rw = rec.first + (n - 1) * rstep;
                 if (rw >= 0 && rw < nrow) tab[(size_t)rw * kRowDoubles + p] = r;
                 r *= v;
             }
         } else {
-            // record = a code: {signed pErr (alt < 0), code | twin << 16}; the alt twin's row is this one mirrored (pair 5 - p)
-            if (rec.x < 0.0) { g1 = 2 - g1; g2 = 2 - g2; }
-            const double lv = log(entry_of(alpha, fabs(rec.x), g1, g2));
-            if (first < nrow) tab[(size_t)first * kRowDoubles + p] = lv;
-            if (twin != 0xffff && twin < nrow) tab[(size_t)twin * kRowDoubles + (5 - p)] = lv;
+            if (rec.alt()) { g1 = 2 - g1; g2 = 2 - g2; }
+            const double lv = log(entry_of(alpha, fabs(rec.p_err), g1, g2));
+            if (rec.first < nrow) tab[(size_t)rec.first * kRowDoubles + p] = lv;
+            if (rec.has_twin() && rec.twin < nrow) tab[(size_t)rec.twin * kRowDoubles + (5 - p)] = lv;
         }
     }
     // the diagonal pairs: p = u_g whatever alpha; an alt code (log domain) or step (probability domain) reads the genotype mirrored
-    for (int e = tid; e < num_single * 3; e += kThreads) {
+    for (int e = tid; e < num_single<PD>(L) * 3; e += kThreads) {
         const int pi = e / 3, g = e - pi * 3;
-        const double2 rec = L.prim[pi];
-        const uint32_t pr = (uint32_t)__double_as_longlong(rec.y);
-        const int first = (int)(pr & 0xffffu), twin = (int)(pr >> 16);
-        const double p_err = fabs(rec.x), p_ok = 1.0 - p_err;
-        const double u = (double)g * (1.0 / 6.0) * p_err + (1.0 - 0.5 * (double)g) * p_ok;
+        const SingleRec rec = single_rec(L, pi);
+        const double u = diag_entry_of(fabs(rec.p_err), g);
         if constexpr (PD) {
-            const int kq = twin & 0xff, rstep = (int)(int8_t)(twin >> 8);
+            const int kq = rec.kq(), rstep = rec.rstep();
             double r = u;
             for (int n = 1; n <= kq; ++n) {
-                const int rw = first + (n - 1) * rstep;
+                const int rw = rec.first + (n - 1) * rstep;
                 if (rw >= 0 && rw < nrow) tab[(size_t)rw * kRowDoubles + 6 + g] = r;
                 r *= u;
             }
         } else {
             const double lu = log(u);
-            if (first < nrow) tab[(size_t)first * kRowDoubles + 6 + (rec.x < 0.0 ? 2 - g : g)] = lu;
-            if (twin != 0xffff && twin < nrow) tab[(size_t)twin * kRowDoubles + 6 + (2 - g)] = lu;
+            if (rec.first < nrow) tab[(size_t)rec.first * kRowDoubles + 6 + (rec.alt() ? 2 - g : g)] = lu;
+            if (rec.has_twin() && rec.twin < nrow) tab[(size_t)rec.twin * kRowDoubles + 6 + (2 - g)] = lu;
         }
     }
     for (int e = tid; e < kRowDoubles; e += kThreads)           // padding row: P = 1 (log domain: 0)
         tab[(size_t)L.num_code * kRowDoubles + e] = PD ? 1.0 : 0.0;
-    if constexpr (PD) {
-        // window rows: the product of two rows (level 1 uses rows of level 0)
-        for (int level = 0; level < 2; ++level) {
-            const int nrec = level == 0 ? L.num_pair - L.num_pair2 : L.num_pair2;
-            const int base = num_single + (level == 0 ? 0 : L.num_pair - L.num_pair2);
-            __syncthreads();
-            for (int e = tid; e < nrec * kRowDoubles; e += kThreads) {
-                const int pi = e / kRowDoubles, p = e - pi * kRowDoubles;
-                const double2 rec = L.prim[base + pi];
-                const uint32_t ab = (uint32_t)__double_as_longlong(rec.x), dst = (uint32_t)__double_as_longlong(rec.y);
-                const uint32_t ra = ab & 0xffffu, rb = ab >> 16;
-                if (ra >= (uint32_t)nrow || rb >= (uint32_t)nrow || dst >= (uint32_t)nrow) continue;
-                tab[(size_t)dst * kRowDoubles + p] = tab[(size_t)ra * kRowDoubles + p] * tab[(size_t)rb * kRowDoubles + p];
-            }
-        }
-    }
+    if constexpr (PD)
+        for_each_window<kRowDoubles>(L, nrow, tid, [&](uint32_t ra, uint32_t rb, uint32_t dst, int p) {
+            tab[(size_t)dst * kRowDoubles + p] = tab[(size_t)ra * kRowDoubles + p] * tab[(size_t)rb * kRowDoubles + p];
+        });
     __syncthreads();
 
     // ---- one thread per marker of the sorted order ----
     const int m = tid & 15;
-    const int ntile_grp = (L.num_mt + 15) / 16;
+    const int ntile_grp = tile_groups(L);
     for (int tg = blockIdx.x; tg < ntile_grp; tg += gridDim.x) {
         const int mt = tg * 16 + (tid >> 4);
         if (mt >= L.num_mt) continue;
@@ -161,40 +111,18 @@ source_marginal_kernel(const DeviceLayout L, const int num_marker, const double*
         double acc[6], dacc[3];
         for (int p = 0; p < 6; ++p) acc[p] = PD ? kPdScale : L.ediag[pos];
         for (int g = 0; g < 3; ++g) dacc[g] = PD ? kPdScale : L.ediag[pos];     // (log domain: c_other + the sums)
-        if constexpr (PD) {
-            // {ref steps | all steps << 16}; a step = a 16-bit byte offset of its row (+ kPdAltOffset for class alt), two per word
-            const uint32_t s1 = rec.y & 0xffffu, s2 = rec.y >> 16;
-            const uint16_t* c16 = reinterpret_cast<const uint16_t*>(L.codes);
-            for (uint32_t s = 0; s < s2; ++s) {
-                const bool alt = s >= s1;
-                uint32_t off = c16[(((size_t)rec.x + (s >> 1)) * 16 + (size_t)m) * 2 + (s & 1u)];
-                if (alt) off -= (uint32_t)kPdAltOffset;
-                uint32_t rw = off / (uint32_t)L.row_bytes;
-                rw = rw < (uint32_t)nrow ? rw : (uint32_t)L.num_code;
-                const double* t = tab + (size_t)rw * kRowDoubles;
+        for_each_step<PD, kRowDoubles>(L, tab, nrow, rec, m, [&](const double* t, bool alt, double n) {
 #pragma unroll
-                for (int p = 0; p < 6; ++p) acc[p] *= t[alt ? 5 - p : p];
-#pragma unroll
-                for (int g = 0; g < 3; ++g) dacc[g] *= t[6 + (alt ? 2 - g : g)];
+            for (int p = 0; p < 6; ++p) {
+                if constexpr (PD) acc[p] *= t[alt ? 5 - p : p];
+                else acc[p] = fma(n, t[p], acc[p]);
             }
-        } else {
-            // {first row, rows}; a row = two run words, run = row byte offset | top 16 bits of double(count) << 16
-            for (uint32_t r = 0; r < rec.y; ++r) {
-                const uint2 w = L.codes[((size_t)rec.x + r) * 16 + (size_t)m];
 #pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const uint32_t rw = j ? w.y : w.x;
-                    const double n = __hiloint2double((int)(rw & 0xffff0000u), 0);
-                    uint32_t trow = (rw & 0xffffu) / (uint32_t)L.row_bytes;
-                    trow = trow < (uint32_t)nrow ? trow : (uint32_t)L.num_code;
-                    const double* t = tab + (size_t)trow * kRowDoubles;
-#pragma unroll
-                    for (int p = 0; p < 6; ++p) acc[p] = fma(n, t[p], acc[p]);
-#pragma unroll
-                    for (int g = 0; g < 3; ++g) dacc[g] = fma(n, t[6 + g], dacc[g]);
-                }
+            for (int g = 0; g < 3; ++g) {
+                if constexpr (PD) dacc[g] *= t[6 + (alt ? 2 - g : g)];
+                else dacc[g] = fma(n, t[6 + g], dacc[g]);
             }
-        }
+        });
         // ---- epilogue ----
         double af1, af2;
         if (L.known_af != nullptr) {
@@ -238,9 +166,7 @@ source_marginal_kernel(const DeviceLayout L, const int num_marker, const double*
                 W[g1][g2] = exp(acc[p] - scale);
             }
         }
-        double lk = 0.0;         // L itself, in the reference's order (h:307-309)
-        for (int g1 = 0; g1 < 3; ++g1)
-            for (int g2 = 0; g2 < 3; ++g2) lk += Wu[g1][g2] * G1[g1] * G2[g2];
+        const double lk = mix_of(Wu, G1, G2);         // L itself, in the reference's order
         if (!(lk > 0)) continue;
         double r0[3], c0[3], Ls = 0.0;
         for (int a = 0; a < 3; ++a) {
@@ -353,11 +279,7 @@ hipError_t launch_source_marginals(const DeviceLayout& L, int num_marker, const 
     if (L.num_mt <= 0 || L.num_active <= 0) return hipSuccess;
     const int nrow = L.num_code + 1;
     const size_t shmem = (size_t)nrow * kRowDoubles * sizeof(double);
-    const int ntile_grp = (L.num_mt + 15) / 16;
-    int gx = 4 * (L.num_cu > 0 ? L.num_cu : 1);            // about four workgroups per CU, each with one table
-    gx = gx < ntile_grp ? gx : ntile_grp;
-    gx = gx > 0 ? gx : 1;
-    const dim3 grid((unsigned)gx), block(kThreads);
+    const dim3 grid((unsigned)stripe_grid(L, 1)), block(kThreads);
     if (L.pd)
         hipLaunchKernelGGL(source_marginal_kernel<true>, grid, block, shmem, stream, L, num_marker, d_point, pidx, contam_lik,
                            geno_post, log_l, row);

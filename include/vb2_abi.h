@@ -554,6 +554,53 @@ int vb2_cohort_run_intervals(const vb2_cohort_args *args, int32_t source_top, vb
                              int32_t *status /* [num_sample] */, vb2_interval *ci);
 
 /* ------------------------------------------------------------------------- *
+ * 3e. Duplicates and relatives within a cohort (--FindRelated).  Not in the reference: its model
+ *     again.  Per counted marker, at the point vb2_source_set_add takes (3b), with p the clamped allele frequency GF2 is
+ *     formed from:
+ *         h[g]  = (sum_g1 GF1[g1] W[g1][g]) / L      own-genotype likelihood relative to a random individual; q = GF2 h
+ *         t[g'] = sum_g q[g] T_p[g][g']              genotype distribution of a relative sharing one allele by descent,
+ *         T_p   = [(1-p, p, 0), ((1-p)/2, 1/2, p/2), (0, 1-p, p)]
+ *     and for target i, partner j over the markers both count, d2 = q_i . h_j, d1 = t_i . h_j,
+ *         K_r(i, j) = sum_m log max(k0_r + k1_r d1 + k2_r d2, VB2_SOURCE_DOT_FLOOR)
+ *     with (k0, k1, k2) = DUP (0, 0, 1), PO (0, 1, 0), FS (1/4, 1/2, 1/4), D2 (1/2, 1/2, 0): the log-likelihood ratio of "j's
+ *     reads come from a relative r of i's individual, genotype prior at i's fitted ancestry" against "two unrelated
+ *     individuals, each at its own fitted ancestry".  The matrix is ordered; K(i, i) is NAN.
+ * ------------------------------------------------------------------------- */
+#define VB2_SET_SOURCE 1               /* planes of a set: c and q -- vb2_source_set_scores                     */
+#define VB2_SET_RELATED 2              /*                  q, h and t -- vb2_source_set_relations               */
+#define VB2_NUM_RELATION 4
+#define VB2_REL_DUP 0                  /* the same individual (a second library, a swap)                        */
+#define VB2_REL_PO 1                   /* parent and child                                                      */
+#define VB2_REL_FS 2                   /* full siblings                                                         */
+#define VB2_REL_D2 3                   /* second degree: grandparent, half sibling, uncle or aunt               */
+
+/* vb2_source_set_create with the planes to keep, VB2_SET_SOURCE | VB2_SET_RELATED in any combination: 12 bytes per marker
+ * and sample for each of c, q, h, t the set holds (source: c q; related: q h t; both: c q h t).  vb2_source_set_create is
+ * planes = VB2_SET_SOURCE.  vb2_source_set_add fills whatever planes the set has from ONE launch.  An entry asked of a set
+ * without its planes returns VB2_ERR_INVALID. */
+int vb2_source_set_create_ex(int32_t num_marker, int32_t capacity, int32_t device, int32_t planes, vb2_source_set **out);
+/* llr [n][n][VB2_NUM_RELATION] (row = target, column = partner; NAN on the diagonal and for an empty slot's row and column)
+ * and shared [n][n]; either may be NULL.  A pair's four values are the same bits from call to call and whatever else the
+ * set holds. */
+int vb2_source_set_relations(vb2_source_set *set, double *llr, int32_t *shared);
+/* h and t at ONE point, per marker in panel order: own_lik [M][3], kin_post [M][3]; host pointers, either may be NULL; zeros
+ * for the markers the sample does not count.  Synchronous, like vb2_ctx_marginals. */
+int vb2_ctx_marginals_related(vb2_ctx *ctx, const double *pc1, const double *pc2, double alpha, double *own_lik,
+                              double *kin_post);
+/* vb2_cohort_run that also adds every searched sample to a set with the related planes before its context is released, in
+ * both cohort modes (one device only: VB2_ERR_INVALID otherwise, before any file is read).  llr [num_sample][num_sample][4]
+ * and shared [num_sample][num_sample] in the order of the samples, or NULL.  With output prefixes it writes <output_prefix of
+ * base>.Related, tab-separated with %g:
+ *     #SAMPLE PARTNER RANK RELATION LLR LLR_DUP LLR_PO LLR_FS LLR_D2 MARKERS
+ * per sample its `related_top` partners by descending LLR = max_r K_r; RELATION names the arg-max (DUP, PO, FS, D2), or UN
+ * when that LLR <= 0.  A sample that failed its search or sanity check keeps its files and status and is absent from the
+ * file.  source_top > 0: what vb2_cohort_run_sources does with top = source_top as well (score and shared NULL), from the
+ * same set and the same launch per sample.  Everything else is what vb2_cohort_run does and writes. */
+int vb2_cohort_run_related(const vb2_cohort_args *args, int32_t related_top, int32_t source_top,
+                           vb2_run_result *out /* [num_sample] */, int32_t *status /* [num_sample] */, double *llr,
+                           int32_t *shared);
+
+/* ------------------------------------------------------------------------- *
  * 3c. Weighted-marker replicates (--PerChromosome, --Bootstrap).  Not in the reference: its model
  *     with integer marker weights,  LLK_w(theta) = sum_i w_i log L_i(theta)  (L_i as in h:285-311; a marker counts where
  *     L_i > 0, h:310), for many weight vectors ("replicates") over the ONE resident copy of a sample.  LLK_w is what

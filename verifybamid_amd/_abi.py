@@ -177,6 +177,9 @@ class ReplicatesInfo(C.Structure):
 
 
 VB2_SOURCE_FIT_NONE = 1
+VB2_SET_SOURCE, VB2_SET_RELATED = 1, 2
+VB2_NUM_RELATION = 4
+VB2_REL_DUP, VB2_REL_PO, VB2_REL_FS, VB2_REL_D2 = 0, 1, 2, 3
 
 
 class SourceFit(C.Structure):
@@ -209,6 +212,7 @@ SYMBOLS = [
     "vb2_panel_get_view", "vb2_panel_write", "vb2_panel_destroy",
     "vb2_ctx_marginals", "vb2_source_set_create", "vb2_source_set_add", "vb2_source_set_scores",
     "vb2_source_set_destroy", "vb2_source_set_size", "vb2_cohort_run_sources",
+    "vb2_source_set_create_ex", "vb2_source_set_relations", "vb2_ctx_marginals_related", "vb2_cohort_run_related",
     "vb2_batch_derivs", "vb2_batch_interval", "vb2_intervals_lockstep", "vb2_cohort_run_intervals",
     "vb2_replicates_create", "vb2_replicates_destroy", "vb2_replicates_eval", "vb2_replicates_optimize_llk",
     "vb2_replicates_info_get", "vb2_replicates_lockstep", "vb2_chromosome_weights", "vb2_bootstrap_weights", "vb2_jackknife",
@@ -298,6 +302,11 @@ def lib():
     L.vb2_panel_destroy.restype = None
     L.vb2_ctx_marginals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
     L.vb2_source_set_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    L.vb2_source_set_create_ex.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    L.vb2_source_set_relations.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.vb2_ctx_marginals_related.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+    L.vb2_cohort_run_related.argtypes = [C.POINTER(CohortArgs), C.c_int32, C.c_int32, C.POINTER(RunResult), C.POINTER(C.c_int32),
+                                         C.c_void_p, C.c_void_p]
     L.vb2_source_set_add.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Model), C.POINTER(Estimate), C.POINTER(C.c_int32)]
     L.vb2_source_set_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.vb2_source_set_size.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]

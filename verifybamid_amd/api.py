@@ -236,10 +236,12 @@ class LikelihoodContext:
                    "vb2_llk_derivs_batch")
         return llk, grad, hess
 
-    def marginals(self, pc1, pc2, alpha):
+    def marginals(self, pc1, pc2, alpha, related=False):
         """Per marker, in panel order, at ONE point (vb2_ctx_marginals): the contaminant-genotype likelihood relative to a
         random contaminant c [M, 3], the posterior of the sample's own genotype q [M, 3] and log L [M]; zeros for the
-        markers the sample does not count.  g1 (c) is the alpha-fraction component, g2 (q) the other."""
+        markers the sample does not count.  g1 (c) is the alpha-fraction component, g2 (q) the other.
+        related: (c, q, log L, h, t) -- also the own-genotype likelihood relative to a random individual h [M, 3] and the
+        genotype distribution of a relative sharing one allele by descent t [M, 3] (vb2_ctx_marginals_related)."""
         pc1 = np.ascontiguousarray(np.asarray(pc1, dtype=np.float64).reshape(-1))
         pc2 = np.ascontiguousarray(np.asarray(pc2, dtype=np.float64).reshape(-1))
         assert pc1.shape == (self.num_pc,) and pc2.shape == (self.num_pc,)
@@ -247,6 +249,11 @@ class LikelihoodContext:
         c, q, ll = np.zeros((M, 3)), np.zeros((M, 3)), np.zeros(M)
         _abi.check(self._lib.vb2_ctx_marginals(self._h, _p(pc1), _p(pc2), float(alpha), _p(c), _p(q), _p(ll)),
                    "vb2_ctx_marginals")
+        if related:
+            h, t = np.zeros((M, 3)), np.zeros((M, 3))
+            _abi.check(self._lib.vb2_ctx_marginals_related(self._h, _p(pc1), _p(pc2), float(alpha), _p(h), _p(t)),
+                       "vb2_ctx_marginals_related")
+            return c, q, ll, h, t
         return c, q, ll
 
     def interval(self, estimate, **model_kw):
@@ -330,14 +337,20 @@ def _estimate_struct(estimate, k):
 class SourceSet:
     """vb2_source_set: the genotype marginals of a cohort's samples (float32, 24 bytes per marker and sample, on one
     device) and every pair's source score S(target, candidate): the log-likelihood ratio of "the target's contaminant
-    carries the candidate's genotypes" against "a random individual of the target's fitted contaminant ancestry"."""
+    carries the candidate's genotypes" against "a random individual of the target's fitted contaminant ancestry".
+    planes: SourceSet.SOURCE (c, q: scores()), SourceSet.RELATED (q, h, t: relations()) or both; 12 bytes per marker and
+    sample for each of c, q, h, t the set holds."""
 
-    def __init__(self, num_marker, capacity, device=-1):
+    SOURCE, RELATED = _abi.VB2_SET_SOURCE, _abi.VB2_SET_RELATED
+    RELATIONS = ("DUP", "PO", "FS", "D2")
+
+    def __init__(self, num_marker, capacity, device=-1, planes=_abi.VB2_SET_SOURCE):
         self._lib = _abi.lib()
         h = C.c_void_p()
-        _abi.check(self._lib.vb2_source_set_create(int(num_marker), int(capacity), int(device), C.byref(h)),
-                   "vb2_source_set_create")
+        _abi.check(self._lib.vb2_source_set_create_ex(int(num_marker), int(capacity), int(device), int(planes), C.byref(h)),
+                   "vb2_source_set_create_ex")
         self._h = h
+        self.planes = int(planes)
 
     @property
     def count(self):
@@ -374,6 +387,14 @@ class SourceSet:
         score, shared = np.zeros((n, n)), np.zeros((n, n), dtype=np.int32)
         _abi.check(self._lib.vb2_source_set_scores(self._h, _p(score), _p(shared)), "vb2_source_set_scores")
         return score, shared
+
+    def relations(self):
+        """(llr [n, n, 4] float64 in the order of RELATIONS, NaN on the diagonal; shared [n, n] int32): row = target,
+        column = partner (vb2_source_set_relations; a set with the RELATED planes)."""
+        n = self.count
+        llr, shared = np.zeros((n, n, _abi.VB2_NUM_RELATION)), np.zeros((n, n), dtype=np.int32)
+        _abi.check(self._lib.vb2_source_set_relations(self._h, _p(llr), _p(shared)), "vb2_source_set_relations")
+        return llr, shared
 
 
 class CohortBatch:
@@ -957,7 +978,7 @@ def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_san
 def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, disable_sanity=False,
                      known_af_path=None, device=-1, output_pileup=False, group_size=0, num_host_thread=0,
                      devices=None, find_source=False, source_top=3, sources_prefix=None, confidence_interval=False,
-                     refit_source=False, **model_kw):
+                     refit_source=False, find_related=False, related_top=3, **model_kw):
     """Many pileups against one panel (vb2_cohort_run): the panel is read once, the pileups are read
     and flattened by host threads while the device searches the previous group in lock-step.
     Returns one dict per sample (with its own "status" code).
@@ -969,12 +990,18 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
     <prefix>.CI is written.
     refit_source (with find_source; vb2_cohort_run_source_fits): sources also has `fit`, one dict per sample -- candidate
     (-1: none), markers, status (0: refitted, 1: no refit asked, < 0: the refit's error), llr, freemix, freelk1,
-    alpha_given, lk1_given, lk0_given, delta_lk -- and <sources_prefix>.SourceFit is written."""
+    alpha_given, lk1_given, lk0_given, delta_lk -- and <sources_prefix>.SourceFit is written.
+    find_related (vb2_cohort_run_related; one device; may be combined with find_source, which then returns no score
+    matrix; not with confidence_interval or refit_source): returns (samples, related), related = dict(llr [S, S, 4] in the
+    order DUP, PO, FS, D2 -- row = target, column = partner --, shared [S, S]); with output_prefixes and sources_prefix it
+    writes <sources_prefix>.Related, related_top partners per sample."""
     S = len(pileup_paths)
+    if find_related and (confidence_interval or refit_source):
+        raise ValueError("find_related cannot be combined with confidence_interval or refit_source")
     if refit_source and (not find_source or confidence_interval):
         raise ValueError("refit_source needs find_source and cannot be combined with confidence_interval")
     args, keep = _run_args(svd_prefix, pileup_paths[0], num_pc, disable_sanity, known_af_path,
-                           sources_prefix if find_source else None,
+                           sources_prefix if find_source or find_related else None,
                            device, output_pileup, devices=devices, **model_kw)
     ca = _abi.CohortArgs()
     ca.base = args
@@ -991,7 +1018,11 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
     status = (C.c_int32 * S)()
     score = shared = None
     civ = None
-    if confidence_interval:
+    if find_related:
+        llr, shared = np.zeros((S, S, _abi.VB2_NUM_RELATION)), np.zeros((S, S), dtype=np.int32)
+        _abi.check(_abi.lib().vb2_cohort_run_related(C.byref(ca), int(related_top), int(source_top) if find_source else 0, res,
+                                                     status, _p(llr), _p(shared)), "vb2_cohort_run_related")
+    elif confidence_interval:
         civ = (_abi.Interval * S)()
         _abi.check(_abi.lib().vb2_cohort_run_intervals(C.byref(ca), int(source_top) if find_source else 0, res, status, civ),
                    "vb2_cohort_run_intervals")
@@ -1015,6 +1046,8 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
         if civ is not None and status[s] == _abi.VB2_OK:
             d["interval"] = _interval_dict(civ[s])
         out.append(d)
+    if find_related:
+        return out, dict(llr=llr, shared=shared)
     if refit_source:
         fit = [{name: getattr(fits[s], name) for name, _ in _abi.SourceFit._fields_ if name != "reserved"} for s in range(S)]
         return out, dict(score=score, shared=shared, fit=fit)

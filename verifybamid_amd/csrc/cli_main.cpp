@@ -99,6 +99,8 @@ int main(int argc, char** argv)
     bool findSource = false;
     int sourceTop = 3;
     bool refitSource = false;
+    bool findRelated = false;
+    int relatedTop = 3;
     bool perChromosome = false;
     int bootstrap = 0;
     // "Pileup Options" (main.cpp:176-187), defaults main.cpp:81-96 (MPLP_REALN | MPLP_SMART_OVERLAPS; UNMAP | SECONDARY |
@@ -162,6 +164,11 @@ int main(int argc, char** argv)
         // not in the reference: after --FindSource, every sample's FREEMIX refitted given its best candidate's genotypes
         // (vb2_cohort_run_source_fits), to <Output>.SourceFit
         {"RefitSource", {Flag::kBool, &refitSource, false}},
+        // not in the reference: which samples of the --PileupList cohort are the same individual, parent and child, full
+        // siblings or second-degree relatives?  Every ordered pair's four log-likelihood ratios (vb2_cohort_run_related); the
+        // --RelatedTop best partners per sample go to <Output>.Related
+        {"FindRelated", {Flag::kBool, &findRelated, false}},
+        {"RelatedTop", {Flag::kInt, &relatedTop, false}},
         // not in the reference: FREEMIX refitted on every chromosome alone and with every chromosome left out, with a
         // delete-one-chromosome jackknife (<Output>.Chrom), and over --Bootstrap N marker resamples seeded by --Seed
         // (<Output>.Boot): weighted-marker replicates of the one resident sample, searched in lock-step (vb2_run_replicates)
@@ -221,6 +228,17 @@ int main(int argc, char** argv)
             fatal("--RefitSource cannot be combined with --CohortInterval: run the intervals and the refits separately");
         if (Devices != "Empty" && Devices.find(',') != std::string::npos)
             fatal("--RefitSource cannot be combined with more than one --Devices: the refits read a source set on one device");
+    }
+    if (findRelated) {                                                  // a cohort on one device
+        if (PileupList == "Empty")
+            fatal("--FindRelated needs --PileupList: duplicates and relatives are looked for among the samples of one cohort run");
+        if (refitSource)
+            fatal("--FindRelated cannot be combined with --RefitSource: run the refits and the relatedness separately");
+        if (cohortInterval)
+            fatal("--FindRelated cannot be combined with --CohortInterval: run the intervals and the relatedness separately");
+        if (Devices != "Empty" && Devices.find(',') != std::string::npos)
+            fatal("--FindRelated cannot be combined with more than one --Devices: a set of samples lives on one device");
+        if (relatedTop < 1) fatal("--RelatedTop takes a positive number of partners");
     }
     if (findSource) {                                                   // a cohort on one device
         if (PileupList == "Empty")
@@ -378,7 +396,8 @@ int main(int argc, char** argv)
         ca.num_host_thread = nthread > 4 ? nthread : 0;               // --NumThread above its default: reader threads
         std::vector<vb2_run_result> cres(pile.size());
         std::vector<int32_t> cst(pile.size());
-        const int rcc = cohortInterval ? vb2_cohort_run_intervals(&ca, findSource ? sourceTop : 0, cres.data(), cst.data(), nullptr)
+        const int rcc = findRelated ? vb2_cohort_run_related(&ca, relatedTop, findSource ? sourceTop : 0, cres.data(), cst.data(), nullptr, nullptr)
+                        : cohortInterval ? vb2_cohort_run_intervals(&ca, findSource ? sourceTop : 0, cres.data(), cst.data(), nullptr)
                         : refitSource ? vb2_cohort_run_source_fits(&ca, sourceTop, cres.data(), cst.data(), nullptr, nullptr, nullptr)
                         : findSource ? vb2_cohort_run_sources(&ca, sourceTop, cres.data(), cst.data(), nullptr, nullptr)
                                      : vb2_cohort_run(&ca, cres.data(), cst.data());

@@ -114,6 +114,16 @@ public:
         ngroup_ = (int)group_begin_.size() - 1;
     }
 
+    // related (vb2_cohort_run_related): the set also keeps the related planes -- one marginal launch per sample all the same --,
+    // llr ([S][S][4]) / shared ([S][S]; may be null) and <Output>.Related after the last sample
+    void enable_related(int top, double* llr, int32_t* shared)
+    {
+        related_ = true;
+        related_top_ = top;
+        llr_ = llr;
+        rel_shared_ = shared;
+    }
+
     ~CohortRunner()
     {
         shutdown();
@@ -153,9 +163,10 @@ public:
         const double t_warm = now_s();
         model_ = a_->base.model;
         if (panel_->isAFknown) model_.is_af_known = 1;
-        if (find_source_) {
+        if (find_source_ || related_) {
             vb2::SourceSet* set = nullptr;
-            if (const int rcs = vb2::SourceSet::create((int)panel_->NumMarker, S_, devices_[0], &set)) {
+            const int planes = (find_source_ ? VB2_SET_SOURCE : 0) | (related_ ? VB2_SET_RELATED : 0);
+            if (const int rcs = vb2::SourceSet::create((int)panel_->NumMarker, S_, devices_[0], &set, planes)) {
                 err_all_ = vb2::g_last_error;
                 return rcs;
             }
@@ -191,7 +202,8 @@ public:
         dev_threads_.clear();
         const double t_dev = now_s();
         shutdown();
-        if (sources_ && !rc_all_) rc_all_ = finish_sources();
+        if (sources_ && find_source_ && !rc_all_) rc_all_ = finish_sources();
+        if (sources_ && related_ && !rc_all_) rc_all_ = finish_related();
         if (refit_) {
             if (!rc_all_) rc_all_ = refit_sources();
             release_parked();
@@ -287,6 +299,34 @@ private:
         if (!score && !shared) return VB2_OK;
         int rc = sources_->scores(score, shared);
         if (!rc && file) rc = vb2::write_sources(a_->base.output_prefix, S_, top_, a_->output_prefixes, out_, status_, score, shared);
+        if (rc) err_all_ = vb2::g_last_error;
+        return rc;
+    }
+    // --FindRelated (false without it: nothing else then differs)
+    bool related_ = false;
+    int related_top_ = 0;
+    double* llr_ = nullptr;
+    int32_t* rel_shared_ = nullptr;
+
+    // after the last context is gone: K, and <Output>.Related next to the samples' own files
+    int finish_related()
+    {
+        sources_->set_count(S_);
+        for (int s = 0; s < S_; ++s)
+            if (status_[s] != VB2_OK)
+                std::fprintf(stderr, "NOTICE - --FindRelated: sample %d failed (status %d) and is left out of the relatedness matrix\n",
+                             s, (int)status_[s]);
+        const size_t nn = (size_t)S_ * (size_t)S_;
+        std::vector<double> kk;
+        std::vector<int32_t> sh;
+        const bool file = a_->output_prefixes && a_->base.output_prefix;
+        double* llr = llr_;
+        int32_t* shared = rel_shared_;
+        if (file && !llr) { kk.resize(nn * VB2_NUM_RELATION); llr = kk.data(); }
+        if (file && !shared) { sh.resize(nn); shared = sh.data(); }
+        if (!llr && !shared) return VB2_OK;
+        int rc = sources_->relations(llr, shared);
+        if (!rc && file) rc = vb2::write_related(a_->base.output_prefix, S_, related_top_, a_->output_prefixes, status_, llr, shared);
         if (rc) err_all_ = vb2::g_last_error;
         return rc;
     }
@@ -790,8 +830,8 @@ private:
                         // (a sample whose row cannot be made keeps its files and its status -- it was searched and written as
                         // the plain run does it --; its row and column of the matrix are NaN and a NOTICE says why)
                         if (sources_->put(d.s, d.ctx->impl, model_, d.est))
-                            std::fprintf(stderr, "NOTICE - --FindSource: sample %d has no row in the source set: %s\n", d.s,
-                                         vb2::g_last_error.c_str());
+                            std::fprintf(stderr, "NOTICE - %s: sample %d has no row in the source set: %s\n",
+                                         find_source_ ? "--FindSource" : "--FindRelated", d.s, vb2::g_last_error.c_str());
                         else if (refit_) {               // searched, written, in the set: parked for the refit, not destroyed
                             if (parked_.empty()) parked_.assign((size_t)S_, nullptr);
                             parked_[(size_t)d.s] = d.ctx;
@@ -976,6 +1016,33 @@ extern "C" int vb2_cohort_run_sources(const vb2_cohort_args* a, int32_t top, vb2
     }
     try {
         CohortRunner runner(a, out, status, true, top, score, shared);
+        const int rc = runner.run();
+        if (rc && !runner.error().empty()) set_error(runner.error());
+        return rc;
+    } catch (const std::bad_alloc&) {
+        set_error("out of host memory");
+        return VB2_ERR_NOMEM;
+    } catch (const std::exception& e) {
+        set_error(e.what());
+        return VB2_ERR_INVALID;
+    }
+}
+
+extern "C" int vb2_cohort_run_related(const vb2_cohort_args* a, int32_t related_top, int32_t source_top, vb2_run_result* out,
+                                      int32_t* status, double* llr, int32_t* shared)
+{
+    if (!a || !out || !status || a->num_sample < 1 || !a->pileup_paths || !a->base.ud_path || !a->base.mean_path ||
+        !a->base.bed_path || a->base.num_pc < 1 || a->base.num_pc > VB2_MAX_PC || related_top < 0 || source_top < 0) {
+        set_error("vb2_cohort_run_related: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    if (a->base.num_device > 1 || a->base.num_device < 0) {
+        set_error("--FindRelated takes one device: a set of samples is not spread over several --Devices");
+        return VB2_ERR_INVALID;
+    }
+    try {
+        CohortRunner runner(a, out, status, source_top > 0, source_top);
+        runner.enable_related(related_top, llr, shared);
         const int rc = runner.run();
         if (rc && !runner.error().empty()) set_error(runner.error());
         return rc;

@@ -198,6 +198,7 @@ Context::~Context()
     if (d_codes16_own) (void)hipFree(d_codes16_own);
     if (d_deriv && !slab_cache().give(slab_cache().dev, d_deriv, d_deriv_bytes, device)) (void)hipFree(d_deriv);
     if (d_marg && !slab_cache().give(slab_cache().dev, d_marg, d_marg_bytes, device)) (void)hipFree(d_marg);
+    if (d_marg_rel && !slab_cache().give(slab_cache().dev, d_marg_rel, d_marg_rel_bytes, device)) (void)hipFree(d_marg_rel);
     if (d_pidx && !slab_cache().give(slab_cache().dev, d_pidx, d_pidx_bytes, device)) (void)hipFree(d_pidx);
     for (CohortSched& e : cohort_sched_)
         if (e.d_mem && !slab_cache().give(slab_cache().dev, e.d_mem, e.bytes, device)) (void)hipFree(e.d_mem);

@@ -26,6 +26,7 @@ int usable_device_count();
 // container with a CFS quota still sees every core of the host; threads beyond the quota only
 // get the whole cgroup throttled (measured on the 256-thread GPU host with a 16-CPU quota).
 int usable_cpu_count();
+struct MarginalRelated;         // source_kernels.h: where the marginal kernel's related instantiation writes
 // The host half of vb2_ctx_create (flatten) without a device: timing aid for tools/ubench/host_pipeline.cpp.
 int flatten_dry_run(const vb2_input* in, double* ms);
 // ... and a digest of what it produced (run words, tile records, panel rows, per-marker constants, dictionary): lets a
@@ -164,8 +165,10 @@ public:
     // c [M][3], the posterior of the sample's own genotype q [M][3] and log L [M], in panel order, zeros for markers the
     // sample does not count.  Host pointers (any may be null), synchronous; d_row: a device row of a source set (float32
     // planes c | q, kSourceRowFloats * M floats) written on the context's stream, or null.  Not inside a resident search.
+    // own_lik / kin_post (host, [M][3]) and planes (device float32 planes of a set row, instead of d_row): h and t of
+    // DESIGN.md section 15 as well, from the kernel's related instantiation -- still ONE launch.
     int marginals(const double* pc1, const double* pc2, double alpha, double* contam_lik, double* geno_post, double* log_l,
-                  float* d_row);
+                  float* d_row, double* own_lik = nullptr, double* kin_post = nullptr, const MarginalRelated* planes = nullptr);
     // sorted position -> panel marker on the device, uploaded on first use (the flatten keeps only the two host vectors it
     // sorted with: h_perm[position] indexes h_active, the counted markers' panel rows)
     int ensure_pidx();
@@ -175,6 +178,8 @@ public:
     size_t d_pidx_bytes = 0;
     void* d_marg = nullptr;                   // scratch of marginals(): the point's row and the three double outputs
     size_t d_marg_bytes = 0;
+    void* d_marg_rel = nullptr;               // ... and the two double outputs of its related form, on first use
+    size_t d_marg_rel_bytes = 0;
 
     int device = -1;
     int num_marker = 0;

@@ -1,5 +1,5 @@
-// source.cpp -- host side of --FindSource (source_kernels.hip): Context::marginals, the source set, its C entries and the
-// <Output>.Sources writer.
+// source.cpp -- host side of --FindSource (source_kernels.hip) and --FindRelated (related_kernels.hip): Context::marginals,
+// the set and its planes, its C entries and the <Output>.Sources / .Related / .SourceFit writers.
 #include "source.h"
 
 #include <hip/hip_runtime_api.h>
@@ -13,6 +13,7 @@
 #include <new>
 
 #include "device_util.h"
+#include "related_kernels.h"
 #include "source_kernels.h"
 
 namespace vb2 {
@@ -46,7 +47,7 @@ int Context::ensure_pidx()
 }
 
 int Context::marginals(const double* pc1, const double* pc2, double alpha, double* contam_lik, double* geno_post, double* log_l,
-                       float* d_row)
+                       float* d_row, double* own_lik, double* kin_post, const MarginalRelated* planes)
 {
     if (!pc1 || !pc2) {
         set_error("vb2_ctx_marginals: invalid argument");
@@ -60,6 +61,8 @@ int Context::marginals(const double* pc1, const double* pc2, double alpha, doubl
     const int k = num_pc;
     const size_t M = (size_t)num_marker;
     const bool want_host = contam_lik || geno_post || log_l;
+    const bool want_rel = own_lik || kin_post;
+    const bool related = want_rel || planes;          // the kernel's related instantiation (the caller zero-fills `planes`)
     if (d_row) VB2_HIP(hipMemsetAsync(d_row, 0, sizeof(float) * kSourceRowFloats * M, stream));
     // NaN parameters: no marker counts (context.h: params_hold_nan)
     const bool none = params_hold_nan(pc1, pc2, alpha, k, L.known_af != nullptr) || L.num_active == 0;
@@ -79,14 +82,46 @@ int Context::marginals(const double* pc1, const double* pc2, double alpha, doubl
         d_c = static_cast<double*>(d_marg);
         VB2_HIP(hipMemsetAsync(d_c, 0, 7 * M * sizeof(double), stream));
     }
+    double* d_r = nullptr;
+    if (want_rel && !none) {
+        if (!d_marg_rel) {
+            const size_t bytes = 6 * M * sizeof(double);
+            size_t got = 0;
+            void* p = cached_device_slab(bytes, device, &got);
+            if (!p) {
+                VB2_HIP(hipMalloc(&p, bytes));
+                got = bytes;
+            }
+            d_marg_rel = p;
+            d_marg_rel_bytes = got;
+        }
+        d_r = static_cast<double*>(d_marg_rel);
+        VB2_HIP(hipMemsetAsync(d_r, 0, 6 * M * sizeof(double), stream));
+    }
     if (!none) {
         if (const int rc = ensure_pidx()) return rc;
         // the point travels through the context's mapped staging row (as eval_host's points do)
         std::memcpy(h_points, pc1, sizeof(double) * k);
         std::memcpy(h_points + k, pc2, sizeof(double) * k);
         h_points[2 * k] = alpha;
-        VB2_HIP(launch_source_marginals(L, num_marker, d_points, d_pidx, d_c, d_c ? d_c + 3 * M : nullptr,
-                                          d_c ? d_c + 6 * M : nullptr, d_row, stream));
+        if (related) {
+            MarginalRelated rel;
+            if (planes) rel = *planes;
+            rel.own_lik = d_r;
+            rel.kin_post = d_r ? d_r + 3 * M : nullptr;
+            VB2_HIP(launch_related_marginals(L, num_marker, d_points, d_pidx, d_c, d_c ? d_c + 3 * M : nullptr,
+                                               d_c ? d_c + 6 * M : nullptr, rel, stream));
+        } else {
+            VB2_HIP(launch_source_marginals(L, num_marker, d_points, d_pidx, d_c, d_c ? d_c + 3 * M : nullptr,
+                                              d_c ? d_c + 6 * M : nullptr, d_row, stream));
+        }
+    }
+    if (want_rel && !none) {
+        if (own_lik) VB2_HIP(hipMemcpyAsync(own_lik, d_r, 3 * M * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (kin_post) VB2_HIP(hipMemcpyAsync(kin_post, d_r + 3 * M, 3 * M * sizeof(double), hipMemcpyDeviceToHost, stream));
+    } else if (want_rel) {
+        if (own_lik) std::memset(own_lik, 0, 3 * M * sizeof(double));
+        if (kin_post) std::memset(kin_post, 0, 3 * M * sizeof(double));
     }
     if (want_host && !none) {
         if (contam_lik) VB2_HIP(hipMemcpyAsync(contam_lik, d_c, 3 * M * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -101,10 +136,10 @@ int Context::marginals(const double* pc1, const double* pc2, double alpha, doubl
     return VB2_OK;
 }
 
-int SourceSet::create(int num_marker, int capacity, int device, SourceSet** out)
+int SourceSet::create(int num_marker, int capacity, int device, SourceSet** out, int planes)
 {
     *out = nullptr;
-    if (num_marker < 1 || capacity < 1) {
+    if (num_marker < 1 || capacity < 1 || planes < 1 || (planes & ~(VB2_SET_SOURCE | VB2_SET_RELATED))) {
         set_error("vb2_source_set_create: invalid argument");
         return VB2_ERR_INVALID;
     }
@@ -119,7 +154,14 @@ int SourceSet::create(int num_marker, int capacity, int device, SourceSet** out)
     s->num_marker_ = num_marker;
     s->capacity_ = capacity;
     s->rows_.assign((size_t)capacity, nullptr);
-    const unsigned long long bytes = (unsigned long long)capacity * (unsigned long long)num_marker * kSourceRowFloats * sizeof(float);
+    // the planes a row holds, [num_marker][3] floats each, in the order c q h t: the source pair kernel finds c | q at the
+    // row's start, the related one q | h | t from q_offset_ on
+    s->planes_ = planes;
+    const int num_plane = ((planes & VB2_SET_SOURCE) ? 2 : 1) + ((planes & VB2_SET_RELATED) ? 2 : 0);
+    s->q_offset_ = (planes & VB2_SET_SOURCE) ? 3 * (size_t)num_marker : 0;
+    s->row_floats_ = (size_t)num_plane * 3 * (size_t)num_marker;
+    static_assert(kSourceRowFloats == 6, "a source-only row is c | q");
+    const unsigned long long bytes = (unsigned long long)capacity * (unsigned long long)num_marker * (3ull * num_plane) * sizeof(float);
     size_t free_b = 0, total_b = 0;
     const bool known = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
     if (!known) (void)hipGetLastError();
@@ -200,16 +242,80 @@ int SourceSet::put(int slot, Context* ctx, const vb2_model& model, const vb2_est
         p1.swap(p2);
         alpha = 1.0 - alpha;
     }
-    float* row = d_slab_ + (size_t)slot * (size_t)num_marker_ * kSourceRowFloats;
-    if (const int rc = ctx->marginals(p1.data(), p2.data(), alpha, nullptr, nullptr, nullptr, row)) return rc;
+    float* row = d_slab_ + (size_t)slot * row_floats_;
+    if (planes_ == VB2_SET_SOURCE) {
+        if (const int rc = ctx->marginals(p1.data(), p2.data(), alpha, nullptr, nullptr, nullptr, row)) return rc;
+    } else {                // every plane the set has, from one launch
+        VB2_HIP(hipSetDevice(device_));
+        VB2_HIP(hipMemsetAsync(row, 0, sizeof(float) * row_floats_, ctx->stream));
+        const MarginalRelated rel = planes_of(row);
+        if (const int rc = ctx->marginals(p1.data(), p2.data(), alpha, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &rel))
+            return rc;
+    }
     std::lock_guard<std::mutex> lk(mu_);
     rows_[(size_t)slot] = row;
     n_ = std::max(n_, slot + 1);
     return VB2_OK;
 }
 
+MarginalRelated SourceSet::planes_of(float* row) const
+{
+    const size_t plane = 3 * (size_t)num_marker_;
+    MarginalRelated rel;
+    if (planes_ & VB2_SET_SOURCE) rel.c = row;
+    rel.q = row + q_offset_;
+    if (planes_ & VB2_SET_RELATED) {
+        rel.h = row + q_offset_ + plane;
+        rel.t = row + q_offset_ + 2 * plane;
+    }
+    return rel;
+}
+
+int SourceSet::relations(double* llr, int32_t* shared)
+{
+    if (!(planes_ & VB2_SET_RELATED)) {
+        set_error("vb2_source_set_relations: the set was created without the related planes (VB2_SET_RELATED)");
+        return VB2_ERR_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(mu_);
+    const int n = n_;
+    if (n == 0) return VB2_OK;
+    VB2_HIP(hipSetDevice(device_));
+    const size_t nn = (size_t)n * (size_t)n, np = related_partial_count(n, num_marker_);
+    // [rows: n pointers][llr: 4 nn doubles][partial sums: 4 np doubles][shared: nn ints][partial counts: np ints]
+    const size_t ptr_bytes = ((size_t)n * sizeof(float*) + 15) / 16 * 16;
+    const size_t bytes = ptr_bytes + (nn + np) * kNumRelation * sizeof(double) + (nn + np) * sizeof(int32_t);
+    char* d = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&d), bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("vb2_source_set_relations: " + std::to_string(bytes) + " bytes of device scratch do not fit");
+        return VB2_ERR_NOMEM;
+    }
+    const float** d_rows = reinterpret_cast<const float**>(d);
+    double* d_llr = reinterpret_cast<double*>(d + ptr_bytes);
+    double* d_pk = d_llr + nn * kNumRelation;
+    int32_t* d_shared = reinterpret_cast<int32_t*>(d_pk + np * kNumRelation);
+    int32_t* d_pn = d_shared + nn;
+    hipError_t e = hipMemcpyAsync(d_rows, rows_.data(), (size_t)n * sizeof(float*), hipMemcpyHostToDevice, stream_);
+    if (e == hipSuccess) e = launch_related_pairs(d_rows, q_offset_, n, num_marker_, d_pk, d_pn, d_llr, d_shared, stream_);
+    if (e == hipSuccess && llr) e = hipMemcpyAsync(llr, d_llr, nn * kNumRelation * sizeof(double), hipMemcpyDeviceToHost, stream_);
+    if (e == hipSuccess && shared) e = hipMemcpyAsync(shared, d_shared, nn * sizeof(int32_t), hipMemcpyDeviceToHost, stream_);
+    const hipError_t es = hipStreamSynchronize(stream_);
+    (void)hipFree(d);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) {
+        set_error(std::string("vb2_source_set_relations: ") + hipGetErrorString(e));
+        return VB2_ERR_HIP;
+    }
+    return VB2_OK;
+}
+
 int SourceSet::scores(double* score, int32_t* shared)
 {
+    if (!(planes_ & VB2_SET_SOURCE)) {
+        set_error("vb2_source_set_scores: the set was created without the source planes (VB2_SET_SOURCE)");
+        return VB2_ERR_INVALID;
+    }
     std::lock_guard<std::mutex> lk(mu_);
     const int n = n_;
     if (n == 0) return VB2_OK;
@@ -254,15 +360,15 @@ struct EventPair {
 };
 }  // namespace
 
-int SourceSet::time_pairs(int n, uint32_t seed, int warmup, int reps, double* ms)
+int SourceSet::time_pairs(int n, uint32_t seed, int warmup, int reps, double* ms, bool related)
 {
-    if (n < 1 || n > capacity_ || reps < 1 || warmup < 0 || !ms) {
+    if (n < 1 || n > capacity_ || reps < 1 || warmup < 0 || !ms || !(planes_ & (related ? VB2_SET_RELATED : VB2_SET_SOURCE))) {
         set_error("time_pairs: invalid argument");
         return VB2_ERR_INVALID;
     }
     std::lock_guard<std::mutex> lk(mu_);
     VB2_HIP(hipSetDevice(device_));
-    const size_t row_floats = (size_t)num_marker_ * kSourceRowFloats;
+    const size_t row_floats = row_floats_;
     // eight distinct rows, dealt to the slots in turn (the kernels' time does not depend on the values)
     std::vector<float> host(row_floats);
     uint32_t x = seed * 2654435761u + 1u;
@@ -279,14 +385,15 @@ int SourceSet::time_pairs(int n, uint32_t seed, int warmup, int reps, double* ms
     for (int sl = 0; sl < n; ++sl) rows_[(size_t)sl] = d_slab_ + (size_t)sl * row_floats;
     n_ = std::max(n_, n);
     const size_t nn = (size_t)n * (size_t)n, np = source_partial_count(n, num_marker_);
+    const size_t per = related ? kNumRelation : 1;          // doubles per pair
     const size_t ptr_bytes = ((size_t)n * sizeof(float*) + 15) / 16 * 16;
-    const size_t bytes = ptr_bytes + (nn + np) * sizeof(double) + (nn + np) * sizeof(int32_t);
+    const size_t bytes = ptr_bytes + (nn + np) * per * sizeof(double) + (nn + np) * sizeof(int32_t);
     char* d = nullptr;
     VB2_HIP(hipMalloc(reinterpret_cast<void**>(&d), bytes));
     const float** d_rows = reinterpret_cast<const float**>(d);
     double* d_score = reinterpret_cast<double*>(d + ptr_bytes);
-    double* d_ps = d_score + nn;
-    int32_t* d_shared = reinterpret_cast<int32_t*>(d_ps + np);
+    double* d_ps = d_score + nn * per;
+    int32_t* d_shared = reinterpret_cast<int32_t*>(d_ps + np * per);
     int32_t* d_pn = d_shared + nn;
     EventPair ev;
     hipError_t e = hipMemcpy(d_rows, rows_.data(), (size_t)n * sizeof(float*), hipMemcpyHostToDevice);
@@ -294,7 +401,9 @@ int SourceSet::time_pairs(int n, uint32_t seed, int warmup, int reps, double* ms
     if (e == hipSuccess) e = hipEventCreate(&ev.b);
     for (int r = -warmup; r < reps && e == hipSuccess; ++r) {
         e = hipEventRecord(ev.a, stream_);
-        if (e == hipSuccess) e = launch_source_pairs(d_rows, n, num_marker_, d_ps, d_pn, d_score, d_shared, stream_);
+        if (e == hipSuccess)
+            e = related ? launch_related_pairs(d_rows, q_offset_, n, num_marker_, d_ps, d_pn, d_score, d_shared, stream_)
+                        : launch_source_pairs(d_rows, n, num_marker_, d_ps, d_pn, d_score, d_shared, stream_);
         if (e == hipSuccess) e = hipEventRecord(ev.b, stream_);
         if (e == hipSuccess) e = hipEventSynchronize(ev.b);
         float t = 0.0f;
@@ -326,9 +435,13 @@ int SourceSet::time_marginals(Context* ctx, double alpha, int warmup, int reps, 
     VB2_HIP(hipEventCreate(&ev.b));
     for (int r = -warmup; r < reps; ++r) {
         VB2_HIP(hipEventRecord(ev.a, ctx->stream));
-        VB2_HIP(hipMemsetAsync(d_slab_, 0, sizeof(float) * kSourceRowFloats * (size_t)num_marker_, ctx->stream));
-        VB2_HIP(launch_source_marginals(ctx->L, num_marker_, ctx->d_points, ctx->d_pidx, nullptr, nullptr, nullptr, d_slab_,
-                                          ctx->stream));
+        VB2_HIP(hipMemsetAsync(d_slab_, 0, sizeof(float) * row_floats_, ctx->stream));
+        if (planes_ == VB2_SET_SOURCE)
+            VB2_HIP(launch_source_marginals(ctx->L, num_marker_, ctx->d_points, ctx->d_pidx, nullptr, nullptr, nullptr, d_slab_,
+                                              ctx->stream));
+        else
+            VB2_HIP(launch_related_marginals(ctx->L, num_marker_, ctx->d_points, ctx->d_pidx, nullptr, nullptr, nullptr,
+                                               planes_of(d_slab_), ctx->stream));
         VB2_HIP(hipEventRecord(ev.b, ctx->stream));
         VB2_HIP(hipEventSynchronize(ev.b));
         float t = 0.0f;
@@ -366,6 +479,47 @@ int write_sources(const std::string& prefix, int n, int top, const char* const* 
             const int j = order[(size_t)r];
             std::fprintf(f, "%s\t%g\t%d\t%s\t%g\t%d\n", names[i], freemix, r + 1, names[j], score[(size_t)i * n + j],
                          (int)shared[(size_t)i * n + j]);
+        }
+    }
+    if (std::fclose(f) != 0) {
+        set_error("cannot write " + name);
+        return VB2_ERR_IO;
+    }
+    return VB2_OK;
+}
+
+int write_related(const std::string& prefix, int n, int top, const char* const* names, const int32_t* status, const double* llr,
+                  const int32_t* shared)
+{
+    static const char* const kName[VB2_NUM_RELATION] = {"DUP", "PO", "FS", "D2"};
+    const std::string name(prefix + ".Related");
+    std::FILE* f = std::fopen(name.c_str(), "w");
+    if (!f) {
+        set_error("cannot write " + name);
+        return VB2_ERR_IO;
+    }
+    std::fprintf(f, "#SAMPLE\tPARTNER\tRANK\tRELATION\tLLR\tLLR_DUP\tLLR_PO\tLLR_FS\tLLR_D2\tMARKERS\n");
+    std::vector<int> order, best((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        if (status[i] != VB2_OK) continue;          // never searched: absent
+        order.clear();
+        for (int j = 0; j < n; ++j) {
+            const double* k = llr + ((size_t)i * n + j) * VB2_NUM_RELATION;
+            if (j == i || std::isnan(k[0])) continue;
+            int b = 0;
+            for (int r = 1; r < VB2_NUM_RELATION; ++r)
+                if (k[r] > k[b]) b = r;
+            best[(size_t)j] = b;
+            order.push_back(j);
+        }
+        const auto top_of = [&](int j) { return llr[((size_t)i * n + j) * VB2_NUM_RELATION + best[(size_t)j]]; };
+        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return top_of(x) > top_of(y); });
+        const int lim = std::min<int>(top, (int)order.size());
+        for (int r = 0; r < lim; ++r) {
+            const int j = order[(size_t)r];
+            const double* k = llr + ((size_t)i * n + j) * VB2_NUM_RELATION;
+            std::fprintf(f, "%s\t%s\t%d\t%s\t%g\t%g\t%g\t%g\t%g\t%d\n", names[i], names[j], r + 1,
+                         top_of(j) > 0 ? kName[best[(size_t)j]] : "UN", top_of(j), k[0], k[1], k[2], k[3], (int)shared[(size_t)i * n + j]);
         }
     }
     if (std::fclose(f) != 0) {
@@ -419,7 +573,7 @@ int vb2_ctx_marginals(vb2_ctx* ctx, const double* pc1, const double* pc2, double
     }
 }
 
-int vb2_source_set_create(int32_t num_marker, int32_t capacity, int32_t device, vb2_source_set** out)
+int vb2_source_set_create_ex(int32_t num_marker, int32_t capacity, int32_t device, int32_t planes, vb2_source_set** out)
 {
     if (!out) {
         set_error("vb2_source_set_create: out is NULL");
@@ -428,9 +582,54 @@ int vb2_source_set_create(int32_t num_marker, int32_t capacity, int32_t device, 
     *out = nullptr;
     try {
         vb2::SourceSet* s = nullptr;
-        if (const int rc = vb2::SourceSet::create(num_marker, capacity, device, &s)) return rc;
+        if (const int rc = vb2::SourceSet::create(num_marker, capacity, device, &s, planes)) return rc;
         *out = new vb2_source_set{s};
         return VB2_OK;
+    } catch (const std::bad_alloc&) {
+        set_error("out of host memory");
+        return VB2_ERR_NOMEM;
+    }
+}
+
+int vb2_source_set_create(int32_t num_marker, int32_t capacity, int32_t device, vb2_source_set** out)
+{
+    return vb2_source_set_create_ex(num_marker, capacity, device, VB2_SET_SOURCE, out);
+}
+
+int vb2_source_set_relations(vb2_source_set* set, double* llr, int32_t* shared)
+{
+    if (!set || !set->impl) {
+        set_error("vb2_source_set_relations: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    try {
+        return set->impl->relations(llr, shared);
+    } catch (const std::bad_alloc&) {
+        set_error("out of host memory");
+        return VB2_ERR_NOMEM;
+    }
+}
+
+int vb2_ctx_marginals_related(vb2_ctx* ctx, const double* pc1, const double* pc2, double alpha, double* own_lik, double* kin_post)
+{
+    if (!ctx || !ctx->impl) {
+        set_error("vb2_ctx_marginals_related: invalid context");
+        return VB2_ERR_INVALID;
+    }
+    try {
+        return ctx->impl->marginals(pc1, pc2, alpha, nullptr, nullptr, nullptr, nullptr, own_lik, kin_post);
+    } catch (const std::bad_alloc&) {
+        set_error("out of host memory");
+        return VB2_ERR_NOMEM;
+    }
+}
+
+// measurement aid (not in vb2_abi.h): tools/related_time.py
+int vb2_debug_related_time_pairs(vb2_source_set* set, int32_t n, uint32_t seed, int32_t warmup, int32_t reps, double* ms)
+{
+    if (!set || !set->impl) return VB2_ERR_INVALID;
+    try {
+        return set->impl->time_pairs(n, seed, warmup, reps, ms, true);
     } catch (const std::bad_alloc&) {
         set_error("out of host memory");
         return VB2_ERR_NOMEM;

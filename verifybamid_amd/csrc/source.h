@@ -1,5 +1,5 @@
-// source.h -- vb2_source_set internals (source.cpp): the float32 marginals of a cohort's samples on one device and
-// their pairwise source scores (source_kernels.hip).
+// source.h -- vb2_source_set internals (source.cpp): the float32 marginals of a cohort's samples on one device, their
+// pairwise source scores (source_kernels.hip) and their pairwise relatedness statistics (related_kernels.hip).
 #ifndef VB2_SOURCE_H_
 #define VB2_SOURCE_H_
 
@@ -10,12 +10,14 @@
 #include <vector>
 
 #include "context.h"
+#include "source_kernels.h"
 
 namespace vb2 {
 
 class SourceSet {
 public:
-    static int create(int num_marker, int capacity, int device, SourceSet** out);
+    // planes: VB2_SET_SOURCE (c q), VB2_SET_RELATED (q h t) or both (c q h t)
+    static int create(int num_marker, int capacity, int device, SourceSet** out, int planes = VB2_SET_SOURCE);
     ~SourceSet();
     // the next free slot (add) or a given one (put: a cohort's samples retire in any order); thread-safe
     int add(Context* ctx, const vb2_model& model, const vb2_estimate& est, int* index);
@@ -24,6 +26,9 @@ public:
     void set_count(int n);
     int count();
     int scores(double* score, int32_t* shared);
+    // K [n][n][4] and shared [n][n] of a set with the related planes (related_kernels.hip)
+    int relations(double* llr, int32_t* shared);
+    int planes() const { return planes_; }
     // what a set of hypotheses reads of a sample (conditioned.cpp): the q plane [num_marker][3] of the slot's device row,
     // nullptr = the slot holds none
     int device() const { return device_; }
@@ -32,16 +37,18 @@ public:
     {
         std::lock_guard<std::mutex> lk(mu_);
         if (slot < 0 || slot >= capacity_ || !rows_[(size_t)slot]) return nullptr;
-        return rows_[(size_t)slot] + 3 * (size_t)num_marker_;
+        return rows_[(size_t)slot] + q_offset_;
     }
     // Measurement aids (tools/source_time.py; event-timed, milliseconds per repetition into ms[reps]): the pair kernels
     // over n synthetic rows (seeded non-negative triples; what was in the set is overwritten), and the marginal kernel of
     // a context into slot 0 (the row's memset included, as an add pays it).
-    int time_pairs(int n, uint32_t seed, int warmup, int reps, double* ms);
+    int time_pairs(int n, uint32_t seed, int warmup, int reps, double* ms, bool related = false);
     int time_marginals(Context* ctx, double alpha, int warmup, int reps, double* ms);
 
 private:
-    int device_ = -1, num_marker_ = 0, capacity_ = 0, n_ = 0;
+    MarginalRelated planes_of(float* row) const;      // where the planes of a slot's row lie
+    int device_ = -1, num_marker_ = 0, capacity_ = 0, n_ = 0, planes_ = VB2_SET_SOURCE;
+    size_t row_floats_ = 0, q_offset_ = 0;            // floats of a row; where its q plane begins
     float* d_slab_ = nullptr;
     hipStream_t stream_ = nullptr;
     std::vector<const float*> rows_;         // [capacity] device rows, nullptr = none
@@ -51,6 +58,10 @@ private:
 // <prefix>.Sources (vb2_cohort_run_sources): per sample its `top` best candidates by descending score
 int write_sources(const std::string& prefix, int n, int top, const char* const* names, const vb2_run_result* res,
                   const int32_t* status, const double* score, const int32_t* shared);
+
+// <prefix>.Related (vb2_cohort_run_related): per searched sample its `top` partners by descending max_r K_r
+int write_related(const std::string& prefix, int n, int top, const char* const* names, const int32_t* status, const double* llr,
+                  const int32_t* shared);
 
 // <prefix>.SourceFit (vb2_cohort_run_source_fits): per searched sample with a first candidate the refit given it
 int write_source_fit(const std::string& prefix, int n, const char* const* names, const vb2_source_fit* fit);

@@ -37,6 +37,21 @@ constexpr int kPairLogBatch = 1;
 hipError_t launch_source_marginals(const DeviceLayout& L, int num_marker, const double* d_point, const int32_t* pidx,
                                    double* contam_lik, double* geno_post, double* log_l, float* row, hipStream_t stream);
 
+// What the marginal kernel's related instantiation writes besides contam_lik / geno_post / log_l: the
+// doubles own_lik = h and kin_post = t [M][3] in panel order, and the float32 planes [M][3] of a set row, each wherever the
+// set keeps it.  Any may be nullptr; zero-filled beforehand like the other outputs.
+struct MarginalRelated {
+    double* own_lik = nullptr;
+    double* kin_post = nullptr;
+    float* c = nullptr;
+    float* q = nullptr;
+    float* h = nullptr;
+    float* t = nullptr;
+};
+hipError_t launch_related_marginals(const DeviceLayout& L, int num_marker, const double* d_point, const int32_t* pidx,
+                                    double* contam_lik, double* geno_post, double* log_l, const MarginalRelated& rel,
+                                    hipStream_t stream);
+
 inline int source_num_stripe(int64_t num_marker) { return (int)((num_marker + kPairStripe - 1) / kPairStripe); }
 // entries of scratch (doubles in part_s, ints in part_n) for n samples
 inline size_t source_partial_count(int n, int64_t num_marker) { return (size_t)n * (size_t)n * (size_t)source_num_stripe(num_marker); }

@@ -35,11 +35,14 @@ constexpr int kRowDoubles = 9;
 // reach q (measured: 1.2e-4 relative on a marker 400 reads deep).  c_other, common to the nine, cancels in the ratios.
 constexpr double kPdScale = 0x1p900, kPdUnscale = 0x1p-900;
 
-template <bool PD>
+// REL (--FindRelated): the epilogue also forms h = q / GF2, the sample's own-genotype likelihood
+// relative to a random individual, and t = q T_p, the genotype distribution of a relative who shares one allele identical by
+// descent (p: the clamped allele frequency GF2 is formed from); the float32 planes then go where `rel` says, not to `row`.
+template <bool PD, bool REL>
 __global__ void __launch_bounds__(kThreads)
 source_marginal_kernel(const DeviceLayout L, const int num_marker, const double* __restrict__ point,
                        const int32_t* __restrict__ pidx, double* __restrict__ contam_lik, double* __restrict__ geno_post,
-                       double* __restrict__ log_l, float* __restrict__ row)
+                       double* __restrict__ log_l, float* __restrict__ row, const MarginalRelated rel)
 {
     extern __shared__ __attribute__((aligned(16))) double tab[];      // [nrow][kRowDoubles]
     const int tid = threadIdx.x;
@@ -180,13 +183,37 @@ source_marginal_kernel(const DeviceLayout L, const int num_marker, const double*
         for (int a = 0; a < 3; ++a) Ls += G1[a] * r0[a];
         if (!(Ls > 0)) continue;
         const size_t pm3 = (size_t)pm * 3;
-        for (int g = 0; g < 3; ++g) {
-            const double c = r0[g] / Ls, q = G2[g] * c0[g] / Ls;
-            if (contam_lik) contam_lik[pm3 + g] = c;
-            if (geno_post) geno_post[pm3 + g] = q;
-            if (row) {
-                row[pm3 + g] = (float)c;                                   // round to nearest
-                row[(size_t)num_marker * 3 + pm3 + g] = (float)q;
+        if constexpr (REL) {
+            double qq[3], hh[3], tt[3];
+            for (int g = 0; g < 3; ++g) {
+                const double c = r0[g] / Ls;
+                hh[g] = c0[g] / Ls;
+                qq[g] = G2[g] * c0[g] / Ls;                                // (the expression of the other instantiation)
+                if (contam_lik) contam_lik[pm3 + g] = c;
+                if (geno_post) geno_post[pm3 + g] = qq[g];
+                if (rel.c) rel.c[pm3 + g] = (float)c;
+                if (rel.q) rel.q[pm3 + g] = (float)qq[g];
+            }
+            // rows of T_p: (1 - p, p, 0), ((1 - p) / 2, 1 / 2, p / 2), (0, 1 - p, p)
+            const double p = clamp_af(af2), np = 1 - p;
+            tt[0] = qq[0] * np + qq[1] * (0.5 * np);
+            tt[1] = qq[0] * p + qq[1] * 0.5 + qq[2] * np;
+            tt[2] = qq[1] * (0.5 * p) + qq[2] * p;
+            for (int g = 0; g < 3; ++g) {
+                if (rel.own_lik) rel.own_lik[pm3 + g] = hh[g];
+                if (rel.kin_post) rel.kin_post[pm3 + g] = tt[g];
+                if (rel.h) rel.h[pm3 + g] = (float)hh[g];
+                if (rel.t) rel.t[pm3 + g] = (float)tt[g];
+            }
+        } else {
+            for (int g = 0; g < 3; ++g) {
+                const double c = r0[g] / Ls, q = G2[g] * c0[g] / Ls;
+                if (contam_lik) contam_lik[pm3 + g] = c;
+                if (geno_post) geno_post[pm3 + g] = q;
+                if (row) {
+                    row[pm3 + g] = (float)c;                                   // round to nearest
+                    row[(size_t)num_marker * 3 + pm3 + g] = (float)q;
+                }
             }
         }
         if (log_l) log_l[pm] = log(lk);
@@ -280,12 +307,30 @@ hipError_t launch_source_marginals(const DeviceLayout& L, int num_marker, const 
     const int nrow = L.num_code + 1;
     const size_t shmem = (size_t)nrow * kRowDoubles * sizeof(double);
     const dim3 grid((unsigned)stripe_grid(L, 1)), block(kThreads);
+    const MarginalRelated none{};
     if (L.pd)
-        hipLaunchKernelGGL(source_marginal_kernel<true>, grid, block, shmem, stream, L, num_marker, d_point, pidx, contam_lik,
-                           geno_post, log_l, row);
+        hipLaunchKernelGGL((source_marginal_kernel<true, false>), grid, block, shmem, stream, L, num_marker, d_point, pidx,
+                           contam_lik, geno_post, log_l, row, none);
     else
-        hipLaunchKernelGGL(source_marginal_kernel<false>, grid, block, shmem, stream, L, num_marker, d_point, pidx, contam_lik,
-                           geno_post, log_l, row);
+        hipLaunchKernelGGL((source_marginal_kernel<false, false>), grid, block, shmem, stream, L, num_marker, d_point, pidx,
+                           contam_lik, geno_post, log_l, row, none);
+    return hipGetLastError();
+}
+
+hipError_t launch_related_marginals(const DeviceLayout& L, int num_marker, const double* d_point, const int32_t* pidx,
+                                    double* contam_lik, double* geno_post, double* log_l, const MarginalRelated& rel,
+                                    hipStream_t stream)
+{
+    if (L.num_mt <= 0 || L.num_active <= 0) return hipSuccess;
+    const int nrow = L.num_code + 1;
+    const size_t shmem = (size_t)nrow * kRowDoubles * sizeof(double);
+    const dim3 grid((unsigned)stripe_grid(L, 1)), block(kThreads);
+    if (L.pd)
+        hipLaunchKernelGGL((source_marginal_kernel<true, true>), grid, block, shmem, stream, L, num_marker, d_point, pidx,
+                           contam_lik, geno_post, log_l, nullptr, rel);
+    else
+        hipLaunchKernelGGL((source_marginal_kernel<false, true>), grid, block, shmem, stream, L, num_marker, d_point, pidx,
+                           contam_lik, geno_post, log_l, nullptr, rel);
     return hipGetLastError();
 }
 

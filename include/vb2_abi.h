@@ -186,7 +186,8 @@ typedef struct vb2_model {
     int32_t is_af_known;       /* --KnownAF                    (main.cpp:314-319)  */
     double fix_alpha;          /* --FixAlpha value                                 */
     const double *fix_pc;      /* --FixPC values (num_pc) or NULL                  */
-    double epsilon;            /* --Epsilon, 1e-8 by default   (main.cpp:76)       */
+    double epsilon;            /* --Epsilon, 1e-8 by default   (main.cpp:76); a value that is not positive
+                                * (0 of a zero-initialised struct, negative, NaN) means that default */
     int32_t verbose;           /* --Verbose: per-evaluation notice (h:435-440)     */
     int32_t notices;           /* print the reference's stderr lines: PhaseTimer "Starting/Finished
                                 * phase" (ContaminationEstimator.cpp:10-24, 93-155) and the

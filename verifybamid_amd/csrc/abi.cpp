@@ -252,6 +252,22 @@ void vb2_debug_set_device_simplex(vb2_ctx* ctx, int on)
     ctx->impl->device_simplex_enabled = on != 0;
 }
 
+// ... and the largest simplex dimension the context's last resident kernel kept state for (Context::resident_nmax;
+// 0: none yet, the mode off, or 2 * num_pc + 1 beyond kDeviceSimplexMaxDim)
+int vb2_debug_resident_nmax(vb2_ctx* ctx)
+{
+    if (guard_ctx(ctx)) return -1;
+    return ctx->impl->resident_nmax;
+}
+
+// Test aid (no device): the point a device Minimize() of `status` hands back to the host's minimiser (estimator.cpp)
+void vb2_debug_minimize_handback(int status, int dim, const double* point, const double* start, double* out)
+{
+    std::vector<double> v;
+    vb2::minimize_handback(status, dim, point, start, &v);
+    std::copy(v.begin(), v.end(), out);
+}
+
 // Test aid: is the context in resident mode right now?
 // test hook (not in vb2_abi.h): `runs` OptimizeLLK searches over a caller's evaluator, advancing in
 // lock-step as fibers of this thread (lockstep.h: what cohorts and multi-start searches use), every

@@ -8,6 +8,7 @@
 //               [--min-BQ n] [--min-MQ n] [--adjust-MQ n] [--max-depth n] [--no-orphans]
 //               [--incl-flags n] [--excl-flags n]      (the reference's "Pileup Options", main.cpp:176-187: --BamFile only)
 //
+// --Epsilon e is the simplex's relative tolerance; a value that is not positive (0, negative, NaN) means the default 1e-8.
 // --BamFile needs a build with htslib (CMake finds it: bam_flatten.cpp); a build without it --
 // this image's -- reports that and suggests the reference's own --OutputPileup file with --PileupFile.
 // --RefVCF V [--NumSVDPCs k] [--SkipMinSampleCountCheck] [--IncludeChr a,b,..] [--GramSVD] builds a reference panel

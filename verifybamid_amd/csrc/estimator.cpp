@@ -175,6 +175,15 @@ Estimator::Estimator(int nPC, vb2_eval_fn eval, void* user)
     objective.fixPC2 = objective.globalPC = objective.globalPC2 = objective.fixPC;
 }
 
+// What a Minimize() that ran on the device leaves in the host's minimiser object: the minimum it found (status 1), or -- at
+// the cycle limit, status 2 -- the start: the reference leaves `point` untouched there (MathGenMin.cpp:380-383), and a
+// following phase starts from it.
+void minimize_handback(int status, int dim, const double* point, const double* start, std::vector<double>* out)
+{
+    const double* from = status == 1 ? point : start;
+    out->assign(from, from + dim);
+}
+
 // The whole Minimize() on the device when the context offers it (resident_kernel.inc): same
 // decisions, same evaluation batches, bit-identical trajectory; one host round trip.
 static bool device_minimizer(Estimator* e, AmoebaMinimizer& m, int dim, const std::vector<double>& start,
@@ -202,7 +211,7 @@ static bool device_minimizer(Estimator* e, AmoebaMinimizer& m, int dim, const st
         return false;                                     // the host optimiser takes this search
     }
     m.Reset(dim);
-    m.point.assign(rq.status == 1 ? rq.point : start.data(), (rq.status == 1 ? rq.point : start.data()) + dim);
+    minimize_handback(rq.status, dim, rq.point, start.data(), &m.point);
     m.cycleCount = rq.cycle_count;
     e->objective.llk1 = rq.out_llk1;
     e->objective.globalAlpha = rq.out_g_alpha;
@@ -217,16 +226,20 @@ static bool device_minimizer(Estimator* e, AmoebaMinimizer& m, int dim, const st
     return true;
 }
 
+// MathGenMin.cpp:381 through statgen's warning() (Error.cpp): "\n\aWARNING - \n", the message, "\n" -- its bytes
+static void cycle_limit_reached(Estimator* e, const AmoebaMinimizer& m)
+{
+    e->hit_cycle_limit = true;
+    if (e->notices)
+        std::fprintf(stderr, "\n\aWARNING - \nAmoeba.Minimize - Couldn't converge in %ld cycles\n", m.cycleMax);
+}
+
 static bool run_minimizer(Estimator* e, AmoebaMinimizer& m, int dim,
                           const std::vector<double>& start, double* ret)
 {
     bool dev_ok = false;
     if (device_minimizer(e, m, dim, start, ret, &dev_ok)) {
-        if (!dev_ok) {                                    // MathGenMin.cpp:381 (statgen warning())
-            e->hit_cycle_limit = true;
-            if (e->notices)
-                std::fprintf(stderr, "WARNING - Amoeba.Minimize - Couldn't converge in %ld cycles\n", m.cycleMax);
-        }
+        if (!dev_ok) cycle_limit_reached(e, m);
         return dev_ok;
     }
     m.func = &e->objective;
@@ -237,11 +250,7 @@ static bool run_minimizer(Estimator* e, AmoebaMinimizer& m, int dim,
     *ret = m.Minimize(e->epsilon);
     if (m.error && !e->error) e->error = m.error;
     const bool ok = *ret != std::numeric_limits<double>::max();
-    if (!ok) {                                            // MathGenMin.cpp:381 (statgen warning())
-        e->hit_cycle_limit = true;
-        if (e->notices)
-            std::fprintf(stderr, "WARNING - Amoeba.Minimize - Couldn't converge in %ld cycles\n", m.cycleMax);
-    }
+    if (!ok) cycle_limit_reached(e, m);
     return ok;
 }
 
@@ -416,7 +425,7 @@ void apply_model(Estimator& est, const vb2_model& model)
     est.verbose = model.verbose != 0;
     est.notices = model.notices != 0;
     est.isHeter = model.is_heter != 0;
-    if (model.epsilon > 0) est.epsilon = model.epsilon;
+    if (model.epsilon > 0) est.epsilon = model.epsilon;   // (0, negative, NaN: the default -- vb2_abi.h, vb2_model.epsilon)
     if (model.is_pc_fixed && model.fix_pc) {
         for (int i = 0; i < est.npc; ++i) est.coord[1][i] = model.fix_pc[i];
         est.isPCFixed = true;

@@ -100,6 +100,7 @@ void apply_model(Estimator& est, const vb2_model& model);
 // model says.  ONE place, used by every context-, batch- and shard-level optimise entry point.
 void apply_model(Estimator& est, const vb2_model& model, bool data_has_known_af);
 void fill_estimate(const Estimator& est, vb2_estimate* out);
+void minimize_handback(int status, int dim, const double* point, const double* start, std::vector<double>* out);
 
 }  // namespace vb2
 #endif

@@ -547,6 +547,35 @@ int vb2_cohort_run_source_fits(const vb2_cohort_args *args, int32_t top, vb2_run
                                int32_t *status /* [num_sample] */, double *score, int32_t *shared,
                                vb2_source_fit *fit /* [num_sample] or NULL */);
 
+/* vb2_cohort_run, then FREEMIX of every listed tumour given its matched normal (--MatchedNormal; 3e).
+ * Pair p is (tumour[p], normal[p]), sample indices of the cohort.  The normals get a q row in a source set; only the
+ * tumours' contexts stay on the device after their search (a NOTICE names the bytes); after the last sample every pair is
+ * refitted in ONE vb2_paired_optimize_llk -- pi2 = the normal's q where max(q[0], q[2]) >= hom_min, every other marker left
+ * out, pc2 held at the normal's intended PCs at its search point, alpha and pc1 searched -- and <output_prefix>.PairFit is
+ * written (tab-separated, %g, minus log-likelihoods as in .SourceFit):
+ *     #TUMOUR NORMAL NORMAL_FREEMIX MARKERS FREEMIX FREELK1 ALPHA_PAIRED LK1_PAIRED LK0_PAIRED
+ * A pair whose tumour or normal failed its own run is a row of NA (status VB2_PAIR_FIT_NONE) and changes no other row; a
+ * refit that fails leaves NA in the last three columns, gives a NOTICE and does not fail the run.  stdout, .selfSM and
+ * .Ancestry are what vb2_cohort_run writes.  VB2_ERR_INVALID before any file is read: an index out of range, a tumour listed
+ * twice, a sample paired with itself, hom_min outside [0, 1], is_alpha_fixed, more than one device. */
+#define VB2_PAIR_FIT_NONE 1            /* vb2_pair_fit.status: the tumour or the normal failed its own run */
+typedef struct vb2_pair_fit {
+    int32_t tumour, normal;    /* sample indices                                                                      */
+    int32_t markers;           /* markers of the tumour the refit walks (vb2_paired_info_get's given)                 */
+    int32_t status;            /* VB2_OK: refitted; VB2_PAIR_FIT_NONE; or the refit's error                           */
+    double normal_freemix;     /* the normal's anonymous fit: min(alpha, 1 - alpha)                                   */
+    double freemix, freelk1;   /* the tumour's anonymous fit                                                          */
+    double alpha_paired, lk1_paired, lk0_paired;           /* NAN where no refit ran                                  */
+} vb2_pair_fit;
+int vb2_cohort_run_paired(const vb2_cohort_args *args, int32_t num_pair, const int32_t *tumour, const int32_t *normal,
+                          double hom_min, vb2_run_result *out /* [num_sample] */, int32_t *status /* [num_sample] */,
+                          vb2_pair_fit *fits /* [num_pair] or NULL */);
+/* The --MatchedNormal file: lines "TUMOUR<TAB>NORMAL", each a pileup path exactly as in pileup_paths.  tumour / normal:
+ * [num_sample] (a tumour is listed once).  VB2_ERR_IO: the file cannot be read; VB2_ERR_INVALID with a message that names
+ * the line: a name that is not in the list, a tumour listed twice, a sample paired with itself, no pair at all.  Host only. */
+int vb2_matched_normal_read(const char *path, int32_t num_sample, const char *const *pileup_paths, int32_t *num_pair,
+                            int32_t *tumour, int32_t *normal);
+
 /* vb2_cohort_run that also computes every searched sample's interval (vb2_batch_interval: in lock-step, on a stage of its own
  * next to the search) and writes <prefix>.CI per sample; ci: [num_sample] or NULL.  A sample that failed its search or its
  * sanity check has no .CI (and a zeroed ci entry).  source_top > 0: --FindSource as well, what vb2_cohort_run_sources does
@@ -740,6 +769,67 @@ typedef int (*vb2_conditioned_eval_fn)(void *user, int32_t num_hyp, const int32_
                                        const double *pc2, const double *alpha, double *llk);
 int vb2_conditioned_lockstep(vb2_conditioned_eval_fn fn, void *user, int32_t num_hyp, int32_t num_pc, const vb2_model *model,
                              const double *pc1_fixed, vb2_estimate *est_out, int32_t *status);
+
+/* ------------------------------------------------------------------------- *
+ * 3e. The likelihood given genotype priors on BOTH components, with markers left out (DESIGN.md section 16;
+ *     --MatchedNormal).  Not in the reference.  In the notation of 3d, a pair hypothesis h carries two float32 triples per
+ *     panel marker, pi1_h[m] for the contaminant (g1) and pi2_h[m] for the intended sample (g2):
+ *         L_m(pc1, pc2, alpha | h) = sum_g1 P1[g1] sum_g2 P2[g2] W[g1][g2]
+ *             P1 = pi1_h[m] where that triple is not all zero, else GF1(pc1)[m]      (3d's rule)
+ *             P2 = pi2_h[m] where that triple is not all zero, else GF2(pc2)[m]
+ *             a marker whose pi2_h[m][0] is negative is LEFT OUT: not walked, adds nothing
+ *         LLK(. | h) = sum_m log L_m  over the walked markers with L_m > 0  (h:310)
+ *     With pi2 all zero and no marker left out this is vb2_conditioned_eval; with both all zero vb2_llk_eval_batch; with
+ *     both all zero on a set S and the rest left out vb2_replicates_eval under the 0/1 weights of S; LLK(pc1, pc2, alpha |
+ *     pi1 = a, pi2 = b) = LLK(pc2, pc1, 1 - alpha | pi1 = b, pi2 = a).  alpha is the share of the non-intended component,
+ *     reported as fitted and never folded at 0.5.
+ *     The paired refit of a tumour given its matched normal: pi1 all zero (an anonymous contaminant at a searched
+ *     ancestry), pi2 = the normal's genotype posterior q (3b) where the normal counts the marker and max(q[0], q[2]) >=
+ *     hom_min, every other marker left out -- a tumour's allelic imbalance at its heterozygous sites cannot pass for
+ *     contamination.  A wrong normal yields a meaningless alpha: identity is vb2_cohort_run_related's to check.
+ * ------------------------------------------------------------------------- */
+typedef struct vb2_paired vb2_paired;
+
+/* prior: [num_hyp][num_marker][6] float32 in panel order (num_marker = the context's), host memory: pi1[3] then pi2[3] per
+ * marker.  Uploaded once and permuted on the device into the context's marker order (six planes per hypothesis); device
+ * memory comes from the library's slab cache.  The context must outlive the set and must not be inside
+ * vb2_ctx_search_begin / vb2_ctx_search_end when the set is used. */
+int vb2_paired_create(vb2_ctx *ctx, int32_t num_hyp, const float *prior, vb2_paired **out);
+/* Hypothesis h = the paired rule on the q row of sample normal[h] of a source set (3b), device to device; hom_min within
+ * [0, 1] (0 keeps every marker the normal counts).  The set must be of the context's panel size and on the context's
+ * device, and the normal must have a row: VB2_ERR_INVALID otherwise. */
+int vb2_paired_create_from_set(vb2_ctx *ctx, vb2_source_set *set, int32_t num_hyp, const int32_t *normal, double hom_min,
+                               vb2_paired **out);
+void vb2_paired_destroy(vb2_paired *pair);
+/* One step: hypothesis h evaluates num_point[h] (0..VB2_BATCH_SLOTS) points; rows concatenated in hypothesis order as in
+ * vb2_conditioned_eval.  A point's value is the same bits whatever else the step holds and from call to call; a hypothesis
+ * that leaves every marker out evaluates to 0.0; an alpha outside [0, 1] leaves every marker out. */
+int vb2_paired_eval(vb2_paired *pair, const int32_t *num_point, const double *pc1, const double *pc2, const double *alpha,
+                    double *llk_out);
+/* The refit of every hypothesis of every set, all in ONE lock-step gang: the reference-exact OptimizeLLK under a copy of
+ * `model` with is_heter = 0, whose pc2 rows are overwritten with pc2_fixed on their way to the device, the llk0 call
+ * included -- alpha and the contaminant's PCs are searched (alpha alone with is_pc_fixed or known allele frequencies);
+ * is_alpha_fixed is VB2_ERR_INVALID.  pc2_fixed: [num_set][num_pc], one row per set.  Sets on different contexts overlap
+ * on the device.  est_out / status: [sum of num_hyp] in set order; est_out has alpha, pc1 (in pc and pc2), llk1 and llk0.
+ * status: VB2_OK, or VB2_ERR_INVALID for a hypothesis whose first evaluation is exactly 0.0 everywhere (no walked marker;
+ * the others finish).  All sets must share num_pc.  The return value: an error that concerns all. */
+int vb2_paired_optimize_llk(vb2_paired *const *sets, int32_t num_set, const vb2_model *model, const double *pc2_fixed,
+                            vb2_estimate *est_out, int32_t *status);
+typedef struct vb2_paired_info {
+    int32_t num_hyp;
+    int32_t num_marker;
+    int64_t device_bytes;      /* device memory the set holds beyond the context's                   */
+    int64_t num_step;          /* evaluations that reached the device (the searches' steps included)  */
+    int64_t num_launch;        /* marker-kernel launches of those steps                               */
+} vb2_paired_info;
+/* given [num_hyp] or NULL: the context's counted markers that hypothesis h does not leave out */
+int vb2_paired_info_get(const vb2_paired *pair, vb2_paired_info *info, int64_t *given);
+/* The same driver over a caller's evaluator: no device needed.  The pc2 rows fn sees are pc2_fixed [num_hyp][num_pc] at
+ * every call, the llk0 call included.  Non-zero from fn ends every search and is returned. */
+typedef int (*vb2_paired_eval_fn)(void *user, int32_t num_hyp, const int32_t *num_point, const double *pc1,
+                                  const double *pc2, const double *alpha, double *llk);
+int vb2_paired_lockstep(vb2_paired_eval_fn fn, void *user, int32_t num_hyp, int32_t num_pc, const vb2_model *model,
+                        const double *pc2_fixed, vb2_estimate *est_out, int32_t *status);
 
 /* Host-side flattening only (no device): reads panel + pileup, resolves markers
  * and returns the arrays of vb2_input in library-owned memory; free with

@@ -167,6 +167,8 @@ REPLICATES_EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_i
                                  C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double))
 # vb2_conditioned_eval_fn: (user, num_hyp, num_point, pc1, pc2, alpha, llk)
 CONDITIONED_EVAL_FN = REPLICATES_EVAL_FN
+# vb2_paired_eval_fn: the same
+PAIRED_EVAL_FN = REPLICATES_EVAL_FN
 VB2_BATCH_SLOTS = 8
 VB2_CHROM_NAME_LEN = 32
 
@@ -188,6 +190,19 @@ class SourceFit(C.Structure):
 
 
 class ConditionedInfo(C.Structure):
+    _fields_ = [("num_hyp", C.c_int32), ("num_marker", C.c_int32), ("device_bytes", C.c_int64), ("num_step", C.c_int64),
+                ("num_launch", C.c_int64)]
+
+
+VB2_PAIR_FIT_NONE = 1
+
+
+class PairFit(C.Structure):
+    _fields_ = [("tumour", C.c_int32), ("normal", C.c_int32), ("markers", C.c_int32), ("status", C.c_int32)] + \
+               [(n, C.c_double) for n in ("normal_freemix", "freemix", "freelk1", "alpha_paired", "lk1_paired", "lk0_paired")]
+
+
+class PairedInfo(C.Structure):
     _fields_ = [("num_hyp", C.c_int32), ("num_marker", C.c_int32), ("device_bytes", C.c_int64), ("num_step", C.c_int64),
                 ("num_launch", C.c_int64)]
 
@@ -219,6 +234,8 @@ SYMBOLS = [
     "vb2_run_replicates",
     "vb2_conditioned_create", "vb2_conditioned_create_from_set", "vb2_conditioned_destroy", "vb2_conditioned_eval",
     "vb2_conditioned_optimize_llk", "vb2_conditioned_info_get", "vb2_conditioned_lockstep", "vb2_cohort_run_source_fits",
+    "vb2_paired_create", "vb2_paired_create_from_set", "vb2_paired_destroy", "vb2_paired_eval", "vb2_paired_optimize_llk",
+    "vb2_paired_info_get", "vb2_paired_lockstep", "vb2_cohort_run_paired", "vb2_matched_normal_read",
 ]
 
 _lib = None
@@ -348,6 +365,21 @@ def lib():
     L.vb2_conditioned_lockstep.argtypes = [CONDITIONED_EVAL_FN, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Model), C.c_void_p,
                                            C.POINTER(Estimate), C.POINTER(C.c_int32)]
     L.vb2_debug_conditioned_time.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+    L.vb2_paired_create.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]
+    L.vb2_paired_create_from_set.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.POINTER(C.c_void_p)]
+    L.vb2_paired_destroy.argtypes = [C.c_void_p]
+    L.vb2_paired_destroy.restype = None
+    L.vb2_paired_eval.argtypes = [C.c_void_p] * 6
+    L.vb2_paired_optimize_llk.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(Model), C.c_void_p,
+                                          C.POINTER(Estimate), C.POINTER(C.c_int32)]
+    L.vb2_paired_info_get.argtypes = [C.c_void_p, C.POINTER(PairedInfo), C.c_void_p]
+    L.vb2_paired_lockstep.argtypes = [PAIRED_EVAL_FN, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Model), C.c_void_p,
+                                      C.POINTER(Estimate), C.POINTER(C.c_int32)]
+    L.vb2_cohort_run_paired.argtypes = [C.POINTER(CohortArgs), C.c_int32, C.c_void_p, C.c_void_p, C.c_double,
+                                        C.POINTER(RunResult), C.POINTER(C.c_int32), C.POINTER(PairFit)]
+    L.vb2_matched_normal_read.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_void_p,
+                                          C.c_void_p]
+    L.vb2_debug_paired_time.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     L.vb2_debug_replicates_time.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     L.vb2_debug_set_tunable.argtypes = [C.c_char_p, C.c_int]
     L.vb2_debug_get_tunable.argtypes = [C.c_char_p, C.POINTER(C.c_int)]

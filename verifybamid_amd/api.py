@@ -767,6 +767,129 @@ def conditioned_with_evaluator(evaluate, num_hyp, num_pc, pc1_fixed, known_af=Fa
     return [dict(_estimate_dict(est[h], k), status=int(status[h])) for h in range(H)]
 
 
+class Paired:
+    """vb2_paired: the likelihood of the ONE resident sample given genotype priors on BOTH components -- per hypothesis two
+    float32 triples per panel marker, pi1 for the contaminant and pi2 for the intended sample; an all-zero triple falls back
+    to that side's Hardy-Weinberg prior, a negative pi2[0] leaves the marker out.  prior: [H, M, 6] (pi1 | pi2); or
+    source_set=, normals= (indices into a SourceSet on the context's device) and hom_min=: hypothesis h is the matched-normal
+    rule on that sample's genotype posterior, built on the device."""
+    SLOTS = _abi.VB2_BATCH_SLOTS
+
+    def __init__(self, ctx: LikelihoodContext, prior=None, source_set=None, normals=None, hom_min=0.99):
+        self._lib = _abi.lib()
+        self.ctx = ctx
+        self.num_pc = ctx.num_pc
+        h = C.c_void_p()
+        if source_set is not None:
+            nrm = np.ascontiguousarray(np.atleast_1d(np.asarray(normals)), dtype=np.int32)
+            self.num_hyp = int(nrm.shape[0])
+            _abi.check(self._lib.vb2_paired_create_from_set(ctx._h, source_set._h, self.num_hyp, _p(nrm), float(hom_min),
+                                                            C.byref(h)), "vb2_paired_create_from_set")
+        else:
+            pr = np.asarray(prior)
+            if pr.ndim == 2:
+                pr = pr[None]
+            if pr.ndim != 3 or pr.shape[1:] != (ctx.data.num_marker, 6):
+                raise ValueError("prior must be [hypotheses, %d markers, 6]" % ctx.data.num_marker)
+            pr = np.ascontiguousarray(pr, dtype=np.float32)
+            self.num_hyp = int(pr.shape[0])
+            _abi.check(self._lib.vb2_paired_create(ctx._h, self.num_hyp, _p(pr), C.byref(h)), "vb2_paired_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.vb2_paired_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def info(self):
+        i = _abi.PairedInfo()
+        given = np.zeros(self.num_hyp, dtype=np.int64)
+        _abi.check(self._lib.vb2_paired_info_get(self._h, C.byref(i), _p(given)), "vb2_paired_info_get")
+        return dict(num_hyp=i.num_hyp, num_marker=i.num_marker, device_bytes=int(i.device_bytes), num_step=int(i.num_step),
+                    num_launch=int(i.num_launch), given=given)
+
+    def eval(self, num_point, pc1, pc2, alpha):
+        """One step (vb2_paired_eval): num_point [H] ints 0..8; pc1 / pc2 [P, k] and alpha [P] with P = sum(num_point),
+        the hypotheses' rows one after the other.  Returns llk [P]."""
+        k = self.num_pc
+        npt = np.ascontiguousarray(num_point, dtype=np.int32).reshape(self.num_hyp)
+        P = int(npt.sum())
+        pc1 = np.ascontiguousarray(np.asarray(pc1, dtype=np.float64).reshape(P, k))
+        pc2 = np.ascontiguousarray(np.asarray(pc2, dtype=np.float64).reshape(P, k))
+        alpha = np.ascontiguousarray(np.asarray(alpha, dtype=np.float64).reshape(P))
+        out = np.zeros(P)
+        _abi.check(self._lib.vb2_paired_eval(self._h, _p(npt), _p(pc1), _p(pc2), _p(alpha), _p(out)), "vb2_paired_eval")
+        return out
+
+    def optimize(self, pc2_fixed, **model_kw):
+        """The refit of every hypothesis in lock-step (Paired.optimize_sets on this set alone)."""
+        return Paired.optimize_sets([self], [pc2_fixed], **model_kw)[0]
+
+    @staticmethod
+    def optimize_sets(sets, pc2_fixed, **model_kw):
+        """vb2_paired_optimize_llk: the refits of every hypothesis of every set in ONE lock-step gang -- alpha and the
+        contaminant's PCs (alpha alone with fix_pc= or known allele frequencies), the intended sample's PCs held at
+        pc2_fixed[s] ([num_set, k]).  Returns per set a list of dicts (alpha, pc -- the contaminant's --, llk1, llk0,
+        "status")."""
+        L = _abi.lib()
+        k = sets[0].num_pc
+        S = len(sets)
+        fixed = np.ascontiguousarray(np.asarray(pc2_fixed, dtype=np.float64).reshape(S, k))
+        m, keep = _model(**model_kw)
+        H = sum(c.num_hyp for c in sets)
+        handles = (C.c_void_p * S)(*[c._h for c in sets])
+        est = (_abi.Estimate * H)()
+        status = (C.c_int32 * H)()
+        _abi.check(L.vb2_paired_optimize_llk(handles, S, C.byref(m), _p(fixed), est, status), "vb2_paired_optimize_llk")
+        del keep
+        out, at = [], 0
+        for c in sets:
+            out.append([dict(_estimate_dict(est[at + h], k), status=int(status[at + h])) for h in range(c.num_hyp)])
+            at += c.num_hyp
+        return out
+
+
+def paired_with_evaluator(evaluate, num_hyp, num_pc, pc2_fixed, known_af=False, **model_kw):
+    """The paired refits' lock-step driver over a Python evaluator (vb2_paired_lockstep): no device.
+    evaluate(num_point [H] int32, pc1 [P, k], pc2 [P, k], alpha [P]) -> llk [P], P = sum(num_point), called once per step
+    with the points of every hypothesis still searching; the pc2 rows are pc2_fixed [H, k] at every call.  Returns one dict
+    per hypothesis (with "status")."""
+    L = _abi.lib()
+    k, H = int(num_pc), int(num_hyp)
+    err = []
+
+    def cb(_user, nh, npt, p1, p2, a, out):
+        try:
+            num_point = np.ctypeslib.as_array(npt, (nh,)).copy()
+            P = int(num_point.sum())
+            res = evaluate(num_point, np.ctypeslib.as_array(p1, (P, k)).copy(), np.ctypeslib.as_array(p2, (P, k)).copy(),
+                           np.ctypeslib.as_array(a, (P,)).copy())
+            np.ctypeslib.as_array(out, (P,))[:] = np.asarray(res, dtype=np.float64).reshape(P)
+            return 0
+        except Exception as exc:   # never let an exception cross the C boundary
+            err.append(exc)
+            return _abi.VB2_ERR_INVALID
+    fn = _abi.PAIRED_EVAL_FN(cb)
+    fixed = np.ascontiguousarray(np.asarray(pc2_fixed, dtype=np.float64).reshape(H, k))
+    m, keep = _model(known_af=known_af, **model_kw)
+    est = (_abi.Estimate * H)()
+    status = (C.c_int32 * H)()
+    rc = L.vb2_paired_lockstep(fn, None, H, k, C.byref(m), _p(fixed), est, status)
+    del keep
+    if err:
+        raise err[0]
+    _abi.check(rc, "vb2_paired_lockstep")
+    return [dict(_estimate_dict(est[h], k), status=int(status[h])) for h in range(H)]
+
+
 def chromosome_weights(bed_path, num_marker=None):
     """The chromosomes of a panel's .bed as blocks, in order of first appearance (vb2_chromosome_weights): a dict with
     names, block_of [M], block_size (distinct positions per block) and the weight rows only / without [C, M] uint8.
@@ -978,7 +1101,8 @@ def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_san
 def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, disable_sanity=False,
                      known_af_path=None, device=-1, output_pileup=False, group_size=0, num_host_thread=0,
                      devices=None, find_source=False, source_top=3, sources_prefix=None, confidence_interval=False,
-                     refit_source=False, find_related=False, related_top=3, **model_kw):
+                     refit_source=False, find_related=False, related_top=3, matched_normal=None, normal_hom_min=0.99,
+                     **model_kw):
     """Many pileups against one panel (vb2_cohort_run): the panel is read once, the pileups are read
     and flattened by host threads while the device searches the previous group in lock-step.
     Returns one dict per sample (with its own "status" code).
@@ -994,14 +1118,20 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
     find_related (vb2_cohort_run_related; one device; may be combined with find_source, which then returns no score
     matrix; not with confidence_interval or refit_source): returns (samples, related), related = dict(llr [S, S, 4] in the
     order DUP, PO, FS, D2 -- row = target, column = partner --, shared [S, S]); with output_prefixes and sources_prefix it
-    writes <sources_prefix>.Related, related_top partners per sample."""
+    writes <sources_prefix>.Related, related_top partners per sample.
+    matched_normal (vb2_cohort_run_paired; one device; with none of the above): a list of (tumour, normal) sample indices;
+    returns (samples, fits), one dict per pair -- tumour, normal, markers, status (0: refitted, 1: the tumour or the normal
+    failed its own run, < 0: the refit's error), normal_freemix, freemix, freelk1, alpha_paired, lk1_paired, lk0_paired --
+    and with output_prefixes and sources_prefix <sources_prefix>.PairFit is written.  normal_hom_min: --NormalHomMin."""
     S = len(pileup_paths)
+    if matched_normal is not None and (find_source or find_related or confidence_interval or refit_source):
+        raise ValueError("matched_normal cannot be combined with find_source, find_related, confidence_interval or refit_source")
     if find_related and (confidence_interval or refit_source):
         raise ValueError("find_related cannot be combined with confidence_interval or refit_source")
     if refit_source and (not find_source or confidence_interval):
         raise ValueError("refit_source needs find_source and cannot be combined with confidence_interval")
     args, keep = _run_args(svd_prefix, pileup_paths[0], num_pc, disable_sanity, known_af_path,
-                           sources_prefix if find_source or find_related else None,
+                           sources_prefix if find_source or find_related or matched_normal is not None else None,
                            device, output_pileup, devices=devices, **model_kw)
     ca = _abi.CohortArgs()
     ca.base = args
@@ -1018,7 +1148,13 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
     status = (C.c_int32 * S)()
     score = shared = None
     civ = None
-    if find_related:
+    if matched_normal is not None:
+        pairs = np.ascontiguousarray(np.asarray(matched_normal, dtype=np.int32).reshape(-1, 2))
+        tum, nrm = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+        pfits = (_abi.PairFit * max(len(pairs), 1))()
+        _abi.check(_abi.lib().vb2_cohort_run_paired(C.byref(ca), len(pairs), _p(tum), _p(nrm), float(normal_hom_min), res, status,
+                                                    pfits), "vb2_cohort_run_paired")
+    elif find_related:
         llr, shared = np.zeros((S, S, _abi.VB2_NUM_RELATION)), np.zeros((S, S), dtype=np.int32)
         _abi.check(_abi.lib().vb2_cohort_run_related(C.byref(ca), int(related_top), int(source_top) if find_source else 0, res,
                                                      status, _p(llr), _p(shared)), "vb2_cohort_run_related")
@@ -1046,6 +1182,8 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
         if civ is not None and status[s] == _abi.VB2_OK:
             d["interval"] = _interval_dict(civ[s])
         out.append(d)
+    if matched_normal is not None:
+        return out, [{name: getattr(pfits[p], name) for name, _ in _abi.PairFit._fields_} for p in range(len(pairs))]
     if find_related:
         return out, dict(llr=llr, shared=shared)
     if refit_source:

@@ -104,6 +104,8 @@ int main(int argc, char** argv)
     int relatedTop = 3;
     bool perChromosome = false;
     int bootstrap = 0;
+    std::string MatchedNormal("Empty");
+    double normalHomMin = 0.99;
     // "Pileup Options" (main.cpp:176-187), defaults main.cpp:81-96 (MPLP_REALN | MPLP_SMART_OVERLAPS; UNMAP | SECONDARY |
     // QCFAIL | DUP): they shape what --BamFile input becomes and, as in the reference, do nothing to --PileupFile input
     int minBQ = 13, minMQ = 2, adjustMQ = 40, maxDepth = 8000, inclFlags = (1 << 4) | (1 << 10), exclFlags = 0x4 | 0x100 | 0x200 | 0x400;
@@ -175,6 +177,11 @@ int main(int argc, char** argv)
         // (<Output>.Boot): weighted-marker replicates of the one resident sample, searched in lock-step (vb2_run_replicates)
         {"PerChromosome", {Flag::kBool, &perChromosome, false}},
         {"Bootstrap", {Flag::kInt, &bootstrap, false}},
+        // not in the reference: FREEMIX of the tumours of a --PileupList cohort given their matched normals' genotypes
+        // (vb2_cohort_run_paired), to <Output>.PairFit.  File of lines "<tumour pileup>\t<normal pileup>", names as in the
+        // list; only the markers where the normal is homozygous with a posterior of at least --NormalHomMin are used
+        {"MatchedNormal", {Flag::kString, &MatchedNormal, false}},
+        {"NormalHomMin", {Flag::kDouble, &normalHomMin, false}},
     };
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
@@ -240,6 +247,25 @@ int main(int argc, char** argv)
         if (Devices != "Empty" && Devices.find(',') != std::string::npos)
             fatal("--FindRelated cannot be combined with more than one --Devices: a set of samples lives on one device");
         if (relatedTop < 1) fatal("--RelatedTop takes a positive number of partners");
+    }
+    if (MatchedNormal != "Empty") {                                     // a cohort on one device, a stage of its own
+        if (PileupList == "Empty")
+            fatal("--MatchedNormal needs --PileupList: tumours and normals are samples of one cohort run");
+        if (flags["FixAlpha"].seen)
+            fatal("--MatchedNormal cannot be combined with --FixAlpha: a fixed alpha leaves the refit nothing to estimate");
+        if (cohortInterval)
+            fatal("--MatchedNormal cannot be combined with --CohortInterval: run the intervals and the paired refits separately");
+        if (refitSource)
+            fatal("--MatchedNormal cannot be combined with --RefitSource: run the two refits separately");
+        if (findSource)
+            fatal("--MatchedNormal cannot be combined with --FindSource: run the source scores and the paired refits separately");
+        if (findRelated)
+            fatal("--MatchedNormal cannot be combined with --FindRelated: run the relatedness and the paired refits separately");
+        if (Devices != "Empty" && Devices.find(',') != std::string::npos)
+            fatal("--MatchedNormal cannot be combined with more than one --Devices: the normals' rows live on one device");
+        if (!(normalHomMin >= 0.0 && normalHomMin <= 1.0)) fatal("--NormalHomMin takes a probability within [0, 1]");
+    } else if (flags["NormalHomMin"].seen) {
+        fatal("--NormalHomMin needs --MatchedNormal");
     }
     if (findSource) {                                                   // a cohort on one device
         if (PileupList == "Empty")
@@ -397,7 +423,13 @@ int main(int argc, char** argv)
         ca.num_host_thread = nthread > 4 ? nthread : 0;               // --NumThread above its default: reader threads
         std::vector<vb2_run_result> cres(pile.size());
         std::vector<int32_t> cst(pile.size());
-        const int rcc = findRelated ? vb2_cohort_run_related(&ca, relatedTop, findSource ? sourceTop : 0, cres.data(), cst.data(), nullptr, nullptr)
+        std::vector<int32_t> tumour(pile.size()), normal(pile.size());
+        int32_t numPair = 0;
+        if (MatchedNormal != "Empty" &&         // (before the panel is read and any device is touched)
+            vb2_matched_normal_read(MatchedNormal.c_str(), ca.num_sample, cpile.data(), &numPair, tumour.data(), normal.data()) != VB2_OK)
+            fatal(vb2_last_error());
+        const int rcc = numPair > 0 ? vb2_cohort_run_paired(&ca, numPair, tumour.data(), normal.data(), normalHomMin, cres.data(), cst.data(), nullptr)
+                        : findRelated ? vb2_cohort_run_related(&ca, relatedTop, findSource ? sourceTop : 0, cres.data(), cst.data(), nullptr, nullptr)
                         : cohortInterval ? vb2_cohort_run_intervals(&ca, findSource ? sourceTop : 0, cres.data(), cst.data(), nullptr)
                         : refitSource ? vb2_cohort_run_source_fits(&ca, sourceTop, cres.data(), cst.data(), nullptr, nullptr, nullptr)
                         : findSource ? vb2_cohort_run_sources(&ca, sourceTop, cres.data(), cst.data(), nullptr, nullptr)

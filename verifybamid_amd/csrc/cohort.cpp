@@ -35,6 +35,7 @@
 #include "estimator.h"
 #include "hostio.h"
 #include "interval.h"
+#include "paired.h"
 #include "source.h"
 #include "stream_search.h"
 #include "tunables.h"
@@ -124,6 +125,24 @@ public:
         rel_shared_ = shared;
     }
 
+    // paired (vb2_cohort_run_paired; --MatchedNormal): the listed normals get a q row in a source set, the listed tumours'
+    // contexts are parked instead of destroyed, and after the last sample every pair is refitted (paired.h) --
+    // <Output>.PairFit, and fits[p] when fits is not null
+    void enable_paired(int num_pair, const int32_t* tumour, const int32_t* normal, double hom_min, vb2_pair_fit* fits)
+    {
+        paired_ = true;
+        pair_t_.assign(tumour, tumour + num_pair);
+        pair_n_.assign(normal, normal + num_pair);
+        hom_min_ = hom_min;
+        pair_fit_ = fits;
+        is_tumour_.assign((size_t)S_, 0);
+        is_normal_.assign((size_t)S_, 0);
+        for (int p = 0; p < num_pair; ++p) {
+            is_tumour_[(size_t)tumour[p]] = 1;
+            is_normal_[(size_t)normal[p]] = 1;
+        }
+    }
+
     ~CohortRunner()
     {
         shutdown();
@@ -163,9 +182,9 @@ public:
         const double t_warm = now_s();
         model_ = a_->base.model;
         if (panel_->isAFknown) model_.is_af_known = 1;
-        if (find_source_ || related_) {
+        if (find_source_ || related_ || paired_) {
             vb2::SourceSet* set = nullptr;
-            const int planes = (find_source_ ? VB2_SET_SOURCE : 0) | (related_ ? VB2_SET_RELATED : 0);
+            const int planes = (find_source_ || paired_ ? VB2_SET_SOURCE : 0) | (related_ ? VB2_SET_RELATED : 0);
             if (const int rcs = vb2::SourceSet::create((int)panel_->NumMarker, S_, devices_[0], &set, planes)) {
                 err_all_ = vb2::g_last_error;
                 return rcs;
@@ -204,8 +223,9 @@ public:
         shutdown();
         if (sources_ && find_source_ && !rc_all_) rc_all_ = finish_sources();
         if (sources_ && related_ && !rc_all_) rc_all_ = finish_related();
-        if (refit_) {
-            if (!rc_all_) rc_all_ = refit_sources();
+        if (refit_ || paired_) {
+            if (refit_ && !rc_all_) rc_all_ = refit_sources();
+            if (paired_ && !rc_all_) rc_all_ = refit_pairs();
             release_parked();
             drop_streams();
         }
@@ -362,7 +382,7 @@ private:
                 sl.ctx = nullptr;
             }
         vb2::g_flatten_thread_cap.store(0);
-        if (!refit_) drop_streams();                     // (--RefitSource: the parked contexts still run on them)
+        if (!refit_ && !paired_) drop_streams();         // (--RefitSource, --MatchedNormal: the parked contexts still run on them)
     }
 
     void drop_streams()
@@ -471,6 +491,109 @@ private:
         if (fit_) std::memcpy(fit_, fit.data(), sizeof(vb2_source_fit) * (size_t)S_);
         if (a_->output_prefixes && a_->base.output_prefix) {
             const int rc = vb2::write_source_fit(a_->base.output_prefix, S_, a_->output_prefixes, fit.data());
+            if (rc) {
+                err_all_ = vb2::g_last_error;
+                return rc;
+            }
+        }
+        return VB2_OK;
+    }
+
+    // --MatchedNormal (false without it: nothing else then differs from a plain run)
+    bool paired_ = false;
+    std::vector<int32_t> pair_t_, pair_n_;     // [pair] sample indices
+    std::vector<char> is_tumour_, is_normal_;  // [sample]
+    double hom_min_ = 0.99;
+    vb2_pair_fit* pair_fit_ = nullptr;
+
+    // --MatchedNormal, after the last sample: one refit per pair whose tumour and normal were both searched -- a
+    // one-hypothesis set on the tumour's parked context, built on the device from the normal's q row --, ALL in one lock-step
+    // call; fits[] and <Output>.PairFit.  A refit that fails leaves NA, gives a NOTICE and does not fail the run.
+    int refit_pairs()
+    {
+        const int k = a_->base.num_pc, P = (int)pair_t_.size();
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        std::vector<vb2_pair_fit> fit((size_t)P);
+        std::vector<std::unique_ptr<vb2::Paired>> sets;
+        std::vector<int> who;
+        std::vector<double> fixed;
+        if (parked_bytes_ > 0)
+            std::fprintf(stderr, "NOTICE - --MatchedNormal: the contexts of %d tumours stayed on the device for the refit (%lld bytes)\n",
+                         (int)std::count_if(parked_.begin(), parked_.end(), [](vb2_ctx* c) { return c != nullptr; }),
+                         (long long)parked_bytes_);
+        auto folded = [](double a) { return a < 0.5 ? a : 1 - a; };
+        for (int p = 0; p < P; ++p) {
+            const int t = pair_t_[(size_t)p], n = pair_n_[(size_t)p];
+            vb2_pair_fit& f = fit[(size_t)p];
+            std::memset(&f, 0, sizeof(f));
+            f.tumour = t;
+            f.normal = n;
+            f.status = VB2_PAIR_FIT_NONE;
+            f.normal_freemix = f.freemix = f.freelk1 = f.alpha_paired = f.lk1_paired = f.lk0_paired = nan;
+            if (status_[t] != VB2_OK || status_[n] != VB2_OK) {
+                std::fprintf(stderr, "NOTICE - --MatchedNormal: pair %d is not refitted: its %s failed (status %d)\n", p + 1,
+                             status_[t] != VB2_OK ? "tumour" : "normal", (int)(status_[t] != VB2_OK ? status_[t] : status_[n]));
+                continue;
+            }
+            const vb2_estimate& e = out_[n].est;
+            f.normal_freemix = folded(e.alpha);
+            f.freemix = folded(out_[t].est.alpha);
+            f.freelk1 = out_[t].est.llk1;
+            f.status = VB2_ERR_INVALID;
+            if ((size_t)t >= parked_.size() || !parked_[(size_t)t]) {
+                std::fprintf(stderr, "NOTICE - --MatchedNormal: pair %d is not refitted: the tumour's context is gone\n", p + 1);
+                continue;
+            }
+            // the normal's search point, as the source set took it (SourceSet::put): the swap of indices 0 and 1 undone,
+            // mirrored when alpha >= 0.5; its pc2 -- the intended sample's -- is what the refit holds
+            vb2::Context* c = parked_[(size_t)t]->impl;
+            const bool kaf = model_.is_af_known != 0 || c->L.known_af != nullptr;
+            const bool heter = model_.is_heter && !kaf;
+            std::vector<double> p1(e.pc, e.pc + k), p2(e.pc2, e.pc2 + k);
+            if (heter && e.alpha >= 0.5 && k >= 1) {
+                std::swap(p1[0], p2[0]);
+                if (k >= 2) std::swap(p1[1], p2[1]);
+            }
+            if (e.alpha >= 0.5) p1.swap(p2);
+            vb2::Paired* set = nullptr;
+            const int32_t nrm = n;
+            if (const int rc = vb2::Paired::create_from_set(c, sources_.get(), 1, &nrm, hom_min_, &set)) {
+                f.status = rc;
+                std::fprintf(stderr, "NOTICE - --MatchedNormal: pair %d is not refitted: %s\n", p + 1, vb2::g_last_error.c_str());
+                continue;
+            }
+            f.markers = (int32_t)set->given[0];
+            sets.emplace_back(set);
+            who.push_back(p);
+            fixed.insert(fixed.end(), p2.begin(), p2.end());
+        }
+        if (!sets.empty()) {
+            std::vector<vb2::Paired*> raw;
+            for (auto& q : sets) raw.push_back(q.get());
+            std::vector<vb2_estimate> est(sets.size());
+            std::vector<int32_t> st(sets.size(), VB2_ERR_INVALID);
+            const double t0 = now_s();
+            if (model_.notices)
+                std::fprintf(stderr, "NOTICE - Starting phase: Refit given the matched normal (%d searches in lock-step)\n", (int)sets.size());
+            const int rc = vb2::paired_optimize(raw.data(), (int)raw.size(), model_, fixed.data(), est.data(), st.data());
+            if (model_.notices)
+                std::fprintf(stderr, "NOTICE - Finished phase: Refit given the matched normal  [%.3f seconds]\n", now_s() - t0);
+            for (size_t i = 0; i < who.size(); ++i) {
+                vb2_pair_fit& f = fit[(size_t)who[i]];
+                f.status = rc ? rc : st[i];
+                if (f.status != VB2_OK) {
+                    std::fprintf(stderr, "NOTICE - --MatchedNormal: the refit of pair %d failed: %s\n", who[i] + 1, vb2::g_last_error.c_str());
+                    continue;
+                }
+                f.alpha_paired = est[i].alpha;
+                f.lk1_paired = est[i].llk1;
+                f.lk0_paired = est[i].llk0;
+            }
+            sets.clear();                               // before their contexts go
+        }
+        if (pair_fit_) std::memcpy(pair_fit_, fit.data(), sizeof(vb2_pair_fit) * (size_t)P);
+        if (a_->output_prefixes && a_->base.output_prefix) {
+            const int rc = vb2::write_pair_fit(a_->base.output_prefix, P, a_->pileup_paths, fit.data());
             if (rc) {
                 err_all_ = vb2::g_last_error;
                 return rc;
@@ -826,7 +949,20 @@ private:
                         if (!rw) rw = vb2::write_selfsm(prefix, *d.flat, d.est, true);   // (cohort input is text pileups: #READS = NA)
                         if (rw) status_[d.s] = rw;
                     }
-                    if (sources_ && d.add && d.ctx && d.ctx->impl && status_[d.s] == VB2_OK) {
+                    if (paired_) {
+                        // a searched normal gets its row; a searched tumour stays for the refit; the rest go as ever
+                        if (d.add && d.ctx && d.ctx->impl && status_[d.s] == VB2_OK) {
+                            if (is_normal_[(size_t)d.s] && sources_->put(d.s, d.ctx->impl, model_, d.est))
+                                std::fprintf(stderr, "NOTICE - --MatchedNormal: sample %d has no row in the source set: %s\n", d.s,
+                                             vb2::g_last_error.c_str());
+                            if (is_tumour_[(size_t)d.s]) {
+                                if (parked_.empty()) parked_.assign((size_t)S_, nullptr);
+                                parked_[(size_t)d.s] = d.ctx;
+                                parked_bytes_ += d.ctx->impl->device_bytes;
+                                d.ctx = nullptr;
+                            }
+                        }
+                    } else if (sources_ && d.add && d.ctx && d.ctx->impl && status_[d.s] == VB2_OK) {
                         // (a sample whose row cannot be made keeps its files and its status -- it was searched and written as
                         // the plain run does it --; its row and column of the matrix are NaN and a NOTICE says why)
                         if (sources_->put(d.s, d.ctx->impl, model_, d.est))
@@ -1099,6 +1235,42 @@ extern "C" int vb2_cohort_run_intervals(const vb2_cohort_args* a, int32_t source
     }
     try {
         CohortRunner runner(a, out, status, source_top > 0, source_top, nullptr, nullptr, true, ci);
+        const int rc = runner.run();
+        if (rc && !runner.error().empty()) set_error(runner.error());
+        return rc;
+    } catch (const std::bad_alloc&) {
+        set_error("out of host memory");
+        return VB2_ERR_NOMEM;
+    } catch (const std::exception& e) {
+        set_error(e.what());
+        return VB2_ERR_INVALID;
+    }
+}
+
+extern "C" int vb2_cohort_run_paired(const vb2_cohort_args* a, int32_t num_pair, const int32_t* tumour, const int32_t* normal,
+                                     double hom_min, vb2_run_result* out, int32_t* status, vb2_pair_fit* fits)
+{
+    if (!a || !out || !status || a->num_sample < 1 || !a->pileup_paths || !a->base.ud_path || !a->base.mean_path ||
+        !a->base.bed_path || a->base.num_pc < 1 || a->base.num_pc > VB2_MAX_PC || num_pair < 1 || !tumour || !normal) {
+        set_error("vb2_cohort_run_paired: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    if (a->base.num_device > 1 || a->base.num_device < 0) {
+        set_error("--MatchedNormal takes one device: the normals' rows and the refits given them are not spread over several --Devices");
+        return VB2_ERR_INVALID;
+    }
+    if (a->base.model.is_alpha_fixed) {
+        set_error("--MatchedNormal cannot be combined with --FixAlpha: a fixed alpha leaves the refit nothing to estimate");
+        return VB2_ERR_INVALID;
+    }
+    if (!(hom_min >= 0.0 && hom_min <= 1.0)) {
+        set_error("--NormalHomMin takes a probability within [0, 1]");
+        return VB2_ERR_INVALID;
+    }
+    if (const int rc = vb2::check_pairs("vb2_cohort_run_paired", a->num_sample, num_pair, tumour, normal)) return rc;
+    try {
+        CohortRunner runner(a, out, status);
+        runner.enable_paired(num_pair, tumour, normal, hom_min, fits);
         const int rc = runner.run();
         if (rc && !runner.error().empty()) set_error(runner.error());
         return rc;

@@ -964,7 +964,108 @@ void print_summary(const char* title, int numPC, const vb2_estimate& est)
     std::cout << "FREEMIX(Alpha):" << (est.alpha < 0.5 ? est.alpha : (1 - est.alpha)) << std::endl;
 }
 
+// <prefix>.PairFit (vb2_cohort_run_paired): one row per listed pair, in the file's order
+int write_pair_fit(const std::string& prefix, int num_pair, const char* const* names, const vb2_pair_fit* fit)
+{
+    const std::string name(prefix + ".PairFit");
+    std::FILE* f = std::fopen(name.c_str(), "w");
+    if (!f) return io_error("cannot write " + name);
+    std::fprintf(f, "#TUMOUR\tNORMAL\tNORMAL_FREEMIX\tMARKERS\tFREEMIX\tFREELK1\tALPHA_PAIRED\tLK1_PAIRED\tLK0_PAIRED\n");
+    for (int p = 0; p < num_pair; ++p) {
+        const vb2_pair_fit& s = fit[p];
+        std::fprintf(f, "%s\t%s", names[s.tumour], names[s.normal]);
+        if (s.status == VB2_PAIR_FIT_NONE) {
+            std::fprintf(f, "\tNA\tNA\tNA\tNA\tNA\tNA\tNA\n");
+            continue;
+        }
+        std::fprintf(f, "\t%g\t%d\t%g\t%g", s.normal_freemix, (int)s.markers, s.freemix, s.freelk1);
+        if (s.status == VB2_OK) std::fprintf(f, "\t%g\t%g\t%g\n", s.alpha_paired, s.lk1_paired, s.lk0_paired);
+        else std::fprintf(f, "\tNA\tNA\tNA\n");
+    }
+    if (std::fclose(f) != 0) return io_error("cannot write " + name);
+    return VB2_OK;
+}
+
+// what vb2_cohort_run_paired refuses in a list of pairs (vb2_matched_normal_read says the same of a file, by line)
+int check_pairs(const char* who, int num_sample, int num_pair, const int32_t* tumour, const int32_t* normal)
+{
+    std::vector<char> seen((size_t)std::max(num_sample, 0), 0);
+    for (int p = 0; p < num_pair; ++p) {
+        const int t = tumour[p], n = normal[p];
+        const std::string at = std::string(who) + ": pair " + std::to_string(p + 1) + ": ";
+        if (t < 0 || t >= num_sample || n < 0 || n >= num_sample) {
+            set_error(at + "a sample index outside the cohort");
+            return VB2_ERR_INVALID;
+        }
+        if (t == n) {
+            set_error(at + "a sample is paired with itself");
+            return VB2_ERR_INVALID;
+        }
+        if (seen[(size_t)t]) {
+            set_error(at + "the tumour is listed twice");
+            return VB2_ERR_INVALID;
+        }
+        seen[(size_t)t] = 1;
+    }
+    return VB2_OK;
+}
+
 }  // namespace vb2
+
+extern "C" int vb2_matched_normal_read(const char* path, int32_t num_sample, const char* const* pileup_paths, int32_t* num_pair,
+                                       int32_t* tumour, int32_t* normal)
+{
+    using vb2::set_error;
+    if (!path || num_sample < 1 || !pileup_paths || !num_pair || !tumour || !normal) {
+        set_error("vb2_matched_normal_read: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    *num_pair = 0;
+    std::ifstream in(path);
+    if (!in.is_open()) return vb2::io_error(std::string("cannot open the --MatchedNormal file ") + path);
+    auto find = [&](const std::string& name) {
+        for (int s = 0; s < num_sample; ++s)
+            if (pileup_paths[s] && name == pileup_paths[s]) return s;
+        return -1;
+    };
+    std::string line;
+    int lineno = 0, n = 0;
+    while (std::getline(in, line)) {
+        ++lineno;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty()) continue;
+        const std::string at = std::string("--MatchedNormal ") + path + " line " + std::to_string(lineno) + ": ";
+        const size_t tab = line.find('\t');
+        if (tab == std::string::npos || line.find('\t', tab + 1) != std::string::npos) {
+            set_error(at + "expected TUMOUR<TAB>NORMAL");
+            return VB2_ERR_INVALID;
+        }
+        const std::string tn = line.substr(0, tab), nn = line.substr(tab + 1);
+        const int t = find(tn), m = find(nn);
+        if (t < 0 || m < 0) {
+            set_error(at + "'" + (t < 0 ? tn : nn) + "' is not a pileup of the --PileupList");
+            return VB2_ERR_INVALID;
+        }
+        if (t == m) {
+            set_error(at + "'" + tn + "' is paired with itself");
+            return VB2_ERR_INVALID;
+        }
+        for (int p = 0; p < n; ++p)
+            if (tumour[p] == t) {
+                set_error(at + "the tumour '" + tn + "' is listed twice");
+                return VB2_ERR_INVALID;
+            }
+        tumour[n] = t;                     // (at most num_sample: a tumour is listed once)
+        normal[n] = m;
+        ++n;
+    }
+    if (n == 0) {
+        set_error(std::string("--MatchedNormal ") + path + " names no pair");
+        return VB2_ERR_INVALID;
+    }
+    *num_pair = n;
+    return VB2_OK;
+}
 
 // ContaminationEstimator.cpp:67-86, emitting panel-ordered offsets instead of
 // an index into the viewer: marker i owns [read_off[i], read_off[i+1]).

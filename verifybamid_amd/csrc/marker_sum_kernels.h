@@ -34,5 +34,21 @@ hipError_t launch_llk_weighted(const DeviceLayout& L, int num_point, const doubl
 hipError_t launch_llk_conditioned(const DeviceLayout& L, int num_point, const double* d_points, const int32_t* d_hyp,
                                   const float* d_planes, double* d_partial, double* d_out, hipStream_t stream);
 
+// The pair hypotheses of DESIGN.md section 16: floats of one hypothesis in the sorted order, six planes of m_pad (pi1[0..2],
+// pi2[0..2]).
+inline size_t paired_hyp_floats(const DeviceLayout& L) { return 6 * (size_t)L.m_pad; }
+// panel-order rows d_panel [num_hyp][num_marker][6] (pi1 | pi2) -> planes d_planes [num_hyp][6][m_pad]; the tiles' padding
+// and positions whose panel marker is out of range get 0 (no counted marker: never read).
+hipError_t launch_pair_permute(const DeviceLayout& L, int num_marker, int num_hyp, const float* d_panel, const int32_t* d_pidx,
+                               float* d_planes, hipStream_t stream);
+// ONE hypothesis's planes from the q plane d_q [num_marker][3] of a source set's row: pi1 all zero; pi2 = q where the triple
+// is not all zero and max(q[0], q[2]) >= hom_min; every other counted position left out (pi2 = -1, 0, 0).
+hipError_t launch_pair_build(const DeviceLayout& L, int num_marker, const float* d_q, const int32_t* d_pidx, double hom_min,
+                             float* d_planes, hipStream_t stream);
+// LLK(. | h) with a prior on either component: d_hyp[p] the hypothesis of point p in d_planes [..][6][m_pad]; a position
+// whose pi2[0] is negative is not walked.
+hipError_t launch_llk_paired(const DeviceLayout& L, int num_point, const double* d_points, const int32_t* d_hyp,
+                             const float* d_planes, double* d_partial, double* d_out, hipStream_t stream);
+
 }  // namespace vb2
 #endif

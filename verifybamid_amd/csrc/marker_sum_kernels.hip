@@ -11,6 +11,9 @@
 //   * PriorTerm: three coalesced floats of the point's hypothesis, P_h[m] (the genotype posterior of another sample of the
 //     cohort), in flight under the walk; where the triple is not all zero it stands in for the Hardy-Weinberg prior
 //     GF1(pc1); the term is log L.
+//   * PairTerm: six coalesced floats of the point's hypothesis, pi1_h[m] and pi2_h[m]; a negative
+//     pi2_h[m][0] leaves the marker out like a weight of 0; a triple that is not all zero stands in for GF1(pc1) or
+//     GF2(pc2); the term is log L.
 //   * llk_sum_marker_kernel<Term, PD, K>: one workgroup per (stripe of 16-tile groups, point).  It builds the point's table
 //     in LDS -- per table row the six off-diagonal genotype pairs' P^n (probability domain) or log p (run words) -- and
 //     one thread per marker walks the marker's steps or runs, forms L = G1' W GF2 in the reference's order (h:307-309)
@@ -23,6 +26,8 @@
 //   * weights_permute_kernel, prior_permute_kernel: the caller's rows (panel order) into the context's sorted order, once
 //     per set -- bytes [m_pad] per replicate; three planes [3][m_pad] per hypothesis (structure of arrays, so that the
 //     marker kernel's thread of sorted position tg * 256 + tid reads three coalesced floats).
+//   * pair_permute_kernel, pair_build_kernel: the six planes [6][m_pad] of a pair hypothesis, from the caller's rows
+//     [M][6] or, device to device, from the q plane of a source set's row under the rule of section 16.
 #include "marker_sum_kernels.h"
 
 #include "marker_walk.h"
@@ -36,7 +41,7 @@ constexpr int kRowDoubles = 6;                    // the six off-diagonal genoty
 
 // A Term: a marker's share of the sum, a small struct the kernel makes per marker from the point's row of its `rows`
 // argument (Row, row_elems) and holds by value.  walks() -- false: the marker is not walked --, then, behind the marker's
-// record, load(); prior() may replace G1 and value() turns L into what the marker adds.  (walks and load are two calls
+// record, load(); prior() may replace G1 and G2, and value() turns L into what the marker adds.  (walks and load are two calls
 // because the weight has to be read before the marker's record and the prior's triple behind it, inside the one branch:
 // folded into one call the prior term's loads get a branch of their own.)
 struct WeightTerm {
@@ -45,13 +50,13 @@ struct WeightTerm {
     const uint8_t* row;
     uint32_t w;
     __device__ __forceinline__ explicit WeightTerm(const uint8_t* r) : row(r) {}
-    __device__ __forceinline__ bool walks(bool counted, size_t pos)
+    __device__ __forceinline__ bool walks(bool counted, size_t pos, size_t)
     {
         w = counted ? (uint32_t)row[pos] : 0u;
         return w != 0u;
     }
     __device__ __forceinline__ void load(size_t, size_t) {}
-    __device__ __forceinline__ void prior(double*) const {}
+    __device__ __forceinline__ void prior(double*, double*) const {}
     __device__ __forceinline__ double value(double lk) const { return (double)w * log(lk); }
 };
 
@@ -61,16 +66,49 @@ struct PriorTerm {
     const float* row;
     float h0, h1, h2;
     __device__ __forceinline__ explicit PriorTerm(const float* r) : row(r) {}
-    __device__ __forceinline__ bool walks(bool counted, size_t) const { return counted; }   // no weights
+    __device__ __forceinline__ bool walks(bool counted, size_t, size_t) const { return counted; }   // no weights
     // the marker's triple: three coalesced floats, in flight under the walk
     __device__ __forceinline__ void load(size_t pos, size_t mp) { h0 = row[pos], h1 = row[mp + pos], h2 = row[2 * mp + pos]; }
     // an all-zero triple carries no information: the anonymous model's term, GF1 at the fixed pc1
-    __device__ __forceinline__ void prior(double* G1) const
+    __device__ __forceinline__ void prior(double* G1, double*) const
     {
         const bool given = h0 != 0.0f || h1 != 0.0f || h2 != 0.0f;
         G1[0] = given ? (double)h0 : G1[0];
         G1[1] = given ? (double)h1 : G1[1];
         G1[2] = given ? (double)h2 : G1[2];
+    }
+    __device__ __forceinline__ double value(double lk) const { return log(lk); }
+};
+
+struct PairTerm {
+    typedef float Row;                            // a pair hypothesis: six planes [6][mp], pi1[0..2] then pi2[0..2]
+    static __device__ __forceinline__ size_t row_elems(size_t mp) { return 6 * mp; }
+    const float* row;
+    float a0, a1, a2, b0, b1, b2;
+    __device__ __forceinline__ explicit PairTerm(const float* r) : row(r) {}
+    // a negative pi2[0] leaves the marker out of the hypothesis: read before the marker's record, like a weight
+    __device__ __forceinline__ bool walks(bool counted, size_t pos, size_t mp)
+    {
+        b0 = counted ? row[3 * mp + pos] : -1.0f;
+        return !(b0 < 0.0f);
+    }
+    // the other five floats, coalesced, in flight under the walk
+    __device__ __forceinline__ void load(size_t pos, size_t mp)
+    {
+        a0 = row[pos], a1 = row[mp + pos], a2 = row[2 * mp + pos];
+        b1 = row[4 * mp + pos], b2 = row[5 * mp + pos];
+    }
+    // either side's all-zero triple falls back to its Hardy-Weinberg prior
+    __device__ __forceinline__ void prior(double* G1, double* G2) const
+    {
+        const bool given1 = a0 != 0.0f || a1 != 0.0f || a2 != 0.0f;
+        const bool given2 = b0 != 0.0f || b1 != 0.0f || b2 != 0.0f;
+        G1[0] = given1 ? (double)a0 : G1[0];
+        G1[1] = given1 ? (double)a1 : G1[1];
+        G1[2] = given1 ? (double)a2 : G1[2];
+        G2[0] = given2 ? (double)b0 : G2[0];
+        G2[1] = given2 ? (double)b1 : G2[1];
+        G2[2] = given2 ? (double)b2 : G2[2];
     }
     __device__ __forceinline__ double value(double lk) const { return log(lk); }
 };
@@ -130,7 +168,7 @@ llk_sum_marker_kernel(const DeviceLayout L, const double* __restrict__ points, c
         const size_t pos = (size_t)mt * 16 + (size_t)m;
         double val = 0.0;
         Term term(row);
-        if (term.walks(mt < L.num_mt && pos < (size_t)L.num_active, pos)) {
+        if (term.walks(mt < L.num_mt && pos < (size_t)L.num_active, pos, mp)) {
             const uint2 rec = L.mt_rec[mt];
             term.load(pos, mp);
             double acc[6];
@@ -161,7 +199,7 @@ llk_sum_marker_kernel(const DeviceLayout L, const double* __restrict__ points, c
             double G1[3], G2[3], W[3][3];
             gf_of(af1, G1);
             gf_of(af2, G2);
-            term.prior(G1);
+            term.prior(G1, G2);
             const double cst = PD ? L.ediag[pos] : 0.0;
             for (int g = 0; g < 3; ++g) W[g][g] = L.ediag[(size_t)(1 + g) * mp + pos];
 #pragma unroll
@@ -233,6 +271,53 @@ prior_permute_kernel(const float* __restrict__ panel, const int32_t* __restrict_
     dst[0] = v0;
     dst[(size_t)m_pad] = v1;
     dst[2 * (size_t)m_pad] = v2;
+}
+
+// one thread per (hypothesis, sorted position): rows [M][6] of the panel order into six planes
+__global__ void __launch_bounds__(kThreads)
+pair_permute_kernel(const float* __restrict__ panel, const int32_t* __restrict__ pidx, float* __restrict__ planes,
+                    int num_marker, long long num_active, long long m_pad)
+{
+    const long long pos = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (pos >= m_pad) return;
+    const size_t h = blockIdx.y;
+    float v[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (pos < num_active) {
+        const int32_t i = pidx[pos];
+        if (i >= 0 && i < num_marker) {
+            const float* src = panel + (h * (size_t)num_marker + (size_t)i) * 6;
+#pragma unroll
+            for (int j = 0; j < 6; ++j) v[j] = src[j];
+        }
+    }
+    float* dst = planes + h * 6 * (size_t)m_pad + (size_t)pos;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) dst[(size_t)j * (size_t)m_pad] = v[j];
+}
+
+// one thread per sorted position of ONE hypothesis: the q plane [M][3] of a source set's row under the paired rule -- pi1
+// all zero; pi2 = q where the triple is not all zero and max(q[0], q[2]) >= hom_min; every other marker left out (-1, 0, 0)
+__global__ void __launch_bounds__(kThreads)
+pair_build_kernel(const float* __restrict__ q, const int32_t* __restrict__ pidx, float* __restrict__ planes, int num_marker,
+                  long long num_active, long long m_pad, double hom_min)
+{
+    const long long pos = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (pos >= m_pad) return;
+    float b0 = 0.0f, b1 = 0.0f, b2 = 0.0f;
+    if (pos < num_active) {
+        b0 = -1.0f;
+        const int32_t i = pidx[pos];
+        if (i >= 0 && i < num_marker) {
+            const float* src = q + (size_t)i * 3;
+            const float q0 = src[0], q1 = src[1], q2 = src[2];
+            const bool counted = q0 != 0.0f || q1 != 0.0f || q2 != 0.0f;
+            if (counted && (double)(q0 > q2 ? q0 : q2) >= hom_min) { b0 = q0; b1 = q1; b2 = q2; }
+        }
+    }
+    const size_t mp = (size_t)m_pad;
+    float* dst = planes + (size_t)pos;
+    dst[0] = 0.0f; dst[mp] = 0.0f; dst[2 * mp] = 0.0f;
+    dst[3 * mp] = b0; dst[4 * mp] = b1; dst[5 * mp] = b2;
 }
 
 template <class Term, bool PD, int K>
@@ -312,6 +397,28 @@ hipError_t launch_llk_conditioned(const DeviceLayout& L, int num_point, const do
                                   const float* d_planes, double* d_partial, double* d_out, hipStream_t stream)
 {
     return launch_llk_sum<PriorTerm>(L, num_point, d_points, d_hyp, d_planes, d_partial, d_out, stream);
+}
+
+hipError_t launch_pair_permute(const DeviceLayout& L, int num_marker, int num_hyp, const float* d_panel, const int32_t* d_pidx,
+                               float* d_planes, hipStream_t stream)
+{
+    return launch_permute(pair_permute_kernel, L, num_marker, num_hyp, d_panel, d_pidx, d_planes, stream);
+}
+
+hipError_t launch_pair_build(const DeviceLayout& L, int num_marker, const float* d_q, const int32_t* d_pidx, double hom_min,
+                             float* d_planes, hipStream_t stream)
+{
+    if (L.m_pad <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((L.m_pad + kThreads - 1) / kThreads));
+    hipLaunchKernelGGL(pair_build_kernel, grid, dim3(kThreads), 0, stream, d_q, d_pidx, d_planes, num_marker,
+                       (long long)L.num_active, (long long)L.m_pad, hom_min);
+    return hipGetLastError();
+}
+
+hipError_t launch_llk_paired(const DeviceLayout& L, int num_point, const double* d_points, const int32_t* d_hyp,
+                             const float* d_planes, double* d_partial, double* d_out, hipStream_t stream)
+{
+    return launch_llk_sum<PairTerm>(L, num_point, d_points, d_hyp, d_planes, d_partial, d_out, stream);
 }
 
 }  // namespace vb2

@@ -415,8 +415,8 @@ __device__ __forceinline__ int lane_of(int m, int g)
 // 0,3,5,6, of parity 1 in 1,2,4,7), i.e. quad j <-> 3 - j with the lane in the quad kept: a row rotation by 4 for the
 // quads 0 and 2, by 12 for 1 and 3 (tools/ubench/dpp_map.hip: row_ror:n gives lane i the value of lane i - n of its row)
 // -- two DPP moves with bank masks.  The exchange over 8 crosses rows and stays a ds_bpermute (as three VALU moves per dword
-// -- lane ^ 4, then v_permlane16_swap -- it was measured slower: HISTORY.md, round 4).  Multiplication commutes: the same bits
-// whatever the route.
+// -- lane ^ 4, then v_permlane16_swap -- it was measured slower: HISTORY.md, round 4; the split launches, whose LDS pipe is the
+// busier one now, take lane_pair8_u32 below instead).  Multiplication commutes: the same bits whatever the route.
 __device__ __forceinline__ int lane_xchg_i32(int x, int off, int partner)
 {
     if (off == 1) return __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xf, 0xf, true);     // quad_perm [1,0,3,2]
@@ -432,6 +432,27 @@ __device__ __forceinline__ double lane_xchg_f64(double x, int off, int partner)
     if (off == 1 || off == 2 || off == 4)
         return __hiloint2double(lane_xchg_i32(__double2hiint(x), off, partner), lane_xchg_i32(__double2loint(x), off, partner));
     return __shfl(x, partner, 64);
+}
+
+// The exchange over marker bit 3 as VALU moves (VB2_EPI_TRIPS part 4; the 8-point shape, where only the lane of marker 0 -- a
+// lane of an EVEN 16-lane row -- stores the tile's product).  Under lane_map a marker's partner over bit 3 sits in the other row
+// of its 32-lane half, at quad j ^ 1 of that row (slot parity 0: quads 0, 3 of the even row hold ranks 0, 1, quads 1, 2 of the
+// odd row ranks 2, 3; parity 1: quads 1, 2 and 0, 3).  So the ODD rows swap their quads j <-> j ^ 1 -- two DPP moves
+// under a row mask, the even rows keep their own --, and v_permlane16_swap puts the two rows' values side by
+// side: a lane of an even row holds {its own, its partner's}, in this order.  A lane of an odd row holds the same two values
+// as the even row's lane at its position: the odd rows become copies of the even ones, go through the later exchanges (all
+// inside a row) as such, and none of their lanes is stored.  The same two factors into the same multiply in every even-row
+// lane: the same bits as through ds_bpermute.
+__device__ __forceinline__ void lane_pair8_u32(unsigned x, unsigned& own, unsigned& other)
+{
+    // (row_half_mirror -- lane i <- lane 7 - i of its half row: quad j ^ 1 with its lanes reversed --, then the lanes of every quad
+    // reversed again: both moves read only their own result, so they work in place, where two bank-masked rotations of x each
+    // needed x itself -- a copy per dword)
+    const int a = __builtin_amdgcn_update_dpp((int)x, (int)x, 0x141, 0xa, 0xf, false);             // odd rows: row_half_mirror
+    const unsigned z = (unsigned)__builtin_amdgcn_update_dpp(a, a, 0x1B, 0xa, 0xf, false);         // odd rows: quad_perm [3,2,1,0]
+    const auto r = __builtin_amdgcn_permlane16_swap(z, z, false, false);      // [0]: the even row's value in both rows, [1]: the odd row's
+    own = r[0];
+    other = r[1];
 }
 
 // Occupancy target: one 1024-thread workgroup per CU (4 waves/SIMD, <=128 VGPRs).  Two
@@ -510,6 +531,14 @@ __host__ __device__ __forceinline__ bool eval_is_dynamic(const DeviceLayout& L, 
 // and the ring of row words has FIXED registers: a row's two table addresses are taken from its word before the refill is
 // loaded into the same register, so no loop of the walk begins or ends with a copy of a register that is being loaded.
 // (The item drawn a WHOLE item early -- round 4, above -- cost balance; this draw is one epilogue early.)
+// EPI (VB2_EPI_TRIPS; the same shape): a mask over the three dependent LDS round trips an item's epilogue makes while the
+// other fifteen waves' row reads fill the LDS queue.  1: the draw (ds_add_rtn) goes out behind the last row's twelve table reads and
+// before its multiplies -- LDS returns in order, so it is back with the row.  2: the 2 k projection coefficients are requested
+// directly behind the last row's multiplies, ahead of the draw's wait, the item -> tile arithmetic and the record's request.
+// 4: the butterfly's exchange over marker bit 3 as DPP moves and v_permlane16_swap (lane_pair8_u32) instead of ds_bpermute.
+// 8: as 1 with the draw in FRONT of the last row's reads.  (Shipped: 4 on the split launches, -1.2 %: it takes six instructions
+// per item off the LDS pipe.  1 and 8 measured slower -- the tile's last row on its own costs more than the draw's trip --, 2
+// without effect: the waves fill each other's epilogue holes.  HISTORY.md.)
 // PD: a probability-domain context (DeviceLayout::pd; llk_kernels.h, kMaxPow): the table holds P^n rows of class ref only,
 // a marker's list is one 16-bit row offset per step, ref steps first and alt steps behind them; the six sums are PRODUCTS,
 // class alt multiplies them with the row read the other way round (g -> 2 - g, h:164-177: T[alt][q][g1][g2] is T[ref][q][2-g1][2-g2]),
@@ -523,7 +552,7 @@ __host__ __device__ __forceinline__ bool eval_is_dynamic(const DeviceLayout& L, 
 // multiplied in the same order and its sum goes to the same word of the partial sums as in a plain launch of this grid:
 // the same bits, and no second pass over the tiles (llk_eval_passes_kernel: +4 us per pass at C3).
 template <int MODE, bool W16 = false, class Hook = NoHook, bool STREAM = false, int QUEUE = -1, int KSEL = 0,
-          bool LCACHE = false, int ESH = 8, bool PD = false, int SPLIT = 0, int RAHEAD = 0, int AHEAD = 0>
+          bool LCACHE = false, int ESH = 8, bool PD = false, int SPLIT = 0, int RAHEAD = 0, int AHEAD = 0, int EPI = 0>
 __device__ __forceinline__ void
 eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const double* __restrict__ points, int num_valid,
           double* __restrict__ partials, double* __restrict__ llk_out,
@@ -552,6 +581,13 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
     static_assert(AHEAD == 0 || (PD && MODE == 2 && QUEUE == 1 && !STREAM && !LCACHE && !W16 && std::is_same<Hook, NoHook>::value),
                   "items requested ahead: the 8-point probability-domain shape on the queue");
     constexpr bool kAhead = AHEAD != 0 && (kAblate & (kAblNoReads | kAblNoRowLoads)) == 0;      // (item_ahead; see the item loop)
+    static_assert(EPI == 0 || (PD && MODE == 2 && QUEUE == 1 && !STREAM && !LCACHE && !W16 && std::is_same<Hook, NoHook>::value),
+                  "the epilogue's trips: the 8-point probability-domain shape on the queue");
+    constexpr bool kEpiOn = EPI != 0 && (kAblate & (kAblNoReads | kAblNoMul | kAblNoEpi)) == 0;
+    // (the early draw sits between a row's reads and its multiplies -- walk_pd, a row at a time -- or, bit 8, in front of the reads)
+    constexpr bool kEpiDrawF = kEpiOn && (EPI & 8) != 0 && kAhead && (kReadsAhead == 1 || kReadsAhead >= 3);
+    constexpr bool kEpiDraw = kEpiOn && (EPI & 1) != 0 && kAhead && (kReadsAhead == 1 || kReadsAhead >= 3) && !kEpiDrawF;
+    constexpr bool kEpiX8 = kEpiOn && (EPI & 4) != 0;
     // (the run-word kernels of the static deal in the paired shapes: the layout's four sizes in scalar registers of their own.
     // Under those kernels' scalar pressure the register allocator gave up the {num_code, row_bytes, num_prim, num_mt} quad of the
     // kernel arguments, loaded it again at each of six uses and left the quad's spill slot behind: scratch memory set up for
@@ -1096,13 +1132,33 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
     // behind its own twelve reads and before its multiplies -- pre_tag -- and marker_lk finds them in registers: all 2 k quads
     // [3], or those of the first kCqK <= 2 components [4], the rest at the epilogue's head as before)
     constexpr bool kEpiAhead = (kReadsAhead == 3 || kReadsAhead == 4) && KSEL > 0 && BTL == 2;
-    constexpr int kCqK = !kEpiAhead ? 0 : (kReadsAhead == 3 || KSEL < 2) ? KSEL : 2;
-    constexpr int kCq = kEpiAhead ? 2 * kCqK : 1;
+    // (kEpiCoef, VB2_EPI_TRIPS part 2: all 2 k quads again, but requested BEHIND the last row's multiplies -- request_cq_late in the
+    // item loop --, when the row's landing registers are dead; kEpiDraw, part 1: the queue's ds_add_rtn rides where digits 3 and 4 put
+    // their coefficient reads, between the last row's reads and its multiplies, and nxt_early takes the draw)
+    constexpr bool kEpiCoef = kEpiOn && (EPI & 2) != 0 && KSEL > 0 && BTL == 2 && !kEpiAhead;
+    constexpr int kCqK = kEpiCoef ? KSEL : !kEpiAhead ? 0 : (kReadsAhead == 3 || KSEL < 2) ? KSEL : 2;
+    constexpr int kCq = kCqK > 0 ? 2 * kCqK : 1;
+    constexpr int kPreLds = (kEpiAhead ? kCq : 0) + (kEpiDraw ? 1 : 0);      // LDS requests a last row makes behind its own twelve
     vdouble2 cq[kCq];                           // {first sample's, second sample's} coefficient of component j at [2 j], [2 j + 1]
     uint32_t cq_addr = 0;
-    auto request_cq = [&]() {
+    uint32_t nxt_early = 0;
+    auto request_cq_late = [&]() {
 #pragma unroll
         for (int i = 0; i < kCq; ++i) cq[i] = *reinterpret_cast<lds_cdouble2*>(cq_addr + (uint32_t)((i & 1) * KSEL + (i >> 1)) * 16u);
+    };
+    auto draw_early = [&]() {
+        // (the queue's address through an opaque VECTOR register: an atomic on a uniform address is rewritten as a wave-wide
+        // count, one atomic and a broadcast -- which WAITS for the atomic where it stands, in front of the row's multiplies)
+        uint32_t qa = lds_byte_addr(queue);
+        asm volatile("" : "+v"(qa));
+        nxt_early = 0;
+        if (lane == 0)
+            nxt_early = __hip_atomic_fetch_add(reinterpret_cast<__attribute__((address_space(3))) unsigned int*>(qa), 1u, __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_WORKGROUP);
+    };
+    auto request_cq = [&]() {
+        if constexpr (kEpiDraw) draw_early();
+        if constexpr (kEpiAhead) request_cq_late();
     };
     // (pre_tag's bit 1, AHEAD 2: the caller has taken the word's two row addresses from it and passes THEM as w_cur and my_tab)
     auto walk_pd = [&](const uint32_t w_cur, double* acc, const uint32_t my_tab, auto alt0_tag, auto alt1_tag, auto first_tag, auto pre_tag) {
@@ -1140,10 +1196,14 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
             };
             // (0x100: LDS reads, 0x002: vector ALU; the groups of one id follow each other in this order)
             if constexpr (kReadsAhead == 1 || kReadsAhead == 3 || kReadsAhead == 4) {
-                request(0); request(1);
+                request(0);
+                // (EPI part 1: the draw's branch on the lane ends the block before the multiplies, where the group barriers below
+                // order nothing -- the first step's reads are kept first by hand)
+                if constexpr (kPre && kEpiDraw) __builtin_amdgcn_sched_barrier(0);
+                request(1);
                 if constexpr (kPre) request_cq();
                 multiply(0); multiply(1);
-                __builtin_amdgcn_sched_group_barrier(0x100, 6 * BTL + (kPre ? kCq : 0), 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 6 * BTL + (kPre ? kPreLds : 0), 0);
                 __builtin_amdgcn_sched_group_barrier(0x002, 12 * BTL, 0);
             } else {
                 // (each step a scheduling region of its own: with four groups in one region the scheduler mixed the steps)
@@ -1242,7 +1302,7 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
                 auto project = [&](int kk, double uu) {
                     if constexpr (BTL == 2) {              // both points' coefficient in one ds_read_b128
                         vdouble2 c1, c2;
-                        if (kEpiAhead && kk < kCqK) { c1 = cq[kCq > 1 ? 2 * kk : 0]; c2 = cq[kCq > 1 ? 2 * kk + 1 : 0]; }   // (requested under the tile's last row)
+                        if (kCqK > 0 && kk < kCqK) { c1 = cq[kCq > 1 ? 2 * kk : 0]; c2 = cq[kCq > 1 ? 2 * kk + 1 : 0]; }   // (requested under the tile's last row)
                         else {
                             c1 = *reinterpret_cast<lds_cdouble2*>(my_ptq + (uint32_t)kk * 16u);
                             c2 = *reinterpret_cast<lds_cdouble2*>(my_ptq + (uint32_t)(k + kk) * 16u);
@@ -1674,9 +1734,10 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
                 }
                 if (r < end) row_step(kS0, alt_tag, alt_tag, kNotFirst);
             };
-            if constexpr (kEpiAhead) {
+            if constexpr (kEpiCoef) cq_addr = my_ptq;
+            if constexpr (kEpiAhead || kEpiDraw || kEpiDrawF) {
                 // the tile's last row on its own, whichever kind it is (ref, the mixed row, alt) and whichever slot it has
-                cq_addr = my_ptq;
+                if constexpr (kEpiAhead) cq_addr = my_ptq;
                 const int last = rows - 1;
                 rows_of_kind(rows_ra < last ? rows_ra : last, kRef);
                 if ((steps_ref & 1) && r == rows_ra && r < last) {
@@ -1685,6 +1746,7 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
                 }
                 rows_of_kind(last, kAltT);
                 const std::true_type kPreT;
+                if constexpr (kEpiDrawF) draw_early();    // (EPI bit 8: in FRONT of the last row's reads; a tile of one row or none: where it always was)
                 if (r < rows) {                           // (r == last >= 1: never the first row)
                     if (r < rows_ra) {
                         if (r & 1) row_step_pre(kS1, kRef, kRef, kNotFirst, kPreT);
@@ -1697,7 +1759,7 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
                         else row_step_pre(kS0, kAltT, kAltT, kNotFirst, kPreT);
                     }
                 } else
-                    request_cq();                         // (a tile of one row or none: at the epilogue's head, as before)
+                    request_cq();                         // (a tile of one row or none: at the epilogue's head, as before; the draw too)
             } else {
             rows_of_kind(rows_ra, kRef);
             if ((steps_ref & 1) && r == rows_ra && r < rows) {
@@ -1736,8 +1798,17 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
 
         // AHEAD: the last row's multiplies are issued -- the next item is drawn and its record requested
         uint32_t idx_ah = nitem;
+        // (EPI part 2: the projection coefficients first, pinned between the last row's multiplies and everything below -- the
+        // draw's wait, the item -> tile arithmetic and the record's request run under their trip; part 1: the draw went out
+        // with the last row's reads and has arrived with them)
+        if constexpr (kEpiCoef) {
+            __builtin_amdgcn_sched_barrier(0);
+            request_cq_late();
+            __builtin_amdgcn_sched_barrier(0);
+        }
         if constexpr (kAhead) {
-            idx_ah = draw_item();
+            if constexpr (kEpiDraw || kEpiDrawF) idx_ah = (uint32_t)__builtin_amdgcn_readfirstlane(nxt_early);
+            else idx_ah = draw_item();
             request_rec_ahead(idx_ah);
         }
         __builtin_amdgcn_s_setprio(0);
@@ -1780,8 +1851,20 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
         // does not depend on whether it was evaluated alone, among four, or in a group of eight.
         // Butterfly over the 16 lanes that share slot g: mantissas multiply (16 factors in
         // [0.5, 1): no underflow), exponents add as integers (three dwords per exchange, not four)
+        if constexpr (kEpiX8) {
+            // (EPI part 4: the step over marker bit 3 without the LDS crossbar -- lane_pair8_u32; the steps over 4, 2, 1 follow below)
 #pragma unroll
-        for (int off = 8; off >= 1; off >>= 1) {
+            for (int t = 0; t < BTL; ++t) {
+                unsigned h0, h1, l0, l1, x0, x1;
+                lane_pair8_u32((unsigned)__double2hiint(lk_m[t]), h0, h1);
+                lane_pair8_u32((unsigned)__double2loint(lk_m[t]), l0, l1);
+                lane_pair8_u32((unsigned)lk_e[t], x0, x1);
+                lk_m[t] = __hiloint2double((int)h0, (int)l0) * __hiloint2double((int)h1, (int)l1);
+                lk_e[t] = (int)x0 + (int)x1;
+            }
+        }
+#pragma unroll
+        for (int off = kEpiX8 ? 4 : 8; off >= 1; off >>= 1) {
             const int partner = lane_of(m ^ off, g4);
 #pragma unroll
             for (int t = 0; t < BTL; ++t) {

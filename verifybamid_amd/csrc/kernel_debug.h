@@ -41,6 +41,20 @@
 //                         2 as 1, and the ring of row words has fixed registers: a row's two table addresses are taken from its word
 //                           before the refill is loaded into the same register -- no copy of a ring word in any loop of the walk
 //                       (default 0x02: -2.6 % on the 48-point launch; P measured faster, but not by three times the spread: HISTORY.md)
+//   VB2_EPI_TRIPS=0xPS  the three dependent LDS round trips of an item's epilogue in the 8-point probability-domain shape on the work queue
+//                       (eval_body, EPI), one hex digit per kernel family as for VB2_ITEM_AHEAD; each digit a MASK of three parts (bit 8: another
+//                       place for part 1):
+//                         1 the draw rides the last row's reads: the queue's ds_add_rtn goes out behind that row's twelve table reads and
+//                           before its multiplies, its result is taken behind them (needs VB2_ITEM_AHEAD != 0 in that family; a tile of
+//                           one row or none draws where it did)
+//                         2 the 2 k projection coefficients are requested directly behind the last row's multiplies -- its landing registers
+//                           are dead --, ahead of the next item's bookkeeping and the record's request (KSEL 2, 4)
+//                         4 the tile butterfly's exchange over marker bit 3 without the LDS crossbar: two row-masked DPP moves and a
+//                           v_permlane16_swap per dword instead of a ds_bpermute
+//                         8 part 1 with the draw in FRONT of the last row's reads: the lane-0 branch around the atomic then does not cut
+//                           the row's block between its reads and its multiplies (takes precedence over bit 1)
+//                       (default 0x04: -1.2 % on the 48-point launch.  Parts 1 and 8 measured SLOWER by 0.4 us -- the tile's last row on its own
+//                       costs more than the draw's trip --, part 2 without effect, digit P = 4 without effect: HISTORY.md)
 #ifndef VB2_KERNEL_DEBUG_H_
 #define VB2_KERNEL_DEBUG_H_
 
@@ -65,8 +79,11 @@
 #ifndef VB2_ITEM_AHEAD
 #define VB2_ITEM_AHEAD 0x02     // (profiles/r10/ab_item_head.txt)
 #endif
+#ifndef VB2_EPI_TRIPS
+#define VB2_EPI_TRIPS 0x04      // (profiles/r11/ab_epi_trips.txt)
+#endif
 #ifndef VB2_SIMD_DEAL
-#define VB2_SIMD_DEAL 1     // (0: wave w takes item w -- the A/B of the SIMD-balanced first deal, see eval_body)
+#define VB2_SIMD_DEAL 1    // (0: wave w takes item w -- the A/B of the SIMD-balanced first deal, see eval_body)
 #endif
 #ifndef VB2_STAMP_ROUND
 #define VB2_STAMP_ROUND 0
@@ -80,6 +97,8 @@ constexpr int kReadsAheadMask = VB2_READS_AHEAD;
 constexpr int reads_ahead(int family) { return (kReadsAheadMask >> (4 * family)) & 0xf; }      // family: 0 S, 1 P, 2 N, 3 R
 constexpr int kItemAheadMask = VB2_ITEM_AHEAD;
 constexpr int item_ahead(int family) { return (kItemAheadMask >> (4 * family)) & 0xf; }        // family: 0 S, 1 P
+constexpr int kEpiTripsMask = VB2_EPI_TRIPS;
+constexpr int epi_trips(int family) { return (kEpiTripsMask >> (4 * family)) & 0xf; }          // family: 0 S, 1 P
 }  // namespace vb2
 
 #ifdef VB2_WITH_STAMPS

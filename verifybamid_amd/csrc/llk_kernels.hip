@@ -25,7 +25,7 @@ llk_eval_kernel(const DeviceLayout L, const InlinePoints ip, const double* __res
                 unsigned int* __restrict__ ticket, unsigned long long* __restrict__ done_flag,
                 unsigned long long done_seq, int ngrp, unsigned long long tag, const Schedule sch)
 {
-    eval_body<MODE, false, NoHook, false, QUEUE, KSEL, false, 8, PD, 0, reads_ahead(MODE == 2 ? 1 : 2), (MODE == 2 && QUEUE == 1 && PD) ? item_ahead(1) : 0>(L, ip.v, ip.count, points, num_valid, partials, llk_out, ticket,
+    eval_body<MODE, false, NoHook, false, QUEUE, KSEL, false, 8, PD, 0, reads_ahead(MODE == 2 ? 1 : 2), (MODE == 2 && QUEUE == 1 && PD) ? item_ahead(1) : 0, (MODE == 2 && QUEUE == 1 && PD) ? epi_trips(1) : 0>(L, ip.v, ip.count, points, num_valid, partials, llk_out, ticket,
                                                                      done_flag, done_seq, blockIdx.x, gridDim.x, nullptr, 0u, ngrp, tag, sch);
 }
 
@@ -36,7 +36,7 @@ llk_eval_split_kernel(const DeviceLayout L, const double* __restrict__ points, i
                       double* __restrict__ llk_out, unsigned int* __restrict__ ticket, unsigned long long* __restrict__ done_flag,
                       unsigned long long done_seq, int ngrp)
 {
-    eval_body<2, false, NoHook, false, 1, KSEL, false, 8, true, S, reads_ahead(0), item_ahead(0)>(L, nullptr, 0, points, num_valid, partials, llk_out, ticket, done_flag,
+    eval_body<2, false, NoHook, false, 1, KSEL, false, 8, true, S, reads_ahead(0), item_ahead(0), epi_trips(0)>(L, nullptr, 0, points, num_valid, partials, llk_out, ticket, done_flag,
                                                                      done_seq, blockIdx.x, gridDim.x, nullptr, 0u, ngrp, 0ull,
                                                                      Schedule{nullptr, nullptr});
 }

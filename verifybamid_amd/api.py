@@ -509,6 +509,15 @@ class CohortBatch:
         return [dict(_interval_dict(ci[s]), status=int(status[s])) for s in range(S)]
 
 
+def _step_points(n, npt, p1, p2, a, k):
+    """What a lock-step driver hands a step's callback, as arrays of the callback's own: (num_point [n] int32, pc1 [P, k],
+    pc2 [P, k], alpha [P]) and P = sum(num_point)."""
+    num_point = np.ctypeslib.as_array(npt, (n,)).copy()
+    P = int(num_point.sum())
+    return (num_point, np.ctypeslib.as_array(p1, (P, k)).copy(), np.ctypeslib.as_array(p2, (P, k)).copy(),
+            np.ctypeslib.as_array(a, (P,)).copy()), P
+
+
 def intervals_with_evaluator(evaluate, num_pc, estimates, known_af=None, **model_kw):
     """The lock-step interval driver over a Python evaluator (vb2_intervals_lockstep): no device.
     evaluate(num_point [S] int32, pc1 [P, k], pc2 [P, k], alpha [P]) -> (llk [P], grad [P, 2k+1], hess [P, 2k+1, 2k+1]),
@@ -522,10 +531,8 @@ def intervals_with_evaluator(evaluate, num_pc, estimates, known_af=None, **model
 
     def cb(_user, ns, npt, p1, p2, a, llk, grad, hess):
         try:
-            num_point = np.ctypeslib.as_array(npt, (ns,)).copy()
-            P = int(num_point.sum())
-            res = evaluate(num_point, np.ctypeslib.as_array(p1, (P, k)).copy(), np.ctypeslib.as_array(p2, (P, k)).copy(),
-                           np.ctypeslib.as_array(a, (P,)).copy())
+            points, P = _step_points(ns, npt, p1, p2, a, k)
+            res = evaluate(*points)
             np.ctypeslib.as_array(llk, (P,))[:] = np.asarray(res[0], dtype=np.float64).reshape(P)
             np.ctypeslib.as_array(grad, (P, n))[:] = np.asarray(res[1], dtype=np.float64).reshape(P, n)
             np.ctypeslib.as_array(hess, (P, n, n))[:] = np.asarray(res[2], dtype=np.float64).reshape(P, n, n)
@@ -551,11 +558,92 @@ def intervals_with_evaluator(evaluate, num_pc, estimates, known_af=None, **model
     return [dict(_interval_dict(ci[s]), status=int(status[s])) for s in range(S)], int(steps.value)
 
 
-class Replicates:
+class _RowSet:
+    """What Replicates, Conditioned and Paired share: the life of the handle and one step.  A class says which entries are
+    its own (_NAME: vb2_<_NAME>_eval, vb2_<_NAME>_destroy) and which attribute holds its rows' number (_ROWS)."""
+    SLOTS = _abi.VB2_BATCH_SLOTS
+    _NAME = _ROWS = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._lib, "vb2_%s_destroy" % self._NAME)(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _eval(self, num_point, pc1, pc2, alpha):
+        k, where = self.num_pc, "vb2_%s_eval" % self._NAME
+        npt = np.ascontiguousarray(num_point, dtype=np.int32).reshape(getattr(self, self._ROWS))
+        P = int(npt.sum())
+        pc1 = np.ascontiguousarray(np.asarray(pc1, dtype=np.float64).reshape(P, k))
+        pc2 = np.ascontiguousarray(np.asarray(pc2, dtype=np.float64).reshape(P, k))
+        alpha = np.ascontiguousarray(np.asarray(alpha, dtype=np.float64).reshape(P))
+        out = np.zeros(P)
+        _abi.check(getattr(self._lib, where)(self._h, _p(npt), _p(pc1), _p(pc2), _p(alpha), _p(out)), where)
+        return out
+
+
+def _optimize_sets(symbol, sets, fixed, **model_kw):
+    """vb2_conditioned_optimize_llk / vb2_paired_optimize_llk (`symbol`) over `sets`, their held PCs fixed [num_set, k]:
+    per set a list of dicts, one per hypothesis (with "status")."""
+    k = sets[0].num_pc
+    S = len(sets)
+    fixed = np.ascontiguousarray(np.asarray(fixed, dtype=np.float64).reshape(S, k))
+    m, keep = _model(**model_kw)
+    H = sum(c.num_hyp for c in sets)
+    handles = (C.c_void_p * S)(*[c._h for c in sets])
+    est = (_abi.Estimate * H)()
+    status = (C.c_int32 * H)()
+    _abi.check(getattr(_abi.lib(), symbol)(handles, S, C.byref(m), _p(fixed), est, status), symbol)
+    del keep
+    out, at = [], 0
+    for c in sets:
+        out.append([dict(_estimate_dict(est[at + h], k), status=int(status[at + h])) for h in range(c.num_hyp)])
+        at += c.num_hyp
+    return out
+
+
+def _rows_with_evaluator(fn_type, symbol, evaluate, n, k, fixed, known_af, **model_kw):
+    """A lock-step driver over a Python evaluator (`symbol`: vb2_replicates_lockstep, vb2_conditioned_lockstep,
+    vb2_paired_lockstep; its callback type fn_type): n rows, fixed [n, k] the held PCs or None where the driver takes
+    none.  One dict per row (with "status")."""
+    k, n = int(k), int(n)
+    err = []
+
+    def cb(_user, rows, npt, p1, p2, a, out):
+        try:
+            points, P = _step_points(rows, npt, p1, p2, a, k)
+            np.ctypeslib.as_array(out, (P,))[:] = np.asarray(evaluate(*points), dtype=np.float64).reshape(P)
+            return 0
+        except Exception as exc:   # never let an exception cross the C boundary
+            err.append(exc)
+            return _abi.VB2_ERR_INVALID
+    fn = fn_type(cb)
+    if fixed is not None:
+        fixed = np.ascontiguousarray(np.asarray(fixed, dtype=np.float64).reshape(n, k))
+    held = [] if fixed is None else [_p(fixed)]
+    m, keep = _model(known_af=known_af, **model_kw)
+    est = (_abi.Estimate * n)()
+    status = (C.c_int32 * n)()
+    rc = getattr(_abi.lib(), symbol)(fn, None, n, k, C.byref(m), *held, est, status)
+    del keep
+    if err:
+        raise err[0]
+    _abi.check(rc, symbol)
+    return [dict(_estimate_dict(est[r], k), status=int(status[r])) for r in range(n)]
+
+
+class Replicates(_RowSet):
     """vb2_replicates: many integer weight vectors ("replicates") over the ONE resident copy of a sample -- the
     log-likelihood under marker weights, LLK_w = sum_i w_i log L_i, evaluated for all of them together and searched in
     lock-step.  weights: [R, M] counts 0..255 in panel order (chromosome_weights, bootstrap_weights, or the caller's)."""
-    SLOTS = _abi.VB2_BATCH_SLOTS
+    _NAME, _ROWS = "replicates", "num_rep"
 
     def __init__(self, ctx: LikelihoodContext, weights):
         self._lib = _abi.lib()
@@ -572,19 +660,6 @@ class Replicates:
         _abi.check(self._lib.vb2_replicates_create(ctx._h, self.num_rep, _p(w), C.byref(h)), "vb2_replicates_create")
         self._h = h
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.vb2_replicates_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
     def info(self):
         i = _abi.ReplicatesInfo()
         counted = np.zeros(self.num_rep, dtype=np.int64)
@@ -595,15 +670,7 @@ class Replicates:
     def eval(self, num_point, pc1, pc2, alpha):
         """One step (vb2_replicates_eval): num_point [R] ints 0..8; pc1 / pc2 [P, k] and alpha [P] with P = sum(num_point),
         the replicates' rows one after the other.  Returns llk [P]."""
-        k = self.num_pc
-        npt = np.ascontiguousarray(num_point, dtype=np.int32).reshape(self.num_rep)
-        P = int(npt.sum())
-        pc1 = np.ascontiguousarray(np.asarray(pc1, dtype=np.float64).reshape(P, k))
-        pc2 = np.ascontiguousarray(np.asarray(pc2, dtype=np.float64).reshape(P, k))
-        alpha = np.ascontiguousarray(np.asarray(alpha, dtype=np.float64).reshape(P))
-        out = np.zeros(P)
-        _abi.check(self._lib.vb2_replicates_eval(self._h, _p(npt), _p(pc1), _p(pc2), _p(alpha), _p(out)), "vb2_replicates_eval")
-        return out
+        return self._eval(num_point, pc1, pc2, alpha)
 
     def optimize(self, **model_kw):
         """OptimizeLLK of every replicate in lock-step (vb2_replicates_optimize_llk): one dict per replicate with its own
@@ -620,39 +687,16 @@ def replicates_with_evaluator(evaluate, num_rep, num_pc, known_af=False, **model
     """The replicates' lock-step driver over a Python evaluator (vb2_replicates_lockstep): no device.
     evaluate(num_point [R] int32, pc1 [P, k], pc2 [P, k], alpha [P]) -> llk [P], P = sum(num_point), called once per step
     with the points of every replicate still searching.  Returns one dict per replicate (with "status")."""
-    L = _abi.lib()
-    k, R = int(num_pc), int(num_rep)
-    err = []
-
-    def cb(_user, nr, npt, p1, p2, a, out):
-        try:
-            num_point = np.ctypeslib.as_array(npt, (nr,)).copy()
-            P = int(num_point.sum())
-            res = evaluate(num_point, np.ctypeslib.as_array(p1, (P, k)).copy(), np.ctypeslib.as_array(p2, (P, k)).copy(),
-                           np.ctypeslib.as_array(a, (P,)).copy())
-            np.ctypeslib.as_array(out, (P,))[:] = np.asarray(res, dtype=np.float64).reshape(P)
-            return 0
-        except Exception as exc:   # never let an exception cross the C boundary
-            err.append(exc)
-            return _abi.VB2_ERR_INVALID
-    fn = _abi.REPLICATES_EVAL_FN(cb)
-    m, keep = _model(known_af=known_af, **model_kw)
-    est = (_abi.Estimate * R)()
-    status = (C.c_int32 * R)()
-    rc = L.vb2_replicates_lockstep(fn, None, R, k, C.byref(m), est, status)
-    del keep
-    if err:
-        raise err[0]
-    _abi.check(rc, "vb2_replicates_lockstep")
-    return [dict(_estimate_dict(est[r], k), status=int(status[r])) for r in range(R)]
+    return _rows_with_evaluator(_abi.REPLICATES_EVAL_FN, "vb2_replicates_lockstep", evaluate, num_rep, num_pc, None, known_af,
+                                **model_kw)
 
 
-class Conditioned:
+class Conditioned(_RowSet):
     """vb2_conditioned: the likelihood of the ONE resident sample given a hypothesised contaminant -- per hypothesis one
     genotype triple per panel marker (float32, panel order) in place of the Hardy-Weinberg prior of the alpha-fraction
     component; an all-zero triple falls back to that prior.  prior: [H, M, 3]; or source_set= and candidates= (indices
     into a SourceSet on the context's device): hypothesis h is the genotype posterior of that sample, copied on the device."""
-    SLOTS = _abi.VB2_BATCH_SLOTS
+    _NAME, _ROWS = "conditioned", "num_hyp"
 
     def __init__(self, ctx: LikelihoodContext, prior=None, source_set=None, candidates=None):
         self._lib = _abi.lib()
@@ -675,19 +719,6 @@ class Conditioned:
             _abi.check(self._lib.vb2_conditioned_create(ctx._h, self.num_hyp, _p(pr), C.byref(h)), "vb2_conditioned_create")
         self._h = h
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.vb2_conditioned_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
     def info(self):
         i = _abi.ConditionedInfo()
         _abi.check(self._lib.vb2_conditioned_info_get(self._h, C.byref(i)), "vb2_conditioned_info_get")
@@ -697,15 +728,7 @@ class Conditioned:
     def eval(self, num_point, pc1, pc2, alpha):
         """One step (vb2_conditioned_eval): num_point [H] ints 0..8; pc1 / pc2 [P, k] and alpha [P] with P = sum(num_point),
         the hypotheses' rows one after the other.  Returns llk [P]."""
-        k = self.num_pc
-        npt = np.ascontiguousarray(num_point, dtype=np.int32).reshape(self.num_hyp)
-        P = int(npt.sum())
-        pc1 = np.ascontiguousarray(np.asarray(pc1, dtype=np.float64).reshape(P, k))
-        pc2 = np.ascontiguousarray(np.asarray(pc2, dtype=np.float64).reshape(P, k))
-        alpha = np.ascontiguousarray(np.asarray(alpha, dtype=np.float64).reshape(P))
-        out = np.zeros(P)
-        _abi.check(self._lib.vb2_conditioned_eval(self._h, _p(npt), _p(pc1), _p(pc2), _p(alpha), _p(out)), "vb2_conditioned_eval")
-        return out
+        return self._eval(num_point, pc1, pc2, alpha)
 
     def optimize(self, pc1_fixed, **model_kw):
         """The refit of every hypothesis in lock-step (Conditioned.optimize_sets on this set alone)."""
@@ -716,22 +739,7 @@ class Conditioned:
         """vb2_conditioned_optimize_llk: the refits of every hypothesis of every set in ONE lock-step gang -- alpha and the
         intended sample's PCs (alpha alone with fix_pc= or known allele frequencies), the contaminant's PCs held at
         pc1_fixed[s] ([num_set, k]).  Returns per set a list of dicts (alpha, pc2 -- also in pc --, llk1, llk0, "status")."""
-        L = _abi.lib()
-        k = sets[0].num_pc
-        S = len(sets)
-        fixed = np.ascontiguousarray(np.asarray(pc1_fixed, dtype=np.float64).reshape(S, k))
-        m, keep = _model(**model_kw)
-        H = sum(c.num_hyp for c in sets)
-        handles = (C.c_void_p * S)(*[c._h for c in sets])
-        est = (_abi.Estimate * H)()
-        status = (C.c_int32 * H)()
-        _abi.check(L.vb2_conditioned_optimize_llk(handles, S, C.byref(m), _p(fixed), est, status), "vb2_conditioned_optimize_llk")
-        del keep
-        out, at = [], 0
-        for c in sets:
-            out.append([dict(_estimate_dict(est[at + h], k), status=int(status[at + h])) for h in range(c.num_hyp)])
-            at += c.num_hyp
-        return out
+        return _optimize_sets("vb2_conditioned_optimize_llk", sets, pc1_fixed, **model_kw)
 
 
 def conditioned_with_evaluator(evaluate, num_hyp, num_pc, pc1_fixed, known_af=False, **model_kw):
@@ -739,41 +747,17 @@ def conditioned_with_evaluator(evaluate, num_hyp, num_pc, pc1_fixed, known_af=Fa
     evaluate(num_point [H] int32, pc1 [P, k], pc2 [P, k], alpha [P]) -> llk [P], P = sum(num_point), called once per step
     with the points of every hypothesis still searching; the pc1 rows are pc1_fixed [H, k] at every call.  Returns one dict
     per hypothesis (with "status")."""
-    L = _abi.lib()
-    k, H = int(num_pc), int(num_hyp)
-    err = []
-
-    def cb(_user, nh, npt, p1, p2, a, out):
-        try:
-            num_point = np.ctypeslib.as_array(npt, (nh,)).copy()
-            P = int(num_point.sum())
-            res = evaluate(num_point, np.ctypeslib.as_array(p1, (P, k)).copy(), np.ctypeslib.as_array(p2, (P, k)).copy(),
-                           np.ctypeslib.as_array(a, (P,)).copy())
-            np.ctypeslib.as_array(out, (P,))[:] = np.asarray(res, dtype=np.float64).reshape(P)
-            return 0
-        except Exception as exc:   # never let an exception cross the C boundary
-            err.append(exc)
-            return _abi.VB2_ERR_INVALID
-    fn = _abi.CONDITIONED_EVAL_FN(cb)
-    fixed = np.ascontiguousarray(np.asarray(pc1_fixed, dtype=np.float64).reshape(H, k))
-    m, keep = _model(known_af=known_af, **model_kw)
-    est = (_abi.Estimate * H)()
-    status = (C.c_int32 * H)()
-    rc = L.vb2_conditioned_lockstep(fn, None, H, k, C.byref(m), _p(fixed), est, status)
-    del keep
-    if err:
-        raise err[0]
-    _abi.check(rc, "vb2_conditioned_lockstep")
-    return [dict(_estimate_dict(est[h], k), status=int(status[h])) for h in range(H)]
+    return _rows_with_evaluator(_abi.CONDITIONED_EVAL_FN, "vb2_conditioned_lockstep", evaluate, num_hyp, num_pc, pc1_fixed,
+                                known_af, **model_kw)
 
 
-class Paired:
+class Paired(_RowSet):
     """vb2_paired: the likelihood of the ONE resident sample given genotype priors on BOTH components -- per hypothesis two
     float32 triples per panel marker, pi1 for the contaminant and pi2 for the intended sample; an all-zero triple falls back
     to that side's Hardy-Weinberg prior, a negative pi2[0] leaves the marker out.  prior: [H, M, 6] (pi1 | pi2); or
     source_set=, normals= (indices into a SourceSet on the context's device) and hom_min=: hypothesis h is the matched-normal
     rule on that sample's genotype posterior, built on the device."""
-    SLOTS = _abi.VB2_BATCH_SLOTS
+    _NAME, _ROWS = "paired", "num_hyp"
 
     def __init__(self, ctx: LikelihoodContext, prior=None, source_set=None, normals=None, hom_min=0.99):
         self._lib = _abi.lib()
@@ -796,19 +780,6 @@ class Paired:
             _abi.check(self._lib.vb2_paired_create(ctx._h, self.num_hyp, _p(pr), C.byref(h)), "vb2_paired_create")
         self._h = h
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.vb2_paired_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
     def info(self):
         i = _abi.PairedInfo()
         given = np.zeros(self.num_hyp, dtype=np.int64)
@@ -819,15 +790,7 @@ class Paired:
     def eval(self, num_point, pc1, pc2, alpha):
         """One step (vb2_paired_eval): num_point [H] ints 0..8; pc1 / pc2 [P, k] and alpha [P] with P = sum(num_point),
         the hypotheses' rows one after the other.  Returns llk [P]."""
-        k = self.num_pc
-        npt = np.ascontiguousarray(num_point, dtype=np.int32).reshape(self.num_hyp)
-        P = int(npt.sum())
-        pc1 = np.ascontiguousarray(np.asarray(pc1, dtype=np.float64).reshape(P, k))
-        pc2 = np.ascontiguousarray(np.asarray(pc2, dtype=np.float64).reshape(P, k))
-        alpha = np.ascontiguousarray(np.asarray(alpha, dtype=np.float64).reshape(P))
-        out = np.zeros(P)
-        _abi.check(self._lib.vb2_paired_eval(self._h, _p(npt), _p(pc1), _p(pc2), _p(alpha), _p(out)), "vb2_paired_eval")
-        return out
+        return self._eval(num_point, pc1, pc2, alpha)
 
     def optimize(self, pc2_fixed, **model_kw):
         """The refit of every hypothesis in lock-step (Paired.optimize_sets on this set alone)."""
@@ -839,22 +802,7 @@ class Paired:
         contaminant's PCs (alpha alone with fix_pc= or known allele frequencies), the intended sample's PCs held at
         pc2_fixed[s] ([num_set, k]).  Returns per set a list of dicts (alpha, pc -- the contaminant's --, llk1, llk0,
         "status")."""
-        L = _abi.lib()
-        k = sets[0].num_pc
-        S = len(sets)
-        fixed = np.ascontiguousarray(np.asarray(pc2_fixed, dtype=np.float64).reshape(S, k))
-        m, keep = _model(**model_kw)
-        H = sum(c.num_hyp for c in sets)
-        handles = (C.c_void_p * S)(*[c._h for c in sets])
-        est = (_abi.Estimate * H)()
-        status = (C.c_int32 * H)()
-        _abi.check(L.vb2_paired_optimize_llk(handles, S, C.byref(m), _p(fixed), est, status), "vb2_paired_optimize_llk")
-        del keep
-        out, at = [], 0
-        for c in sets:
-            out.append([dict(_estimate_dict(est[at + h], k), status=int(status[at + h])) for h in range(c.num_hyp)])
-            at += c.num_hyp
-        return out
+        return _optimize_sets("vb2_paired_optimize_llk", sets, pc2_fixed, **model_kw)
 
 
 def paired_with_evaluator(evaluate, num_hyp, num_pc, pc2_fixed, known_af=False, **model_kw):
@@ -862,32 +810,8 @@ def paired_with_evaluator(evaluate, num_hyp, num_pc, pc2_fixed, known_af=False, 
     evaluate(num_point [H] int32, pc1 [P, k], pc2 [P, k], alpha [P]) -> llk [P], P = sum(num_point), called once per step
     with the points of every hypothesis still searching; the pc2 rows are pc2_fixed [H, k] at every call.  Returns one dict
     per hypothesis (with "status")."""
-    L = _abi.lib()
-    k, H = int(num_pc), int(num_hyp)
-    err = []
-
-    def cb(_user, nh, npt, p1, p2, a, out):
-        try:
-            num_point = np.ctypeslib.as_array(npt, (nh,)).copy()
-            P = int(num_point.sum())
-            res = evaluate(num_point, np.ctypeslib.as_array(p1, (P, k)).copy(), np.ctypeslib.as_array(p2, (P, k)).copy(),
-                           np.ctypeslib.as_array(a, (P,)).copy())
-            np.ctypeslib.as_array(out, (P,))[:] = np.asarray(res, dtype=np.float64).reshape(P)
-            return 0
-        except Exception as exc:   # never let an exception cross the C boundary
-            err.append(exc)
-            return _abi.VB2_ERR_INVALID
-    fn = _abi.PAIRED_EVAL_FN(cb)
-    fixed = np.ascontiguousarray(np.asarray(pc2_fixed, dtype=np.float64).reshape(H, k))
-    m, keep = _model(known_af=known_af, **model_kw)
-    est = (_abi.Estimate * H)()
-    status = (C.c_int32 * H)()
-    rc = L.vb2_paired_lockstep(fn, None, H, k, C.byref(m), _p(fixed), est, status)
-    del keep
-    if err:
-        raise err[0]
-    _abi.check(rc, "vb2_paired_lockstep")
-    return [dict(_estimate_dict(est[h], k), status=int(status[h])) for h in range(H)]
+    return _rows_with_evaluator(_abi.PAIRED_EVAL_FN, "vb2_paired_lockstep", evaluate, num_hyp, num_pc, pc2_fixed, known_af,
+                                **model_kw)
 
 
 def chromosome_weights(bed_path, num_marker=None):

@@ -21,6 +21,7 @@
 #include "batch.h"
 #include "context.h"
 #include "estimator.h"
+#include "guard.h"
 #include "line_search.h"
 #include "lockstep.h"
 #include "hostio.h"
@@ -124,20 +125,14 @@ int vb2_ctx_create(const vb2_input* in, const vb2_options* opt, vb2_ctx** out)
         return VB2_ERR_INVALID;
     }
     *out = nullptr;
-    try {
+    return vb2::guarded([&]() -> int {
         vb2::Context* c = nullptr;
         const int rc = vb2::Context::create(in, opt, &c);
         if (rc) return rc;
         vb2_ctx* h = new vb2_ctx{c};
         *out = h;
         return VB2_OK;
-    } catch (const std::bad_alloc&) {
-        set_error("out of host memory");
-        return VB2_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return VB2_ERR_INVALID;
-    }
+    });
 }
 
 void vb2_ctx_destroy(vb2_ctx* ctx)
@@ -431,7 +426,7 @@ int vb2_ctx_optimize_llk_ex(vb2_ctx* ctx, const vb2_model* model, const vb2_sear
     }
     vb2::Context* c = ctx->impl;
     const int k = c->num_pc;
-    try {
+    return vb2::guarded([&]() -> int {
         if (S == 1) {
             // one run, Brent's single-point evaluations served by the resident kernel
             const bool resident = c->resident_begin();
@@ -481,13 +476,7 @@ int vb2_ctx_optimize_llk_ex(vb2_ctx* ctx, const vb2_model* model, const vb2_sear
         best->reserved = win;
         if (all) std::memcpy(all, ests.data(), sizeof(vb2_estimate) * S);
         return VB2_OK;
-    } catch (const std::bad_alloc&) {
-        set_error("out of host memory");
-        return VB2_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return VB2_ERR_INVALID;
-    }
+    });
 }
 
 int vb2_batch_create(vb2_ctx* const* ctxs, int32_t num_sample, vb2_batch** out)
@@ -564,15 +553,9 @@ int vb2_batch_derivs(vb2_batch* b, const int32_t* num_point, const double* pc1, 
         set_error("vb2_batch_derivs: invalid argument");
         return VB2_ERR_INVALID;
     }
-    try {
+    return vb2::guarded([&]() -> int {
         return b->impl->derivs(num_point, pc1, pc2, alpha, llk_out, grad_out, hess_out);
-    } catch (const std::bad_alloc&) {
-        set_error("out of host memory");
-        return VB2_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return VB2_ERR_INVALID;
-    }
+    });
 }
 
 int vb2_batch_interval(vb2_batch* b, const vb2_model* models, int32_t num_model, const vb2_estimate* est, vb2_interval* out,
@@ -583,15 +566,9 @@ int vb2_batch_interval(vb2_batch* b, const vb2_model* models, int32_t num_model,
         set_error("vb2_batch_interval: invalid argument");
         return VB2_ERR_INVALID;
     }
-    try {
+    return vb2::guarded([&]() -> int {
         return vb2::batch_interval(b->impl, models, num_model, est, out, status, num_step, nullptr);
-    } catch (const std::bad_alloc&) {
-        set_error("out of host memory");
-        return VB2_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return VB2_ERR_INVALID;
-    }
+    });
 }
 
 int vb2_intervals_lockstep(vb2_batch_derivs_fn fn, void* user, int32_t num_sample, int32_t num_pc, const int32_t* data_has_known_af,
@@ -603,7 +580,7 @@ int vb2_intervals_lockstep(vb2_batch_derivs_fn fn, void* user, int32_t num_sampl
         set_error("vb2_intervals_lockstep: invalid argument");
         return VB2_ERR_INVALID;
     }
-    try {
+    return vb2::guarded([&]() -> int {
         const vb2::BatchDerivsFn call = [fn, user](int32_t ns, const int32_t* np, const double* p1, const double* p2,
                                                    const double* a, double* llk, double* grad, double* hess) {
             const int rc = fn(user, ns, np, p1, p2, a, llk, grad, hess);
@@ -612,32 +589,20 @@ int vb2_intervals_lockstep(vb2_batch_derivs_fn fn, void* user, int32_t num_sampl
         };
         return vb2::intervals_lockstep(num_sample, num_pc, data_has_known_af, models, num_model, est, call, out, status, num_step,
                                        nullptr);
-    } catch (const std::bad_alloc&) {
-        set_error("out of host memory");
-        return VB2_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return VB2_ERR_INVALID;
-    }
+    });
 }
 
 int vb2_shard_group_create(const vb2_input* in, const int32_t* devices, int32_t num_device, vb2_shard_group** out)
 {
     if (!out) return VB2_ERR_INVALID;
     *out = nullptr;
-    try {
+    return vb2::guarded([&]() -> int {
         vb2::ShardGroup* g = nullptr;
         const int rc = vb2::ShardGroup::create(in, devices, num_device, &g);
         if (rc) return rc;
         *out = new vb2_shard_group{g};
         return VB2_OK;
-    } catch (const std::bad_alloc&) {
-        set_error("out of host memory");
-        return VB2_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return VB2_ERR_INVALID;
-    }
+    });
 }
 
 int vb2_rccl_unique_id(void* id128)
@@ -651,19 +616,13 @@ int vb2_shard_group_create_rank(const vb2_input* in, int32_t device, int32_t ran
 {
     if (!out) return VB2_ERR_INVALID;
     *out = nullptr;
-    try {
+    return vb2::guarded([&]() -> int {
         vb2::ShardGroup* g = nullptr;
         const int rc = vb2::ShardGroup::create_rank(in, device, rank, nranks, id128, &g);
         if (rc) return rc;
         *out = new vb2_shard_group{g};
         return VB2_OK;
-    } catch (const std::bad_alloc&) {
-        set_error("out of host memory");
-        return VB2_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return VB2_ERR_INVALID;
-    }
+    });
 }
 
 int vb2_shard_group_eval(vb2_shard_group* g, int32_t num_point, const double* pc1, const double* pc2,
@@ -738,7 +697,7 @@ int vb2_flat_load(const vb2_run_args* a, vb2_flat** out)
         return VB2_ERR_INVALID;
     }
     *out = nullptr;
-    try {
+    return vb2::guarded([&]() -> int {
         std::unique_ptr<vb2_flat> f(new vb2_flat());
         f->panel.numPC = a->num_pc;
         int rc;
@@ -800,13 +759,7 @@ int vb2_flat_load(const vb2_run_args* a, vb2_flat** out)
                          1e3 * (tl_join - tl_pile), 1e3 * (tl_san - tl_join), 1e3 * (now_s() - tl_san));
         *out = f.release();
         return VB2_OK;
-    } catch (const std::bad_alloc&) {
-        set_error("out of host memory");
-        return VB2_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return VB2_ERR_INVALID;
-    }
+    });
 }
 
 const vb2_input* vb2_flat_input(const vb2_flat* f) { return f ? &f->input : nullptr; }

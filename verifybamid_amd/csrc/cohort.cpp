@@ -33,6 +33,7 @@
 #include "conditioned.h"
 #include "context.h"
 #include "estimator.h"
+#include "guard.h"
 #include "hostio.h"
 #include "interval.h"
 #include "paired.h"
@@ -404,12 +405,38 @@ private:
             }
     }
 
+    // The tail both refits share: the one-row sets on the parked contexts, ALL in one lock-step call of `optimize` between
+    // the phase's notices.  fit[who[n]].status becomes set n's (the call's own failure is everybody's), a failure gives
+    // "NOTICE - <failed> <who[n] + first>" with the last error, and the sets go before their contexts do.  The estimates, by set.
+    template <class Set, class Optimize, class Fit>
+    std::vector<vb2_estimate> refit_sets(const char* phase, const char* failed, int first, Optimize optimize,
+                                         std::vector<std::unique_ptr<Set>>& sets, const std::vector<double>& fixed,
+                                         const std::vector<int>& who, std::vector<Fit>& fit)
+    {
+        std::vector<vb2_estimate> est(sets.size());
+        if (sets.empty()) return est;
+        std::vector<Set*> raw;
+        for (auto& p : sets) raw.push_back(p.get());
+        std::vector<int32_t> st(sets.size(), VB2_ERR_INVALID);
+        const double t0 = now_s();
+        if (model_.notices) std::fprintf(stderr, "NOTICE - Starting phase: %s (%d searches in lock-step)\n", phase, (int)sets.size());
+        const int rc = optimize(raw.data(), (int)raw.size(), model_, fixed.data(), est.data(), st.data());
+        if (model_.notices) std::fprintf(stderr, "NOTICE - Finished phase: %s  [%.3f seconds]\n", phase, now_s() - t0);
+        for (size_t n = 0; n < who.size(); ++n) {
+            Fit& f = fit[(size_t)who[n]];
+            f.status = rc ? rc : st[n];
+            if (f.status != VB2_OK)
+                std::fprintf(stderr, "NOTICE - %s %d failed: %s\n", failed, who[n] + first, vb2::g_last_error.c_str());
+        }
+        sets.clear();
+        return est;
+    }
+
     // --RefitSource, after the matrix: one refit per sample -- its best candidate, where that candidate's score is finite
     // and > 0 --, each a one-hypothesis set on the sample's parked context, ALL in one lock-step call; fit[] and
     // <Output>.SourceFit.  A refit that fails leaves its row NA, gives a NOTICE and does not fail the run.
     int refit_sources()
     {
-        const int k = a_->base.num_pc;
         const double nan = std::numeric_limits<double>::quiet_NaN();
         std::vector<vb2_source_fit> fit((size_t)S_);
         std::vector<std::unique_ptr<vb2::Conditioned>> sets;
@@ -441,17 +468,10 @@ private:
             f.llr = fit_score_[(size_t)i * S_ + best];
             f.markers = fit_shared_ ? fit_shared_[(size_t)i * S_ + best] : 0;
             if (!(std::isfinite(f.llr) && f.llr > 0) || (size_t)i >= parked_.size() || !parked_[(size_t)i]) continue;
-            // the target's search point, as the source set took it (SourceSet::put): the swap of indices 0 and 1 undone,
-            // mirrored when alpha >= 0.5; its pc1 is what the refit holds
+            // the target's search point, as the source set took it: its pc1 is what the refit holds
             vb2::Context* c = parked_[(size_t)i]->impl;
-            const bool kaf = model_.is_af_known != 0 || c->L.known_af != nullptr;
-            const bool heter = model_.is_heter && !kaf;
-            std::vector<double> p1(e.pc, e.pc + k), p2(e.pc2, e.pc2 + k);
-            if (heter && e.alpha >= 0.5 && k >= 1) {
-                std::swap(p1[0], p2[0]);
-                if (k >= 2) std::swap(p1[1], p2[1]);
-            }
-            if (e.alpha >= 0.5) p1.swap(p2);
+            std::vector<double> p1, p2;
+            vb2::search_point(*c, model_, e, &p1, &p2, nullptr);
             vb2::Conditioned* set = nullptr;
             const int32_t cand = best;
             if (const int rc = vb2::Conditioned::create_from_set(c, sources_.get(), 1, &cand, &set)) {
@@ -463,30 +483,15 @@ private:
             who.push_back(i);
             fixed.insert(fixed.end(), p1.begin(), p1.end());
         }
-        if (!sets.empty()) {
-            std::vector<vb2::Conditioned*> raw;
-            for (auto& p : sets) raw.push_back(p.get());
-            std::vector<vb2_estimate> est(sets.size());
-            std::vector<int32_t> st(sets.size(), VB2_ERR_INVALID);
-            const double t0 = now_s();
-            if (model_.notices)
-                std::fprintf(stderr, "NOTICE - Starting phase: Refit given the source (%d searches in lock-step)\n", (int)sets.size());
-            const int rc = vb2::conditioned_optimize(raw.data(), (int)raw.size(), model_, fixed.data(), est.data(), st.data());
-            if (model_.notices)
-                std::fprintf(stderr, "NOTICE - Finished phase: Refit given the source  [%.3f seconds]\n", now_s() - t0);
-            for (size_t n = 0; n < who.size(); ++n) {
-                vb2_source_fit& f = fit[(size_t)who[n]];
-                f.status = rc ? rc : st[n];
-                if (f.status != VB2_OK) {
-                    std::fprintf(stderr, "NOTICE - --RefitSource: the refit of sample %d failed: %s\n", who[n], vb2::g_last_error.c_str());
-                    continue;
-                }
-                f.alpha_given = est[n].alpha;
-                f.lk1_given = est[n].llk1;
-                f.lk0_given = est[n].llk0;
-                f.delta_lk = (-f.lk1_given) - (-f.freelk1);
-            }
-            sets.clear();                               // before their contexts go
+        const std::vector<vb2_estimate> est =
+            refit_sets("Refit given the source", "--RefitSource: the refit of sample", 0, vb2::conditioned_optimize, sets, fixed, who, fit);
+        for (size_t n = 0; n < who.size(); ++n) {
+            vb2_source_fit& f = fit[(size_t)who[n]];
+            if (f.status != VB2_OK) continue;
+            f.alpha_given = est[n].alpha;
+            f.lk1_given = est[n].llk1;
+            f.lk0_given = est[n].llk0;
+            f.delta_lk = (-f.lk1_given) - (-f.freelk1);
         }
         if (fit_) std::memcpy(fit_, fit.data(), sizeof(vb2_source_fit) * (size_t)S_);
         if (a_->output_prefixes && a_->base.output_prefix) {
@@ -511,7 +516,7 @@ private:
     // call; fits[] and <Output>.PairFit.  A refit that fails leaves NA, gives a NOTICE and does not fail the run.
     int refit_pairs()
     {
-        const int k = a_->base.num_pc, P = (int)pair_t_.size();
+        const int P = (int)pair_t_.size();
         const double nan = std::numeric_limits<double>::quiet_NaN();
         std::vector<vb2_pair_fit> fit((size_t)P);
         std::vector<std::unique_ptr<vb2::Paired>> sets;
@@ -544,17 +549,10 @@ private:
                 std::fprintf(stderr, "NOTICE - --MatchedNormal: pair %d is not refitted: the tumour's context is gone\n", p + 1);
                 continue;
             }
-            // the normal's search point, as the source set took it (SourceSet::put): the swap of indices 0 and 1 undone,
-            // mirrored when alpha >= 0.5; its pc2 -- the intended sample's -- is what the refit holds
+            // the normal's search point, as the source set took it: its pc2 -- the intended sample's -- is what the refit holds
             vb2::Context* c = parked_[(size_t)t]->impl;
-            const bool kaf = model_.is_af_known != 0 || c->L.known_af != nullptr;
-            const bool heter = model_.is_heter && !kaf;
-            std::vector<double> p1(e.pc, e.pc + k), p2(e.pc2, e.pc2 + k);
-            if (heter && e.alpha >= 0.5 && k >= 1) {
-                std::swap(p1[0], p2[0]);
-                if (k >= 2) std::swap(p1[1], p2[1]);
-            }
-            if (e.alpha >= 0.5) p1.swap(p2);
+            std::vector<double> p1, p2;
+            vb2::search_point(*c, model_, e, &p1, &p2, nullptr);
             vb2::Paired* set = nullptr;
             const int32_t nrm = n;
             if (const int rc = vb2::Paired::create_from_set(c, sources_.get(), 1, &nrm, hom_min_, &set)) {
@@ -567,29 +565,14 @@ private:
             who.push_back(p);
             fixed.insert(fixed.end(), p2.begin(), p2.end());
         }
-        if (!sets.empty()) {
-            std::vector<vb2::Paired*> raw;
-            for (auto& q : sets) raw.push_back(q.get());
-            std::vector<vb2_estimate> est(sets.size());
-            std::vector<int32_t> st(sets.size(), VB2_ERR_INVALID);
-            const double t0 = now_s();
-            if (model_.notices)
-                std::fprintf(stderr, "NOTICE - Starting phase: Refit given the matched normal (%d searches in lock-step)\n", (int)sets.size());
-            const int rc = vb2::paired_optimize(raw.data(), (int)raw.size(), model_, fixed.data(), est.data(), st.data());
-            if (model_.notices)
-                std::fprintf(stderr, "NOTICE - Finished phase: Refit given the matched normal  [%.3f seconds]\n", now_s() - t0);
-            for (size_t i = 0; i < who.size(); ++i) {
-                vb2_pair_fit& f = fit[(size_t)who[i]];
-                f.status = rc ? rc : st[i];
-                if (f.status != VB2_OK) {
-                    std::fprintf(stderr, "NOTICE - --MatchedNormal: the refit of pair %d failed: %s\n", who[i] + 1, vb2::g_last_error.c_str());
-                    continue;
-                }
-                f.alpha_paired = est[i].alpha;
-                f.lk1_paired = est[i].llk1;
-                f.lk0_paired = est[i].llk0;
-            }
-            sets.clear();                               // before their contexts go
+        const std::vector<vb2_estimate> est = refit_sets("Refit given the matched normal", "--MatchedNormal: the refit of pair", 1,
+                                                         vb2::paired_optimize, sets, fixed, who, fit);
+        for (size_t i = 0; i < who.size(); ++i) {
+            vb2_pair_fit& f = fit[(size_t)who[i]];
+            if (f.status != VB2_OK) continue;
+            f.alpha_paired = est[i].alpha;
+            f.lk1_paired = est[i].llk1;
+            f.lk0_paired = est[i].llk0;
         }
         if (pair_fit_) std::memcpy(pair_fit_, fit.data(), sizeof(vb2_pair_fit) * (size_t)P);
         if (a_->output_prefixes && a_->base.output_prefix) {
@@ -1124,18 +1107,12 @@ extern "C" int vb2_cohort_run(const vb2_cohort_args* a, vb2_run_result* out, int
                 set_error("vb2_cohort_run: a device is listed twice");
                 return VB2_ERR_INVALID;
             }
-    try {
+    return vb2::guarded([&] {
         CohortRunner runner(a, out, status);
         const int rc = runner.run();
         if (rc && !runner.error().empty()) set_error(runner.error());
         return rc;
-    } catch (const std::bad_alloc&) {
-        set_error("out of host memory");
-        return VB2_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return VB2_ERR_INVALID;
-    }
+    });
 }
 
 extern "C" int vb2_cohort_run_sources(const vb2_cohort_args* a, int32_t top, vb2_run_result* out, int32_t* status, double* score,
@@ -1150,18 +1127,12 @@ extern "C" int vb2_cohort_run_sources(const vb2_cohort_args* a, int32_t top, vb2
         set_error("--FindSource takes one device: a source set is not spread over several --Devices");
         return VB2_ERR_INVALID;
     }
-    try {
+    return vb2::guarded([&] {
         CohortRunner runner(a, out, status, true, top, score, shared);
         const int rc = runner.run();
         if (rc && !runner.error().empty()) set_error(runner.error());
         return rc;
-    } catch (const std::bad_alloc&) {
-        set_error("out of host memory");
-        return VB2_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return VB2_ERR_INVALID;
-    }
+    });
 }
 
 extern "C" int vb2_cohort_run_related(const vb2_cohort_args* a, int32_t related_top, int32_t source_top, vb2_run_result* out,
@@ -1176,19 +1147,13 @@ extern "C" int vb2_cohort_run_related(const vb2_cohort_args* a, int32_t related_
         set_error("--FindRelated takes one device: a set of samples is not spread over several --Devices");
         return VB2_ERR_INVALID;
     }
-    try {
+    return vb2::guarded([&] {
         CohortRunner runner(a, out, status, source_top > 0, source_top);
         runner.enable_related(related_top, llr, shared);
         const int rc = runner.run();
         if (rc && !runner.error().empty()) set_error(runner.error());
         return rc;
-    } catch (const std::bad_alloc&) {
-        set_error("out of host memory");
-        return VB2_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return VB2_ERR_INVALID;
-    }
+    });
 }
 
 extern "C" int vb2_cohort_run_source_fits(const vb2_cohort_args* a, int32_t top, vb2_run_result* out, int32_t* status, double* score,
@@ -1207,18 +1172,12 @@ extern "C" int vb2_cohort_run_source_fits(const vb2_cohort_args* a, int32_t top,
         set_error("--RefitSource cannot be combined with --FixAlpha: a fixed alpha leaves the refit nothing to estimate");
         return VB2_ERR_INVALID;
     }
-    try {
+    return vb2::guarded([&] {
         CohortRunner runner(a, out, status, true, top, score, shared, false, nullptr, true, fit);
         const int rc = runner.run();
         if (rc && !runner.error().empty()) set_error(runner.error());
         return rc;
-    } catch (const std::bad_alloc&) {
-        set_error("out of host memory");
-        return VB2_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return VB2_ERR_INVALID;
-    }
+    });
 }
 
 extern "C" int vb2_cohort_run_intervals(const vb2_cohort_args* a, int32_t source_top, vb2_run_result* out, int32_t* status,
@@ -1233,18 +1192,12 @@ extern "C" int vb2_cohort_run_intervals(const vb2_cohort_args* a, int32_t source
         set_error("--CohortInterval takes one device: the intervals of a cohort are not spread over several --Devices");
         return VB2_ERR_INVALID;
     }
-    try {
+    return vb2::guarded([&] {
         CohortRunner runner(a, out, status, source_top > 0, source_top, nullptr, nullptr, true, ci);
         const int rc = runner.run();
         if (rc && !runner.error().empty()) set_error(runner.error());
         return rc;
-    } catch (const std::bad_alloc&) {
-        set_error("out of host memory");
-        return VB2_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return VB2_ERR_INVALID;
-    }
+    });
 }
 
 extern "C" int vb2_cohort_run_paired(const vb2_cohort_args* a, int32_t num_pair, const int32_t* tumour, const int32_t* normal,
@@ -1268,17 +1221,11 @@ extern "C" int vb2_cohort_run_paired(const vb2_cohort_args* a, int32_t num_pair,
         return VB2_ERR_INVALID;
     }
     if (const int rc = vb2::check_pairs("vb2_cohort_run_paired", a->num_sample, num_pair, tumour, normal)) return rc;
-    try {
+    return vb2::guarded([&] {
         CohortRunner runner(a, out, status);
         runner.enable_paired(num_pair, tumour, normal, hom_min, fits);
         const int rc = runner.run();
         if (rc && !runner.error().empty()) set_error(runner.error());
         return rc;
-    } catch (const std::bad_alloc&) {
-        set_error("out of host memory");
-        return VB2_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return VB2_ERR_INVALID;
-    }
+    });
 }

@@ -195,19 +195,23 @@ int FiberGang::search(int i, const Search& cfg, const char* caller, vb2_estimate
     }
 }
 
-FiberGang::StepFn FiberGang::concat_step(int num_pc, vb2_eval_fn eval, void* user)
+FiberGang::StepFn FiberGang::concat_step(int num_pc, ConcatEval eval)
 {
+    std::vector<int32_t> npt;
     std::vector<double> p1, p2, al, vals;
     return [=](std::vector<Request>& req) mutable {
         p1.clear(); p2.clear(); al.clear();
-        for (const Request& r : req) {
+        npt.assign(req.size(), 0);
+        for (size_t i = 0; i < req.size(); ++i) {
+            const Request& r = req[i];
             if (r.n <= 0) continue;
+            npt[i] = r.n;
             p1.insert(p1.end(), r.p1, r.p1 + (size_t)r.n * num_pc);
             p2.insert(p2.end(), r.p2, r.p2 + (size_t)r.n * num_pc);
             al.insert(al.end(), r.a, r.a + r.n);
         }
-        vals.resize(al.size());
-        if (const int rc = eval(user, (int32_t)al.size(), p1.data(), p2.data(), al.data(), vals.data())) return rc;
+        vals.assign(al.size(), 0.0);
+        if (const int rc = eval(npt.data(), al.size(), p1.data(), p2.data(), al.data(), vals.data())) return rc;
         size_t o = 0;
         for (Request& r : req) {
             if (r.n <= 0) continue;
@@ -216,6 +220,12 @@ FiberGang::StepFn FiberGang::concat_step(int num_pc, vb2_eval_fn eval, void* use
         }
         return 0;
     };
+}
+
+FiberGang::StepFn FiberGang::concat_step(int num_pc, vb2_eval_fn eval, void* user)
+{
+    return concat_step(num_pc, [eval, user](const int32_t*, size_t total, const double* p1, const double* p2, const double* a,
+                                            double* out) { return eval(user, (int32_t)total, p1, p2, a, out); });
 }
 
 }  // namespace vb2

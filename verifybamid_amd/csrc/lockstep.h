@@ -77,14 +77,20 @@ public:
         uint32_t start_seed = 0;
         double start_sd = 0;                // <= 0: the Estimator's own
         // what the Estimator calls for its values instead of eval_cb on user(i) (null: that); it must end up in eval_cb on
-        // user(i) itself -- a wrapper that looks at the values on their way (replicates.cpp)
+        // user(i) itself -- a wrapper that holds one side of the points or looks at the values on their way (refit.cpp)
         vb2_eval_fn eval = nullptr;
         void* eval_user = nullptr;
     };
     // For body(i): that search on fiber i's evaluator.  Fills *out when the optimiser returned and gives its code, or
     // VB2_ERR_NOMEM / VB2_ERR_INVALID with the last error set (`caller` goes into the message for an unknown exception).
     int search(int i, const Search& cfg, const char* caller, vb2_estimate* out) noexcept;
-    // a StepFn that evaluates the points of all requests with one call of eval(user, ...) and hands the values back
+    // A StepFn that evaluates the points of all requests with ONE call and hands the values back: the requests' rows one
+    // after the other, `total` points, num_point[i] of them fiber i's (0: it asked for none); out[] starts as zeros.
+    typedef std::function<int(const int32_t* num_point, size_t total, const double* p1, const double* p2, const double* a,
+                              double* out)>
+        ConcatEval;
+    static StepFn concat_step(int num_pc, ConcatEval eval);
+    // the same for an evaluator that does not ask whose the points are: eval(user, total, ...)
     static StepFn concat_step(int num_pc, vb2_eval_fn eval, void* user);
 
 private:

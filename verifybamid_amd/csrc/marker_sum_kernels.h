@@ -1,5 +1,6 @@
-// marker_sum_kernels.h -- launchers of the two per-marker sums over one resident sample (marker_sum_kernels.hip): the
-// weighted-marker evaluation and the likelihood conditioned on a hypothesised contaminant (section 13).
+// marker_sum_kernels.h -- launchers of the three per-marker sums over one resident sample (marker_sum_kernels.hip): the
+// weighted-marker evaluation, the likelihood conditioned on a hypothesised contaminant (section 13)
+// and the likelihood given priors on both components (section 16).
 #ifndef VB2_MARKER_SUM_KERNELS_H_
 #define VB2_MARKER_SUM_KERNELS_H_
 

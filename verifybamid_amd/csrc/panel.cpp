@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "context.h"
+#include "guard.h"
 #include "panel.h"
 
 struct vb2_vcf {
@@ -461,20 +462,17 @@ int64_t chunk_width(const vb2_panel_args* a)
     return round_up(c, kGramKStep);
 }
 
+// guard.h's clauses around a body that may also throw HipFail (its code; the message is set where it is thrown)
 template <class F>
-int guarded(F&& f)
+int entry(F&& f)
 {
-    try {
-        return f();
-    } catch (const HipFail& e) {
-        return e.code;
-    } catch (const std::bad_alloc&) {
-        set_error("out of host memory");
-        return VB2_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return VB2_ERR_INVALID;
-    }
+    return guarded([&]() -> int {
+        try {
+            return f();
+        } catch (const HipFail& e) {
+            return e.code;
+        }
+    });
 }
 
 }  // namespace
@@ -492,7 +490,7 @@ int vb2_vcf_read(const vb2_panel_args* a, vb2_vcf** out)
         return VB2_ERR_INVALID;
     }
     *out = nullptr;
-    return vb2::guarded([&] {
+    return vb2::entry([&] {
         std::unique_ptr<vb2_vcf> v(new vb2_vcf);
         const auto inc = vb2::parse_include_chr(a->include_chr);
         const int rc = vb2::read_vcf(a->vcf_path, inc, a->num_thread, a->notices != 0, &v->mk, nullptr,
@@ -538,7 +536,7 @@ int vb2_panel_build(const vb2_panel_args* a, vb2_panel** out)
     }
     *out = nullptr;
     const auto t0 = vb2::Clock::now();
-    return vb2::guarded([&] {
+    return vb2::entry([&] {
         std::unique_ptr<vb2_panel> p(new vb2_panel);
         p->has_markers = true;
         const bool notices = a->notices != 0;
@@ -601,7 +599,7 @@ int vb2_panel_build_genotypes(const vb2_panel_args* a, const int8_t* geno, int64
     }
     *out = nullptr;
     const auto t0 = vb2::Clock::now();
-    return vb2::guarded([&] {
+    return vb2::entry([&] {
         std::unique_ptr<vb2_panel> p(new vb2_panel);
         for (int64_t i = 0; i < M * (int64_t)N; ++i)
             if (geno[i] < -1 || geno[i] > 2) {
@@ -655,7 +653,7 @@ int vb2_panel_write(vb2_panel* p, const char* prefix)
         set_error("vb2_panel_write: a panel built from a genotype matrix has no marker names (.bed/.mu need them)");
         return VB2_ERR_INVALID;
     }
-    return vb2::guarded([&] {
+    return vb2::entry([&] {
         const auto t0 = vb2::Clock::now();
         const std::string pre(prefix);
         const int64_t M = p->M;

@@ -1,7 +1,8 @@
 // point_stage.h -- the stage of a set that evaluates points of several rows (weight rows, hypotheses) over one context
 // in launches of at most kMaxPointsPerLaunch points: one pinned slab and one device slab laid out
 //     rows [cap][2k+1] | row indices [cap] | results [cap]        (on the device also: a launch's partial sums)
-// with the fill, the upload, the chunked launches, the download and the event-timed loop.  Replicates and Conditioned.
+// with the fill, the upload, the chunked launches, the download and the event-timed loop.  The stage of every RowSet
+// (row_set.h): Replicates, Conditioned and Paired.
 #ifndef VB2_POINT_STAGE_H_
 #define VB2_POINT_STAGE_H_
 

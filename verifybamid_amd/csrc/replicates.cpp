@@ -1,6 +1,7 @@
-// replicates.cpp -- host side of the weighted-marker replicates (marker_sum_kernels.hip): the replicate
-// set on a context, its lock-step searches, the host-only helpers (chromosome and bootstrap weights, the delete-m_j
-// jackknife) and the file flow behind --PerChromosome / --Bootstrap.
+// replicates.cpp -- host side of the weighted-marker replicates (marker_sum_kernels.hip): what fills
+// the weight rows of a replicate set (the rest of the set: row_set.cpp), the options of its lock-step searches (refit.h), the
+// host-only helpers (chromosome and bootstrap weights, the delete-m_j jackknife) and the file flow behind --PerChromosome /
+// --Bootstrap.
 #include "replicates.h"
 
 #include <hip/hip_runtime_api.h>
@@ -12,34 +13,38 @@
 #include <cstring>
 #include <fstream>
 #include <memory>
-#include <new>
 #include <string>
 #include <vector>
 
 #include "context.h"
-#include "device_util.h"
+#include "guard.h"
 #include "hostio.h"
-#include "lockstep.h"
 #include "marker_sum_kernels.h"
 
 namespace vb2 {
 
+namespace {
+const RowSet::Kind kKind = {
+    "vb2_replicates_eval", "a replicate's", "replicates", nullptr, true,
+    [](const DeviceLayout& L) { return (size_t)L.m_pad; },
+    [](const DeviceLayout& L, int num_point, const double* d_rows, const int32_t* d_row_of, const void* d_weights, double* d_partial,
+       double* d_out, hipStream_t s) {
+        return launch_llk_weighted(L, num_point, d_rows, d_row_of, static_cast<const uint8_t*>(d_weights), d_partial, d_out, s);
+    }};
+}  // namespace
+
+Replicates::Replicates() : RowSet(kKind) {}
+
 int Replicates::create(Context* ctx, int num_rep, const uint8_t* weight, Replicates** out)
 {
     *out = nullptr;
-    if (!ctx || num_rep < 1 || num_rep > 65535 || !weight) {
+    if (!weight) {
         set_error("vb2_replicates_create: invalid argument (1..65535 replicates)");
         return VB2_ERR_INVALID;
     }
-    if (ctx->resident_active) {
-        set_error("vb2_replicates_create: not inside vb2_ctx_search_begin / vb2_ctx_search_end");
-        return VB2_ERR_INVALID;
-    }
     std::unique_ptr<Replicates> r(new Replicates());
-    r->ctx = ctx;
-    r->num_rep = num_rep;
-    const DeviceLayout& L = ctx->L;
-    const size_t M = (size_t)ctx->num_marker, mp = (size_t)L.m_pad, na = (size_t)L.num_active;
+    if (const int rc = r->init(ctx, num_rep, "vb2_replicates_create")) return rc;
+    const size_t M = (size_t)ctx->num_marker, na = (size_t)ctx->L.num_active;
     // counted markers per replicate, on the host: the sorted positions' panel rows are h_active[h_perm[position]]
     r->counted.assign(num_rep, 0);
     if (na > 0 && ctx->h_perm.size() < na) {
@@ -53,152 +58,25 @@ int Replicates::create(Context* ctx, int num_rep, const uint8_t* weight, Replica
         if (i >= M) continue;
         for (int q = 0; q < num_rep; ++q) r->counted[q] += weight[(size_t)q * M + i] != 0;
     }
-    VB2_HIP(hipSetDevice(ctx->device));
-    if (const int rc = ctx->ensure_pidx()) return rc;
-    if (const int rc = take_device(std::max<size_t>(mp * (size_t)num_rep, 256), ctx->device, reinterpret_cast<void**>(&r->d_weights_),
-                                   &r->d_weights_bytes_))
+    if (const int rc = r->upload(weight, M * (size_t)num_rep, "vb2_replicates_create: weight upload failed: ", [&](const void* d_panel) {
+            return launch_weights_permute(ctx->L, ctx->num_marker, num_rep, static_cast<const uint8_t*>(d_panel), ctx->d_pidx,
+                                          static_cast<uint8_t*>(r->d_payload_), ctx->stream);
+        }))
         return rc;
-    if (const int rc = r->stage_.create(ctx, (size_t)num_rep * VB2_BATCH_SLOTS,
-                                        (size_t)kMaxPointsPerLaunch * (size_t)std::max(1, marker_sum_tile_groups(L)), nullptr))
-        return rc;
-    r->device_bytes = (int64_t)(r->d_weights_bytes_ + r->stage_.device_bytes());
-    // the panel-order rows go up once, into a slab that goes back to the cache when the permutation is done
-    void* d_panel = nullptr;
-    size_t d_panel_bytes = 0;
-    if (const int rc = take_device(std::max<size_t>(M * (size_t)num_rep, 256), ctx->device, &d_panel, &d_panel_bytes)) return rc;
-    hipError_t e = hipMemcpyAsync(d_panel, weight, M * (size_t)num_rep, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess)
-        e = launch_weights_permute(L, ctx->num_marker, num_rep, static_cast<const uint8_t*>(d_panel), ctx->d_pidx, r->d_weights_,
-                                   ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    give_device(d_panel, d_panel_bytes, ctx->device);
-    if (e != hipSuccess) {
-        set_error(std::string("vb2_replicates_create: weight upload failed: ") + hipGetErrorString(e));
-        return VB2_ERR_HIP;
-    }
     *out = r.release();
     return VB2_OK;
 }
 
-Replicates::~Replicates()
-{
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    give_device(d_weights_, d_weights_bytes_, ctx->device);
-}
-
-PointStage::Launch Replicates::launcher() const
-{
-    return [this](int c, const double* d_rows, const int32_t* d_row_of, double* d_partial, double* d_out, hipStream_t s) {
-        return launch_llk_weighted(ctx->L, c, d_rows, d_row_of, d_weights_, d_partial, d_out, s);
-    };
-}
-
-int Replicates::eval(const int32_t* num_point, const double* pc1, const double* pc2, const double* alpha, double* llk)
-{
-    if (!num_point) {
-        set_error("vb2_replicates_eval: invalid argument");
-        return VB2_ERR_INVALID;
-    }
-    size_t total = 0;
-    if (!PointStage::count(num_rep, num_point, &total)) {
-        set_error("vb2_replicates_eval: a replicate's point count outside 0..VB2_BATCH_SLOTS");
-        return VB2_ERR_INVALID;
-    }
-    if (total == 0) return VB2_OK;
-    if (!pc1 || !pc2 || !alpha || !llk) {
-        set_error("vb2_replicates_eval: invalid argument");
-        return VB2_ERR_INVALID;
-    }
-    if (ctx->resident_active) {
-        set_error("vb2_replicates_eval: not inside vb2_ctx_search_begin / vb2_ctx_search_end");
-        return VB2_ERR_INVALID;
-    }
-    if (const int rc = stage_.begin(num_rep, num_point, total, pc1, pc2, alpha, launcher())) {
-        (void)stage_.end(nullptr);         // whatever reached the stream has left the stages when this returns
-        return rc;
-    }
-    return stage_.end(llk);
-}
-
-int Replicates::time_launch(int num_point, int warmup, int reps, double* ms)
-{
-    return stage_.time_launch(num_point, num_rep, warmup, reps, ms, launcher());
-}
-
-namespace {
-// what a replicate's Estimator calls: the gang's evaluator, and a look at the first values it returns
-struct Probe {
-    void* gang_user = nullptr;
-    bool first = true, empty = false;
-};
-int probe_eval(void* user, int32_t n, const double* p1, const double* p2, const double* a, double* o)
-{
-    Probe* pr = static_cast<Probe*>(user);
-    if (const int rc = FiberGang::eval_cb(pr->gang_user, n, p1, p2, a, o)) return rc;
-    if (pr->first) {
-        pr->first = false;
-        bool all_zero = n > 0;
-        for (int i = 0; i < n; ++i) all_zero = all_zero && o[i] == 0.0;
-        if (all_zero) {
-            pr->empty = true;
-            return VB2_ERR_INVALID;
-        }
-    }
-    return 0;
-}
-}  // namespace
-
 int replicates_lockstep(vb2_replicates_eval_fn fn, void* user, int num_rep, int num_pc, bool data_has_known_af,
                         const vb2_model& model, vb2_estimate* est, int32_t* status, int64_t* num_step)
 {
-    const int R = num_rep, k = num_pc;
-    FiberGang gang(R, VB2_BATCH_SLOTS);
-    std::vector<Probe> probes(R);
-    vb2_model quiet = model;                   // (the reference's phase lines belong to the run's own search)
-    quiet.notices = 0;
-    quiet.verbose = 0;
-    auto body = [&](int i) {
-        probes[i].gang_user = gang.user(i);
-        FiberGang::Search cfg;
-        cfg.model = &quiet;
-        cfg.data_has_known_af = data_has_known_af;
-        cfg.eval = probe_eval;
-        cfg.eval_user = &probes[i];
-        std::memset(&est[i], 0, sizeof(est[i]));
-        status[i] = gang.search(i, cfg, "vb2_replicates_optimize_llk", &est[i]);
-    };
-    std::vector<int32_t> npt(R);
-    std::vector<double> p1, p2, al, vals;
-    auto step = [&](std::vector<FiberGang::Request>& req) {
-        p1.clear(); p2.clear(); al.clear();
-        for (int r = 0; r < R; ++r) {
-            const FiberGang::Request& q = req[r];
-            npt[r] = q.n > 0 ? q.n : 0;
-            if (q.n <= 0) continue;
-            p1.insert(p1.end(), q.p1, q.p1 + (size_t)q.n * k);
-            p2.insert(p2.end(), q.p2, q.p2 + (size_t)q.n * k);
-            al.insert(al.end(), q.a, q.a + q.n);
-        }
-        vals.assign(al.size(), 0.0);
-        if (const int rc = fn(user, R, npt.data(), p1.data(), p2.data(), al.data(), vals.data())) return rc;
-        size_t o = 0;
-        for (int r = 0; r < R; ++r) {
-            if (req[r].n <= 0) continue;
-            std::memcpy(req[r].out, &vals[o], sizeof(double) * req[r].n);
-            o += (size_t)req[r].n;
-        }
-        return 0;
-    };
-    const int rc = gang.run(k, body, step);
-    if (num_step) *num_step = gang.steps;
-    if (rc) return rc;
-    for (int r = 0; r < R; ++r)
-        if (probes[r].empty) {
-            status[r] = VB2_ERR_INVALID;
-            set_error("vb2_replicates_optimize_llk: a replicate's weights select no counted marker");
-        }
-    return VB2_OK;
+    const std::vector<uint8_t> known_af((size_t)std::max(num_rep, 0), data_has_known_af ? 1 : 0);
+    Refit o;                                   // the model's own search from the reference start: no side is held
+    o.who = "vb2_replicates_optimize_llk";
+    o.empty_message = "vb2_replicates_optimize_llk: a replicate's weights select no counted marker";
+    o.known_af = known_af.data();
+    o.num_step = num_step;
+    return refit_lockstep(o, fn, user, num_rep, num_pc, model, est, status);
 }
 
 namespace {
@@ -219,7 +97,7 @@ int Replicates::optimize(const vb2_model& model, vb2_estimate* est, int32_t* sta
         set_error("vb2_replicates_optimize_llk: not inside vb2_ctx_search_begin / vb2_ctx_search_end");
         return VB2_ERR_INVALID;
     }
-    return replicates_lockstep(replicates_eval_cb, this, num_rep, ctx->num_pc, ctx->L.known_af != nullptr, model, est, status,
+    return replicates_lockstep(replicates_eval_cb, this, num_row, ctx->num_pc, ctx->L.known_af != nullptr, model, est, status,
                                nullptr);
 }
 
@@ -270,6 +148,7 @@ double freemix_of(const vb2_estimate& e) { return e.alpha < 0.5 ? e.alpha : 1 - 
 
 }  // namespace vb2
 
+using vb2::guarded;
 using vb2::set_error;
 
 extern "C" {
@@ -285,18 +164,12 @@ int vb2_replicates_create(vb2_ctx* ctx, int32_t num_rep, const uint8_t* weight, 
         set_error("null vb2_ctx");
         return VB2_ERR_INVALID;
     }
-    try {
+    return guarded([&]() -> int {
         vb2::Replicates* r = nullptr;
         if (const int rc = vb2::Replicates::create(ctx->impl, num_rep, weight, &r)) return rc;
         *out = new vb2_replicates{r};
         return VB2_OK;
-    } catch (const std::bad_alloc&) {
-        set_error("out of host memory");
-        return VB2_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return VB2_ERR_INVALID;
-    }
+    });
 }
 
 void vb2_replicates_destroy(vb2_replicates* rep)
@@ -322,15 +195,7 @@ int vb2_replicates_optimize_llk(vb2_replicates* rep, const vb2_model* model, vb2
         set_error("vb2_replicates_optimize_llk: invalid argument");
         return VB2_ERR_INVALID;
     }
-    try {
-        return rep->impl->optimize(*model, est_out, status);
-    } catch (const std::bad_alloc&) {
-        set_error("out of host memory");
-        return VB2_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return VB2_ERR_INVALID;
-    }
+    return guarded([&] { return rep->impl->optimize(*model, est_out, status); });
 }
 
 int vb2_debug_replicates_time(vb2_replicates* rep, int32_t num_point, int32_t warmup, int32_t reps, double* ms)
@@ -343,12 +208,12 @@ int vb2_replicates_info_get(const vb2_replicates* rep, vb2_replicates_info* info
 {
     if (!rep || !rep->impl || !info) return VB2_ERR_INVALID;
     const vb2::Replicates& r = *rep->impl;
-    info->num_rep = r.num_rep;
+    info->num_rep = r.num_row;
     info->num_marker = r.ctx->num_marker;
     info->device_bytes = r.device_bytes;
     info->num_step = r.num_step();
     info->num_launch = r.num_launch();
-    if (counted) std::memcpy(counted, r.counted.data(), sizeof(int64_t) * (size_t)r.num_rep);
+    if (counted) std::memcpy(counted, r.counted.data(), sizeof(int64_t) * (size_t)r.num_row);
     return VB2_OK;
 }
 
@@ -359,15 +224,7 @@ int vb2_replicates_lockstep(vb2_replicates_eval_fn fn, void* user, int32_t num_r
         set_error("vb2_replicates_lockstep: invalid argument");
         return VB2_ERR_INVALID;
     }
-    try {
-        return vb2::replicates_lockstep(fn, user, num_rep, num_pc, false, *model, est_out, status, nullptr);
-    } catch (const std::bad_alloc&) {
-        set_error("out of host memory");
-        return VB2_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return VB2_ERR_INVALID;
-    }
+    return guarded([&] { return vb2::replicates_lockstep(fn, user, num_rep, num_pc, false, *model, est_out, status, nullptr); });
 }
 
 int vb2_chromosome_weights(const char* bed_path, int32_t num_marker, int32_t max_block, int32_t* num_block, int32_t* block_of,
@@ -377,7 +234,7 @@ int vb2_chromosome_weights(const char* bed_path, int32_t num_marker, int32_t max
         set_error("vb2_chromosome_weights: invalid argument");
         return VB2_ERR_INVALID;
     }
-    try {
+    return guarded([&]() -> int {
         vb2::Panel panel;
         if (const int rc = vb2::read_bed(bed_path, &panel)) return rc;
         vb2::Blocks b;
@@ -408,13 +265,7 @@ int vb2_chromosome_weights(const char* bed_path, int32_t num_marker, int32_t max
             }
         }
         return VB2_OK;
-    } catch (const std::bad_alloc&) {
-        set_error("out of host memory");
-        return VB2_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return VB2_ERR_INVALID;
-    }
+    });
 }
 
 int vb2_bootstrap_weights(int32_t num_marker, int32_t num_rep, uint32_t seed, uint8_t* out)
@@ -615,17 +466,11 @@ int vb2_run_replicates(const vb2_run_args* args, int32_t per_chromosome, int32_t
                          sum.boot_mean, sum.boot_sd, sum.boot_p025, sum.boot_p975);
         return VB2_OK;
     };
-    try {
+    return guarded([&] {
         const int rc = vb2::run_with_hook(args, out, hook);
         if (summary) *summary = sum;
         return rc;
-    } catch (const std::bad_alloc&) {
-        set_error("out of host memory");
-        return VB2_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return VB2_ERR_INVALID;
-    }
+    });
 }
 
 }  // extern "C"

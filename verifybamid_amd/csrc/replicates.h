@@ -1,16 +1,14 @@
 // replicates.h -- weighted-marker likelihood replicates: many integer weight vectors over ONE resident
-// sample, evaluated together (marker_sum_kernels.hip) and searched in lock-step (lockstep.h).  vb2_replicates_* of the C-ABI.
+// sample, evaluated together (marker_sum_kernels.hip) and searched in lock-step (refit.h).  vb2_replicates_* of the C-ABI.
 #ifndef VB2_REPLICATES_H_
 #define VB2_REPLICATES_H_
-
-#include <hip/hip_runtime_api.h>
 
 #include <cstdint>
 #include <functional>
 #include <vector>
 
 #include "../../include/vb2_abi.h"
-#include "point_stage.h"
+#include "row_set.h"
 
 struct vb2_flat;
 
@@ -18,34 +16,20 @@ namespace vb2 {
 
 class Context;
 
-class Replicates {
+// A row set (row_set.h: eval, time_launch, num_row, device_bytes) whose rows are weight vectors.  Its eval refuses a null llk
+// before anything reaches the stream.
+class Replicates : public RowSet {
 public:
     // weight: [num_rep][ctx->num_marker] counts in panel order.  Device memory from the slab cache: the sorted weight rows
     // [num_rep][m_pad] and one stage (rows, weight-row indices, results, a launch's partial sums); the context must outlive it.
     static int create(Context* ctx, int num_rep, const uint8_t* weight, Replicates** out);
-    ~Replicates();
-    // replicate r evaluates num_point[r] (0..VB2_BATCH_SLOTS) points; rows and results concatenated in replicate order
-    int eval(const int32_t* num_point, const double* pc1, const double* pc2, const double* alpha, double* llk);
     // one OptimizeLLK per replicate under `model`, all advancing in lock-step, each step one eval()
     int optimize(const vb2_model& model, vb2_estimate* est, int32_t* status);
-    // Measurement aid (tools/conditioned_time.py; event-timed, milliseconds per repetition into ms[reps]): ONE launch pair
-    // of num_point <= kMaxPointsPerLaunch points (pc = 0.01, alpha = 0.03), point p under weight row p % num_rep.
-    int time_launch(int num_point, int warmup, int reps, double* ms);
 
-    Context* ctx = nullptr;
-    int num_rep = 0;
     std::vector<int64_t> counted;          // [num_rep] counted markers of the sample with a weight > 0
-    int64_t device_bytes = 0;              // what the set holds in device memory
-    // eval() calls that reached the device, and their marker launches
-    int64_t num_step() const { return stage_.num_step; }
-    int64_t num_launch() const { return stage_.num_launch; }
 
 private:
-    Replicates() {}
-    PointStage::Launch launcher() const;
-    uint8_t* d_weights_ = nullptr;
-    size_t d_weights_bytes_ = 0;
-    PointStage stage_;                     // num_rep * VB2_BATCH_SLOTS points; the indices: weight rows
+    Replicates();
 };
 
 // The lock-step driver over any evaluator of a step (vb2_replicates_lockstep; no device): replicate r's search is the

@@ -217,6 +217,24 @@ int SourceSet::add(Context* ctx, const vb2_model& model, const vb2_estimate& est
     return put(slot, ctx, model, est);
 }
 
+void search_point(const Context& ctx, const vb2_model& model, const vb2_estimate& est, std::vector<double>* p1,
+                  std::vector<double>* p2, double* alpha)
+{
+    // the search's own point: the reported PCs with the reference's swap of indices 0, 1 undone (as interval.cpp) ...
+    const int k = ctx.num_pc;
+    const bool kaf = model.is_af_known != 0 || ctx.L.known_af != nullptr;
+    const bool heter = model.is_heter && !kaf;
+    p1->assign(est.pc, est.pc + k);
+    p2->assign(est.pc2, est.pc2 + k);
+    if (heter && est.alpha >= 0.5 && k >= 1) {
+        std::swap((*p1)[0], (*p2)[0]);
+        if (k >= 2) std::swap((*p1)[1], (*p2)[1]);
+    }
+    // ... mirrored when the fit put the larger share first: g1 is always the minor component
+    if (est.alpha >= 0.5) p1->swap(*p2);
+    if (alpha) *alpha = est.alpha >= 0.5 ? 1.0 - est.alpha : est.alpha;
+}
+
 int SourceSet::put(int slot, Context* ctx, const vb2_model& model, const vb2_estimate& est)
 {
     if (slot < 0 || slot >= capacity_ || !ctx) {
@@ -227,21 +245,9 @@ int SourceSet::put(int slot, Context* ctx, const vb2_model& model, const vb2_est
         set_error("vb2_source_set_add: the context is of another panel size or on another device than the set");
         return VB2_ERR_INVALID;
     }
-    // the search's own point: the reported PCs with the reference's swap of indices 0, 1 undone (as interval.cpp) ...
-    const int k = ctx->num_pc;
-    const bool kaf = model.is_af_known != 0 || ctx->L.known_af != nullptr;
-    const bool heter = model.is_heter && !kaf;
-    std::vector<double> p1(est.pc, est.pc + k), p2(est.pc2, est.pc2 + k);
-    double alpha = est.alpha;
-    if (heter && alpha >= 0.5 && k >= 1) {
-        std::swap(p1[0], p2[0]);
-        if (k >= 2) std::swap(p1[1], p2[1]);
-    }
-    // ... mirrored when the fit put the larger share first: g1 is always the minor component
-    if (alpha >= 0.5) {
-        p1.swap(p2);
-        alpha = 1.0 - alpha;
-    }
+    std::vector<double> p1, p2;
+    double alpha = 0;
+    search_point(*ctx, model, est, &p1, &p2, &alpha);
     float* row = d_slab_ + (size_t)slot * row_floats_;
     if (planes_ == VB2_SET_SOURCE) {
         if (const int rc = ctx->marginals(p1.data(), p2.data(), alpha, nullptr, nullptr, nullptr, row)) return rc;

@@ -14,6 +14,12 @@
 
 namespace vb2 {
 
+// The search point of `ctx`'s sample as a source set takes it (SourceSet::put), from the estimate a search under `model`
+// reported: the reference's swap of indices 0 and 1 undone (as interval.cpp), then mirrored when the fit put the larger
+// share first -- p1 [num_pc] is always the minor component's, *alpha (may be null) its share.
+void search_point(const Context& ctx, const vb2_model& model, const vb2_estimate& est, std::vector<double>* p1,
+                  std::vector<double>* p2, double* alpha);
+
 class SourceSet {
 public:
     // planes: VB2_SET_SOURCE (c q), VB2_SET_RELATED (q h t) or both (c q h t)

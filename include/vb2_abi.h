@@ -570,6 +570,16 @@ typedef struct vb2_pair_fit {
 int vb2_cohort_run_paired(const vb2_cohort_args *args, int32_t num_pair, const int32_t *tumour, const int32_t *normal,
                           double hom_min, vb2_run_result *out /* [num_sample] */, int32_t *status /* [num_sample] */,
                           vb2_pair_fit *fits /* [num_pair] or NULL */);
+/* vb2_cohort_run_paired followed by ONE vb2_paired_interval (3f) over every refitted pair, on the
+ * parked tumour contexts before they are released (--MatchedNormal --PairInterval): ci [num_pair] or NULL, zeroed for a pair
+ * without a refit or whose interval failed (a NOTICE; the run goes on).  <output_prefix>.PairCI is written (tab-separated,
+ * %g, names as in the pair file, NA for such a pair and for an SE that does not exist):
+ *     #TUMOUR NORMAL MARKERS ALPHA_PAIRED SE LO95 HI95 LLK_MAX LLK_LO LLK_HI POS_DEF PROFILE_POINTS
+ * ALPHA_PAIRED is unfolded and LO95 / HI95 lie within [0, 1].  stdout, .selfSM, .Ancestry and .PairFit are what
+ * vb2_cohort_run_paired writes, byte for byte. */
+int vb2_cohort_run_paired_intervals(const vb2_cohort_args *args, int32_t num_pair, const int32_t *tumour, const int32_t *normal,
+                                    double hom_min, vb2_run_result *out /* [num_sample] */, int32_t *status /* [num_sample] */,
+                                    vb2_pair_fit *fits /* [num_pair] or NULL */, vb2_interval *ci /* [num_pair] or NULL */);
 /* The --MatchedNormal file: lines "TUMOUR<TAB>NORMAL", each a pileup path exactly as in pileup_paths.  tumour / normal:
  * [num_sample] (a tumour is listed once).  VB2_ERR_IO: the file cannot be read; VB2_ERR_INVALID with a message that names
  * the line: a name that is not in the list, a tumour listed twice, a sample paired with itself, no pair at all.  Host only. */
@@ -830,6 +840,43 @@ typedef int (*vb2_paired_eval_fn)(void *user, int32_t num_hyp, const int32_t *nu
                                   const double *pc2, const double *alpha, double *llk);
 int vb2_paired_lockstep(vb2_paired_eval_fn fn, void *user, int32_t num_hyp, int32_t num_pc, const vb2_model *model,
                         const double *pc2_fixed, vb2_estimate *est_out, int32_t *status);
+
+/* 3f. Derivatives of LLK(. | h) and the interval of a paired refit.  Section 10's math with 3e's
+ *     rule per marker and per side: where a side's triple is given, its prior is that triple and nothing at the marker
+ *     depends on that side's PCs (P' = P'' = 0 there); a left-out marker adds nothing; a marker counts where L > 0.
+ *
+ * vb2_paired_derivs: hypothesis h evaluates num_point[h] >= 0 points (any number; chunks inside), rows concatenated in
+ * hypothesis order as in vb2_paired_eval: llk [sum], grad [sum][2k+1], hess [sum][2k+1][2k+1] in the order pc1 pc2 alpha, as
+ * vb2_llk_derivs_batch returns them.  Every chunk is ONE launch pair over all hypotheses that still have points.  A point's
+ * results are the same bits whatever else the call holds and from call to call; with both sides all zero and no marker
+ * left out they are vb2_llk_derivs_batch's bits; the blocks of a side whose prior is given at every walked marker are
+ * exactly 0; a hypothesis that leaves every marker out gives zeros.  The per-hypothesis marker scratch comes from the slab
+ * cache on the first call and is counted in vb2_paired_info.device_bytes from then on. */
+int vb2_paired_derivs(vb2_paired *pair, const int32_t *num_point, const double *pc1, const double *pc2, const double *alpha,
+                      double *llk, double *grad, double *hess);
+/* The same for every hypothesis of every set -- the sets may be on different contexts of one device and must share num_pc --
+ * every chunk still ONE launch pair: num_point [sum of num_hyp] in set order, rows and results concatenated in that order.
+ * A point's results are vb2_paired_derivs' bits on its own set. */
+int vb2_paired_derivs_sets(vb2_paired *const *sets, int32_t num_set, const int32_t *num_point, const double *pc1,
+                           const double *pc2, const double *alpha, double *llk, double *grad, double *hess);
+/* The interval of every hypothesis of every set at est[] (the results of vb2_paired_optimize_llk under `model` with the same
+ * pc2_fixed [num_set][num_pc]), all in ONE lock-step gang: every step is ONE launch pair with the point of every interval
+ * still running, whatever set or context it is on (all on one device).  alpha is reported as fitted, never folded: the
+ * profile runs over alpha in [0, 1], lo = 0 where the profile at 0 is above the cut and hi = 1 where the profile at 1 is.
+ * Free parameters: the contaminant's PCs, then logit alpha; alpha alone with is_pc_fixed or known allele frequencies;
+ * is_alpha_fixed is VB2_ERR_INVALID.  Rows of vb2_interval: row 0 is alpha (in `freemix`, row_kind 0), then the
+ * ContaminatingSample.PC rows (row_kind 1) as fitted.  out / status: [sum of num_hyp] in set order; out[i] is bit for bit
+ * what the hypothesis gives alone; status VB2_ERR_INVALID for a hypothesis that walks no marker (the others finish).
+ * *num_step (may be NULL): the launch pairs taken = the largest num_launch. */
+int vb2_paired_interval(vb2_paired *const *sets, int32_t num_set, const vb2_model *model, const double *pc2_fixed,
+                        const vb2_estimate *est, vb2_interval *out, int32_t *status, int64_t *num_step);
+/* The same driver over a caller's derivative evaluator (vb2_batch_derivs_fn, one slot per hypothesis): no device needed.
+ * held: 0 none -- vb2_intervals_lockstep's intervals bit for bit, fold included --, 1 pc1, 2 pc2; fixed [num_hyp][num_pc]
+ * the held side's PCs (NULL with held = 0), which are what fn sees on that side at every call.  held = 1 is the interval
+ * of a refit given the contaminant (3d): its rows after row 0 are the IntendedSample.PC rows. */
+int vb2_paired_intervals_lockstep(vb2_batch_derivs_fn fn, void *user, int32_t num_hyp, int32_t num_pc,
+                                  const int32_t *data_has_known_af, const vb2_model *model, int32_t held, const double *fixed,
+                                  const vb2_estimate *est, vb2_interval *out, int32_t *status, int64_t *num_step);
 
 /* Host-side flattening only (no device): reads panel + pileup, resolves markers
  * and returns the arrays of vb2_input in library-owned memory; free with

@@ -236,6 +236,7 @@ SYMBOLS = [
     "vb2_conditioned_optimize_llk", "vb2_conditioned_info_get", "vb2_conditioned_lockstep", "vb2_cohort_run_source_fits",
     "vb2_paired_create", "vb2_paired_create_from_set", "vb2_paired_destroy", "vb2_paired_eval", "vb2_paired_optimize_llk",
     "vb2_paired_info_get", "vb2_paired_lockstep", "vb2_cohort_run_paired", "vb2_matched_normal_read",
+    "vb2_cohort_run_paired_intervals", "vb2_paired_derivs", "vb2_paired_derivs_sets", "vb2_paired_interval", "vb2_paired_intervals_lockstep",
 ]
 
 _lib = None
@@ -375,11 +376,22 @@ def lib():
     L.vb2_paired_info_get.argtypes = [C.c_void_p, C.POINTER(PairedInfo), C.c_void_p]
     L.vb2_paired_lockstep.argtypes = [PAIRED_EVAL_FN, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Model), C.c_void_p,
                                       C.POINTER(Estimate), C.POINTER(C.c_int32)]
+    L.vb2_paired_derivs.argtypes = [C.c_void_p] * 8
+    L.vb2_paired_derivs_sets.argtypes = [C.POINTER(C.c_void_p), C.c_int32] + [C.c_void_p] * 7
+    L.vb2_paired_interval.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(Model), C.c_void_p, C.POINTER(Estimate),
+                                      C.POINTER(Interval), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    L.vb2_paired_intervals_lockstep.argtypes = [BATCH_DERIVS_FN, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                                C.POINTER(Model), C.c_int32, C.c_void_p, C.POINTER(Estimate),
+                                                C.POINTER(Interval), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     L.vb2_cohort_run_paired.argtypes = [C.POINTER(CohortArgs), C.c_int32, C.c_void_p, C.c_void_p, C.c_double,
                                         C.POINTER(RunResult), C.POINTER(C.c_int32), C.POINTER(PairFit)]
+    L.vb2_cohort_run_paired_intervals.argtypes = [C.POINTER(CohortArgs), C.c_int32, C.c_void_p, C.c_void_p, C.c_double,
+                                                  C.POINTER(RunResult), C.POINTER(C.c_int32), C.POINTER(PairFit),
+                                                  C.POINTER(Interval)]
     L.vb2_matched_normal_read.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_void_p,
                                           C.c_void_p]
     L.vb2_debug_paired_time.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+    L.vb2_debug_paired_derivs_time.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     L.vb2_debug_replicates_time.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     L.vb2_debug_set_tunable.argtypes = [C.c_char_p, C.c_int]
     L.vb2_debug_get_tunable.argtypes = [C.c_char_p, C.POINTER(C.c_int)]

@@ -805,6 +805,113 @@ class Paired(_RowSet):
         return _optimize_sets("vb2_paired_optimize_llk", sets, pc2_fixed, **model_kw)
 
 
+    def derivatives(self, num_point, pc1, pc2, alpha):
+        """LLK(. | h), its gradient and Hessian with respect to (pc1[0..k), pc2[0..k), alpha) (vb2_paired_derivs): num_point
+        [H] ints >= 0 (any number); pc1 / pc2 [P, k] and alpha [P] with P = sum(num_point), the hypotheses' rows one after the
+        other.  Returns (llk [P], grad [P, 2k+1], hess [P, 2k+1, 2k+1]).  Where a side's prior is given its PC entries are
+        0; a left-out marker adds nothing; at alpha 0 or 1 the alpha entries are not defined."""
+        k = self.num_pc
+        npt = np.ascontiguousarray(num_point, dtype=np.int32).reshape(self.num_hyp)
+        P = int(npt.sum())
+        pc1 = np.ascontiguousarray(np.asarray(pc1, dtype=np.float64).reshape(P, k))
+        pc2 = np.ascontiguousarray(np.asarray(pc2, dtype=np.float64).reshape(P, k))
+        alpha = np.ascontiguousarray(np.asarray(alpha, dtype=np.float64).reshape(P))
+        n = 2 * k + 1
+        llk, grad, hess = np.zeros(P), np.zeros((P, n)), np.zeros((P, n, n))
+        _abi.check(self._lib.vb2_paired_derivs(self._h, _p(npt), _p(pc1), _p(pc2), _p(alpha), _p(llk), _p(grad), _p(hess)),
+                   "vb2_paired_derivs")
+        return llk, grad, hess
+
+    @staticmethod
+    def derivatives_sets(sets, num_point, pc1, pc2, alpha):
+        """derivatives for every hypothesis of several sets -- on different contexts of one device -- in one launch pair per
+        chunk (vb2_paired_derivs_sets): num_point [sum of num_hyp] in set order.  Every row is the bits of derivatives on
+        its own set."""
+        k, S = sets[0].num_pc, len(sets)
+        npt = np.ascontiguousarray(num_point, dtype=np.int32).reshape(sum(c.num_hyp for c in sets))
+        P = int(npt.sum())
+        pc1 = np.ascontiguousarray(np.asarray(pc1, dtype=np.float64).reshape(P, k))
+        pc2 = np.ascontiguousarray(np.asarray(pc2, dtype=np.float64).reshape(P, k))
+        alpha = np.ascontiguousarray(np.asarray(alpha, dtype=np.float64).reshape(P))
+        n = 2 * k + 1
+        llk, grad, hess = np.zeros(P), np.zeros((P, n)), np.zeros((P, n, n))
+        handles = (C.c_void_p * S)(*[c._h for c in sets])
+        _abi.check(_abi.lib().vb2_paired_derivs_sets(handles, S, _p(npt), _p(pc1), _p(pc2), _p(alpha), _p(llk), _p(grad),
+                                                     _p(hess)), "vb2_paired_derivs_sets")
+        return llk, grad, hess
+
+    def interval(self, estimates, pc2_fixed, **model_kw):
+        """The 95 % interval of every hypothesis's refit (Paired.interval_sets on this set alone): one dict per hypothesis."""
+        return Paired.interval_sets([self], [estimates], [pc2_fixed], **model_kw)[0][0]
+
+    @staticmethod
+    def interval_sets(sets, estimates, pc2_fixed, **model_kw):
+        """vb2_paired_interval: the intervals of every hypothesis of every set in ONE lock-step gang, every step one launch
+        pair.  estimates: per set the list optimize_sets returned under the same model and pc2_fixed [num_set, k].  Returns
+        (per set a list of dicts as LikelihoodContext.interval gives them -- "freemix" is alpha as fitted, unfolded, its
+        interval within [0, 1]; the rows after the first are the contaminant's PCs; "status" --, the launch pairs taken)."""
+        k, S = sets[0].num_pc, len(sets)
+        fixed = np.ascontiguousarray(np.asarray(pc2_fixed, dtype=np.float64).reshape(S, k))
+        m, keep = _model(**model_kw)
+        H = sum(c.num_hyp for c in sets)
+        flat = [e for per_set in estimates for e in per_set]
+        if len(flat) != H:
+            raise ValueError("one estimate per hypothesis of every set")
+        handles = (C.c_void_p * S)(*[c._h for c in sets])
+        est = (_abi.Estimate * H)(*[_estimate_struct(e, k) for e in flat])
+        ci = (_abi.Interval * H)()
+        status = (C.c_int32 * H)()
+        steps = C.c_int64(0)
+        _abi.check(_abi.lib().vb2_paired_interval(handles, S, C.byref(m), _p(fixed), est, ci, status, C.byref(steps)),
+                   "vb2_paired_interval")
+        del keep
+        out, at = [], 0
+        for c in sets:
+            out.append([dict(_interval_dict(ci[at + h]), status=int(status[at + h])) for h in range(c.num_hyp)])
+            at += c.num_hyp
+        return out, int(steps.value)
+
+
+def paired_intervals_with_evaluator(evaluate, num_pc, estimates, fixed, held="pc2", known_af=None, **model_kw):
+    """The paired interval driver over a Python derivative evaluator (vb2_paired_intervals_lockstep): no device.
+    evaluate as for intervals_with_evaluator, one slot per hypothesis; the rows it sees on the held side ("pc2", "pc1") are
+    fixed [H, k] at every call.  held=None: the anonymous model's intervals, fold included (fixed is not read).  Returns
+    (intervals, num_step)."""
+    L = _abi.lib()
+    k, H = int(num_pc), len(estimates)
+    n = 2 * k + 1
+    err = []
+
+    def cb(_user, ns, npt, p1, p2, a, llk, grad, hess):
+        try:
+            points, P = _step_points(ns, npt, p1, p2, a, k)
+            res = evaluate(*points)
+            np.ctypeslib.as_array(llk, (P,))[:] = np.asarray(res[0], dtype=np.float64).reshape(P)
+            np.ctypeslib.as_array(grad, (P, n))[:] = np.asarray(res[1], dtype=np.float64).reshape(P, n)
+            np.ctypeslib.as_array(hess, (P, n, n))[:] = np.asarray(res[2], dtype=np.float64).reshape(P, n, n)
+            return 0
+        except Exception as exc:   # never let an exception cross the C boundary
+            err.append(exc)
+            return _abi.VB2_ERR_INVALID
+    fn = _abi.BATCH_DERIVS_FN(cb)
+    code = {None: 0, "pc1": 1, "pc2": 2}[held]
+    flags = [bool(f) for f in known_af] if known_af is not None else [False] * H
+    m, keep = _model(known_af=False, **model_kw)
+    kaf = (C.c_int32 * H)(*[int(f) for f in flags])
+    fx = None if code == 0 else np.ascontiguousarray(np.asarray(fixed, dtype=np.float64).reshape(H, k))
+    est = (_abi.Estimate * H)(*[_estimate_struct(e, k) for e in estimates])
+    ci = (_abi.Interval * H)()
+    status = (C.c_int32 * H)()
+    steps = C.c_int64(0)
+    rc = L.vb2_paired_intervals_lockstep(fn, None, H, k, kaf, C.byref(m), code, None if fx is None else _p(fx), est, ci, status,
+                                         C.byref(steps))
+    del keep
+    if err:
+        raise err[0]
+    _abi.check(rc, "vb2_paired_intervals_lockstep")
+    return [dict(_interval_dict(ci[h]), status=int(status[h])) for h in range(H)], int(steps.value)
+
+
 def paired_with_evaluator(evaluate, num_hyp, num_pc, pc2_fixed, known_af=False, **model_kw):
     """The paired refits' lock-step driver over a Python evaluator (vb2_paired_lockstep): no device.
     evaluate(num_point [H] int32, pc1 [P, k], pc2 [P, k], alpha [P]) -> llk [P], P = sum(num_point), called once per step
@@ -1026,7 +1133,7 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
                      known_af_path=None, device=-1, output_pileup=False, group_size=0, num_host_thread=0,
                      devices=None, find_source=False, source_top=3, sources_prefix=None, confidence_interval=False,
                      refit_source=False, find_related=False, related_top=3, matched_normal=None, normal_hom_min=0.99,
-                     **model_kw):
+                     pair_interval=False, **model_kw):
     """Many pileups against one panel (vb2_cohort_run): the panel is read once, the pileups are read
     and flattened by host threads while the device searches the previous group in lock-step.
     Returns one dict per sample (with its own "status" code).
@@ -1046,8 +1153,12 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
     matched_normal (vb2_cohort_run_paired; one device; with none of the above): a list of (tumour, normal) sample indices;
     returns (samples, fits), one dict per pair -- tumour, normal, markers, status (0: refitted, 1: the tumour or the normal
     failed its own run, < 0: the refit's error), normal_freemix, freemix, freelk1, alpha_paired, lk1_paired, lk0_paired --
-    and with output_prefixes and sources_prefix <sources_prefix>.PairFit is written.  normal_hom_min: --NormalHomMin."""
+    and with output_prefixes and sources_prefix <sources_prefix>.PairFit is written.  normal_hom_min: --NormalHomMin.
+    pair_interval (with matched_normal; vb2_cohort_run_paired_intervals): every refitted pair's dict also has `interval` --
+    alpha_paired unfolded in "freemix", its interval within [0, 1] -- and <sources_prefix>.PairCI is written."""
     S = len(pileup_paths)
+    if pair_interval and matched_normal is None:
+        raise ValueError("pair_interval needs matched_normal")
     if matched_normal is not None and (find_source or find_related or confidence_interval or refit_source):
         raise ValueError("matched_normal cannot be combined with find_source, find_related, confidence_interval or refit_source")
     if find_related and (confidence_interval or refit_source):
@@ -1076,8 +1187,13 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
         pairs = np.ascontiguousarray(np.asarray(matched_normal, dtype=np.int32).reshape(-1, 2))
         tum, nrm = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
         pfits = (_abi.PairFit * max(len(pairs), 1))()
-        _abi.check(_abi.lib().vb2_cohort_run_paired(C.byref(ca), len(pairs), _p(tum), _p(nrm), float(normal_hom_min), res, status,
-                                                    pfits), "vb2_cohort_run_paired")
+        pci = (_abi.Interval * max(len(pairs), 1))()
+        if pair_interval:
+            _abi.check(_abi.lib().vb2_cohort_run_paired_intervals(C.byref(ca), len(pairs), _p(tum), _p(nrm), float(normal_hom_min),
+                                                                  res, status, pfits, pci), "vb2_cohort_run_paired_intervals")
+        else:
+            _abi.check(_abi.lib().vb2_cohort_run_paired(C.byref(ca), len(pairs), _p(tum), _p(nrm), float(normal_hom_min), res,
+                                                        status, pfits), "vb2_cohort_run_paired")
     elif find_related:
         llr, shared = np.zeros((S, S, _abi.VB2_NUM_RELATION)), np.zeros((S, S), dtype=np.int32)
         _abi.check(_abi.lib().vb2_cohort_run_related(C.byref(ca), int(related_top), int(source_top) if find_source else 0, res,
@@ -1107,7 +1223,11 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
             d["interval"] = _interval_dict(civ[s])
         out.append(d)
     if matched_normal is not None:
-        return out, [{name: getattr(pfits[p], name) for name, _ in _abi.PairFit._fields_} for p in range(len(pairs))]
+        fits = [{name: getattr(pfits[p], name) for name, _ in _abi.PairFit._fields_} for p in range(len(pairs))]
+        for p, f in enumerate(fits):
+            if pair_interval and f["status"] == _abi.VB2_OK and pci[p].num_profile > 0:
+                f["interval"] = _interval_dict(pci[p])
+        return out, fits
     if find_related:
         return out, dict(llr=llr, shared=shared)
     if refit_source:

@@ -106,6 +106,7 @@ int main(int argc, char** argv)
     int bootstrap = 0;
     std::string MatchedNormal("Empty");
     double normalHomMin = 0.99;
+    bool pairInterval = false;
     // "Pileup Options" (main.cpp:176-187), defaults main.cpp:81-96 (MPLP_REALN | MPLP_SMART_OVERLAPS; UNMAP | SECONDARY |
     // QCFAIL | DUP): they shape what --BamFile input becomes and, as in the reference, do nothing to --PileupFile input
     int minBQ = 13, minMQ = 2, adjustMQ = 40, maxDepth = 8000, inclFlags = (1 << 4) | (1 << 10), exclFlags = 0x4 | 0x100 | 0x200 | 0x400;
@@ -182,6 +183,9 @@ int main(int argc, char** argv)
         // list; only the markers where the normal is homozygous with a posterior of at least --NormalHomMin are used
         {"MatchedNormal", {Flag::kString, &MatchedNormal, false}},
         {"NormalHomMin", {Flag::kDouble, &normalHomMin, false}},
+        // not in the reference: with --MatchedNormal, a 95% confidence interval (profile likelihood, unfolded) and a
+        // standard error for every ALPHA_PAIRED, computed in lock-step (vb2_cohort_run_paired_intervals), to <Output>.PairCI
+        {"PairInterval", {Flag::kBool, &pairInterval, false}},
     };
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
@@ -266,6 +270,8 @@ int main(int argc, char** argv)
         if (!(normalHomMin >= 0.0 && normalHomMin <= 1.0)) fatal("--NormalHomMin takes a probability within [0, 1]");
     } else if (flags["NormalHomMin"].seen) {
         fatal("--NormalHomMin needs --MatchedNormal");
+    } else if (pairInterval) {
+        fatal("--PairInterval needs --MatchedNormal: it computes the interval of every tumour's FREEMIX given its matched normal");
     }
     if (findSource) {                                                   // a cohort on one device
         if (PileupList == "Empty")
@@ -428,7 +434,10 @@ int main(int argc, char** argv)
         if (MatchedNormal != "Empty" &&         // (before the panel is read and any device is touched)
             vb2_matched_normal_read(MatchedNormal.c_str(), ca.num_sample, cpile.data(), &numPair, tumour.data(), normal.data()) != VB2_OK)
             fatal(vb2_last_error());
-        const int rcc = numPair > 0 ? vb2_cohort_run_paired(&ca, numPair, tumour.data(), normal.data(), normalHomMin, cres.data(), cst.data(), nullptr)
+        const int rcc = numPair > 0 && pairInterval
+                            ? vb2_cohort_run_paired_intervals(&ca, numPair, tumour.data(), normal.data(), normalHomMin, cres.data(),
+                                                              cst.data(), nullptr, nullptr)
+                        : numPair > 0 ? vb2_cohort_run_paired(&ca, numPair, tumour.data(), normal.data(), normalHomMin, cres.data(), cst.data(), nullptr)
                         : findRelated ? vb2_cohort_run_related(&ca, relatedTop, findSource ? sourceTop : 0, cres.data(), cst.data(), nullptr, nullptr)
                         : cohortInterval ? vb2_cohort_run_intervals(&ca, findSource ? sourceTop : 0, cres.data(), cst.data(), nullptr)
                         : refitSource ? vb2_cohort_run_source_fits(&ca, sourceTop, cres.data(), cst.data(), nullptr, nullptr, nullptr)

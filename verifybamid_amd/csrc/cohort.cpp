@@ -128,10 +128,14 @@ public:
 
     // paired (vb2_cohort_run_paired; --MatchedNormal): the listed normals get a q row in a source set, the listed tumours'
     // contexts are parked instead of destroyed, and after the last sample every pair is refitted (paired.h) --
-    // <Output>.PairFit, and fits[p] when fits is not null
-    void enable_paired(int num_pair, const int32_t* tumour, const int32_t* normal, double hom_min, vb2_pair_fit* fits)
+    // <Output>.PairFit, and fits[p] when fits is not null.  interval (vb2_cohort_run_paired_intervals; --PairInterval): and
+    // then ONE vb2_paired_interval over the refitted pairs, before the contexts go -- <Output>.PairCI, and ci[p]
+    void enable_paired(int num_pair, const int32_t* tumour, const int32_t* normal, double hom_min, vb2_pair_fit* fits,
+                       bool interval = false, vb2_interval* ci = nullptr)
     {
         paired_ = true;
+        pair_interval_ = interval;
+        pair_ci_ = ci;
         pair_t_.assign(tumour, tumour + num_pair);
         pair_n_.assign(normal, normal + num_pair);
         hom_min_ = hom_min;
@@ -408,10 +412,11 @@ private:
     // The tail both refits share: the one-row sets on the parked contexts, ALL in one lock-step call of `optimize` between
     // the phase's notices.  fit[who[n]].status becomes set n's (the call's own failure is everybody's), a failure gives
     // "NOTICE - <failed> <who[n] + first>" with the last error, and the sets go before their contexts do.  The estimates, by set.
+    // keep: the sets stay (the caller has more to do on them, and clears them itself).
     template <class Set, class Optimize, class Fit>
     std::vector<vb2_estimate> refit_sets(const char* phase, const char* failed, int first, Optimize optimize,
                                          std::vector<std::unique_ptr<Set>>& sets, const std::vector<double>& fixed,
-                                         const std::vector<int>& who, std::vector<Fit>& fit)
+                                         const std::vector<int>& who, std::vector<Fit>& fit, bool keep = false)
     {
         std::vector<vb2_estimate> est(sets.size());
         if (sets.empty()) return est;
@@ -428,7 +433,7 @@ private:
             if (f.status != VB2_OK)
                 std::fprintf(stderr, "NOTICE - %s %d failed: %s\n", failed, who[n] + first, vb2::g_last_error.c_str());
         }
-        sets.clear();
+        if (!keep) sets.clear();
         return est;
     }
 
@@ -510,6 +515,8 @@ private:
     std::vector<char> is_tumour_, is_normal_;  // [sample]
     double hom_min_ = 0.99;
     vb2_pair_fit* pair_fit_ = nullptr;
+    bool pair_interval_ = false;               // --PairInterval
+    vb2_interval* pair_ci_ = nullptr;
 
     // --MatchedNormal, after the last sample: one refit per pair whose tumour and normal were both searched -- a
     // one-hypothesis set on the tumour's parked context, built on the device from the normal's q row --, ALL in one lock-step
@@ -566,7 +573,7 @@ private:
             fixed.insert(fixed.end(), p2.begin(), p2.end());
         }
         const std::vector<vb2_estimate> est = refit_sets("Refit given the matched normal", "--MatchedNormal: the refit of pair", 1,
-                                                         vb2::paired_optimize, sets, fixed, who, fit);
+                                                         vb2::paired_optimize, sets, fixed, who, fit, pair_interval_);
         for (size_t i = 0; i < who.size(); ++i) {
             vb2_pair_fit& f = fit[(size_t)who[i]];
             if (f.status != VB2_OK) continue;
@@ -574,9 +581,51 @@ private:
             f.lk1_paired = est[i].llk1;
             f.lk0_paired = est[i].llk0;
         }
+        // --PairInterval: the intervals of the refitted pairs, ALL in one lock-step gang on the parked contexts
+        std::vector<vb2_interval> ci((size_t)P);
+        std::vector<int32_t> ci_status((size_t)P, VB2_PAIR_FIT_NONE);
+        if (P > 0) std::memset(ci.data(), 0, sizeof(vb2_interval) * (size_t)P);
+        if (pair_interval_) {
+            std::vector<vb2::Paired*> raw;
+            std::vector<int> pair_of;
+            std::vector<double> fixed_l;
+            std::vector<vb2_estimate> est_l;
+            const int k = a_->base.num_pc;
+            for (size_t i = 0; i < who.size(); ++i) {
+                if (fit[(size_t)who[i]].status != VB2_OK) continue;
+                raw.push_back(sets[i].get());
+                pair_of.push_back(who[i]);
+                fixed_l.insert(fixed_l.end(), fixed.begin() + (long)i * k, fixed.begin() + (long)(i + 1) * k);
+                est_l.push_back(est[i]);
+            }
+            if (!raw.empty()) {
+                std::vector<vb2_interval> ci_l(raw.size());
+                std::vector<int32_t> st_l(raw.size(), VB2_ERR_INVALID);
+                int64_t steps = 0;
+                const double t0 = now_s();
+                if (model_.notices)
+                    std::fprintf(stderr, "NOTICE - Starting phase: Intervals given the matched normal (%d intervals in lock-step)\n",
+                                 (int)raw.size());
+                const int rc = vb2::paired_interval(raw.data(), (int)raw.size(), model_, fixed_l.data(), est_l.data(), ci_l.data(),
+                                                    st_l.data(), &steps);
+                if (model_.notices)
+                    std::fprintf(stderr, "NOTICE - Finished phase: Intervals given the matched normal (%lld launch pairs)  [%.3f seconds]\n",
+                                 (long long)steps, now_s() - t0);
+                for (size_t i = 0; i < raw.size(); ++i) {
+                    const int p = pair_of[i];
+                    ci_status[(size_t)p] = rc ? rc : st_l[i];
+                    if (ci_status[(size_t)p] == VB2_OK) ci[(size_t)p] = ci_l[i];
+                    else std::fprintf(stderr, "NOTICE - --PairInterval: the interval of pair %d failed: %s\n", p + 1, vb2::g_last_error.c_str());
+                }
+            }
+            sets.clear();                              // (before their contexts go)
+            if (pair_ci_) std::memcpy(pair_ci_, ci.data(), sizeof(vb2_interval) * (size_t)P);
+        }
         if (pair_fit_) std::memcpy(pair_fit_, fit.data(), sizeof(vb2_pair_fit) * (size_t)P);
         if (a_->output_prefixes && a_->base.output_prefix) {
-            const int rc = vb2::write_pair_fit(a_->base.output_prefix, P, a_->pileup_paths, fit.data());
+            int rc = vb2::write_pair_fit(a_->base.output_prefix, P, a_->pileup_paths, fit.data());
+            if (!rc && pair_interval_)
+                rc = vb2::write_pair_ci(a_->base.output_prefix, P, a_->pileup_paths, fit.data(), ci.data(), ci_status.data());
             if (rc) {
                 err_all_ = vb2::g_last_error;
                 return rc;
@@ -1200,8 +1249,9 @@ extern "C" int vb2_cohort_run_intervals(const vb2_cohort_args* a, int32_t source
     });
 }
 
-extern "C" int vb2_cohort_run_paired(const vb2_cohort_args* a, int32_t num_pair, const int32_t* tumour, const int32_t* normal,
-                                     double hom_min, vb2_run_result* out, int32_t* status, vb2_pair_fit* fits)
+namespace {
+int cohort_run_paired(const vb2_cohort_args* a, int32_t num_pair, const int32_t* tumour, const int32_t* normal, double hom_min,
+                      vb2_run_result* out, int32_t* status, vb2_pair_fit* fits, bool interval, vb2_interval* ci)
 {
     if (!a || !out || !status || a->num_sample < 1 || !a->pileup_paths || !a->base.ud_path || !a->base.mean_path ||
         !a->base.bed_path || a->base.num_pc < 1 || a->base.num_pc > VB2_MAX_PC || num_pair < 1 || !tumour || !normal) {
@@ -1223,9 +1273,23 @@ extern "C" int vb2_cohort_run_paired(const vb2_cohort_args* a, int32_t num_pair,
     if (const int rc = vb2::check_pairs("vb2_cohort_run_paired", a->num_sample, num_pair, tumour, normal)) return rc;
     return vb2::guarded([&] {
         CohortRunner runner(a, out, status);
-        runner.enable_paired(num_pair, tumour, normal, hom_min, fits);
+        runner.enable_paired(num_pair, tumour, normal, hom_min, fits, interval, ci);
         const int rc = runner.run();
         if (rc && !runner.error().empty()) set_error(runner.error());
         return rc;
     });
+}
+}  // namespace
+
+extern "C" int vb2_cohort_run_paired(const vb2_cohort_args* a, int32_t num_pair, const int32_t* tumour, const int32_t* normal,
+                                     double hom_min, vb2_run_result* out, int32_t* status, vb2_pair_fit* fits)
+{
+    return cohort_run_paired(a, num_pair, tumour, normal, hom_min, out, status, fits, false, nullptr);
+}
+
+extern "C" int vb2_cohort_run_paired_intervals(const vb2_cohort_args* a, int32_t num_pair, const int32_t* tumour,
+                                               const int32_t* normal, double hom_min, vb2_run_result* out, int32_t* status,
+                                               vb2_pair_fit* fits, vb2_interval* ci)
+{
+    return cohort_run_paired(a, num_pair, tumour, normal, hom_min, out, status, fits, true, ci);
 }

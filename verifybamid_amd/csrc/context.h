@@ -244,18 +244,33 @@ int write_ci(const std::string& prefix, const vb2_interval& ci);
 // The same interval over any evaluator of ONE point's LLK, gradient [2k+1] and Hessian [2k+1][2k+1] (order pc1 pc2 alpha):
 // the same points in the same order whatever answers them.  label (may be null) starts the NOTICE lines.
 typedef std::function<int(const double* pc1, const double* pc2, double alpha, double* llk, double* grad, double* hess)> DerivFn;
+// What the interval of a refit with one side held differs in; the defaults are the anonymous model's
+// interval, bit for bit.
+//   held, fixed: that side's PCs are `fixed` [num_pc] at every point and no parameter.  The free parameters are the other
+//     side's PCs, then x = logit alpha (alpha alone with is_pc_fixed or known allele frequencies), whatever is_heter says;
+//     the estimate's PCs are taken as they stand (a refit swaps no indices), and the rows after row 0 are that side's.
+//   fold = false: alpha is reported as fitted and the profile runs over f = alpha in [0, 1] -- lo = 0 where the profile at
+//     0 is above the cut, hi = 1 where the profile at 1 is.  (The fold at 0.5 rests on the symmetry pc1 <-> pc2,
+//     alpha <-> 1 - alpha, which a likelihood given priors lacks: section 16, identity 6.)
+struct IntervalOptions {
+    enum Held { kNone = 0, kPc1 = 1, kPc2 = 2 };
+    int held = kNone;
+    const double* fixed = nullptr;
+    bool fold = true;
+};
 int interval_at(int num_pc, bool data_has_known_af, const vb2_model& model, const vb2_estimate& est, const DerivFn& fn,
-                vb2_interval* out, const char* label);
+                vb2_interval* out, const char* label, const IntervalOptions* opt = nullptr);
 // A batched evaluator: slot s has num_point[s] (0 or 1 here) points, the rows of all slots concatenated in slot order.
 typedef std::function<int(int32_t num_slot, const int32_t* num_point, const double* pc1, const double* pc2, const double* alpha,
                           double* llk, double* grad, double* hess)> BatchDerivsFn;
 // interval_at for every sample, advancing in lock-step (lockstep.h: one fiber per sample, parked at every request; a step =
 // ONE call of fn with every live sample's point, made on the caller's own stack).  A sample whose interval ends early stops
 // contributing.  status[s]: the sample's own code; the return value: a failure of fn (it ends every interval).
-// models: 1 or num_sample entries; labels: null or [num_sample]; *num_step (may be null): calls of fn.
+// models: 1 or num_sample entries; labels: null or [num_sample]; *num_step (may be null): calls of fn; opts: null (the
+// defaults) or [num_sample].
 int intervals_lockstep(int num_sample, int num_pc, const int32_t* data_has_known_af, const vb2_model* models, int num_model,
                        const vb2_estimate* est, const BatchDerivsFn& fn, vb2_interval* out, int32_t* status, int64_t* num_step,
-                       const char* const* labels);
+                       const char* const* labels, const IntervalOptions* opts = nullptr);
 class Batch;
 int batch_interval(Batch* b, const vb2_model* models, int num_model, const vb2_estimate* est, vb2_interval* out, int32_t* status,
                    int64_t* num_step, const char* const* labels);

@@ -44,6 +44,18 @@ struct DerivJob {
 // stream-ordered before this call -- on the device.  Every point's results are launch_llk_derivs' bits.
 hipError_t launch_llk_derivs_multi(const DerivJob* h_jobs, const DerivJob* d_jobs, int num_job, hipStream_t stream);
 
+// The derivatives of LLK(. | h) for a pair hypothesis (DESIGN.md sections 16 and 17): d_planes its six planes [6][m_pad] in
+// the layout's sorted order (pi1[0..2] | pi2[0..2], marker_sum_kernels.h).  A marker whose pi2[0] is negative is not walked
+// and adds ten zeros; a side whose triple is not all zero takes it for its prior and has no derivative in its PCs there.
+// The same scratch, outputs and reduction as launch_llk_derivs; all-zero planes give its bits.
+hipError_t launch_llk_pair_derivs(const DeviceLayout& L, int num_point, const double* d_points, const float* d_planes,
+                                  double* d_marker, double* d_out, hipStream_t stream);
+// ... and of several (context, hypothesis) jobs in one launch pair: job j's hypothesis is d_planes[j] (a table in device
+// memory beside d_jobs, in the jobs' order).  Two hypotheses of one context are two jobs with that context's layout and
+// marker scratch of their own.  Every point's results are launch_llk_pair_derivs' bits.
+hipError_t launch_llk_pair_derivs_multi(const DerivJob* h_jobs, const DerivJob* d_jobs, const float* const* d_planes, int num_job,
+                                        hipStream_t stream);
+
 }  // namespace vb2
 
 #endif

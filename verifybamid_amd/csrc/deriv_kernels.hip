@@ -18,6 +18,10 @@
 //   * llk_derivs_marker_multi_kernel / llk_derivs_reduce_multi_kernel: the same two bodies for the points of SEVERAL samples
 //     in one launch pair (Batch::derivs), each workgroup reading its sample's layout through a job table in device memory.
 //     A point's results are the single-sample kernels' bits.
+//   * llk_pair_derivs_marker_kernel / llk_pair_derivs_marker_multi_kernel: the marker body given a pair hypothesis (DESIGN.md
+//     sections 16 and 17), its Prior template parameter a PairPrior: a marker the hypothesis leaves out is not walked, and a
+//     side with a prior at a marker is (pi, 0, 0) there.  The anonymous kernels are the body under HardyWeinberg, which
+//     compiles to nothing.  The reduction kernels serve both.
 #include "deriv_kernels.h"
 
 #include "marker_walk.h"
@@ -53,11 +57,61 @@ __device__ __forceinline__ void gf_derivs(double af, bool fixed, double* gf, dou
     d2[2] = clamped ? 0.0 : 2.0;
 }
 
+// A Prior: what a marker's genotype priors are, a small struct the body makes per marker from the planes of the point's
+// hypothesis and holds by value (the Term of marker_sum_kernels.hip, for the derivatives).  walks() -- false: the marker is
+// left out, not walked, and contributes ten zeros -- is asked before the marker's record is read; apply(), in the
+// epilogue, may replace a side's {GF, GF', GF''}.
+struct HardyWeinberg {                            // the anonymous model: GF1(pc1), GF2(pc2) at every marker
+    __device__ __forceinline__ explicit HardyWeinberg(const float*) {}
+    __device__ __forceinline__ bool walks(size_t, size_t) const { return true; }
+    __device__ __forceinline__ void apply(size_t, size_t, double*, double*, double*, double*, double*, double*) const {}
+};
+
+// A pair hypothesis (DESIGN.md sections 16 and 17): six planes [6][mp], pi1[0..2] then pi2[0..2], as PairTerm reads them.
+struct PairPrior {
+    const float* row;
+    float b0;
+    __device__ __forceinline__ explicit PairPrior(const float* r) : row(r) {}
+    // a negative pi2[0] leaves the marker out of the hypothesis: read before the marker's record
+    __device__ __forceinline__ bool walks(size_t pos, size_t mp)
+    {
+        b0 = row[3 * mp + pos];
+        return !(b0 < 0.0f);
+    }
+    // The other five floats are loaded here, behind the walk: only the epilogue needs them, and the probability-domain
+    // kernels have no registers to keep them live across it.  A triple that is not all zero stands in for that side's
+    // Hardy-Weinberg prior, and nothing at the marker depends on that side's PCs any more: (pi, 0, 0).  The float32 values
+    // widened to double, exactly as PairTerm::prior() uses them.
+    __device__ __forceinline__ void apply(size_t pos, size_t mp, double* G1, double* G1d, double* G1dd, double* G2, double* G2d,
+                                          double* G2dd) const
+    {
+        const float a0 = row[pos], a1 = row[mp + pos], a2 = row[2 * mp + pos];
+        const float b1 = row[4 * mp + pos], b2 = row[5 * mp + pos];
+        const bool given1 = a0 != 0.0f || a1 != 0.0f || a2 != 0.0f;
+        const bool given2 = b0 != 0.0f || b1 != 0.0f || b2 != 0.0f;
+        G1[0] = given1 ? (double)a0 : G1[0];
+        G1[1] = given1 ? (double)a1 : G1[1];
+        G1[2] = given1 ? (double)a2 : G1[2];
+        G2[0] = given2 ? (double)b0 : G2[0];
+        G2[1] = given2 ? (double)b1 : G2[1];
+        G2[2] = given2 ? (double)b2 : G2[2];
+#pragma unroll
+        for (int g = 0; g < 3; ++g) {
+            G1d[g] = given1 ? 0.0 : G1d[g];
+            G1dd[g] = given1 ? 0.0 : G1dd[g];
+            G2d[g] = given2 ? 0.0 : G2d[g];
+            G2dd[g] = given2 ? 0.0 : G2dd[g];
+        }
+    }
+};
+
 // The body of the marker kernels: point pt of `points`, as workgroup bx of the nbx that share the point's 16-tile groups.
-// What a marker's ten scalars are does not depend on bx / nbx, nor on where L was read from.
-template <bool PD>
+// What a marker's ten scalars are does not depend on bx / nbx, nor on where L was read from.  planes: the hypothesis of a
+// PairPrior (HardyWeinberg: not read).
+template <bool PD, class Prior>
 __device__ __forceinline__ void derivs_marker_body(const DeviceLayout& L, const double* __restrict__ points,
-                                                   double* __restrict__ out, double* tab, int pt, int bx, int nbx)
+                                                   const float* __restrict__ planes, double* __restrict__ out, double* tab,
+                                                   int pt, int bx, int nbx)
 {
     constexpr int kRowDoubles = PD ? kRowDoublesPd : kRowDoublesLog;
     const int tid = threadIdx.x;
@@ -138,6 +192,11 @@ __device__ __forceinline__ void derivs_marker_body(const DeviceLayout& L, const 
             for (int j = 0; j < kDerivVals; ++j) o[(size_t)j * mp] = 0.0;
             continue;
         }
+        Prior prior(planes);
+        if (!prior.walks(pos, mp)) {
+            for (int j = 0; j < kDerivVals; ++j) o[(size_t)j * mp] = 0.0;
+            continue;
+        }
         const uint2 rec = L.mt_rec[mt];
         double acc[6], a1[6], a2[6], dacc[3];
         for (int p = 0; p < 6; ++p) { acc[p] = PD ? 1.0 : L.ediag[pos]; a1[p] = 0.0; a2[p] = 0.0; }
@@ -205,6 +264,7 @@ __device__ __forceinline__ void derivs_marker_body(const DeviceLayout& L, const 
         double G1[3], G1d[3], G1dd[3], G2[3], G2d[3], G2dd[3];
         gf_derivs(af1, kaf, G1, G1d, G1dd);
         gf_derivs(af2, kaf, G2, G2d, G2dd);
+        prior.apply(pos, mp, G1, G1d, G1dd, G2, G2d, G2dd);
         double W[3][3], WA[3][3], WB[3][3];
         const double cst = PD ? L.ediag[pos] : 0.0;
         for (int g = 0; g < 3; ++g) { W[g][g] = L.ediag[(size_t)(1 + g) * mp + pos]; WA[g][g] = 0.0; WB[g][g] = 0.0; }
@@ -290,7 +350,17 @@ __global__ void __launch_bounds__(kThreads)
 llk_derivs_marker_kernel(const DeviceLayout L, const double* __restrict__ points, double* __restrict__ out)
 {
     extern __shared__ __attribute__((aligned(16))) double tab[];      // [nrow][6 pairs][kEntry] (+ [3] in the log domain)
-    derivs_marker_body<PD>(L, points, out, tab, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x);
+    derivs_marker_body<PD, HardyWeinberg>(L, points, nullptr, out, tab, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// The same given ONE pair hypothesis, `planes` [6][m_pad]
+template <bool PD>
+__global__ void __launch_bounds__(kThreads)
+llk_pair_derivs_marker_kernel(const DeviceLayout L, const double* __restrict__ points, const float* __restrict__ planes,
+                              double* __restrict__ out)
+{
+    extern __shared__ __attribute__((aligned(16))) double tab[];
+    derivs_marker_body<PD, PairPrior>(L, points, planes, out, tab, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // The same for several samples: workgroup (x, y, z) is stripe x of point y of job z.  The job -- its layout included -- is
@@ -304,7 +374,22 @@ llk_derivs_marker_multi_kernel(const DerivJob* __restrict__ jobs)
     const DerivJob& job = jobs[blockIdx.z];
     if ((int)blockIdx.y >= job.num_point) return;
     if ((int)blockIdx.x >= tile_groups(job.L)) return;
-    derivs_marker_body<PD>(job.L, job.points, job.marker, tab, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x);
+    derivs_marker_body<PD, HardyWeinberg>(job.L, job.points, nullptr, job.marker, tab, (int)blockIdx.y, (int)blockIdx.x,
+                                          (int)gridDim.x);
+}
+
+// ... and given pair hypotheses: job z's is planes[z], [6][m_pad] of its own context's order.  Several hypotheses of one
+// context are several jobs with that context's layout, each with marker scratch of its own.
+template <bool PD>
+__global__ void __launch_bounds__(kThreads)
+llk_pair_derivs_marker_multi_kernel(const DerivJob* __restrict__ jobs, const float* const* __restrict__ planes)
+{
+    extern __shared__ __attribute__((aligned(16))) double tab[];
+    const DerivJob& job = jobs[blockIdx.z];
+    if ((int)blockIdx.y >= job.num_point) return;
+    if ((int)blockIdx.x >= tile_groups(job.L)) return;
+    derivs_marker_body<PD, PairPrior>(job.L, job.points, planes[blockIdx.z], job.marker, tab, (int)blockIdx.y, (int)blockIdx.x,
+                                      (int)gridDim.x);
 }
 
 // Output e of a point (deriv_out_count): 0 = LLK, then the gradient, then the Hessian's upper triangle row by row.
@@ -383,15 +468,21 @@ llk_derivs_reduce_multi_kernel(const DerivJob* __restrict__ jobs)
 
 }  // namespace
 
-hipError_t launch_llk_derivs(const DeviceLayout& L, int num_point, const double* d_points, double* d_marker, double* d_out,
-                             hipStream_t stream)
+namespace {
+hipError_t launch_derivs(const DeviceLayout& L, int num_point, const double* d_points, const float* d_planes, double* d_marker,
+                         double* d_out, hipStream_t stream)
 {
     if (num_point <= 0) return hipSuccess;
     if (num_point > kDerivChunk) return hipErrorInvalidValue;
     const int nrow = L.num_code + 1;
     const size_t shmem = (size_t)nrow * (L.pd ? kRowDoublesPd : kRowDoublesLog) * sizeof(double);
     const dim3 grid((unsigned)stripe_grid(L, num_point), (unsigned)num_point), block(kThreads);
-    if (L.pd)
+    if (d_planes) {
+        if (L.pd)
+            hipLaunchKernelGGL(llk_pair_derivs_marker_kernel<true>, grid, block, shmem, stream, L, d_points, d_planes, d_marker);
+        else
+            hipLaunchKernelGGL(llk_pair_derivs_marker_kernel<false>, grid, block, shmem, stream, L, d_points, d_planes, d_marker);
+    } else if (L.pd)
         hipLaunchKernelGGL(llk_derivs_marker_kernel<true>, grid, block, shmem, stream, L, d_points, d_marker);
     else
         hipLaunchKernelGGL(llk_derivs_marker_kernel<false>, grid, block, shmem, stream, L, d_points, d_marker);
@@ -401,8 +492,24 @@ hipError_t launch_llk_derivs(const DeviceLayout& L, int num_point, const double*
     hipLaunchKernelGGL(llk_derivs_reduce_kernel, rgrid, block, 0, stream, L, d_marker, d_out);
     return hipGetLastError();
 }
+}  // namespace
 
-hipError_t launch_llk_derivs_multi(const DerivJob* h_jobs, const DerivJob* d_jobs, int num_job, hipStream_t stream)
+hipError_t launch_llk_derivs(const DeviceLayout& L, int num_point, const double* d_points, double* d_marker, double* d_out,
+                             hipStream_t stream)
+{
+    return launch_derivs(L, num_point, d_points, nullptr, d_marker, d_out, stream);
+}
+
+hipError_t launch_llk_pair_derivs(const DeviceLayout& L, int num_point, const double* d_points, const float* d_planes,
+                                  double* d_marker, double* d_out, hipStream_t stream)
+{
+    if (!d_planes) return hipErrorInvalidValue;
+    return launch_derivs(L, num_point, d_points, d_planes, d_marker, d_out, stream);
+}
+
+namespace {
+hipError_t launch_derivs_multi(const DerivJob* h_jobs, const DerivJob* d_jobs, const float* const* d_planes, int num_job,
+                               hipStream_t stream)
 {
     if (num_job <= 0) return hipSuccess;
     // the jobs come sorted: probability domain first.  Per class one launch of the marker kernel.
@@ -436,7 +543,14 @@ hipError_t launch_llk_derivs_multi(const DerivJob* h_jobs, const DerivJob* d_job
         }
         const int gx = gx_all < max_grp ? gx_all : max_grp;
         const dim3 grid((unsigned)gx, (unsigned)kDerivChunk, (unsigned)count);
-        if (cls == 0)
+        if (d_planes) {
+            if (cls == 0)
+                hipLaunchKernelGGL(llk_pair_derivs_marker_multi_kernel<true>, grid, block, shmem, stream, d_jobs + first,
+                                   d_planes + first);
+            else
+                hipLaunchKernelGGL(llk_pair_derivs_marker_multi_kernel<false>, grid, block, shmem, stream, d_jobs + first,
+                                   d_planes + first);
+        } else if (cls == 0)
             hipLaunchKernelGGL(llk_derivs_marker_multi_kernel<true>, grid, block, shmem, stream, d_jobs + first);
         else
             hipLaunchKernelGGL(llk_derivs_marker_multi_kernel<false>, grid, block, shmem, stream, d_jobs + first);
@@ -446,6 +560,19 @@ hipError_t launch_llk_derivs_multi(const DerivJob* h_jobs, const DerivJob* d_job
     const dim3 rgrid((unsigned)nout, (unsigned)kDerivChunk, (unsigned)num_job);
     hipLaunchKernelGGL(llk_derivs_reduce_multi_kernel, rgrid, block, 0, stream, d_jobs);
     return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_llk_derivs_multi(const DerivJob* h_jobs, const DerivJob* d_jobs, int num_job, hipStream_t stream)
+{
+    return launch_derivs_multi(h_jobs, d_jobs, nullptr, num_job, stream);
+}
+
+hipError_t launch_llk_pair_derivs_multi(const DerivJob* h_jobs, const DerivJob* d_jobs, const float* const* d_planes, int num_job,
+                                        hipStream_t stream)
+{
+    if (!d_planes) return hipErrorInvalidValue;
+    return launch_derivs_multi(h_jobs, d_jobs, d_planes, num_job, stream);
 }
 
 }  // namespace vb2

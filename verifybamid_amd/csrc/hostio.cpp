@@ -986,6 +986,40 @@ int write_pair_fit(const std::string& prefix, int num_pair, const char* const* n
     return VB2_OK;
 }
 
+// <prefix>.PairCI: one row per pair; NA where the pair has no refit or its interval failed, and for an SE that does not exist
+int write_pair_ci(const std::string& prefix, int num_pair, const char* const* names, const vb2_pair_fit* fit, const vb2_interval* ci,
+                  const int32_t* ci_status)
+{
+    const std::string name(prefix + ".PairCI");
+    std::FILE* f = std::fopen(name.c_str(), "w");
+    if (!f) return io_error("cannot write " + name);
+    std::fprintf(f, "#TUMOUR\tNORMAL\tMARKERS\tALPHA_PAIRED\tSE\tLO95\tHI95\tLLK_MAX\tLLK_LO\tLLK_HI\tPOS_DEF\tPROFILE_POINTS\n");
+    auto num = [f](double v) {
+        if (std::isnan(v)) std::fprintf(f, "\tNA");
+        else std::fprintf(f, "\t%g", v);
+    };
+    for (int p = 0; p < num_pair; ++p) {
+        const vb2_pair_fit& s = fit[p];
+        const vb2_interval& c = ci[p];
+        std::fprintf(f, "%s\t%s", names[s.tumour], names[s.normal]);
+        if (s.status != VB2_OK || ci_status[p] != VB2_OK) {
+            std::fprintf(f, "\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\n");
+            continue;
+        }
+        std::fprintf(f, "\t%d", (int)s.markers);
+        num(c.freemix);
+        num(c.freemix_se);
+        num(c.lo);
+        num(c.hi);
+        num(c.llk_max);
+        num(c.llk_lo);
+        num(c.llk_hi);
+        std::fprintf(f, "\t%d\t%d\n", (int)c.pos_def, (int)c.num_profile);
+    }
+    if (std::fclose(f) != 0) return io_error("cannot write " + name);
+    return VB2_OK;
+}
+
 // what vb2_cohort_run_paired refuses in a list of pairs (vb2_matched_normal_read says the same of a file, by line)
 int check_pairs(const char* who, int num_sample, int num_pair, const int32_t* tumour, const int32_t* normal)
 {

@@ -130,6 +130,9 @@ int write_pileup(const std::string& prefix, const vb2_flat& f);
 void print_summary(const char* title, int numPC, const vb2_estimate& est);
 // <prefix>.PairFit (vb2_cohort_run_paired): names [num_sample], fit [num_pair]
 int write_pair_fit(const std::string& prefix, int num_pair, const char* const* names, const vb2_pair_fit* fit);
+// <prefix>.PairCI (--PairInterval): ci / ci_status [num_pair], the interval of pair p's refit and its own code
+int write_pair_ci(const std::string& prefix, int num_pair, const char* const* names, const vb2_pair_fit* fit, const vb2_interval* ci,
+                  const int32_t* ci_status);
 // VB2_ERR_INVALID with a message for an index out of range, a sample paired with itself or a tumour listed twice
 int check_pairs(const char* who, int num_sample, int num_pair, const int32_t* tumour, const int32_t* normal);
 // The panel files of a run (abi.cpp): .UD and .mu parsed on helper threads while the caller's

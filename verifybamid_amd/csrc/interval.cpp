@@ -30,6 +30,7 @@ const double kNaN = std::numeric_limits<double>::quiet_NaN();
 struct Free {
     int k = 0, nu = 0;
     bool heter = false, shared = false, pc2_free = false, alpha_free = false;
+    bool one_side = false, side_pc2 = false;     // a refit with one side held: u = the other side's PCs (side_pc2: pc2's)
     std::vector<double> base1, base2;            // the fixed parts: the estimate's PCs
     void unpack(const double* u, double* pc1, double* pc2) const
     {
@@ -37,6 +38,8 @@ struct Free {
         if (nu == 0) return;
         if (shared) {
             for (int j = 0; j < k; ++j) pc1[j] = pc2[j] = u[j];
+        } else if (one_side) {
+            for (int j = 0; j < k; ++j) (side_pc2 ? pc2 : pc1)[j] = u[j];
         } else {
             for (int j = 0; j < k; ++j) pc1[j] = u[j];
             if (pc2_free) for (int j = 0; j < k; ++j) pc2[j] = u[k + j];
@@ -44,7 +47,7 @@ struct Free {
     }
     // full coordinate(s) of u component i: pc1[i] -> i, pc2[i] -> k + i; a shared PC is both
     int nmap(int) const { return shared ? 2 : 1; }
-    int map(int i, int t) const { return shared ? (t == 0 ? i : k + i) : i; }
+    int map(int i, int t) const { return shared ? (t == 0 ? i : k + i) : (one_side && side_pc2) ? k + i : i; }
 };
 
 // One point: LLK, and its derivatives in u and alpha
@@ -170,32 +173,43 @@ int ctx_interval(Context* ctx, const vb2_model& model_in, const vb2_estimate& es
 }
 
 int interval_at(int k, bool data_has_known_af, const vb2_model& model_in, const vb2_estimate& est, const DerivFn& fn,
-                vb2_interval* out, const char* label)
+                vb2_interval* out, const char* label, const IntervalOptions* opt)
 {
     std::memset(out, 0, sizeof(*out));
+    const IntervalOptions defaults;
+    const IntervalOptions& o = opt ? *opt : defaults;
+    const bool held = o.held != IntervalOptions::kNone;
+    if (held && !o.fixed) {
+        set_error("interval: a held side without its PCs");
+        return VB2_ERR_INVALID;
+    }
     const bool kaf = model_in.is_af_known != 0 || data_has_known_af;
     const std::string who = label ? std::string(label) + ": " : std::string();       // (a cohort run: whose NOTICE it is)
-    const bool heter = model_in.is_heter && !kaf;                                  // apply_model (estimator.cpp)
+    const bool heter = model_in.is_heter && !kaf && !held;                         // apply_model (estimator.cpp)
     const bool pcfix = (model_in.is_pc_fixed && model_in.fix_pc) || kaf;
     const bool afix = !pcfix && model_in.is_alpha_fixed;
     const bool notices = model_in.notices != 0;
     Free fr;
     fr.k = k;
     fr.heter = heter;
-    fr.shared = !heter && !pcfix;
+    fr.shared = !heter && !pcfix && !held;
     fr.pc2_free = heter && !pcfix;
+    fr.one_side = held && !pcfix;
+    fr.side_pc2 = o.held == IntervalOptions::kPc1;
     fr.alpha_free = !afix;
     fr.nu = heter ? (pcfix ? k : 2 * k) : (pcfix ? 0 : k);
-    // the search's own point: the reported PCs with the reference's swap of indices 0, 1 undone (estimator.cpp)
+    // the search's own point: the reported PCs with the reference's swap of indices 0, 1 undone (estimator.cpp); a held
+    // side is where it is held
     fr.base1.assign(est.pc, est.pc + k);
     fr.base2.assign(est.pc2, est.pc2 + k);
+    if (held) (o.held == IntervalOptions::kPc1 ? fr.base1 : fr.base2).assign(o.fixed, o.fixed + k);
     const bool swapped = heter && est.alpha >= 0.5;
     if (swapped && k >= 1) {
         std::swap(fr.base1[0], fr.base2[0]);
         if (k >= 2) std::swap(fr.base1[1], fr.base2[1]);
     }
     std::vector<double> u0(fr.nu);
-    for (int j = 0; j < fr.nu; ++j) u0[j] = j < k ? fr.base1[j] : fr.base2[j - k];
+    for (int j = 0; j < fr.nu; ++j) u0[j] = (fr.one_side && fr.side_pc2) ? fr.base2[j] : j < k ? fr.base1[j] : fr.base2[j - k];
     if (!est.converged && notices)
         std::fprintf(stderr, "NOTICE - %sthe search did not converge: the interval is computed at its best point all the same\n",
                      who.c_str());
@@ -204,7 +218,7 @@ int interval_at(int k, bool data_has_known_af, const vb2_model& model_in, const 
     const double a_hat = est.alpha;
     out->alpha_free = fr.alpha_free ? 1 : 0;
     out->num_free = fr.nu + (fr.alpha_free ? 1 : 0);
-    out->freemix = a_hat < 0.5 ? a_hat : 1 - a_hat;
+    out->freemix = (!o.fold || a_hat < 0.5) ? a_hat : 1 - a_hat;
 
     // ---- standard errors: -H in the free parameters (alpha as x = logit alpha: da/dx = a(1-a), d2a/dx2 = a(1-a)(1-2a)) ----
     Eval e;
@@ -241,8 +255,9 @@ int interval_at(int k, bool data_has_known_af, const vb2_model& model_in, const 
     out->lo = out->hi = out->llk_lo = out->llk_hi = kNaN;
     out->llk_max = -est.llk1;
     if (fr.alpha_free) {
-        const bool side = a_hat >= 0.5;                    // profile at alpha = 1 - f: the estimate's side
+        const bool side = o.fold && a_hat >= 0.5;          // profile at alpha = 1 - f: the estimate's side
         const double f_hat = out->freemix;
+        const double f_top = o.fold ? 0.5 : 1.0;           // where f ends
         struct Pt { double f, v; std::vector<double> u; };
         std::vector<Pt> pts;
         double llk_max = -est.llk1;
@@ -277,7 +292,7 @@ int interval_at(int k, bool data_has_known_af, const vb2_model& model_in, const 
         double v_hat = 0, v0 = 0, v5 = 0;
         if (int rc = lp(f_hat, &v_hat)) return rc;
         if (int rc = lp(0.0, &v0)) return rc;
-        if (int rc = lp(0.5, &v5)) return rc;
+        if (int rc = lp(f_top, &v5)) return rc;
         // the root of lp(f) = llk_max - c between a and b (lp on opposite sides of the cut there): Illinois false position,
         // to |b - a| <= max(1e-6 f, 1e-9)
         auto root = [&](double a, double va, double b, double vb, double* r, double* vr) -> int {
@@ -308,8 +323,8 @@ int interval_at(int k, bool data_has_known_af, const vb2_model& model_in, const 
         };
         if (v0 >= llk_max - kHalfChi2) { out->lo = 0.0; out->llk_lo = v0; }
         else if (int rc = root(0.0, v0, f_hat, v_hat, &out->lo, &out->llk_lo)) return rc;
-        if (v5 >= llk_max - kHalfChi2) { out->hi = 0.5; out->llk_hi = v5; }
-        else if (int rc = root(f_hat, v_hat, 0.5, v5, &out->hi, &out->llk_hi)) return rc;
+        if (v5 >= llk_max - kHalfChi2) { out->hi = f_top; out->llk_hi = v5; }
+        else if (int rc = root(f_hat, v_hat, f_top, v5, &out->hi, &out->llk_hi)) return rc;
         if (llk_max > -est.llk1 + 1e-9 * std::fabs(est.llk1) && notices)
             std::fprintf(stderr, "NOTICE - %sa profile point has a higher log-likelihood (%.10g) than the search's estimate "
                                  "(%.10g): the search stopped short of the maximum\n", who.c_str(), llk_max, -est.llk1);
@@ -320,6 +335,7 @@ int interval_at(int k, bool data_has_known_af, const vb2_model& model_in, const 
     std::vector<double> se1(k, kNaN), se2(k, kNaN), v1(est.pc, est.pc + k), v2(est.pc2, est.pc2 + k);
     for (int j = 0; j < nu; ++j) {
         if (fr.shared) se1[j] = se2[j] = se[j];
+        else if (fr.one_side) (fr.side_pc2 ? se2 : se1)[j] = se[j];
         else if (j < k) se1[j] = se[j];
         else se2[j - k] = se[j];
     }
@@ -341,6 +357,8 @@ int interval_at(int k, bool data_has_known_af, const vb2_model& model_in, const 
     auto wald = [&](int kind, int j, double v, double s) { row(kind, j + 1, v, s, v - kZ * s, v + kZ * s); };
     if (fr.shared) {
         for (int j = 0; j < k; ++j) wald(3, j, v1[j], se1[j]);
+    } else if (fr.one_side) {                              // the free side's PCs, as fitted: no index swap
+        for (int j = 0; j < k; ++j) wald(fr.side_pc2 ? 2 : 1, j, fr.side_pc2 ? fr.base2[j] : fr.base1[j], fr.side_pc2 ? se2[j] : se1[j]);
     } else if (heter) {
         for (int j = 0; j < k; ++j) wald(1, j, v1[j], se1[j]);
         if (fr.pc2_free) {
@@ -368,7 +386,7 @@ IntervalGang::IntervalGang(int num_fiber, int num_pc) : gang_(num_fiber, 1), k_(
             const DerivFn fn = [user](const double* pc1, const double* pc2, double a, double* llk, double* grad, double* hess) {
                 return FiberGang::derivs_cb(user, pc1, pc2, a, llk, grad, hess);      // (parks: no device call on this stack)
             };
-            rc = interval_at(k_, t.data_has_known_af, *t.model, *t.est, fn, t.out, t.label);
+            rc = interval_at(k_, t.data_has_known_af, *t.model, *t.est, fn, t.out, t.label, t.opt);
         } catch (const std::bad_alloc&) {
             rc = VB2_ERR_NOMEM;
         } catch (const std::exception& e) {
@@ -432,7 +450,7 @@ int IntervalGang::step(const BatchDerivsFn& fn)
 
 int intervals_lockstep(int num_sample, int num_pc, const int32_t* data_has_known_af, const vb2_model* models, int num_model,
                        const vb2_estimate* est, const BatchDerivsFn& fn, vb2_interval* out, int32_t* status, int64_t* num_step,
-                       const char* const* labels)
+                       const char* const* labels, const IntervalOptions* opts)
 {
     if (num_step) *num_step = 0;
     if (num_sample < 1 || num_pc < 1 || num_pc > VB2_MAX_PC || !models || (num_model != 1 && num_model != num_sample) || !est ||
@@ -448,6 +466,7 @@ int intervals_lockstep(int num_sample, int num_pc, const int32_t* data_has_known
         t.out = &out[s];
         t.data_has_known_af = data_has_known_af && data_has_known_af[s];
         t.label = labels ? labels[s] : nullptr;
+        t.opt = opts ? &opts[s] : nullptr;
         (void)g.spawn(s, t);                         // (up to its first request; a failure is the sample's own)
     }
     int rc = VB2_OK;

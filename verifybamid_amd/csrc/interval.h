@@ -20,6 +20,7 @@ public:
         vb2_interval* out = nullptr;
         bool data_has_known_af = false;
         const char* label = nullptr;        // starts the sample's NOTICE lines (null: none)
+        const IntervalOptions* opt = nullptr;   // null: the defaults
     };
     IntervalGang(int num_fiber, int num_pc);
     // fiber i takes the task and runs up to its first request, or to its end (what t points to outlives the fiber's run)

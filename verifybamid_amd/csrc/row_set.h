@@ -45,6 +45,7 @@ public:
         return begin(num_point, pc1, pc2, alpha, true);
     }
     int eval_end(double* llk) { return stage_.end(llk); }
+    bool eval_pending() const { return stage_.pending() != 0; }     // between an eval_begin with points and its eval_end
     // Measurement aid (tools/conditioned_time.py, paired_time.py, replicate_time.py; event-timed, milliseconds per repetition
     // into ms[reps]): ONE launch pair of num_point <= kMaxPointsPerLaunch points (pc = 0.01, alpha = 0.03), point p under
     // row p % num_row.

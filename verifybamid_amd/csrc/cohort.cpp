@@ -9,20 +9,27 @@
 // (vb2_batch_*; still there as VB2_COHORT_STREAM=0).  Samples are independent, so several devices
 // need no collective: sample s runs on devices[s % n] (--Devices a,b,...; groups: group g on
 // devices[g % n]), which is the sample-parallel sharding of SURVEY.md 8e(2) inside one process.
-// vb2_cohort_run_intervals (--CohortInterval; one device): every searched sample's confidence interval as well, computed in
-// lock-step (interval.h) -- on the group's batch after its search, or, streaming, on an interval stage with a thread and a
-// stream of its own that takes the samples the search is done with.
+// --CohortInterval (one device): every searched sample's confidence interval as well, computed in lock-step (interval.h)
+// -- on the group's batch after its search, or, streaming, on an interval stage with a thread and a stream of its own that
+// takes the samples the search is done with.
+//
+// This unit is the PIPELINE: group schedule, readers, the streamed and the grouped device pipelines, the interval stage
+// and the releaser.  What a run does after its last sample is a list of vb2::CohortStage (cohort_stages.h; the stages and
+// the entry points that choose them: cohort_stages.cpp), and nothing here knows one by name.  Three rules hold whatever
+// the stages are:
+//   1. the releaser thread alone puts a sample into the run's set and parks its context, after the sample's files are
+//      written (streamed runs write them there, grouped runs on the device thread; a .CI before the sample gets there);
+//   2. a run ends in ONE order: every thread joined, the stages' finish() in the order given, the parked contexts
+//      destroyed, the run's own streams destroyed -- a set a stage builds on a parked context goes inside its finish();
+//   3. a device-level failure is recorded with the last error of the thread it happened on (device_failure).
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
-#include <chrono>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <cmath>
 #include <deque>
-#include <limits>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -30,25 +37,19 @@
 #include <vector>
 
 #include "batch.h"
-#include "conditioned.h"
+#include "cohort_stages.h"
 #include "context.h"
 #include "estimator.h"
 #include "guard.h"
 #include "hostio.h"
 #include "interval.h"
-#include "paired.h"
-#include "source.h"
 #include "stream_search.h"
 #include "tunables.h"
 
+using vb2::now_s;
 using vb2::set_error;
 
 namespace {
-
-double now_s()
-{
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 struct Slot {
     std::unique_ptr<vb2_flat> flat;
@@ -59,19 +60,13 @@ struct Slot {
 
 class CohortRunner {
 public:
-    // find_source: every searched sample also goes into a source set (vb2_cohort_run_sources) -- on the releaser thread,
-    // before its context is destroyed; score / shared ([S][S], may be null) and <Output>.Sources after the last sample
-    // intervals: every searched sample's vb2_interval as well (vb2_cohort_run_intervals; one device) -- <prefix>.CI, and
-    // ci[s] when ci is not null -- before the sample goes to the releaser
-    // refit (with find_source; vb2_cohort_run_source_fits): the contexts of the samples that got a row in the source set are
-    // parked instead of destroyed, and after the score matrix every sample's FREEMIX is refitted given its best candidate
-    // (conditioned.h) -- <Output>.SourceFit, and fit[s] when fit is not null
-    CohortRunner(const vb2_cohort_args* a, vb2_run_result* out, int32_t* status, bool find_source = false, int top = 0,
-                 double* score = nullptr, int32_t* shared = nullptr, bool intervals = false, vb2_interval* ci = nullptr,
-                 bool refit = false, vb2_source_fit* fit = nullptr)
-        : a_(a), out_(out), status_(status), S_(a->num_sample), find_source_(find_source), top_(top), score_(score),
-          shared_(shared), intervals_(intervals), ci_(ci), refit_(refit && find_source), fit_(fit)
+    // stages.after: what the run does after its last sample (cohort_stages.h); stages.intervals: every searched sample's
+    // vb2_interval as well (one device) -- <prefix>.CI, and ci[s] when ci is not null -- before the sample goes to the releaser
+    CohortRunner(const vb2_cohort_args* a, vb2_run_result* out, int32_t* status, const vb2::CohortStages& stages)
+        : a_(a), out_(out), status_(status), S_(a->num_sample), intervals_(stages.intervals), ci_(stages.ci)
     {
+        for (vb2::CohortStage* st : stages.after)
+            if (st) after_.push_back(st);
         if (a->base.devices && a->base.num_device > 0) devices_.assign(a->base.devices, a->base.devices + a->base.num_device);
         else devices_.push_back(a->base.device);
         ndev_ = (int)devices_.size();
@@ -116,44 +111,7 @@ public:
         ngroup_ = (int)group_begin_.size() - 1;
     }
 
-    // related (vb2_cohort_run_related): the set also keeps the related planes -- one marginal launch per sample all the same --,
-    // llr ([S][S][4]) / shared ([S][S]; may be null) and <Output>.Related after the last sample
-    void enable_related(int top, double* llr, int32_t* shared)
-    {
-        related_ = true;
-        related_top_ = top;
-        llr_ = llr;
-        rel_shared_ = shared;
-    }
-
-    // paired (vb2_cohort_run_paired; --MatchedNormal): the listed normals get a q row in a source set, the listed tumours'
-    // contexts are parked instead of destroyed, and after the last sample every pair is refitted (paired.h) --
-    // <Output>.PairFit, and fits[p] when fits is not null.  interval (vb2_cohort_run_paired_intervals; --PairInterval): and
-    // then ONE vb2_paired_interval over the refitted pairs, before the contexts go -- <Output>.PairCI, and ci[p]
-    void enable_paired(int num_pair, const int32_t* tumour, const int32_t* normal, double hom_min, vb2_pair_fit* fits,
-                       bool interval = false, vb2_interval* ci = nullptr)
-    {
-        paired_ = true;
-        pair_interval_ = interval;
-        pair_ci_ = ci;
-        pair_t_.assign(tumour, tumour + num_pair);
-        pair_n_.assign(normal, normal + num_pair);
-        hom_min_ = hom_min;
-        pair_fit_ = fits;
-        is_tumour_.assign((size_t)S_, 0);
-        is_normal_.assign((size_t)S_, 0);
-        for (int p = 0; p < num_pair; ++p) {
-            is_tumour_[(size_t)tumour[p]] = 1;
-            is_normal_[(size_t)normal[p]] = 1;
-        }
-    }
-
-    ~CohortRunner()
-    {
-        shutdown();
-        release_parked();
-        drop_streams();
-    }
+    ~CohortRunner() { shutdown(); release_parked_and_streams(); }
 
     int run()
     {
@@ -187,14 +145,15 @@ public:
         const double t_warm = now_s();
         model_ = a_->base.model;
         if (panel_->isAFknown) model_.is_af_known = 1;
-        if (find_source_ || related_ || paired_) {
+        int planes = 0;                                  // one set with every plane a stage reads: a sample is put once
+        for (const vb2::CohortStage* st : after_) planes |= st->planes;
+        if (planes) {
             vb2::SourceSet* set = nullptr;
-            const int planes = (find_source_ || paired_ ? VB2_SET_SOURCE : 0) | (related_ ? VB2_SET_RELATED : 0);
             if (const int rcs = vb2::SourceSet::create((int)panel_->NumMarker, S_, devices_[0], &set, planes)) {
                 err_all_ = vb2::g_last_error;
                 return rcs;
             }
-            sources_.reset(set);
+            set_.reset(set);
         }
         vb2::g_flatten_thread_cap.store(std::max(1, 16 / T_));
 
@@ -208,8 +167,7 @@ public:
         if (stream_ && vb2::tunables().cohort_own_queues) {
             own_streams_.assign((size_t)ndev_ * 4, nullptr);
             for (int d = 0; d < ndev_; ++d) {
-                int dev = devices_[d];
-                if (dev < 0) (void)hipGetDevice(&dev);
+                const int dev = device_index(d);
                 if (hipSetDevice(dev) != hipSuccess) { (void)hipGetLastError(); continue; }
                 vb2::drop_cached_streams(dev);
                 for (int q = 0; q < 4; ++q)
@@ -225,15 +183,11 @@ public:
         for (auto& t : dev_threads_) t.join();
         dev_threads_.clear();
         const double t_dev = now_s();
-        shutdown();
-        if (sources_ && find_source_ && !rc_all_) rc_all_ = finish_sources();
-        if (sources_ && related_ && !rc_all_) rc_all_ = finish_related();
-        if (refit_ || paired_) {
-            if (refit_ && !rc_all_) rc_all_ = refit_sources();
-            if (paired_ && !rc_all_) rc_all_ = refit_pairs();
-            release_parked();
-            drop_streams();
-        }
+        shutdown();                                      // (rule 2 of this file's head, for every run)
+        const vb2::CohortEnd end{a_, out_, status_, model_, set_.get(), parked_, parked_bytes_};
+        for (size_t i = 0; i < after_.size() && !rc_all_; ++i)
+            if ((rc_all_ = after_[i]->finish(end)) != VB2_OK) err_all_ = vb2::g_last_error;
+        release_parked_and_streams();
         if (timing)
             std::fprintf(stderr, "vb2_cohort_run: panel %.1f ms, HIP start-up beyond that %.1f ms, pipelines %.1f ms, "
                                  "shutdown (release contexts, join) %.1f ms; releaser: %.2f ms per context, %.2f ms per sample's host arrays\n",
@@ -268,7 +222,6 @@ private:
     std::thread releaser_;
     std::mutex rel_mu_;
     std::condition_variable rel_cv_;
-    std::deque<std::pair<vb2_ctx*, std::unique_ptr<vb2_flat>>> rel_queue_;
     bool rel_stop_ = false;
     bool down_ = false;
 
@@ -280,13 +233,14 @@ private:
     std::vector<int> inflight_;            // [device] samples handed to a reader and not yet done
     std::vector<int> remaining_;           // [device] samples not yet delivered to the search (or failed before it)
     std::vector<std::deque<int>> ready_q_; // [device] prepared samples, in the order they became ready
-    struct Done { int s; vb2_ctx* ctx; std::unique_ptr<vb2_flat> flat; bool write; vb2_estimate est; bool add = false; };
-    // --FindSource (null without it: nothing below then differs from a plain run)
-    bool find_source_ = false;
-    int top_ = 0;
-    double* score_ = nullptr;
-    int32_t* shared_ = nullptr;
-    std::unique_ptr<vb2::SourceSet> sources_;
+    // a sample on its way out: files to write (streamed runs); row: it was searched, the stages are asked about it
+    struct Done { int s; vb2_ctx* ctx; std::unique_ptr<vb2_flat> flat; bool write; vb2_estimate est; bool row = false; };
+    std::deque<Done> done_queue_;          // (rel_mu_)
+    // the stages after the run (none: a plain run), their set (null without planes), the contexts they keep (releaser thread)
+    std::vector<vb2::CohortStage*> after_;
+    std::unique_ptr<vb2::SourceSet> set_;
+    std::vector<vb2_ctx*> parked_;
+    int64_t parked_bytes_ = 0;
     // --CohortInterval (false without it: nothing below then differs from a plain run).  Streaming: a searched sample waits
     // in iv_queue_ for a fiber of the interval stage (interval_loop), which has a thread and a stream of its own.
     bool intervals_ = false;
@@ -296,66 +250,6 @@ private:
     std::condition_variable iv_cv_;
     std::deque<IvItem> iv_queue_;
     bool iv_closed_ = false;
-
-    // --RefitSource (false without it: nothing else then differs from a --FindSource run)
-    bool refit_ = false;
-    vb2_source_fit* fit_ = nullptr;
-    std::vector<vb2_ctx*> parked_;         // [sample] the context of a sample with a row in the source set (releaser thread)
-    int64_t parked_bytes_ = 0;
-    std::vector<double> sc_;               // the matrix, where the caller gave no room for it
-    std::vector<int32_t> sh_;
-    const double* fit_score_ = nullptr;
-    const int32_t* fit_shared_ = nullptr;
-
-    // after the last context is gone: the matrix, and <Output>.Sources next to the samples' own files
-    int finish_sources()
-    {
-        sources_->set_count(S_);
-        const size_t nn = (size_t)S_ * (size_t)S_;
-        std::vector<double>& sc = sc_;
-        std::vector<int32_t>& sh = sh_;
-        const bool file = a_->output_prefixes && a_->base.output_prefix;
-        double* score = score_;
-        int32_t* shared = shared_;
-        if ((file || refit_) && !score) { sc.resize(nn); score = sc.data(); }
-        if ((file || refit_) && !shared) { sh.resize(nn); shared = sh.data(); }
-        fit_score_ = score;
-        fit_shared_ = shared;
-        if (!score && !shared) return VB2_OK;
-        int rc = sources_->scores(score, shared);
-        if (!rc && file) rc = vb2::write_sources(a_->base.output_prefix, S_, top_, a_->output_prefixes, out_, status_, score, shared);
-        if (rc) err_all_ = vb2::g_last_error;
-        return rc;
-    }
-    // --FindRelated (false without it: nothing else then differs)
-    bool related_ = false;
-    int related_top_ = 0;
-    double* llr_ = nullptr;
-    int32_t* rel_shared_ = nullptr;
-
-    // after the last context is gone: K, and <Output>.Related next to the samples' own files
-    int finish_related()
-    {
-        sources_->set_count(S_);
-        for (int s = 0; s < S_; ++s)
-            if (status_[s] != VB2_OK)
-                std::fprintf(stderr, "NOTICE - --FindRelated: sample %d failed (status %d) and is left out of the relatedness matrix\n",
-                             s, (int)status_[s]);
-        const size_t nn = (size_t)S_ * (size_t)S_;
-        std::vector<double> kk;
-        std::vector<int32_t> sh;
-        const bool file = a_->output_prefixes && a_->base.output_prefix;
-        double* llr = llr_;
-        int32_t* shared = rel_shared_;
-        if (file && !llr) { kk.resize(nn * VB2_NUM_RELATION); llr = kk.data(); }
-        if (file && !shared) { sh.resize(nn); shared = sh.data(); }
-        if (!llr && !shared) return VB2_OK;
-        int rc = sources_->relations(llr, shared);
-        if (!rc && file) rc = vb2::write_related(a_->base.output_prefix, S_, related_top_, a_->output_prefixes, status_, llr, shared);
-        if (rc) err_all_ = vb2::g_last_error;
-        return rc;
-    }
-    std::deque<Done> done_queue_;          // (rel_mu_) searched samples: outputs to write, context and arrays to free
 
     int device_of_group(int gi) const { return gi % ndev_; }
     int device_of_sample(int s) const { return stream_ ? s % ndev_ : device_of_group(group_of_[s]); }
@@ -387,12 +281,17 @@ private:
                 sl.ctx = nullptr;
             }
         vb2::g_flatten_thread_cap.store(0);
-        if (!refit_ && !paired_) drop_streams();         // (--RefitSource, --MatchedNormal: the parked contexts still run on them)
     }
 
-    void drop_streams()
+    // the contexts the stages kept, THEN the run's own streams (every context and batch that used them is gone)
+    void release_parked_and_streams()
     {
-        for (hipStream_t& st : own_streams_)             // (every context and batch that used them is gone)
+        for (vb2_ctx*& c : parked_)
+            if (c) {
+                vb2_ctx_destroy(c);
+                c = nullptr;
+            }
+        for (hipStream_t& st : own_streams_)
             if (st) {
                 (void)hipStreamSynchronize(st);
                 (void)hipStreamDestroy(st);
@@ -400,238 +299,46 @@ private:
             }
     }
 
-    void release_parked()
+    // device d of the run as HIP numbers it, and its compute units
+    int device_index(int d) const
     {
-        for (vb2_ctx*& c : parked_)
-            if (c) {
-                vb2_ctx_destroy(c);
-                c = nullptr;
-            }
+        int dev = devices_[d];
+        if (dev < 0) (void)hipGetDevice(&dev);
+        return dev;
+    }
+    static int cu_count(int dev)
+    {
+        hipDeviceProp_t prop;
+        return hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
 
-    // The tail both refits share: the one-row sets on the parked contexts, ALL in one lock-step call of `optimize` between
-    // the phase's notices.  fit[who[n]].status becomes set n's (the call's own failure is everybody's), a failure gives
-    // "NOTICE - <failed> <who[n] + first>" with the last error, and the sets go before their contexts do.  The estimates, by set.
-    // keep: the sets stay (the caller has more to do on them, and clears them itself).
-    template <class Set, class Optimize, class Fit>
-    std::vector<vb2_estimate> refit_sets(const char* phase, const char* failed, int first, Optimize optimize,
-                                         std::vector<std::unique_ptr<Set>>& sets, const std::vector<double>& fixed,
-                                         const std::vector<int>& who, std::vector<Fit>& fit, bool keep = false)
+    // a device-level failure concerns every sample: the run stops with the first one's code and text (the last error of
+    // the thread it happened on, which is the caller's)
+    void device_failure(int rc)
     {
-        std::vector<vb2_estimate> est(sets.size());
-        if (sets.empty()) return est;
-        std::vector<Set*> raw;
-        for (auto& p : sets) raw.push_back(p.get());
-        std::vector<int32_t> st(sets.size(), VB2_ERR_INVALID);
-        const double t0 = now_s();
-        if (model_.notices) std::fprintf(stderr, "NOTICE - Starting phase: %s (%d searches in lock-step)\n", phase, (int)sets.size());
-        const int rc = optimize(raw.data(), (int)raw.size(), model_, fixed.data(), est.data(), st.data());
-        if (model_.notices) std::fprintf(stderr, "NOTICE - Finished phase: %s  [%.3f seconds]\n", phase, now_s() - t0);
-        for (size_t n = 0; n < who.size(); ++n) {
-            Fit& f = fit[(size_t)who[n]];
-            f.status = rc ? rc : st[n];
-            if (f.status != VB2_OK)
-                std::fprintf(stderr, "NOTICE - %s %d failed: %s\n", failed, who[n] + first, vb2::g_last_error.c_str());
+        std::lock_guard<std::mutex> lk(mu_);
+        if (!rc_all_) {
+            rc_all_ = rc;
+            err_all_ = vb2::g_last_error;
         }
-        if (!keep) sets.clear();
-        return est;
+        stop_ = true;
     }
 
-    // --RefitSource, after the matrix: one refit per sample -- its best candidate, where that candidate's score is finite
-    // and > 0 --, each a one-hypothesis set on the sample's parked context, ALL in one lock-step call; fit[] and
-    // <Output>.SourceFit.  A refit that fails leaves its row NA, gives a NOTICE and does not fail the run.
-    int refit_sources()
+    // Sample s's own files, each failure the sample's status: <prefix>.Ancestry and .selfSM of its search (flat: the
+    // flattened sample's counters; null: not now), and of its interval (ci; ci_rc: the interval's own outcome) <prefix>.CI
+    // and the caller's ci[s].
+    void write_sample_files(int s, const vb2_flat* flat, const vb2_estimate& est, const vb2_interval* ci = nullptr, int ci_rc = VB2_OK)
     {
-        const double nan = std::numeric_limits<double>::quiet_NaN();
-        std::vector<vb2_source_fit> fit((size_t)S_);
-        std::vector<std::unique_ptr<vb2::Conditioned>> sets;
-        std::vector<int> who;
-        std::vector<double> fixed;
-        if (parked_bytes_ > 0)
-            std::fprintf(stderr, "NOTICE - --RefitSource: the contexts of %d samples stayed on the device for the refit (%lld bytes)\n",
-                         (int)std::count_if(parked_.begin(), parked_.end(), [](vb2_ctx* c) { return c != nullptr; }),
-                         (long long)parked_bytes_);
-        for (int i = 0; i < S_; ++i) {
-            vb2_source_fit& f = fit[(size_t)i];
-            std::memset(&f, 0, sizeof(f));
-            f.candidate = -1;
-            f.status = VB2_SOURCE_FIT_NONE;
-            f.llr = f.freemix = f.freelk1 = f.alpha_given = f.lk1_given = f.lk0_given = f.delta_lk = nan;
-            if (status_[i] != VB2_OK || !fit_score_ || top_ < 1) continue;
-            const vb2_estimate& e = out_[i].est;
-            f.freemix = e.alpha < 0.5 ? e.alpha : 1 - e.alpha;
-            f.freelk1 = e.llk1;
-            // the first row of the sample in .Sources: the first of the largest scores (write_sources: a stable sort)
-            int best = -1;
-            for (int j = 0; j < S_; ++j) {
-                const double v = fit_score_[(size_t)i * S_ + j];
-                if (j == i || std::isnan(v)) continue;
-                if (best < 0 || v > fit_score_[(size_t)i * S_ + best]) best = j;
-            }
-            if (best < 0) continue;
-            f.candidate = best;
-            f.llr = fit_score_[(size_t)i * S_ + best];
-            f.markers = fit_shared_ ? fit_shared_[(size_t)i * S_ + best] : 0;
-            if (!(std::isfinite(f.llr) && f.llr > 0) || (size_t)i >= parked_.size() || !parked_[(size_t)i]) continue;
-            // the target's search point, as the source set took it: its pc1 is what the refit holds
-            vb2::Context* c = parked_[(size_t)i]->impl;
-            std::vector<double> p1, p2;
-            vb2::search_point(*c, model_, e, &p1, &p2, nullptr);
-            vb2::Conditioned* set = nullptr;
-            const int32_t cand = best;
-            if (const int rc = vb2::Conditioned::create_from_set(c, sources_.get(), 1, &cand, &set)) {
-                f.status = rc;
-                std::fprintf(stderr, "NOTICE - --RefitSource: sample %d is not refitted: %s\n", i, vb2::g_last_error.c_str());
-                continue;
-            }
-            sets.emplace_back(set);
-            who.push_back(i);
-            fixed.insert(fixed.end(), p1.begin(), p1.end());
+        const char* prefix = a_->output_prefixes ? a_->output_prefixes[s] : nullptr;
+        if (flat && prefix) {
+            int rw = vb2::write_ancestry(prefix, a_->base.num_pc, est.pc, est.pc2);
+            if (!rw) rw = vb2::write_selfsm(prefix, *flat, est, true);   // (cohort input is text pileups: #READS = NA)
+            if (rw) status_[s] = rw;
         }
-        const std::vector<vb2_estimate> est =
-            refit_sets("Refit given the source", "--RefitSource: the refit of sample", 0, vb2::conditioned_optimize, sets, fixed, who, fit);
-        for (size_t n = 0; n < who.size(); ++n) {
-            vb2_source_fit& f = fit[(size_t)who[n]];
-            if (f.status != VB2_OK) continue;
-            f.alpha_given = est[n].alpha;
-            f.lk1_given = est[n].llk1;
-            f.lk0_given = est[n].llk0;
-            f.delta_lk = (-f.lk1_given) - (-f.freelk1);
-        }
-        if (fit_) std::memcpy(fit_, fit.data(), sizeof(vb2_source_fit) * (size_t)S_);
-        if (a_->output_prefixes && a_->base.output_prefix) {
-            const int rc = vb2::write_source_fit(a_->base.output_prefix, S_, a_->output_prefixes, fit.data());
-            if (rc) {
-                err_all_ = vb2::g_last_error;
-                return rc;
-            }
-        }
-        return VB2_OK;
-    }
-
-    // --MatchedNormal (false without it: nothing else then differs from a plain run)
-    bool paired_ = false;
-    std::vector<int32_t> pair_t_, pair_n_;     // [pair] sample indices
-    std::vector<char> is_tumour_, is_normal_;  // [sample]
-    double hom_min_ = 0.99;
-    vb2_pair_fit* pair_fit_ = nullptr;
-    bool pair_interval_ = false;               // --PairInterval
-    vb2_interval* pair_ci_ = nullptr;
-
-    // --MatchedNormal, after the last sample: one refit per pair whose tumour and normal were both searched -- a
-    // one-hypothesis set on the tumour's parked context, built on the device from the normal's q row --, ALL in one lock-step
-    // call; fits[] and <Output>.PairFit.  A refit that fails leaves NA, gives a NOTICE and does not fail the run.
-    int refit_pairs()
-    {
-        const int P = (int)pair_t_.size();
-        const double nan = std::numeric_limits<double>::quiet_NaN();
-        std::vector<vb2_pair_fit> fit((size_t)P);
-        std::vector<std::unique_ptr<vb2::Paired>> sets;
-        std::vector<int> who;
-        std::vector<double> fixed;
-        if (parked_bytes_ > 0)
-            std::fprintf(stderr, "NOTICE - --MatchedNormal: the contexts of %d tumours stayed on the device for the refit (%lld bytes)\n",
-                         (int)std::count_if(parked_.begin(), parked_.end(), [](vb2_ctx* c) { return c != nullptr; }),
-                         (long long)parked_bytes_);
-        auto folded = [](double a) { return a < 0.5 ? a : 1 - a; };
-        for (int p = 0; p < P; ++p) {
-            const int t = pair_t_[(size_t)p], n = pair_n_[(size_t)p];
-            vb2_pair_fit& f = fit[(size_t)p];
-            std::memset(&f, 0, sizeof(f));
-            f.tumour = t;
-            f.normal = n;
-            f.status = VB2_PAIR_FIT_NONE;
-            f.normal_freemix = f.freemix = f.freelk1 = f.alpha_paired = f.lk1_paired = f.lk0_paired = nan;
-            if (status_[t] != VB2_OK || status_[n] != VB2_OK) {
-                std::fprintf(stderr, "NOTICE - --MatchedNormal: pair %d is not refitted: its %s failed (status %d)\n", p + 1,
-                             status_[t] != VB2_OK ? "tumour" : "normal", (int)(status_[t] != VB2_OK ? status_[t] : status_[n]));
-                continue;
-            }
-            const vb2_estimate& e = out_[n].est;
-            f.normal_freemix = folded(e.alpha);
-            f.freemix = folded(out_[t].est.alpha);
-            f.freelk1 = out_[t].est.llk1;
-            f.status = VB2_ERR_INVALID;
-            if ((size_t)t >= parked_.size() || !parked_[(size_t)t]) {
-                std::fprintf(stderr, "NOTICE - --MatchedNormal: pair %d is not refitted: the tumour's context is gone\n", p + 1);
-                continue;
-            }
-            // the normal's search point, as the source set took it: its pc2 -- the intended sample's -- is what the refit holds
-            vb2::Context* c = parked_[(size_t)t]->impl;
-            std::vector<double> p1, p2;
-            vb2::search_point(*c, model_, e, &p1, &p2, nullptr);
-            vb2::Paired* set = nullptr;
-            const int32_t nrm = n;
-            if (const int rc = vb2::Paired::create_from_set(c, sources_.get(), 1, &nrm, hom_min_, &set)) {
-                f.status = rc;
-                std::fprintf(stderr, "NOTICE - --MatchedNormal: pair %d is not refitted: %s\n", p + 1, vb2::g_last_error.c_str());
-                continue;
-            }
-            f.markers = (int32_t)set->given[0];
-            sets.emplace_back(set);
-            who.push_back(p);
-            fixed.insert(fixed.end(), p2.begin(), p2.end());
-        }
-        const std::vector<vb2_estimate> est = refit_sets("Refit given the matched normal", "--MatchedNormal: the refit of pair", 1,
-                                                         vb2::paired_optimize, sets, fixed, who, fit, pair_interval_);
-        for (size_t i = 0; i < who.size(); ++i) {
-            vb2_pair_fit& f = fit[(size_t)who[i]];
-            if (f.status != VB2_OK) continue;
-            f.alpha_paired = est[i].alpha;
-            f.lk1_paired = est[i].llk1;
-            f.lk0_paired = est[i].llk0;
-        }
-        // --PairInterval: the intervals of the refitted pairs, ALL in one lock-step gang on the parked contexts
-        std::vector<vb2_interval> ci((size_t)P);
-        std::vector<int32_t> ci_status((size_t)P, VB2_PAIR_FIT_NONE);
-        if (P > 0) std::memset(ci.data(), 0, sizeof(vb2_interval) * (size_t)P);
-        if (pair_interval_) {
-            std::vector<vb2::Paired*> raw;
-            std::vector<int> pair_of;
-            std::vector<double> fixed_l;
-            std::vector<vb2_estimate> est_l;
-            const int k = a_->base.num_pc;
-            for (size_t i = 0; i < who.size(); ++i) {
-                if (fit[(size_t)who[i]].status != VB2_OK) continue;
-                raw.push_back(sets[i].get());
-                pair_of.push_back(who[i]);
-                fixed_l.insert(fixed_l.end(), fixed.begin() + (long)i * k, fixed.begin() + (long)(i + 1) * k);
-                est_l.push_back(est[i]);
-            }
-            if (!raw.empty()) {
-                std::vector<vb2_interval> ci_l(raw.size());
-                std::vector<int32_t> st_l(raw.size(), VB2_ERR_INVALID);
-                int64_t steps = 0;
-                const double t0 = now_s();
-                if (model_.notices)
-                    std::fprintf(stderr, "NOTICE - Starting phase: Intervals given the matched normal (%d intervals in lock-step)\n",
-                                 (int)raw.size());
-                const int rc = vb2::paired_interval(raw.data(), (int)raw.size(), model_, fixed_l.data(), est_l.data(), ci_l.data(),
-                                                    st_l.data(), &steps);
-                if (model_.notices)
-                    std::fprintf(stderr, "NOTICE - Finished phase: Intervals given the matched normal (%lld launch pairs)  [%.3f seconds]\n",
-                                 (long long)steps, now_s() - t0);
-                for (size_t i = 0; i < raw.size(); ++i) {
-                    const int p = pair_of[i];
-                    ci_status[(size_t)p] = rc ? rc : st_l[i];
-                    if (ci_status[(size_t)p] == VB2_OK) ci[(size_t)p] = ci_l[i];
-                    else std::fprintf(stderr, "NOTICE - --PairInterval: the interval of pair %d failed: %s\n", p + 1, vb2::g_last_error.c_str());
-                }
-            }
-            sets.clear();                              // (before their contexts go)
-            if (pair_ci_) std::memcpy(pair_ci_, ci.data(), sizeof(vb2_interval) * (size_t)P);
-        }
-        if (pair_fit_) std::memcpy(pair_fit_, fit.data(), sizeof(vb2_pair_fit) * (size_t)P);
-        if (a_->output_prefixes && a_->base.output_prefix) {
-            int rc = vb2::write_pair_fit(a_->base.output_prefix, P, a_->pileup_paths, fit.data());
-            if (!rc && pair_interval_)
-                rc = vb2::write_pair_ci(a_->base.output_prefix, P, a_->pileup_paths, fit.data(), ci.data(), ci_status.data());
-            if (rc) {
-                err_all_ = vb2::g_last_error;
-                return rc;
-            }
-        }
-        return VB2_OK;
+        if (!ci) return;
+        if (!ci_rc && prefix) ci_rc = vb2::write_ci(prefix, *ci);
+        if (!ci_rc && ci_) ci_[s] = *ci;
+        if (ci_rc) status_[s] = ci_rc;
     }
 
     void prepare(int s)
@@ -736,7 +443,7 @@ private:
             std::lock_guard<std::mutex> lk(rel_mu_);
             Done d{s, slots_[s].ctx, std::move(slots_[s].flat), write, vb2_estimate{}};
             if (est) d.est = *est;
-            d.add = write && est;
+            d.row = write && est;
             slots_[s].ctx = nullptr;
             done_queue_.push_back(std::move(d));
         }
@@ -783,10 +490,7 @@ private:
             if (r->intervals_ && rc == VB2_OK) {             // its interval first: the stage finishes the sample
                 {
                     std::lock_guard<std::mutex> lk(r->iv_mu_);
-                    IvItem it;
-                    it.s = s;
-                    it.est = est;
-                    r->iv_queue_.push_back(it);
+                    r->iv_queue_.push_back(IvItem{s, est});
                 }
                 r->iv_cv_.notify_one();
                 return;
@@ -815,10 +519,7 @@ private:
     // without intervals -- its other files are the search's
     void complete_interval(int s, int rc, const vb2_estimate& est, const vb2_interval& ci)
     {
-        const char* prefix = a_->output_prefixes ? a_->output_prefixes[s] : nullptr;
-        if (!rc && prefix) rc = vb2::write_ci(prefix, ci);
-        if (!rc && ci_) ci_[s] = ci;
-        if (rc) status_[s] = rc;
+        write_sample_files(s, nullptr, est, &ci, rc);
         finish_sample(s, true, &est, /*delivered=*/true);
     }
 
@@ -828,32 +529,17 @@ private:
     // samples goes on meanwhile on its own thread and streams.
     void interval_loop(int d)
     {
-        int dev = devices_[d];
-        if (dev < 0) (void)hipGetDevice(&dev);
+        const int dev = device_index(d);
         int fail = hipSetDevice(dev) == hipSuccess ? VB2_OK : VB2_ERR_HIP;
         if (fail) set_error("--CohortInterval: hipSetDevice failed");
-        int num_cu = 256;
-        {
-            hipDeviceProp_t prop;
-            if (!fail && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) num_cu = prop.multiProcessorCount;
-        }
         const int k = a_->base.num_pc;
         std::unique_ptr<vb2::Batch> batch;
         if (!fail) {
             vb2::Batch* bp = nullptr;
-            fail = vb2::Batch::create_slots(G_, dev, k, num_cu, &bp);
+            fail = vb2::Batch::create_slots(G_, dev, k, cu_count(dev), &bp);
             batch.reset(bp);
         }
-        auto device_failure = [&](int rc) {          // concerns every sample: the run stops, what is queued leaves with rc
-            fail = rc;
-            std::lock_guard<std::mutex> lk(mu_);
-            if (!rc_all_) {
-                rc_all_ = rc;
-                err_all_ = vb2::g_last_error;
-            }
-            stop_ = true;
-        };
-        if (fail) device_failure(fail);
+        if (fail) device_failure(fail);              // (the run stops, what is queued leaves with the failure's code)
         vb2::IntervalGang gang(G_, k);
         std::vector<IvItem> cur(G_);
         std::vector<vb2_interval> civ(G_);
@@ -904,7 +590,7 @@ private:
                 continue;
             }
             if (const int rc = gang.step(fn))
-                if (!fail) device_failure(rc);
+                if (!fail) device_failure(fail = rc);
             for (int i = 0; i < G_; ++i)
                 if (live[i] && gang.idle(i)) retire(i);
         }
@@ -917,14 +603,8 @@ private:
         const double t0 = now_s();
         DeviceSource src(this, d);
         int rc = VB2_OK;
-        int num_cu = 256;
-        {
-            hipDeviceProp_t prop;
-            const int dev = devices_[d];
-            int cur = dev;
-            if (dev < 0) (void)hipGetDevice(&cur);
-            if (hipGetDeviceProperties(&prop, cur) == hipSuccess && prop.multiProcessorCount > 0) num_cu = prop.multiProcessorCount;
-        }
+        const int dev = device_index(d);
+        const int num_cu = cu_count(dev);
         std::thread iv;
         if (intervals_) iv = std::thread([this, d] { interval_loop(d); });
         struct IvJoin {                              // the stage ends when the search has handed over its last sample
@@ -943,8 +623,6 @@ private:
         };
         try {
             IvJoin join{this, &iv};
-            int dev = devices_[d];
-            if (dev < 0) (void)hipGetDevice(&dev);
             rc = vb2::stream_search(dev, a_->base.num_pc, num_cu, G_, src, own_streams_.empty() ? nullptr : &own_streams_[(size_t)d * 4]);
         } catch (const std::exception& e) {
             set_error(e.what());
@@ -952,73 +630,46 @@ private:
         }
         if (timing)
             std::fprintf(stderr, "vb2_cohort_run: device %d: %d slots, stream over after %.1f ms\n", devices_[d], G_, 1e3 * (now_s() - t0));
-        if (rc) {                                // device-level failure: concerns every sample
-            std::lock_guard<std::mutex> lk(mu_);
-            if (!rc_all_) {
-                rc_all_ = rc;
-                err_all_ = vb2::g_last_error;
-            }
-            stop_ = true;
-        }
+        if (rc) device_failure(rc);
         cv_.notify_all();
     }
 
+    // The releaser: a sample's files (streamed runs: here; grouped runs wrote them on the device thread), THEN its row in the
+    // set and whether its context stays -- the stages' answers, in their order --, then the context and the host arrays go.
     void release_loop()
     {
         for (;;) {
-            std::pair<vb2_ctx*, std::unique_ptr<vb2_flat>> item;
-            {
-                std::unique_lock<std::mutex> lk(rel_mu_);
-                rel_cv_.wait(lk, [&] { return rel_stop_ || !rel_queue_.empty() || !done_queue_.empty(); });
-                if (!done_queue_.empty()) {
-                    Done d = std::move(done_queue_.front());
-                    done_queue_.pop_front();
-                    lk.unlock();
-                    // a searched sample: its output files first (they need the flattened sample's counters)
-                    const char* prefix = a_->output_prefixes ? a_->output_prefixes[d.s] : nullptr;
-                    if (d.write && prefix && d.flat) {
-                        int rw = vb2::write_ancestry(prefix, a_->base.num_pc, d.est.pc, d.est.pc2);
-                        if (!rw) rw = vb2::write_selfsm(prefix, *d.flat, d.est, true);   // (cohort input is text pileups: #READS = NA)
-                        if (rw) status_[d.s] = rw;
+            std::unique_lock<std::mutex> lk(rel_mu_);
+            rel_cv_.wait(lk, [&] { return rel_stop_ || !done_queue_.empty(); });
+            if (done_queue_.empty()) return;
+            Done d = std::move(done_queue_.front());
+            done_queue_.pop_front();
+            lk.unlock();
+            if (d.write && d.flat) write_sample_files(d.s, d.flat.get(), d.est);    // (they need the flattened sample's counters)
+            if (d.row && d.ctx && d.ctx->impl && status_[d.s] == VB2_OK) {
+                // (a sample whose row cannot be made keeps its files and its status -- it was searched and written as the
+                // plain run does it --; its row and column of a matrix are NaN and a NOTICE says why)
+                bool made = false, keep = false;
+                for (const vb2::CohortStage* st : after_)
+                    if (set_ && st->planes && st->wants_row(d.s)) {
+                        made = set_->put(d.s, d.ctx->impl, model_, d.est) == VB2_OK;
+                        if (!made)
+                            std::fprintf(stderr, "NOTICE - %s: sample %d has no row in the source set: %s\n", st->flag, d.s,
+                                         vb2::g_last_error.c_str());
+                        break;                           // (put once, whatever the number of stages that read the row)
                     }
-                    if (paired_) {
-                        // a searched normal gets its row; a searched tumour stays for the refit; the rest go as ever
-                        if (d.add && d.ctx && d.ctx->impl && status_[d.s] == VB2_OK) {
-                            if (is_normal_[(size_t)d.s] && sources_->put(d.s, d.ctx->impl, model_, d.est))
-                                std::fprintf(stderr, "NOTICE - --MatchedNormal: sample %d has no row in the source set: %s\n", d.s,
-                                             vb2::g_last_error.c_str());
-                            if (is_tumour_[(size_t)d.s]) {
-                                if (parked_.empty()) parked_.assign((size_t)S_, nullptr);
-                                parked_[(size_t)d.s] = d.ctx;
-                                parked_bytes_ += d.ctx->impl->device_bytes;
-                                d.ctx = nullptr;
-                            }
-                        }
-                    } else if (sources_ && d.add && d.ctx && d.ctx->impl && status_[d.s] == VB2_OK) {
-                        // (a sample whose row cannot be made keeps its files and its status -- it was searched and written as
-                        // the plain run does it --; its row and column of the matrix are NaN and a NOTICE says why)
-                        if (sources_->put(d.s, d.ctx->impl, model_, d.est))
-                            std::fprintf(stderr, "NOTICE - %s: sample %d has no row in the source set: %s\n",
-                                         find_source_ ? "--FindSource" : "--FindRelated", d.s, vb2::g_last_error.c_str());
-                        else if (refit_) {               // searched, written, in the set: parked for the refit, not destroyed
-                            if (parked_.empty()) parked_.assign((size_t)S_, nullptr);
-                            parked_[(size_t)d.s] = d.ctx;
-                            parked_bytes_ += d.ctx->impl->device_bytes;
-                            d.ctx = nullptr;
-                        }
-                    }
-                    item.first = d.ctx;
-                    item.second = std::move(d.flat);
-                } else {
-                    if (rel_queue_.empty()) return;
-                    item = std::move(rel_queue_.front());
-                    rel_queue_.pop_front();
+                for (const vb2::CohortStage* st : after_) keep = keep || st->keeps(d.s, made);
+                if (keep) {                              // searched and written: parked for finish(), not destroyed
+                    if (parked_.empty()) parked_.assign((size_t)S_, nullptr);
+                    parked_[(size_t)d.s] = d.ctx;
+                    parked_bytes_ += d.ctx->impl->device_bytes;
+                    d.ctx = nullptr;
                 }
             }
             const double t0 = now_s();
-            if (item.first) vb2_ctx_destroy(item.first);
+            if (d.ctx) vb2_ctx_destroy(d.ctx);
             const double t1 = now_s();
-            item.second.reset();
+            d.flat.reset();
             rel_s_[0] += t1 - t0;
             rel_s_[1] += now_s() - t1;
         }
@@ -1080,18 +731,7 @@ private:
                         const int s = who[i];
                         out_[s].est = est[i];
                         out_[s].seconds_optimize = dt;
-                        const char* prefix = a_->output_prefixes ? a_->output_prefixes[s] : nullptr;
-                        if (prefix) {
-                            int rw = vb2::write_ancestry(prefix, a_->base.num_pc, est[i].pc, est[i].pc2);
-                            if (!rw) rw = vb2::write_selfsm(prefix, *slots_[s].flat, est[i], true);   // (cohort input is text pileups: #READS = NA)
-                            if (rw) status_[s] = rw;
-                        }
-                        if (intervals_) {
-                            int ri = ist[i];
-                            if (!ri && prefix) ri = vb2::write_ci(prefix, civ[i]);
-                            if (!ri && ci_) ci_[s] = civ[i];
-                            if (ri) status_[s] = ri;
-                        }
+                        write_sample_files(s, slots_[s].flat.get(), est[i], intervals_ ? &civ[i] : nullptr, intervals_ ? ist[i] : VB2_OK);
                     }
                 }
             }
@@ -1099,14 +739,10 @@ private:
             {   // freeing device and pinned memory synchronises with the device and takes milliseconds
                 // per context: hand the group to the releaser thread and move on
                 std::lock_guard<std::mutex> lk(rel_mu_);
-                for (int s = g0; s < g1; ++s) {
-                    if (sources_) {              // (the releaser adds the sample to the source set first; its files are written)
-                        Done d{s, slots_[s].ctx, std::move(slots_[s].flat), false, out_[s].est};
-                        d.add = !rcb && status_[s] == VB2_OK && slots_[s].ctx != nullptr;
-                        done_queue_.push_back(std::move(d));
-                    } else {
-                        rel_queue_.emplace_back(slots_[s].ctx, std::move(slots_[s].flat));
-                    }
+                for (int s = g0; s < g1; ++s) {      // (nothing to write: the files are written)
+                    Done d{s, slots_[s].ctx, std::move(slots_[s].flat), false, out_[s].est};
+                    d.row = !rcb && status_[s] == VB2_OK && slots_[s].ctx != nullptr;
+                    done_queue_.push_back(std::move(d));
                     slots_[s].ctx = nullptr;
                 }
             }
@@ -1115,16 +751,10 @@ private:
                 std::fprintf(stderr, "vb2_cohort_run: device %d group %d (samples %d-%d): waited %.1f ms for the "
                                      "readers, search + outputs %.1f ms\n", devices_[d], gi, g0, g1 - 1,
                              1e3 * (tg_wait - tg0), 1e3 * (tg_opt - tg_wait));
+            if (rcb) device_failure(rcb);
             {
                 std::lock_guard<std::mutex> lk(mu_);
                 ++cnt_[d];
-                if (rcb) {                       // device-level failure: concerns every sample
-                    if (!rc_all_) {
-                        rc_all_ = rcb;
-                        err_all_ = vb2::g_last_error;
-                    }
-                    stop_ = true;
-                }
             }
             cv_.notify_all();
             if (rcb) return;
@@ -1133,163 +763,17 @@ private:
 
 public:
     const std::string& error() const { return err_all_; }
-    int num_reader() const { return T_; }
 };
 
 }  // namespace
 
-extern "C" int vb2_cohort_run(const vb2_cohort_args* a, vb2_run_result* out, int32_t* status)
+int vb2::cohort_run_with(const vb2_cohort_args* a, vb2_run_result* out, int32_t* status, const CohortStages& stages)
 {
-    if (!a || !out || !status || a->num_sample < 1 || !a->pileup_paths || !a->base.ud_path ||
-        !a->base.mean_path || !a->base.bed_path || a->base.num_pc < 1 || a->base.num_pc > VB2_MAX_PC ||
-        a->base.num_device < 0 || a->base.num_device > 64) {
-        set_error("vb2_cohort_run: invalid argument");
-        return VB2_ERR_INVALID;
-    }
-    // (Tunables::cohort_dup_devices: a test switch -- the pipelines of a several-device run, their group
-    // schedule and the readers' per-device look-ahead exercised on a machine with one GPU)
-    const bool dup_ok = vb2::tunables().cohort_dup_devices != 0;
-    for (int i = 0; i < a->base.num_device && !dup_ok; ++i)
-        for (int j = 0; j < i; ++j)
-            if (a->base.devices && a->base.devices[i] == a->base.devices[j]) {
-                // (two lock-step pipelines on one device would each launch device-filling grids)
-                set_error("vb2_cohort_run: a device is listed twice");
-                return VB2_ERR_INVALID;
-            }
     return vb2::guarded([&] {
-        CohortRunner runner(a, out, status);
+        CohortRunner runner(a, out, status, stages);
         const int rc = runner.run();
         if (rc && !runner.error().empty()) set_error(runner.error());
         return rc;
     });
 }
 
-extern "C" int vb2_cohort_run_sources(const vb2_cohort_args* a, int32_t top, vb2_run_result* out, int32_t* status, double* score,
-                                      int32_t* shared)
-{
-    if (!a || !out || !status || a->num_sample < 1 || !a->pileup_paths || !a->base.ud_path || !a->base.mean_path ||
-        !a->base.bed_path || a->base.num_pc < 1 || a->base.num_pc > VB2_MAX_PC || top < 0) {
-        set_error("vb2_cohort_run_sources: invalid argument");
-        return VB2_ERR_INVALID;
-    }
-    if (a->base.num_device > 1 || a->base.num_device < 0) {
-        set_error("--FindSource takes one device: a source set is not spread over several --Devices");
-        return VB2_ERR_INVALID;
-    }
-    return vb2::guarded([&] {
-        CohortRunner runner(a, out, status, true, top, score, shared);
-        const int rc = runner.run();
-        if (rc && !runner.error().empty()) set_error(runner.error());
-        return rc;
-    });
-}
-
-extern "C" int vb2_cohort_run_related(const vb2_cohort_args* a, int32_t related_top, int32_t source_top, vb2_run_result* out,
-                                      int32_t* status, double* llr, int32_t* shared)
-{
-    if (!a || !out || !status || a->num_sample < 1 || !a->pileup_paths || !a->base.ud_path || !a->base.mean_path ||
-        !a->base.bed_path || a->base.num_pc < 1 || a->base.num_pc > VB2_MAX_PC || related_top < 0 || source_top < 0) {
-        set_error("vb2_cohort_run_related: invalid argument");
-        return VB2_ERR_INVALID;
-    }
-    if (a->base.num_device > 1 || a->base.num_device < 0) {
-        set_error("--FindRelated takes one device: a set of samples is not spread over several --Devices");
-        return VB2_ERR_INVALID;
-    }
-    return vb2::guarded([&] {
-        CohortRunner runner(a, out, status, source_top > 0, source_top);
-        runner.enable_related(related_top, llr, shared);
-        const int rc = runner.run();
-        if (rc && !runner.error().empty()) set_error(runner.error());
-        return rc;
-    });
-}
-
-extern "C" int vb2_cohort_run_source_fits(const vb2_cohort_args* a, int32_t top, vb2_run_result* out, int32_t* status, double* score,
-                                          int32_t* shared, vb2_source_fit* fit)
-{
-    if (!a || !out || !status || a->num_sample < 1 || !a->pileup_paths || !a->base.ud_path || !a->base.mean_path ||
-        !a->base.bed_path || a->base.num_pc < 1 || a->base.num_pc > VB2_MAX_PC || top < 0) {
-        set_error("vb2_cohort_run_source_fits: invalid argument");
-        return VB2_ERR_INVALID;
-    }
-    if (a->base.num_device > 1 || a->base.num_device < 0) {
-        set_error("--RefitSource takes one device: a source set and the refits given it are not spread over several --Devices");
-        return VB2_ERR_INVALID;
-    }
-    if (a->base.model.is_alpha_fixed) {
-        set_error("--RefitSource cannot be combined with --FixAlpha: a fixed alpha leaves the refit nothing to estimate");
-        return VB2_ERR_INVALID;
-    }
-    return vb2::guarded([&] {
-        CohortRunner runner(a, out, status, true, top, score, shared, false, nullptr, true, fit);
-        const int rc = runner.run();
-        if (rc && !runner.error().empty()) set_error(runner.error());
-        return rc;
-    });
-}
-
-extern "C" int vb2_cohort_run_intervals(const vb2_cohort_args* a, int32_t source_top, vb2_run_result* out, int32_t* status,
-                                        vb2_interval* ci)
-{
-    if (!a || !out || !status || a->num_sample < 1 || !a->pileup_paths || !a->base.ud_path || !a->base.mean_path ||
-        !a->base.bed_path || a->base.num_pc < 1 || a->base.num_pc > VB2_MAX_PC || source_top < 0) {
-        set_error("vb2_cohort_run_intervals: invalid argument");
-        return VB2_ERR_INVALID;
-    }
-    if (a->base.num_device > 1 || a->base.num_device < 0) {
-        set_error("--CohortInterval takes one device: the intervals of a cohort are not spread over several --Devices");
-        return VB2_ERR_INVALID;
-    }
-    return vb2::guarded([&] {
-        CohortRunner runner(a, out, status, source_top > 0, source_top, nullptr, nullptr, true, ci);
-        const int rc = runner.run();
-        if (rc && !runner.error().empty()) set_error(runner.error());
-        return rc;
-    });
-}
-
-namespace {
-int cohort_run_paired(const vb2_cohort_args* a, int32_t num_pair, const int32_t* tumour, const int32_t* normal, double hom_min,
-                      vb2_run_result* out, int32_t* status, vb2_pair_fit* fits, bool interval, vb2_interval* ci)
-{
-    if (!a || !out || !status || a->num_sample < 1 || !a->pileup_paths || !a->base.ud_path || !a->base.mean_path ||
-        !a->base.bed_path || a->base.num_pc < 1 || a->base.num_pc > VB2_MAX_PC || num_pair < 1 || !tumour || !normal) {
-        set_error("vb2_cohort_run_paired: invalid argument");
-        return VB2_ERR_INVALID;
-    }
-    if (a->base.num_device > 1 || a->base.num_device < 0) {
-        set_error("--MatchedNormal takes one device: the normals' rows and the refits given them are not spread over several --Devices");
-        return VB2_ERR_INVALID;
-    }
-    if (a->base.model.is_alpha_fixed) {
-        set_error("--MatchedNormal cannot be combined with --FixAlpha: a fixed alpha leaves the refit nothing to estimate");
-        return VB2_ERR_INVALID;
-    }
-    if (!(hom_min >= 0.0 && hom_min <= 1.0)) {
-        set_error("--NormalHomMin takes a probability within [0, 1]");
-        return VB2_ERR_INVALID;
-    }
-    if (const int rc = vb2::check_pairs("vb2_cohort_run_paired", a->num_sample, num_pair, tumour, normal)) return rc;
-    return vb2::guarded([&] {
-        CohortRunner runner(a, out, status);
-        runner.enable_paired(num_pair, tumour, normal, hom_min, fits, interval, ci);
-        const int rc = runner.run();
-        if (rc && !runner.error().empty()) set_error(runner.error());
-        return rc;
-    });
-}
-}  // namespace
-
-extern "C" int vb2_cohort_run_paired(const vb2_cohort_args* a, int32_t num_pair, const int32_t* tumour, const int32_t* normal,
-                                     double hom_min, vb2_run_result* out, int32_t* status, vb2_pair_fit* fits)
-{
-    return cohort_run_paired(a, num_pair, tumour, normal, hom_min, out, status, fits, false, nullptr);
-}
-
-extern "C" int vb2_cohort_run_paired_intervals(const vb2_cohort_args* a, int32_t num_pair, const int32_t* tumour,
-                                               const int32_t* normal, double hom_min, vb2_run_result* out, int32_t* status,
-                                               vb2_pair_fit* fits, vb2_interval* ci)
-{
-    return cohort_run_paired(a, num_pair, tumour, normal, hom_min, out, status, fits, true, ci);
-}

@@ -1,10 +1,11 @@
-"""The epilogue of a work item in the 8-point probability-domain shape on the LDS queue (eval_body, EPI / VB2_EPI_TRIPS): the
-queue's draw may ride the last row's table reads, the projection coefficients may be requested behind that row's multiplies,
-and the tile butterfly's exchange over marker bit 3 may go through DPP moves and v_permlane16_swap instead of ds_bpermute.
-None of it may move a bit: a tile's product keeps its own slot and its pairing order, so the split launch, the pass-per-group
+"""The epilogue of a work item in the 8-point probability-domain shape on the LDS queue (eval_body, EPI_X8): on the split
+launch the tile butterfly's exchange over marker bit 3 goes through DPP moves and v_permlane16_swap instead of ds_bpermute.
+(Two more parts were built with it and retired: the queue's draw riding the last row's table reads, and the projection
+coefficients requested behind that row's multiplies; the shapes below still cover what they could get wrong.)
+It may not move a bit: a tile's product keeps its own slot and its pairing order, so the split launch, the pass-per-group
 launch, the plain 8-point launches and the narrower wave shapes -- whose exchange goes through __shfl and so pins the pairing
-order of the new one -- must agree exactly, whichever parts the library was built with.  Shapes chosen for what the three parts
-can get wrong, not for size."""
+order of the new one -- must agree exactly.  Shapes chosen for what the epilogue and the item loop around it can get wrong,
+not for size."""
 import os
 
 import numpy as np

@@ -1,7 +1,7 @@
 """The branches of the probability-domain row walk (eval_body: walk_pd and the loops around it), which go wrong by KIND of row and
 not by size: a tile without rows, a first row that is ref-ref, ref-alt or alt-alt, an odd or even count of ref rows, the mixed
 row, odd and even alt tails.  Small, shallow samples reach them all -- at a mean depth of 0.5 most markers have no read and
-many have alt reads only.  The order in which a row's table reads and multiplies are issued (VB2_READS_AHEAD) may not move a
+many have alt reads only.  The order in which a row's table reads and multiplies are issued (READS_AHEAD) may not move a
 bit: each launch is compared with the pass-per-group kernel, with the plain 8-point launches, with the oracle, and with
 the bytes the commit before that change computed (tests/golden/read_loop, tools/make_read_loop_golden.py)."""
 import json

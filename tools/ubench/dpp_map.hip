@@ -11,7 +11,7 @@ __global__ void ksw32(int* out) {
     auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
     out[threadIdx.x] = r[0]; out[64 + threadIdx.x] = r[1];
 }
-// the tile butterfly's exchange over marker bit 3 as eval_body.h does it (lane_pair8_u32, VB2_EPI_TRIPS part 4): the odd rows swap
+// the tile butterfly's exchange over marker bit 3 as eval_body.h does it (lane_pair8_u32; eval_body's EPI_X8): the odd rows swap
 // their quads j <-> j ^ 1 under a row mask, then v_permlane16_swap puts the two rows side by side
 __global__ void kpair8(int* out) {
     const int x = threadIdx.x;

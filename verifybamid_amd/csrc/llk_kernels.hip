@@ -18,6 +18,20 @@
 
 namespace vb2 {
 
+// What each kernel of this unit takes of the evaluation body (eval_body.h, EvalConfig).  The plain launches: a row's table
+// reads before its multiplies, in every probability-domain shape
+template <int MODE_, int QUEUE_, int KSEL_, bool PD_>
+struct PlainEval : EvalConfig {
+    static constexpr int MODE = MODE_, QUEUE = QUEUE_, KSEL = KSEL_;
+    static constexpr bool PD = PD_, READS_AHEAD = true;
+};
+// ... the split launch: the 8-point probability-domain shape on the queue with everything that shape has
+template <int KSEL_, int S>
+struct SplitEval : EvalConfig {
+    static constexpr int MODE = 2, QUEUE = 1, KSEL = KSEL_, SPLIT = S;
+    static constexpr bool PD = true, READS_AHEAD = true, ITEM_AHEAD = true, EPI_X8 = true;
+};
+
 template <int MODE, int QUEUE, int KSEL = 0, bool PD = false>
 __global__ void __launch_bounds__(Geom<MODE>::kMaxWaves * 64, Geom<MODE>::kWavesPerSimd)
 llk_eval_kernel(const DeviceLayout L, const InlinePoints ip, const double* __restrict__ points,
@@ -25,8 +39,8 @@ llk_eval_kernel(const DeviceLayout L, const InlinePoints ip, const double* __res
                 unsigned int* __restrict__ ticket, unsigned long long* __restrict__ done_flag,
                 unsigned long long done_seq, int ngrp, unsigned long long tag, const Schedule sch)
 {
-    eval_body<MODE, false, NoHook, false, QUEUE, KSEL, false, 8, PD, 0, reads_ahead(MODE == 2 ? 1 : 2), (MODE == 2 && QUEUE == 1 && PD) ? item_ahead(1) : 0, (MODE == 2 && QUEUE == 1 && PD) ? epi_trips(1) : 0>(L, ip.v, ip.count, points, num_valid, partials, llk_out, ticket,
-                                                                     done_flag, done_seq, blockIdx.x, gridDim.x, nullptr, 0u, ngrp, tag, sch);
+    eval_body<PlainEval<MODE, QUEUE, KSEL, PD>>(L, ip.v, ip.count, points, num_valid, partials, llk_out, ticket,
+                                                done_flag, done_seq, blockIdx.x, gridDim.x, nullptr, 0u, ngrp, tag, sch);
 }
 
 // see eval_body, SPLIT
@@ -36,9 +50,9 @@ llk_eval_split_kernel(const DeviceLayout L, const double* __restrict__ points, i
                       double* __restrict__ llk_out, unsigned int* __restrict__ ticket, unsigned long long* __restrict__ done_flag,
                       unsigned long long done_seq, int ngrp)
 {
-    eval_body<2, false, NoHook, false, 1, KSEL, false, 8, true, S, reads_ahead(0), item_ahead(0), epi_trips(0)>(L, nullptr, 0, points, num_valid, partials, llk_out, ticket, done_flag,
-                                                                     done_seq, blockIdx.x, gridDim.x, nullptr, 0u, ngrp, 0ull,
-                                                                     Schedule{nullptr, nullptr});
+    eval_body<SplitEval<KSEL, S>>(L, nullptr, 0, points, num_valid, partials, llk_out, ticket, done_flag,
+                                  done_seq, blockIdx.x, gridDim.x, nullptr, 0u, ngrp, 0ull,
+                                  Schedule{nullptr, nullptr});
 }
 
 #include "resident_kernel.inc"
@@ -74,7 +88,7 @@ llk_finalize_kernel(const double* __restrict__ partials, int nb, int num_point,
     if (done_flag) {                    // (stores through the caches, acknowledged, then the flag: see eval_body)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (threadIdx.x == 0) __hip_atomic_store(done_flag, done_seq, VB2_FLAG_RELEASE ? __ATOMIC_RELEASE : __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (threadIdx.x == 0) __hip_atomic_store(done_flag, done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 
@@ -491,7 +505,7 @@ publish_kernel(const double* __restrict__ src, double* __restrict__ dst_mapped, 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0)
-        __hip_atomic_store(done_flag, done_seq, VB2_FLAG_RELEASE ? __ATOMIC_RELEASE : __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(done_flag, done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 hipError_t launch_publish(const double* d_src, double* d_dst_mapped, int n, unsigned long long* done_flag,

@@ -21,6 +21,13 @@ namespace vb2 {
 // bits.  The results of the earlier passes are stored through the caches like the last one's (eval_body does that when it
 // is given a flag to raise: theirs is a scratch word on the device), and acknowledged before the storing workgroup draws
 // its next ticket, so the flag the host waits for is behind every pass's results.
+// (the 8-point shape on the queue; run words: beside the compact exp table -- launch_passes)
+template <int KSEL_, bool PD_>
+struct PassesEval : EvalConfig {
+    static constexpr int MODE = 2, QUEUE = 1, KSEL = KSEL_, ESH = PD_ ? 8 : 6;
+    static constexpr bool PD = PD_;
+};
+
 template <int KSEL, bool PD = false>
 __global__ void __launch_bounds__(Geom<2>::kMaxWaves * 64, Geom<2>::kWavesPerSimd)
 llk_eval_passes_kernel(const DeviceLayout L, const double* __restrict__ points, int num_valid, int points_per_pass,
@@ -35,7 +42,7 @@ llk_eval_passes_kernel(const DeviceLayout L, const double* __restrict__ points, 
         const int nv = left < points_per_pass ? left : points_per_pass;
         const bool last = left <= points_per_pass;
         if (pass > 0) __syncthreads();                      // the pass before is done with the workgroup's LDS
-        eval_body<2, false, NoHook, false, 1, KSEL, false, (PD ? 8 : 6), PD>(
+        eval_body<PassesEval<KSEL, PD>>(
             L, nullptr, 0, points + (size_t)first * stride, nv, partials + (size_t)first * gridDim.x, llk_out + first,
             tickets + pass, (last || !done_flag) ? done_flag : scratch_flag, done_seq, blockIdx.x, gridDim.x, nullptr, 0u,
             (nv + 7) / 8, 0ull, Schedule{nullptr, nullptr});
@@ -92,8 +99,13 @@ hipError_t launch_passes(const DeviceLayout& L, const double* d_points, int num_
 // w / bps as that sample's workgroup w % bps.  Every sample has its own layout, parameter rows,
 // partials, ticket and output slot; samples with num_valid == 0 sit this step out.
 // STATIC: every sample of the launch is known (on the host) to run the static deal: the item loop is compiled for it
-// alone, and pipelined across items (eval_body: PIPE).
-template <int MODE, bool W16, int KSEL = 0, int STATIC = 0, bool PD = false>     // KSEL 2 / 4: every sample has that --NumPC and no known-AF column
+// alone, and pipelined across items (eval_body: PIPE); else each sample's way of dealing is decided in the kernel.
+template <int MODE_, bool W16_, int KSEL_, int STATIC, bool PD_>
+struct MultiEval : EvalConfig {
+    static constexpr int MODE = MODE_, QUEUE = STATIC ? 0 : -1, KSEL = KSEL_;
+    static constexpr bool W16 = W16_, STREAM = true, PD = PD_;
+};
+template <int MODE, bool W16, int KSEL = 0, int STATIC = 0, bool PD = false>    // KSEL 2 / 4: every sample has that --NumPC and no known-AF column
 __global__ void __launch_bounds__(Geom<MODE>::kMaxWaves * 64, Geom<MODE>::kWavesPerSimd)
 llk_eval_multi_kernel(const DeviceLayout* __restrict__ layouts, const Schedule* __restrict__ scheds,
                       const double* __restrict__ points,
@@ -112,7 +124,7 @@ llk_eval_multi_kernel(const DeviceLayout* __restrict__ layouts, const Schedule* 
     if (nv <= 0) return;                                   // uniform for the workgroup
     const DeviceLayout L = layouts[s];
     const int stride = 2 * L.num_pc + 1;
-    eval_body<MODE, W16, NoHook, true, (STATIC ? 0 : -1), KSEL, false, 8, PD>(L, mi.v + (size_t)s * NP * stride, mi.count, points + (size_t)s * NP * stride, nv,
+    eval_body<MultiEval<MODE, W16, KSEL, STATIC, PD>>(L, mi.v + (size_t)s * NP * stride, mi.count, points + (size_t)s * NP * stride, nv,
                           partials + (size_t)s * (NP + 1) * bps, llk_out + (size_t)s * NP, tickets + s,
                           done_flag, done_seq, (uint32_t)(blockIdx.x % bps), (uint32_t)bps,
                           batch_done, batch_active, 1, use_ticket ? 0ull : done_seq,

@@ -1041,11 +1041,12 @@ resident_control(const unsigned long long* h_cmd, unsigned long long* relay, dou
 // that went the short way, then prepare the rows sets of the next one.
 // The control wave's share of a search round's tile phase (see the head of this file): replay, then prepare.
 // prof (VB2_STAMPS): [48] total, [56] state load, [64] apply_outcome, [80] speculate, [88] save + drain
+constexpr int kCtrlPrio = 3;      // the control wave's priority during its tile-phase work
 __device__ __attribute__((noinline)) void
 control_tile_phase(double* st_in, unsigned long long* spec_in, unsigned long long round_in, int nmax_in, int k_in,
                    int lane, unsigned long long* prof_in)
 {
-    __builtin_amdgcn_s_setprio(VB2_CTRL_PRIO);   // one wave with the round's bookkeeping among fifteen busy ones
+    __builtin_amdgcn_s_setprio(kCtrlPrio);       // one wave with the round's bookkeeping among fifteen busy ones
     double* const st = reinterpret_cast<double*>(uniform_u64((unsigned long long)st_in));
     unsigned long long* const spec = reinterpret_cast<unsigned long long*>(uniform_u64((unsigned long long)spec_in));
     unsigned long long* const prof = reinterpret_cast<unsigned long long*>(uniform_u64((unsigned long long)prof_in));
@@ -1137,6 +1138,13 @@ __host__ __device__ inline uint32_t cache_start(bool pd, uint32_t off, uint32_t 
     if (pd) return ((it & 1u) && ((off - prev_start) & 3u) == 0u) ? off + 1u : off;
     return ((it & 1u) && ((off ^ prev_start) & 1u) == 0u) ? off + 1u : off;
 }
+
+// the evaluation body of a search round: the four-point shape, the table reads in the scheduler's order (eval_body, READS_AHEAD)
+template <int QUEUE_, int KSEL_, bool LCACHE_, bool PD_>
+struct ResidentEval : EvalConfig {
+    static constexpr int MODE = 3, QUEUE = QUEUE_, KSEL = KSEL_;
+    static constexpr bool LCACHE = LCACHE_, PD = PD_;
+};
 
 template <int QUEUE, int KSEL = 0, bool LCACHE = false, bool PD = false>     // KSEL 2 / 4: that --NumPC, no known-AF column
 __global__ void __launch_bounds__(Geom<3>::kMaxWaves * 64, Geom<3>::kWavesPerSimd)
@@ -1409,13 +1417,13 @@ llk_resident_kernel(const DeviceLayout L, const ResidentArgs ra, double* __restr
         etab_built = true;
         hook.stage_sums = sum_stage;
         hook.crec = crec_addr;
-        hook.sync = VB2_SOFT_PROLOGUE ? reinterpret_cast<unsigned int*>(stage + 2) : nullptr;
+        hook.sync = reinterpret_cast<unsigned int*>(stage + 2);
         // ONE instance of the evaluation body (a single point goes through the four-point shape too,
         // replicated: results do not depend on the wave shape, and a second inlined body would push
         // the kernel past the instruction cache -- every round would refetch its code)
-        eval_body<3, false, ControlHook, false, QUEUE, KSEL, LCACHE, 8, PD, 0, reads_ahead(3)>(Lr, nullptr, 0, nullptr, nv, partials, dst, ticket, dflag, dseq, blockIdx.x,
-                                                   nblk_eval, nullptr, 0u, 1, tag, ra.sched_multi, false, tid_r, lds_rows,
-                                                   hook);
+        eval_body<ResidentEval<QUEUE, KSEL, LCACHE, PD>, ControlHook>(Lr, nullptr, 0, nullptr, nv, partials, dst, ticket, dflag, dseq, blockIdx.x,
+                                                                      nblk_eval, nullptr, 0u, 1, tag, ra.sched_multi, false, tid_r, lds_rows,
+                                                                      hook);
     }
 }
 

@@ -419,8 +419,9 @@ typedef struct vb2_run_args {
     const int32_t *devices;
     int32_t num_device;
     int32_t reserved;
-    /* --BamFile / --Reference: BAM or CRAM input through htslib (SimplePileupViewer.cpp:172-557);
-     * used when pileup_path is NULL.  A library built without htslib fails with VB2_ERR_IO. */
+    /* --BamFile / --Reference: BAM input (SimplePileupViewer.cpp:172-557), used when pileup_path is NULL: the built-in
+     * reader (vb2_bam_stats below), or htslib's where the library was configured with it.  reference_path is not read by
+     * the built-in reader: the reference base of a site is the panel's REF allele. */
     const char *bam_path;
     const char *reference_path;
     /* --NumStart / --Seed / --LineSearch: optimiser variants (vb2_search_opts); all zero = the
@@ -886,6 +887,43 @@ int vb2_flat_load(const vb2_run_args *args, vb2_flat **out);
 const vb2_input *vb2_flat_input(const vb2_flat *f);
 int vb2_flat_stats(const vb2_flat *f, vb2_run_result *out);
 void vb2_flat_free(vb2_flat *f);
+
+/* --BamFile through the built-in reader (no htslib): BGZF, the header, the .bai index and the
+ * record chain on the host, the per-marker pileup on args->device.  vb2_flat_load opens the file and its index before it
+ * touches a device: an unreadable BAM is VB2_ERR_IO, a valid one without a GPU VB2_ERR_NO_DEVICE (no CPU fallback).
+ * What one load did: */
+typedef struct vb2_bam_stats {
+    int64_t blocks;             /* BGZF blocks inflated (the header's included)                          */
+    int64_t bytes_inflated;     /* ... and the bytes they held, the header's not included               */
+    int64_t chunks;             /* merged chunks of the index that were read                            */
+    int64_t records_seen;       /* records walked in them                                               */
+    int64_t records_kept;       /* ... of which on a panel sequence and reaching a marker: sent up      */
+    int64_t long_cigar_skipped; /* records whose CIGAR is in a CG tag (more than 65 535 operations)     */
+    int64_t batches;            /* uploads (tunable bam_batch_kb)                                       */
+    int64_t entries;            /* (record, marker) pairs that passed the read filters                  */
+    int64_t sites;              /* markers some record spans: indexed sites                             */
+    int64_t empty_sites;        /* ... of which without a base (every read below --min-BQ, or deleted)  */
+    int64_t pairs_resolved;     /* overlapping mates met at a site                                      */
+    int64_t capped_sites;       /* sites deeper than --max-depth                                        */
+    double seconds_index;       /* open, header, index, plan                                            */
+    double seconds_inflate;     /* inflate and walk                                                     */
+    double seconds_device;      /* upload, kernels, sort                                                */
+    double seconds_copyback;    /* pools back and the sites added                                       */
+} vb2_bam_stats;
+/* VB2_ERR_INVALID for a vb2_flat that was not loaded from a BAM by the built-in reader. */
+int vb2_flat_bam_stats(const vb2_flat *f, vb2_bam_stats *out);
+
+/* The host stage alone -- no device: the records the reader would send up for the markers of bed_path. */
+/* (the handle cannot share the function's name: one namespace in C) */
+typedef struct vb2_bam_scan_result vb2_bam_scan_result;
+int vb2_bam_scan(const char *bam_path, const char *bed_path, vb2_bam_scan_result **out);
+int vb2_bam_scan_stats(const vb2_bam_scan_result *scan, vb2_bam_stats *out);     /* the host fields; the others 0 */
+/* Virtual offsets of the fetched records, ascending: returns their number, writes the first `capacity` (voffset may be
+ * NULL with capacity 0). */
+int64_t vb2_bam_scan_records(const vb2_bam_scan_result *scan, uint64_t *voffset, int64_t capacity);
+/* @RG SM: of the header, "DefaultSampleName" without one (two different ones fail vb2_bam_scan itself) */
+const char *vb2_bam_scan_sample(const vb2_bam_scan_result *scan);
+void vb2_bam_scan_free(vb2_bam_scan_result *scan);
 
 /* ------------------------------------------------------------------------- *
  * 4. Reference-panel builder: --RefVCF (main.cpp:233-257, SVDcalculator::

@@ -115,6 +115,14 @@ class RunResult(C.Structure):
     ]
 
 
+class BamStats(C.Structure):
+    """vb2_bam_stats: what one --BamFile load through the built-in reader did."""
+    _fields_ = [(n, C.c_int64) for n in ("blocks", "bytes_inflated", "chunks", "records_seen", "records_kept",
+                                          "long_cigar_skipped", "batches", "entries", "sites", "empty_sites",
+                                          "pairs_resolved", "capped_sites")] + \
+               [(n, C.c_double) for n in ("seconds_index", "seconds_inflate", "seconds_device", "seconds_copyback")]
+
+
 class CohortArgs(C.Structure):
     _fields_ = [
         ("base", RunArgs), ("num_sample", C.c_int32), ("pileup_paths", C.POINTER(C.c_char_p)),
@@ -237,6 +245,7 @@ SYMBOLS = [
     "vb2_paired_create", "vb2_paired_create_from_set", "vb2_paired_destroy", "vb2_paired_eval", "vb2_paired_optimize_llk",
     "vb2_paired_info_get", "vb2_paired_lockstep", "vb2_cohort_run_paired", "vb2_matched_normal_read",
     "vb2_cohort_run_paired_intervals", "vb2_paired_derivs", "vb2_paired_derivs_sets", "vb2_paired_interval", "vb2_paired_intervals_lockstep",
+    "vb2_flat_bam_stats", "vb2_bam_scan", "vb2_bam_scan_stats", "vb2_bam_scan_records", "vb2_bam_scan_sample", "vb2_bam_scan_free",
 ]
 
 _lib = None
@@ -293,6 +302,15 @@ def lib():
     L.vb2_flat_stats.argtypes = [C.c_void_p, C.POINTER(RunResult)]
     L.vb2_flat_free.argtypes = [C.c_void_p]
     L.vb2_flat_free.restype = None
+    L.vb2_flat_bam_stats.argtypes = [C.c_void_p, C.POINTER(BamStats)]
+    L.vb2_bam_scan.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
+    L.vb2_bam_scan_stats.argtypes = [C.c_void_p, C.POINTER(BamStats)]
+    L.vb2_bam_scan_records.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.vb2_bam_scan_records.restype = C.c_int64
+    L.vb2_bam_scan_sample.argtypes = [C.c_void_p]
+    L.vb2_bam_scan_sample.restype = C.c_char_p
+    L.vb2_bam_scan_free.argtypes = [C.c_void_p]
+    L.vb2_bam_scan_free.restype = None
     L.vb2_batch_create.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p)]
     L.vb2_batch_destroy.argtypes = [C.c_void_p]
     L.vb2_batch_destroy.restype = None

@@ -1096,15 +1096,43 @@ def optimize_with_evaluator(evaluate, num_pc, trace_capacity=0, known_af=False, 
     return out
 
 
+# the reference's defaults of its "Pileup Options" (main.cpp:81-96)
+_MPILEUP_DEFAULTS = dict(min_bq=13, min_mq=2, adjust_mq=40, max_depth=8000, no_orphans=0, incl_flags=16 | 1024,
+                         excl_flags=4 | 256 | 512 | 1024)
+
+
+def _mpileup_opts(mpileup):
+    """vb2_mpileup_opts from a dict of --min-BQ ... --excl-flags (names as in _MPILEUP_DEFAULTS); None = the defaults."""
+    if mpileup is None:
+        return _abi.MpileupOpts()
+    unknown = set(mpileup) - set(_MPILEUP_DEFAULTS)
+    if unknown:
+        raise ValueError("unknown pileup option(s): %s" % sorted(unknown))
+    o = dict(_MPILEUP_DEFAULTS, **mpileup)
+    return _abi.MpileupOpts(1, *[int(o[n]) for n in ("min_bq", "min_mq", "adjust_mq", "max_depth", "no_orphans",
+                                                      "incl_flags", "excl_flags")])
+
+
+def _set_bam(args, bam_path, mpileup):
+    if bam_path is not None:
+        if args.pileup_path is not None:
+            raise ValueError("pileup_path and bam_path exclude each other")
+        args.bam_path = str(bam_path).encode()
+    args.mpileup = _mpileup_opts(mpileup)
+
+
 def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_sanity=False,
               known_af_path=None, device=-1, output_pileup=False, devices=None, confidence_interval=False,
-              per_chromosome=False, bootstrap=0, **model_kw):
+              per_chromosome=False, bootstrap=0, bam_path=None, mpileup=None, **model_kw):
     """The --SVDPrefix/--PileupFile flow of execute() (vb2_run); devices=[a, b, ...] shards the
     sample's markers over those GPUs.  confidence_interval: vb2_run_interval (<output_prefix>.CI, and an
     `interval` entry in the result).  per_chromosome / bootstrap=N (seeded by seed=): vb2_run_replicates
-    (<output_prefix>.Chrom / .Boot, and a `replicates` entry with the jackknife and bootstrap summaries)."""
+    (<output_prefix>.Chrom / .Boot, and a `replicates` entry with the jackknife and bootstrap summaries).
+    bam_path (with pileup_path=None): --BamFile through the built-in reader; mpileup: a dict of the reference's pileup
+    options (min_bq, min_mq, adjust_mq, max_depth, no_orphans, incl_flags, excl_flags), None = its defaults."""
     args, keep = _run_args(svd_prefix, pileup_path, num_pc, disable_sanity, known_af_path,
                            output_prefix, device, output_pileup, devices=devices, **model_kw)
+    _set_bam(args, bam_path, mpileup)
     res = _abi.RunResult()
     ci = _abi.Interval() if confidence_interval else None
     summary = None
@@ -1127,6 +1155,49 @@ def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_san
                avg_depth=res.avg_depth, sd_depth=res.sd_depth, seconds_load=res.seconds_load,
                seconds_optimize=res.seconds_optimize)
     return out
+
+
+def load_bam(svd_prefix, bam_path, num_pc=2, mpileup=None, device=-1, disable_sanity=True, known_af_path=None):
+    """vb2_flat_load of a BAM (the built-in reader: host stage, then the pileup on `device`), without a search: the
+    panel-ordered reads -- read_off [M + 1], bases, quals as bytes --, num_site, num_bases, avg_depth and the load's
+    vb2_bam_stats as `stats`."""
+    args, keep = _run_args(svd_prefix, None, num_pc, disable_sanity, known_af_path, None, device)
+    _set_bam(args, bam_path, mpileup)
+    L = _abi.lib()
+    h = C.c_void_p()
+    _abi.check(L.vb2_flat_load(C.byref(args), C.byref(h)), "vb2_flat_load")
+    try:
+        inp = L.vb2_flat_input(h).contents
+        M = inp.num_marker
+        off = np.ctypeslib.as_array(C.cast(inp.read_off, C.POINTER(C.c_int64)), shape=(M + 1,)).copy()
+        n = int(off[M])
+        res = _abi.RunResult()
+        _abi.check(L.vb2_flat_stats(h, C.byref(res)), "vb2_flat_stats")
+        st = _abi.BamStats()
+        _abi.check(L.vb2_flat_bam_stats(h, C.byref(st)), "vb2_flat_bam_stats")
+        return dict(read_off=off, bases=C.string_at(inp.bases, n) if n else b"", quals=C.string_at(inp.quals, n) if n else b"",
+                    num_site=res.num_site, num_bases=int(res.num_bases), avg_depth=res.avg_depth,
+                    stats={name: getattr(st, name) for name, _ in _abi.BamStats._fields_})
+    finally:
+        L.vb2_flat_free(h)
+
+
+def bam_scan(bam_path, bed_path):
+    """The built-in reader's host stage alone (vb2_bam_scan; no device): dict(voffsets -- the virtual offsets of the
+    records it would send to the device, ascending --, sample, stats)."""
+    L = _abi.lib()
+    h = C.c_void_p()
+    _abi.check(L.vb2_bam_scan(str(bam_path).encode(), str(bed_path).encode(), C.byref(h)), "vb2_bam_scan")
+    try:
+        n = L.vb2_bam_scan_records(h, None, 0)
+        v = np.zeros(max(n, 1), dtype=np.uint64)
+        L.vb2_bam_scan_records(h, v.ctypes.data_as(C.c_void_p), n)
+        st = _abi.BamStats()
+        L.vb2_bam_scan_stats(h, C.byref(st))
+        return dict(voffsets=v[:n], sample=L.vb2_bam_scan_sample(h).decode(),
+                    stats={name: getattr(st, name) for name, _ in _abi.BamStats._fields_})
+    finally:
+        L.vb2_bam_scan_free(h)
 
 
 def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, disable_sanity=False,

@@ -728,8 +728,9 @@ int vb2_flat_load(const vb2_run_args* a, vb2_flat** out)
         if (!rc) {
             rc_pile = a->pileup_path ? vb2::read_pileup(a->pileup_path, f->panel, &f->viewer)
                                      : vb2::read_bam(a->bam_path, a->reference_path ? a->reference_path : "",
-                                                     f->panel, &f->viewer, &a->mpileup);
+                                                     f->panel, &f->viewer, &a->mpileup, a->device, &f->bam_stats);
             if (rc_pile) err_pile = vb2::g_last_error;
+            f->from_bam = !a->pileup_path && !rc_pile;
         }
         tl_pile = now_s();
         t_ud.join();
@@ -777,6 +778,56 @@ int vb2_flat_stats(const vb2_flat* f, vb2_run_result* out)
 }
 
 void vb2_flat_free(vb2_flat* f) { delete f; }
+
+int vb2_flat_bam_stats(const vb2_flat* f, vb2_bam_stats* out)
+{
+    if (!f || !out || !f->from_bam) {
+        set_error("vb2_flat_bam_stats: not a vb2_flat loaded from a BAM");
+        return VB2_ERR_INVALID;
+    }
+    *out = f->bam_stats;
+    return VB2_OK;
+}
+
+struct vb2_bam_scan_result {
+    std::vector<uint64_t> voffset;
+    vb2_bam_stats stats;
+    std::string sample;
+};
+
+int vb2_bam_scan(const char* bam_path, const char* bed_path, vb2_bam_scan_result** out)
+{
+    if (!bam_path || !bed_path || !out) {
+        set_error("vb2_bam_scan: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    *out = nullptr;
+    return vb2::guarded([&]() -> int {
+        std::unique_ptr<vb2_bam_scan_result> s(new vb2_bam_scan_result());
+        if (int rc = vb2::bam_scan_file(bam_path, bed_path, &s->voffset, &s->stats, &s->sample)) return rc;
+        *out = s.release();
+        return VB2_OK;
+    });
+}
+
+int vb2_bam_scan_stats(const vb2_bam_scan_result* scan, vb2_bam_stats* out)
+{
+    if (!scan || !out) return VB2_ERR_INVALID;
+    *out = scan->stats;
+    return VB2_OK;
+}
+
+int64_t vb2_bam_scan_records(const vb2_bam_scan_result* scan, uint64_t* voffset, int64_t capacity)
+{
+    if (!scan) return VB2_ERR_INVALID;
+    const int64_t n = (int64_t)scan->voffset.size();
+    for (int64_t i = 0; voffset && i < n && i < capacity; ++i) voffset[i] = scan->voffset[(size_t)i];
+    return n;
+}
+
+const char* vb2_bam_scan_sample(const vb2_bam_scan_result* scan) { return scan ? scan->sample.c_str() : ""; }
+
+void vb2_bam_scan_free(vb2_bam_scan_result* scan) { delete scan; }
 
 int vb2_ctx_interval(vb2_ctx* ctx, const vb2_model* model, const vb2_estimate* est, vb2_interval* out)
 {

@@ -11,14 +11,17 @@
 // It fills the same PileupViewer (sites in two pools, hostio.h) the text-pileup reader fills, so the
 // sanity check, BuildResolvedMarkers and the flattening into pinned SoA arrays are shared.
 //
-// NEEDS htslib (>= 1.10: hts_pos_t), which neither this build image nor the GPU box has (probed
-// in round 3: no htslib/sam.h, no libhts anywhere on either).  The file is compiled only on an
-// explicit opt-in, `cmake -DVB2_WITH_HTSLIB=ON` (default OFF since round 3: a machine that happens
-// to have libhts must not silently ship an unvalidated reader); otherwise read_bam() reports that
-// and --BamFile fails loudly.  STATUS: written against htslib's public API, NOT compiled and NOT
-// validated anywhere (no htslib, and the reference's resource/test/test.bam is absent): parity at
-// this boundary is UNPINNED -- validate with `--OutputPileup` against the reference's
-// expected/result.Pileup where htslib and a BAM exist before relying on it.
+// TWO READERS, one per build.  The default build has the built-in one at the end of this file: the
+// host stage of bam_io.cpp (BGZF, header, .bai, records; plain C++ and zlib), the per-marker pileup of the decoded records on
+// the device (bam_pileup_kernels.hip), the pools back into the PileupViewer.  It applies neither BAQ nor the mapQ cap and
+// takes the panel's REF allele as the reference base; it is pinned to tests/bam_ref.py's restatement and to the reference's
+// golden files (tests/test_bam_gpu.py).
+// The htslib reader below NEEDS htslib (>= 1.10: hts_pos_t), which neither this build image nor the GPU box has (probed
+// in round 3: no htslib/sam.h, no libhts anywhere on either).  It is compiled only on an explicit opt-in,
+// `cmake -DVB2_WITH_HTSLIB=ON` (default OFF since round 3: a machine that happens to have libhts must not silently ship an
+// unvalidated reader).  STATUS: written against htslib's public API, NOT compiled and NOT validated anywhere: parity at
+// this boundary is UNPINNED -- validate with `--OutputPileup` against the reference's expected/result.Pileup where htslib
+// and a BAM exist before relying on it.
 //
 // Two behaviours of the reference that look like slips are kept on purpose, because the golden
 // outputs were produced with them (SimplePileupViewer.cpp:448-476, 502-511):
@@ -145,7 +148,7 @@ std::string sample_name(sam_hdr_t* hdr)     // @RG SM: (SimplePileupViewer.cpp:2
 }  // namespace
 
 int read_bam(const std::string& bam_path, const std::string& ref_path, const Panel& panel, PileupViewer* v,
-             const vb2_mpileup_opts* mp)
+             const vb2_mpileup_opts* mp, int, vb2_bam_stats*)
 {
     Aux a;
     a.conf.apply(mp);
@@ -239,20 +242,394 @@ int read_bam(const std::string& bam_path, const std::string& ref_path, const Pan
 
 bool bam_support() { return true; }
 
-}  // namespace vb2
-
-#else   // ---- built without htslib ----
-
-namespace vb2 {
-
-int read_bam(const std::string&, const std::string&, const Panel&, PileupViewer*, const vb2_mpileup_opts*)
+int bam_scan_file(const std::string&, const std::string&, std::vector<uint64_t>*, vb2_bam_stats*, std::string*)
 {
-    set_error("--BamFile needs htslib, which this build does not have (configure with CMake where libhts is "
-              "installed); run the reference once with --OutputPileup and pass the result with --PileupFile");
-    return VB2_ERR_IO;
+    set_error("vb2_bam_scan: this library reads BAM through htslib (VB2_WITH_HTSLIB); the built-in reader's host stage is not in it");
+    return VB2_ERR_INVALID;
 }
 
-bool bam_support() { return false; }
+}  // namespace vb2
+
+#else   // ---- built without htslib: the built-in reader ----
+
+#include "bam_io.h"
+#include "bam_pileup_kernels.h"
+#include "device_util.h"
+#include "tunables.h"
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <string>
+#include <utility>
+#include <vector>
+
+namespace vb2 {
+namespace {
+
+constexpr int kMplpNoOrphan = 1 << 3, kMplpRealn = 1 << 4, kMplpSmartOverlaps = 1 << 10;
+
+struct MplpConf {                      // main.cpp:81-96
+    int min_mq = 2, min_baseQ = 13, capQ_thres = 40, max_depth = 8000;
+    int flag = kMplpRealn | kMplpSmartOverlaps;
+    uint32_t rflag_filter = 4 | 256 | 512 | 1024;      // UNMAP | SECONDARY | QCFAIL | DUP
+    void apply(const vb2_mpileup_opts* mp)      // main.cpp:176-187, 208-211
+    {
+        if (!mp || !mp->given) return;
+        min_baseQ = mp->min_bq;
+        min_mq = mp->min_mq;
+        capQ_thres = mp->adjust_mq;
+        max_depth = mp->max_depth;
+        flag = mp->incl_flags;
+        if (mp->no_orphans) flag |= kMplpNoOrphan;
+        else flag &= ~kMplpNoOrphan;
+        rflag_filter = (uint32_t)mp->excl_flags;
+    }
+};
+
+double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+uint8_t nt16(char c)                   // htslib's seq_nt16_table for the letters a .bed's REF column can hold
+{
+    static const char kCodes[] = "=ACMGRSVTWYHKDBN";
+    if (c >= 'a' && c <= 'z') c = (char)(c - 32);
+    for (int i = 0; i < 16; ++i)
+        if (kCodes[i] == c) return (uint8_t)i;
+    return 15;
+}
+
+// device, pinned and stream handles that every exit path releases
+struct Dev {
+    void* p = nullptr;
+    ~Dev() { if (p) (void)hipFree(p); }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+struct Pinned {
+    void* p = nullptr;
+    ~Pinned() { if (p) (void)hipHostFree(p); }
+};
+struct StreamHolder {
+    hipStream_t s = nullptr;
+    ~StreamHolder() { if (s) (void)hipStreamDestroy(s); }
+};
+struct DevList {
+    std::vector<void*> v;
+    ~DevList() { for (void* p : v) (void)hipFree(p); }
+};
+
+// Stages 2 and 3: the scan's records up in batches, entries, sort, sites, pools back, the viewer filled.
+int device_pileup(const bamio::Scan& scan, const std::vector<std::vector<std::pair<int32_t, int32_t>>>& by_seq, const Panel& panel,
+                  const MplpConf& conf, int device, PileupViewer* v, vb2_bam_stats* stats)
+{
+    const double t0 = now_s();
+    const int32_t num_slot = (int32_t)panel.num_slot();
+    const int32_t n_ref = (int32_t)scan.ref_name.size();
+    if (device >= 0) VB2_HIP(hipSetDevice(device));
+    StreamHolder st;
+    VB2_HIP(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    hipStream_t s = st.s;
+
+    // marker tables: per tid a run of (position, slot), ascending
+    std::vector<int32_t> h_tid_lo((size_t)n_ref + 1, 0), h_pos, h_slot;
+    {
+        std::vector<int32_t> seq_of_tid((size_t)n_ref, -1);
+        for (size_t c = 0; c < scan.tid_of_seq.size(); ++c)
+            if (scan.tid_of_seq[c] >= 0) seq_of_tid[(size_t)scan.tid_of_seq[c]] = (int32_t)c;
+        for (int32_t t = 0; t < n_ref; ++t) {
+            h_tid_lo[(size_t)t] = (int32_t)h_pos.size();
+            if (seq_of_tid[(size_t)t] < 0) continue;
+            for (const auto& ps : by_seq[(size_t)seq_of_tid[(size_t)t]]) {
+                h_pos.push_back(ps.first);
+                h_slot.push_back(ps.second);
+            }
+        }
+        h_tid_lo[(size_t)n_ref] = (int32_t)h_pos.size();
+    }
+    std::vector<uint8_t> h_refnib((size_t)num_slot);
+    for (int32_t k = 0; k < num_slot; ++k) h_refnib[(size_t)k] = nt16(panel.slotRef[(size_t)k]);
+    Dev d_tid_lo, d_pos, d_slot, d_refnib, d_ctr;
+    VB2_HIP(hipMalloc(&d_tid_lo.p, h_tid_lo.size() * 4));
+    VB2_HIP(hipMalloc(&d_pos.p, std::max<size_t>(h_pos.size(), 1) * 4));
+    VB2_HIP(hipMalloc(&d_slot.p, std::max<size_t>(h_slot.size(), 1) * 4));
+    VB2_HIP(hipMalloc(&d_refnib.p, std::max<size_t>(h_refnib.size(), 1)));
+    VB2_HIP(hipMalloc(&d_ctr.p, sizeof(PileCounters)));
+    VB2_HIP(hipMemcpyAsync(d_tid_lo.p, h_tid_lo.data(), h_tid_lo.size() * 4, hipMemcpyHostToDevice, s));
+    if (!h_pos.empty()) {
+        VB2_HIP(hipMemcpyAsync(d_pos.p, h_pos.data(), h_pos.size() * 4, hipMemcpyHostToDevice, s));
+        VB2_HIP(hipMemcpyAsync(d_slot.p, h_slot.data(), h_slot.size() * 4, hipMemcpyHostToDevice, s));
+    }
+    if (num_slot > 0) VB2_HIP(hipMemcpyAsync(d_refnib.p, h_refnib.data(), h_refnib.size(), hipMemcpyHostToDevice, s));
+    VB2_HIP(hipMemsetAsync(d_ctr.p, 0, sizeof(PileCounters), s));
+    VB2_HIP(hipStreamSynchronize(s));            // (the host vectors above may go)
+    const PileMarkers markers{d_tid_lo.as<int32_t>(), d_pos.as<int32_t>(), d_slot.as<int32_t>(), n_ref};
+    const PileFilter filter{(int32_t)conf.rflag_filter, conf.min_mq, (conf.flag & kMplpNoOrphan) ? 1 : 0};
+    const int32_t max_depth = conf.max_depth < 0 ? 0 : conf.max_depth;
+
+    // ---- batches: the kept records' names, CIGARs, bases and qualities, back to back, and their descriptors ----
+    auto var_bytes = [](const bamio::RecordDesc& d) {
+        return (size_t)d.l_read_name + 4 * (size_t)d.n_cigar + ((size_t)d.l_seq + 1) / 2 + (size_t)d.l_seq;
+    };
+    size_t largest = 0, total_rec = 0;
+    for (const bamio::Chunk& ch : scan.chunks) {
+        total_rec += ch.recs.size();
+        for (const bamio::RecordDesc& d : ch.recs) largest = std::max(largest, var_bytes(d));
+    }
+    const size_t batch_bytes = std::max<size_t>((size_t)std::max(vb2::tunables().bam_batch_kb, 1) << 10, largest);
+    if (batch_bytes > 0xfff00000ull) { set_error("--BamFile: bam_batch_kb asks for batches of 4 GiB or more"); return VB2_ERR_INVALID; }
+    // a batch closes when its bytes are full; its records are bounded by its bytes (a record has at least a name)
+    // ... or when its descriptors weigh as much as its bytes would
+    const size_t batch_rec = std::min<size_t>(std::max<size_t>(total_rec, 1), std::max<size_t>(batch_bytes / sizeof(bamio::RecordDesc), 1));
+    Pinned h_data, h_desc, h_total;
+    VB2_HIP(hipHostMalloc(&h_data.p, batch_bytes, hipHostMallocDefault));
+    VB2_HIP(hipHostMalloc(&h_desc.p, batch_rec * sizeof(bamio::RecordDesc), hipHostMallocDefault));
+    VB2_HIP(hipHostMalloc(&h_total.p, sizeof(unsigned long long), hipHostMallocDefault));
+    Dev d_desc, d_count, d_offset, d_total;
+    VB2_HIP(hipMalloc(&d_desc.p, batch_rec * sizeof(bamio::RecordDesc)));
+    VB2_HIP(hipMalloc(&d_count.p, batch_rec * 4));
+    VB2_HIP(hipMalloc(&d_offset.p, batch_rec * 4));
+    VB2_HIP(hipMalloc(&d_total.p, sizeof(unsigned long long)));
+    DevList d_batches;                            // the batches' bytes stay: the overlap rule compares read names in them
+    Dev d_entries, d_keys;
+    size_t cap_entries = 0;
+    int64_t num_entries = 0, num_batch = 0;
+    uint8_t* const hd = static_cast<uint8_t*>(h_data.p);
+    bamio::RecordDesc* const hr = static_cast<bamio::RecordDesc*>(h_desc.p);
+
+    size_t ci = 0, ri = 0;                        // next record: scan.chunks[ci].recs[ri]
+    auto skip_empty = [&] { while (ci < scan.chunks.size() && ri >= scan.chunks[ci].recs.size()) { ++ci; ri = 0; } };
+    skip_empty();
+    while (ci < scan.chunks.size()) {
+        size_t nb = 0, nr = 0;
+        while (ci < scan.chunks.size() && nr < batch_rec) {
+            const bamio::Chunk& ch = scan.chunks[ci];
+            const bamio::RecordDesc& d = ch.recs[ri];
+            const size_t vb = var_bytes(d);
+            if ((size_t)d.data > ch.bytes.size() || vb > ch.bytes.size() - d.data) {      // (bam_io.cpp has checked this)
+                set_error("--BamFile: internal error: a record passes its chunk");
+                return VB2_ERR_INVALID;
+            }
+            if (nb + vb > batch_bytes) break;
+            std::memcpy(hd + nb, ch.bytes.data() + d.data, vb);
+            hr[nr] = d;
+            hr[nr].data = (uint32_t)nb;
+            nb += vb;
+            ++nr;
+            ++ri;
+            skip_empty();
+        }
+        void* d_data = nullptr;
+        VB2_HIP(hipMalloc(&d_data, std::max<size_t>(nb, 1)));
+        d_batches.v.push_back(d_data);
+        VB2_HIP(hipMemcpyAsync(d_data, hd, nb, hipMemcpyHostToDevice, s));
+        VB2_HIP(hipMemcpyAsync(d_desc.p, hr, nr * sizeof(bamio::RecordDesc), hipMemcpyHostToDevice, s));
+        VB2_HIP(launch_cover_count(d_desc.as<bamio::RecordDesc>(), (int64_t)nr, static_cast<const uint8_t*>(d_data), nb, filter,
+                                   markers, d_count.as<uint32_t>(), s));
+        VB2_HIP(launch_scan_u32(d_count.as<uint32_t>(), d_offset.as<uint32_t>(), (int64_t)nr, d_total.as<unsigned long long>(), s));
+        VB2_HIP(hipMemcpyAsync(h_total.p, d_total.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        VB2_HIP(hipStreamSynchronize(s));        // the staging buffers are free again; the fill below runs under the next copy-in
+        const unsigned long long add = *static_cast<unsigned long long*>(h_total.p);
+        if ((unsigned long long)num_entries + add >= 0x7fffffffull) {
+            set_error("--BamFile: more than 2^31 (record, marker) pairs over the panel");
+            return VB2_ERR_INVALID;
+        }
+        if ((size_t)num_entries + add > cap_entries) {
+            const size_t want = std::max<size_t>({(size_t)num_entries + (size_t)add, cap_entries * 2, (size_t)1 << 16});
+            Dev ne, nk;
+            VB2_HIP(hipMalloc(&ne.p, want * sizeof(PileEntry)));
+            VB2_HIP(hipMalloc(&nk.p, want * sizeof(uint64_t)));
+            if (num_entries > 0) {
+                VB2_HIP(hipMemcpyAsync(ne.p, d_entries.p, (size_t)num_entries * sizeof(PileEntry), hipMemcpyDeviceToDevice, s));
+                VB2_HIP(hipMemcpyAsync(nk.p, d_keys.p, (size_t)num_entries * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+                VB2_HIP(hipStreamSynchronize(s));
+            }
+            std::swap(ne.p, d_entries.p);
+            std::swap(nk.p, d_keys.p);
+            cap_entries = want;
+        }
+        if (add > 0)
+            VB2_HIP(launch_cover_fill(d_desc.as<bamio::RecordDesc>(), (int64_t)nr, static_cast<const uint8_t*>(d_data), nb, filter,
+                                      markers, d_offset.as<uint32_t>(), d_entries.as<PileEntry>() + num_entries,
+                                      d_keys.as<uint64_t>() + num_entries, s));
+        // (d_desc and d_offset are written again only by the next batch's copies, which the stream orders behind this fill)
+        num_entries += (int64_t)add;
+        ++num_batch;
+    }
+    VB2_HIP(hipStreamSynchronize(s));
+
+    // ---- sort by slot (file order within a slot), the overlap rule, the sites ----
+    Dev d_keys2, d_idx, d_idx2, d_temp, d_sorted, d_qual, d_range, d_depth, d_off, d_rep, d_bases, d_quals;
+    const size_t ne1 = std::max<size_t>((size_t)num_entries, 1), ns1 = (size_t)num_slot + 1;
+    VB2_HIP(hipMalloc(&d_range.p, ns1 * 4));
+    VB2_HIP(hipMalloc(&d_depth.p, ns1 * 4));
+    VB2_HIP(hipMalloc(&d_off.p, ns1 * 4));
+    VB2_HIP(hipMalloc(&d_rep.p, ns1));
+    VB2_HIP(hipMalloc(&d_qual.p, ne1));
+    VB2_HIP(hipMalloc(&d_sorted.p, ne1 * sizeof(PileEntry)));
+    VB2_HIP(hipMalloc(&d_keys2.p, ne1 * sizeof(uint64_t)));
+    if (num_entries > 0) {
+        VB2_HIP(hipMalloc(&d_idx.p, ne1 * 4));
+        VB2_HIP(hipMalloc(&d_idx2.p, ne1 * 4));
+        size_t temp_bytes = 0;
+        VB2_HIP(sort_entries(nullptr, &temp_bytes, d_keys.as<uint64_t>(), d_keys2.as<uint64_t>(), d_idx.as<uint32_t>(),
+                             d_idx2.as<uint32_t>(), num_entries, s));
+        VB2_HIP(hipMalloc(&d_temp.p, std::max<size_t>(temp_bytes, 1)));
+        VB2_HIP(launch_iota_u32(d_idx.as<uint32_t>(), num_entries, s));
+        VB2_HIP(sort_entries(d_temp.p, &temp_bytes, d_keys.as<uint64_t>(), d_keys2.as<uint64_t>(), d_idx.as<uint32_t>(),
+                             d_idx2.as<uint32_t>(), num_entries, s));
+        VB2_HIP(launch_gather(d_entries.as<PileEntry>(), d_idx2.as<uint32_t>(), d_sorted.as<PileEntry>(), num_entries, s));
+    }
+    VB2_HIP(launch_site_ranges(d_keys2.as<uint64_t>(), num_entries, num_slot, d_range.as<uint32_t>(), s));
+    VB2_HIP(launch_overlap(d_sorted.as<PileEntry>(), d_range.as<uint32_t>(), num_entries, max_depth,
+                           (conf.flag & kMplpSmartOverlaps) ? 1 : 0, d_qual.as<uint8_t>(), d_ctr.as<PileCounters>(), s));
+    VB2_HIP(launch_sites(false, d_sorted.as<PileEntry>(), d_range.as<uint32_t>(), d_qual.as<uint8_t>(), num_slot, max_depth,
+                         conf.min_baseQ, d_refnib.as<uint8_t>(), d_depth.as<uint32_t>(), d_rep.as<uint8_t>(), nullptr, nullptr,
+                         nullptr, d_ctr.as<PileCounters>(), s));
+    VB2_HIP(launch_scan_u32(d_depth.as<uint32_t>(), d_off.as<uint32_t>(), num_slot, d_total.as<unsigned long long>(), s));
+    VB2_HIP(hipMemcpyAsync(h_total.p, d_total.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    VB2_HIP(hipStreamSynchronize(s));
+    const unsigned long long total_bases = *static_cast<unsigned long long*>(h_total.p);
+    if (total_bases > 0x7fffffffull) {
+        set_error("pileup too large: more than 2 GiB of bases at the panel's sites");
+        return VB2_ERR_INVALID;
+    }
+    VB2_HIP(hipMalloc(&d_bases.p, std::max<size_t>((size_t)total_bases, 1)));
+    VB2_HIP(hipMalloc(&d_quals.p, std::max<size_t>((size_t)total_bases, 1)));
+    VB2_HIP(launch_sites(true, d_sorted.as<PileEntry>(), d_range.as<uint32_t>(), d_qual.as<uint8_t>(), num_slot, max_depth,
+                         conf.min_baseQ, d_refnib.as<uint8_t>(), d_depth.as<uint32_t>(), d_rep.as<uint8_t>(), d_off.as<uint32_t>(),
+                         d_bases.as<char>(), d_quals.as<char>(), d_ctr.as<PileCounters>(), s));
+    VB2_HIP(hipStreamSynchronize(s));
+    const double t1 = now_s();
+
+    // ---- stage 3: the pools back, the sites in .bed row order ----
+    std::vector<uint32_t> depth((size_t)num_slot), off((size_t)num_slot);
+    std::vector<uint8_t> rep((size_t)num_slot);
+    std::string bases((size_t)total_bases, '\0'), quals((size_t)total_bases, '\0');
+    PileCounters ctr{0, 0};
+    if (num_slot > 0) {
+        VB2_HIP(hipMemcpy(depth.data(), d_depth.p, (size_t)num_slot * 4, hipMemcpyDeviceToHost));
+        VB2_HIP(hipMemcpy(off.data(), d_off.p, (size_t)num_slot * 4, hipMemcpyDeviceToHost));
+        VB2_HIP(hipMemcpy(rep.data(), d_rep.p, (size_t)num_slot, hipMemcpyDeviceToHost));
+    }
+    if (total_bases > 0) {
+        VB2_HIP(hipMemcpy(&bases[0], d_bases.p, (size_t)total_bases, hipMemcpyDeviceToHost));
+        VB2_HIP(hipMemcpy(&quals[0], d_quals.p, (size_t)total_bases, hipMemcpyDeviceToHost));
+    }
+    VB2_HIP(hipMemcpy(&ctr, d_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost));
+    int64_t empty_sites = 0;
+    for (size_t row = 0; row < panel.PosVec.size(); ++row) {
+        const int32_t slot = panel.rowSlot[row];
+        if (slot < 0 || slot >= num_slot || !rep[(size_t)slot] || v->siteOfSlot[(size_t)slot] >= 0) continue;
+        const uint32_t n = depth[(size_t)slot];
+        if (n > 0) {
+            v->effectiveNumSite++;
+            v->numBases += (int)n;
+        } else {
+            ++empty_sites;
+        }
+        v->add_site(slot, bases.data() + off[(size_t)slot], quals.data() + off[(size_t)slot], n);
+    }
+    v->avgDepth = v->effectiveNumSite ? (double)v->numBases / v->effectiveNumSite : 0.0;
+    if (stats) {
+        stats->entries = num_entries;
+        stats->batches = num_batch;
+        stats->sites = v->num_site();
+        stats->empty_sites = empty_sites;
+        stats->pairs_resolved = (int64_t)ctr.pairs_resolved;
+        stats->capped_sites = (int64_t)ctr.capped_sites;
+        stats->seconds_device = t1 - t0;
+        stats->seconds_copyback = now_s() - t1;
+    }
+    return VB2_OK;
+}
+
+// the panel's markers per sequence name, (position, slot) ascending
+void markers_by_sequence(const Panel& panel, std::vector<bamio::SeqMarkers>* seqs,
+                         std::vector<std::vector<std::pair<int32_t, int32_t>>>* by_seq)
+{
+    by_seq->assign(panel.chrNames.size(), {});
+    for (size_t k = 0; k < panel.num_slot(); ++k) (*by_seq)[(size_t)panel.slotChr[k]].emplace_back(panel.slotPos[k], (int32_t)k);
+    seqs->resize(panel.chrNames.size());
+    for (size_t c = 0; c < by_seq->size(); ++c) {
+        std::sort((*by_seq)[c].begin(), (*by_seq)[c].end());
+        (*seqs)[c].name = panel.chrNames[c];
+        for (const auto& ps : (*by_seq)[c]) (*seqs)[c].pos.push_back(ps.first);
+    }
+}
+
+int reader_threads()
+{
+    const int t = vb2::tunables().bam_threads;
+    return std::max(1, std::min(t > 0 ? t : usable_cpu_count(), 16));
+}
+
+void host_stats(const bamio::Scan& scan, vb2_bam_stats* st)
+{
+    std::memset(st, 0, sizeof(*st));
+    st->blocks = scan.stats.blocks;
+    st->bytes_inflated = scan.stats.bytes_inflated;
+    st->records_seen = scan.stats.records_seen;
+    st->records_kept = scan.stats.records_kept;
+    st->long_cigar_skipped = scan.stats.long_cigar_skipped;
+    st->chunks = scan.stats.chunks;
+    st->seconds_index = scan.stats.seconds_index;
+    st->seconds_inflate = scan.stats.seconds_inflate;
+}
+
+}  // namespace
+
+int read_bam(const std::string& bam_path, const std::string&, const Panel& panel, PileupViewer* v, const vb2_mpileup_opts* mp,
+             int device, vb2_bam_stats* stats)
+{
+    MplpConf conf;
+    conf.apply(mp);
+    std::vector<bamio::SeqMarkers> seqs;
+    std::vector<std::vector<std::pair<int32_t, int32_t>>> by_seq;
+    markers_by_sequence(panel, &seqs, &by_seq);
+    // the file and its index first: no device is touched for an input that cannot be read
+    bamio::Scan scan;
+    std::string err;
+    if (int rc = bamio::scan(bam_path, seqs, reader_threads(), &scan, &err)) {
+        set_error(err);
+        return rc;                     // bamio's codes are the ABI's
+    }
+    vb2_bam_stats local;
+    if (!stats) stats = &local;
+    host_stats(scan, stats);
+    v->SEQ_SM = scan.sample;
+    v->init(panel);
+    v->numBases = 0;
+    v->effectiveNumSite = 0;
+    if (usable_device_count() < 1) {
+        set_error("--BamFile: no gfx950 device is visible; the pileup of the decoded records runs on the GPU only "
+                  "(there is no CPU fallback)");
+        return VB2_ERR_NO_DEVICE;
+    }
+    return device_pileup(scan, by_seq, panel, conf, device, v, stats);
+}
+
+bool bam_support() { return true; }
+
+// Stage 1 alone (vb2_bam_scan): no device
+int bam_scan_file(const std::string& bam_path, const std::string& bed_path, std::vector<uint64_t>* voffsets, vb2_bam_stats* stats,
+                  std::string* sample)
+{
+    Panel panel;
+    if (int rc = read_bed(bed_path, &panel)) return rc;
+    std::vector<bamio::SeqMarkers> seqs;
+    std::vector<std::vector<std::pair<int32_t, int32_t>>> by_seq;
+    markers_by_sequence(panel, &seqs, &by_seq);
+    bamio::Scan scan;
+    std::string err;
+    if (int rc = bamio::scan(bam_path, seqs, reader_threads(), &scan, &err)) {
+        set_error(err);
+        return rc;
+    }
+    host_stats(scan, stats);
+    *sample = scan.sample;
+    voffsets->clear();
+    for (const bamio::Chunk& ch : scan.chunks) voffsets->insert(voffsets->end(), ch.voffset.begin(), ch.voffset.end());
+    return VB2_OK;
+}
 
 }  // namespace vb2
 

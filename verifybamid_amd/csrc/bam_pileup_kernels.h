@@ -1,0 +1,79 @@
+// bam_pileup_kernels.h -- the device stage of the built-in BAM reader (bam_pileup_kernels.hip):
+// decoded records -> one entry per (record, covered marker) in file order -> the per-site bases and qualities of a
+// PileupViewer.
+#ifndef VB2_BAM_PILEUP_KERNELS_H_
+#define VB2_BAM_PILEUP_KERNELS_H_
+
+#include <hip/hip_runtime_api.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "bam_io.h"
+
+namespace vb2 {
+
+// One record over one marker.  bits: the base's 4-bit code | reverse << 4 | deleted (D or N) << 5 | pair-eligible << 6
+// | (mate position >= own position) << 7.
+struct PileEntry {
+    uint64_t name;          // device address of the read name in its batch's bytes (kept until the sites are written)
+    uint64_t hash;          // FNV-1a of the name
+    uint32_t order;         // the record's file-order number
+    int32_t slot;           // the marker's panel slot
+    uint8_t qual;
+    uint8_t bits;
+    uint8_t l_name;
+    uint8_t pad[5];
+};
+static_assert(sizeof(PileEntry) == 32, "entries are 32 bytes");
+constexpr uint8_t kEntryReverse = 16, kEntryDeleted = 32, kEntryEligible = 64, kEntryMateAhead = 128;
+
+struct PileFilter {         // mplp_func's read filter (SimplePileupViewer.cpp:172-237) without BAQ and the mapQ cap
+    int32_t excl_flags, min_mq, no_orphans;
+};
+
+// The markers of the BAM's sequences: tid t owns [tid_lo[t], tid_lo[t + 1]) of pos (1-based, ascending) and slot.
+struct PileMarkers {
+    const int32_t* tid_lo;
+    const int32_t* pos;
+    const int32_t* slot;
+    int32_t n_ref;
+};
+
+struct PileCounters {       // device-side statistics, added to by the kernels
+    unsigned long long pairs_resolved, capped_sites;
+};
+
+// Pass 1 of a batch: count[r] = markers record r covers (0 for a filtered record).  data: the batch's record bytes.
+hipError_t launch_cover_count(const bamio::RecordDesc* desc, int64_t num_rec, const uint8_t* data, uint64_t data_bytes,
+                              PileFilter f, PileMarkers m, uint32_t* count, hipStream_t s);
+// offset = exclusive scan of count [n], *total = its sum (a single workgroup walks the array)
+hipError_t launch_scan_u32(const uint32_t* count, uint32_t* offset, int64_t n, unsigned long long* total, hipStream_t s);
+// Pass 2: record r's entries go to entries[offset[r] ...], and their sort keys slot << 32 | order to keys[...]
+hipError_t launch_cover_fill(const bamio::RecordDesc* desc, int64_t num_rec, const uint8_t* data, uint64_t data_bytes,
+                             PileFilter f, PileMarkers m, const uint32_t* offset, PileEntry* entries, uint64_t* keys,
+                             hipStream_t s);
+
+// Sorts the keys with the entries' indices: keys_out ascending, idx_out the permutation (n < 2^31).  temp / temp_bytes as
+// hipcub wants them: call with temp == nullptr to learn temp_bytes.
+hipError_t sort_entries(void* temp, size_t* temp_bytes, const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* idx_in,
+                        uint32_t* idx_out, int64_t n, hipStream_t s);
+hipError_t launch_iota_u32(uint32_t* idx, int64_t n, hipStream_t s);
+hipError_t launch_gather(const PileEntry* entries, const uint32_t* perm, PileEntry* sorted, int64_t n, hipStream_t s);
+// range[s] = first sorted entry of a slot >= s, s in [0, num_slot]: slot s owns the sorted entries [range[s], range[s + 1])
+hipError_t launch_site_ranges(const uint64_t* keys, int64_t n, int32_t num_slot, uint32_t* range, hipStream_t s);
+
+// The mate-overlap rule over the sorted entries: qual_out[i] = entry i's quality afterwards.  smart == 0: qualities as
+// they are.  The depth cap applies first: entries behind a site's first max_depth are left alone.
+hipError_t launch_overlap(const PileEntry* sorted, const uint32_t* range, int64_t n, int32_t max_depth, int32_t smart,
+                          uint8_t* qual_out, PileCounters* ctr, hipStream_t s);
+
+// Per slot: fill == false: depth[slot] = bases the site stores, reported[slot] = some record spans it; fill == true: the
+// characters at base_pool / qual_pool + offset[slot].  ref_nib: the 4-bit code of the panel's REF allele per slot.
+hipError_t launch_sites(bool fill, const PileEntry* sorted, const uint32_t* range, const uint8_t* qual, int32_t num_slot,
+                        int32_t max_depth, int32_t min_bq, const uint8_t* ref_nib, uint32_t* depth, uint8_t* reported,
+                        const uint32_t* offset, char* base_pool, char* qual_pool, PileCounters* ctr, hipStream_t s);
+
+}  // namespace vb2
+
+#endif

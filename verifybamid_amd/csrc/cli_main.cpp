@@ -9,8 +9,11 @@
 //               [--incl-flags n] [--excl-flags n]      (the reference's "Pileup Options", main.cpp:176-187: --BamFile only)
 //
 // --Epsilon e is the simplex's relative tolerance; a value that is not positive (0, negative, NaN) means the default 1e-8.
-// --BamFile needs a build with htslib (CMake finds it: bam_flatten.cpp); a build without it --
-// this image's -- reports that and suggests the reference's own --OutputPileup file with --PileupFile.
+// --BamFile B reads a coordinate-sorted BAM with its .bai through the built-in reader (no htslib):
+// BGZF, index and records on the host (--NumThread above its default of 4 sizes that pool), the per-marker pileup on the
+// GPU.  BAQ and the mapQ cap need htslib and the FASTA and are not applied -- a NOTICE says so when the options ask for
+// them, and names the reference command that matches what was computed (--incl-flags 1024 --adjust-MQ 0); the reference
+// base of a site is the panel's REF allele, so --Reference stays required and unread.  CRAM and .csi are not read.
 // --RefVCF V [--NumSVDPCs k] [--SkipMinSampleCountCheck] [--IncludeChr a,b,..] [--GramSVD] builds a reference panel
 // (main.cpp:233-257): V.UD, V.mu, V.bed, V.V, decomposed on the GPU (vb2_panel_build), and returns before --Reference
 // is looked at.  --NumThread sizes the VCF parser pool there.
@@ -38,6 +41,8 @@
 #include <vector>
 
 #include "../../include/vb2_abi.h"
+
+extern "C" int vb2_debug_set_tunable(const char* name, int value);      // (abi.cpp; csrc/tunables.h)
 
 namespace {
 
@@ -344,7 +349,7 @@ int main(int argc, char** argv)
     args.mean_path = MeanPath.c_str();
     args.bed_path = BedPath.c_str();
     args.pileup_path = PileupFile == "Empty" ? nullptr : PileupFile.c_str();
-    args.bam_path = BamFile == "Empty" ? nullptr : BamFile.c_str();       // needs an htslib build (bam_flatten.cpp)
+    args.bam_path = BamFile == "Empty" ? nullptr : BamFile.c_str();       // the built-in reader (bam_flatten.cpp)
     args.reference_path = RefPath.c_str();
     args.known_af_path = knownAF == "Empty" ? nullptr : knownAF.c_str();
     args.output_prefix = outputPrefix.c_str();
@@ -381,6 +386,18 @@ int main(int argc, char** argv)
     if (args.mpileup.given && BamFile == "Empty")
         std::fprintf(stderr, "NOTICE - pileup options (--min-BQ, --min-MQ, ...) apply to --BamFile input only; "
                              "the text pileup is taken as it is (as in the reference)\n");
+    if (BamFile != "Empty" && PileupFile == "Empty") {
+        // what the built-in reader leaves out of the reference's pileup (both need htslib's HMM and the FASTA)
+        const int effFlags = args.mpileup.given ? inclFlags : (16 | 1024), effCap = args.mpileup.given ? adjustMQ : 40;
+        if (effFlags & 16)
+            std::fprintf(stderr, "NOTICE - --BamFile: base alignment quality (BAQ, --incl-flags bit 16) is not applied by the built-in "
+                                 "BAM reader; the reference computes the same with --incl-flags 1024 --adjust-MQ 0\n");
+        if (effCap > 10)
+            std::fprintf(stderr, "NOTICE - --BamFile: the mapping quality cap (--adjust-MQ %d) is not applied by the built-in BAM "
+                                 "reader; the reference computes the same with --incl-flags 1024 --adjust-MQ 0\n", effCap);
+        std::fprintf(stderr, "NOTICE - --BamFile: the reference base of a site is the panel's REF allele (.bed); --Reference is not read\n");
+        if (nthread > 4) vb2_debug_set_tunable("bam_threads", nthread);       // --NumThread above its default: the reader's pool
+    }
     args.model.is_heter = !withinAncestry;
     args.model.epsilon = epsilon;
     args.model.verbose = verbose;

@@ -93,12 +93,17 @@ int read_ud(const std::string& path, Panel* p);
 int read_mean(const std::string& path, Panel* p);
 int read_known_af(const std::string& path, Panel* p);
 int read_pileup(const std::string& path, const Panel& panel, PileupViewer* v);
-// BAM/CRAM input through htslib (bam_flatten.cpp; VB2_ERR_IO with an explanation when the library was
-// built without htslib).  SimplePileupViewer.cpp:172-557 with main.cpp:81-96's defaults.
-// mp: the reference's "Pileup Options" (main.cpp:176-187), nullptr or given == 0 = its defaults (main.cpp:81-96)
+// BAM input (bam_flatten.cpp): the built-in reader -- BGZF, header, .bai and records on the host (bam_io.cpp), the pileup
+// on `device` (bam_pileup_kernels.hip) --, or htslib's where the library was configured with
+// VB2_WITH_HTSLIB.  SimplePileupViewer.cpp:172-557 with main.cpp:81-96's defaults, less BAQ and the mapQ cap.
+// mp: the reference's "Pileup Options" (main.cpp:176-187), nullptr or given == 0 = its defaults (main.cpp:81-96);
+// stats (may be null): what vb2_flat_bam_stats reports.  The file and its index are opened before any device is touched.
 int read_bam(const std::string& bam_path, const std::string& ref_path, const Panel& panel, PileupViewer* v,
-             const vb2_mpileup_opts* mp = nullptr);
+             const vb2_mpileup_opts* mp = nullptr, int device = -1, vb2_bam_stats* stats = nullptr);
 bool bam_support();
+// the host stage alone over the markers of a .bed (vb2_bam_scan): the fetched records' virtual offsets, ascending
+int bam_scan_file(const std::string& bam_path, const std::string& bed_path, std::vector<uint64_t>* voffsets, vb2_bam_stats* stats,
+                  std::string* sample);
 bool sanity_check(const Panel& p, PileupViewer* v);
 
 }  // namespace vb2
@@ -118,6 +123,8 @@ struct vb2_flat {
     std::vector<double> known_af;
     int32_t num_site = 0;
     bool sanity_disabled = true;
+    bool from_bam = false;                    // bam_stats holds the load's counts and times
+    vb2_bam_stats bam_stats{};
     vb2_input input{};
     void resolve();          // BuildResolvedMarkers -> input
 };

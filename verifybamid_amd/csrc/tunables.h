@@ -67,7 +67,10 @@ namespace vb2 {
     X(scalar_parse, 0)     /* 1: no AVX2 scanner */                                                                      \
     /* ---- diagnostics ---- */                                                                                         \
     X(debug_timing, 0)                                                                                                   \
-    X(debug_lockstep, 0)
+    X(debug_lockstep, 0)                                                                                                 \
+    /* ---- the built-in BAM reader (bam_flatten.cpp, bam_io.cpp) ---- */                                               \
+    X(bam_batch_kb, 65536) /* KiB of record bytes that go up to the device at a time (pinned staging of that size) */     \
+    X(bam_threads, 0)      /* host threads that inflate and walk: 0 = min(cpus, 16); --NumThread above 4 sets it */
 
 struct Tunables {
 #define VB2_X(name, dflt) int name = dflt;

@@ -21,7 +21,7 @@ def _dump_with_hash(obj, fp, **kw):
 
 
 json.dump = _dump_with_hash
-EVAL_KERNELS = ("llk_eval_kernel", "llk_eval_split_kernel")
+EVAL_KERNELS = ("llk_eval_kernel", "llk_eval_split")      # (llk_eval_split_kernel and llk_eval_split6_kernel)
 src, dst = os.path.join(ROOT, "gpurun_out", R), os.path.join(ROOT, "profiles", R)
 os.makedirs(dst, exist_ok=True)
 with open(os.path.join(src, "bench.json")) as f:
@@ -188,7 +188,7 @@ for aname, qlo, qhi in (("wide", 2, 60), ("mid", 10, 45)):
         if sq1 and gr:
             sub = "llk_eval_passes_kernel"          # (one launch of two passes of 24 points since round 4; VB2_PASSES=0: llk_eval_kernel x 3)
             if avg_of(gr, sub, "GRBM_GUI_ACTIVE") is None:
-                sub = "llk_eval_split_kernel"       # (round 6, probability domain: one launch, the groups split between workgroup pairs)
+                sub = "llk_eval_split"              # (round 6, probability domain: one launch, the groups split between sets of workgroups -- llk_eval_split_kernel, llk_eval_split6_kernel)
             if avg_of(gr, sub, "GRBM_GUI_ACTIVE") is None:
                 sub = "llk_eval_kernel"
             cyc = avg_of(gr, sub, "GRBM_GUI_ACTIVE") / 8.0

@@ -207,6 +207,9 @@ int vb2_debug_layout_digest(vb2_ctx* ctx, unsigned long long* digest)
     return ctx->impl->layout_digest(digest);
 }
 
+// Test aid (not part of the public header): split launches of this process in sets of `ways` workgroups (-1: no such sets).
+long long vb2_debug_split_launches(int ways) { return vb2::split_launches(ways); }
+
 int vb2_debug_read_stamps(vb2_ctx* ctx, unsigned long long* out, int max_blocks)
 {
     if (guard_ctx(ctx)) return 0;

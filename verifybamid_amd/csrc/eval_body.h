@@ -565,7 +565,10 @@ __host__ __device__ __forceinline__ bool eval_is_dynamic(const DeviceLayout& L, 
 // half of the groups, 2v + 1 the second, both over the tiles of the VIRTUAL blocks v and v + grid / 2, i.e. over exactly the
 // tiles two workgroups of a plain launch own.  A tile's product still has its own slot, a virtual block's slots are
 // multiplied in the same order and its sum goes to the same word of the partial sums as in a plain launch of this grid:
-// the same bits, and no second pass over the tiles (llk_eval_passes_kernel: +4 us per pass at C3).
+// the same bits, and no second pass over the tiles (llk_eval_passes_kernel: +4 us per pass at C3).  In general SPLIT = S
+// workgroups make a set: workgroup S v + j takes share j of the groups over the tiles of the virtual blocks v + i * grid / S.
+// S = kMaxGroups (a launch of six groups on a grid that is a multiple of six): every workgroup has exactly ONE group -- half the
+// table entries per workgroup of S = 3, no group arithmetic per item (ONEGRP), the same items, slots and sums.
 //
 // A kernel's configuration of the body: a type that derives from EvalConfig, names its MODE and sets what differs (the members
 // are explained above; W16: the cohort steps' 16-bit run lists / 8-bit step lists).
@@ -592,10 +595,13 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
     static_assert(!PD || ESH == 8, "probability-domain contexts have no exp table");
     static_assert(!(PD && W16) || ((MODE == 4 || MODE == 5) && STREAM), "8-bit step lists: cohort steps of one and two points");
     static_assert(!SPLIT || (PD && MODE == 2 && QUEUE == 1 && !STREAM && !LCACHE), "split launches: the 8-point shape on the queue");
+    static_assert(SPLIT == 0 || SPLIT == 2 || SPLIT == 3 || SPLIT == kMaxGroups, "sets of two, three or kMaxGroups workgroups");
+    static_assert(SPLIT + 1 <= kTicketScratchWord, "a ticket per share and one word to count the shares");
     constexpr int OSH = PD ? 1 : 0;             // a workgroup owns pairs of neighbouring micro-tiles (owned_tile)
     // the launch is known to carry ONE group of points (every shape but the 8-point one always does; cohort steps too):
     // the group loops and the item -> (group, unit) division go at compile time
-    constexpr bool ONEGRP = MODE != 2 || STREAM;
+    // (SPLIT == 6: the launcher takes sets of six only for launches of six groups -- a workgroup has exactly one)
+    constexpr bool ONEGRP = MODE != 2 || STREAM || SPLIT == kMaxGroups;
     constexpr int KAF = KSEL > 0 ? 0 : -1;      // 0: no known-AF column, known at compile time
     constexpr int BTL = MODE == 4 ? 1 : 2;
     constexpr int TPW = MODE == 3 ? 2 : (MODE == 4 || MODE == 5) ? 4 : 1;   // micro-tiles per wave
@@ -714,13 +720,14 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
     // wait at a barrier for the staged rows and records to be read back (the resident kernel's early_table, for launches of
     // many groups).  The same numbers into the same expressions.
     constexpr int kTabSide = 3;                       // groups whose entries a thread builds side by side (see the table loop)
+    constexpr int kTabN = ONEGRP ? 1 : kTabSide;      // ... of which a workgroup with one group has one
     const int ntab_split = (kAblate & kAblNoTable) ? 0 : (PD ? l_num_prim() - L.num_pair : l_num_prim()) * 6 * NP;
     auto table_inputs = [&](int e, int g0, double2& rec_o, double* al_o) {
         const int pi = e / (6 * NP);
         const int bb = (e - pi * (6 * NP)) / 6;
         rec_o = L.prim[pi];
 #pragma unroll
-        for (int u = 0; u < kTabSide; ++u) {
+        for (int u = 0; u < kTabN; ++u) {
             const int ge = g0 + u < ngrp ? g0 + u : ngrp - 1;
             const int b = ge * NP + bb;
             const int idx = (p_off + b < num_valid ? p_off + b : num_valid - 1) * stride + 2 * k;
@@ -788,7 +795,7 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
         // (the loop below on inputs that are in registers: the next step's are requested before this step's entries are computed)
         int e = ptid, g0 = 0;
         while (e < ntab_split) {
-            int e_n = e, g0_n = g0 + kTabSide;
+            int e_n = e, g0_n = g0 + kTabN;
             if (g0_n >= ngrp) {
                 g0_n = 0;
                 e_n = e + pnthread;
@@ -807,7 +814,7 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
             double v3[kTabSide], r3[kTabSide];
             double* cell3[kTabSide];
 #pragma unroll
-            for (int u = 0; u < kTabSide; ++u) {
+            for (int u = 0; u < kTabN; ++u) {
                 const int ge = g0 + u < ngrp ? g0 + u : ngrp - 1;      // (past the last group: the last one again, the same values)
                 v3[u] = prob_entry(tin_al[u], tin_rec.x, g1, g2);
                 r3[u] = v3[u];
@@ -817,7 +824,7 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
             const int kq = twin & 0xff, pstride = RS * (int)(int8_t)(twin >> 8);
             for (int n = 1; n < kq; ++n) {
 #pragma unroll
-                for (int u = 0; u < kTabSide; ++u) {
+                for (int u = 0; u < kTabN; ++u) {
                     r3[u] *= v3[u];
                     cell3[u] += pstride;
                     *cell3[u] = r3[u];
@@ -825,7 +832,7 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
             }
             tin_rec = rec_n;
 #pragma unroll
-            for (int u = 0; u < kTabSide; ++u) tin_al[u] = al_n[u];
+            for (int u = 0; u < kTabN; ++u) tin_al[u] = al_n[u];
             e = e_n;
             g0 = g0_n;
         }
@@ -951,7 +958,21 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
     const uint32_t nt_v0 = owned_count(OSH, (uint32_t)l_num_mt(), vb0, nblk);
     const uint32_t nt_v1 = SPLIT ? owned_count(OSH, (uint32_t)l_num_mt(), vb0 + vstep, nblk) : 0u;
     const uint32_t nt_v2 = SPLIT > 2 ? owned_count(OSH, (uint32_t)l_num_mt(), vb0 + 2u * vstep, nblk) : 0u;
-    auto nt_of = [&](uint32_t vs) { return vs == 0u ? nt_v0 : vs == 1u ? nt_v1 : nt_v2; };
+    // (more than three virtual blocks: owned_count does not grow with the block index and takes two neighbouring values over a
+    // grid, so the counts are nt_v0 for the first nv_full virtual blocks and the last one's for the rest -- two scalars and a
+    // compare, where an array of NVS counts indexed by the item's virtual block went to scratch memory)
+    uint32_t nv_full = 0u, nt_last = nt_v0;
+    if constexpr (NVS > 3) {
+#pragma unroll
+        for (int j = 0; j < NVS; ++j) {
+            nt_last = owned_count(OSH, (uint32_t)l_num_mt(), vb0 + (uint32_t)j * vstep, nblk);
+            nv_full += nt_last == nt_v0 ? 1u : 0u;
+        }
+    }
+    auto nt_of = [&](uint32_t vs) {
+        if constexpr (NVS > 3) return vs < nv_full ? nt_v0 : nt_last;
+        else return vs == 0u ? nt_v0 : vs == 1u ? nt_v1 : nt_v2;
+    };
     // (SPLIT: per virtual block, the largest -- virtual block vb0 has it: owned_count does not grow with the block index)
     const uint32_t ntile_blk = nt_v0;
     const size_t mp = L.m_pad;
@@ -1384,7 +1405,7 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
     // 5.86 -> 5.60 ms on one box (three alternating rounds; either workgroup kind alone: no gain -- the round ends with the
     // other kind), the control wave's SIMD with ONE item as before: no gain; tables for 13 items built by hand: the same 5.59-5.61.
     int deal_rank = hook_blk ? spare_rank : wave;
-    if (dyn && nwave == 16 && ONEGRP && nitem <= (uint32_t)(hook_blk ? 15 : 16)) {
+    if (dyn && nwave == 16 && ONEGRP && SPLIT == 0 && nitem <= (uint32_t)(hook_blk ? 15 : 16)) {
         const int n = (int)nitem, sd = wave & 3, sj = wave >> 2;
         int r;
         if (!hook_blk && n <= 8) r = sj == 0 ? sd : sj == 1 ? 7 - sd : n;

@@ -40,7 +40,7 @@ constexpr double kPdMaxBound = 900.0;      // binary orders of magnitude a marke
                                            // its (het, het) term's, a lower bound of the likelihood that no alpha or PC changes)
 // d_ticket of launch_llk_eval: kTicketWords zero-initialised unsigned ints -- [0, kTicketScratchWord) the arrival tickets of a
 // launch's passes (llk_eval_passes_kernel; a plain launch uses [0]; a split launch of `ways` shares uses [0, ways) for the
-// shares and [ways] to count the shares that are added up), two words from kTicketScratchWord on a scratch flag
+// shares and [ways] to count the shares that are added up: seven words at six ways), two words from kTicketScratchWord on a scratch flag
 constexpr int kTicketScratchWord = 8, kTicketWords = 16;
 constexpr int kInlinePointDoubles = 96;    // parameter rows that travel as kernel arguments (768 B)
 
@@ -213,6 +213,8 @@ hipError_t launch_llk_eval(const DeviceLayout& L, int num_point, const double* d
                            unsigned long long* tag_counter, hipStream_t stream,
                            int reduce_override = 0,      // 1 ticket / 2 tagged for this call only
                            ScheduleProvider* sched = nullptr);
+// (test aid) split launches this process has made in sets of `ways` workgroups (2, 3 or kMaxGroups)
+long long split_launches(int ways);
 
 // A cohort step's point counts and parameter rows as kernel arguments (count = doubles valid in v; 0 = the kernel reads
 // d_num_valid / d_points): rows of sample s at v[s * np * (2k+1) ..)

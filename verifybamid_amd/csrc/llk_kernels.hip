@@ -55,6 +55,18 @@ llk_eval_split_kernel(const DeviceLayout L, const double* __restrict__ points, i
                                   Schedule{nullptr, nullptr});
 }
 
+// ... in sets of kMaxGroups workgroups, one point group apiece (eval_body, SPLIT == kMaxGroups): launches of kMaxGroups groups
+template <int KSEL>
+__global__ void __launch_bounds__(Geom<2>::kMaxWaves * 64, Geom<2>::kWavesPerSimd)
+llk_eval_split6_kernel(const DeviceLayout L, const double* __restrict__ points, int num_valid, double* __restrict__ partials,
+                       double* __restrict__ llk_out, unsigned int* __restrict__ ticket, unsigned long long* __restrict__ done_flag,
+                       unsigned long long done_seq, int ngrp)
+{
+    eval_body<SplitEval<KSEL, kMaxGroups>>(L, nullptr, 0, points, num_valid, partials, llk_out, ticket, done_flag,
+                                           done_seq, blockIdx.x, gridDim.x, nullptr, 0u, ngrp, 0ull,
+                                           Schedule{nullptr, nullptr});
+}
+
 #include "resident_kernel.inc"
 
 // Sums the per-block partials in a fixed order -> bitwise reproducible: wave w takes
@@ -114,7 +126,8 @@ LaunchGeom launch_geom(const DeviceLayout& L, int btl, int ngrp)
     if (L.pd && grid > (L.num_mt >> 1)) grid = L.num_mt >> 1 > 0 ? L.num_mt >> 1 : 1;      // (a workgroup owns pairs of tiles)
     // A dictionary whose tables of a full launch (kMaxGroups groups) do not fit PAIRS of workgroups is split three ways
     // (eval_body, SPLIT): the grid -- the same for every launch kind of the context, so that a point's sum is the same bits in
-    // all of them -- is then a multiple of 6 (256 CUs: 252 workgroups)
+    // all of them -- is then a multiple of 6 (256 CUs: 252 workgroups).  (The rule asks about pairs and nothing else: that sets
+    // of six exist -- split_ways -- does not enter, the grid of a context is what it was before them.)
     if (L.pd && grid >= 12 && split_shmem(L, grid & ~1, max_waves, kMaxGroups, 2) > (size_t)kLdsLimitBytes)
         grid -= grid % 6;
     // Several point groups: a workgroup's work items are (tile, group) pairs, so a small sample -- a marker shard
@@ -220,9 +233,17 @@ static size_t split_shmem(const DeviceLayout& L, int grid, int block_waves, int 
     const size_t slots1 = (size_t)owned_most(1, (uint32_t)L.num_mt, (uint32_t)(grid >= 1 ? grid : 1)) * per;
     return eval_shmem_np(L, 8, grid >= 1 ? grid : 1, block_waves, (int)per) + sizeof(double) * ((size_t)(ways - 1) * 2 * slots1 * 8 + (size_t)(ways - 1) * 8 * per);
 }
-// ways of a split launch of ngrp groups: the fewest workgroups per set whose tables fit (0: none does)
-static int split_ways(const DeviceLayout& L, const LaunchGeom& gm, int ngrp)
+// ways of a split launch of ngrp groups (0: none fits).  Sets of kMaxGroups workgroups with ONE group apiece where a launch
+// has that many groups, the grid divides, the LDS holds it and the set's items fit the queue -- the same items, slots and sums
+// as three ways, half the table entries per workgroup; else the fewest workgroups per set whose tables fit.
+// max_ways: 3 = what the dictionary and the grid are sized on (pd_row_budget, launch_geom), Tunables::split = 3.
+static int split_ways(const DeviceLayout& L, const LaunchGeom& gm, int ngrp, int max_ways = kMaxGroups)
 {
+    constexpr int kSix = kMaxGroups;
+    if (max_ways >= kSix && tunables().split == 1 && ngrp == kSix && gm.grid >= kSix && gm.grid % kSix == 0 &&
+        split_shmem(L, gm.grid, gm.block_waves, ngrp, kSix) <= (size_t)kLdsLimitBytes &&
+        (uint32_t)kSix * owned_most(1, (uint32_t)L.num_mt, (uint32_t)gm.grid) <= (uint32_t)(L.dyn_limit * gm.block_waves))
+        return kSix;
     for (int ways = 2; ways <= 3; ++ways) {
         if (gm.grid < ways || gm.grid % ways || (ways == 3 && tunables().split == 2)) continue;
         const int per = (ngrp + ways - 1) / ways;
@@ -231,6 +252,9 @@ static int split_ways(const DeviceLayout& L, const LaunchGeom& gm, int ngrp)
     }
     return 0;
 }
+
+// (test aid: split launches of this process by their ways -- vb2_debug_split_launches)
+static std::atomic<long long> g_split_launches[kMaxGroups + 1];
 
 // see eval_body, SPLIT.  *taken = false: the geometry does not allow it (the caller falls back to passes / several launches)
 static hipError_t launch_split(const DeviceLayout& L, const double* d_points, int num_valid, double* d_partials, double* d_out,
@@ -249,7 +273,11 @@ static hipError_t launch_split(const DeviceLayout& L, const double* d_points, in
     if (tiles_set * (uint32_t)((ngrp + ways - 1) / ways) > (uint32_t)(L.dyn_limit * gm.block_waves)) return hipSuccess;
     const size_t shmem = split_shmem(L, gm.grid, gm.block_waves, ngrp, ways);
     const int ksel = L.known_af == nullptr ? (L.num_pc == 4 ? 4 : L.num_pc == 2 ? 2 : 0) : 0;
-    const void* fn = ways == 2 ? (ksel == 4 ? reinterpret_cast<const void*>(&llk_eval_split_kernel<4, 2>)
+    const void* fn = ways == kMaxGroups
+                         ? (ksel == 4 ? reinterpret_cast<const void*>(&llk_eval_split6_kernel<4>)
+                            : ksel == 2 ? reinterpret_cast<const void*>(&llk_eval_split6_kernel<2>)
+                                        : reinterpret_cast<const void*>(&llk_eval_split6_kernel<0>))
+                     : ways == 2 ? (ksel == 4 ? reinterpret_cast<const void*>(&llk_eval_split_kernel<4, 2>)
                                   : ksel == 2 ? reinterpret_cast<const void*>(&llk_eval_split_kernel<2, 2>)
                                               : reinterpret_cast<const void*>(&llk_eval_split_kernel<0, 2>))
                                : (ksel == 4 ? reinterpret_cast<const void*>(&llk_eval_split_kernel<4, 3>)
@@ -263,7 +291,13 @@ static hipError_t launch_split(const DeviceLayout& L, const double* d_points, in
     unsigned long long a_seq = done_seq;
     void* args[] = {&Lc, &a_points, &a_nv, &d_partials, &d_out, &d_ticket, &done_flag, &a_seq, &a_ngrp};
     *taken = true;
+    g_split_launches[ways].fetch_add(1, std::memory_order_relaxed);
     return hipLaunchKernel(fn, dim3(gm.grid), dim3(gm.block_waves * 64), args, shmem, stream);
+}
+
+long long split_launches(int ways)
+{
+    return ways >= 0 && ways <= kMaxGroups ? g_split_launches[ways].load(std::memory_order_relaxed) : -1;
 }
 
 hipError_t launch_llk_eval(const DeviceLayout& L, int num_point, const double* d_points,
@@ -368,7 +402,9 @@ int pd_row_budget(int num_marker, int num_pc, int num_cu)
     for (int rows = kMaxWideCodes; rows > 1; --rows) {
         T.num_code = T.num_prim = rows;
         const LaunchGeom gm = launch_geom(T, 2, kMaxGroups);
-        const int ways = split_ways(T, gm, kMaxGroups);
+        // (priced on at most THREE ways, whatever a launch then takes: on six the budget would grow, every probability-domain
+        // context would get another dictionary and every value other bits)
+        const int ways = split_ways(T, gm, kMaxGroups, 3);
         const size_t need = (tunables().split != 0 && ways >= 2) ? split_shmem(T, gm.grid, gm.block_waves, kMaxGroups, ways)
                                   : eval_shmem_np(T, 8, gm.grid, gm.block_waves, kMaxGroups);
         if (need <= (size_t)kLdsLimitBytes) return rows;

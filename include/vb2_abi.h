@@ -925,6 +925,60 @@ int64_t vb2_bam_scan_records(const vb2_bam_scan_result *scan, uint64_t *voffset,
 const char *vb2_bam_scan_sample(const vb2_bam_scan_result *scan);
 void vb2_bam_scan_free(vb2_bam_scan_result *scan);
 
+/* ---- per read group (--PerReadGroup) ----
+ * The header's @RG lines, in header order and identified by ID:, are the groups of a BAM; a record belongs to the group its
+ * RG field of type Z names, and to none without one, with an RG of another type or with an ID the header lacks.  Two
+ * lines with one ID, a line without ID:, more than 65 535 lines, and groups x panel positions beyond 2^31 - 2 are
+ * VB2_ERR_INVALID; so is an auxiliary field that does not fit its record, with the record's virtual offset in the message.
+ * A group's pileup: the whole sample's site after the read filters, --max-depth and the mate-overlap rule, restricted to
+ * the group's reads, then --min-BQ, the characters and the deletion quirk as for any site.
+ *
+ * vb2_bam_scan with flags: VB2_BAM_SCAN_GROUPS also parses the @RG lines and walks every kept record's auxiliary fields
+ * (without it they are not looked at, and the three accessors below report no group).  No device. */
+#define VB2_BAM_SCAN_GROUPS 1u
+#define VB2_BAM_NO_GROUP 0xFFFFu
+int vb2_bam_scan_ex(const char *bam_path, const char *bed_path, uint32_t flags, vb2_bam_scan_result **out);
+int32_t vb2_bam_scan_num_group(const vb2_bam_scan_result *scan);
+const char *vb2_bam_scan_group_id(const vb2_bam_scan_result *scan, int32_t group);       /* NULL out of range */
+/* The kept records' group numbers (VB2_BAM_NO_GROUP = none), parallel to vb2_bam_scan_records: returns their number (0
+ * for a scan without VB2_BAM_SCAN_GROUPS), writes the first `capacity`. */
+int64_t vb2_bam_scan_record_groups(const vb2_bam_scan_result *scan, uint16_t *group, int64_t capacity);
+
+/* vb2_flat_load of args->bam_path (built-in reader; a pileup_path is VB2_ERR_INVALID) and, beside the whole sample's
+ * vb2_flat -- byte for byte what vb2_flat_load gives --, one vb2_flat per group over the same panel.  A group's status:
+ * VB2_OK, VB2_ERR_SANITY (its own marker sanity check failed; not run with disable_sanity) or VB2_GROUP_NO_BASE (no base at
+ * any marker).  Return codes as vb2_flat_load's: with VB2_ERR_SANITY for the whole sample both handles are still set; a
+ * valid BAM without a GPU is VB2_ERR_NO_DEVICE after the file and its index were opened. */
+#define VB2_GROUP_NO_BASE 1
+typedef struct vb2_flat_groups vb2_flat_groups;
+int vb2_flat_load_groups(const vb2_run_args *args, vb2_flat **whole, vb2_flat_groups **groups);
+int32_t vb2_flat_groups_count(const vb2_flat_groups *g);
+const char *vb2_flat_groups_id(const vb2_flat_groups *g, int32_t group);                 /* NULL out of range */
+int64_t vb2_flat_groups_records(const vb2_flat_groups *g, int32_t group);                /* kept records naming it */
+int32_t vb2_flat_groups_status(const vb2_flat_groups *g, int32_t group);
+/* usable with vb2_flat_input and vb2_flat_stats; owned by the handle */
+const vb2_flat *vb2_flat_groups_flat(const vb2_flat_groups *g, int32_t group);
+int64_t vb2_flat_groups_unassigned(const vb2_flat_groups *g);                            /* kept records of no group */
+/* what the groups' part of the load took beside the whole sample's vb2_bam_stats: second keys, second sort and sites on the
+ * device; pools back and sites added on the host */
+int vb2_flat_groups_seconds(const vb2_flat_groups *g, double *seconds_device, double *seconds_copyback);
+void vb2_flat_groups_free(vb2_flat_groups *g);
+
+/* vb2_run for the whole sample -- the same stdout, .selfSM, .Ancestry and .Pileup -- and then FREEMIX of every group under
+ * the same model, the groups searched in lock-step in batches of at most 64 (vb2_batch_optimize_llk).  A group whose
+ * status is not VB2_OK is not searched.  Writes <output_prefix>.selfRG (.selfSM's header; per group SEQ_ID = its SM: or the
+ * sample, RG = its ID, #READS = its bases, FREEMIX / FREELK1 / FREELK0 "NA" when not searched) and, with output_pileup,
+ * <output_prefix>.RG<header index>.Pileup per group.  group_results: the first `capacity` groups; *num_group: how many
+ * the header has.  One device, no vb2_search_opts variants: VB2_ERR_INVALID otherwise, before any file is read. */
+typedef struct vb2_group_result {
+    vb2_run_result run;         /* est is zero for a group that was not searched */
+    int32_t status;             /* as vb2_flat_groups_status */
+    int32_t header_index;       /* 0-based @RG line */
+    int64_t records;
+} vb2_group_result;
+int vb2_run_read_groups(const vb2_run_args *args, vb2_run_result *whole, int32_t capacity, vb2_group_result *group_results,
+                        int32_t *num_group);
+
 /* ------------------------------------------------------------------------- *
  * 4. Reference-panel builder: --RefVCF (main.cpp:233-257, SVDcalculator::
  *    ProcessRefVCF, SVDcalculator.cpp:363-400).  The kept markers' genotypes

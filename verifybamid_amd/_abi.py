@@ -123,6 +123,16 @@ class BamStats(C.Structure):
                [(n, C.c_double) for n in ("seconds_index", "seconds_inflate", "seconds_device", "seconds_copyback")]
 
 
+VB2_BAM_SCAN_GROUPS = 1
+VB2_BAM_NO_GROUP = 0xFFFF
+VB2_GROUP_NO_BASE = 1
+
+
+class GroupResult(C.Structure):
+    """vb2_group_result: one read group of vb2_run_read_groups."""
+    _fields_ = [("run", RunResult), ("status", C.c_int32), ("header_index", C.c_int32), ("records", C.c_int64)]
+
+
 class CohortArgs(C.Structure):
     _fields_ = [
         ("base", RunArgs), ("num_sample", C.c_int32), ("pileup_paths", C.POINTER(C.c_char_p)),
@@ -246,6 +256,9 @@ SYMBOLS = [
     "vb2_paired_info_get", "vb2_paired_lockstep", "vb2_cohort_run_paired", "vb2_matched_normal_read",
     "vb2_cohort_run_paired_intervals", "vb2_paired_derivs", "vb2_paired_derivs_sets", "vb2_paired_interval", "vb2_paired_intervals_lockstep",
     "vb2_flat_bam_stats", "vb2_bam_scan", "vb2_bam_scan_stats", "vb2_bam_scan_records", "vb2_bam_scan_sample", "vb2_bam_scan_free",
+    "vb2_bam_scan_ex", "vb2_bam_scan_num_group", "vb2_bam_scan_group_id", "vb2_bam_scan_record_groups",
+    "vb2_flat_load_groups", "vb2_flat_groups_count", "vb2_flat_groups_id", "vb2_flat_groups_records", "vb2_flat_groups_status",
+    "vb2_flat_groups_flat", "vb2_flat_groups_unassigned", "vb2_flat_groups_seconds", "vb2_flat_groups_free", "vb2_run_read_groups",
 ]
 
 _lib = None
@@ -311,6 +324,30 @@ def lib():
     L.vb2_bam_scan_sample.restype = C.c_char_p
     L.vb2_bam_scan_free.argtypes = [C.c_void_p]
     L.vb2_bam_scan_free.restype = None
+    L.vb2_bam_scan_ex.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.vb2_bam_scan_num_group.argtypes = [C.c_void_p]
+    L.vb2_bam_scan_num_group.restype = C.c_int32
+    L.vb2_bam_scan_group_id.argtypes = [C.c_void_p, C.c_int32]
+    L.vb2_bam_scan_group_id.restype = C.c_char_p
+    L.vb2_bam_scan_record_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.vb2_bam_scan_record_groups.restype = C.c_int64
+    L.vb2_flat_load_groups.argtypes = [C.POINTER(RunArgs), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.vb2_flat_groups_count.argtypes = [C.c_void_p]
+    L.vb2_flat_groups_count.restype = C.c_int32
+    L.vb2_flat_groups_id.argtypes = [C.c_void_p, C.c_int32]
+    L.vb2_flat_groups_id.restype = C.c_char_p
+    L.vb2_flat_groups_records.argtypes = [C.c_void_p, C.c_int32]
+    L.vb2_flat_groups_records.restype = C.c_int64
+    L.vb2_flat_groups_status.argtypes = [C.c_void_p, C.c_int32]
+    L.vb2_flat_groups_status.restype = C.c_int32
+    L.vb2_flat_groups_flat.argtypes = [C.c_void_p, C.c_int32]
+    L.vb2_flat_groups_flat.restype = C.c_void_p
+    L.vb2_flat_groups_unassigned.argtypes = [C.c_void_p]
+    L.vb2_flat_groups_unassigned.restype = C.c_int64
+    L.vb2_flat_groups_seconds.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.vb2_flat_groups_free.argtypes = [C.c_void_p]
+    L.vb2_flat_groups_free.restype = None
+    L.vb2_run_read_groups.argtypes = [C.POINTER(RunArgs), C.POINTER(RunResult), C.c_int32, C.POINTER(GroupResult), C.POINTER(C.c_int32)]
     L.vb2_batch_create.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p)]
     L.vb2_batch_destroy.argtypes = [C.c_void_p]
     L.vb2_batch_destroy.restype = None

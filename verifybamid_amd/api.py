@@ -1123,20 +1123,43 @@ def _set_bam(args, bam_path, mpileup):
 
 def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_sanity=False,
               known_af_path=None, device=-1, output_pileup=False, devices=None, confidence_interval=False,
-              per_chromosome=False, bootstrap=0, bam_path=None, mpileup=None, **model_kw):
+              per_chromosome=False, bootstrap=0, bam_path=None, mpileup=None, per_read_group=False, **model_kw):
     """The --SVDPrefix/--PileupFile flow of execute() (vb2_run); devices=[a, b, ...] shards the
     sample's markers over those GPUs.  confidence_interval: vb2_run_interval (<output_prefix>.CI, and an
     `interval` entry in the result).  per_chromosome / bootstrap=N (seeded by seed=): vb2_run_replicates
     (<output_prefix>.Chrom / .Boot, and a `replicates` entry with the jackknife and bootstrap summaries).
     bam_path (with pileup_path=None): --BamFile through the built-in reader; mpileup: a dict of the reference's pileup
-    options (min_bq, min_mq, adjust_mq, max_depth, no_orphans, incl_flags, excl_flags), None = its defaults."""
+    options (min_bq, min_mq, adjust_mq, max_depth, no_orphans, incl_flags, excl_flags), None = its defaults.
+    per_read_group (with bam_path): vb2_run_read_groups -- the whole sample as ever, <output_prefix>.selfRG, and a
+    `read_groups` list in the result: per @RG line of the header its id, status (0, VB2_ERR_SANITY or 1 = no base), records,
+    the estimate's entries (zero when not searched) and num_site, num_bases, avg_depth."""
     args, keep = _run_args(svd_prefix, pileup_path, num_pc, disable_sanity, known_af_path,
                            output_prefix, device, output_pileup, devices=devices, **model_kw)
     _set_bam(args, bam_path, mpileup)
     res = _abi.RunResult()
     ci = _abi.Interval() if confidence_interval else None
     summary = None
-    if per_chromosome or bootstrap:
+    groups = None
+    if per_read_group:
+        if confidence_interval or per_chromosome or bootstrap:
+            raise ValueError("per_read_group cannot be combined with confidence_interval, per_chromosome or bootstrap")
+        L = _abi.lib()
+        n = C.c_int32(0)
+        cap = 64
+        while True:
+            buf = (_abi.GroupResult * cap)()
+            _abi.check(L.vb2_run_read_groups(C.byref(args), C.byref(res), cap, buf, C.byref(n)), "vb2_run_read_groups")
+            if n.value <= cap:
+                break
+            cap = n.value                     # (a header of more than 64 groups: once more with room for all)
+        groups = []
+        for g in buf[:n.value]:
+            d = _estimate_dict(g.run.est, num_pc)
+            d.update(status=int(g.status), header_index=int(g.header_index), records=int(g.records), num_site=g.run.num_site,
+                     num_bases=int(g.run.num_bases), avg_depth=g.run.avg_depth, searched=g.status == _abi.VB2_OK,
+                     seconds_optimize=g.run.seconds_optimize)
+            groups.append(d)
+    elif per_chromosome or bootstrap:
         if confidence_interval:
             raise ValueError("per_chromosome / bootstrap cannot be combined with confidence_interval")
         summary = _abi.ReplicateSummary()
@@ -1151,6 +1174,8 @@ def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_san
         out["interval"] = _interval_dict(ci)
     if summary is not None:
         out["replicates"] = {name: getattr(summary, name) for name, _ in _abi.ReplicateSummary._fields_}
+    if groups is not None:
+        out["read_groups"] = groups
     out.update(num_marker=res.num_marker, num_site=res.num_site, num_bases=int(res.num_bases),
                avg_depth=res.avg_depth, sd_depth=res.sd_depth, seconds_load=res.seconds_load,
                seconds_optimize=res.seconds_optimize)
@@ -1182,20 +1207,74 @@ def load_bam(svd_prefix, bam_path, num_pc=2, mpileup=None, device=-1, disable_sa
         L.vb2_flat_free(h)
 
 
-def bam_scan(bam_path, bed_path):
+def _flat_bam_dict(L, h):
+    """read_off, bases, quals, num_site, num_bases, avg_depth of a vb2_flat"""
+    inp = L.vb2_flat_input(h).contents
+    M = inp.num_marker
+    off = np.ctypeslib.as_array(C.cast(inp.read_off, C.POINTER(C.c_int64)), shape=(M + 1,)).copy()
+    n = int(off[M])
+    res = _abi.RunResult()
+    _abi.check(L.vb2_flat_stats(h, C.byref(res)), "vb2_flat_stats")
+    return dict(read_off=off, bases=C.string_at(inp.bases, n) if n else b"", quals=C.string_at(inp.quals, n) if n else b"",
+                num_site=res.num_site, num_bases=int(res.num_bases), avg_depth=res.avg_depth)
+
+
+def load_bam_groups(svd_prefix, bam_path, num_pc=2, mpileup=None, device=-1, disable_sanity=True, known_af_path=None):
+    """vb2_flat_load_groups: the whole sample's dict as load_bam returns it, plus `groups` -- a list with one such dict (less
+    `stats`) per @RG line of the header with its `id`, `records` and `status` --, `unassigned`, the number of kept records
+    that belong to no group, and what the groups' part of the load took (groups_seconds_device, groups_seconds_copyback)."""
+    args, keep = _run_args(svd_prefix, None, num_pc, disable_sanity, known_af_path, None, device)
+    _set_bam(args, bam_path, mpileup)
+    L = _abi.lib()
+    h, hg = C.c_void_p(), C.c_void_p()
+    try:
+        _abi.check(L.vb2_flat_load_groups(C.byref(args), C.byref(h), C.byref(hg)), "vb2_flat_load_groups")
+        whole = _flat_bam_dict(L, h)
+        st = _abi.BamStats()
+        _abi.check(L.vb2_flat_bam_stats(h, C.byref(st)), "vb2_flat_bam_stats")
+        whole["stats"] = {name: getattr(st, name) for name, _ in _abi.BamStats._fields_}
+        groups = []
+        for g in range(L.vb2_flat_groups_count(hg)):
+            d = _flat_bam_dict(L, C.c_void_p(L.vb2_flat_groups_flat(hg, g)))
+            d.update(id=L.vb2_flat_groups_id(hg, g).decode(), records=int(L.vb2_flat_groups_records(hg, g)),
+                     status=int(L.vb2_flat_groups_status(hg, g)))
+            groups.append(d)
+        sd, sc = C.c_double(0), C.c_double(0)
+        L.vb2_flat_groups_seconds(hg, C.byref(sd), C.byref(sc))
+        whole.update(groups=groups, unassigned=int(L.vb2_flat_groups_unassigned(hg)), groups_seconds_device=sd.value,
+                     groups_seconds_copyback=sc.value)
+        return whole
+    finally:
+        if hg:
+            L.vb2_flat_groups_free(hg)
+        if h:
+            L.vb2_flat_free(h)
+
+
+def bam_scan(bam_path, bed_path, groups=False):
     """The built-in reader's host stage alone (vb2_bam_scan; no device): dict(voffsets -- the virtual offsets of the
-    records it would send to the device, ascending --, sample, stats)."""
+    records it would send to the device, ascending --, sample, stats).  groups=True (vb2_bam_scan_ex with
+    VB2_BAM_SCAN_GROUPS): also group_ids -- the header's @RG IDs in header order -- and record_groups, the records' group
+    numbers parallel to voffsets (0xFFFF = none)."""
     L = _abi.lib()
     h = C.c_void_p()
-    _abi.check(L.vb2_bam_scan(str(bam_path).encode(), str(bed_path).encode(), C.byref(h)), "vb2_bam_scan")
+    _abi.check(L.vb2_bam_scan_ex(str(bam_path).encode(), str(bed_path).encode(), _abi.VB2_BAM_SCAN_GROUPS if groups else 0,
+                                 C.byref(h)), "vb2_bam_scan")
     try:
         n = L.vb2_bam_scan_records(h, None, 0)
         v = np.zeros(max(n, 1), dtype=np.uint64)
         L.vb2_bam_scan_records(h, v.ctypes.data_as(C.c_void_p), n)
         st = _abi.BamStats()
         L.vb2_bam_scan_stats(h, C.byref(st))
-        return dict(voffsets=v[:n], sample=L.vb2_bam_scan_sample(h).decode(),
-                    stats={name: getattr(st, name) for name, _ in _abi.BamStats._fields_})
+        out = dict(voffsets=v[:n], sample=L.vb2_bam_scan_sample(h).decode(),
+                   stats={name: getattr(st, name) for name, _ in _abi.BamStats._fields_})
+        if groups:
+            ng = L.vb2_bam_scan_record_groups(h, None, 0)
+            g = np.zeros(max(ng, 1), dtype=np.uint16)
+            L.vb2_bam_scan_record_groups(h, g.ctypes.data_as(C.c_void_p), ng)
+            out["group_ids"] = [L.vb2_bam_scan_group_id(h, i).decode() for i in range(L.vb2_bam_scan_num_group(h))]
+            out["record_groups"] = g[:ng]
+        return out
     finally:
         L.vb2_bam_scan_free(h)
 

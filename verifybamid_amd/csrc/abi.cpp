@@ -27,6 +27,7 @@
 #include "hostio.h"
 #include "shard.h"
 #include "replicates.h"
+#include "read_groups.h"
 
 using vb2::set_error;
 
@@ -692,11 +693,32 @@ void vb2_shard_group_destroy(vb2_shard_group* g)
     delete g;
 }
 
-int vb2_flat_load(const vb2_run_args* a, vb2_flat** out)
+}  // extern "C"
+
+namespace {
+
+// A group's own sanity check (unless disabled), BuildResolvedMarkers and status, once the panel is complete.
+void finish_group(const vb2_run_args* a, size_t g, vb2_flat_groups* groups)
+{
+    vb2_flat& f = *groups->flat[g];
+    vb2_flat_groups::Info& gi = groups->info[g];
+    f.sanity_disabled = a->disable_sanity != 0;
+    f.from_bam = false;
+    gi.status = VB2_OK;
+    if (!f.sanity_disabled) {
+        std::fprintf(stderr, "NOTICE - Marker sanity check of read group %s:\n", gi.id.c_str());
+        if (!vb2::sanity_check(f.panel, &f.viewer)) gi.status = VB2_ERR_SANITY;
+    }
+    f.resolve();
+    if (gi.status == VB2_OK && (f.read_off.empty() || f.read_off.back() == 0)) gi.status = VB2_GROUP_NO_BASE;
+}
+
+// vb2_flat_load, and with groups != nullptr vb2_flat_load_groups
+int flat_load_impl(const vb2_run_args* a, vb2_flat** out, vb2_flat_groups* groups)
 {
     if (!a || !out || !a->ud_path || !a->mean_path || !a->bed_path || (!a->pileup_path && !a->bam_path) ||
-        a->num_pc < 1 || a->num_pc > VB2_MAX_PC) {
-        set_error("vb2_flat_load: invalid argument");
+        a->num_pc < 1 || a->num_pc > VB2_MAX_PC || (groups && (a->pileup_path || !a->bam_path))) {
+        set_error(groups ? "vb2_flat_load_groups: invalid argument (read groups are read from bam_path alone)" : "vb2_flat_load: invalid argument");
         return VB2_ERR_INVALID;
     }
     *out = nullptr;
@@ -730,6 +752,7 @@ int vb2_flat_load(const vb2_run_args* a, vb2_flat** out)
         std::string err_main = rc ? vb2::g_last_error : std::string(), err_pile;
         if (!rc) {
             rc_pile = a->pileup_path ? vb2::read_pileup(a->pileup_path, f->panel, &f->viewer)
+                      : groups       ? vb2::read_bam_groups(a->bam_path, f->panel_ptr, &f->viewer, &a->mpileup, a->device, &f->bam_stats, groups)
                                      : vb2::read_bam(a->bam_path, a->reference_path ? a->reference_path : "",
                                                      f->panel, &f->viewer, &a->mpileup, a->device, &f->bam_stats);
             if (rc_pile) err_pile = vb2::g_last_error;
@@ -749,6 +772,8 @@ int vb2_flat_load(const vb2_run_args* a, vb2_flat** out)
         if (rc_pile) { set_error(err_pile); return rc_pile; }
         f->sanity_disabled = a->disable_sanity != 0;
         if (!f->sanity_disabled && !vb2::sanity_check(f->panel, &f->viewer)) {
+            if (groups)
+                for (size_t g = 0; g < groups->flat.size(); ++g) finish_group(a, g, groups);
             set_error("Insufficient Available markers, check input bam depth distribution in "
                       "output pileup file after specifying --OutputPileup");
             f->resolve();
@@ -757,6 +782,8 @@ int vb2_flat_load(const vb2_run_args* a, vb2_flat** out)
         }
         const double tl_san = now_s();
         f->resolve();
+        if (groups)
+            for (size_t g = 0; g < groups->flat.size(); ++g) finish_group(a, g, groups);
         if (timing)
             std::fprintf(stderr, "vb2_flat_load: .bed %.1f ms, pileup %.1f ms, wait for .UD/.mu %.1f ms, "
                          "sanity %.1f ms, resolve %.1f ms\n", 1e3 * (tl_bed - tl0), 1e3 * (tl_pile - tl_bed),
@@ -765,6 +792,61 @@ int vb2_flat_load(const vb2_run_args* a, vb2_flat** out)
         return VB2_OK;
     });
 }
+
+}  // namespace
+
+extern "C" {
+
+int vb2_flat_load(const vb2_run_args* a, vb2_flat** out) { return flat_load_impl(a, out, nullptr); }
+
+int vb2_flat_load_groups(const vb2_run_args* a, vb2_flat** whole, vb2_flat_groups** groups)
+{
+    if (!groups || !whole) {
+        set_error("vb2_flat_load_groups: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    *groups = nullptr;
+    *whole = nullptr;
+    std::unique_ptr<vb2_flat_groups> g(new (std::nothrow) vb2_flat_groups());
+    if (!g) return VB2_ERR_NOMEM;
+    const int rc = flat_load_impl(a, whole, g.get());
+    if (*whole) *groups = g.release();
+    return rc;
+}
+
+int32_t vb2_flat_groups_count(const vb2_flat_groups* g) { return g ? (int32_t)g->info.size() : 0; }
+
+const char* vb2_flat_groups_id(const vb2_flat_groups* g, int32_t i)
+{
+    return g && i >= 0 && (size_t)i < g->info.size() ? g->info[(size_t)i].id.c_str() : nullptr;
+}
+
+int64_t vb2_flat_groups_records(const vb2_flat_groups* g, int32_t i)
+{
+    return g && i >= 0 && (size_t)i < g->info.size() ? g->info[(size_t)i].records : 0;
+}
+
+int32_t vb2_flat_groups_status(const vb2_flat_groups* g, int32_t i)
+{
+    return g && i >= 0 && (size_t)i < g->info.size() ? g->info[(size_t)i].status : (int32_t)VB2_ERR_INVALID;
+}
+
+const vb2_flat* vb2_flat_groups_flat(const vb2_flat_groups* g, int32_t i)
+{
+    return g && i >= 0 && (size_t)i < g->flat.size() ? g->flat[(size_t)i].get() : nullptr;
+}
+
+int64_t vb2_flat_groups_unassigned(const vb2_flat_groups* g) { return g ? g->unassigned : 0; }
+
+int vb2_flat_groups_seconds(const vb2_flat_groups* g, double* seconds_device, double* seconds_copyback)
+{
+    if (!g || !seconds_device || !seconds_copyback) return VB2_ERR_INVALID;
+    *seconds_device = g->seconds_device;
+    *seconds_copyback = g->seconds_copyback;
+    return VB2_OK;
+}
+
+void vb2_flat_groups_free(vb2_flat_groups* g) { delete g; }
 
 const vb2_input* vb2_flat_input(const vb2_flat* f) { return f ? &f->input : nullptr; }
 
@@ -796,21 +878,43 @@ struct vb2_bam_scan_result {
     std::vector<uint64_t> voffset;
     vb2_bam_stats stats;
     std::string sample;
+    std::vector<std::string> group_id;      // with VB2_BAM_SCAN_GROUPS
+    std::vector<uint16_t> group;            // ... parallel to voffset
 };
 
-int vb2_bam_scan(const char* bam_path, const char* bed_path, vb2_bam_scan_result** out)
+int vb2_bam_scan_ex(const char* bam_path, const char* bed_path, uint32_t flags, vb2_bam_scan_result** out)
 {
-    if (!bam_path || !bed_path || !out) {
+    if (!bam_path || !bed_path || !out || (flags & ~VB2_BAM_SCAN_GROUPS)) {
         set_error("vb2_bam_scan: invalid argument");
         return VB2_ERR_INVALID;
     }
     *out = nullptr;
     return vb2::guarded([&]() -> int {
         std::unique_ptr<vb2_bam_scan_result> s(new vb2_bam_scan_result());
-        if (int rc = vb2::bam_scan_file(bam_path, bed_path, &s->voffset, &s->stats, &s->sample)) return rc;
+        const bool want = (flags & VB2_BAM_SCAN_GROUPS) != 0;
+        if (int rc = vb2::bam_scan_file(bam_path, bed_path, &s->voffset, &s->stats, &s->sample, want ? &s->group_id : nullptr,
+                                        want ? &s->group : nullptr))
+            return rc;
         *out = s.release();
         return VB2_OK;
     });
+}
+
+int vb2_bam_scan(const char* bam_path, const char* bed_path, vb2_bam_scan_result** out) { return vb2_bam_scan_ex(bam_path, bed_path, 0, out); }
+
+int32_t vb2_bam_scan_num_group(const vb2_bam_scan_result* scan) { return scan ? (int32_t)scan->group_id.size() : 0; }
+
+const char* vb2_bam_scan_group_id(const vb2_bam_scan_result* scan, int32_t group)
+{
+    return scan && group >= 0 && (size_t)group < scan->group_id.size() ? scan->group_id[(size_t)group].c_str() : nullptr;
+}
+
+int64_t vb2_bam_scan_record_groups(const vb2_bam_scan_result* scan, uint16_t* group, int64_t capacity)
+{
+    if (!scan) return VB2_ERR_INVALID;
+    const int64_t n = (int64_t)scan->group.size();
+    for (int64_t i = 0; group && i < n && i < capacity; ++i) group[i] = scan->group[(size_t)i];
+    return n;
 }
 
 int vb2_bam_scan_stats(const vb2_bam_scan_result* scan, vb2_bam_stats* out)
@@ -847,7 +951,8 @@ int vb2_ctx_interval(vb2_ctx* ctx, const vb2_model* model, const vb2_estimate* e
 namespace {
 
 // vb2_run, and with ci != nullptr vb2_run_interval; hook (may be null): a stage on the run's context after the search
-int run_impl(const vb2_run_args* a, vb2_run_result* out, vb2_interval* ci, const vb2::RunHook* hook)
+// groups (may be null): loaded beside the whole sample (vb2_run_read_groups searches them afterwards)
+int run_impl(const vb2_run_args* a, vb2_run_result* out, vb2_interval* ci, const vb2::RunHook* hook, vb2_flat_groups* groups = nullptr)
 {
     if (!a || !out) {
         set_error("vb2_run: invalid argument");
@@ -874,7 +979,7 @@ int run_impl(const vb2_run_args* a, vb2_run_result* out, vb2_interval* ci, const
     if (notices) std::fprintf(stderr, "NOTICE - Starting phase: Load SVD reference data + Read pileup + Marker sanity check\n");
     {
         JoinGuard j_warm(warm);
-        rc = vb2_flat_load(a, &flat);
+        rc = flat_load_impl(a, &flat, groups);
     }
     if (notices) {
         std::fprintf(stderr, "NOTICE - Finished phase: Load SVD reference data + Read pileup + Marker sanity check  "
@@ -964,6 +1069,33 @@ int run_with_hook(const vb2_run_args* args, vb2_run_result* out, const RunHook& 
 extern "C" {
 
 int vb2_run(const vb2_run_args* a, vb2_run_result* out) { return run_impl(a, out, nullptr, nullptr); }
+
+int vb2_run_read_groups(const vb2_run_args* a, vb2_run_result* whole, int32_t capacity, vb2_group_result* group_results,
+                        int32_t* num_group)
+{
+    if (!a || !whole || !num_group || capacity < 0 || (capacity > 0 && !group_results)) {
+        set_error("vb2_run_read_groups: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    *num_group = 0;
+    if (!a->bam_path || a->pileup_path) {
+        set_error("--PerReadGroup needs --BamFile (and no --PileupFile): read groups are read from a BAM's header and RG:Z fields");
+        return VB2_ERR_INVALID;
+    }
+    if (a->devices && a->num_device > 1) {
+        set_error("--PerReadGroup takes one device: it cannot be combined with marker shards over several --Devices");
+        return VB2_ERR_INVALID;
+    }
+    if (a->search.num_start > 1 || a->search.line_search) {
+        set_error("--PerReadGroup cannot be combined with --NumStart / --LineSearch: the groups are searched in lock-step by the "
+                  "reference's optimiser");
+        return VB2_ERR_INVALID;
+    }
+    std::unique_ptr<vb2_flat_groups> groups(new (std::nothrow) vb2_flat_groups());
+    if (!groups) return VB2_ERR_NOMEM;
+    if (int rc = run_impl(a, whole, nullptr, nullptr, groups.get())) return rc;
+    return vb2::guarded([&]() -> int { return vb2::run_read_groups_stage(a, groups.get(), capacity, group_results, num_group); });
+}
 
 int vb2_run_interval(const vb2_run_args* a, vb2_run_result* out, vb2_interval* ci)
 {

@@ -240,9 +240,17 @@ int read_bam(const std::string& bam_path, const std::string& ref_path, const Pan
     return VB2_OK;
 }
 
+int read_bam_groups(const std::string&, const std::shared_ptr<Panel>&, PileupViewer*, const vb2_mpileup_opts*, int, vb2_bam_stats*,
+                    vb2_flat_groups*)
+{
+    set_error("--PerReadGroup: this library reads BAM through htslib (VB2_WITH_HTSLIB); read groups are the built-in reader's");
+    return VB2_ERR_INVALID;
+}
+
 bool bam_support() { return true; }
 
-int bam_scan_file(const std::string&, const std::string&, std::vector<uint64_t>*, vb2_bam_stats*, std::string*)
+int bam_scan_file(const std::string&, const std::string&, std::vector<uint64_t>*, vb2_bam_stats*, std::string*,
+                  std::vector<std::string>*, std::vector<uint16_t>*)
 {
     set_error("vb2_bam_scan: this library reads BAM through htslib (VB2_WITH_HTSLIB); the built-in reader's host stage is not in it");
     return VB2_ERR_INVALID;
@@ -259,7 +267,9 @@ int bam_scan_file(const std::string&, const std::string&, std::vector<uint64_t>*
 
 #include <algorithm>
 #include <chrono>
+#include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -317,12 +327,22 @@ struct DevList {
     ~DevList() { for (void* p : v) (void)hipFree(p); }
 };
 
+// groups x panel slots must fit the 32-bit virtual slot of the second sort's key, with the all-ones key behind them
+bool group_slots_fit(size_t num_group, size_t num_slot) { return (uint64_t)num_group * (uint64_t)num_slot <= 0x7ffffffeull; }
+
 // Stages 2 and 3: the scan's records up in batches, entries, sort, sites, pools back, the viewer filled.
+// groups (may be null; its flat[g]->viewer initialised): also every read group's sites, behind the
+// whole sample's and from the same sorted entries: the whole sample's launches and bytes are what they are without it.
 int device_pileup(const bamio::Scan& scan, const std::vector<std::vector<std::pair<int32_t, int32_t>>>& by_seq, const Panel& panel,
-                  const MplpConf& conf, int device, PileupViewer* v, vb2_bam_stats* stats)
+                  const MplpConf& conf, int device, PileupViewer* v, vb2_bam_stats* stats, vb2_flat_groups* groups = nullptr)
 {
     const double t0 = now_s();
     const int32_t num_slot = (int32_t)panel.num_slot();
+    const int32_t num_group = groups ? (int32_t)groups->flat.size() : 0;
+    if (!group_slots_fit((size_t)num_group, (size_t)num_slot)) {      // (read_bam_groups has said so already)
+        set_error("--PerReadGroup: read groups x panel positions exceed 2^31 - 2");
+        return VB2_ERR_INVALID;
+    }
     const int32_t n_ref = (int32_t)scan.ref_name.size();
     if (device >= 0) VB2_HIP(hipSetDevice(device));
     StreamHolder st;
@@ -383,6 +403,13 @@ int device_pileup(const bamio::Scan& scan, const std::vector<std::vector<std::pa
     VB2_HIP(hipHostMalloc(&h_data.p, batch_bytes, hipHostMallocDefault));
     VB2_HIP(hipHostMalloc(&h_desc.p, batch_rec * sizeof(bamio::RecordDesc), hipHostMallocDefault));
     VB2_HIP(hipHostMalloc(&h_total.p, sizeof(unsigned long long), hipHostMallocDefault));
+    Pinned h_grp;
+    Dev d_grp;
+    if (num_group > 0) {
+        VB2_HIP(hipHostMalloc(&h_grp.p, batch_rec * sizeof(uint16_t), hipHostMallocDefault));
+        VB2_HIP(hipMalloc(&d_grp.p, batch_rec * sizeof(uint16_t)));
+    }
+    uint16_t* const hg = static_cast<uint16_t*>(h_grp.p);
     Dev d_desc, d_count, d_offset, d_total;
     VB2_HIP(hipMalloc(&d_desc.p, batch_rec * sizeof(bamio::RecordDesc)));
     VB2_HIP(hipMalloc(&d_count.p, batch_rec * 4));
@@ -412,6 +439,7 @@ int device_pileup(const bamio::Scan& scan, const std::vector<std::vector<std::pa
             std::memcpy(hd + nb, ch.bytes.data() + d.data, vb);
             hr[nr] = d;
             hr[nr].data = (uint32_t)nb;
+            if (hg) hg[nr] = ri < ch.group.size() ? ch.group[ri] : bamio::kNoGroup;
             nb += vb;
             ++nr;
             ++ri;
@@ -422,6 +450,7 @@ int device_pileup(const bamio::Scan& scan, const std::vector<std::vector<std::pa
         d_batches.v.push_back(d_data);
         VB2_HIP(hipMemcpyAsync(d_data, hd, nb, hipMemcpyHostToDevice, s));
         VB2_HIP(hipMemcpyAsync(d_desc.p, hr, nr * sizeof(bamio::RecordDesc), hipMemcpyHostToDevice, s));
+        if (hg) VB2_HIP(hipMemcpyAsync(d_grp.p, hg, nr * sizeof(uint16_t), hipMemcpyHostToDevice, s));
         VB2_HIP(launch_cover_count(d_desc.as<bamio::RecordDesc>(), (int64_t)nr, static_cast<const uint8_t*>(d_data), nb, filter,
                                    markers, d_count.as<uint32_t>(), s));
         VB2_HIP(launch_scan_u32(d_count.as<uint32_t>(), d_offset.as<uint32_t>(), (int64_t)nr, d_total.as<unsigned long long>(), s));
@@ -449,7 +478,7 @@ int device_pileup(const bamio::Scan& scan, const std::vector<std::vector<std::pa
         if (add > 0)
             VB2_HIP(launch_cover_fill(d_desc.as<bamio::RecordDesc>(), (int64_t)nr, static_cast<const uint8_t*>(d_data), nb, filter,
                                       markers, d_offset.as<uint32_t>(), d_entries.as<PileEntry>() + num_entries,
-                                      d_keys.as<uint64_t>() + num_entries, s));
+                                      d_keys.as<uint64_t>() + num_entries, s, d_grp.as<uint16_t>()));
         // (d_desc and d_offset are written again only by the next batch's copies, which the stream orders behind this fill)
         num_entries += (int64_t)add;
         ++num_batch;
@@ -466,10 +495,10 @@ int device_pileup(const bamio::Scan& scan, const std::vector<std::vector<std::pa
     VB2_HIP(hipMalloc(&d_qual.p, ne1));
     VB2_HIP(hipMalloc(&d_sorted.p, ne1 * sizeof(PileEntry)));
     VB2_HIP(hipMalloc(&d_keys2.p, ne1 * sizeof(uint64_t)));
+    size_t temp_bytes = 0;
     if (num_entries > 0) {
         VB2_HIP(hipMalloc(&d_idx.p, ne1 * 4));
         VB2_HIP(hipMalloc(&d_idx2.p, ne1 * 4));
-        size_t temp_bytes = 0;
         VB2_HIP(sort_entries(nullptr, &temp_bytes, d_keys.as<uint64_t>(), d_keys2.as<uint64_t>(), d_idx.as<uint32_t>(),
                              d_idx2.as<uint32_t>(), num_entries, s));
         VB2_HIP(hipMalloc(&d_temp.p, std::max<size_t>(temp_bytes, 1)));
@@ -539,6 +568,76 @@ int device_pileup(const bamio::Scan& scan, const std::vector<std::vector<std::pa
         stats->seconds_device = t1 - t0;
         stats->seconds_copyback = now_s() - t1;
     }
+    if (num_group == 0 || num_slot == 0) return VB2_OK;
+
+    // ---- every read group's sites: a second key per sorted entry, a second sort, the site kernel over virtual slots ----
+    const double g0 = now_s();
+    const int32_t num_vslot = num_group * num_slot;
+    const size_t nv1 = (size_t)num_vslot + 1;
+    Dev d_qual2, d_range2, d_depth2, d_off2, d_rep2, d_gbases, d_gquals;
+    VB2_HIP(hipMalloc(&d_range2.p, nv1 * 4));
+    VB2_HIP(hipMalloc(&d_depth2.p, nv1 * 4));
+    VB2_HIP(hipMalloc(&d_off2.p, nv1 * 4));
+    VB2_HIP(hipMalloc(&d_rep2.p, nv1));
+    VB2_HIP(hipMalloc(&d_qual2.p, ne1));
+    // (the unsorted entries and their keys have been gathered: their arrays take the second keys and the second gather)
+    PileEntry* const d_sorted2 = num_entries > 0 ? d_entries.as<PileEntry>() : d_sorted.as<PileEntry>();
+    if (num_entries > 0) {
+        VB2_HIP(launch_group_keys(d_sorted.as<PileEntry>(), d_range.as<uint32_t>(), num_entries, num_slot, num_group, max_depth,
+                                  d_keys.as<uint64_t>(), s));
+        VB2_HIP(launch_iota_u32(d_idx.as<uint32_t>(), num_entries, s));
+        VB2_HIP(sort_entries(d_temp.p, &temp_bytes, d_keys.as<uint64_t>(), d_keys2.as<uint64_t>(), d_idx.as<uint32_t>(),
+                             d_idx2.as<uint32_t>(), num_entries, s));
+        VB2_HIP(launch_group_gather(d_sorted.as<PileEntry>(), d_qual.as<uint8_t>(), d_idx2.as<uint32_t>(), d_sorted2,
+                                    d_qual2.as<uint8_t>(), num_entries, s));
+    }
+    VB2_HIP(launch_site_ranges(d_keys2.as<uint64_t>(), num_entries, num_vslot, d_range2.as<uint32_t>(), s));
+    VB2_HIP(launch_group_sites(false, d_sorted2, d_range2.as<uint32_t>(), d_qual2.as<uint8_t>(), num_vslot, num_slot, conf.min_baseQ,
+                               d_refnib.as<uint8_t>(), d_depth2.as<uint32_t>(), d_rep2.as<uint8_t>(), nullptr, nullptr, nullptr, s));
+    VB2_HIP(launch_scan_u32(d_depth2.as<uint32_t>(), d_off2.as<uint32_t>(), num_vslot, d_total.as<unsigned long long>(), s));
+    VB2_HIP(hipMemcpyAsync(h_total.p, d_total.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    VB2_HIP(hipStreamSynchronize(s));
+    const unsigned long long group_bases = *static_cast<unsigned long long*>(h_total.p);
+    if (group_bases > total_bases) {      // the groups partition a subset of the whole sample's bases
+        set_error("--PerReadGroup: internal error: the groups hold more bases than the whole sample");
+        return VB2_ERR_INVALID;
+    }
+    VB2_HIP(hipMalloc(&d_gbases.p, std::max<size_t>((size_t)group_bases, 1)));
+    VB2_HIP(hipMalloc(&d_gquals.p, std::max<size_t>((size_t)group_bases, 1)));
+    VB2_HIP(launch_group_sites(true, d_sorted2, d_range2.as<uint32_t>(), d_qual2.as<uint8_t>(), num_vslot, num_slot, conf.min_baseQ,
+                               d_refnib.as<uint8_t>(), d_depth2.as<uint32_t>(), d_rep2.as<uint8_t>(), d_off2.as<uint32_t>(),
+                               d_gbases.as<char>(), d_gquals.as<char>(), s));
+    VB2_HIP(hipStreamSynchronize(s));
+    const double g1 = now_s();
+    depth.assign((size_t)num_vslot, 0u);
+    off.assign((size_t)num_vslot, 0u);
+    rep.assign((size_t)num_vslot, 0);
+    bases.assign((size_t)group_bases, '\0');
+    quals.assign((size_t)group_bases, '\0');
+    VB2_HIP(hipMemcpy(depth.data(), d_depth2.p, (size_t)num_vslot * 4, hipMemcpyDeviceToHost));
+    VB2_HIP(hipMemcpy(off.data(), d_off2.p, (size_t)num_vslot * 4, hipMemcpyDeviceToHost));
+    VB2_HIP(hipMemcpy(rep.data(), d_rep2.p, (size_t)num_vslot, hipMemcpyDeviceToHost));
+    if (group_bases > 0) {
+        VB2_HIP(hipMemcpy(&bases[0], d_gbases.p, (size_t)group_bases, hipMemcpyDeviceToHost));
+        VB2_HIP(hipMemcpy(&quals[0], d_gquals.p, (size_t)group_bases, hipMemcpyDeviceToHost));
+    }
+    for (int32_t g = 0; g < num_group; ++g) {      // as the whole sample's stage 3: .bed row order, a position listed twice once
+        PileupViewer& gv = groups->flat[(size_t)g]->viewer;
+        const size_t v0 = (size_t)g * (size_t)num_slot;
+        for (size_t row = 0; row < panel.PosVec.size(); ++row) {
+            const int32_t slot = panel.rowSlot[row];
+            if (slot < 0 || slot >= num_slot || !rep[v0 + (size_t)slot] || gv.siteOfSlot[(size_t)slot] >= 0) continue;
+            const uint32_t n = depth[v0 + (size_t)slot];
+            if (n > 0) {
+                gv.effectiveNumSite++;
+                gv.numBases += (int)n;
+            }
+            gv.add_site(slot, bases.data() + off[v0 + (size_t)slot], quals.data() + off[v0 + (size_t)slot], n);
+        }
+        gv.avgDepth = gv.effectiveNumSite ? (double)gv.numBases / gv.effectiveNumSite : 0.0;
+    }
+    groups->seconds_device = g1 - g0;
+    groups->seconds_copyback = now_s() - g1;
     return VB2_OK;
 }
 
@@ -577,8 +676,9 @@ void host_stats(const bamio::Scan& scan, vb2_bam_stats* st)
 
 }  // namespace
 
-int read_bam(const std::string& bam_path, const std::string&, const Panel& panel, PileupViewer* v, const vb2_mpileup_opts* mp,
-             int device, vb2_bam_stats* stats)
+// read_bam, and read_bam_groups with groups != nullptr
+static int read_bam_impl(const std::string& bam_path, const Panel& panel, PileupViewer* v, const vb2_mpileup_opts* mp, int device,
+                         vb2_bam_stats* stats, vb2_flat_groups* groups, const std::shared_ptr<Panel>& shared)
 {
     MplpConf conf;
     conf.apply(mp);
@@ -588,9 +688,41 @@ int read_bam(const std::string& bam_path, const std::string&, const Panel& panel
     // the file and its index first: no device is touched for an input that cannot be read
     bamio::Scan scan;
     std::string err;
-    if (int rc = bamio::scan(bam_path, seqs, reader_threads(), &scan, &err)) {
+    if (int rc = bamio::scan(bam_path, seqs, reader_threads(), &scan, &err, groups != nullptr)) {
         set_error(err);
         return rc;                     // bamio's codes are the ABI's
+    }
+    if (groups) {
+        if (!group_slots_fit(scan.groups.size(), panel.num_slot())) {      // before anything is sized by the product
+            set_error("--PerReadGroup: " + std::to_string(scan.groups.size()) + " read groups x " + std::to_string(panel.num_slot()) +
+                      " panel positions exceed 2^31 - 2, the range of the per-group site index");
+            return VB2_ERR_INVALID;
+        }
+        groups->info.resize(scan.groups.size());
+        for (size_t g = 0; g < scan.groups.size(); ++g) {
+            vb2_flat_groups::Info& gi = groups->info[g];
+            gi.id = scan.groups[g].id;
+            gi.sm = scan.groups[g].sm;
+            gi.lb = scan.groups[g].lb;
+            gi.pu = scan.groups[g].pu;
+        }
+        for (const bamio::Chunk& ch : scan.chunks)
+            for (const uint16_t g : ch.group)
+                if (g != bamio::kNoGroup) ++groups->info[g].records;
+        groups->unassigned = scan.stats.records_unassigned;
+        groups->flat.clear();
+        for (size_t g = 0; g < scan.groups.size(); ++g) {
+            groups->flat.emplace_back(new vb2_flat(shared));
+            PileupViewer& gv = groups->flat.back()->viewer;
+            gv.SEQ_SM = scan.groups[g].sm.empty() ? scan.sample : scan.groups[g].sm;
+            gv.init(panel);
+            gv.numBases = 0;
+            gv.effectiveNumSite = 0;
+        }
+        if (scan.stats.records_unassigned > 0)
+            std::fprintf(stderr, "NOTICE - --PerReadGroup: %lld of %lld records over the panel's markers belong to no read group of the "
+                                 "header (no RG:Z field, or an ID it lacks); they count in the whole sample only\n",
+                         (long long)scan.stats.records_unassigned, (long long)scan.stats.records_kept);
     }
     vb2_bam_stats local;
     if (!stats) stats = &local;
@@ -604,14 +736,30 @@ int read_bam(const std::string& bam_path, const std::string&, const Panel& panel
                   "(there is no CPU fallback)");
         return VB2_ERR_NO_DEVICE;
     }
-    return device_pileup(scan, by_seq, panel, conf, device, v, stats);
+    return device_pileup(scan, by_seq, panel, conf, device, v, stats, groups);
+}
+
+int read_bam(const std::string& bam_path, const std::string&, const Panel& panel, PileupViewer* v, const vb2_mpileup_opts* mp,
+             int device, vb2_bam_stats* stats)
+{
+    return read_bam_impl(bam_path, panel, v, mp, device, stats, nullptr, nullptr);
+}
+
+int read_bam_groups(const std::string& bam_path, const std::shared_ptr<Panel>& panel, PileupViewer* v, const vb2_mpileup_opts* mp,
+                    int device, vb2_bam_stats* stats, vb2_flat_groups* groups)
+{
+    if (!panel || !groups) {
+        set_error("read_bam_groups: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    return read_bam_impl(bam_path, *panel, v, mp, device, stats, groups, panel);
 }
 
 bool bam_support() { return true; }
 
 // Stage 1 alone (vb2_bam_scan): no device
 int bam_scan_file(const std::string& bam_path, const std::string& bed_path, std::vector<uint64_t>* voffsets, vb2_bam_stats* stats,
-                  std::string* sample)
+                  std::string* sample, std::vector<std::string>* group_ids, std::vector<uint16_t>* groups)
 {
     Panel panel;
     if (int rc = read_bed(bed_path, &panel)) return rc;
@@ -620,7 +768,8 @@ int bam_scan_file(const std::string& bam_path, const std::string& bed_path, std:
     markers_by_sequence(panel, &seqs, &by_seq);
     bamio::Scan scan;
     std::string err;
-    if (int rc = bamio::scan(bam_path, seqs, reader_threads(), &scan, &err)) {
+    const bool want_groups = group_ids && groups;
+    if (int rc = bamio::scan(bam_path, seqs, reader_threads(), &scan, &err, want_groups)) {
         set_error(err);
         return rc;
     }
@@ -628,6 +777,12 @@ int bam_scan_file(const std::string& bam_path, const std::string& bed_path, std:
     *sample = scan.sample;
     voffsets->clear();
     for (const bamio::Chunk& ch : scan.chunks) voffsets->insert(voffsets->end(), ch.voffset.begin(), ch.voffset.end());
+    if (want_groups) {
+        group_ids->clear();
+        groups->clear();
+        for (const bamio::ReadGroup& g : scan.groups) group_ids->push_back(g.id);
+        for (const bamio::Chunk& ch : scan.chunks) groups->insert(groups->end(), ch.group.begin(), ch.group.end());
+    }
     return VB2_OK;
 }
 

@@ -193,6 +193,101 @@ std::string sample_of(const std::string& text, bool* several)      // @RG SM: (S
     return sm.empty() ? std::string("DefaultSampleName") : sm;
 }
 
+// The header's @RG lines in header order: the tab-separated fields ID:, SM:, LB: and PU:, wherever they stand in the line.
+void read_groups_of(const std::string& path, const std::string& text, std::vector<ReadGroup>* out)
+{
+    std::map<std::string, size_t> seen;
+    size_t line = 0;
+    while (line < text.size()) {
+        size_t eol = text.find('\n', line);
+        if (eol == std::string::npos) eol = text.size();
+        size_t end = eol;
+        while (end > line && (text[end - 1] == '\r' || text[end - 1] == '\0')) --end;
+        if (end - line >= 3 && text.compare(line, 3, "@RG") == 0 && (end - line == 3 || text[line + 3] == '\t')) {
+            ReadGroup g;
+            bool has_id = false;
+            size_t f = line + 3;
+            while (f < end) {
+                ++f;                                             // the tab
+                size_t e = text.find('\t', f);
+                if (e == std::string::npos || e > end) e = end;
+                if (e - f >= 3 && text[f + 2] == ':') {
+                    const std::string val = text.substr(f + 3, e - f - 3);
+                    if (text.compare(f, 2, "ID") == 0) { g.id = val; has_id = true; }
+                    else if (text.compare(f, 2, "SM") == 0) g.sm = val;
+                    else if (text.compare(f, 2, "LB") == 0) g.lb = val;
+                    else if (text.compare(f, 2, "PU") == 0) g.pu = val;
+                }
+                f = e;
+            }
+            const std::string nth = "@RG line " + std::to_string(out->size() + 1) + " of the header";
+            if (!has_id) throw Fail{kErrInvalid, path + ": " + nth + " has no ID: field"};
+            if (seen.count(g.id))
+                throw Fail{kErrInvalid, path + ": " + nth + " repeats the ID \"" + g.id + "\" of line " + std::to_string(seen[g.id] + 1)};
+            if (out->size() >= kMaxGroups)
+                throw Fail{kErrInvalid, path + ": more than " + std::to_string(kMaxGroups) + " @RG lines in the header"};
+            seen[g.id] = out->size();
+            out->push_back(std::move(g));
+        }
+        line = eol + 1;
+    }
+}
+
+// The group of one record: its auxiliary fields [p, end) walked once (SAMv1 4.2.4), every field's length checked against
+// the record's end.  The first RG field of type Z names the group; an RG of another type, or an ID the header lacks, none.
+uint16_t group_of_record(const uint8_t* p, const uint8_t* end, const std::map<std::string, uint16_t>& group_of,
+                         const std::string& path, uint64_t voff)
+{
+    auto fail = [&](const std::string& what) -> Fail {
+        return Fail{kErrInvalid, path + ": record at virtual offset " + std::to_string(voff) + ": " + what};
+    };
+    auto width = [](uint8_t t) -> size_t {
+        switch (t) {
+        case 'A': case 'c': case 'C': return 1;
+        case 's': case 'S': return 2;
+        case 'i': case 'I': case 'f': return 4;
+        default: return 0;
+        }
+    };
+    uint16_t group = kNoGroup;
+    bool found = false;
+    while (p < end) {
+        const size_t left = (size_t)(end - p);
+        if (left < 3) throw fail(std::to_string(left) + " stray byte(s) behind its last auxiliary field");
+        const uint8_t t0 = p[0], t1 = p[1], type = p[2];
+        const std::string tag{(char)t0, (char)t1};
+        p += 3;
+        const size_t avail = (size_t)(end - p);
+        size_t len = 0;
+        if (type == 'Z' || type == 'H') {
+            const void* nul = avail ? std::memchr(p, 0, avail) : nullptr;
+            if (!nul) throw fail("auxiliary field " + tag + " of type " + std::string(1, (char)type) + " has no terminator before the record's end");
+            len = (size_t)((const uint8_t*)nul - p) + 1;
+            if (!found && t0 == 'R' && t1 == 'G') {
+                found = true;
+                if (type == 'Z') {
+                    auto it = group_of.find(std::string((const char*)p, len - 1));
+                    if (it != group_of.end()) group = it->second;
+                }
+            }
+        } else if (type == 'B') {
+            if (avail < 5) throw fail("auxiliary array " + tag + " passes the end of the record");
+            const size_t w = width(p[0]);
+            if (w == 0 || p[0] == 'A') throw fail("auxiliary array " + tag + " has the unknown subtype byte " + std::to_string((int)p[0]));
+            const uint64_t count = le32(p + 1);
+            if (count > (avail - 5) / w) throw fail("auxiliary array " + tag + " of " + std::to_string(count) + " elements passes the end of the record");
+            len = 5 + (size_t)count * w;
+        } else {
+            len = width(type);
+            if (len == 0) throw fail("auxiliary field " + tag + " has the unknown type byte " + std::to_string((int)type));
+            if (len > avail) throw fail("auxiliary field " + tag + " passes the end of the record");
+            if (t0 == 'R' && t1 == 'G') found = true;           // an RG that is no string: the record has no group
+        }
+        p += len;
+    }
+    return group;
+}
+
 struct Header {
     std::vector<std::string> name;
     std::vector<int64_t> len;
@@ -388,7 +483,9 @@ inline bool consumes_ref(uint32_t op) { return op == 0 || op == 2 || op == 3 || 
 
 // Walks the record chain of one chunk whose planned blocks are inflated; inflates further blocks where its last record
 // straddles.  Keeps the records on the chunk's sequence that can reach one of `pos`.
-void walk_chunk(const File& f, Chunk* ch, Work* w, const std::vector<int32_t>& pos, int32_t n_ref, Stats* st)
+// group_of (may be null): the header's group IDs; then every kept record's auxiliary fields are walked for its group.
+void walk_chunk(const File& f, Chunk* ch, Work* w, const std::vector<int32_t>& pos, int32_t n_ref, Stats* st,
+                const std::map<std::string, uint16_t>* group_of)
 {
     std::vector<uint8_t>& b = ch->bytes;
     Stream s{f, w->next_off, &b, &w->blocks, &st->blocks};
@@ -460,6 +557,14 @@ void walk_chunk(const File& f, Chunk* ch, Work* w, const std::vector<int32_t>& p
         if (it == pos.end() || (int64_t)*it > (int64_t)d.pos + rlen) continue;
         ch->recs.push_back(d);
         ch->voffset.push_back(voff);
+        if (group_of) {
+            // from the end of the qualities to the end of the record's block (o is behind it; the check above keeps the
+            // start inside)
+            const uint64_t var = (uint64_t)d.l_read_name + 4ull * d.n_cigar + ((uint64_t)d.l_seq + 1) / 2 + (uint64_t)d.l_seq;
+            const uint16_t g = group_of_record(b.data() + d.data + var, b.data() + o, *group_of, f.path, voff);
+            ch->group.push_back(g);
+            if (g == kNoGroup) ++st->records_unassigned;
+        }
     }
 }
 
@@ -497,7 +602,7 @@ template <class F> void parallel(size_t n, int threads, F fn)
     if (failed) throw first;
 }
 
-void scan_impl(const std::string& bam_path, const std::vector<SeqMarkers>& markers, int threads, Scan* out)
+void scan_impl(const std::string& bam_path, const std::vector<SeqMarkers>& markers, int threads, Scan* out, bool want_groups)
 {
     threads = std::max(1, std::min(threads, 16));
     const double t0 = now_s();
@@ -515,6 +620,11 @@ void scan_impl(const std::string& bam_path, const std::vector<SeqMarkers>& marke
     if (several) throw Fail{kErrInvalid, "This BAM or CRAM file contains more than 1 sample, please demultiplex or separate first!"};
     out->ref_name = hd.name;
     out->ref_len = hd.len;
+    std::map<std::string, uint16_t> group_of;
+    if (want_groups) {
+        read_groups_of(bam_path, hd.text, &out->groups);
+        for (size_t g = 0; g < out->groups.size(); ++g) group_of[out->groups[g].id] = (uint16_t)g;
+    }
     const int32_t n_ref = (int32_t)hd.name.size();
     std::map<std::string, int32_t> tid_of;
     for (int32_t t = n_ref - 1; t >= 0; --t) tid_of[hd.name[(size_t)t]] = t;
@@ -577,13 +687,14 @@ void scan_impl(const std::string& bam_path, const std::vector<SeqMarkers>& marke
     parallel(nc, threads, [&](size_t i) {
         work[i].raw.clear();
         work[i].raw.shrink_to_fit();
-        walk_chunk(bam, &out->chunks[i], &work[i], *pos_of[(size_t)out->chunks[i].tid], n_ref, &st[i]);
+        walk_chunk(bam, &out->chunks[i], &work[i], *pos_of[(size_t)out->chunks[i].tid], n_ref, &st[i], want_groups ? &group_of : nullptr);
     });
     uint64_t order = 0;
     for (size_t i = 0; i < nc; ++i) {
         out->stats.blocks += st[i].blocks;
         out->stats.records_seen += st[i].records_seen;
         out->stats.long_cigar_skipped += st[i].long_cigar_skipped;
+        out->stats.records_unassigned += st[i].records_unassigned;
         out->stats.bytes_inflated += (int64_t)out->chunks[i].bytes.size();
         out->stats.records_kept += (int64_t)out->chunks[i].recs.size();
         for (RecordDesc& d : out->chunks[i].recs) d.order = (uint32_t)order++;
@@ -594,10 +705,11 @@ void scan_impl(const std::string& bam_path, const std::vector<SeqMarkers>& marke
 
 }  // namespace
 
-int scan(const std::string& bam_path, const std::vector<SeqMarkers>& markers, int threads, Scan* out, std::string* err)
+int scan(const std::string& bam_path, const std::vector<SeqMarkers>& markers, int threads, Scan* out, std::string* err,
+         bool want_groups)
 {
     try {
-        scan_impl(bam_path, markers, threads, out);
+        scan_impl(bam_path, markers, threads, out, want_groups);
         return kOk;
     } catch (const Fail& e) {
         if (err) *err = e.msg;

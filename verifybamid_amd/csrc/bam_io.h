@@ -35,16 +35,25 @@ struct RecordDesc {
 };
 static_assert(sizeof(RecordDesc) == 32, "descriptors are 32 bytes");
 
+// One @RG line of the header.  Only the ID is needed downstream; SM, LB and PU are there for whoever writes a report.
+struct ReadGroup {
+    std::string id, sm, lb, pu;
+};
+constexpr uint16_t kNoGroup = 0xFFFF;        // a record without an RG:Z field, or with an ID the header lacks
+constexpr size_t kMaxGroups = 0xFFFF;
+
 struct Chunk {               // one merged run of the index's chunks, inflated
     int32_t tid = -1;
     uint64_t beg = 0, end = 0;               // virtual offsets
     std::vector<uint8_t> bytes;              // inflated blocks back to back, from beg's block on
     std::vector<RecordDesc> recs;            // the records that start in [beg, end) on `tid` and may reach a marker
     std::vector<uint64_t> voffset;           // ... and their virtual offsets
+    std::vector<uint16_t> group;             // ... and, when the scan was asked for groups, their index into Scan::groups
 };
 
 struct Stats {
     int64_t blocks = 0, bytes_inflated = 0, records_seen = 0, records_kept = 0, long_cigar_skipped = 0, chunks = 0;
+    int64_t records_unassigned = 0;          // kept records of no group (0 when groups were not asked for)
     double seconds_index = 0, seconds_inflate = 0;
 };
 
@@ -60,13 +69,18 @@ struct Scan {
     std::vector<int64_t> ref_len;
     std::vector<int32_t> tid_of_seq;         // per entry of the markers passed in: its tid in the header, -1 = absent
     std::vector<Chunk> chunks;               // ascending by (tid, beg)
+    std::vector<ReadGroup> groups;           // the header's @RG lines in header order (filled only when asked for)
     Stats stats;
 };
 
 // Opens bam_path and its index (<bam>.bai, else <stem>.bai), plans the chunks that can hold a record over one of the
 // markers, inflates every block once on a pool of `threads` threads (<= 16) and walks the records.  kErrIo / kErrInvalid
 // with *err set otherwise.
-int scan(const std::string& bam_path, const std::vector<SeqMarkers>& markers, int threads, Scan* out, std::string* err);
+// want_groups: also parse the header's @RG lines into out->groups (two lines with one ID, a line without ID or more than
+// 65 535 lines: kErrInvalid) and walk every kept record's auxiliary fields for its RG:Z, into Chunk::group.  Without it the
+// auxiliary bytes are not looked at.
+int scan(const std::string& bam_path, const std::vector<SeqMarkers>& markers, int threads, Scan* out, std::string* err,
+         bool want_groups = false);
 
 }  // namespace bamio
 }  // namespace vb2

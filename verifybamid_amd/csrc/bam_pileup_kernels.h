@@ -23,7 +23,9 @@ struct PileEntry {
     uint8_t qual;
     uint8_t bits;
     uint8_t l_name;
-    uint8_t pad[5];
+    uint8_t pad0;
+    uint16_t group;         // the record's read group (bamio::kNoGroup = none); 0 in a load that was not asked for groups
+    uint8_t pad[2];
 };
 static_assert(sizeof(PileEntry) == 32, "entries are 32 bytes");
 constexpr uint8_t kEntryReverse = 16, kEntryDeleted = 32, kEntryEligible = 64, kEntryMateAhead = 128;
@@ -49,10 +51,11 @@ hipError_t launch_cover_count(const bamio::RecordDesc* desc, int64_t num_rec, co
                               PileFilter f, PileMarkers m, uint32_t* count, hipStream_t s);
 // offset = exclusive scan of count [n], *total = its sum (a single workgroup walks the array)
 hipError_t launch_scan_u32(const uint32_t* count, uint32_t* offset, int64_t n, unsigned long long* total, hipStream_t s);
-// Pass 2: record r's entries go to entries[offset[r] ...], and their sort keys slot << 32 | order to keys[...]
+// Pass 2: record r's entries go to entries[offset[r] ...], and their sort keys slot << 32 | order to keys[...].
+// group (may be null): the records' read groups, parallel to desc; null leaves every entry's group 0.
 hipError_t launch_cover_fill(const bamio::RecordDesc* desc, int64_t num_rec, const uint8_t* data, uint64_t data_bytes,
                              PileFilter f, PileMarkers m, const uint32_t* offset, PileEntry* entries, uint64_t* keys,
-                             hipStream_t s);
+                             hipStream_t s, const uint16_t* group = nullptr);
 
 // Sorts the keys with the entries' indices: keys_out ascending, idx_out the permutation (n < 2^31).  temp / temp_bytes as
 // hipcub wants them: call with temp == nullptr to learn temp_bytes.
@@ -73,6 +76,21 @@ hipError_t launch_overlap(const PileEntry* sorted, const uint32_t* range, int64_
 hipError_t launch_sites(bool fill, const PileEntry* sorted, const uint32_t* range, const uint8_t* qual, int32_t num_slot,
                         int32_t max_depth, int32_t min_bq, const uint8_t* ref_nib, uint32_t* depth, uint8_t* reported,
                         const uint32_t* offset, char* base_pool, char* qual_pool, PileCounters* ctr, hipStream_t s);
+
+// ---- per-read-group sites ----
+// A group's site is a "virtual slot" v = group * num_slot + slot, v < num_group * num_slot <= 2^31 - 2.
+// Per sorted entry i: keys[i] = v << 32 | order when the entry lies within its site's first max_depth entries and has a
+// group below num_group, all ones otherwise (those sort behind every virtual slot and belong to nobody).
+hipError_t launch_group_keys(const PileEntry* sorted, const uint32_t* range, int64_t n, int32_t num_slot, int32_t num_group,
+                             int32_t max_depth, uint64_t* keys, hipStream_t s);
+// sorted2[i] = sorted[perm[i]], qual2[i] = qual[perm[i]] (the quality after the overlap rule travels with its entry)
+hipError_t launch_group_gather(const PileEntry* sorted, const uint8_t* qual, const uint32_t* perm, PileEntry* sorted2,
+                               uint8_t* qual2, int64_t n, hipStream_t s);
+// launch_sites over virtual slots: no depth cap (it was applied to the whole site), the REF nibble of slot v % num_slot,
+// no counters.  range: launch_site_ranges of the second sort's keys with num_vslot for num_slot.
+hipError_t launch_group_sites(bool fill, const PileEntry* sorted2, const uint32_t* range, const uint8_t* qual2, int32_t num_vslot,
+                              int32_t num_slot, int32_t min_bq, const uint8_t* ref_nib, uint32_t* depth, uint8_t* reported,
+                              const uint32_t* offset, char* base_pool, char* qual_pool, hipStream_t s);
 
 }  // namespace vb2
 

@@ -8,6 +8,11 @@
 //                       eligible entry of the site, so that every quality has exactly one writer.
 //   bam_site_kernel     one wave per site: depth cap, min-BQ, characters, the deletion quirk; in-order compaction with
 //                       ballots, so a site of any depth comes out in file order.  Two passes (depth, scan, characters).
+// Per read group, behind the above and only when asked for:
+//   bam_group_key_kernel one thread per sorted entry: a second key (group * num_slot + slot) << 32 | file order for the
+//                       entries under the cap that have a group, all ones for the rest.
+//   (radix sort)        again, and bam_group_gather_kernel: the entries and their qualities after the overlap rule.
+//   bam_site_kernel     its GROUPS form over the virtual slots group * num_slot + slot: no cap, REF of slot % num_slot.
 //
 // Records are not aligned in the stream: every multi-byte field is put together from bytes.  The host stage has checked
 // that a record's name, CIGAR, bases and qualities lie inside its bytes (bam_io.cpp); the cover kernel checks the same
@@ -40,7 +45,7 @@ __global__ __launch_bounds__(kBlock) void bam_cover_kernel(const bamio::RecordDe
                                                             const uint8_t* __restrict__ data, uint64_t data_bytes, PileFilter f,
                                                             PileMarkers m, uint32_t* __restrict__ count,
                                                             const uint32_t* __restrict__ offset, PileEntry* __restrict__ entries,
-                                                            uint64_t* __restrict__ keys)
+                                                            uint64_t* __restrict__ keys, const uint16_t* __restrict__ group)
 {
     const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (r >= num_rec) return;
@@ -73,7 +78,11 @@ __global__ __launch_bounds__(kBlock) void bam_cover_kernel(const bamio::RecordDe
         uint64_t hash = 0;
         bool hashed = false;
         uint32_t out = 0;
-        if (FILL) out = offset[r];
+        uint16_t grp = 0;
+        if (FILL) {
+            out = offset[r];
+            if (group) grp = group[r];
+        }
         int64_t x = d.pos, y = 0;           // reference and query offsets at the start of the operation
         int32_t mi = lo;
         for (uint32_t k = 0; k < d.n_cigar && mi < hi; ++k) {
@@ -106,7 +115,9 @@ __global__ __launch_bounds__(kBlock) void bam_cover_kernel(const bamio::RecordDe
                         if (d.mpos >= d.pos) bits |= kEntryMateAhead;
                         e.bits = bits;
                         e.l_name = d.l_read_name;
-                        for (int z = 0; z < 5; ++z) e.pad[z] = 0;
+                        e.pad0 = 0;
+                        e.group = grp;
+                        e.pad[0] = e.pad[1] = 0;
                         entries[out + n] = e;
                         keys[out + n] = ((uint64_t)(uint32_t)e.slot << 32) | d.order;
                     }
@@ -255,10 +266,12 @@ __global__ __launch_bounds__(kBlock) void bam_overlap_kernel(const PileEntry* __
 
 // One wave per site.  Lane l of round k looks at the site's entry 64 k + l; the ballots of "contributes a base" and
 // "contributes a quality" give every lane its place behind what the lanes before it and the rounds before this one wrote.
-template <bool FILL>
+// GROUPS: the slots are virtual (group * ref_slots + slot): the cap was applied to the whole site before, the REF nibble is
+// that of slot % ref_slots, and nothing is counted.
+template <bool FILL, bool GROUPS>
 __global__ __launch_bounds__(kBlock) void bam_site_kernel(const PileEntry* __restrict__ sorted, const uint32_t* __restrict__ range,
                                                            const uint8_t* __restrict__ qual, int32_t num_slot, int32_t max_depth,
-                                                           int32_t min_bq, const uint8_t* __restrict__ ref_nib,
+                                                           int32_t ref_slots, int32_t min_bq, const uint8_t* __restrict__ ref_nib,
                                                            uint32_t* __restrict__ depth, uint8_t* __restrict__ reported,
                                                            const uint32_t* __restrict__ offset, char* __restrict__ base_pool,
                                                            char* __restrict__ qual_pool, PileCounters* __restrict__ ctr)
@@ -267,10 +280,10 @@ __global__ __launch_bounds__(kBlock) void bam_site_kernel(const PileEntry* __res
     const int64_t slot = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
     if (slot >= num_slot) return;                  // (whole waves leave: the ballots below see full rounds)
     const int64_t lo = range[slot], hi = range[slot + 1];
-    const int64_t cap = hi - lo > (int64_t)max_depth ? lo + max_depth : hi;
+    const int64_t cap = !GROUPS && hi - lo > (int64_t)max_depth ? lo + max_depth : hi;
     const uint32_t nb_total = FILL ? depth[slot] : 0u;
     const uint64_t off = FILL ? offset[slot] : 0u;
-    const uint8_t rn = FILL ? ref_nib[slot] : (uint8_t)0;
+    const uint8_t rn = FILL ? ref_nib[GROUPS ? (int64_t)((int32_t)slot % ref_slots) : slot] : (uint8_t)0;
     const unsigned long long below = (1ull << lane) - 1ull;
     uint32_t nb = 0, nq = 0;
     for (int64_t base = lo; base < cap; base += 64) {
@@ -309,8 +322,35 @@ __global__ __launch_bounds__(kBlock) void bam_site_kernel(const PileEntry* __res
     if (!FILL && lane == 0) {
         depth[slot] = nb;
         reported[slot] = hi > lo ? 1 : 0;
-        if (hi - lo > (int64_t)max_depth) atomicAdd(&ctr->capped_sites, 1ull);
+        if (!GROUPS && hi - lo > (int64_t)max_depth) atomicAdd(&ctr->capped_sites, 1ull);
     }
+}
+
+__global__ __launch_bounds__(kBlock) void bam_group_key_kernel(const PileEntry* __restrict__ sorted, const uint32_t* __restrict__ range,
+                                                                int64_t n, int32_t num_slot, int32_t num_group, int32_t max_depth,
+                                                                uint64_t* __restrict__ keys)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const PileEntry e = sorted[i];
+    uint64_t key = ~0ull;
+    if (e.slot >= 0 && e.slot < num_slot && (int32_t)e.group < num_group) {
+        const int64_t lo = range[e.slot], hi = range[e.slot + 1];
+        const int64_t cap = hi - lo > (int64_t)max_depth ? lo + max_depth : hi;
+        if (i < cap) key = ((uint64_t)((uint32_t)e.group * (uint32_t)num_slot + (uint32_t)e.slot) << 32) | e.order;
+    }
+    keys[i] = key;
+}
+
+__global__ __launch_bounds__(kBlock) void bam_group_gather_kernel(const PileEntry* __restrict__ sorted, const uint8_t* __restrict__ qual,
+                                                                   const uint32_t* __restrict__ perm, PileEntry* __restrict__ sorted2,
+                                                                   uint8_t* __restrict__ qual2, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t j = perm[i];
+    sorted2[i] = sorted[j];
+    qual2[i] = qual[j];
 }
 
 inline unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
@@ -322,17 +362,17 @@ hipError_t launch_cover_count(const bamio::RecordDesc* desc, int64_t num_rec, co
 {
     if (num_rec <= 0) return hipSuccess;
     bam_cover_kernel<false><<<blocks_for(num_rec, kBlock), kBlock, 0, s>>>(desc, num_rec, data, data_bytes, f, m, count, nullptr,
-                                                                            nullptr, nullptr);
+                                                                            nullptr, nullptr, nullptr);
     return hipGetLastError();
 }
 
 hipError_t launch_cover_fill(const bamio::RecordDesc* desc, int64_t num_rec, const uint8_t* data, uint64_t data_bytes,
                              PileFilter f, PileMarkers m, const uint32_t* offset, PileEntry* entries, uint64_t* keys,
-                             hipStream_t s)
+                             hipStream_t s, const uint16_t* group)
 {
     if (num_rec <= 0) return hipSuccess;
     bam_cover_kernel<true><<<blocks_for(num_rec, kBlock), kBlock, 0, s>>>(desc, num_rec, data, data_bytes, f, m, nullptr, offset,
-                                                                           entries, keys);
+                                                                           entries, keys, group);
     return hipGetLastError();
 }
 
@@ -383,11 +423,42 @@ hipError_t launch_sites(bool fill, const PileEntry* sorted, const uint32_t* rang
     if (num_slot <= 0) return hipSuccess;
     const unsigned grid = blocks_for(num_slot, kBlock / 64);
     if (fill)
-        bam_site_kernel<true><<<grid, kBlock, 0, s>>>(sorted, range, qual, num_slot, max_depth, min_bq, ref_nib, depth, reported,
-                                                       offset, base_pool, qual_pool, ctr);
+        bam_site_kernel<true, false><<<grid, kBlock, 0, s>>>(sorted, range, qual, num_slot, max_depth, num_slot, min_bq, ref_nib, depth,
+                                                              reported, offset, base_pool, qual_pool, ctr);
     else
-        bam_site_kernel<false><<<grid, kBlock, 0, s>>>(sorted, range, qual, num_slot, max_depth, min_bq, ref_nib, depth, reported,
-                                                        offset, base_pool, qual_pool, ctr);
+        bam_site_kernel<false, false><<<grid, kBlock, 0, s>>>(sorted, range, qual, num_slot, max_depth, num_slot, min_bq, ref_nib, depth,
+                                                               reported, offset, base_pool, qual_pool, ctr);
+    return hipGetLastError();
+}
+
+hipError_t launch_group_keys(const PileEntry* sorted, const uint32_t* range, int64_t n, int32_t num_slot, int32_t num_group,
+                             int32_t max_depth, uint64_t* keys, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    bam_group_key_kernel<<<blocks_for(n, kBlock), kBlock, 0, s>>>(sorted, range, n, num_slot, num_group, max_depth, keys);
+    return hipGetLastError();
+}
+
+hipError_t launch_group_gather(const PileEntry* sorted, const uint8_t* qual, const uint32_t* perm, PileEntry* sorted2,
+                               uint8_t* qual2, int64_t n, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    bam_group_gather_kernel<<<blocks_for(n, kBlock), kBlock, 0, s>>>(sorted, qual, perm, sorted2, qual2, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_group_sites(bool fill, const PileEntry* sorted2, const uint32_t* range, const uint8_t* qual2, int32_t num_vslot,
+                              int32_t num_slot, int32_t min_bq, const uint8_t* ref_nib, uint32_t* depth, uint8_t* reported,
+                              const uint32_t* offset, char* base_pool, char* qual_pool, hipStream_t s)
+{
+    if (num_vslot <= 0 || num_slot <= 0) return hipSuccess;
+    const unsigned grid = blocks_for(num_vslot, kBlock / 64);
+    if (fill)
+        bam_site_kernel<true, true><<<grid, kBlock, 0, s>>>(sorted2, range, qual2, num_vslot, 0, num_slot, min_bq, ref_nib, depth,
+                                                             reported, offset, base_pool, qual_pool, nullptr);
+    else
+        bam_site_kernel<false, true><<<grid, kBlock, 0, s>>>(sorted2, range, qual2, num_vslot, 0, num_slot, min_bq, ref_nib, depth,
+                                                              reported, offset, base_pool, qual_pool, nullptr);
     return hipGetLastError();
 }
 

@@ -112,6 +112,7 @@ int main(int argc, char** argv)
     std::string MatchedNormal("Empty");
     double normalHomMin = 0.99;
     bool pairInterval = false;
+    bool perReadGroup = false;
     // "Pileup Options" (main.cpp:176-187), defaults main.cpp:81-96 (MPLP_REALN | MPLP_SMART_OVERLAPS; UNMAP | SECONDARY |
     // QCFAIL | DUP): they shape what --BamFile input becomes and, as in the reference, do nothing to --PileupFile input
     int minBQ = 13, minMQ = 2, adjustMQ = 40, maxDepth = 8000, inclFlags = (1 << 4) | (1 << 10), exclFlags = 0x4 | 0x100 | 0x200 | 0x400;
@@ -191,6 +192,9 @@ int main(int argc, char** argv)
         // not in the reference: with --MatchedNormal, a 95% confidence interval (profile likelihood, unfolded) and a
         // standard error for every ALPHA_PAIRED, computed in lock-step (vb2_cohort_run_paired_intervals), to <Output>.PairCI
         {"PairInterval", {Flag::kBool, &pairInterval, false}},
+        // not in the reference (VerifyBamID 1 had it): FREEMIX of every read group of the --BamFile header beside the whole
+        // sample's, each from the group's own pileup, the groups searched in lock-step (vb2_run_read_groups), to <Output>.selfRG
+        {"PerReadGroup", {Flag::kBool, &perReadGroup, false}},
     };
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
@@ -297,6 +301,20 @@ int main(int argc, char** argv)
         }
         if (flags["Bootstrap"].seen && (bootstrap < 1 || bootstrap > 1000)) fatal("--Bootstrap takes 1 to 1000 replicates");
         if (confidenceInterval) fatal("--PerChromosome / --Bootstrap cannot be combined with --ConfidenceInterval: run them separately");
+    }
+    if (perReadGroup) {                                                 // one BAM, one device, the plain search
+        if (PileupFile != "Empty" || PileupList != "Empty")
+            fatal("--PerReadGroup cannot be combined with --PileupFile or --PileupList: a text pileup does not say which read group "
+                  "a base came from");
+        if (BamFile == "Empty") fatal("--PerReadGroup needs --BamFile: read groups are read from a BAM's header and RG:Z fields");
+        if (Devices != "Empty" && Devices.find(',') != std::string::npos)
+            fatal("--PerReadGroup cannot be combined with more than one --Devices: the groups are searched in lock-step on one device");
+        if (confidenceInterval) fatal("--PerReadGroup cannot be combined with --ConfidenceInterval: run them separately");
+        if (perChromosome || flags["Bootstrap"].seen)
+            fatal("--PerReadGroup cannot be combined with --PerChromosome / --Bootstrap: run them separately");
+        if (flags["NumStart"].seen || lineSearch)
+            fatal("--PerReadGroup cannot be combined with --NumStart / --LineSearch: the groups are searched in lock-step by the "
+                  "reference's optimiser");
     }
     // --Seed: parsed and never used by the reference (main.cpp:137,286); here it seeds --NumStart's starting points
     // --NumThread: the likelihood runs on the GPU; the VCF parser pool of --RefVCF and the reader threads of --PileupList use it
@@ -480,7 +498,9 @@ int main(int argc, char** argv)
 
     vb2_run_result res;
     vb2_interval ci;
-    const int rc = (perChromosome || bootstrap > 0) ? vb2_run_replicates(&args, perChromosome ? 1 : 0, bootstrap, &res, nullptr)
+    int32_t numGroup = 0;
+    const int rc = perReadGroup                     ? vb2_run_read_groups(&args, &res, 0, nullptr, &numGroup)
+                   : (perChromosome || bootstrap > 0) ? vb2_run_replicates(&args, perChromosome ? 1 : 0, bootstrap, &res, nullptr)
                    : confidenceInterval             ? vb2_run_interval(&args, &res, &ci)
                                                     : vb2_run(&args, &res);
     if (rc != VB2_OK) {
@@ -490,6 +510,7 @@ int main(int argc, char** argv)
     }
     std::fprintf(stderr, "NOTICE - %lld likelihood evaluations, %lld points launched on the device\n",
                  (long long)res.est.num_eval, (long long)res.est.num_launch_point);
+    if (perReadGroup) std::fprintf(stderr, "NOTICE - %d read groups written to %s.selfRG\n", (int)numGroup, outputPrefix.c_str());
     std::fprintf(stderr, "NOTICE - Success!\n");
     return 0;
 }

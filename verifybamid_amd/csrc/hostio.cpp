@@ -928,6 +928,29 @@ int write_selfsm(const std::string& prefix, const vb2_flat& f, const vb2_estimat
     return VB2_OK;
 }
 
+// <prefix>.selfRG (--PerReadGroup): .selfSM's header line and one row per read group in header order, formatted as
+// write_selfsm formats; #READS is the group's numBases; a group that was not searched has NA for FREEMIX and its two LLKs.
+int write_selfrg(const std::string& prefix, const vb2_flat_groups& groups, const vb2_estimate* est, const uint8_t* searched)
+{
+    const std::string name(prefix + ".selfRG");
+    std::ofstream fout(name);
+    if (!fout.is_open()) return io_error("Open file " + name + " failed!");
+    fout << "#SEQ_ID\tRG\tCHIP_ID\t#SNPS\t#READS\tAVG_DP\tFREEMIX\tFREELK1\tFREELK0\tFREE_RH\tFREE_RA\t"
+            "CHIPMIX\tCHIPLK1\tCHIPLK0\tCHIP_RH\tCHIP_RA\tDPREF\tRDPHET\tRDPALT"
+         << std::endl;
+    for (size_t g = 0; g < groups.flat.size(); ++g) {
+        const vb2_flat& f = *groups.flat[g];
+        fout << f.viewer.SEQ_SM << "\t" << groups.info[g].id << "\tNA\t" << f.panel.NumMarker << "\t" << f.viewer.numBases << "\t"
+             << f.viewer.avgDepth << "\t";
+        if (searched[g]) fout << ((est[g].alpha < 0.5) ? est[g].alpha : (1.f - est[g].alpha)) << "\t" << -est[g].llk1 << "\t" << -est[g].llk0;
+        else fout << "NA\tNA\tNA";
+        fout << "\t" << "NA\tNA\t" << "NA\tNA\tNA\tNA\tNA\t" << "NA\tNA\tNA" << std::endl;
+    }
+    fout.close();
+    if (!fout) return io_error("Errors detected when writing to file " + name + " !");
+    return VB2_OK;
+}
+
 // main.cpp:336-369: sites with depth > 0 in bed order.
 int write_pileup(const std::string& prefix, const vb2_flat& f)
 {

@@ -20,6 +20,8 @@
 
 #include "../../include/vb2_abi.h"
 
+struct vb2_flat_groups;
+
 namespace vb2 {
 
 // The .bed rows name positions; a position listed twice is ONE entry of the reference's
@@ -100,10 +102,16 @@ int read_pileup(const std::string& path, const Panel& panel, PileupViewer* v);
 // stats (may be null): what vb2_flat_bam_stats reports.  The file and its index are opened before any device is touched.
 int read_bam(const std::string& bam_path, const std::string& ref_path, const Panel& panel, PileupViewer* v,
              const vb2_mpileup_opts* mp = nullptr, int device = -1, vb2_bam_stats* stats = nullptr);
+// read_bam, and every read group of the header beside the whole sample (built-in reader only):
+// groups->info and groups->flat are filled, one vb2_flat per @RG line over `panel` with its viewer's sites added; the whole sample's viewer and stats are what
+// read_bam gives.  VB2_ERR_INVALID for a header whose groups x panel slots pass 2^31 - 2, before any device is touched.
+int read_bam_groups(const std::string& bam_path, const std::shared_ptr<Panel>& panel, PileupViewer* v, const vb2_mpileup_opts* mp,
+                    int device, vb2_bam_stats* stats, vb2_flat_groups* groups);
 bool bam_support();
-// the host stage alone over the markers of a .bed (vb2_bam_scan): the fetched records' virtual offsets, ascending
+// the host stage alone over the markers of a .bed (vb2_bam_scan): the fetched records' virtual offsets, ascending;
+// group_ids / groups (both or neither): the header's @RG IDs and the records' group numbers (vb2_bam_scan_ex)
 int bam_scan_file(const std::string& bam_path, const std::string& bed_path, std::vector<uint64_t>* voffsets, vb2_bam_stats* stats,
-                  std::string* sample);
+                  std::string* sample, std::vector<std::string>* group_ids = nullptr, std::vector<uint16_t>* groups = nullptr);
 bool sanity_check(const Panel& p, PileupViewer* v);
 
 }  // namespace vb2
@@ -129,11 +137,27 @@ struct vb2_flat {
     void resolve();          // BuildResolvedMarkers -> input
 };
 
+// The read groups of one BAM (vb2_flat_load_groups): per @RG line of the header, in header order, a vb2_flat over the whole
+// sample's panel.
+struct vb2_flat_groups {
+    struct Info {
+        std::string id, sm, lb, pu;
+        int64_t records = 0;                  // kept records that name the group
+        int32_t status = VB2_OK;              // VB2_OK, VB2_ERR_SANITY, or VB2_GROUP_NO_BASE
+    };
+    std::vector<Info> info;
+    std::vector<std::unique_ptr<vb2_flat>> flat;
+    int64_t unassigned = 0;                   // kept records of no group
+    double seconds_device = 0, seconds_copyback = 0;      // of the groups' part of the load alone
+};
+
 namespace vb2 {
+// <prefix>.selfRG: .selfSM's header and one row per group; est[g] is read where searched[g] != 0
+int write_selfrg(const std::string& prefix, const vb2_flat_groups& groups, const vb2_estimate* est, const uint8_t* searched);
 int write_ancestry(const std::string& prefix, int numPC, const double* pc, const double* pc2);
 int write_selfsm(const std::string& prefix, const vb2_flat& f, const vb2_estimate& est,
                  bool pileup_input);
-int write_pileup(const std::string& prefix, const vb2_flat& f);
+int write_pileup(const std::string& prefix, const vb2_flat& f);      // <prefix>.Pileup
 void print_summary(const char* title, int numPC, const vb2_estimate& est);
 // <prefix>.PairFit (vb2_cohort_run_paired): names [num_sample], fit [num_pair]
 int write_pair_fit(const std::string& prefix, int num_pair, const char* const* names, const vb2_pair_fit* fit);

@@ -454,6 +454,22 @@ __device__ __forceinline__ void lane_pair8_u32(unsigned x, unsigned& own, unsign
     own = r[0];
     other = r[1];
 }
+// The same exchange as a reduce-scatter (eval_body, EPI_SCATTER): a lane holds a dword of TWO points, p0 and p1.  The odd rows
+// swap their quads of both in place, as above; v_permlane16_swap then swaps the odd rows of its first operand, p0, with the even
+// rows of its second, p1.  An even-row lane ends with {own p0, partner's p0} -- lane_pair8_u32's pair of point 0 --, the odd-row
+// lane sixteen above it with {that even lane's p1, its partner's p1} -- the pair of point 1 that lane_pair8_u32 leaves in the
+// even-row lane, in the same order.  The odd rows carry point 1 under the even rows' labelling (marker m - 8, slot parity flipped),
+// through the later exchanges -- all inside a row -- as copies of the even rows did.  Five moves per dword of two points, not six.
+__device__ __forceinline__ void lane_scatter8_u32(unsigned p0, unsigned p1, unsigned& own, unsigned& other)
+{
+    const int a0 = __builtin_amdgcn_update_dpp((int)p0, (int)p0, 0x141, 0xa, 0xf, false);          // odd rows: row_half_mirror
+    const unsigned z0 = (unsigned)__builtin_amdgcn_update_dpp(a0, a0, 0x1B, 0xa, 0xf, false);      // odd rows: quad_perm [3,2,1,0]
+    const int a1 = __builtin_amdgcn_update_dpp((int)p1, (int)p1, 0x141, 0xa, 0xf, false);
+    const unsigned z1 = (unsigned)__builtin_amdgcn_update_dpp(a1, a1, 0x1B, 0xa, 0xf, false);
+    const auto r = __builtin_amdgcn_permlane16_swap(z0, z1, false, false);
+    own = r[0];
+    other = r[1];
+}
 
 // Occupancy target: one 1024-thread workgroup per CU (4 waves/SIMD, <=128 VGPRs).  Two
 // smaller workgroups per CU were measured slower: the per-alpha table is built once per
@@ -551,6 +567,14 @@ __host__ __device__ __forceinline__ bool eval_is_dynamic(const DeviceLayout& L, 
 // EPI_X8 (the same shape; the split launch takes it): the tile butterfly's exchange over marker bit 3 as DPP moves and
 // v_permlane16_swap (lane_pair8_u32) instead of ds_bpermute -- six instructions per item off the LDS pipe, which the other
 // fifteen waves' row reads fill: -1.2 % on the 48-point launch, no effect on the plain 8-point launch (HISTORY.md).
+// EPI_SCATTER (needs EPI_X8; the split launches take it): the tile butterfly as a reduce-scatter, ONE point per lane.  Marker bit 3
+// is the lane's row parity, so after the exchange over it an even 16-lane row only ever needs point 0 and an odd row point 1:
+// the odd rows swap their quads in place as for EPI_X8, both points' dwords, and v_permlane16_swap takes point 0's dword and
+// point 1's as its two operands (lane_scatter8_u32) -- an even-row lane then holds {its own point 0, its partner's}, the odd-row
+// lane sixteen above it {that even lane's point 1, its partner's}: one multiply and one add per lane where there were two, the
+// steps over bits 2, 1, 0 on one value, and the lanes of marker 0 AND the lanes sixteen above them store, each one point, in one
+// ds_write_b128.  The same two factors into every multiply: the same bits.  With it marker_lk's `lk > 0 ? lk : 1.0` moves into
+// the branch of the tiny values (a value of at least 2^-960 is positive; a NaN takes the branch): HISTORY.md, profiles/r13.
 // PD: a probability-domain context (DeviceLayout::pd; llk_kernels.h, kMaxPow): the table holds P^n rows of class ref only,
 // a marker's list is one 16-bit row offset per step, ref steps first and alt steps behind them; the six sums are PRODUCTS,
 // class alt multiplies them with the row read the other way round (g -> 2 - g, h:164-177: T[alt][q][g1][g2] is T[ref][q][2-g1][2-g2]),
@@ -575,7 +599,7 @@ __host__ __device__ __forceinline__ bool eval_is_dynamic(const DeviceLayout& L, 
 struct EvalConfig {
     static constexpr bool W16 = false, STREAM = false, LCACHE = false, PD = false;
     static constexpr int QUEUE = -1, KSEL = 0, ESH = 8, SPLIT = 0;
-    static constexpr bool READS_AHEAD = false, ITEM_AHEAD = false, EPI_X8 = false;
+    static constexpr bool READS_AHEAD = false, ITEM_AHEAD = false, EPI_X8 = false, EPI_SCATTER = false;
 };
 template <class Config, class Hook = NoHook>
 __device__ __forceinline__ void
@@ -608,11 +632,13 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
     constexpr int SLOTS = 4 / TPW;                           // candidate slots per wave
     constexpr int NP = SLOTS * BTL;
     constexpr bool kReadsAhead = PD && Config::READS_AHEAD;    // walk_pd requests a row's table reads before it multiplies
+    static_assert(!Config::EPI_SCATTER || Config::EPI_X8, "the reduce-scatter is the exchange over marker bit 3 of EPI_X8, two operands");
     static_assert(!(Config::ITEM_AHEAD || Config::EPI_X8) ||
                       (PD && MODE == 2 && QUEUE == 1 && !STREAM && !LCACHE && !W16 && std::is_same<Hook, NoHook>::value),
                   "items requested ahead, the exchange over marker bit 3: the 8-point probability-domain shape on the queue");
     constexpr bool kAhead = Config::ITEM_AHEAD && (kAblate & (kAblNoReads | kAblNoRowLoads)) == 0;      // (see the item loop)
     constexpr bool kEpiX8 = Config::EPI_X8 && (kAblate & (kAblNoReads | kAblNoMul | kAblNoEpi)) == 0;
+    constexpr bool kEpiScatter = Config::EPI_SCATTER && kEpiX8;      // (one point per lane behind the exchange over marker bit 3)
     // (items ahead: every row but a tile's first is walked from its two table ADDRESSES, taken from the ring's word before that
     // register is refilled -- row_step and walk_pd, kAt)
     constexpr bool kFixedRing = kAhead && kReadsAhead && (kAblate & kAblNoMul) == 0;
@@ -1346,8 +1372,10 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
                     const double off = fma(o2, gf[2], fma(o1, gf[1], o0 * gf[0]));
                     const double dg = fma(e2 * gf2[2], gf[2], fma(e1 * gf2[1], gf[1], (e0 * gf2[0]) * gf[0]));
                     lk = fma(cst_pd, off, dg);
+                    if constexpr (!kEpiScatter) {              // (EPI_SCATTER: in the one branch of the tiny values, below)
                     if (__builtin_expect(lk < 0x1p-960, 0)) {
                         x01 *= cst_pd; x02 *= cst_pd; x10 *= cst_pd; x12 *= cst_pd; x20 *= cst_pd; x21 *= cst_pd;
+                    }
                     }
                 } else {
                 const double s0 = fma(x02, gf2[2], fma(x01, gf2[1], e0 * gf2[0]));
@@ -1361,7 +1389,13 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
                 // of LLK apart (markers with ~1000 reads).  There the sum is redone term by term in the
                 // reference's own order (g1 outer, g2 inner, h:307-309), as round 1 did everywhere;
                 // wave-divergent, and never taken on whole-genome depths.
-                if (__builtin_expect(lk < 0x1p-960, 0)) {
+                // (EPI_SCATTER: the select of the reference's rule below sits in this branch -- a value of at least 2^-960 is
+                // positive --, and the condition is written so that a NaN takes the branch, is not re-summed and becomes 1.0)
+                if (__builtin_expect(kEpiScatter ? !(lk >= 0x1p-960) : lk < 0x1p-960, 0)) {
+                    if (!kEpiScatter || lk < 0x1p-960) {
+                    if constexpr (PD && kEpiScatter) {
+                        x01 *= cst_pd; x02 *= cst_pd; x10 *= cst_pd; x12 *= cst_pd; x20 *= cst_pd; x21 *= cst_pd;
+                    }
                     double r = 0;
                     r += e0 * gf[0] * gf2[0];
                     r += x01 * gf[0] * gf2[1];
@@ -1373,10 +1407,12 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
                     r += x21 * gf[2] * gf2[1];
                     r += e2 * gf[2] * gf2[2];
                     lk = r;
+                    }
+                    if constexpr (kEpiScatter) lk = lk > 0 ? lk : 1.0;
                 }
                 // the reference adds log(lk) only if lk > 0 (h:310-311): a dropped marker is
                 // the factor 1
-                lk = lk > 0 ? lk : 1.0;
+                if constexpr (!kEpiScatter) lk = lk > 0 ? lk : 1.0;
                 lk_m[t] = __builtin_amdgcn_frexp_mant(lk);
                 lk_e[t] = __builtin_amdgcn_frexp_exp(lk);
             }
@@ -1781,6 +1817,32 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
         // does not depend on whether it was evaluated alone, among four, or in a group of eight.
         // Butterfly over the 16 lanes that share slot g: mantissas multiply (16 factors in
         // [0.5, 1): no underflow), exponents add as integers (three dwords per exchange, not four)
+        if constexpr (kEpiScatter) {
+            // (EPI_SCATTER: the step over marker bit 3 as a reduce-scatter -- lane_scatter8_u32: the even rows go on with point 0,
+            // the odd rows with point 1 of the even-row lane sixteen below; all 64 lanes, the idle ones carry (1.0, 0))
+            static_assert(BTL == 2, "two points per lane to scatter");
+            unsigned h0, h1, l0, l1, x0, x1;
+            lane_scatter8_u32((unsigned)__double2hiint(lk_m[0]), (unsigned)__double2hiint(lk_m[1]), h0, h1);
+            lane_scatter8_u32((unsigned)__double2loint(lk_m[0]), (unsigned)__double2loint(lk_m[1]), l0, l1);
+            lane_scatter8_u32((unsigned)lk_e[0], (unsigned)lk_e[1], x0, x1);
+            double pm = __hiloint2double((int)h0, (int)l0) * __hiloint2double((int)h1, (int)l1);
+            int pe = (int)x0 + (int)x1;
+            // (the row steps written out: of a loop over `off` the compiler kept a run-time loop with a switch over the exchanges)
+            auto row_step = [&](auto off) {                  // (an exchange inside a row: DPP moves, lane_xchg_i32)
+                pm *= lane_xchg_f64(pm, decltype(off)::value, 0);
+                pe += lane_xchg_i32(pe, decltype(off)::value, 0);
+            };
+            row_step(std::integral_constant<int, 4>());
+            row_step(std::integral_constant<int, 2>());
+            row_step(std::integral_constant<int, 1>());
+            // the lanes of marker 0 store point 0 of their slot, the lanes sixteen above them (marker 8 of the slot of the other
+            // parity) point 1 of THAT slot: {mantissa, exponent} in one 16-byte store, the slots' addresses as ever
+            if ((m & 7) == 0 && have_tile) {
+                const int t = m >> 3;
+                const size_t o = ((((size_t)grp * NVS + vs) * ntile_blk + it) * NP + (g ^ t) * BTL + t) * 2;
+                *reinterpret_cast<double2*>(tile_llk + o) = make_double2(pm, (double)pe);
+            }
+        } else {
         if constexpr (kEpiX8) {
             // (EPI_X8: the step over marker bit 3 without the LDS crossbar -- lane_pair8_u32; the steps over 4, 2, 1 follow below)
 #pragma unroll
@@ -1810,6 +1872,7 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
                 tile_llk[o + 1] = (double)lk_e[t];
             }
         }
+        }      // (!kEpiScatter)
         // next work item of this workgroup, whichever wave gets there first
         if constexpr (kAhead) idx = idx_ah;
         else idx = draw_item();

@@ -879,6 +879,96 @@ int vb2_paired_intervals_lockstep(vb2_batch_derivs_fn fn, void *user, int32_t nu
                                   const int32_t *data_has_known_af, const vb2_model *model, int32_t held, const double *fixed,
                                   const vb2_estimate *est, vb2_interval *out, int32_t *status, int64_t *num_step);
 
+/* ------------------------------------------------------------------------- *
+ * 3g. Reference bias (--RefBias).  Not in the reference (VerifyBamID 1 had --free-refBias): its
+ *     model with beta = P(an error-free read of a heterozygous genotype shows REF) in place of the constant 0.5 of
+ *     h:164-177.  g counts ALT alleles, e = 10^(-q/10):
+ *         class ref:  u(g; e, beta) = (g/6) e     + n_beta(g) (1 - e),          n_beta = {1, beta, 0}[g]
+ *         class alt:  u(g; e, beta) = ((2-g)/6) e + n_(1-beta)(2 - g) (1 - e)   -- the ref entry at 1 - beta, read mirrored
+ *         p(read | g1, g2, alpha, beta) = (alpha e1 + (1 - alpha) e2) p_err + (alpha n1 + (1 - alpha) n2) p_ok   (h:223-225)
+ *     W, GF1, GF2 and L = sum GF1[g1] GF2[g2] W[g1][g2] stay as they are; a marker counts where L > 0; LLK = sum log L.
+ *     At beta = 0.5 the entries are the reference's.  Only the entries of the four off-diagonal pairs with a heterozygous
+ *     genotype and of (het, het) depend on beta.  LLK(.; beta) of a sample is LLK(.; 1 - beta) of the sample with REF and
+ *     ALT exchanged (classes swapped, every allele frequency AF -> 1 - AF).  The domain of beta is [VB2_REFBIAS_MIN, VB2_REFBIAS_MAX] = [0.25, 0.75];
+ *     outside it the entries of this section return VB2_ERR_INVALID.
+ *     Every llk1 of this section is a LOG-LIKELIHOOD (what .selfSM prints as FREELK1: minus vb2_estimate.llk1).
+ * ------------------------------------------------------------------------- */
+#define VB2_REFBIAS_MIN 0.25
+#define VB2_REFBIAS_MAX 0.75
+#define VB2_REFBIAS_NUM_PAIR 28
+typedef struct vb2_refbias vb2_refbias;
+
+/* A set of num_row (1..65535) values of beta over the ONE resident sample of the context: one double per row, host memory.
+ * On a probability-domain context (vb2_info.layout 1) whose deepest marker's (het, het) term may fall below 2^-450 at beta =
+ * 0.5 the set is refused with VB2_ERR_INVALID -- a het factor at beta >= 0.25 is at least half its value at 0.5, so the
+ * bound of the layout (2^-900) would no longer hold; the message names the tunable pd, whose value 0 gives run words, which
+ * take any depth.  The context must outlive the set and must not be inside vb2_ctx_search_begin / vb2_ctx_search_end when
+ * the set is used. */
+int vb2_refbias_create(vb2_ctx *ctx, int32_t num_row, const double *beta, vb2_refbias **out);
+void vb2_refbias_destroy(vb2_refbias *set);
+/* One step: row r evaluates num_point[r] (0..VB2_BATCH_SLOTS) points at its beta; rows concatenated in row order as in
+ * vb2_conditioned_eval.  A point's value is the same bits whatever else the step holds and from call to call; an alpha
+ * outside [0, 1] leaves every marker out. */
+int vb2_refbias_eval(vb2_refbias *set, const int32_t *num_point, const double *pc1, const double *pc2, const double *alpha,
+                     double *llk_out);
+/* The profile refit of every row in lock-step: the reference-exact OptimizeLLK under `model` as it is (Heter, Homo,
+ * is_pc_fixed, known allele frequencies; no side is held), every evaluation at the row's beta.  is_alpha_fixed is
+ * VB2_ERR_INVALID.  est_out / status: [num_row]. */
+int vb2_refbias_optimize_llk(vb2_refbias *set, const vb2_model *model, vb2_estimate *est_out, int32_t *status);
+typedef struct vb2_refbias_info {
+    int32_t num_row;
+    int32_t num_marker;
+    int64_t device_bytes;      /* device memory the set holds beyond the context's                   */
+    int64_t num_step;          /* evaluations that reached the device (the searches' steps included)  */
+    int64_t num_launch;        /* marker-kernel launches of those steps                               */
+} vb2_refbias_info;
+int vb2_refbias_info_get(const vb2_refbias *set, vb2_refbias_info *info);
+
+/* The estimate of beta: the maximum of the profile likelihood l(beta) = max over the model's parameters of LLK(.; beta),
+ * every value of l one search of vb2_refbias_optimize_llk, found by a fixed procedure in lock-step rounds:
+ *   round 0        the nine values 0.25 + j / 16, j = 0..8 (beta = 0.5 is value 4);
+ *   rounds 1..3    the interval between the two neighbours of the best value (the lowest index on ties; a best value at
+ *                  an end of its round takes the end's neighbour as the centre, so the interval never leaves the round's
+ *                  values nor the domain); nine equally spaced values on it, of which the ends and the centre are known:
+ *                  six new searches per round, the last spacing 2^-10;
+ *   beta           the vertex of the parabola through the last round's best value and its two neighbours; that value
+ *                  itself where it is the first or last of its round (at_bound: and 0.25 or 0.75) or where the three lie
+ *                  on no concave parabola;
+ *   beta_se        sqrt(-1 / l'') from the parabola through the last round's two ends and its centre (spacing 2^-8: the
+ *                  searches' own tolerance leaves about 1e-3 nats of noise on every l); NAN where l'' is not negative;
+ *   final          one more search at beta: alpha_bias, pc, pc2, llk1_bias;  lrt = 2 (llk1_bias - l(0.5)).
+ * 27 + 1 searches in 4 + 1 lock-step calls.  A search that fails puts its status into `status` and ends the fit with
+ * VB2_ERR_INVALID. */
+typedef struct vb2_refbias_fit {
+    double beta, beta_se;
+    double alpha_bias, llk1_bias;      /* the final search; alpha as fitted (FREEMIX_BIAS = min(alpha, 1 - alpha))    */
+    double pc[VB2_MAX_PC], pc2[VB2_MAX_PC];
+    double llk1_at_half, alpha_at_half, lrt;
+    double pair_beta[VB2_REFBIAS_NUM_PAIR], pair_llk1[VB2_REFBIAS_NUM_PAIR];   /* in the order evaluated; the last: the final */
+    int64_t num_step;                  /* lock-step steps of all calls                                                */
+    int32_t at_bound;
+    int32_t num_round;                 /* 4                                                                           */
+    int32_t num_refit;                 /* searches: 28                                                                */
+    int32_t num_pair;                  /* pairs filled in                                                             */
+    int32_t status;                    /* VB2_OK, or the status of the search that failed                             */
+    int32_t reserved;
+} vb2_refbias_fit;
+/* the whole procedure on a context (one vb2_refbias set per call) */
+int vb2_refbias_fit_ctx(vb2_ctx *ctx, const vb2_model *model, vb2_refbias_fit *out);
+/* The same procedure over a caller's evaluator: no device needed.  A step calls fn once, on the calling thread's own stack,
+ * with the call's rows beta [num_row]; num_point[r] = 0 for a row that has finished.  Non-zero from fn ends the fit and is
+ * returned. */
+typedef int (*vb2_refbias_eval_fn)(void *user, int32_t num_row, const int32_t *num_point, const double *beta, const double *pc1,
+                                   const double *pc2, const double *alpha, double *llk);
+int vb2_refbias_lockstep(vb2_refbias_eval_fn fn, void *user, int32_t num_pc, const vb2_model *model, int32_t data_has_known_af,
+                         vb2_refbias_fit *out);
+/* vb2_run, then vb2_refbias_fit_ctx on the run's context under the run's model, then <output_prefix>.RefBias
+ * (tab-separated, default ostream formatting):
+ *     #SEQ_ID FREEMIX FREEMIX_BIAS REF_BIAS REF_BIAS_SE LRT FREELK1_BIAS FREELK1_HALF AT_BOUND
+ * FREEMIX is the run's own, as in .selfSM.  stdout, .selfSM and .Ancestry are what vb2_run writes, byte for byte.  One
+ * device and a searched alpha only: VB2_ERR_INVALID otherwise, before any file is read. */
+int vb2_run_refbias(const vb2_run_args *args, vb2_run_result *out, vb2_refbias_fit *fit);
+
 /* Host-side flattening only (no device): reads panel + pileup, resolves markers
  * and returns the arrays of vb2_input in library-owned memory; free with
  * vb2_flat_free.  Lets callers (tests, shard planners) inspect or slice them. */

@@ -225,6 +225,27 @@ class PairedInfo(C.Structure):
                 ("num_launch", C.c_int64)]
 
 
+VB2_REFBIAS_MIN, VB2_REFBIAS_MAX, VB2_REFBIAS_NUM_PAIR = 0.25, 0.75, 28
+# vb2_refbias_eval_fn: (user, num_row, num_point, beta, pc1, pc2, alpha, llk)
+REFBIAS_EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                              C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double))
+
+
+class RefBiasInfo(C.Structure):
+    _fields_ = [("num_row", C.c_int32), ("num_marker", C.c_int32), ("device_bytes", C.c_int64), ("num_step", C.c_int64),
+                ("num_launch", C.c_int64)]
+
+
+class RefBiasFit(C.Structure):
+    """vb2_refbias_fit: every llk1 is a log-likelihood (.selfSM's FREELK1)."""
+    _fields_ = [(n, C.c_double) for n in ("beta", "beta_se", "alpha_bias", "llk1_bias")] + \
+               [("pc", C.c_double * VB2_MAX_PC), ("pc2", C.c_double * VB2_MAX_PC)] + \
+               [(n, C.c_double) for n in ("llk1_at_half", "alpha_at_half", "lrt")] + \
+               [("pair_beta", C.c_double * VB2_REFBIAS_NUM_PAIR), ("pair_llk1", C.c_double * VB2_REFBIAS_NUM_PAIR),
+                ("num_step", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("at_bound", "num_round", "num_refit", "num_pair", "status", "reserved")]
+
+
 class ReplicateSummary(C.Structure):
     _fields_ = [("num_chrom", C.c_int32), ("num_boot", C.c_int32)] + \
                [(n, C.c_double) for n in ("jack_estimate", "jack_se", "jack_lo", "jack_hi", "boot_mean", "boot_sd",
@@ -259,6 +280,8 @@ SYMBOLS = [
     "vb2_bam_scan_ex", "vb2_bam_scan_num_group", "vb2_bam_scan_group_id", "vb2_bam_scan_record_groups",
     "vb2_flat_load_groups", "vb2_flat_groups_count", "vb2_flat_groups_id", "vb2_flat_groups_records", "vb2_flat_groups_status",
     "vb2_flat_groups_flat", "vb2_flat_groups_unassigned", "vb2_flat_groups_seconds", "vb2_flat_groups_free", "vb2_run_read_groups",
+    "vb2_refbias_create", "vb2_refbias_destroy", "vb2_refbias_eval", "vb2_refbias_optimize_llk", "vb2_refbias_info_get",
+    "vb2_refbias_fit_ctx", "vb2_refbias_lockstep", "vb2_run_refbias",
 ]
 
 _lib = None
@@ -445,6 +468,16 @@ def lib():
                                                   C.POINTER(Interval)]
     L.vb2_matched_normal_read.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_void_p,
                                           C.c_void_p]
+    L.vb2_refbias_create.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]
+    L.vb2_refbias_destroy.argtypes = [C.c_void_p]
+    L.vb2_refbias_destroy.restype = None
+    L.vb2_refbias_eval.argtypes = [C.c_void_p] * 6
+    L.vb2_refbias_optimize_llk.argtypes = [C.c_void_p, C.POINTER(Model), C.POINTER(Estimate), C.POINTER(C.c_int32)]
+    L.vb2_refbias_info_get.argtypes = [C.c_void_p, C.POINTER(RefBiasInfo)]
+    L.vb2_refbias_fit_ctx.argtypes = [C.c_void_p, C.POINTER(Model), C.POINTER(RefBiasFit)]
+    L.vb2_refbias_lockstep.argtypes = [REFBIAS_EVAL_FN, C.c_void_p, C.c_int32, C.POINTER(Model), C.c_int32, C.POINTER(RefBiasFit)]
+    L.vb2_run_refbias.argtypes = [C.POINTER(RunArgs), C.POINTER(RunResult), C.POINTER(RefBiasFit)]
+    L.vb2_debug_refbias_time.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     L.vb2_debug_paired_time.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     L.vb2_debug_paired_derivs_time.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     L.vb2_debug_replicates_time.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]

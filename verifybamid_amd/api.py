@@ -751,6 +751,93 @@ def conditioned_with_evaluator(evaluate, num_hyp, num_pc, pc1_fixed, known_af=Fa
                                 known_af, **model_kw)
 
 
+def _refbias_fit_dict(f, k):
+    n = int(f.num_pair)
+    return dict(beta=f.beta, beta_se=f.beta_se, at_bound=bool(f.at_bound), alpha_bias=f.alpha_bias,
+                freemix_bias=min(f.alpha_bias, 1 - f.alpha_bias), pc=np.array(f.pc[:k]), pc2=np.array(f.pc2[:k]),
+                llk1_bias=f.llk1_bias, llk1_at_half=f.llk1_at_half, alpha_at_half=f.alpha_at_half, lrt=f.lrt,
+                num_round=int(f.num_round), num_refit=int(f.num_refit), num_step=int(f.num_step), status=int(f.status),
+                pairs=[(f.pair_beta[i], f.pair_llk1[i]) for i in range(n)])
+
+
+class RefBias(_RowSet):
+    """vb2_refbias: the likelihood of the ONE resident sample under a reference bias -- beta = P(an error-free read of a
+    heterozygous genotype shows REF) in place of the model's 0.5 --, one beta in [0.25, 0.75] per row: evaluated for all
+    rows together and refitted in lock-step.  RefBias.fit(ctx) is the whole estimate of beta (vb2_refbias_fit_ctx).  Every
+    llk1 of a fit is a log-likelihood (.selfSM's FREELK1); the estimates of optimize() are vb2_estimate's, as everywhere."""
+    _NAME, _ROWS = "refbias", "num_row"
+
+    def __init__(self, ctx: LikelihoodContext, beta):
+        self._lib = _abi.lib()
+        self.ctx = ctx
+        self.num_pc = ctx.num_pc
+        b = np.ascontiguousarray(np.atleast_1d(np.asarray(beta, dtype=np.float64)))
+        if b.ndim != 1:
+            raise ValueError("beta must be [rows]")
+        self.num_row = int(b.shape[0])
+        h = C.c_void_p()
+        _abi.check(self._lib.vb2_refbias_create(ctx._h, self.num_row, _p(b), C.byref(h)), "vb2_refbias_create")
+        self._h = h
+
+    def info(self):
+        i = _abi.RefBiasInfo()
+        _abi.check(self._lib.vb2_refbias_info_get(self._h, C.byref(i)), "vb2_refbias_info_get")
+        return dict(num_row=i.num_row, num_marker=i.num_marker, device_bytes=int(i.device_bytes), num_step=int(i.num_step),
+                    num_launch=int(i.num_launch))
+
+    def eval(self, num_point, pc1, pc2, alpha):
+        """One step (vb2_refbias_eval): num_point [R] ints 0..8; pc1 / pc2 [P, k] and alpha [P] with P = sum(num_point), the
+        rows' points one after the other.  Returns llk [P]."""
+        return self._eval(num_point, pc1, pc2, alpha)
+
+    def optimize(self, **model_kw):
+        """The profile refit of every row in lock-step (vb2_refbias_optimize_llk): one dict per row (with "status")."""
+        m, keep = _model(known_af=self.ctx.data.known_af is not None, **model_kw)
+        est = (_abi.Estimate * self.num_row)()
+        status = (C.c_int32 * self.num_row)()
+        _abi.check(self._lib.vb2_refbias_optimize_llk(self._h, C.byref(m), est, status), "vb2_refbias_optimize_llk")
+        del keep
+        return [dict(_estimate_dict(est[r], self.num_pc), status=int(status[r])) for r in range(self.num_row)]
+
+    @staticmethod
+    def fit(ctx: LikelihoodContext, **model_kw):
+        """vb2_refbias_fit_ctx: beta, beta_se, at_bound, alpha_bias (freemix_bias: folded), pc, pc2, llk1_bias, llk1_at_half,
+        alpha_at_half, lrt, the counters and `pairs`, the 28 (beta, llk1) in the order evaluated."""
+        m, keep = _model(known_af=ctx.data.known_af is not None, **model_kw)
+        f = _abi.RefBiasFit()
+        _abi.check(_abi.lib().vb2_refbias_fit_ctx(ctx._h, C.byref(m), C.byref(f)), "vb2_refbias_fit_ctx")
+        del keep
+        return _refbias_fit_dict(f, ctx.num_pc)
+
+
+def refbias_with_evaluator(evaluate, num_pc, known_af=False, **model_kw):
+    """The estimate of beta over a Python evaluator (vb2_refbias_lockstep): no device.
+    evaluate(beta [R], num_point [R] int32, pc1 [P, k], pc2 [P, k], alpha [P]) -> llk [P], P = sum(num_point), called once
+    per step with the rows of the lock-step call in hand and the points of every row still searching.  Returns the dict of
+    RefBias.fit; a search that fails raises with its status in the message's code."""
+    k = int(num_pc)
+    err = []
+
+    def cb(_user, rows, npt, beta, p1, p2, a, out):
+        try:
+            points, P = _step_points(rows, npt, p1, p2, a, k)
+            b = np.ctypeslib.as_array(beta, (rows,)).copy()
+            np.ctypeslib.as_array(out, (P,))[:] = np.asarray(evaluate(b, *points), dtype=np.float64).reshape(P)
+            return 0
+        except Exception as exc:   # never let an exception cross the C boundary
+            err.append(exc)
+            return _abi.VB2_ERR_INVALID
+    fn = _abi.REFBIAS_EVAL_FN(cb)
+    m, keep = _model(known_af=known_af, **model_kw)
+    f = _abi.RefBiasFit()
+    rc = _abi.lib().vb2_refbias_lockstep(fn, None, k, C.byref(m), int(bool(known_af)), C.byref(f))
+    del keep
+    if err:
+        raise err[0]
+    _abi.check(rc, "vb2_refbias_lockstep")
+    return _refbias_fit_dict(f, k)
+
+
 class Paired(_RowSet):
     """vb2_paired: the likelihood of the ONE resident sample given genotype priors on BOTH components -- per hypothesis two
     float32 triples per panel marker, pi1 for the contaminant and pi2 for the intended sample; an all-zero triple falls back
@@ -1123,7 +1210,8 @@ def _set_bam(args, bam_path, mpileup):
 
 def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_sanity=False,
               known_af_path=None, device=-1, output_pileup=False, devices=None, confidence_interval=False,
-              per_chromosome=False, bootstrap=0, bam_path=None, mpileup=None, per_read_group=False, **model_kw):
+              per_chromosome=False, bootstrap=0, bam_path=None, mpileup=None, per_read_group=False, ref_bias=False,
+              **model_kw):
     """The --SVDPrefix/--PileupFile flow of execute() (vb2_run); devices=[a, b, ...] shards the
     sample's markers over those GPUs.  confidence_interval: vb2_run_interval (<output_prefix>.CI, and an
     `interval` entry in the result).  per_chromosome / bootstrap=N (seeded by seed=): vb2_run_replicates
@@ -1132,7 +1220,8 @@ def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_san
     options (min_bq, min_mq, adjust_mq, max_depth, no_orphans, incl_flags, excl_flags), None = its defaults.
     per_read_group (with bam_path): vb2_run_read_groups -- the whole sample as ever, <output_prefix>.selfRG, and a
     `read_groups` list in the result: per @RG line of the header its id, status (0, VB2_ERR_SANITY or 1 = no base), records,
-    the estimate's entries (zero when not searched) and num_site, num_bases, avg_depth."""
+    the estimate's entries (zero when not searched) and num_site, num_bases, avg_depth.
+    ref_bias: vb2_run_refbias (<output_prefix>.RefBias, and a `ref_bias` entry in the result: the dict of RefBias.fit)."""
     args, keep = _run_args(svd_prefix, pileup_path, num_pc, disable_sanity, known_af_path,
                            output_prefix, device, output_pileup, devices=devices, **model_kw)
     _set_bam(args, bam_path, mpileup)
@@ -1140,7 +1229,13 @@ def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_san
     ci = _abi.Interval() if confidence_interval else None
     summary = None
     groups = None
-    if per_read_group:
+    bias = None
+    if ref_bias:
+        if confidence_interval or per_chromosome or bootstrap or per_read_group:
+            raise ValueError("ref_bias cannot be combined with confidence_interval, per_chromosome, bootstrap or per_read_group")
+        bias = _abi.RefBiasFit()
+        _abi.check(_abi.lib().vb2_run_refbias(C.byref(args), C.byref(res), C.byref(bias)), "vb2_run_refbias")
+    elif per_read_group:
         if confidence_interval or per_chromosome or bootstrap:
             raise ValueError("per_read_group cannot be combined with confidence_interval, per_chromosome or bootstrap")
         L = _abi.lib()
@@ -1176,6 +1271,8 @@ def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_san
         out["replicates"] = {name: getattr(summary, name) for name, _ in _abi.ReplicateSummary._fields_}
     if groups is not None:
         out["read_groups"] = groups
+    if bias is not None:
+        out["ref_bias"] = _refbias_fit_dict(bias, num_pc)
     out.update(num_marker=res.num_marker, num_site=res.num_site, num_bases=int(res.num_bases),
                avg_depth=res.avg_depth, sd_depth=res.sd_depth, seconds_load=res.seconds_load,
                seconds_optimize=res.seconds_optimize)

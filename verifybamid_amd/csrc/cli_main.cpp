@@ -29,6 +29,9 @@
 // --FindSource --RefitSource also writes <Output>.SourceFit: every sample's FREEMIX refitted GIVEN the genotypes of its best
 // candidate, and the likelihood difference to the anonymous fit (vb2_cohort_run_source_fits; not with --FixAlpha,
 // --CohortInterval or several --Devices).
+// --RefBias estimates the reference bias beta -- the share of REF among the error-free reads of a heterozygous genotype,
+// 0.5 in the model -- jointly with FREEMIX and writes <Output>.RefBias (vb2_run_refbias; one sample,
+// one device, a searched alpha).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -113,6 +116,7 @@ int main(int argc, char** argv)
     double normalHomMin = 0.99;
     bool pairInterval = false;
     bool perReadGroup = false;
+    bool refBias = false;
     // "Pileup Options" (main.cpp:176-187), defaults main.cpp:81-96 (MPLP_REALN | MPLP_SMART_OVERLAPS; UNMAP | SECONDARY |
     // QCFAIL | DUP): they shape what --BamFile input becomes and, as in the reference, do nothing to --PileupFile input
     int minBQ = 13, minMQ = 2, adjustMQ = 40, maxDepth = 8000, inclFlags = (1 << 4) | (1 << 10), exclFlags = 0x4 | 0x100 | 0x200 | 0x400;
@@ -195,6 +199,9 @@ int main(int argc, char** argv)
         // not in the reference (VerifyBamID 1 had it): FREEMIX of every read group of the --BamFile header beside the whole
         // sample's, each from the group's own pileup, the groups searched in lock-step (vb2_run_read_groups), to <Output>.selfRG
         {"PerReadGroup", {Flag::kBool, &perReadGroup, false}},
+        // not in the reference (VerifyBamID 1 had --free-refBias): the reference bias of the read model estimated jointly with
+        // FREEMIX by profile likelihood, 28 refits of the one resident sample in lock-step (vb2_run_refbias), to <Output>.RefBias
+        {"RefBias", {Flag::kBool, &refBias, false}},
     };
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
@@ -225,6 +232,18 @@ int main(int argc, char** argv)
         if (f.kind == Flag::kInt) *static_cast<int*>(f.dst) = std::atoi(v);
         else if (f.kind == Flag::kDouble) *static_cast<double*>(f.dst) = std::atof(v);
         else *static_cast<std::string*>(f.dst) = v;
+    }
+    if (refBias) {                                                      // one sample, one device, a searched alpha
+        if (PileupList != "Empty")
+            fatal("--RefBias cannot be combined with --PileupList: the reference bias is estimated for one sample per run");
+        if (perReadGroup) fatal("--RefBias cannot be combined with --PerReadGroup: run them separately");
+        if (flags["FixAlpha"].seen)
+            fatal("--RefBias cannot be combined with --FixAlpha: a fixed alpha leaves the refits nothing to estimate");
+        if (confidenceInterval) fatal("--RefBias cannot be combined with --ConfidenceInterval: run them separately");
+        if (perChromosome || flags["Bootstrap"].seen)
+            fatal("--RefBias cannot be combined with --PerChromosome / --Bootstrap: run them separately");
+        if (Devices != "Empty" && Devices.find(',') != std::string::npos)
+            fatal("--RefBias cannot be combined with more than one --Devices: the refits read one resident sample on one device");
     }
     if (confidenceInterval) {                                           // single-sample, single-device runs only
         if (PileupList != "Empty")
@@ -499,7 +518,8 @@ int main(int argc, char** argv)
     vb2_run_result res;
     vb2_interval ci;
     int32_t numGroup = 0;
-    const int rc = perReadGroup                     ? vb2_run_read_groups(&args, &res, 0, nullptr, &numGroup)
+    const int rc = refBias                          ? vb2_run_refbias(&args, &res, nullptr)
+                   : perReadGroup                   ? vb2_run_read_groups(&args, &res, 0, nullptr, &numGroup)
                    : (perChromosome || bootstrap > 0) ? vb2_run_replicates(&args, perChromosome ? 1 : 0, bootstrap, &res, nullptr)
                    : confidenceInterval             ? vb2_run_interval(&args, &res, &ci)
                                                     : vb2_run(&args, &res);

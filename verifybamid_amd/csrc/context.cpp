@@ -1818,6 +1818,7 @@ int fill_context(Context* c, const vb2_input* in, const Modes& md, const Tunable
     L.reserved1 = 0;
     L.pd = md.pd ? 1 : 0;
     c->num_code_seen = cd.num_code_seen;
+    c->pd_max_bound = a.max_bound;
     L.num_code = cd.num_code;
     L.row_bytes = rw.row_bytes;
     L.num_mt = num_mt;

@@ -153,6 +153,9 @@ public:
     void* d_codes16_own = nullptr;
     int64_t cohort_bytes = 0;                 // device bytes one cohort step streams for this sample
     int num_code_seen = 0;                    // distinct (class, quality) codes of the data (vb2_info::num_code)
+    // the flatten's largest kPdMaxBound-style bound of a counted marker (0 where the probability domain was not asked for):
+    // what RefBias::create holds against kPdMaxBound / 2 (internal: vb2_info does not carry it)
+    double pd_max_bound = 0.0;
     // Gradient and Hessian of the LLK at B points (deriv_kernels.hip; host pointers, synchronous): llk[B], grad[B][2k+1],
     // hess[B][2k+1][2k+1] in the order pc1[0..k) pc2[0..k) alpha.  Scratch from the slab cache on the first call (d_deriv),
     // kept for the context's lifetime.  Not between resident_begin and resident_end.  Defined in derivs.cpp.

@@ -7,8 +7,10 @@ both `s_setprio 1` (a wave enters its read loop) and `s_setprio 0` (it leaves it
 the branch of the tiny likelihoods, the refills of a long list -- lie outside the span and are not counted.  Counts are STATIC:
 an instruction of the walk's unrolled row body counts once however many rows a tile has.  Classes: v_mul_f64 between the two
 s_setprio (the walk's multiplies), every other FP64 arithmetic instruction (v_*_f64 but compares), DPP moves (v_mov_b32_dpp),
-v_permlane16_swap, ds_read_b128, other LDS instructions (ds_*), v_cndmask, other vector ALU (v_*), vector memory
-(global_* / buffer_* / flat_*), scalar and the rest (s_*).  --list prints the span's instructions behind the table.
+v_permlane16_swap, ds_read_b128, other LDS instructions (ds_*), v_cndmask, v_lshl_add_u64 (a 64-bit address made per lane), other
+vector ALU (v_*), vector memory by the form of its address -- a scalar base or a buffer descriptor with a 32-bit vector offset
+(global_* with an SGPR pair, buffer_*) against a 64-bit vector address (global_* ... off, flat_*) --, s_nop, scalar and the rest
+(s_*).  --list prints the span's instructions behind the table.
 """
 import re
 import subprocess
@@ -18,7 +20,7 @@ import tempfile
 import isa_diff
 
 CLASSES = ("v_mul_f64 in the walk", "other FP64", "DPP moves", "v_permlane16_swap", "ds_read_b128", "other LDS", "v_cndmask",
-           "other VALU", "vector memory", "scalar and the rest")
+           "v_lshl_add_u64", "other VALU", "vector memory, scalar base", "vector memory, vector address", "s_nop", "scalar and the rest")
 
 
 def disassemble(co):
@@ -73,10 +75,16 @@ def classify(text, in_walk):
         return "other LDS"
     if re.match(r"v_\w+_f64", op) and not op.startswith("v_cmp"):
         return "v_mul_f64 in the walk" if in_walk and op.startswith("v_mul_f64") else "other FP64"
+    if op.startswith("v_lshl_add_u64"):
+        return "v_lshl_add_u64"
     if op.startswith("v_"):
         return "other VALU"
     if op.startswith(("global_", "buffer_", "flat_", "scratch_")):
-        return "vector memory"
+        # (global_load v, v[a:b], off: the address is a 64-bit vector pair; global_load v, v, s[a:b] and buffer_*: a 32-bit offset)
+        vector_address = op.startswith("flat_") or (op.startswith("global_") and re.search(r",\s*off\b", text) is not None)
+        return "vector memory, vector address" if vector_address else "vector memory, scalar base"
+    if op.startswith("s_nop"):
+        return "s_nop"
     return "scalar and the rest"
 
 
@@ -97,9 +105,10 @@ def main():
         counts[classify(t, walk)] += 1
     print("%s\n  %d instructions in the kernel, item loop: instructions %d..%d (%d)" % (name.split("(")[0], len(code), lo, hi, len(span)))
     for c in CLASSES:
-        print("  %-24s %5d" % (c, counts[c]))
-    valu = sum(counts[c] for c in ("v_mul_f64 in the walk", "other FP64", "DPP moves", "v_permlane16_swap", "v_cndmask", "other VALU"))
-    print("  %-24s %5d\n  %-24s %5d" % ("all vector ALU", valu, "all LDS", counts["ds_read_b128"] + counts["other LDS"]))
+        print("  %-30s %5d" % (c, counts[c]))
+    valu = sum(counts[c] for c in ("v_mul_f64 in the walk", "other FP64", "DPP moves", "v_permlane16_swap", "v_cndmask", "v_lshl_add_u64",
+                                   "other VALU"))
+    print("  %-30s %5d\n  %-30s %5d" % ("all vector ALU", valu, "all LDS", counts["ds_read_b128"] + counts["other LDS"]))
     if "--list" in sys.argv[1:]:
         for a, t in span:
             print("    %06x  %s" % (a, t))

@@ -575,6 +575,15 @@ __host__ __device__ __forceinline__ bool eval_is_dynamic(const DeviceLayout& L, 
 // steps over bits 2, 1, 0 on one value, and the lanes of marker 0 AND the lanes sixteen above them store, each one point, in one
 // ds_write_b128.  The same two factors into every multiply: the same bits.  With it marker_lk's `lk > 0 ? lk : 1.0` moves into
 // the branch of the tiny values (a value of at least 2^-960 is positive; a NaN takes the branch): HISTORY.md, profiles/r13.
+// ADDR_SCALAR (needs ITEM_AHEAD; the split launches take it): what the item loop computes per lane although it is the same in every
+// lane, or a scalar plus a constant of the lane, goes to the scalar unit.  The nine per-marker constants are loaded through buffer
+// descriptors, one per column, built by scalar instructions from the layout's pointers (the opaque-scalar base of the other
+// kernels compiles to a 64-bit vector add in front of every load); the list words through one descriptor with the lane's word in
+// the vector offset and the row -- the tile's first row, one v_readfirstlane per item, plus the row in the tile -- in the scalar
+// offset; the tile's record is decoded by scalar shifts and selects; and the queue is drawn by lane 0 alone under an exec mask of
+// one bit, where the compiler's wave-aggregated atomic counts lanes for an add that only ever has one.  The same addresses, no
+// arithmetic on a likelihood: the same bits.  44 vector instructions fewer in the item loop of llk_eval_split6_kernel<4>
+// (tools/item_census.py: 511 -> 467; HISTORY.md, profiles/r14).
 // PD: a probability-domain context (DeviceLayout::pd; llk_kernels.h, kMaxPow): the table holds P^n rows of class ref only,
 // a marker's list is one 16-bit row offset per step, ref steps first and alt steps behind them; the six sums are PRODUCTS,
 // class alt multiplies them with the row read the other way round (g -> 2 - g, h:164-177: T[alt][q][g1][g2] is T[ref][q][2-g1][2-g2]),
@@ -599,7 +608,7 @@ __host__ __device__ __forceinline__ bool eval_is_dynamic(const DeviceLayout& L, 
 struct EvalConfig {
     static constexpr bool W16 = false, STREAM = false, LCACHE = false, PD = false;
     static constexpr int QUEUE = -1, KSEL = 0, ESH = 8, SPLIT = 0;
-    static constexpr bool READS_AHEAD = false, ITEM_AHEAD = false, EPI_X8 = false, EPI_SCATTER = false;
+    static constexpr bool READS_AHEAD = false, ITEM_AHEAD = false, EPI_X8 = false, EPI_SCATTER = false, ADDR_SCALAR = false;
 };
 template <class Config, class Hook = NoHook>
 __device__ __forceinline__ void
@@ -639,6 +648,8 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
     constexpr bool kAhead = Config::ITEM_AHEAD && (kAblate & (kAblNoReads | kAblNoRowLoads)) == 0;      // (see the item loop)
     constexpr bool kEpiX8 = Config::EPI_X8 && (kAblate & (kAblNoReads | kAblNoMul | kAblNoEpi)) == 0;
     constexpr bool kEpiScatter = Config::EPI_SCATTER && kEpiX8;      // (one point per lane behind the exchange over marker bit 3)
+    static_assert(!Config::ADDR_SCALAR || Config::ITEM_AHEAD, "scalar row offsets: the record's words are taken where the rows ahead are requested");
+    constexpr bool kAddrScalar = Config::ADDR_SCALAR && kAhead;      // (the item loop's uniform address arithmetic on the scalar unit)
     // (items ahead: every row but a tile's first is walked from its two table ADDRESSES, taken from the ring's word before that
     // register is refilled -- row_step and walk_pd, kAt)
     constexpr bool kFixedRing = kAhead && kReadsAhead && (kAblate & kAblNoMul) == 0;
@@ -1030,6 +1041,29 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
     g_cdouble* const g_ud = (g_cdouble*)L.ud;
     g_cdouble* const g_mu = (g_cdouble*)L.mu;
     g_cdouble* const g_kaf = (g_cdouble*)known_af_p;
+    // ADDR_SCALAR: the same arrays through buffer descriptors -- kernel arguments, so wave-uniform and built by the scalar unit.
+    // A column of the per-marker constants has a descriptor of its OWN: base + column x m_pad x 8 in 64-bit scalar arithmetic
+    // (m_pad < 2^29: a 32-bit scalar offset would wrap at the third column of the largest contexts), m_pad x 8 bytes long, the lane's
+    // part -- its marker's byte offset -- in the 32-bit vector offset.  The run lists: one descriptor without a length of its own
+    // (the layout does not carry the list's; the array's padding rows bound the reads past a tile as before), the lane's word of a
+    // row in the vector offset, the row in the scalar one (a sample's list stays below 4 GiB: Context::create).
+    constexpr int kRsrcFlags = 0x00020000;                // (raw buffer, 32-bit data format: untyped loads)
+    const uint32_t col_bytes = (uint32_t)(mp * 8);
+    auto col_rsrc = [&](const double* base_) {
+        return __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(base_), 0, (int)col_bytes, kRsrcFlags);
+    };
+    const uint32_t lane_word = (uint32_t)m * kLaneBytes;  // this lane's word of a row of the list
+    auto codes_rsrc = [&] {
+        if constexpr (Config::ADDR_SCALAR && KSEL == 0) {       // (kItemScalars, below: the quad's registers free between the loads)
+            unsigned long long b_ = (unsigned long long)(W16 ? L.codes16 : L.codes);
+            asm volatile("" : "+s"(b_));
+            return __builtin_amdgcn_make_buffer_rsrc((void*)b_, 0, -1, kRsrcFlags);
+        }
+        return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint2*>(W16 ? L.codes16 : L.codes), 0, -1, kRsrcFlags);
+    };
+    auto list_word = [&](const uint32_t row_, const uint32_t ahead_) -> uint32_t {      // row row_ + ahead_ (a constant: the instruction's offset)
+        return __builtin_amdgcn_raw_buffer_load_b32(codes_rsrc(), lane_word + ahead_ * kRowBytes, row_ * kRowBytes, 0);
+    };
     // The per-marker likelihoods of a work item are MULTIPLIED (mantissa x 2^exponent): over
     // the 16 markers of the tile by a butterfly, then slot by slot in the block reduction.
     auto tile_product = [&](ScaledProd* p, bool cross) {  // over the 16 lanes sharing slot g (+ the item's other tiles)
@@ -1128,6 +1162,25 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
         return have_ ? owned_tile(OSH, blk, nblk, it_) : owned_tile(OSH, blk, nblk, 0u);
     };
     auto draw_item = [&]() -> uint32_t {                             // the workgroup's next item, whichever wave asks first
+        if constexpr (kAddrScalar) {
+            // (every wave draws one item, and all its lanes are here: lane 0 alone, under an exec mask of one bit, adds 1 -- the
+            // compiler's wave-aggregated form counts the lanes and finds the first for an atomic that only ever has one.  The
+            // wait is the one the compiler placed: the record's request below needs the item.  Written out because the counter
+            // of LDS returns is not the compiler's to track inside a statement; exec is put back before the statement ends.)
+            uint32_t nxt_, one_;
+            unsigned long long exec_;
+            asm volatile("s_mov_b64 %2, exec\n\t"
+                         "s_mov_b64 exec, 1\n\t"
+                         "v_mov_b32 %1, 1\n\t"
+                         "ds_add_rtn_u32 %1, %3, %1\n\t"
+                         "s_waitcnt lgkmcnt(0)\n\t"
+                         "v_readfirstlane_b32 %0, %1\n\t"
+                         "s_mov_b64 exec, %2"
+                         : "=&s"(nxt_), "=&v"(one_), "=&s"(exec_)
+                         : "v"(lds_byte_addr(queue))
+                         : "memory");
+            return nxt_;
+        }
         uint32_t nxt = 0;
         if (lane == 0) nxt = atomicAdd(queue, 1u);
         return (uint32_t)__builtin_amdgcn_readfirstlane(nxt);
@@ -1291,6 +1344,17 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
             }
         }
     };
+    // (the number of components, the columns' length and the known-AF pointer AS AN ITEM SEES THEM.  The same values in every
+    // kernel; the ADDR_SCALAR kernels of KSEL 0, where they are run-time values, pass them through opaque scalar registers once per
+    // item -- kItemScalars, in the item loop --, so that what is derived from them is computed by a scalar instruction or two where
+    // it is used.  Hoisted out of the item loop, the tests `kk < k` and `known_af == nullptr` were six 64-bit masks, the columns'
+    // bases eighteen registers and the tail of the projection's loop four more, kept across the whole loop: 28 to 30 scalar
+    // registers of those three kernels went to vector lanes, 14 to 31 before ADDR_SCALAR.  With the hand-off's arguments read again
+    // behind the item loop -- see there -- none does.)
+    constexpr bool kItemScalars = kAddrScalar && KSEL == 0;
+    int k_item = k;
+    size_t mp_item = mp;
+    unsigned long long kaf_item = (unsigned long long)known_af_p;
     // ---- per-marker epilogue: a marker's likelihood as (mantissa, exponent) per point, from its six sums per point ----
     auto marker_lk = [&](const bool live, const uint32_t pos, const double* acc, const double e0, const double e1, const double e2,
                          const double* udr, const double mur, const uint32_t my_ptq, double* lk_m, int* lk_e, const double cst_pd) {
@@ -1304,7 +1368,7 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
         }
         if (live) {
             double af1[BTL], af2[BTL];
-            if (known_af_p) {
+            if (kaf_item) {
                 const double a = g_kaf[pos];
 #pragma unroll
                 for (int t = 0; t < BTL; ++t) af1[t] = af2[t] = a;
@@ -1317,18 +1381,18 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
                 auto project = [&](int kk, double uu) {
                     if constexpr (BTL == 2) {              // both points' coefficient in one ds_read_b128
                         const vdouble2 c1 = *reinterpret_cast<lds_cdouble2*>(my_ptq + (uint32_t)kk * 16u);
-                        const vdouble2 c2 = *reinterpret_cast<lds_cdouble2*>(my_ptq + (uint32_t)(k + kk) * 16u);
+                        const vdouble2 c2 = *reinterpret_cast<lds_cdouble2*>(my_ptq + (uint32_t)(k_item + kk) * 16u);
                         af1[0] = fma(uu, c1.x, af1[0]); af1[1] = fma(uu, c1.y, af1[1]);
                         af2[0] = fma(uu, c2.x, af2[0]); af2[1] = fma(uu, c2.y, af2[1]);
                     } else {
                         af1[0] = fma(uu, *reinterpret_cast<lds_cdouble*>(my_ptq + (uint32_t)kk * 8u), af1[0]);
-                        af2[0] = fma(uu, *reinterpret_cast<lds_cdouble*>(my_ptq + (uint32_t)(k + kk) * 8u), af2[0]);
+                        af2[0] = fma(uu, *reinterpret_cast<lds_cdouble*>(my_ptq + (uint32_t)(k_item + kk) * 8u), af2[0]);
                     }
                 };
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk)
-                    if (kk < k) project(kk, udr[kk]);                       // rows loaded before the read loop
-                for (int kk = 4; kk < k; ++kk) project(kk, g_ud[(size_t)kk * mp + pos]);
+                    if (kk < k_item) project(kk, udr[kk]);                       // rows loaded before the read loop
+                for (int kk = 4; kk < k_item; ++kk) project(kk, g_ud[(size_t)kk * mp_item + pos]);
                 const double mu = mur;
 #pragma unroll
                 for (int t = 0; t < BTL; ++t) {
@@ -1489,8 +1553,16 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
         const uint32_t mt_ = have_ ? owned_tile(OSH, vb0 + vs_ * vstep, nblk, it_) : 0u;
         rec_ah = g_rec[mt_];
     };
+    uint32_t rec_ah_x = 0u, rec_ah_y = 0u;                // ADDR_SCALAR: the record's two words in scalar registers -- one v_readfirstlane each per item
     auto request_rows_ahead = [&]() {
         // (a tile shorter than three rows: the rows behind it, never consumed -- the array ends in padding rows)
+        if constexpr (kAddrScalar) {
+            rec_ah_x = (uint32_t)__builtin_amdgcn_readfirstlane((int)rec_ah.x);
+            rec_ah_y = (uint32_t)__builtin_amdgcn_readfirstlane((int)rec_ah.y);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) w_ah[j] = list_word(rec_ah_x, (uint32_t)j);
+            return;
+        }
         const uint32_t cb_ = rec_ah.x * kRowBytes + (uint32_t)m * kLaneBytes;
 #pragma unroll
         for (int j = 0; j < 3; ++j)
@@ -1563,18 +1635,42 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
         auto at = [&](g_cdouble* base_) -> double {
             // (the base through an opaque scalar register: else the compiler re-associates base + offset + column stride
             // and adds the uniform stride in 64-bit vector arithmetic)
+            // (ADDR_SCALAR: the column's descriptor, this offset in the vector offset -- no vector instruction but the load;
+            // a dead lane reads position 0 as before, and the descriptor's length is the column's)
+            if constexpr (kAddrScalar) {
+                // (the base through an opaque scalar register here too: nine descriptors kept across the loop are 36 scalar
+                // registers, and the kernels of three workgroups to a set then spill some; a descriptor is two scalar moves)
+                unsigned long long b_ = (unsigned long long)base_;
+                asm volatile("" : "+s"(b_));
+                const auto v_ = __builtin_amdgcn_raw_buffer_load_b64(col_rsrc((const double*)b_), boff, 0, 0);
+                return __hiloint2double((int)v_[1], (int)v_[0]);
+            }
             unsigned long long b_ = (unsigned long long)base_;
             asm volatile("" : "+s"(b_));
             return *reinterpret_cast<g_cdouble*>(reinterpret_cast<__attribute__((address_space(1))) const char*>(b_) + boff);
         };
-        const double cst = PIPE ? cst_nx : at(g_ediag);
-        const double e0 = at(g_ediag + mp), e1 = at(g_ediag + 2 * mp), e2 = at(g_ediag + 3 * mp);
+        // (column c_ of an array.  kItemScalars: its base from the item's own copy of the columns' length -- two scalar adds a load,
+        // nothing kept across the loop but the arrays' pointers)
+        if constexpr (kItemScalars) asm volatile("" : "+s"(mp_item));
+        const unsigned long long cs_ = (unsigned long long)mp_item * 8ull;
+        auto at_col = [&](g_cdouble* arr_, const int c_) -> double {
+            if constexpr (kItemScalars) {
+                unsigned long long b_ = (unsigned long long)arr_ + (unsigned long long)c_ * cs_;
+                asm volatile("" : "+s"(b_));
+                const auto v_ = __builtin_amdgcn_raw_buffer_load_b64(col_rsrc((const double*)b_), boff, 0, 0);
+                return __hiloint2double((int)v_[1], (int)v_[0]);
+            }
+            return at(arr_ + (size_t)c_ * mp);
+        };
+        const double cst = PIPE ? cst_nx : at_col(g_ediag, 0);
+        const double e0 = at_col(g_ediag, 1), e1 = at_col(g_ediag, 2), e2 = at_col(g_ediag, 3);
 
         // (the panel row of the marker too: up to four UD columns and the mean)
         double udr[4], mur = 0.0;
+        if constexpr (kItemScalars) { asm volatile("" : "+s"(k_item)); asm volatile("" : "+s"(kaf_item)); }
 #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) udr[kk] = (!known_af_p && kk < k) ? at(g_ud + (size_t)kk * mp) : 0.0;
-        if (!known_af_p) mur = at(g_mu);
+        for (int kk = 0; kk < 4; ++kk) udr[kk] = (!kaf_item && kk < k_item) ? at_col(g_ud, kk) : 0.0;
+        if (!kaf_item) mur = at_col(g_mu, 0);
 
         // the six off-diagonal sums start from the marker's "other base" constant (it is part of
         // every genotype pair's sum, h:299-303), so the epilogue needs no separate addition
@@ -1614,10 +1710,13 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
         // a scalar when TPW == 1.  PD: {ref steps | all steps << 16}: the tile's markers have their ref steps at [0, s1) and
         // their alt steps at [s1, s2), two steps to a row (walk_pd)
         // (one tile per wave: both are the same in every lane, and the compiler is told so -- the branches on them are scalar)
-        const int steps_ref_v = PD ? (have_tile ? (int)(rec.y & 0xffffu) : 0) : 0;
-        const int rows_v = have_tile ? (PD ? (int)(((rec.y >> 16) + (W16 ? 3u : 1u)) >> (W16 ? 2 : 1)) : (int)rec.y) : 0;
-        const int steps_ref = (PD && TPW == 1) ? __builtin_amdgcn_readfirstlane(steps_ref_v) : steps_ref_v;
-        const int rows = (PD && TPW == 1) ? __builtin_amdgcn_readfirstlane(rows_v) : rows_v;
+        // (ADDR_SCALAR: from the record's words as request_rows_ahead left them in scalar registers -- shifts and selects of the
+        // scalar unit; the tile's first row for load_row too)
+        const uint32_t rec_sx = rec_ah_x, rec_sy = kAddrScalar ? rec_ah_y : rec.y;
+        const int steps_ref_v = PD ? (have_tile ? (int)(rec_sy & 0xffffu) : 0) : 0;
+        const int rows_v = have_tile ? (PD ? (int)(((rec_sy >> 16) + (W16 ? 3u : 1u)) >> (W16 ? 2 : 1)) : (int)rec_sy) : 0;
+        const int steps_ref = (PD && TPW == 1 && !kAddrScalar) ? __builtin_amdgcn_readfirstlane(steps_ref_v) : steps_ref_v;
+        const int rows = (PD && TPW == 1 && !kAddrScalar) ? __builtin_amdgcn_readfirstlane(rows_v) : rows_v;
         // (ONE sample's pileup sits in L2, and a deep prefetch costs more than it hides there: the loads run past the
         // tile's last row -- up to kPf useless row loads per item of 6..16 rows -- and every block of kPf rows begins
         // by waiting for all of them.  Measured on one box, depth 8 / 4 / 2: 48-point launch 74.9 / 74.4 / 76.6 us;
@@ -1632,6 +1731,8 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
                 const uint32_t r0 = ((uint32_t)m * 7u + (uint32_t)j * 2u) % (uint32_t)nrow, r1 = ((uint32_t)m * 7u + (uint32_t)j * 2u + 1u) % (uint32_t)nrow;
                 return (r0 * (uint32_t)row_bytes) | ((r1 * (uint32_t)row_bytes) << 16);
             }
+            // (ADDR_SCALAR: every caller asks for row r + kPf of the ring -- the kPf rides in the instruction's offset)
+            if constexpr (kAddrScalar) return list_word(rec_sx + (uint32_t)(j - kPf), (uint32_t)kPf);
             if constexpr (LCACHE && PD) return *reinterpret_cast<lds_cuint*>(crow + (uint32_t)j * kRowBytes);
             else if constexpr (LCACHE) return *reinterpret_cast<lds_cuint2v*>(crow + (uint32_t)j * kRowBytes);
             else {
@@ -1881,6 +1982,35 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
         for (uint32_t grp = grp_wave; grp < (uint32_t)ngrp; ++grp) flush_wave(grp);
     }
 
+    if constexpr (Config::ADDR_SCALAR && KSEL == 0) {
+        // (kItemScalars: what only the code from here on needs of the kernel's arguments -- where the sums go -- is read again from the
+        // kernel-argument segment instead of being kept in ten scalar registers across the item loop.  SplitKernArgs restates the
+        // split kernels' parameter list, llk_kernels.hip: a by-value argument sits at its natural alignment, as a member does.)
+        struct SplitKernArgs {
+            DeviceLayout L;
+            const double* points;
+            int num_valid;
+            double* partials;
+            double* llk_out;
+            unsigned int* ticket;
+            unsigned long long* done_flag;
+            unsigned long long done_seq;
+            int ngrp;
+        };
+        static_assert(SPLIT != 0, "the parameter list restated here is the split kernels'");
+        static_assert(offsetof(SplitKernArgs, partials) == sizeof(DeviceLayout) + 16 && offsetof(SplitKernArgs, done_seq) == sizeof(DeviceLayout) + 48,
+                      "the hand-off's arguments behind the layout, the points and their count");
+        typedef __attribute__((address_space(4))) const SplitKernArgs k_args;
+        unsigned long long ka_ = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka_));
+        k_args* const a_ = (k_args*)ka_;
+        partials = a_->partials;
+        llk_out = a_->llk_out;
+        ticket = a_->ticket;
+        done_flag = a_->done_flag;
+        done_seq = a_->done_seq;
+        num_valid = a_->num_valid;
+    }
     if (stamps && lane == 0 && !hook_mine) atomicMax(&stamps[4], wall_clock64());   // the wave that is done with its tiles last
     // ---- deterministic block reduction -> one partial per (point, block) ----
     const uint32_t nres = dyn ? ntile_blk : (uint32_t)nwave;   // result slots per group

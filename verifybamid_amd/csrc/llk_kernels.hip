@@ -26,11 +26,12 @@ struct PlainEval : EvalConfig {
     static constexpr bool PD = PD_, READS_AHEAD = true;
 };
 // ... the split launch: the 8-point probability-domain shape on the queue with everything that shape has; its tile butterfly
-// is a reduce-scatter, one point per lane (EPI_SCATTER)
+// is a reduce-scatter, one point per lane (EPI_SCATTER), and its item loop's uniform address arithmetic is the scalar unit's
+// (ADDR_SCALAR)
 template <int KSEL_, int S>
 struct SplitEval : EvalConfig {
     static constexpr int MODE = 2, QUEUE = 1, KSEL = KSEL_, SPLIT = S;
-    static constexpr bool PD = true, READS_AHEAD = true, ITEM_AHEAD = true, EPI_X8 = true, EPI_SCATTER = true;
+    static constexpr bool PD = true, READS_AHEAD = true, ITEM_AHEAD = true, EPI_X8 = true, EPI_SCATTER = true, ADDR_SCALAR = true;
 };
 
 template <int MODE, int QUEUE, int KSEL = 0, bool PD = false>

@@ -1069,6 +1069,45 @@ typedef struct vb2_group_result {
 int vb2_run_read_groups(const vb2_run_args *args, vb2_run_result *whole, int32_t capacity, vb2_group_result *group_results,
                         int32_t *num_group);
 
+/* ---- BGZF blocks inflated on the device ----
+ * The BGZF blocks of a buffer -- a whole file, or any run of whole blocks -- inflated on `device` (< 0: the current one):
+ * the block headers are walked with the reader's own checks (a buffer that is not BGZF is VB2_ERR_INVALID or VB2_ERR_IO
+ * with a message, before any device is touched), every block's deflate payload is inflated by one wave, in batches of
+ * tunable bam_batch_kb.  NO zlib fallback and NO CRC32 here: block_status[b] is the device decoder's verdict (0 = the
+ * block's ISIZE bytes are in `out`; 1 input exhausted, 2 output would pass ISIZE, 3 reserved block type, 4 stored LEN/NLEN,
+ * 5 code lengths, 6 repeat, 7 symbol, 8 distance, 9 stream ends before ISIZE bytes, 10 step budget), and the bytes of a
+ * block with another status are zero.  out holds the blocks' bytes back to back, *out_bytes of them (the sum of the
+ * ISIZEs; VB2_ERR_INVALID when that passes out_capacity or the blocks pass status_capacity: *out_bytes and *num_block say
+ * what is needed).  The built-in reader uses the same kernel with tunable bam_inflate = 1, and there inflates a block the
+ * device refused again with zlib and checks every block's CRC32 on the host. */
+int vb2_bgzf_inflate(const uint8_t *file_bytes, int64_t n_bytes, int32_t device, uint8_t *out, int64_t out_capacity,
+                     int64_t *out_bytes, int32_t *block_status, int32_t status_capacity, int32_t *num_block);
+/* What the device inflate of this process has done since the last reset, every caller counted (vb2_bgzf_inflate, and
+ * the loads of the built-in reader under bam_inflate = 1): the stages of its batches, timed with events on its stream. */
+typedef struct vb2_bgzf_stats {
+    int64_t blocks;             /* blocks given to the kernel                                            */
+    int64_t refused;            /* ... of which with a status other than 0                              */
+    int64_t batches;            /* launches                                                             */
+    int64_t bytes_raw;          /* deflate payload uploaded                                             */
+    int64_t bytes_inflated;     /* bytes of the accepted blocks                                         */
+    double seconds_upload;      /* payloads and job table up                                            */
+    double seconds_kernel;
+    double seconds_copyback;    /* inflated bytes and statuses down                                     */
+    double seconds_stage;       /* host: inflated bytes out of the staging buffer                       */
+} vb2_bgzf_stats;
+int vb2_bgzf_inflate_stats(vb2_bgzf_stats *out, int32_t reset);
+
+/* ---- .bam lines in a cohort's list ----
+ * A line of vb2_cohort_args.pileup_paths whose name ends in ".bam" is read by the built-in BAM reader (with base.mpileup,
+ * on the sample's device), every other line as a text pileup; lists may mix the two.  A ".cram" name, or a file that
+ * starts with the CRAM magic, is that sample's VB2_ERR_INVALID; an unreadable or corrupt BAM, or one without its index,
+ * is that sample's status too (what went wrong is printed to stderr, the other samples run on).  A BAM sample's .selfSM
+ * has the header's @RG SM: as SEQ_ID and its bases as #READS.  The host pool of one BAM load is 16 / reader threads,
+ * and at most tunable cohort_bam_inflight (4) BAM samples per device are between "file opened" and "context created".
+ * What the load of sample `sample` of this process's most recent cohort run did; VB2_ERR_INVALID for a sample that was
+ * not read from a BAM (or whose load failed). */
+int vb2_cohort_bam_stats(int32_t sample, vb2_bam_stats *out);
+
 /* ------------------------------------------------------------------------- *
  * 4. Reference-panel builder: --RefVCF (main.cpp:233-257, SVDcalculator::
  *    ProcessRefVCF, SVDcalculator.cpp:363-400).  The kept markers' genotypes

@@ -123,6 +123,12 @@ class BamStats(C.Structure):
                [(n, C.c_double) for n in ("seconds_index", "seconds_inflate", "seconds_device", "seconds_copyback")]
 
 
+class BgzfStats(C.Structure):
+    """vb2_bgzf_stats: what the device inflate of this process has done since the last reset."""
+    _fields_ = [(n, C.c_int64) for n in ("blocks", "refused", "batches", "bytes_raw", "bytes_inflated")] + \
+               [(n, C.c_double) for n in ("seconds_upload", "seconds_kernel", "seconds_copyback", "seconds_stage")]
+
+
 VB2_BAM_SCAN_GROUPS = 1
 VB2_BAM_NO_GROUP = 0xFFFF
 VB2_GROUP_NO_BASE = 1
@@ -282,6 +288,7 @@ SYMBOLS = [
     "vb2_flat_groups_flat", "vb2_flat_groups_unassigned", "vb2_flat_groups_seconds", "vb2_flat_groups_free", "vb2_run_read_groups",
     "vb2_refbias_create", "vb2_refbias_destroy", "vb2_refbias_eval", "vb2_refbias_optimize_llk", "vb2_refbias_info_get",
     "vb2_refbias_fit_ctx", "vb2_refbias_lockstep", "vb2_run_refbias",
+    "vb2_bgzf_inflate", "vb2_bgzf_inflate_stats", "vb2_cohort_bam_stats",
 ]
 
 _lib = None
@@ -354,6 +361,10 @@ def lib():
     L.vb2_bam_scan_group_id.restype = C.c_char_p
     L.vb2_bam_scan_record_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     L.vb2_bam_scan_record_groups.restype = C.c_int64
+    L.vb2_bgzf_inflate.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_int32,
+                                   C.POINTER(C.c_int32)]
+    L.vb2_bgzf_inflate_stats.argtypes = [C.POINTER(BgzfStats), C.c_int32]
+    L.vb2_cohort_bam_stats.argtypes = [C.c_int32, C.POINTER(BamStats)]
     L.vb2_flat_load_groups.argtypes = [C.POINTER(RunArgs), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.vb2_flat_groups_count.argtypes = [C.c_void_p]
     L.vb2_flat_groups_count.restype = C.c_int32

@@ -1376,14 +1376,45 @@ def bam_scan(bam_path, bed_path, groups=False):
         L.vb2_bam_scan_free(h)
 
 
+def bgzf_inflate(data, device=-1):
+    """The BGZF blocks of `data` (bytes: a whole file or any run of whole blocks) inflated on the device
+    (vb2_bgzf_inflate: bgzf_inflate_kernel, one wave per block; no zlib fallback and no CRC32).  Returns (bytes, statuses):
+    the blocks' bytes back to back -- zeros for a block the device refused -- and the device decoder's status per block
+    (0 = inflated; the codes are in include/vb2_abi.h)."""
+    L = _abi.lib()
+    data = bytes(data)
+    n_out, n_blk = C.c_int64(0), C.c_int32(0)
+    # once without room, for the sizes (the block headers are checked first: a buffer that is not BGZF fails here)
+    rc = L.vb2_bgzf_inflate(data, len(data), int(device), None, 0, C.byref(n_out), None, 0, C.byref(n_blk))
+    if rc == _abi.VB2_OK:
+        return b"", np.zeros(0, dtype=np.int32)
+    if n_blk.value == 0:
+        _abi.check(rc, "vb2_bgzf_inflate")
+    status = np.zeros(n_blk.value, dtype=np.int32)
+    out = np.zeros(max(n_out.value, 1), dtype=np.uint8)
+    _abi.check(L.vb2_bgzf_inflate(data, len(data), int(device), out.ctypes.data_as(C.c_void_p), out.size, C.byref(n_out),
+                                  status.ctypes.data_as(C.c_void_p), status.size, C.byref(n_blk)), "vb2_bgzf_inflate")
+    return out[:n_out.value].tobytes(), status[:n_blk.value].copy()
+
+
+def bgzf_inflate_stats(reset=False):
+    """vb2_bgzf_inflate_stats: what the device inflate of this process has done since the last reset, as a dict."""
+    st = _abi.BgzfStats()
+    _abi.check(_abi.lib().vb2_bgzf_inflate_stats(C.byref(st), int(bool(reset))), "vb2_bgzf_inflate_stats")
+    return {name: getattr(st, name) for name, _ in _abi.BgzfStats._fields_}
+
+
 def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, disable_sanity=False,
                      known_af_path=None, device=-1, output_pileup=False, group_size=0, num_host_thread=0,
                      devices=None, find_source=False, source_top=3, sources_prefix=None, confidence_interval=False,
                      refit_source=False, find_related=False, related_top=3, matched_normal=None, normal_hom_min=0.99,
-                     pair_interval=False, **model_kw):
+                     pair_interval=False, mpileup=None, **model_kw):
     """Many pileups against one panel (vb2_cohort_run): the panel is read once, the pileups are read
     and flattened by host threads while the device searches the previous group in lock-step.
     Returns one dict per sample (with its own "status" code).
+    A path that ends in ".bam" is read by the built-in BAM reader (its index beside it), with the pileup options of
+    `mpileup` (as run_files'); lists may mix text pileups and BAMs.  The dict of a sample read from a BAM has a `bam` entry,
+    the load's vb2_bam_stats.
     find_source (vb2_cohort_run_sources; one device): returns (samples, sources), sources = dict(score [S, S] -- row =
     target, column = candidate, NaN on the diagonal and for failed samples --, shared [S, S]); with output_prefixes and
     sources_prefix it writes <sources_prefix>.Sources, source_top candidates per sample.
@@ -1415,6 +1446,7 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
     args, keep = _run_args(svd_prefix, pileup_paths[0], num_pc, disable_sanity, known_af_path,
                            sources_prefix if find_source or find_related or matched_normal is not None else None,
                            device, output_pileup, devices=devices, **model_kw)
+    args.mpileup = _mpileup_opts(mpileup)
     ca = _abi.CohortArgs()
     ca.base = args
     ca.num_sample = S
@@ -1468,6 +1500,10 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
                  seconds_load=res[s].seconds_load, seconds_optimize=res[s].seconds_optimize)
         if civ is not None and status[s] == _abi.VB2_OK:
             d["interval"] = _interval_dict(civ[s])
+        if str(pileup_paths[s]).endswith(".bam"):
+            st = _abi.BamStats()
+            if _abi.lib().vb2_cohort_bam_stats(s, C.byref(st)) == _abi.VB2_OK:
+                d["bam"] = {name: getattr(st, name) for name, _ in _abi.BamStats._fields_}
         out.append(d)
     if matched_normal is not None:
         fits = [{name: getattr(pfits[p], name) for name, _ in _abi.PairFit._fields_} for p in range(len(pairs))]

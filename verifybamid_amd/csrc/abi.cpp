@@ -28,6 +28,7 @@
 #include "shard.h"
 #include "replicates.h"
 #include "read_groups.h"
+#include "bgzf_inflate_kernels.h"
 
 using vb2::set_error;
 
@@ -935,6 +936,70 @@ int64_t vb2_bam_scan_records(const vb2_bam_scan_result* scan, uint64_t* voffset,
 const char* vb2_bam_scan_sample(const vb2_bam_scan_result* scan) { return scan ? scan->sample.c_str() : ""; }
 
 void vb2_bam_scan_free(vb2_bam_scan_result* scan) { delete scan; }
+
+int vb2_bgzf_inflate(const uint8_t* file_bytes, int64_t n_bytes, int32_t device, uint8_t* out, int64_t out_capacity, int64_t* out_bytes,
+                     int32_t* block_status, int32_t status_capacity, int32_t* num_block)
+{
+    if (n_bytes < 0 || (!file_bytes && n_bytes > 0) || out_capacity < 0 || (!out && out_capacity > 0) || !out_bytes || status_capacity < 0 ||
+        (!block_status && status_capacity > 0) || !num_block) {
+        set_error("vb2_bgzf_inflate: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    *out_bytes = 0;
+    *num_block = 0;
+    return vb2::guarded([&]() -> int {
+        if (vb2::usable_device_count() < 1) {
+            set_error("vb2_bgzf_inflate: no gfx950 device is visible (the host's inflate is zlib's, not this entry's)");
+            return VB2_ERR_NO_DEVICE;
+        }
+        std::string err;
+        const size_t batch = (size_t)std::max(vb2::tunables().bam_batch_kb, 1) << 10;
+        const int rc = vb2::bgzf_inflate_buffer(file_bytes, (uint64_t)n_bytes, device, batch, out, out_capacity, out_bytes, block_status,
+                                                status_capacity, num_block, &err);
+        if (rc) set_error(err);
+        return rc;                     // bamio's codes are the ABI's
+    });
+}
+
+int vb2_cohort_bam_stats(int32_t sample, vb2_bam_stats* out)
+{
+    if (!out || !vb2::cohort_bam_stats_get(sample, out)) {
+        set_error("vb2_cohort_bam_stats: not a sample of the last cohort run that was read from a BAM");
+        return VB2_ERR_INVALID;
+    }
+    return VB2_OK;
+}
+
+// (tests) how a cohort treats a line of its list (0 text, 1 BAM, 2 CRAM, by name and by the CRAM magic), the host pool
+// of one of its BAM loads among `readers` reader threads, and the most BAM loads in flight on one device in the last run
+int vb2_debug_list_entry_kind(const char* path)
+{
+    if (!path) return -1;
+    vb2::ListEntry k = vb2::classify_list_entry(path);
+    if (k == vb2::ListEntry::kText && vb2::has_cram_magic(path)) k = vb2::ListEntry::kCram;
+    return (int)k;
+}
+int vb2_debug_cohort_bam_pool(int readers) { return vb2::cohort_bam_pool(readers); }
+int vb2_debug_cohort_bam_peak(void) { return vb2::cohort_bam_peak(); }
+
+int vb2_bgzf_inflate_stats(vb2_bgzf_stats* out, int32_t reset)
+{
+    if (!out && !reset) return VB2_ERR_INVALID;
+    vb2::InflateTotals t;
+    vb2::inflate_totals(&t, reset != 0);
+    if (out) {
+        out->blocks = t.blocks;
+        out->refused = t.refused;
+        out->batches = t.batches;
+        out->bytes_raw = t.bytes_raw;
+        out->bytes_inflated = t.bytes_inflated;
+        out->seconds_upload = t.seconds_upload;
+        out->seconds_kernel = t.seconds_kernel;
+        out->seconds_copyback = t.seconds_copyback;
+        out->seconds_stage = t.seconds_stage;
+    }
+    return VB2_OK;
+}
 
 int vb2_ctx_interval(vb2_ctx* ctx, const vb2_model* model, const vb2_estimate* est, vb2_interval* out)
 {

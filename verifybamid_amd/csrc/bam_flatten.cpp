@@ -148,7 +148,7 @@ std::string sample_name(sam_hdr_t* hdr)     // @RG SM: (SimplePileupViewer.cpp:2
 }  // namespace
 
 int read_bam(const std::string& bam_path, const std::string& ref_path, const Panel& panel, PileupViewer* v,
-             const vb2_mpileup_opts* mp, int, vb2_bam_stats*)
+             const vb2_mpileup_opts* mp, int, vb2_bam_stats*, const BamReadHow*)
 {
     Aux a;
     a.conf.apply(mp);
@@ -262,6 +262,7 @@ int bam_scan_file(const std::string&, const std::string&, std::vector<uint64_t>*
 
 #include "bam_io.h"
 #include "bam_pileup_kernels.h"
+#include "bgzf_inflate_kernels.h"
 #include "device_util.h"
 #include "tunables.h"
 
@@ -334,7 +335,8 @@ bool group_slots_fit(size_t num_group, size_t num_slot) { return (uint64_t)num_g
 // groups (may be null; its flat[g]->viewer initialised): also every read group's sites, behind the
 // whole sample's and from the same sorted entries: the whole sample's launches and bytes are what they are without it.
 int device_pileup(const bamio::Scan& scan, const std::vector<std::vector<std::pair<int32_t, int32_t>>>& by_seq, const Panel& panel,
-                  const MplpConf& conf, int device, PileupViewer* v, vb2_bam_stats* stats, vb2_flat_groups* groups = nullptr)
+                  const MplpConf& conf, int device, PileupViewer* v, vb2_bam_stats* stats, vb2_flat_groups* groups = nullptr,
+                  hipStream_t caller_stream = nullptr)
 {
     const double t0 = now_s();
     const int32_t num_slot = (int32_t)panel.num_slot();
@@ -346,8 +348,8 @@ int device_pileup(const bamio::Scan& scan, const std::vector<std::vector<std::pa
     const int32_t n_ref = (int32_t)scan.ref_name.size();
     if (device >= 0) VB2_HIP(hipSetDevice(device));
     StreamHolder st;
-    VB2_HIP(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    hipStream_t s = st.s;
+    if (!caller_stream) VB2_HIP(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    hipStream_t s = caller_stream ? caller_stream : st.s;
 
     // marker tables: per tid a run of (position, slot), ascending
     std::vector<int32_t> h_tid_lo((size_t)n_ref + 1, 0), h_pos, h_slot;
@@ -678,7 +680,7 @@ void host_stats(const bamio::Scan& scan, vb2_bam_stats* st)
 
 // read_bam, and read_bam_groups with groups != nullptr
 static int read_bam_impl(const std::string& bam_path, const Panel& panel, PileupViewer* v, const vb2_mpileup_opts* mp, int device,
-                         vb2_bam_stats* stats, vb2_flat_groups* groups, const std::shared_ptr<Panel>& shared)
+                         vb2_bam_stats* stats, vb2_flat_groups* groups, const std::shared_ptr<Panel>& shared, const BamReadHow* how = nullptr)
 {
     MplpConf conf;
     conf.apply(mp);
@@ -688,10 +690,23 @@ static int read_bam_impl(const std::string& bam_path, const Panel& panel, Pileup
     // the file and its index first: no device is touched for an input that cannot be read
     bamio::Scan scan;
     std::string err;
-    if (int rc = bamio::scan(bam_path, seqs, reader_threads(), &scan, &err, groups != nullptr)) {
+    hipStream_t const stream = how ? static_cast<hipStream_t>(how->stream) : nullptr;
+    const int threads = how && how->threads > 0 ? std::min(how->threads, 16) : reader_threads();
+    // tunable bam_inflate: the planned blocks on the device.  Nothing of it exists without the
+    // tunable, and the scan is then the one it was.
+    std::unique_ptr<DeviceInflater> inflater;
+    if (vb2::tunables().bam_inflate != 0) {
+        if (usable_device_count() < 1) {
+            set_error("--BamFile: bam_inflate = 1 asks for the device inflate and no gfx950 device is visible");
+            return VB2_ERR_NO_DEVICE;
+        }
+        inflater.reset(new DeviceInflater(device, stream, (size_t)std::max(vb2::tunables().bam_batch_kb, 1) << 10));
+    }
+    if (int rc = bamio::scan(bam_path, seqs, threads, &scan, &err, groups != nullptr, inflater.get())) {
         set_error(err);
         return rc;                     // bamio's codes are the ABI's
     }
+    inflater.reset();                  // (its staging buffers go before the pileup's come)
     if (groups) {
         if (!group_slots_fit(scan.groups.size(), panel.num_slot())) {      // before anything is sized by the product
             set_error("--PerReadGroup: " + std::to_string(scan.groups.size()) + " read groups x " + std::to_string(panel.num_slot()) +
@@ -736,13 +751,13 @@ static int read_bam_impl(const std::string& bam_path, const Panel& panel, Pileup
                   "(there is no CPU fallback)");
         return VB2_ERR_NO_DEVICE;
     }
-    return device_pileup(scan, by_seq, panel, conf, device, v, stats, groups);
+    return device_pileup(scan, by_seq, panel, conf, device, v, stats, groups, stream);
 }
 
 int read_bam(const std::string& bam_path, const std::string&, const Panel& panel, PileupViewer* v, const vb2_mpileup_opts* mp,
-             int device, vb2_bam_stats* stats)
+             int device, vb2_bam_stats* stats, const BamReadHow* how)
 {
-    return read_bam_impl(bam_path, panel, v, mp, device, stats, nullptr, nullptr);
+    return read_bam_impl(bam_path, panel, v, mp, device, stats, nullptr, nullptr, how);
 }
 
 int read_bam_groups(const std::string& bam_path, const std::shared_ptr<Panel>& panel, PileupViewer* v, const vb2_mpileup_opts* mp,

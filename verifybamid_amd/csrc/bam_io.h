@@ -55,6 +55,28 @@ struct Stats {
     int64_t blocks = 0, bytes_inflated = 0, records_seen = 0, records_kept = 0, long_cigar_skipped = 0, chunks = 0;
     int64_t records_unassigned = 0;          // kept records of no group (0 when groups were not asked for)
     double seconds_index = 0, seconds_inflate = 0;
+    // with a BlockInflater: the blocks it was given, those of them it refused (inflated again by zlib), and the host pool's
+    // wall-clock over CRC32 and those fallbacks (a block whose bytes missed the CRC32 counts as refused)
+    int64_t inflater_blocks = 0, inflater_refused = 0;
+    double seconds_inflater = 0, seconds_crc = 0;
+};
+
+// The hook for inflating the planned blocks somewhere else than on the host pool.  An item is one
+// BGZF block: its deflate payload, and where its ISIZE bytes belong.  run() fills status[i] for every item: 0 = dst holds
+// the isize inflated bytes; any other value = the block is the host's (zlib inflates it again, and zlib's verdict stands,
+// so a corrupt file ends in the same code and message with and without an inflater).  The host checks the CRC32 of every
+// block the inflater accepted; one whose bytes miss it is the host's again as well.  The return value is kOk, or a code
+// of this header with *err set for a failure that is no block's own (the scan ends with it).
+struct InflateItem {
+    const uint8_t* raw;
+    uint32_t raw_len;
+    uint8_t* dst;
+    uint32_t isize;
+};
+class BlockInflater {
+public:
+    virtual ~BlockInflater() {}
+    virtual int run(const InflateItem* items, size_t n, int32_t* status, std::string* err) = 0;
 };
 
 // The markers of one reference sequence: sorted distinct 1-based positions.
@@ -79,8 +101,19 @@ struct Scan {
 // want_groups: also parse the header's @RG lines into out->groups (two lines with one ID, a line without ID or more than
 // 65 535 lines: kErrInvalid) and walk every kept record's auxiliary fields for its RG:Z, into Chunk::group.  Without it the
 // auxiliary bytes are not looked at.
+// inflater (may be null): the planned blocks of all chunks go through it (above); the header's blocks and the tail blocks a
+// straddling record pulls in stay on zlib.  Without one the scan is what it was before the hook existed.
 int scan(const std::string& bam_path, const std::vector<SeqMarkers>& markers, int threads, Scan* out, std::string* err,
-         bool want_groups = false);
+         bool want_groups = false, BlockInflater* inflater = nullptr);
+
+// The BGZF blocks of a buffer, back to back from offset 0 to its end, with the scan's own header checks: per block the
+// offset and length of its deflate payload, its ISIZE and its CRC32 field.  kErrIo / kErrInvalid with *err otherwise
+// (`name` stands for the file in the messages).
+struct BlockSpan {
+    uint64_t raw_off;
+    uint32_t raw_len, isize, crc;
+};
+int list_bgzf_blocks(const uint8_t* bytes, uint64_t n, const std::string& name, std::vector<BlockSpan>* out, std::string* err);
 
 }  // namespace bamio
 }  // namespace vb2

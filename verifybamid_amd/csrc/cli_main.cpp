@@ -411,6 +411,23 @@ int main(int argc, char** argv)
         args.num_device = (int32_t)devs.size();
         args.device = devs[0];
     }
+    // the lines of --PileupList: a name that ends in ".bam" is read by the built-in BAM reader, any other as a text pileup
+    std::vector<std::string> pile, pref;
+    bool listHasBam = false;
+    if (PileupList != "Empty") {
+        std::ifstream fl(PileupList);
+        if (!fl.is_open()) fatal("cannot open --PileupList file");
+        std::string line;
+        while (std::getline(fl, line)) {
+            if (line.empty()) continue;
+            const size_t tab = line.find('\t');
+            pile.push_back(line.substr(0, tab));
+            pref.push_back(tab == std::string::npos ? line + ".vb2" : line.substr(tab + 1));
+            const std::string& name = pile.back();
+            if (name.size() > 4 && name.compare(name.size() - 4, 4, ".bam") == 0) listHasBam = true;
+        }
+        if (pile.empty()) fatal("--PileupList file names no sample");
+    }
     static const char* const kPileupOpts[] = {"min-BQ", "min-MQ", "adjust-MQ", "max-depth", "no-orphans", "incl-flags", "excl-flags"};
     for (const char* name : kPileupOpts) args.mpileup.given |= flags[name].seen ? 1 : 0;
     args.mpileup.min_bq = minBQ;
@@ -420,10 +437,11 @@ int main(int argc, char** argv)
     args.mpileup.no_orphans = noOrphans ? 1 : 0;
     args.mpileup.incl_flags = inclFlags;
     args.mpileup.excl_flags = exclFlags;
-    if (args.mpileup.given && BamFile == "Empty")
+    if (args.mpileup.given && BamFile == "Empty" && !listHasBam)
         std::fprintf(stderr, "NOTICE - pileup options (--min-BQ, --min-MQ, ...) apply to --BamFile input only; "
                              "the text pileup is taken as it is (as in the reference)\n");
-    if (BamFile != "Empty" && PileupFile == "Empty") {
+    // (once per run, also for the .bam lines of a --PileupList, however many there are)
+    if ((BamFile != "Empty" && PileupFile == "Empty") || listHasBam) {
         // what the built-in reader leaves out of the reference's pileup (both need htslib's HMM and the FASTA)
         const int effFlags = args.mpileup.given ? inclFlags : (16 | 1024), effCap = args.mpileup.given ? adjustMQ : 40;
         if (effFlags & 16)
@@ -433,7 +451,9 @@ int main(int argc, char** argv)
             std::fprintf(stderr, "NOTICE - --BamFile: the mapping quality cap (--adjust-MQ %d) is not applied by the built-in BAM "
                                  "reader; the reference computes the same with --incl-flags 1024 --adjust-MQ 0\n", effCap);
         std::fprintf(stderr, "NOTICE - --BamFile: the reference base of a site is the panel's REF allele (.bed); --Reference is not read\n");
-        if (nthread > 4) vb2_debug_set_tunable("bam_threads", nthread);       // --NumThread above its default: the reader's pool
+        // --NumThread above its default: the reader's pool (of a cohort it stays the number of reader threads, and a BAM
+        // line's pool is 16 / that)
+        if (nthread > 4 && !listHasBam) vb2_debug_set_tunable("bam_threads", nthread);
     }
     args.model.is_heter = !withinAncestry;
     args.model.epsilon = epsilon;
@@ -461,17 +481,6 @@ int main(int argc, char** argv)
     if (args.known_af_path) args.model.is_af_known = 1;               // main.cpp:314-319
 
     if (PileupList != "Empty") {
-        std::ifstream fl(PileupList);
-        if (!fl.is_open()) fatal("cannot open --PileupList file");
-        std::vector<std::string> pile, pref;
-        std::string line;
-        while (std::getline(fl, line)) {
-            if (line.empty()) continue;
-            const size_t tab = line.find('\t');
-            pile.push_back(line.substr(0, tab));
-            pref.push_back(tab == std::string::npos ? line + ".vb2" : line.substr(tab + 1));
-        }
-        if (pile.empty()) fatal("--PileupList file names no sample");
         std::vector<const char*> cpile, cpref;
         for (size_t i = 0; i < pile.size(); ++i) { cpile.push_back(pile[i].c_str()); cpref.push_back(pref[i].c_str()); }
         vb2_cohort_args ca;

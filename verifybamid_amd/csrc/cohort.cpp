@@ -89,6 +89,8 @@ public:
         cnt_.assign(ndev_, 0);
         stream_ = vb2::tunables().cohort_stream != 0;
         inflight_.assign(ndev_, 0);
+        bam_inflight_.assign(ndev_, 0);
+        bam_cap_ = std::max(1, vb2::tunables().cohort_bam_inflight);
         remaining_.assign(ndev_, 0);
         for (int s = 0; s < S_; ++s) ++remaining_[s % ndev_];
         ready_q_.resize(ndev_);
@@ -120,6 +122,16 @@ public:
             status_[s] = VB2_ERR_INVALID;
             if (ci_) std::memset(&ci_[s], 0, sizeof(ci_[s]));
         }
+        vb2::cohort_bam_stats_reset(S_);
+#ifdef VB2_WITH_HTSLIB
+        // the htslib reader has never been compiled, let alone run from many threads at once: refused before anything is read
+        for (int s = 0; s < S_; ++s)
+            if (vb2::classify_list_entry(a_->pileup_paths[s]) == vb2::ListEntry::kBam) {
+                set_error(std::string("vb2_cohort_run: ") + a_->pileup_paths[s] + ": .bam lines of a cohort are read by the built-in BAM "
+                          "reader, which a library configured with VB2_WITH_HTSLIB does not have");
+                return VB2_ERR_INVALID;
+            }
+#endif
         const bool timing = vb2::tunables().debug_timing != 0;
         const double t_run0 = now_s();
         // HIP runtime start-up (per device) behind the panel reading
@@ -251,6 +263,35 @@ private:
     std::deque<IvItem> iv_queue_;
     bool iv_closed_ = false;
 
+    // .bam lines between "file opened" and "context created", per device: each holds its inflated chunks on the host and its
+    // kept records on the device (tunable cohort_bam_inflight)
+    std::mutex bam_mu_;
+    std::condition_variable bam_cv_;
+    std::vector<int> bam_inflight_;
+    int bam_cap_ = 4;
+    struct BamGate {
+        CohortRunner* r;
+        int d;
+        BamGate(CohortRunner* runner, int dev) : r(runner), d(dev)
+        {
+            if (d < 0) return;
+            std::unique_lock<std::mutex> lk(r->bam_mu_);
+            r->bam_cv_.wait(lk, [&] { return r->bam_inflight_[(size_t)d] < r->bam_cap_; });
+            vb2::cohort_bam_peak_note(++r->bam_inflight_[(size_t)d]);
+        }
+        ~BamGate()
+        {
+            if (d < 0) return;
+            {
+                std::lock_guard<std::mutex> lk(r->bam_mu_);
+                --r->bam_inflight_[(size_t)d];
+            }
+            r->bam_cv_.notify_all();
+        }
+        BamGate(const BamGate&) = delete;
+        BamGate& operator=(const BamGate&) = delete;
+    };
+
     int device_of_group(int gi) const { return gi % ndev_; }
     int device_of_sample(int s) const { return stream_ ? s % ndev_ : device_of_group(group_of_[s]); }
 
@@ -332,7 +373,7 @@ private:
         const char* prefix = a_->output_prefixes ? a_->output_prefixes[s] : nullptr;
         if (flat && prefix) {
             int rw = vb2::write_ancestry(prefix, a_->base.num_pc, est.pc, est.pc2);
-            if (!rw) rw = vb2::write_selfsm(prefix, *flat, est, true);   // (cohort input is text pileups: #READS = NA)
+            if (!rw) rw = vb2::write_selfsm(prefix, *flat, est, /*pileup_input=*/!flat->from_bam);   // (#READS: NA for a text pileup)
             if (rw) status_[s] = rw;
         }
         if (!ci) return;
@@ -347,8 +388,33 @@ private:
         const double t0 = now_s();
         sl.flat.reset(new vb2_flat(panel_));
         vb2_flat& f = *sl.flat;
-        sl.rc = vb2::read_pileup(a_->pileup_paths[s], *panel_, &f.viewer);
-        if (sl.rc) return;
+        // a ".bam" line goes through the built-in BAM reader, every other line is a text pileup; what follows the read is the
+        // same for both (the reader fills the same PileupViewer)
+        const std::string path = a_->pileup_paths[s];
+        vb2::ListEntry kind = vb2::classify_list_entry(path);
+        if (kind == vb2::ListEntry::kText && vb2::has_cram_magic(path)) kind = vb2::ListEntry::kCram;
+        BamGate gate(this, kind == vb2::ListEntry::kBam ? device_of_sample(s) : -1);      // (held until the context exists)
+        if (kind == vb2::ListEntry::kCram) {
+            set_error(vb2::cram_message(path));
+            sl.rc = VB2_ERR_INVALID;
+        } else if (kind == vb2::ListEntry::kBam) {
+            vb2::BamReadHow how;
+            how.threads = vb2::cohort_bam_pool(T_);
+            // the device stage on one of the device's two creation streams, never on a lane's hardware queue (see run())
+            if (!own_streams_.empty()) how.stream = own_streams_[(size_t)device_of_sample(s) * 4 + 2 + (size_t)(s / ndev_) % 2];
+            sl.rc = vb2::read_bam(path, a_->base.reference_path ? a_->base.reference_path : "", *panel_, &f.viewer, &a_->base.mpileup,
+                                  devices_[device_of_sample(s)], &f.bam_stats, &how);
+            f.from_bam = sl.rc == VB2_OK;
+            if (f.from_bam) vb2::cohort_bam_stats_put(s, f.bam_stats);
+        } else {
+            sl.rc = vb2::read_pileup(path, *panel_, &f.viewer);
+        }
+        if (sl.rc) {
+            // a sample's own failure is its status; what went wrong is said here, once (the caller's last error is the run's)
+            if (kind != vb2::ListEntry::kText)
+                std::fprintf(stderr, "WARNING - cohort sample %d (%s): %s\n", s, path.c_str(), vb2::g_last_error.c_str());
+            return;
+        }
         const double t_read = now_s();
         const bool sanity_off = a_->base.disable_sanity != 0;
         f.sanity_disabled = sanity_off;

@@ -12,7 +12,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <algorithm>
 #include <iostream>
+#include <mutex>
 #include <sstream>
 #include <thread>
 #include <vector>
@@ -864,6 +866,75 @@ int read_pileup(const std::string& path, const Panel& panel, PileupViewer* v)
     if (rc) return rc;
     v->avgDepth = (double)v->numBases / v->effectiveNumSite;
     return VB2_OK;
+}
+
+// ---- the lines of a cohort's list ----
+ListEntry classify_list_entry(const std::string& path)
+{
+    auto ends = [&](const char* suffix) {
+        const size_t n = std::strlen(suffix);
+        return path.size() > n && path.compare(path.size() - n, n, suffix) == 0;
+    };
+    return ends(".bam") ? ListEntry::kBam : ends(".cram") ? ListEntry::kCram : ListEntry::kText;
+}
+
+bool has_cram_magic(const std::string& path)
+{
+    char magic[4] = {0, 0, 0, 0};
+    if (FILE* fh = std::fopen(path.c_str(), "rb")) {
+        const size_t n = std::fread(magic, 1, 4, fh);
+        std::fclose(fh);
+        return n == 4 && std::memcmp(magic, "CRAM", 4) == 0;
+    }
+    return false;
+}
+
+std::string cram_message(const std::string& path)       // (bam_io.cpp's, for a file it is never asked to open)
+{
+    return path + " is a CRAM file: the built-in reader reads BAM only (this build has no htslib); convert it with `samtools view -b`";
+}
+
+namespace {
+std::mutex g_cohort_bam_mu;
+std::vector<vb2_bam_stats> g_cohort_bam_stats;
+std::vector<char> g_cohort_bam_have;
+int g_cohort_bam_peak = 0;
+}  // namespace
+
+void cohort_bam_stats_reset(int num_sample)
+{
+    std::lock_guard<std::mutex> g(g_cohort_bam_mu);
+    g_cohort_bam_stats.assign((size_t)std::max(num_sample, 0), vb2_bam_stats{});
+    g_cohort_bam_have.assign((size_t)std::max(num_sample, 0), 0);
+    g_cohort_bam_peak = 0;
+}
+
+void cohort_bam_stats_put(int sample, const vb2_bam_stats& st)
+{
+    std::lock_guard<std::mutex> g(g_cohort_bam_mu);
+    if (sample < 0 || (size_t)sample >= g_cohort_bam_stats.size()) return;
+    g_cohort_bam_stats[(size_t)sample] = st;
+    g_cohort_bam_have[(size_t)sample] = 1;
+}
+
+bool cohort_bam_stats_get(int sample, vb2_bam_stats* out)
+{
+    std::lock_guard<std::mutex> g(g_cohort_bam_mu);
+    if (sample < 0 || (size_t)sample >= g_cohort_bam_stats.size() || !g_cohort_bam_have[(size_t)sample]) return false;
+    *out = g_cohort_bam_stats[(size_t)sample];
+    return true;
+}
+
+void cohort_bam_peak_note(int inflight)
+{
+    std::lock_guard<std::mutex> g(g_cohort_bam_mu);
+    g_cohort_bam_peak = std::max(g_cohort_bam_peak, inflight);
+}
+
+int cohort_bam_peak()
+{
+    std::lock_guard<std::mutex> g(g_cohort_bam_mu);
+    return g_cohort_bam_peak;
 }
 
 // ContaminationEstimator.cpp:543-587.

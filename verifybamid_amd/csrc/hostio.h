@@ -100,8 +100,29 @@ int read_pileup(const std::string& path, const Panel& panel, PileupViewer* v);
 // VB2_WITH_HTSLIB.  SimplePileupViewer.cpp:172-557 with main.cpp:81-96's defaults, less BAQ and the mapQ cap.
 // mp: the reference's "Pileup Options" (main.cpp:176-187), nullptr or given == 0 = its defaults (main.cpp:81-96);
 // stats (may be null): what vb2_flat_bam_stats reports.  The file and its index are opened before any device is touched.
+// how: what a caller that runs many loads at once decides for one of them (null: the tunables and a stream of its own)
+struct BamReadHow {
+    int threads = 0;          // host pool that inflates and walks: 0 = tunable bam_threads
+    void* stream = nullptr;   // hipStream_t of the device stage (and of the device inflate): null = one made for the load
+};
 int read_bam(const std::string& bam_path, const std::string& ref_path, const Panel& panel, PileupViewer* v,
-             const vb2_mpileup_opts* mp = nullptr, int device = -1, vb2_bam_stats* stats = nullptr);
+             const vb2_mpileup_opts* mp = nullptr, int device = -1, vb2_bam_stats* stats = nullptr, const BamReadHow* how = nullptr);
+// A line of a cohort's list (vb2_cohort_args.pileup_paths): by its name a BAM (".bam": the built-in reader), a CRAM
+// (".cram": refused with cram_message) or a text pileup (anything else; a file that starts with the CRAM magic is refused
+// like a ".cram" name).
+enum class ListEntry { kText = 0, kBam = 1, kCram = 2 };
+ListEntry classify_list_entry(const std::string& path);
+bool has_cram_magic(const std::string& path);
+std::string cram_message(const std::string& path);
+// The vb2_bam_stats of the .bam lines of the process's most recent cohort run (vb2_cohort_bam_stats), and the most .bam
+// lines that were between "file opened" and "context created" at once on one device in it.
+void cohort_bam_stats_reset(int num_sample);
+void cohort_bam_stats_put(int sample, const vb2_bam_stats& st);
+bool cohort_bam_stats_get(int sample, vb2_bam_stats* out);
+void cohort_bam_peak_note(int inflight);
+int cohort_bam_peak();
+// the host pool of one BAM load among `readers` loads at once: the process keeps to 16 busy host threads
+inline int cohort_bam_pool(int readers) { return readers >= 16 ? 1 : (readers < 1 ? 16 : 16 / readers); }
 // read_bam, and every read group of the header beside the whole sample (built-in reader only):
 // groups->info and groups->flat are filled, one vb2_flat per @RG line over `panel` with its viewer's sites added; the whole sample's viewer and stats are what
 // read_bam gives.  VB2_ERR_INVALID for a header whose groups x panel slots pass 2^31 - 2, before any device is touched.

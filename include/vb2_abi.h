@@ -418,10 +418,15 @@ typedef struct vb2_run_args {
      * (no collective).  NULL / 0 = `device` alone. */
     const int32_t *devices;
     int32_t num_device;
-    int32_t reserved;
+    /* --ApplyBAQ (the field was `reserved`: same offset and size, ABI 7 stays).  0: BAM input is piled up as it is.  1: the
+     * built-in reader applies to every record what the effective mpileup options ask of the FASTA at reference_path, in
+     * mplp_func's order (vb2_baq_stats below): the Illumina-1.3 shift (incl_flags & 128), base alignment quality
+     * (incl_flags & 16; & 64 ignores an existing BQ tag), the mapping-quality cap (adjust_mq > 10).  Any other value is
+     * VB2_ERR_INVALID.  No effect on pileup_path input. */
+    int32_t bam_adjust;
     /* --BamFile / --Reference: BAM input (SimplePileupViewer.cpp:172-557), used when pileup_path is NULL: the built-in
-     * reader (vb2_bam_stats below), or htslib's where the library was configured with it.  reference_path is not read by
-     * the built-in reader: the reference base of a site is the panel's REF allele. */
+     * reader (vb2_bam_stats below), or htslib's where the library was configured with it.  reference_path is read by
+     * the built-in reader under bam_adjust = 1 alone; the reference base of a site is the panel's REF allele either way. */
     const char *bam_path;
     const char *reference_path;
     /* --NumStart / --Seed / --LineSearch: optimiser variants (vb2_search_opts); all zero = the
@@ -1096,6 +1101,59 @@ typedef struct vb2_bgzf_stats {
     double seconds_stage;       /* host: inflated bytes out of the staging buffer                       */
 } vb2_bgzf_stats;
 int vb2_bgzf_inflate_stats(vb2_bgzf_stats *out, int32_t reset);
+
+/* ---- --ApplyBAQ: base alignment quality and the mapping-quality cap on BAM input (vb2_run_args.bam_adjust) ----
+ * The HMM is the reference's bundled samtools/kprobaln.c (kpa_glocal), the wrapper and the cap its samtools/bam_md.c
+ * (bam_prob_realn_core with flag 3 or 7, bam_cap_mapQ), restated once for host and device (csrc/baq_core.h); the device
+ * stage runs between a batch's upload and its cover pass.  Agreement with htslib 1.11's sam_prob_realn / sam_cap_mapq,
+ * which the reference binary links, is UNPINNED. */
+typedef struct vb2_baq_stats {
+    int64_t records;            /* records the stage saw (vb2_bam_stats.records_kept)                     */
+    int64_t realigned;          /* the HMM ran                                                            */
+    int64_t left_alone;         /* by rule: unmapped, no bases, qualities 0xFF, an N operation, a ZQ tag  */
+    int64_t tag_applied;        /* a BQ tag was there and applied (no redo)                               */
+    int64_t no_reference;       /* the FASTA lacks the record's sequence: neither BAQ nor the cap         */
+    int64_t dropped_outside;    /* pos >= the sequence's length in the .fai                               */
+    int64_t dropped_cap;        /* the cap dropped the read                                               */
+    int64_t not_asked;          /* BAQ off in the options (the cap may have run)                          */
+    int64_t records_lds;        /* realigned with the matrix in LDS ...                                   */
+    int64_t records_global;     /* ... and in global memory                                               */
+    int64_t undefined_rows;     /* rows where the reference converts a NaN or an infinity to int: quality 0 */
+    int64_t fasta_bytes;        /* bases read from the FASTA                                              */
+    double seconds_fasta;       /* index, spans                                                           */
+    double seconds_lds;         /* the kernel over the LDS tier (events)                                  */
+    double seconds_global;      /* ... over the global tier                                               */
+    double seconds_cap;         /* the cap's end on the host and its byte per record back up              */
+    double seconds_stage;       /* the whole stage, host clock                                            */
+} vb2_baq_stats;
+/* VB2_ERR_INVALID for a vb2_flat that was not loaded with bam_adjust = 1 */
+int vb2_flat_baq_stats(const vb2_flat *f, vb2_baq_stats *out);
+
+/* Diagnostic: for the records vb2_bam_scan would send up, in its order, what the stage makes of them under `opts` (NULL or
+ * given == 0: the defaults).  where = 0: baq_core.h's sequential host driver, no device (a diagnostic and the tests'
+ * yardstick, NOT a fallback of the product); where = 1: the device stage, in upload batches of tunable bam_batch_kb. */
+typedef struct vb2_baq_result vb2_baq_result;
+int vb2_baq_records(const char *bam_path, const char *bed_path, const char *reference_path, const vb2_mpileup_opts *opts,
+                    int where, int device, vb2_baq_result **out);
+int64_t vb2_baq_result_num(const vb2_baq_result *r);
+int64_t vb2_baq_result_qual_bytes(const vb2_baq_result *r);
+/* qual_off [num + 1]: record i's adjusted qualities are qual[qual_off[i] .. qual_off[i + 1]); mapq [num]: after the cap, -1
+ * = dropped; outcome [num]: 0 realigned, 1 left alone, 2 BQ tag applied, 3 no reference sequence, 4 outside the sequence,
+ * 5 dropped by the cap, 6 BAQ not asked for; cap4 [4 * num]: mm, q, len, clip_q of the cap's walk.  Any may be NULL. */
+int vb2_baq_result_copy(const vb2_baq_result *r, uint64_t *qual_off, uint8_t *qual, int16_t *mapq, uint8_t *outcome, int32_t *cap4);
+int vb2_baq_result_stats(const vb2_baq_result *r, vb2_baq_stats *out);      /* where = 0: the counts; tiers and times 0 */
+void vb2_baq_result_free(vb2_baq_result *r);
+/* The HMM alone on the host: ref and query are codes 0..4, qual the base qualities, bw the band's configured width; state
+ * and q as kpa_glocal fills them.  *undefined (may be NULL): the undefined rows. */
+int vb2_baq_case(const uint8_t *ref, int32_t l_ref, const uint8_t *query, const uint8_t *qual, int32_t l_query, int32_t bw,
+                 int32_t *state, uint8_t *q, int32_t *undefined);
+/* (int)(-4.343*log(z) + .499) for 0 < z by the threshold table the device searches (above 100: 101) */
+int32_t vb2_baq_quantise(double z);
+/* bytes of a record's workspace: what sorts it into the LDS tier (<= tunable baq_lds_kb KiB / 4) or the global one */
+uint64_t vb2_baq_work_bytes(int32_t l_ref, int32_t l_query, int32_t bw);
+/* The FASTA reader alone: *length = the sequence's length in the .fai (VB2_ERR_INVALID when the FASTA lacks it); out (may
+ * be NULL) gets the nt16 codes of [beg, end). */
+int vb2_fasta_fetch(const char *fasta_path, const char *name, int64_t beg, int64_t end, uint8_t *out, int64_t *length);
 
 /* ---- .bam lines in a cohort's list ----
  * A line of vb2_cohort_args.pileup_paths whose name ends in ".bam" is read by the built-in BAM reader (with base.mpileup,

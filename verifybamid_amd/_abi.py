@@ -101,7 +101,7 @@ class RunArgs(C.Structure):
         ("pileup_path", C.c_char_p), ("known_af_path", C.c_char_p), ("output_prefix", C.c_char_p),
         ("num_pc", C.c_int32), ("disable_sanity", C.c_int32), ("output_pileup", C.c_int32),
         ("device", C.c_int32), ("model", Model),
-        ("devices", C.POINTER(C.c_int32)), ("num_device", C.c_int32), ("reserved", C.c_int32),
+        ("devices", C.POINTER(C.c_int32)), ("num_device", C.c_int32), ("bam_adjust", C.c_int32),
         ("bam_path", C.c_char_p), ("reference_path", C.c_char_p), ("search", SearchOpts),
         ("mpileup", MpileupOpts),
     ]
@@ -113,6 +113,14 @@ class RunResult(C.Structure):
         ("num_bases", C.c_int64), ("avg_depth", C.c_double), ("sd_depth", C.c_double),
         ("seconds_load", C.c_double), ("seconds_optimize", C.c_double),
     ]
+
+
+class BaqStats(C.Structure):
+    """vb2_baq_stats: what --ApplyBAQ did to the records of one load (or of one vb2_baq_records call)."""
+    _fields_ = [(n, C.c_int64) for n in ("records", "realigned", "left_alone", "tag_applied", "no_reference", "dropped_outside",
+                                          "dropped_cap", "not_asked", "records_lds", "records_global", "undefined_rows",
+                                          "fasta_bytes")] + \
+               [(n, C.c_double) for n in ("seconds_fasta", "seconds_lds", "seconds_global", "seconds_cap", "seconds_stage")]
 
 
 class BamStats(C.Structure):
@@ -282,6 +290,8 @@ SYMBOLS = [
     "vb2_paired_create", "vb2_paired_create_from_set", "vb2_paired_destroy", "vb2_paired_eval", "vb2_paired_optimize_llk",
     "vb2_paired_info_get", "vb2_paired_lockstep", "vb2_cohort_run_paired", "vb2_matched_normal_read",
     "vb2_cohort_run_paired_intervals", "vb2_paired_derivs", "vb2_paired_derivs_sets", "vb2_paired_interval", "vb2_paired_intervals_lockstep",
+    "vb2_flat_baq_stats", "vb2_baq_records", "vb2_baq_result_num", "vb2_baq_result_qual_bytes", "vb2_baq_result_copy",
+    "vb2_baq_result_stats", "vb2_baq_result_free", "vb2_baq_case", "vb2_baq_quantise", "vb2_baq_work_bytes", "vb2_fasta_fetch",
     "vb2_flat_bam_stats", "vb2_bam_scan", "vb2_bam_scan_stats", "vb2_bam_scan_records", "vb2_bam_scan_sample", "vb2_bam_scan_free",
     "vb2_bam_scan_ex", "vb2_bam_scan_num_group", "vb2_bam_scan_group_id", "vb2_bam_scan_record_groups",
     "vb2_flat_load_groups", "vb2_flat_groups_count", "vb2_flat_groups_id", "vb2_flat_groups_records", "vb2_flat_groups_status",
@@ -346,6 +356,23 @@ def lib():
     L.vb2_flat_free.argtypes = [C.c_void_p]
     L.vb2_flat_free.restype = None
     L.vb2_flat_bam_stats.argtypes = [C.c_void_p, C.POINTER(BamStats)]
+    L.vb2_flat_baq_stats.argtypes = [C.c_void_p, C.POINTER(BaqStats)]
+    L.vb2_baq_records.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(MpileupOpts), C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    L.vb2_baq_result_num.argtypes = [C.c_void_p]
+    L.vb2_baq_result_num.restype = C.c_int64
+    L.vb2_baq_result_qual_bytes.argtypes = [C.c_void_p]
+    L.vb2_baq_result_qual_bytes.restype = C.c_int64
+    L.vb2_baq_result_copy.argtypes = [C.c_void_p] * 6
+    L.vb2_baq_result_stats.argtypes = [C.c_void_p, C.POINTER(BaqStats)]
+    L.vb2_baq_result_free.argtypes = [C.c_void_p]
+    L.vb2_baq_result_free.restype = None
+    L.vb2_baq_case.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                               C.POINTER(C.c_int32)]
+    L.vb2_baq_quantise.argtypes = [C.c_double]
+    L.vb2_baq_quantise.restype = C.c_int32
+    L.vb2_baq_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.vb2_baq_work_bytes.restype = C.c_uint64
+    L.vb2_fasta_fetch.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
     L.vb2_bam_scan.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
     L.vb2_bam_scan_stats.argtypes = [C.c_void_p, C.POINTER(BamStats)]
     L.vb2_bam_scan_records.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]

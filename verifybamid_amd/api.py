@@ -1200,18 +1200,22 @@ def _mpileup_opts(mpileup):
                                                       "incl_flags", "excl_flags")])
 
 
-def _set_bam(args, bam_path, mpileup):
+def _set_bam(args, bam_path, mpileup, apply_baq=False, reference_path=None):
     if bam_path is not None:
         if args.pileup_path is not None:
             raise ValueError("pileup_path and bam_path exclude each other")
         args.bam_path = str(bam_path).encode()
     args.mpileup = _mpileup_opts(mpileup)
+    # --ApplyBAQ (vb2_run_args.bam_adjust): an int passes through as it is, so that a test can hand the library a value it refuses
+    args.bam_adjust = int(apply_baq)
+    if reference_path is not None:
+        args.reference_path = str(reference_path).encode()
 
 
 def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_sanity=False,
               known_af_path=None, device=-1, output_pileup=False, devices=None, confidence_interval=False,
               per_chromosome=False, bootstrap=0, bam_path=None, mpileup=None, per_read_group=False, ref_bias=False,
-              **model_kw):
+              apply_baq=False, reference_path=None, **model_kw):
     """The --SVDPrefix/--PileupFile flow of execute() (vb2_run); devices=[a, b, ...] shards the
     sample's markers over those GPUs.  confidence_interval: vb2_run_interval (<output_prefix>.CI, and an
     `interval` entry in the result).  per_chromosome / bootstrap=N (seeded by seed=): vb2_run_replicates
@@ -1221,10 +1225,12 @@ def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_san
     per_read_group (with bam_path): vb2_run_read_groups -- the whole sample as ever, <output_prefix>.selfRG, and a
     `read_groups` list in the result: per @RG line of the header its id, status (0, VB2_ERR_SANITY or 1 = no base), records,
     the estimate's entries (zero when not searched) and num_site, num_bases, avg_depth.
-    ref_bias: vb2_run_refbias (<output_prefix>.RefBias, and a `ref_bias` entry in the result: the dict of RefBias.fit)."""
+    ref_bias: vb2_run_refbias (<output_prefix>.RefBias, and a `ref_bias` entry in the result: the dict of RefBias.fit).
+    apply_baq (with bam_path and reference_path, the FASTA with its .fai): --ApplyBAQ -- the Illumina shift, base alignment
+    quality and the mapping-quality cap the pileup options ask for are applied to the records before the pileup."""
     args, keep = _run_args(svd_prefix, pileup_path, num_pc, disable_sanity, known_af_path,
                            output_prefix, device, output_pileup, devices=devices, **model_kw)
-    _set_bam(args, bam_path, mpileup)
+    _set_bam(args, bam_path, mpileup, apply_baq, reference_path)
     res = _abi.RunResult()
     ci = _abi.Interval() if confidence_interval else None
     summary = None
@@ -1279,12 +1285,13 @@ def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_san
     return out
 
 
-def load_bam(svd_prefix, bam_path, num_pc=2, mpileup=None, device=-1, disable_sanity=True, known_af_path=None):
+def load_bam(svd_prefix, bam_path, num_pc=2, mpileup=None, device=-1, disable_sanity=True, known_af_path=None, apply_baq=False,
+             reference_path=None):
     """vb2_flat_load of a BAM (the built-in reader: host stage, then the pileup on `device`), without a search: the
     panel-ordered reads -- read_off [M + 1], bases, quals as bytes --, num_site, num_bases, avg_depth and the load's
-    vb2_bam_stats as `stats`."""
+    vb2_bam_stats as `stats`.  apply_baq (with reference_path): --ApplyBAQ, and the stage's vb2_baq_stats as `baq`."""
     args, keep = _run_args(svd_prefix, None, num_pc, disable_sanity, known_af_path, None, device)
-    _set_bam(args, bam_path, mpileup)
+    _set_bam(args, bam_path, mpileup, apply_baq, reference_path)
     L = _abi.lib()
     h = C.c_void_p()
     _abi.check(L.vb2_flat_load(C.byref(args), C.byref(h)), "vb2_flat_load")
@@ -1297,9 +1304,14 @@ def load_bam(svd_prefix, bam_path, num_pc=2, mpileup=None, device=-1, disable_sa
         _abi.check(L.vb2_flat_stats(h, C.byref(res)), "vb2_flat_stats")
         st = _abi.BamStats()
         _abi.check(L.vb2_flat_bam_stats(h, C.byref(st)), "vb2_flat_bam_stats")
-        return dict(read_off=off, bases=C.string_at(inp.bases, n) if n else b"", quals=C.string_at(inp.quals, n) if n else b"",
-                    num_site=res.num_site, num_bases=int(res.num_bases), avg_depth=res.avg_depth,
-                    stats={name: getattr(st, name) for name, _ in _abi.BamStats._fields_})
+        out = dict(read_off=off, bases=C.string_at(inp.bases, n) if n else b"", quals=C.string_at(inp.quals, n) if n else b"",
+                   num_site=res.num_site, num_bases=int(res.num_bases), avg_depth=res.avg_depth,
+                   stats={name: getattr(st, name) for name, _ in _abi.BamStats._fields_})
+        if args.bam_adjust == 1:
+            bs = _abi.BaqStats()
+            _abi.check(L.vb2_flat_baq_stats(h, C.byref(bs)), "vb2_flat_baq_stats")
+            out["baq"] = {name: getattr(bs, name) for name, _ in _abi.BaqStats._fields_}
+        return out
     finally:
         L.vb2_flat_free(h)
 
@@ -1316,12 +1328,13 @@ def _flat_bam_dict(L, h):
                 num_site=res.num_site, num_bases=int(res.num_bases), avg_depth=res.avg_depth)
 
 
-def load_bam_groups(svd_prefix, bam_path, num_pc=2, mpileup=None, device=-1, disable_sanity=True, known_af_path=None):
+def load_bam_groups(svd_prefix, bam_path, num_pc=2, mpileup=None, device=-1, disable_sanity=True, known_af_path=None,
+                    apply_baq=False, reference_path=None):
     """vb2_flat_load_groups: the whole sample's dict as load_bam returns it, plus `groups` -- a list with one such dict (less
     `stats`) per @RG line of the header with its `id`, `records` and `status` --, `unassigned`, the number of kept records
     that belong to no group, and what the groups' part of the load took (groups_seconds_device, groups_seconds_copyback)."""
     args, keep = _run_args(svd_prefix, None, num_pc, disable_sanity, known_af_path, None, device)
-    _set_bam(args, bam_path, mpileup)
+    _set_bam(args, bam_path, mpileup, apply_baq, reference_path)
     L = _abi.lib()
     h, hg = C.c_void_p(), C.c_void_p()
     try:
@@ -1376,6 +1389,59 @@ def bam_scan(bam_path, bed_path, groups=False):
         L.vb2_bam_scan_free(h)
 
 
+def baq_records(bam_path, bed_path, reference_path, mpileup=None, where=0, device=-1):
+    """vb2_baq_records: what --ApplyBAQ makes of the records the scan sends up, in its order.  where=0: the sequential host
+    driver of csrc/baq_core.h (no device; a diagnostic, not a fallback), where=1: the device stage.  dict(qual_off [n + 1],
+    qual (uint8, the adjusted qualities back to back), mapq (int16, -1 = dropped), outcome (uint8), cap4 [n, 4], stats)."""
+    L = _abi.lib()
+    h = C.c_void_p()
+    opts = _mpileup_opts(mpileup)
+    _abi.check(L.vb2_baq_records(str(bam_path).encode(), str(bed_path).encode(),
+                                 None if reference_path is None else str(reference_path).encode(), C.byref(opts), int(where),
+                                 int(device), C.byref(h)), "vb2_baq_records")
+    try:
+        n, nq = L.vb2_baq_result_num(h), L.vb2_baq_result_qual_bytes(h)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        qual = np.zeros(max(nq, 1), dtype=np.uint8)
+        mapq = np.zeros(max(n, 1), dtype=np.int16)
+        outcome = np.zeros(max(n, 1), dtype=np.uint8)
+        cap4 = np.zeros((max(n, 1), 4), dtype=np.int32)
+        _abi.check(L.vb2_baq_result_copy(h, _p(off), _p(qual), _p(mapq), _p(outcome), _p(cap4)), "vb2_baq_result_copy")
+        st = _abi.BaqStats()
+        _abi.check(L.vb2_baq_result_stats(h, C.byref(st)), "vb2_baq_result_stats")
+        return dict(qual_off=off, qual=qual[:nq], mapq=mapq[:n], outcome=outcome[:n], cap4=cap4[:n],
+                    stats={name: getattr(st, name) for name, _ in _abi.BaqStats._fields_})
+    finally:
+        L.vb2_baq_result_free(h)
+
+
+def baq_case(ref, query, qual, bw):
+    """vb2_baq_case: the HMM of --ApplyBAQ alone on the host over codes 0..4: (state [int32], q [uint8], undefined rows)."""
+    ref = np.ascontiguousarray(ref, dtype=np.uint8)
+    query = np.ascontiguousarray(query, dtype=np.uint8)
+    qual = np.ascontiguousarray(qual, dtype=np.uint8)
+    state = np.zeros(max(len(query), 1), dtype=np.int32)
+    q = np.zeros(max(len(query), 1), dtype=np.uint8)
+    und = C.c_int32(0)
+    _abi.check(_abi.lib().vb2_baq_case(_p(ref) if len(ref) else None, len(ref), _p(query) if len(query) else None,
+                                       _p(qual) if len(query) else None, len(query), int(bw), _p(state), _p(q), C.byref(und)),
+               "vb2_baq_case")
+    return state[:len(query)], q[:len(query)], und.value
+
+
+def fasta_fetch(fasta_path, name, beg=0, end=None):
+    """vb2_fasta_fetch: (nt16 codes of [beg, end) of the sequence as uint8, the sequence's length in the .fai)."""
+    L = _abi.lib()
+    length = C.c_int64(0)
+    _abi.check(L.vb2_fasta_fetch(str(fasta_path).encode(), str(name).encode(), 0, 0, None, C.byref(length)), "vb2_fasta_fetch")
+    if end is None:
+        end = length.value
+    out = np.zeros(max(end - beg, 1), dtype=np.uint8)
+    _abi.check(L.vb2_fasta_fetch(str(fasta_path).encode(), str(name).encode(), int(beg), int(end), _p(out), C.byref(length)),
+               "vb2_fasta_fetch")
+    return out[:max(end - beg, 0)], length.value
+
+
 def bgzf_inflate(data, device=-1):
     """The BGZF blocks of `data` (bytes: a whole file or any run of whole blocks) inflated on the device
     (vb2_bgzf_inflate: bgzf_inflate_kernel, one wave per block; no zlib fallback and no CRC32).  Returns (bytes, statuses):
@@ -1408,7 +1474,7 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
                      known_af_path=None, device=-1, output_pileup=False, group_size=0, num_host_thread=0,
                      devices=None, find_source=False, source_top=3, sources_prefix=None, confidence_interval=False,
                      refit_source=False, find_related=False, related_top=3, matched_normal=None, normal_hom_min=0.99,
-                     pair_interval=False, mpileup=None, **model_kw):
+                     pair_interval=False, mpileup=None, apply_baq=False, reference_path=None, **model_kw):
     """Many pileups against one panel (vb2_cohort_run): the panel is read once, the pileups are read
     and flattened by host threads while the device searches the previous group in lock-step.
     Returns one dict per sample (with its own "status" code).
@@ -1447,6 +1513,9 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
                            sources_prefix if find_source or find_related or matched_normal is not None else None,
                            device, output_pileup, devices=devices, **model_kw)
     args.mpileup = _mpileup_opts(mpileup)
+    args.bam_adjust = int(apply_baq)      # --ApplyBAQ for the list's .bam lines (reference_path: the FASTA)
+    if reference_path is not None:
+        args.reference_path = str(reference_path).encode()
     ca = _abi.CohortArgs()
     ca.base = args
     ca.num_sample = S

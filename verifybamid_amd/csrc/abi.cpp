@@ -29,6 +29,8 @@
 #include "replicates.h"
 #include "read_groups.h"
 #include "bgzf_inflate_kernels.h"
+#include "baq_host.h"
+#include "fasta_io.h"
 
 using vb2::set_error;
 
@@ -723,6 +725,14 @@ int flat_load_impl(const vb2_run_args* a, vb2_flat** out, vb2_flat_groups* group
         return VB2_ERR_INVALID;
     }
     *out = nullptr;
+    if (a->bam_adjust != 0 && a->bam_adjust != 1) {
+        set_error("vb2_flat_load: bam_adjust is " + std::to_string(a->bam_adjust) + "; it is 0 (BAM records as they are) or 1 (--ApplyBAQ)");
+        return VB2_ERR_INVALID;
+    }
+    if (a->bam_adjust == 1 && a->bam_path && !a->pileup_path && !a->reference_path) {
+        set_error("vb2_flat_load: bam_adjust = 1 (--ApplyBAQ) needs reference_path, the FASTA the BAM was aligned to");
+        return VB2_ERR_INVALID;
+    }
     return vb2::guarded([&]() -> int {
         std::unique_ptr<vb2_flat> f(new vb2_flat());
         f->panel.numPC = a->num_pc;
@@ -752,12 +762,17 @@ int flat_load_impl(const vb2_run_args* a, vb2_flat** out, vb2_flat_groups* group
         int rc_pile = VB2_OK;
         std::string err_main = rc ? vb2::g_last_error : std::string(), err_pile;
         if (!rc) {
+            vb2::BamReadHow how;
+            how.bam_adjust = a->bam_adjust;
+            how.baq_stats = &f->baq_stats;
+            const std::string ref_path = a->reference_path ? a->reference_path : "";
             rc_pile = a->pileup_path ? vb2::read_pileup(a->pileup_path, f->panel, &f->viewer)
-                      : groups       ? vb2::read_bam_groups(a->bam_path, f->panel_ptr, &f->viewer, &a->mpileup, a->device, &f->bam_stats, groups)
-                                     : vb2::read_bam(a->bam_path, a->reference_path ? a->reference_path : "",
-                                                     f->panel, &f->viewer, &a->mpileup, a->device, &f->bam_stats);
+                      : groups       ? vb2::read_bam_groups(a->bam_path, f->panel_ptr, &f->viewer, &a->mpileup, a->device, &f->bam_stats, groups,
+                                                            ref_path, &how)
+                                     : vb2::read_bam(a->bam_path, ref_path, f->panel, &f->viewer, &a->mpileup, a->device, &f->bam_stats, &how);
             if (rc_pile) err_pile = vb2::g_last_error;
             f->from_bam = !a->pileup_path && !rc_pile;
+            f->with_baq = f->from_bam && a->bam_adjust == 1;
         }
         tl_pile = now_s();
         t_ud.join();
@@ -873,6 +888,110 @@ int vb2_flat_bam_stats(const vb2_flat* f, vb2_bam_stats* out)
     }
     *out = f->bam_stats;
     return VB2_OK;
+}
+
+int vb2_flat_baq_stats(const vb2_flat* f, vb2_baq_stats* out)
+{
+    if (!f || !out || !f->with_baq) {
+        set_error("vb2_flat_baq_stats: not a vb2_flat loaded from a BAM with bam_adjust = 1");
+        return VB2_ERR_INVALID;
+    }
+    *out = f->baq_stats;
+    return VB2_OK;
+}
+
+struct vb2_baq_result {
+    vb2::BaqRecords r;
+};
+
+int vb2_baq_records(const char* bam_path, const char* bed_path, const char* reference_path, const vb2_mpileup_opts* opts, int where,
+                    int device, vb2_baq_result** out)
+{
+    if (!bam_path || !bed_path || !out) {
+        set_error("vb2_baq_records: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    *out = nullptr;
+    return vb2::guarded([&]() -> int {
+        std::unique_ptr<vb2_baq_result> r(new vb2_baq_result());
+        if (int rc = vb2::baq_records_file(bam_path, bed_path, reference_path ? reference_path : "", opts, where, device, &r->r)) return rc;
+        *out = r.release();
+        return VB2_OK;
+    });
+}
+
+int64_t vb2_baq_result_num(const vb2_baq_result* r) { return r ? (int64_t)r->r.outcome.size() : 0; }
+int64_t vb2_baq_result_qual_bytes(const vb2_baq_result* r) { return r ? (int64_t)r->r.qual.size() : 0; }
+
+int vb2_baq_result_copy(const vb2_baq_result* r, uint64_t* qual_off, uint8_t* qual, int16_t* mapq, uint8_t* outcome, int32_t* cap4)
+{
+    if (!r) return VB2_ERR_INVALID;
+    const vb2::BaqRecords& b = r->r;
+    if (qual_off) std::copy(b.qual_off.begin(), b.qual_off.end(), qual_off);
+    if (qual) std::copy(b.qual.begin(), b.qual.end(), qual);
+    if (mapq) std::copy(b.mapq.begin(), b.mapq.end(), mapq);
+    if (outcome) std::copy(b.outcome.begin(), b.outcome.end(), outcome);
+    if (cap4) std::copy(b.cap4.begin(), b.cap4.end(), cap4);
+    return VB2_OK;
+}
+
+int vb2_baq_result_stats(const vb2_baq_result* r, vb2_baq_stats* out)
+{
+    if (!r || !out) return VB2_ERR_INVALID;
+    *out = r->r.stats;
+    return VB2_OK;
+}
+
+void vb2_baq_result_free(vb2_baq_result* r) { delete r; }
+
+int vb2_baq_case(const uint8_t* ref, int32_t l_ref, const uint8_t* query, const uint8_t* qual, int32_t l_query, int32_t bw, int32_t* state,
+                 uint8_t* q, int32_t* undefined)
+{
+    if (l_query < 0 || l_ref < 0 || bw < 0 || (l_query > 0 && (!query || !qual || !state || !q)) || (l_ref > 0 && !ref)) {
+        set_error("vb2_baq_case: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    return vb2::guarded([&]() -> int {
+        const int u = vb2::baq::run_case(ref, l_ref, query, qual, l_query, bw, state, q);
+        if (undefined) *undefined = u;
+        return VB2_OK;
+    });
+}
+
+int32_t vb2_baq_quantise(double z) { return vb2::baq::quantise(vb2::baq::tables().thresh, z); }
+
+uint64_t vb2_baq_work_bytes(int32_t l_ref, int32_t l_query, int32_t bw) { return vb2::baq::work_bytes(l_ref, l_query, bw); }
+
+int vb2_fasta_fetch(const char* fasta_path, const char* name, int64_t beg, int64_t end, uint8_t* out, int64_t* length)
+{
+    if (!fasta_path || !name) {
+        set_error("vb2_fasta_fetch: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    return vb2::guarded([&]() -> int {
+        vb2::fasta::Index idx;
+        std::string err;
+        if (int rc = vb2::fasta::open_index(fasta_path, &idx, &err)) {
+            set_error(err);
+            return rc;
+        }
+        const int s = idx.find(name);
+        if (s < 0) {
+            set_error(std::string("--Reference: ") + fasta_path + " has no sequence " + name);
+            return VB2_ERR_INVALID;
+        }
+        if (length) *length = idx.seqs[(size_t)s].length;
+        if (!out) return VB2_OK;
+        if (beg < 0 || end < beg || end > idx.seqs[(size_t)s].length) {
+            set_error("vb2_fasta_fetch: the span passes the sequence");
+            return VB2_ERR_INVALID;
+        }
+        if (int rc = vb2::fasta::fetch_nt16(idx, s, beg, end, out, &err)) {
+            set_error(err);
+            return rc;
+        }
+        return VB2_OK;
+    });
 }
 
 struct vb2_bam_scan_result {

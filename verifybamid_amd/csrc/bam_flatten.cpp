@@ -13,7 +13,8 @@
 //
 // TWO READERS, one per build.  The default build has the built-in one at the end of this file: the
 // host stage of bam_io.cpp (BGZF, header, .bai, records; plain C++ and zlib), the per-marker pileup of the decoded records on
-// the device (bam_pileup_kernels.hip), the pools back into the PileupViewer.  It applies neither BAQ nor the mapQ cap and
+// the device (bam_pileup_kernels.hip), the pools back into the PileupViewer.  It applies BAQ and the mapQ cap only under
+// bam_adjust = 1 (--ApplyBAQ: fasta_io.cpp, baq_host.cpp, baq_stage.cpp, baq_kernels.hip) and
 // takes the panel's REF allele as the reference base; it is pinned to tests/bam_ref.py's restatement and to the reference's
 // golden files (tests/test_bam_gpu.py).
 // The htslib reader below NEEDS htslib (>= 1.10: hts_pos_t), which neither this build image nor the GPU box has (probed
@@ -241,13 +242,19 @@ int read_bam(const std::string& bam_path, const std::string& ref_path, const Pan
 }
 
 int read_bam_groups(const std::string&, const std::shared_ptr<Panel>&, PileupViewer*, const vb2_mpileup_opts*, int, vb2_bam_stats*,
-                    vb2_flat_groups*)
+                    vb2_flat_groups*, const std::string&, const BamReadHow*)
 {
     set_error("--PerReadGroup: this library reads BAM through htslib (VB2_WITH_HTSLIB); read groups are the built-in reader's");
     return VB2_ERR_INVALID;
 }
 
 bool bam_support() { return true; }
+
+int baq_records_file(const std::string&, const std::string&, const std::string&, const vb2_mpileup_opts*, int, int, BaqRecords*)
+{
+    set_error("vb2_baq_records: this library reads BAM through htslib (VB2_WITH_HTSLIB), which applies BAQ itself");
+    return VB2_ERR_INVALID;
+}
 
 int bam_scan_file(const std::string&, const std::string&, std::vector<uint64_t>*, vb2_bam_stats*, std::string*,
                   std::vector<std::string>*, std::vector<uint16_t>*)
@@ -262,6 +269,8 @@ int bam_scan_file(const std::string&, const std::string&, std::vector<uint64_t>*
 
 #include "bam_io.h"
 #include "bam_pileup_kernels.h"
+#include "baq_host.h"
+#include "baq_stage.h"
 #include "bgzf_inflate_kernels.h"
 #include "device_util.h"
 #include "tunables.h"
@@ -336,7 +345,7 @@ bool group_slots_fit(size_t num_group, size_t num_slot) { return (uint64_t)num_g
 // whole sample's and from the same sorted entries: the whole sample's launches and bytes are what they are without it.
 int device_pileup(const bamio::Scan& scan, const std::vector<std::vector<std::pair<int32_t, int32_t>>>& by_seq, const Panel& panel,
                   const MplpConf& conf, int device, PileupViewer* v, vb2_bam_stats* stats, vb2_flat_groups* groups = nullptr,
-                  hipStream_t caller_stream = nullptr)
+                  hipStream_t caller_stream = nullptr, const baq::Spans* spans = nullptr, vb2_baq_stats* baq_stats = nullptr)
 {
     const double t0 = now_s();
     const int32_t num_slot = (int32_t)panel.num_slot();
@@ -423,12 +432,23 @@ int device_pileup(const bamio::Scan& scan, const std::vector<std::vector<std::pa
     int64_t num_entries = 0, num_batch = 0;
     uint8_t* const hd = static_cast<uint8_t*>(h_data.p);
     bamio::RecordDesc* const hr = static_cast<bamio::RecordDesc*>(h_desc.p);
+    // --ApplyBAQ: a stage between a batch's upload and its cover pass; without it nothing below differs
+    const baq::Options baq_opt = baq::options_of(conf.flag, conf.capQ_thres);
+    std::unique_ptr<BaqStage> baq_stage;
+    std::vector<baq::Task> baq_tasks;
+    std::vector<uint8_t> baq_extra;
+    if (spans) {
+        baq_stage.reset(new BaqStage(baq_opt, s));
+        if (int rc = baq_stage->init(*spans, batch_rec, batch_bytes)) return rc;
+    }
 
     size_t ci = 0, ri = 0;                        // next record: scan.chunks[ci].recs[ri]
     auto skip_empty = [&] { while (ci < scan.chunks.size() && ri >= scan.chunks[ci].recs.size()) { ++ci; ri = 0; } };
     skip_empty();
     while (ci < scan.chunks.size()) {
         size_t nb = 0, nr = 0;
+        baq_tasks.clear();
+        baq_extra.clear();
         while (ci < scan.chunks.size() && nr < batch_rec) {
             const bamio::Chunk& ch = scan.chunks[ci];
             const bamio::RecordDesc& d = ch.recs[ri];
@@ -442,6 +462,15 @@ int device_pileup(const bamio::Scan& scan, const std::vector<std::vector<std::pa
             hr[nr] = d;
             hr[nr].data = (uint32_t)nb;
             if (hg) hg[nr] = ri < ch.group.size() ? ch.group[ri] : bamio::kNoGroup;
+            if (baq_stage) {
+                const uint8_t* bq = nullptr;
+                baq::Task t = baq::make_task(scan, ci, ri, *spans, baq_opt, &bq);
+                if (t.kind == 1 && bq) {
+                    t.bq_off = (uint32_t)baq_extra.size();
+                    baq_extra.insert(baq_extra.end(), bq, bq + d.l_seq);
+                }
+                baq_tasks.push_back(t);
+            }
             nb += vb;
             ++nr;
             ++ri;
@@ -453,8 +482,17 @@ int device_pileup(const bamio::Scan& scan, const std::vector<std::vector<std::pa
         VB2_HIP(hipMemcpyAsync(d_data, hd, nb, hipMemcpyHostToDevice, s));
         VB2_HIP(hipMemcpyAsync(d_desc.p, hr, nr * sizeof(bamio::RecordDesc), hipMemcpyHostToDevice, s));
         if (hg) VB2_HIP(hipMemcpyAsync(d_grp.p, hg, nr * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+        const uint8_t* adj_qual = nullptr;
+        const int16_t* adj_mapq = nullptr;
+        if (baq_stage) {
+            if (int rc = baq_stage->run(baq_tasks, baq_extra, hr, nr, d_desc.as<bamio::RecordDesc>(), static_cast<const uint8_t*>(d_data),
+                                        nb, nullptr, nullptr, nullptr, nullptr))
+                return rc;
+            adj_qual = baq_stage->adjq();
+            adj_mapq = baq_stage->adj_mapq();
+        }
         VB2_HIP(launch_cover_count(d_desc.as<bamio::RecordDesc>(), (int64_t)nr, static_cast<const uint8_t*>(d_data), nb, filter,
-                                   markers, d_count.as<uint32_t>(), s));
+                                   markers, d_count.as<uint32_t>(), s, adj_qual, adj_mapq));
         VB2_HIP(launch_scan_u32(d_count.as<uint32_t>(), d_offset.as<uint32_t>(), (int64_t)nr, d_total.as<unsigned long long>(), s));
         VB2_HIP(hipMemcpyAsync(h_total.p, d_total.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
         VB2_HIP(hipStreamSynchronize(s));        // the staging buffers are free again; the fill below runs under the next copy-in
@@ -480,12 +518,14 @@ int device_pileup(const bamio::Scan& scan, const std::vector<std::vector<std::pa
         if (add > 0)
             VB2_HIP(launch_cover_fill(d_desc.as<bamio::RecordDesc>(), (int64_t)nr, static_cast<const uint8_t*>(d_data), nb, filter,
                                       markers, d_offset.as<uint32_t>(), d_entries.as<PileEntry>() + num_entries,
-                                      d_keys.as<uint64_t>() + num_entries, s, d_grp.as<uint16_t>()));
+                                      d_keys.as<uint64_t>() + num_entries, s, d_grp.as<uint16_t>(), adj_qual, adj_mapq));
         // (d_desc and d_offset are written again only by the next batch's copies, which the stream orders behind this fill)
         num_entries += (int64_t)add;
         ++num_batch;
     }
     VB2_HIP(hipStreamSynchronize(s));
+    if (baq_stage && baq_stats) *baq_stats = baq_stage->stats;
+    baq_stage.reset();
 
     // ---- sort by slot (file order within a slot), the overlap rule, the sites ----
     Dev d_keys2, d_idx, d_idx2, d_temp, d_sorted, d_qual, d_range, d_depth, d_off, d_rep, d_bases, d_quals;
@@ -680,10 +720,16 @@ void host_stats(const bamio::Scan& scan, vb2_bam_stats* st)
 
 // read_bam, and read_bam_groups with groups != nullptr
 static int read_bam_impl(const std::string& bam_path, const Panel& panel, PileupViewer* v, const vb2_mpileup_opts* mp, int device,
-                         vb2_bam_stats* stats, vb2_flat_groups* groups, const std::shared_ptr<Panel>& shared, const BamReadHow* how = nullptr)
+                         vb2_bam_stats* stats, vb2_flat_groups* groups, const std::shared_ptr<Panel>& shared, const BamReadHow* how = nullptr,
+                         const std::string& ref_path = std::string())
 {
     MplpConf conf;
     conf.apply(mp);
+    const int bam_adjust = how ? how->bam_adjust : 0;
+    if (bam_adjust != 0 && bam_adjust != 1) {
+        set_error("--BamFile: bam_adjust is " + std::to_string(bam_adjust) + "; it is 0 (records as they are) or 1 (--ApplyBAQ)");
+        return VB2_ERR_INVALID;
+    }
     std::vector<bamio::SeqMarkers> seqs;
     std::vector<std::vector<std::pair<int32_t, int32_t>>> by_seq;
     markers_by_sequence(panel, &seqs, &by_seq);
@@ -751,23 +797,179 @@ static int read_bam_impl(const std::string& bam_path, const Panel& panel, Pileup
                   "(there is no CPU fallback)");
         return VB2_ERR_NO_DEVICE;
     }
-    return device_pileup(scan, by_seq, panel, conf, device, v, stats, groups, stream);
+    if (!bam_adjust) return device_pileup(scan, by_seq, panel, conf, device, v, stats, groups, stream);
+    // --ApplyBAQ: the spans of the FASTA the records can touch (not opened when the options ask for neither BAQ nor the cap)
+    baq::Spans spans;
+    if (int rc = baq::load_spans(scan, ref_path, baq::options_of(conf.flag, conf.capQ_thres), &spans, &err)) {
+        set_error(err);
+        return rc;
+    }
+    return device_pileup(scan, by_seq, panel, conf, device, v, stats, groups, stream, &spans, how->baq_stats);
 }
 
-int read_bam(const std::string& bam_path, const std::string&, const Panel& panel, PileupViewer* v, const vb2_mpileup_opts* mp,
+int read_bam(const std::string& bam_path, const std::string& ref_path, const Panel& panel, PileupViewer* v, const vb2_mpileup_opts* mp,
              int device, vb2_bam_stats* stats, const BamReadHow* how)
 {
-    return read_bam_impl(bam_path, panel, v, mp, device, stats, nullptr, nullptr, how);
+    return read_bam_impl(bam_path, panel, v, mp, device, stats, nullptr, nullptr, how, ref_path);
 }
 
 int read_bam_groups(const std::string& bam_path, const std::shared_ptr<Panel>& panel, PileupViewer* v, const vb2_mpileup_opts* mp,
-                    int device, vb2_bam_stats* stats, vb2_flat_groups* groups)
+                    int device, vb2_bam_stats* stats, vb2_flat_groups* groups, const std::string& ref_path, const BamReadHow* how)
 {
     if (!panel || !groups) {
         set_error("read_bam_groups: invalid argument");
         return VB2_ERR_INVALID;
     }
-    return read_bam_impl(bam_path, *panel, v, mp, device, stats, groups, panel);
+    return read_bam_impl(bam_path, *panel, v, mp, device, stats, groups, panel, how, ref_path);
+}
+
+// vb2_baq_records: the scan, the spans, and per record the host driver (where 0) or the device stage in the load's batches
+int baq_records_file(const std::string& bam_path, const std::string& bed_path, const std::string& ref_path, const vb2_mpileup_opts* mp,
+                     int where, int device, BaqRecords* out)
+{
+    if (where != 0 && where != 1) {
+        set_error("vb2_baq_records: where is 0 (host driver) or 1 (device stage)");
+        return VB2_ERR_INVALID;
+    }
+    MplpConf conf;
+    conf.apply(mp);
+    const baq::Options opt = baq::options_of(conf.flag, conf.capQ_thres);
+    Panel panel;
+    if (int rc = read_bed(bed_path, &panel)) return rc;
+    std::vector<bamio::SeqMarkers> seqs;
+    std::vector<std::vector<std::pair<int32_t, int32_t>>> by_seq;
+    markers_by_sequence(panel, &seqs, &by_seq);
+    bamio::Scan scan;
+    std::string err;
+    if (int rc = bamio::scan(bam_path, seqs, reader_threads(), &scan, &err)) {
+        set_error(err);
+        return rc;
+    }
+    baq::Spans spans;
+    if (int rc = baq::load_spans(scan, ref_path, opt, &spans, &err)) {
+        set_error(err);
+        return rc;
+    }
+    *out = BaqRecords{};
+    out->qual_off.push_back(0);
+    auto var_bytes = [](const bamio::RecordDesc& d) {
+        return (size_t)d.l_read_name + 4 * (size_t)d.n_cigar + ((size_t)d.l_seq + 1) / 2 + (size_t)d.l_seq;
+    };
+    if (where == 0) {
+        vb2_baq_stats& st = out->stats;
+        st.seconds_fasta = spans.seconds;
+        st.fasta_bytes = spans.bytes_read;
+        std::vector<double> scratch;
+        std::vector<uint8_t> q;
+        for (size_t ci = 0; ci < scan.chunks.size(); ++ci) {
+            const bamio::Chunk& ch = scan.chunks[ci];
+            for (size_t ri = 0; ri < ch.recs.size(); ++ri) {
+                const bamio::RecordDesc& d = ch.recs[ri];
+                const uint8_t* bq = nullptr;
+                baq::Task t = baq::make_task(scan, ci, ri, spans, opt, &bq);
+                if (t.kind == 1) t.bq_off = 0;
+                q.assign((size_t)d.l_seq, 0);
+                int32_t c4[4];
+                st.undefined_rows += baq::run_record(d, ch.bytes.data() + d.data, t, spans.codes.data(), bq, opt, q.data(), c4, &scratch);
+                int mq = d.mapq;
+                uint8_t oc = t.outcome;
+                if (oc == baq::kOutside) {
+                    mq = -1;
+                } else if (t.cap) {
+                    mq = baq::capped_mapq(mq, baq::cap_finish(c4, opt.cap));
+                    if (mq < 0) oc = baq::kCapDropped;
+                }
+                ++st.records;
+                switch (oc) {
+                case baq::kRealigned: ++st.realigned; break;
+                case baq::kAlone: ++st.left_alone; break;
+                case baq::kTagApplied: ++st.tag_applied; break;
+                case baq::kNoReference: ++st.no_reference; break;
+                case baq::kOutside: ++st.dropped_outside; break;
+                case baq::kCapDropped: ++st.dropped_cap; break;
+                default: ++st.not_asked; break;
+                }
+                out->qual.insert(out->qual.end(), q.begin(), q.end());
+                out->qual_off.push_back(out->qual.size());
+                out->mapq.push_back((int16_t)mq);
+                out->outcome.push_back(oc);
+                out->cap4.insert(out->cap4.end(), c4, c4 + 4);
+            }
+        }
+        return VB2_OK;
+    }
+    if (usable_device_count() < 1) {
+        set_error("vb2_baq_records: where = 1 runs the device stage and no gfx950 device is visible");
+        return VB2_ERR_NO_DEVICE;
+    }
+    if (device >= 0) VB2_HIP(hipSetDevice(device));
+    StreamHolder st;
+    VB2_HIP(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    hipStream_t s = st.s;
+    // the batches of device_pileup: closed by tunable bam_batch_kb
+    size_t largest = 0, total_rec = 0;
+    for (const bamio::Chunk& ch : scan.chunks) {
+        total_rec += ch.recs.size();
+        for (const bamio::RecordDesc& d : ch.recs) largest = std::max(largest, var_bytes(d));
+    }
+    const size_t batch_bytes = std::max<size_t>((size_t)std::max(vb2::tunables().bam_batch_kb, 1) << 10, largest);
+    if (batch_bytes > 0xfff00000ull) { set_error("vb2_baq_records: bam_batch_kb asks for batches of 4 GiB or more"); return VB2_ERR_INVALID; }
+    const size_t batch_rec = std::min<size_t>(std::max<size_t>(total_rec, 1), std::max<size_t>(batch_bytes / sizeof(bamio::RecordDesc), 1));
+    std::vector<uint8_t> hd(batch_bytes);
+    std::vector<bamio::RecordDesc> hr(batch_rec);
+    Dev d_data, d_desc;
+    VB2_HIP(hipMalloc(&d_data.p, batch_bytes));
+    VB2_HIP(hipMalloc(&d_desc.p, batch_rec * sizeof(bamio::RecordDesc)));
+    BaqStage stage(opt, s);
+    if (int rc = stage.init(spans, batch_rec, batch_bytes)) return rc;
+    std::vector<baq::Task> tasks;
+    std::vector<uint8_t> extra;
+    size_t ci = 0, ri = 0;
+    auto skip_empty = [&] { while (ci < scan.chunks.size() && ri >= scan.chunks[ci].recs.size()) { ++ci; ri = 0; } };
+    skip_empty();
+    while (ci < scan.chunks.size()) {
+        size_t nb = 0, nr = 0;
+        tasks.clear();
+        extra.clear();
+        while (ci < scan.chunks.size() && nr < batch_rec) {
+            const bamio::Chunk& ch = scan.chunks[ci];
+            const bamio::RecordDesc& d = ch.recs[ri];
+            const size_t vb = var_bytes(d);
+            if ((size_t)d.data > ch.bytes.size() || vb > ch.bytes.size() - d.data) {
+                set_error("vb2_baq_records: internal error: a record passes its chunk");
+                return VB2_ERR_INVALID;
+            }
+            if (nb + vb > batch_bytes) break;
+            std::memcpy(hd.data() + nb, ch.bytes.data() + d.data, vb);
+            hr[nr] = d;
+            hr[nr].data = (uint32_t)nb;
+            const uint8_t* bq = nullptr;
+            baq::Task t = baq::make_task(scan, ci, ri, spans, opt, &bq);
+            if (t.kind == 1 && bq) {
+                t.bq_off = (uint32_t)extra.size();
+                extra.insert(extra.end(), bq, bq + d.l_seq);
+            }
+            tasks.push_back(t);
+            nb += vb;
+            ++nr;
+            ++ri;
+            skip_empty();
+        }
+        VB2_HIP(hipMemcpyAsync(d_data.p, hd.data(), nb, hipMemcpyHostToDevice, s));
+        VB2_HIP(hipMemcpyAsync(d_desc.p, hr.data(), nr * sizeof(bamio::RecordDesc), hipMemcpyHostToDevice, s));
+        VB2_HIP(hipStreamSynchronize(s));
+        const size_t q0 = out->qual.size();
+        if (int rc = stage.run(tasks, extra, hr.data(), nr, d_desc.as<bamio::RecordDesc>(), d_data.as<uint8_t>(), nb, &out->cap4, &out->mapq,
+                               &out->outcome, &out->qual))
+            return rc;
+        size_t at = q0;
+        for (size_t r = 0; r < nr; ++r) {
+            at += (size_t)hr[r].l_seq;
+            out->qual_off.push_back(at);
+        }
+    }
+    out->stats = stage.stats;
+    return VB2_OK;
 }
 
 bool bam_support() { return true; }

@@ -30,7 +30,7 @@ struct PileEntry {
 static_assert(sizeof(PileEntry) == 32, "entries are 32 bytes");
 constexpr uint8_t kEntryReverse = 16, kEntryDeleted = 32, kEntryEligible = 64, kEntryMateAhead = 128;
 
-struct PileFilter {         // mplp_func's read filter (SimplePileupViewer.cpp:172-237) without BAQ and the mapQ cap
+struct PileFilter {         // mplp_func's read filter (SimplePileupViewer.cpp:172-237); BAQ and the mapQ cap reach it as adjusted values
     int32_t excl_flags, min_mq, no_orphans;
 };
 
@@ -47,15 +47,20 @@ struct PileCounters {       // device-side statistics, added to by the kernels
 };
 
 // Pass 1 of a batch: count[r] = markers record r covers (0 for a filtered record).  data: the batch's record bytes.
+// adj_qual / adj_mapq (both or neither; --ApplyBAQ): the qualities after BAQ, at the offsets `data`
+// has the records' own, and the mapQ after the cap per record, below zero for a dropped read.  Without them the kernels
+// are the instantiations they were.
 hipError_t launch_cover_count(const bamio::RecordDesc* desc, int64_t num_rec, const uint8_t* data, uint64_t data_bytes,
-                              PileFilter f, PileMarkers m, uint32_t* count, hipStream_t s);
+                              PileFilter f, PileMarkers m, uint32_t* count, hipStream_t s, const uint8_t* adj_qual = nullptr,
+                              const int16_t* adj_mapq = nullptr);
 // offset = exclusive scan of count [n], *total = its sum (a single workgroup walks the array)
 hipError_t launch_scan_u32(const uint32_t* count, uint32_t* offset, int64_t n, unsigned long long* total, hipStream_t s);
 // Pass 2: record r's entries go to entries[offset[r] ...], and their sort keys slot << 32 | order to keys[...].
 // group (may be null): the records' read groups, parallel to desc; null leaves every entry's group 0.
 hipError_t launch_cover_fill(const bamio::RecordDesc* desc, int64_t num_rec, const uint8_t* data, uint64_t data_bytes,
                              PileFilter f, PileMarkers m, const uint32_t* offset, PileEntry* entries, uint64_t* keys,
-                             hipStream_t s, const uint16_t* group = nullptr);
+                             hipStream_t s, const uint16_t* group = nullptr, const uint8_t* adj_qual = nullptr,
+                             const int16_t* adj_mapq = nullptr);
 
 // Sorts the keys with the entries' indices: keys_out ascending, idx_out the permutation (n < 2^31).  temp / temp_bytes as
 // hipcub wants them: call with temp == nullptr to learn temp_bytes.

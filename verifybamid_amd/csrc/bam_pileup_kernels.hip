@@ -40,19 +40,28 @@ __device__ inline uint64_t fnv1a(const uint8_t* p, int n)
     return h;
 }
 
-template <bool FILL>
+template <bool FILL, bool ADJ>
 __global__ __launch_bounds__(kBlock) void bam_cover_kernel(const bamio::RecordDesc* __restrict__ desc, int64_t num_rec,
                                                             const uint8_t* __restrict__ data, uint64_t data_bytes, PileFilter f,
                                                             PileMarkers m, uint32_t* __restrict__ count,
                                                             const uint32_t* __restrict__ offset, PileEntry* __restrict__ entries,
-                                                            uint64_t* __restrict__ keys, const uint16_t* __restrict__ group)
+                                                            uint64_t* __restrict__ keys, const uint16_t* __restrict__ group,
+                                                            const uint8_t* __restrict__ adj_qual, const int16_t* __restrict__ adj_mapq)
 {
     const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (r >= num_rec) return;
-    const bamio::RecordDesc d = desc[r];
+    bamio::RecordDesc d = desc[r];
     uint32_t n = 0;
+    // --ApplyBAQ: the mapQ after the cap, below zero for a read the stage dropped; the qualities
+    // after BAQ lie in adj_qual where `data` has the record's own
+    bool dropped = false;
+    if (ADJ) {
+        const int mq = adj_mapq[r];
+        dropped = mq < 0;
+        d.mapq = (uint8_t)(dropped ? 0 : mq);
+    }
     // mplp_func's order: unmapped, the exclusion flags, mapQ, orphans
-    bool pass = !(d.flag & 4) && d.tid >= 0 && d.tid < m.n_ref;
+    bool pass = !(d.flag & 4) && d.tid >= 0 && d.tid < m.n_ref && !dropped;
     pass = pass && !(d.flag & f.excl_flags);
     pass = pass && (int32_t)d.mapq >= f.min_mq;
     pass = pass && !(f.no_orphans && (d.flag & 1) && !(d.flag & 2));
@@ -75,6 +84,7 @@ __global__ __launch_bounds__(kBlock) void bam_cover_kernel(const bamio::RecordDe
         const uint8_t* cig = name + d.l_read_name;
         const uint8_t* seq = cig + 4ull * d.n_cigar;
         const uint8_t* qual = seq + (l_seq + 1) / 2;
+        if (ADJ) qual = adj_qual + (qual - data);
         uint64_t hash = 0;
         bool hashed = false;
         uint32_t out = 0;
@@ -358,21 +368,30 @@ inline unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1)
 }  // namespace
 
 hipError_t launch_cover_count(const bamio::RecordDesc* desc, int64_t num_rec, const uint8_t* data, uint64_t data_bytes,
-                              PileFilter f, PileMarkers m, uint32_t* count, hipStream_t s)
+                              PileFilter f, PileMarkers m, uint32_t* count, hipStream_t s, const uint8_t* adj_qual,
+                              const int16_t* adj_mapq)
 {
     if (num_rec <= 0) return hipSuccess;
-    bam_cover_kernel<false><<<blocks_for(num_rec, kBlock), kBlock, 0, s>>>(desc, num_rec, data, data_bytes, f, m, count, nullptr,
-                                                                            nullptr, nullptr, nullptr);
+    if (adj_qual && adj_mapq)
+        bam_cover_kernel<false, true><<<blocks_for(num_rec, kBlock), kBlock, 0, s>>>(desc, num_rec, data, data_bytes, f, m, count, nullptr,
+                                                                                      nullptr, nullptr, nullptr, adj_qual, adj_mapq);
+    else
+        bam_cover_kernel<false, false><<<blocks_for(num_rec, kBlock), kBlock, 0, s>>>(desc, num_rec, data, data_bytes, f, m, count, nullptr,
+                                                                                       nullptr, nullptr, nullptr, nullptr, nullptr);
     return hipGetLastError();
 }
 
 hipError_t launch_cover_fill(const bamio::RecordDesc* desc, int64_t num_rec, const uint8_t* data, uint64_t data_bytes,
                              PileFilter f, PileMarkers m, const uint32_t* offset, PileEntry* entries, uint64_t* keys,
-                             hipStream_t s, const uint16_t* group)
+                             hipStream_t s, const uint16_t* group, const uint8_t* adj_qual, const int16_t* adj_mapq)
 {
     if (num_rec <= 0) return hipSuccess;
-    bam_cover_kernel<true><<<blocks_for(num_rec, kBlock), kBlock, 0, s>>>(desc, num_rec, data, data_bytes, f, m, nullptr, offset,
-                                                                           entries, keys, group);
+    if (adj_qual && adj_mapq)
+        bam_cover_kernel<true, true><<<blocks_for(num_rec, kBlock), kBlock, 0, s>>>(desc, num_rec, data, data_bytes, f, m, nullptr, offset,
+                                                                                     entries, keys, group, adj_qual, adj_mapq);
+    else
+        bam_cover_kernel<true, false><<<blocks_for(num_rec, kBlock), kBlock, 0, s>>>(desc, num_rec, data, data_bytes, f, m, nullptr, offset,
+                                                                                      entries, keys, group, nullptr, nullptr);
     return hipGetLastError();
 }
 

@@ -11,9 +11,13 @@
 // --Epsilon e is the simplex's relative tolerance; a value that is not positive (0, negative, NaN) means the default 1e-8.
 // --BamFile B reads a coordinate-sorted BAM with its .bai through the built-in reader (no htslib):
 // BGZF, index and records on the host (--NumThread above its default of 4 sizes that pool), the per-marker pileup on the
-// GPU.  BAQ and the mapQ cap need htslib and the FASTA and are not applied -- a NOTICE says so when the options ask for
-// them, and names the reference command that matches what was computed (--incl-flags 1024 --adjust-MQ 0); the reference
-// base of a site is the panel's REF allele, so --Reference stays required and unread.  CRAM and .csi are not read.
+// GPU.  Without --ApplyBAQ, BAQ and the mapQ cap are not applied -- a NOTICE says so when the options ask for them, and
+// names the reference command that matches what was computed (--incl-flags 1024 --adjust-MQ 0) -- and --Reference stays
+// required and unread.  --ApplyBAQ (with --BamFile, or a --PileupList that has a .bam line) applies to every record what
+// the effective pileup options ask of the FASTA at --Reference (plain, with its .fai), in the reference's order: the
+// Illumina-1.3 shift, base alignment quality, the mapping-quality cap; one NOTICE says what was
+// applied and from which file.  The reference base of a site is the panel's REF allele either way.  CRAM and .csi are
+// not read.
 // --RefVCF V [--NumSVDPCs k] [--SkipMinSampleCountCheck] [--IncludeChr a,b,..] [--GramSVD] builds a reference panel
 // (main.cpp:233-257): V.UD, V.mu, V.bed, V.V, decomposed on the GPU (vb2_panel_build), and returns before --Reference
 // is looked at.  --NumThread sizes the VCF parser pool there.
@@ -116,6 +120,7 @@ int main(int argc, char** argv)
     double normalHomMin = 0.99;
     bool pairInterval = false;
     bool perReadGroup = false;
+    bool applyBAQ = false;
     bool refBias = false;
     // "Pileup Options" (main.cpp:176-187), defaults main.cpp:81-96 (MPLP_REALN | MPLP_SMART_OVERLAPS; UNMAP | SECONDARY |
     // QCFAIL | DUP): they shape what --BamFile input becomes and, as in the reference, do nothing to --PileupFile input
@@ -199,6 +204,8 @@ int main(int argc, char** argv)
         // not in the reference (VerifyBamID 1 had it): FREEMIX of every read group of the --BamFile header beside the whole
         // sample's, each from the group's own pileup, the groups searched in lock-step (vb2_run_read_groups), to <Output>.selfRG
         {"PerReadGroup", {Flag::kBool, &perReadGroup, false}},
+        // the built-in BAM reader applies base alignment quality and the mapping-quality cap from --Reference (vb2_run_args.bam_adjust)
+        {"ApplyBAQ", {Flag::kBool, &applyBAQ, false}},
         // not in the reference (VerifyBamID 1 had --free-refBias): the reference bias of the read model estimated jointly with
         // FREEMIX by profile likelihood, 28 refits of the one resident sample in lock-step (vb2_run_refbias), to <Output>.RefBias
         {"RefBias", {Flag::kBool, &refBias, false}},
@@ -441,8 +448,21 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "NOTICE - pileup options (--min-BQ, --min-MQ, ...) apply to --BamFile input only; "
                              "the text pileup is taken as it is (as in the reference)\n");
     // (once per run, also for the .bam lines of a --PileupList, however many there are)
-    if ((BamFile != "Empty" && PileupFile == "Empty") || listHasBam) {
-        // what the built-in reader leaves out of the reference's pileup (both need htslib's HMM and the FASTA)
+    if (applyBAQ && !((BamFile != "Empty" && PileupFile == "Empty") || listHasBam))
+        fatal("--ApplyBAQ needs --BamFile, or a --PileupList with a .bam line: a text pileup carries no alignments to realign");
+    args.bam_adjust = applyBAQ ? 1 : 0;
+    if (applyBAQ) {
+        const int effFlags = args.mpileup.given ? inclFlags : (16 | 1024), effCap = args.mpileup.given ? adjustMQ : 40;
+        std::string what;
+        if (effFlags & 128) what += "the Illumina-1.3 quality shift";
+        if (effFlags & 16) what += std::string(what.empty() ? "" : ", ") + "base alignment quality" + ((effFlags & 64) ? " (recomputed: BQ tags ignored)" : "");
+        if (effCap > 10) what += std::string(what.empty() ? "" : ", ") + "the mapping quality cap (--adjust-MQ " + std::to_string(effCap) + ")";
+        if (what.empty()) what = "nothing (the pileup options ask for neither BAQ nor the cap; the FASTA is not opened)";
+        std::fprintf(stderr, "NOTICE - --ApplyBAQ: applied to BAM input from %s: %s; the reference base of a site stays the panel's "
+                             "REF allele (.bed)\n", RefPath.c_str(), what.c_str());
+        if (nthread > 4 && !listHasBam) vb2_debug_set_tunable("bam_threads", nthread);
+    } else if ((BamFile != "Empty" && PileupFile == "Empty") || listHasBam) {
+        // what the built-in reader leaves out of the reference's pileup without --ApplyBAQ
         const int effFlags = args.mpileup.given ? inclFlags : (16 | 1024), effCap = args.mpileup.given ? adjustMQ : 40;
         if (effFlags & 16)
             std::fprintf(stderr, "NOTICE - --BamFile: base alignment quality (BAQ, --incl-flags bit 16) is not applied by the built-in "

@@ -402,6 +402,9 @@ private:
             how.threads = vb2::cohort_bam_pool(T_);
             // the device stage on one of the device's two creation streams, never on a lane's hardware queue (see run())
             if (!own_streams_.empty()) how.stream = own_streams_[(size_t)device_of_sample(s) * 4 + 2 + (size_t)(s / ndev_) % 2];
+            how.bam_adjust = a_->base.bam_adjust;      // --ApplyBAQ reaches a cohort's .bam lines as the pileup options do
+            vb2_baq_stats baq_stats{};
+            how.baq_stats = &baq_stats;
             sl.rc = vb2::read_bam(path, a_->base.reference_path ? a_->base.reference_path : "", *panel_, &f.viewer, &a_->base.mpileup,
                                   devices_[device_of_sample(s)], &f.bam_stats, &how);
             f.from_bam = sl.rc == VB2_OK;

@@ -97,13 +97,18 @@ int read_known_af(const std::string& path, Panel* p);
 int read_pileup(const std::string& path, const Panel& panel, PileupViewer* v);
 // BAM input (bam_flatten.cpp): the built-in reader -- BGZF, header, .bai and records on the host (bam_io.cpp), the pileup
 // on `device` (bam_pileup_kernels.hip) --, or htslib's where the library was configured with
-// VB2_WITH_HTSLIB.  SimplePileupViewer.cpp:172-557 with main.cpp:81-96's defaults, less BAQ and the mapQ cap.
+// VB2_WITH_HTSLIB.  SimplePileupViewer.cpp:172-557 with main.cpp:81-96's defaults; BAQ and the mapQ cap under
+// BamReadHow::bam_adjust alone.
 // mp: the reference's "Pileup Options" (main.cpp:176-187), nullptr or given == 0 = its defaults (main.cpp:81-96);
 // stats (may be null): what vb2_flat_bam_stats reports.  The file and its index are opened before any device is touched.
 // how: what a caller that runs many loads at once decides for one of them (null: the tunables and a stream of its own)
 struct BamReadHow {
     int threads = 0;          // host pool that inflates and walks: 0 = tunable bam_threads
     void* stream = nullptr;   // hipStream_t of the device stage (and of the device inflate): null = one made for the load
+    // --ApplyBAQ (vb2_run_args.bam_adjust = 1): the built-in reader applies the shift, BAQ and the cap
+    // the options ask for from the FASTA at ref_path; baq_stats (may be null) gets what vb2_flat_baq_stats reports
+    int bam_adjust = 0;
+    vb2_baq_stats* baq_stats = nullptr;
 };
 int read_bam(const std::string& bam_path, const std::string& ref_path, const Panel& panel, PileupViewer* v,
              const vb2_mpileup_opts* mp = nullptr, int device = -1, vb2_bam_stats* stats = nullptr, const BamReadHow* how = nullptr);
@@ -127,8 +132,19 @@ inline int cohort_bam_pool(int readers) { return readers >= 16 ? 1 : (readers < 
 // groups->info and groups->flat are filled, one vb2_flat per @RG line over `panel` with its viewer's sites added; the whole sample's viewer and stats are what
 // read_bam gives.  VB2_ERR_INVALID for a header whose groups x panel slots pass 2^31 - 2, before any device is touched.
 int read_bam_groups(const std::string& bam_path, const std::shared_ptr<Panel>& panel, PileupViewer* v, const vb2_mpileup_opts* mp,
-                    int device, vb2_bam_stats* stats, vb2_flat_groups* groups);
+                    int device, vb2_bam_stats* stats, vb2_flat_groups* groups, const std::string& ref_path = std::string(),
+                    const BamReadHow* how = nullptr);
 bool bam_support();
+// vb2_baq_records: what --ApplyBAQ makes of the records the scan sends up (where 0: the host driver, 1: the device stage)
+struct BaqRecords {
+    std::vector<uint64_t> qual_off;
+    std::vector<uint8_t> qual, outcome;
+    std::vector<int16_t> mapq;
+    std::vector<int32_t> cap4;
+    vb2_baq_stats stats{};
+};
+int baq_records_file(const std::string& bam_path, const std::string& bed_path, const std::string& ref_path, const vb2_mpileup_opts* mp,
+                     int where, int device, BaqRecords* out);
 // the host stage alone over the markers of a .bed (vb2_bam_scan): the fetched records' virtual offsets, ascending;
 // group_ids / groups (both or neither): the header's @RG IDs and the records' group numbers (vb2_bam_scan_ex)
 int bam_scan_file(const std::string& bam_path, const std::string& bed_path, std::vector<uint64_t>* voffsets, vb2_bam_stats* stats,
@@ -154,6 +170,8 @@ struct vb2_flat {
     bool sanity_disabled = true;
     bool from_bam = false;                    // bam_stats holds the load's counts and times
     vb2_bam_stats bam_stats{};
+    bool with_baq = false;                    // loaded with bam_adjust = 1: baq_stats holds the stage's
+    vb2_baq_stats baq_stats{};
     vb2_input input{};
     void resolve();          // BuildResolvedMarkers -> input
 };

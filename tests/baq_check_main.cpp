@@ -95,6 +95,7 @@ int main(int argc, char** argv)
         std::ifstream in(argv[7]);
         int n = 0, bad = 0;
         std::vector<double> scratch;
+        vb2_baq_stats tally{};
         for (size_t ci = 0; ci < scan.chunks.size(); ++ci) {
             const bamio::Chunk& ch = scan.chunks[ci];
             for (size_t ri = 0; ri < ch.recs.size(); ++ri) {
@@ -105,13 +106,8 @@ int main(int argc, char** argv)
                 std::vector<uint8_t> q((size_t)d.l_seq + 1);
                 int32_t c4[4];
                 baq::run_record(d, ch.bytes.data() + d.data, t, spans.codes.data(), bq, opt, q.data(), c4, &scratch);
-                int mq = d.mapq, oc = t.outcome;
-                if (oc == baq::kOutside) {
-                    mq = -1;
-                } else if (t.cap) {
-                    mq = baq::capped_mapq(mq, baq::cap_finish(c4, opt.cap));
-                    if (mq < 0) oc = baq::kCapDropped;
-                }
+                const baq::Finished end = baq::finish_record(d.mapq, t, c4, opt, &tally);
+                const int mq = end.mapq, oc = end.outcome;
                 int w_oc, w_mq, w4[4];
                 std::string hex;
                 if (!(in >> w_oc >> w_mq >> w4[0] >> w4[1] >> w4[2] >> w4[3] >> hex)) {
@@ -130,7 +126,7 @@ int main(int argc, char** argv)
             }
         }
         std::printf("records %d bad %d fasta_bytes %lld\n", n, bad, (long long)spans.bytes_read);
-        failures += bad + (n == 0);
+        failures += bad + (n == 0) + (tally.records != n);
     }
     for (int a = 8; a + 1 < argc; a += 2) {
         baq::Spans spans;

@@ -16,6 +16,7 @@ import verifybamid_amd as vb
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bam_ref as br  # noqa: E402
+from test_bam_batches_cpu import cut, var_bytes  # noqa: E402  (the restatement of the cutting rule)
 
 gpu = pytest.mark.gpu
 
@@ -171,7 +172,7 @@ def scenario(tmp_path_factory):
         for c, p, r, a in rows:
             fh.write("%s:%d_%s/%s 0.4\n" % (c, p, r, a))
     bam = str(d / "s.bam")
-    br.write_indexed_bam(bam, REFS, recs, block_payload=300)
+    vo, _, _ = br.write_indexed_bam(bam, REFS, recs, block_payload=300)
     cache = {}
 
     def want(**opts):
@@ -180,7 +181,7 @@ def scenario(tmp_path_factory):
             cache[key] = br.pileup_ref(recs, REFS, rows, opts)
         return cache[key]
 
-    return dict(recs=recs, rows=rows, at=at, pre=pre, bam=bam, want=want, dir=str(d))
+    return dict(recs=recs, rows=rows, at=at, pre=pre, bam=bam, want=want, dir=str(d), vo=vo)
 
 
 def _same(got, want, rows):
@@ -268,6 +269,81 @@ def test_small_batches_give_the_same_bytes(scenario, tunable):
     assert many["bases"] == one["bases"] and many["quals"] == one["quals"] and list(many["read_off"]) == list(one["read_off"])
     assert many["stats"]["entries"] == one["stats"]["entries"] and many["stats"]["pairs_resolved"] == one["stats"]["pairs_resolved"]
     _same(many, scenario["want"](), scenario["rows"])
+
+
+def _write_panel(pre, rows):
+    with open(pre + ".bed", "w") as fh:
+        for c, p, r, a in rows:
+            fh.write("%s\t%d\t%d\t%s\t%s\n" % (c, p - 1, p, r, a))
+    with open(pre + ".UD", "w") as fh:
+        for i in range(len(rows)):
+            fh.write("%g %g\n" % (0.01 * (i % 7 - 3), 0.02 * (i % 5 - 2)))
+    with open(pre + ".mu", "w") as fh:
+        for c, p, r, a in rows:
+            fh.write("%s:%d_%s/%s 0.4\n" % (c, p, r, a))
+
+
+def _cut_of(bam, bed, recs, vo, kb):
+    """(batch_bytes, batch_rec, batches) of the cutting rule over the records the host stage keeps, in its order, with
+    the sizes of their variable parts taken from the record list"""
+    rec_at = dict(zip(vo, recs))
+    kept = [rec_at[int(v)] for v in vb.api.bam_scan(bam, bed)["voffsets"]]
+    return cut(kb, [var_bytes(len(r["name"]) + 1, len(r["cigar"]), len(r["seq"])) for r in kept])
+
+
+@gpu
+def test_batches_are_the_cutting_rules(scenario, tunable, tmp_path):
+    """stats["batches"] at 8 KiB on the scenario, and at 1 KiB on a dozen reads one of which is longer than 1 KiB: it
+    raises the batch to its own size"""
+    tunable("bam_batch_kb", 8)
+    _, _, want = _cut_of(scenario["bam"], scenario["pre"] + ".bed", scenario["recs"], scenario["vo"], 8)
+    got = vb.api.load_bam(scenario["pre"], scenario["bam"])
+    print("8 KiB:", [(len(b), sum(b)) for b in want], got["stats"])
+    assert len(want) >= 3 and got["stats"]["batches"] == len(want)
+    recs = [br.rec("r%d" % i, 0, 100 + 10 * i, "50M", _seq(50, i), _q(50)) for i in range(11)]
+    recs.append(br.rec("long", 0, 150, "1500M", _seq(1500, 1), _q(1500)))
+    recs.sort(key=lambda r: (r["tid"], r["pos"]))
+    rows = [("chr1", p, "A", "C") for p in (130, 160, 190, 220, 1000)]
+    pre, bam = str(tmp_path / "dozen"), str(tmp_path / "dozen.bam")
+    _write_panel(pre, rows)
+    vo, _, _ = br.write_indexed_bam(bam, REFS, recs, block_payload=300)
+    tunable("bam_batch_kb", 1)
+    batch_bytes, _, want = _cut_of(bam, pre + ".bed", recs, vo, 1)
+    got = vb.api.load_bam(pre, bam)
+    print("1 KiB:", batch_bytes, [(len(b), sum(b)) for b in want], got["stats"])
+    assert batch_bytes == var_bytes(5, 1, 1500) > 1024 and sum(len(b) for b in want) == 12 == got["stats"]["records_kept"]
+    assert len(want) >= 3 and got["stats"]["batches"] == len(want)
+    _same(got, br.pileup_ref(recs, REFS, rows, {}), rows)
+
+
+@gpu
+def test_records_that_all_miss_the_panel_leave_nothing(scenario, tmp_path):
+    """a dozen reads on chr1, one marker on chr3: no record is kept, no batch is cut, no entry and no site come back"""
+    recs = [r for r in scenario["recs"] if r["tid"] == 0][:12]
+    rows = [("chr3", 1000, "A", "C")]
+    pre, bam = str(tmp_path / "miss"), str(tmp_path / "miss.bam")
+    _write_panel(pre, rows)
+    br.write_indexed_bam(bam, REFS, recs, block_payload=300)
+    got = vb.api.load_bam(pre, bam)
+    print(got["stats"])
+    st = got["stats"]
+    assert (st["records_kept"], st["batches"], st["entries"], st["sites"], st["empty_sites"]) == (0, 0, 0, 0, 0)
+    assert (got["num_site"], got["num_bases"], got["avg_depth"]) == (0, 0, 0.0)
+    assert got["bases"] == b"" and got["quals"] == b"" and list(got["read_off"]) == [0, 0]
+    _same(got, br.pileup_ref(recs, REFS, rows, {}), rows)
+
+
+@gpu
+def test_batches_of_four_gib_are_refused(scenario, tunable):
+    """bam_batch_kb one KiB above 0xfff00000 bytes: refused with its text and code before any staging buffer is asked for
+    (the tunable's setter lets the value through); the next load is an ordinary one"""
+    tunable("bam_batch_kb", 0xfff00000 // 1024 + 1)
+    with pytest.raises(vb._abi.Vb2Error) as e:
+        vb.api.load_bam(scenario["pre"], scenario["bam"])
+    assert e.value.code == vb._abi.VB2_ERR_INVALID
+    assert str(e.value).endswith("--BamFile: bam_batch_kb asks for batches of 4 GiB or more")
+    tunable("bam_batch_kb", 65536)
+    assert vb.api.load_bam(scenario["pre"], scenario["bam"])["stats"]["batches"] == 1
 
 
 @gpu

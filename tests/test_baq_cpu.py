@@ -211,6 +211,20 @@ def test_the_switch_took_the_reserved_field_and_nothing_moved(scenario):
     assert e.value.code == _abi.VB2_ERR_INVALID
 
 
+@pytest.mark.parametrize("value", [-1, 2])
+def test_refusals_that_need_neither_file_nor_device(scenario, value):
+    """where and bam_adjust outside {0, 1}: text and code, before the BAM is opened (it does not exist).  vb2_flat_load
+    refuses bam_adjust itself, so the reader's own "--BamFile: bam_adjust is ..." lies behind it and is never seen here."""
+    with pytest.raises(_abi.Vb2Error) as e:
+        vb.api.baq_records("no_such.bam", "no_such.bed", "no_such.fa", where=value)
+    assert e.value.code == _abi.VB2_ERR_INVALID
+    assert str(e.value).endswith("vb2_baq_records: where is 0 (host driver) or 1 (device stage)")
+    with pytest.raises(_abi.Vb2Error) as e:
+        vb.api.load_bam(scenario["pre"], "no_such.bam", apply_baq=value, reference_path="no_such.fa")
+    assert e.value.code == _abi.VB2_ERR_INVALID
+    assert str(e.value).endswith("vb2_flat_load: bam_adjust is %d; it is 0 (BAM records as they are) or 1 (--ApplyBAQ)" % value)
+
+
 def test_command_line_refusals(scenario, tmp_path):
     base = [EXE, "--SVDPrefix", scenario["pre"], "--Reference", scenario["fasta"], "--ApplyBAQ"]
     r = subprocess.run(base + ["--PileupFile", str(tmp_path / "x.pileup")], capture_output=True, text=True, timeout=60)

@@ -98,6 +98,56 @@ def test_three_records_share_a_wave_with_an_empty_slot(tmp_path):
     _records_equal(dev, host)
 
 
+@gpu
+def test_records_and_load_report_equal_stats(scenario, tunable):
+    """vb2_baq_records(where = 1) and a --ApplyBAQ load cut the same batches and finish their records alike"""
+    tunable("baq_lds_kb", sc.LDS_KB)
+    tunable("bam_batch_kb", BATCH_KB)
+    dev = vb.api.baq_records(scenario["bam"], scenario["pre"] + ".bed", scenario["fasta"], where=1)
+    got = vb.api.load_bam(scenario["pre"], scenario["bam"], apply_baq=True, reference_path=scenario["fasta"])
+    print(dev["stats"], got["baq"])
+    for k in ("records", "realigned", "left_alone", "tag_applied", "no_reference", "dropped_outside", "dropped_cap", "not_asked",
+              "undefined_rows", "records_lds", "records_global", "fasta_bytes"):
+        assert dev["stats"][k] == got["baq"][k], k
+    assert got["baq"]["records"] == len(scenario["recs"])
+
+
+@gpu
+def test_batches_of_four_gib_are_refused(scenario, tunable):
+    tunable("bam_batch_kb", 0xfff00000 // 1024 + 1)
+    with pytest.raises(vb._abi.Vb2Error) as e:
+        vb.api.baq_records(scenario["bam"], scenario["pre"] + ".bed", scenario["fasta"], where=1)
+    assert e.value.code == vb._abi.VB2_ERR_INVALID
+    assert str(e.value).endswith("vb2_baq_records: bam_batch_kb asks for batches of 4 GiB or more")
+    with pytest.raises(vb._abi.Vb2Error) as e:
+        vb.api.load_bam(scenario["pre"], scenario["bam"], apply_baq=True, reference_path=scenario["fasta"])
+    assert e.value.code == vb._abi.VB2_ERR_INVALID
+    assert str(e.value).endswith("--BamFile: bam_batch_kb asks for batches of 4 GiB or more")
+
+
+@gpu
+def test_records_that_all_miss_the_panel_leave_nothing(scenario, tmp_path):
+    """reads on chr1 only, one marker on chr2: the stage sees no record; the FASTA's index is still opened (an absent
+    FASTA is the load's error as with records), and none of its bases are read"""
+    recs = [r for r in scenario["recs"] if r["tid"] == 0][:12]
+    assert len(recs) == 12
+    pre, bam = str(tmp_path / "miss"), str(tmp_path / "miss.bam")
+    sc.write_panel(pre, [("chr2", 1000, "A", "C")])
+    br.write_indexed_bam(bam, sc.REFS, recs, block_payload=300)
+    got = vb.api.load_bam(pre, bam, apply_baq=True, reference_path=scenario["fasta"])
+    print(got["stats"], got["baq"])
+    st = got["stats"]
+    assert (st["records_kept"], st["batches"], st["entries"], st["sites"]) == (0, 0, 0, 0)
+    assert (got["num_site"], got["num_bases"], got["avg_depth"]) == (0, 0, 0.0)
+    assert got["baq"]["records"] == 0 and got["baq"]["fasta_bytes"] == 0
+    assert got["baq"]["records_lds"] == 0 == got["baq"]["records_global"]
+    with pytest.raises(vb._abi.Vb2Error) as e:
+        vb.api.load_bam(pre, bam, apply_baq=True, reference_path=scenario["dir"] + "/absent.fa")
+    assert e.value.code == vb._abi.VB2_ERR_IO
+    dev = vb.api.baq_records(bam, pre + ".bed", scenario["fasta"], where=1)
+    assert len(dev["mapq"]) == 0 and list(dev["qual_off"]) == [0] and dev["stats"]["records"] == 0
+
+
 def _same(got, want, rows):
     off = got["read_off"]
     assert len(off) == len(rows) + 1

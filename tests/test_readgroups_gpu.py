@@ -243,6 +243,29 @@ def test_every_groups_pileup_is_the_restatements_and_the_whole_sample_is_unchang
     assert sum(g["num_bases"] for g in got["groups"]) + unassigned == got["num_bases"]
 
 
+@gpu
+def test_records_that_all_miss_the_panel_leave_every_group_empty(scenario, tmp_path):
+    """reads on chr1 only, one marker on chr2: no record is kept; every group of the header is there, named and empty"""
+    recs = [r for r in scenario["recs"] if r["tid"] == 0][:12]
+    assert len(recs) == 12
+    pre, bam = str(tmp_path / "miss"), str(tmp_path / "miss.bam")
+    with open(pre + ".bed", "w") as fh:
+        fh.write("chr2\t999\t1000\tA\tC\n")
+    open(pre + ".UD", "w").write("0.01 0.02\n")
+    open(pre + ".mu", "w").write("chr2:1000_A/C 0.4\n")
+    br.write_indexed_bam(bam, REFS, recs, block_payload=300, text=rr.rg_header(REFS, IDS))
+    got = vb.api.load_bam_groups(pre, bam)
+    print(got["stats"], [(g["id"], g["records"], g["status"]) for g in got["groups"]])
+    st = got["stats"]
+    assert (st["records_kept"], st["batches"], st["entries"], st["sites"]) == (0, 0, 0, 0)
+    assert (got["num_site"], got["num_bases"], got["avg_depth"], got["unassigned"]) == (0, 0, 0.0, 0)
+    assert [g["id"] for g in got["groups"]] == IDS
+    for g in got["groups"]:
+        assert (g["records"], g["num_site"], g["num_bases"], g["avg_depth"]) == (0, 0, 0, 0.0)
+        assert g["bases"] == b"" and g["quals"] == b"" and list(g["read_off"]) == [0, 0]
+        assert g["status"] == _abi.VB2_GROUP_NO_BASE
+
+
 # ------------------------------------------------------------------ end to end: three groups with different contamination
 
 ALPHAS = (0.01, 0.05, 0.12)

@@ -22,6 +22,7 @@
 #include "context.h"
 #include "estimator.h"
 #include "guard.h"
+#include "host_clock.h"
 #include "line_search.h"
 #include "lockstep.h"
 #include "hostio.h"
@@ -32,6 +33,7 @@
 #include "baq_host.h"
 #include "fasta_io.h"
 
+using vb2::now_s;
 using vb2::set_error;
 
 namespace {
@@ -104,15 +106,6 @@ int load_panel(const vb2_run_args* a, vb2::Panel* panel)
     return VB2_OK;
 }
 }  // namespace vb2
-
-namespace {
-
-double now_s()
-{
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-}  // namespace
 
 extern "C" {
 

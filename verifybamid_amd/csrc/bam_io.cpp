@@ -6,6 +6,7 @@
 // CIGAR, packed bases and qualities; the index has, per reference sequence, the chunks of every bin and the linear index
 // of 16 kb windows.
 #include "bam_io.h"
+#include "host_clock.h"
 
 #include <fcntl.h>
 #include <sys/stat.h>
@@ -14,7 +15,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -26,11 +26,6 @@ namespace {
 
 constexpr uint32_t kMaxRecord = 64u << 20;       // a record larger than this is taken for a corrupt block_size
 constexpr int kBinPseudo = 37450;
-
-double now_s()
-{
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 struct Fail {
     int code;

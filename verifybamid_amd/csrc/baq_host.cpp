@@ -1,8 +1,8 @@
 // baq_host.cpp -- see baq_host.h.  Built with -ffp-contract=off like every unit that includes baq_core.h.
 #include "baq_host.h"
+#include "host_clock.h"
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <mutex>
@@ -17,8 +17,6 @@ struct NoSync {
 };
 
 inline uint32_t le32(const uint8_t* p) { return rd32u(p); }
-
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // what one record needs of its sequence: the HMM's window and the cap's walk
 struct Need {
@@ -269,6 +267,28 @@ int cap_finish(const int32_t cap4[4], int thres)
     if (t < 0) t = 0;
     t = std::sqrt((thres - t) / thres) * thres;
     return (int)(t + .499);
+}
+
+Finished finish_record(int mapq, const Task& t, const int32_t cap4[4], const Options& opt, vb2_baq_stats* st)
+{
+    Finished f{mapq, t.outcome};
+    if (f.outcome == kOutside) {
+        f.mapq = -1;
+    } else if (t.cap) {
+        f.mapq = capped_mapq(mapq, cap_finish(cap4, opt.cap));
+        if (f.mapq < 0) f.outcome = kCapDropped;
+    }
+    ++st->records;
+    switch (f.outcome) {
+    case kRealigned: ++st->realigned; break;
+    case kAlone: ++st->left_alone; break;
+    case kTagApplied: ++st->tag_applied; break;
+    case kNoReference: ++st->no_reference; break;
+    case kOutside: ++st->dropped_outside; break;
+    case kCapDropped: ++st->dropped_cap; break;
+    default: ++st->not_asked; break;
+    }
+    return f;
 }
 
 int run_record(const bamio::RecordDesc& d, const uint8_t* rec, const Task& t, const uint8_t* span_codes, const uint8_t* extra,

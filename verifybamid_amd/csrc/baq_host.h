@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/vb2_abi.h"      // vb2_baq_stats (plain C)
 #include "bam_io.h"
 #include "baq_core.h"
 #include "fasta_io.h"
@@ -78,6 +79,13 @@ Task make_task(const bamio::Scan& scan, size_t ci, size_t ri, const Spans& spans
 int cap_finish(const int32_t cap4[4], int thres);
 // mplp_func's use of it: the record's mapQ afterwards, -1 = dropped
 inline int capped_mapq(int mapq, int cap) { return cap < 0 ? -1 : (mapq > cap ? cap : mapq); }
+// A record's end once its cap4 is known: the mapQ the pileup sees (-1 = dropped: outside the sequence, or by the cap) and
+// the final outcome, which is counted into *st (records and the outcome's own counter).
+struct Finished {
+    int mapq;
+    uint8_t outcome;
+};
+Finished finish_record(int mapq, const Task& t, const int32_t cap4[4], const Options& opt, vb2_baq_stats* st);
 
 // One record on the host, sequentially: out_qual (l_seq bytes) and cap4; returns the undefined rows.  rec: the record's
 // variable part (name, CIGAR, bases, qualities); span: the spans' codes; extra: the bytes Task::bq_off points into.
@@ -89,6 +97,24 @@ int run_case(const uint8_t* ref, int l_ref, const uint8_t* query, const uint8_t*
              uint8_t* q);
 
 }  // namespace baq
+
+// vb2_baq_records: what --ApplyBAQ makes of the records the scan sends up (where 0: the host driver, 1: the device stage)
+struct BaqRecords {
+    std::vector<uint64_t> qual_off{0};       // record r's adjusted qualities are qual[qual_off[r], qual_off[r + 1])
+    std::vector<uint8_t> qual, outcome;
+    std::vector<int16_t> mapq;
+    std::vector<int32_t> cap4;
+    vb2_baq_stats stats{};
+    void append(const uint8_t* q, int32_t l_seq, const baq::Finished& end, const int32_t c4[4])
+    {
+        qual.insert(qual.end(), q, q + l_seq);
+        qual_off.push_back(qual.size());
+        mapq.push_back((int16_t)end.mapq);
+        outcome.push_back(end.outcome);
+        cap4.insert(cap4.end(), c4, c4 + 4);
+    }
+};
+
 }  // namespace vb2
 
 #endif

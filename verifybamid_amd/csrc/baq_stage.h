@@ -11,38 +11,44 @@
 #include <vector>
 
 #include "../../include/vb2_abi.h"
-#include "bam_io.h"
+#include "bam_batches.h"
 #include "baq_host.h"
+#include "device_util.h"
 
 namespace vb2 {
 
 class BaqStage {
 public:
     BaqStage(const baq::Options& opt, hipStream_t s) : opt_(opt), s_(s) {}
-    ~BaqStage();
     BaqStage(const BaqStage&) = delete;
     BaqStage& operator=(const BaqStage&) = delete;
     // the spans and the tables up; the buffers of a batch of at most max_rec records and max_bytes bytes
     int init(const baq::Spans& spans, size_t max_rec, size_t max_bytes);
-    // One batch.  tasks / extra: of its records, in order; h_desc: its descriptors (host), d_desc / d_data: on the device.
-    // Afterwards adjq() holds the adjusted qualities (at the offsets of d_data's) and adj_mapq() the mapQ per record, -1 =
-    // dropped.  cap4 / mapq / outcome / qual (each may be null) get the batch's values appended (qual: per record its
-    // l_seq adjusted qualities).
-    int run(const std::vector<baq::Task>& tasks, const std::vector<uint8_t>& extra, const bamio::RecordDesc* h_desc, size_t nr,
-            const bamio::RecordDesc* d_desc, const uint8_t* d_data, size_t nb, std::vector<int32_t>* cap4, std::vector<int16_t>* mapq,
-            std::vector<uint8_t>* outcome, std::vector<uint8_t>* qual);
-    const uint8_t* adjq() const { return static_cast<const uint8_t*>(d_adjq_); }
-    const int16_t* adj_mapq() const { return static_cast<const int16_t*>(d_mapq_); }
+    // One batch of the cutter, with its tasks; d_desc / d_data: its descriptors and bytes on the device.  Afterwards
+    // adjq() holds the adjusted qualities (at the offsets of d_data's) and adj_mapq() the mapQ per record, -1 = dropped.
+    // sink (may be null) gets every record's adjusted qualities, mapQ, outcome and cap4 appended.
+    int run(const RecordBatch& batch, const bamio::RecordDesc* d_desc, const uint8_t* d_data, BaqRecords* sink);
+    const uint8_t* adjq() const { return d_adjq_.as<uint8_t>(); }
+    const int16_t* adj_mapq() const { return d_mapq_.as<int16_t>(); }
     vb2_baq_stats stats{};
 
 private:
+    struct Tiers {
+        size_t n_lds, n_glob;
+        uint64_t stride, slice;        // bytes of workspace a global-tier record gets, and an LDS-tier one
+        uint32_t lds_bytes;
+        int grid_g;
+    };
+    int plan_tiers(const RecordBatch& batch, std::vector<uint32_t>* list, Tiers* t);
     baq::Options opt_;
     hipStream_t s_;
     size_t max_rec_ = 0, max_bytes_ = 0, extra_cap_ = 0, slab_cap_ = 0;
     uint64_t span_bytes_ = 0;
-    void *d_spans_ = nullptr, *d_tables_ = nullptr, *d_tasks_ = nullptr, *d_list_ = nullptr, *d_adjq_ = nullptr, *d_cap4_ = nullptr,
-         *d_undef_ = nullptr, *d_mapq_ = nullptr, *d_extra_ = nullptr, *d_slab_ = nullptr;
-    hipEvent_t ev_[4] = {nullptr, nullptr, nullptr, nullptr};
+    // (members go in reverse order of declaration: the buffers from d_spans_ to d_slab_, then the events from begin to spare)
+    struct Events {
+        OwnedEvent spare, end, mid, begin;
+    } ev_;
+    DeviceBuffer d_slab_, d_extra_, d_mapq_, d_undef_, d_cap4_, d_adjq_, d_list_, d_tasks_, d_tables_, d_spans_;
 };
 
 }  // namespace vb2

@@ -13,6 +13,7 @@
 
 #include "device_util.h"
 #include "estimator.h"
+#include "host_clock.h"
 #include "lockstep.h"
 #include "stream_search.h"
 #include "tunables.h"
@@ -652,11 +653,6 @@ int Batch::eval_end()
 // ---------------------------------------------------------------------------
 namespace {
 
-double wall_s()
-{
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 struct SearchLane;
 struct LaneTeam {                           // the lanes of one search and its first device-level error
     SearchLane* lanes = nullptr;
@@ -713,12 +709,12 @@ struct SearchLane {
             ++team->steps; team->active += act; team->points += pts;
             team->by_eighths[std::min(8, (8 * act + nslot - 1) / nslot)]++;
         }
-        const double tl = team->dbg ? wall_s() : 0.0;
+        const double tl = team->dbg ? now_s() : 0.0;
         if (const int rc = batch->eval_begin(npts.data(), pc1.data(), pc2.data(), alpha.data(), llk.data())) {
             fail(rc);
             return;
         }
-        if (team->dbg) team->s_launch += (t_launch = wall_s()) - tl;
+        if (team->dbg) team->s_launch += (t_launch = now_s()) - tl;
         flying = true;
     }
     // wait for the lane's step, hand the values out, run its fibers up to their next requests
@@ -726,11 +722,11 @@ struct SearchLane {
     {
         if (flying) {
             flying = false;
-            const double tw = team->dbg ? wall_s() : 0.0;
+            const double tw = team->dbg ? now_s() : 0.0;
             if (const int rc = batch->eval_end()) fail(rc);
             if (team->dbg) {
                 const int ns = std::min(64, (int)slot_fiber.size());
-                const double now = wall_s();
+                const double now = now_s();
                 team->s_wait += now - tw;
                 team->s_flight_by_slots[ns] += now - t_launch;
                 ++team->steps_by_slots[ns];
@@ -741,9 +737,9 @@ struct SearchLane {
                     if (npts[i] > 0) std::memcpy(req[slot_fiber[i]].out, &llk[i * kSlot], sizeof(double) * npts[i]);
             }
         }
-        const double tr = team->dbg ? wall_s() : 0.0;
+        const double tr = team->dbg ? now_s() : 0.0;
         if (gang->pending()) gang->resume_parked();           // (after an error: the fibers unwind)
-        if (team->dbg) team->s_resume += wall_s() - tr;
+        if (team->dbg) team->s_resume += now_s() - tr;
     }
 };
 
@@ -834,7 +830,7 @@ int Batch::optimize(const vb2_model* models, int num_model, vb2_estimate* out)
                 part.push_back(ctx_[base[l] + j]);
             }
         Batch* nb = nullptr;
-        const double tr0 = wall_s();
+        const double tr0 = now_s();
         int rc = Batch::create(part, &nb, regroup_bps(ctx_[0]->L.num_cu, (int)part.size()));
         if (!rc && nlane > 1 && lane_streams_[l]) nb->borrow_stream(lane_streams_[l]);
         if (!rc) rc = nb->ensure_resources();
@@ -843,7 +839,7 @@ int Batch::optimize(const vb2_model* models, int num_model, vb2_estimate* out)
             L.fail(rc);
             return;
         }
-        regroup_s += wall_s() - tr0;
+        regroup_s += now_s() - tr0;
         regrouped[l].reset(nb);                // (the batch it replaces has no step in flight: its slabs go back to the caches)
         L.batch = nb;
         L.slot_fiber.swap(keep);
@@ -872,12 +868,12 @@ int Batch::optimize(const vb2_model* models, int num_model, vb2_estimate* out)
             return VB2_ERR_INVALID;
         }
     }
-    const double t_loop0 = wall_s();
+    const double t_loop0 = now_s();
     regroup_lane(lanes[0]);
     lanes[0].launch();
     take_turns(team, regroup_lane, [](SearchLane&) {});
     if (team.dbg) {
-        std::fprintf(stderr, "lock-step loop %.2f ms, of which regrouping %.2f ms\n", 1e3 * (wall_s() - t_loop0), 1e3 * regroup_s);
+        std::fprintf(stderr, "lock-step loop %.2f ms, of which regrouping %.2f ms\n", 1e3 * (now_s() - t_loop0), 1e3 * regroup_s);
         for (int n = 1; n <= 64; ++n)
             if (team.steps_by_slots[n])
                 std::fprintf(stderr, "  batches of %d: %ld steps, %.1f us from launch to landing each\n", n, team.steps_by_slots[n],
@@ -954,11 +950,11 @@ int stream_search(int device, int num_pc, int num_cu, int capacity, StreamSource
     const bool dbg = team.dbg;
     long dbg_samples = 0;
     double dbg_blocked = 0, dbg_refill = 0, dbg_retire = 0;
-    const double dbg_t0 = wall_s();
+    const double dbg_t0 = now_s();
     auto retire = [&](SearchLane& L, int i) {
         Slots& sl = slots[&L - lanes];
         const int rc = team.error ? team.error : sl.rc[i];
-        src.done(sl.id[i], rc, sl.est[i], wall_s() - sl.t0[i]);
+        src.done(sl.id[i], rc, sl.est[i], now_s() - sl.t0[i]);
         sl.id[i] = -1;
         (void)sl.batch->set_slot(i, nullptr);
     };
@@ -969,16 +965,16 @@ int stream_search(int device, int num_pc, int num_cu, int capacity, StreamSource
         for (int i = 0; i < L.gang->size() && !ended; ++i) {
             if (sl.id[i] >= 0) continue;
             Context* c = nullptr;
-            const double tb = dbg ? wall_s() : 0.0;
+            const double tb = dbg ? now_s() : 0.0;
             const int id = src.next(block, &c);
-            if (dbg && block) dbg_blocked += wall_s() - tb;
+            if (dbg && block) dbg_blocked += now_s() - tb;
             block = false;
             if (id == StreamSource::kEnd) ended = true;
             if (id < 0) break;
             sl.id[i] = id;
             sl.rc[i] = 0;
             std::memset(&sl.est[i], 0, sizeof(vb2_estimate));
-            sl.t0[i] = wall_s();
+            sl.t0[i] = now_s();
             ++dbg_samples;
             // (Tunables::cohort_fail_sample: a test's way to send one sample down this error path)
             const int rc_slot = id == tunables().cohort_fail_sample ? (set_error("streaming batch: sample refused (test hook)"), VB2_ERR_INVALID)
@@ -999,16 +995,16 @@ int stream_search(int device, int num_pc, int num_cu, int capacity, StreamSource
                 retire(L, i);
                 --i;
             }
-            if (dbg) dbg_refill += wall_s() - sl.t0[i < 0 ? 0 : i];
+            if (dbg) dbg_refill += now_s() - sl.t0[i < 0 ? 0 : i];
         }
     };
     // the slots whose searches are over are reported and fall free
     auto retire_idle = [&](SearchLane& L) {
         const Slots& sl = slots[&L - lanes];
-        const double tr = dbg ? wall_s() : 0.0;
+        const double tr = dbg ? now_s() : 0.0;
         for (int i = 0; i < L.gang->size(); ++i)
             if (sl.id[i] >= 0 && L.gang->idle(i)) retire(L, i);
-        if (dbg) dbg_retire += wall_s() - tr;
+        if (dbg) dbg_retire += now_s() - tr;
     };
     for (;;) {
         take_turns(team, [&](SearchLane& L) { refill(L, false); }, retire_idle);
@@ -1022,7 +1018,7 @@ int stream_search(int device, int num_pc, int num_cu, int capacity, StreamSource
         std::fprintf(stderr, "stream search: %ld samples through %d slots in %.1f ms: %ld steps, %.1f active samples and %.1f points "
                              "per step (a lane holds %d); waited %.1f ms with nothing to do, %.1f ms taking samples in; the pipeline thread per step: "
                              "%.1f us waiting for a step to land, %.1f us in the samples' optimisers, %.1f us retiring, %.1f us launching\n",
-                     dbg_samples, capacity, 1e3 * (wall_s() - dbg_t0), team.steps, (double)team.active / per, (double)team.points / per, cnt[0],
+                     dbg_samples, capacity, 1e3 * (now_s() - dbg_t0), team.steps, (double)team.active / per, (double)team.points / per, cnt[0],
                      1e3 * dbg_blocked, 1e3 * dbg_refill, 1e6 * team.s_wait / per, 1e6 * team.s_resume / per, 1e6 * dbg_retire / per,
                      1e6 * team.s_launch / per);
     }

@@ -4,16 +4,14 @@
 #ifndef VB2_COHORT_STAGES_H_
 #define VB2_COHORT_STAGES_H_
 
-#include <chrono>
 #include <initializer_list>
 #include <vector>
 
 #include "context.h"
+#include "host_clock.h"
 #include "source.h"
 
 namespace vb2 {
-
-inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // What finish() works on.  The pipeline's threads are joined; `set` (null when no stage asked for planes) and the parked
 // contexts ([sample], null = not kept; empty when none was) are the pipeline's and outlive every stage's finish().

@@ -1,13 +1,15 @@
 // device_util.h -- what the host files around the per-marker kernels share (internal): the HIP error macro, device slabs
-// from the context's cache, and a pair of timing events.
+// from the context's cache, the owners of device buffers, pinned buffers, streams and events, and the host clock.
 #ifndef VB2_DEVICE_UTIL_H_
 #define VB2_DEVICE_UTIL_H_
 
 #include <hip/hip_runtime_api.h>
 
 #include <string>
+#include <vector>
 
 #include "context.h"
+#include "host_clock.h"
 
 // in a function that returns a VB2_* code: a failed call sets the error text and returns VB2_ERR_HIP
 #define VB2_HIP(call)                                                                  \
@@ -44,6 +46,45 @@ inline void give_device(void* p, size_t bytes, int device)
 {
     if (p && !recycle_device_slab(p, bytes, device)) (void)hipFree(p);
 }
+
+// device and pinned allocations, a stream, an event: owned by a scope or an object, released on every exit path
+struct DeviceBuffer {
+    void* p = nullptr;
+    DeviceBuffer() = default;
+    DeviceBuffer(const DeviceBuffer&) = delete;
+    DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+    ~DeviceBuffer() { if (p) (void)hipFree(p); }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+struct PinnedBuffer {
+    void* p = nullptr;
+    PinnedBuffer() = default;
+    PinnedBuffer(const PinnedBuffer&) = delete;
+    PinnedBuffer& operator=(const PinnedBuffer&) = delete;
+    ~PinnedBuffer() { if (p) (void)hipHostFree(p); }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+struct OwnedStream {
+    hipStream_t s = nullptr;
+    OwnedStream() = default;
+    OwnedStream(const OwnedStream&) = delete;
+    OwnedStream& operator=(const OwnedStream&) = delete;
+    ~OwnedStream() { if (s) (void)hipStreamDestroy(s); }
+};
+struct OwnedEvent {
+    hipEvent_t e = nullptr;
+    OwnedEvent() = default;
+    OwnedEvent(const OwnedEvent&) = delete;
+    OwnedEvent& operator=(const OwnedEvent&) = delete;
+    ~OwnedEvent() { if (e) (void)hipEventDestroy(e); }
+};
+struct DeviceBufferList {      // freed first to last
+    std::vector<void*> v;
+    DeviceBufferList() = default;
+    DeviceBufferList(const DeviceBufferList&) = delete;
+    DeviceBufferList& operator=(const DeviceBufferList&) = delete;
+    ~DeviceBufferList() { for (void* p : v) (void)hipFree(p); }
+};
 
 struct TimerEvents {
     hipEvent_t a = nullptr, b = nullptr;

@@ -136,13 +136,7 @@ int read_bam_groups(const std::string& bam_path, const std::shared_ptr<Panel>& p
                     const BamReadHow* how = nullptr);
 bool bam_support();
 // vb2_baq_records: what --ApplyBAQ makes of the records the scan sends up (where 0: the host driver, 1: the device stage)
-struct BaqRecords {
-    std::vector<uint64_t> qual_off;
-    std::vector<uint8_t> qual, outcome;
-    std::vector<int16_t> mapq;
-    std::vector<int32_t> cap4;
-    vb2_baq_stats stats{};
-};
+struct BaqRecords;      // baq_host.h
 int baq_records_file(const std::string& bam_path, const std::string& bed_path, const std::string& ref_path, const vb2_mpileup_opts* mp,
                      int where, int device, BaqRecords* out);
 // the host stage alone over the markers of a .bed (vb2_bam_scan): the fetched records' virtual offsets, ascending;

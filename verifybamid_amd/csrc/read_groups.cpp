@@ -3,18 +3,16 @@
 #include "read_groups.h"
 
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "context.h"   // set_error
+#include "host_clock.h"
 
 namespace vb2 {
 namespace {
-
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 struct CtxList {         // every exit path destroys what was created
     std::vector<vb2_ctx*> v;

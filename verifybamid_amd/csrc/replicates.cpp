@@ -7,7 +7,6 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -18,6 +17,7 @@
 
 #include "context.h"
 #include "guard.h"
+#include "host_clock.h"
 #include "hostio.h"
 #include "marker_sum_kernels.h"
 
@@ -132,8 +132,6 @@ void blocks_of_panel(const Panel& p, size_t rows, Blocks* b)
         }
     }
 }
-
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 inline uint64_t splitmix64(uint64_t& s)
 {

@@ -12,6 +12,7 @@
 
 #include "context.h"
 #include "hostio.h"
+#include "run.h"
 
 static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 

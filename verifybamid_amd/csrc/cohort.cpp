@@ -39,10 +39,12 @@
 #include "batch.h"
 #include "cohort_stages.h"
 #include "context.h"
+#include "device_util.h"
 #include "estimator.h"
 #include "guard.h"
 #include "hostio.h"
 #include "interval.h"
+#include "run.h"
 #include "stream_search.h"
 #include "tunables.h"
 
@@ -137,11 +139,7 @@ public:
         // HIP runtime start-up (per device) behind the panel reading
         std::vector<std::thread> warm;
         for (int d : devices_)
-            warm.emplace_back([d] {
-                if (d >= 0) (void)hipSetDevice(d);
-                (void)hipFree(nullptr);
-                (void)hipGetLastError();
-            });
+            warm.emplace_back(vb2::warm_device, d);
         panel_ = std::make_shared<vb2::Panel>();
         panel_->numPC = a_->base.num_pc;
         int rc = VB2_OK;

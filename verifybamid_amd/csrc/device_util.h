@@ -25,6 +25,15 @@ namespace vb2 {
 
 inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// The HIP runtime takes ~0.2 s to come up in a fresh process: the body of a helper thread that starts it on `device`
+// (< 0: the current one) while the caller reads files.  Errors surface later, where a context is created.
+inline void warm_device(int device)
+{
+    if (device >= 0) (void)hipSetDevice(device);
+    (void)hipFree(nullptr);
+    (void)hipGetLastError();
+}
+
 // A device slab from the cache, or a fresh one.  When hipMalloc fails: VB2_ERR_HIP with the call's text, or, where the
 // caller names itself in nomem_who, VB2_ERR_NOMEM with "<who>: N bytes of device memory do not fit".
 inline int take_device(size_t bytes, int device, void** p, size_t* got, const char* nomem_who = nullptr)

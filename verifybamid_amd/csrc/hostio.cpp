@@ -965,84 +965,78 @@ bool sanity_check(const Panel& p, PileupViewer* v)
     return v->effectiveNumSite > 1000 && v->effectiveNumSite > (p.NumMarker * 0.1);
 }
 
-// ContaminationEstimator.cpp:168-188 (default ostream formatting, 6 significant digits).
-int write_ancestry(const std::string& prefix, int numPC, const double* pc, const double* pc2)
+int write_text_file(const std::string& name, const std::function<void(std::ostream&)>& body)
 {
-    const std::string name(prefix + ".Ancestry");
     std::ofstream fout(name);
     if (!fout.is_open()) return io_error("Open file " + name + " failed!");
-    fout << "PC\tContaminatingSample\tIntendedSample" << std::endl;
-    for (int i = 0; i < numPC; ++i) fout << i + 1 << "\t" << pc[i] << "\t" << pc2[i] << std::endl;
+    body(fout);
     fout.close();
     if (!fout) return io_error("Errors detected when writing to file " + name + " !");
     return VB2_OK;
+}
+
+// ContaminationEstimator.cpp:168-188 (default ostream formatting, 6 significant digits).
+int write_ancestry(const std::string& prefix, int numPC, const double* pc, const double* pc2)
+{
+    return write_text_file(prefix + ".Ancestry", [&](std::ostream& fout) {
+        fout << "PC\tContaminatingSample\tIntendedSample" << std::endl;
+        for (int i = 0; i < numPC; ++i) fout << i + 1 << "\t" << pc[i] << "\t" << pc2[i] << std::endl;
+    });
 }
 
 // main.cpp:386-411.
 int write_selfsm(const std::string& prefix, const vb2_flat& f, const vb2_estimate& est,
                  bool pileup_input)
 {
-    const std::string name(prefix + ".selfSM");
-    std::ofstream fout(name);
-    if (!fout.is_open()) return io_error("Open file " + name + " failed!");
-    fout << "#SEQ_ID\tRG\tCHIP_ID\t#SNPS\t#READS\tAVG_DP\tFREEMIX\tFREELK1\tFREELK0\tFREE_RH\tFREE_RA\t"
-            "CHIPMIX\tCHIPLK1\tCHIPLK0\tCHIP_RH\tCHIP_RA\tDPREF\tRDPHET\tRDPALT"
-         << std::endl;
-    fout << f.viewer.SEQ_SM << "\tNA\tNA\t" << f.panel.NumMarker << "\t";
-    if (pileup_input) fout << "NA";
-    else fout << f.viewer.numBases;
-    fout << "\t" << f.viewer.avgDepth << "\t" << ((est.alpha < 0.5) ? est.alpha : (1.f - est.alpha))
-         << "\t" << -est.llk1 << "\t" << -est.llk0 << "\t"
-         << "NA\tNA\t" << "NA\tNA\tNA\tNA\tNA\t" << "NA\tNA\tNA" << std::endl;
-    fout.close();
-    if (!fout) return io_error("Errors detected when writing to file " + name + " !");
-    return VB2_OK;
+    return write_text_file(prefix + ".selfSM", [&](std::ostream& fout) {
+        fout << "#SEQ_ID\tRG\tCHIP_ID\t#SNPS\t#READS\tAVG_DP\tFREEMIX\tFREELK1\tFREELK0\tFREE_RH\tFREE_RA\t"
+                "CHIPMIX\tCHIPLK1\tCHIPLK0\tCHIP_RH\tCHIP_RA\tDPREF\tRDPHET\tRDPALT"
+             << std::endl;
+        fout << f.viewer.SEQ_SM << "\tNA\tNA\t" << f.panel.NumMarker << "\t";
+        if (pileup_input) fout << "NA";
+        else fout << f.viewer.numBases;
+        fout << "\t" << f.viewer.avgDepth << "\t" << ((est.alpha < 0.5) ? est.alpha : (1.f - est.alpha))
+             << "\t" << -est.llk1 << "\t" << -est.llk0 << "\t"
+             << "NA\tNA\t" << "NA\tNA\tNA\tNA\tNA\t" << "NA\tNA\tNA" << std::endl;
+    });
 }
 
 // <prefix>.selfRG (--PerReadGroup): .selfSM's header line and one row per read group in header order, formatted as
 // write_selfsm formats; #READS is the group's numBases; a group that was not searched has NA for FREEMIX and its two LLKs.
 int write_selfrg(const std::string& prefix, const vb2_flat_groups& groups, const vb2_estimate* est, const uint8_t* searched)
 {
-    const std::string name(prefix + ".selfRG");
-    std::ofstream fout(name);
-    if (!fout.is_open()) return io_error("Open file " + name + " failed!");
-    fout << "#SEQ_ID\tRG\tCHIP_ID\t#SNPS\t#READS\tAVG_DP\tFREEMIX\tFREELK1\tFREELK0\tFREE_RH\tFREE_RA\t"
-            "CHIPMIX\tCHIPLK1\tCHIPLK0\tCHIP_RH\tCHIP_RA\tDPREF\tRDPHET\tRDPALT"
-         << std::endl;
-    for (size_t g = 0; g < groups.flat.size(); ++g) {
-        const vb2_flat& f = *groups.flat[g];
-        fout << f.viewer.SEQ_SM << "\t" << groups.info[g].id << "\tNA\t" << f.panel.NumMarker << "\t" << f.viewer.numBases << "\t"
-             << f.viewer.avgDepth << "\t";
-        if (searched[g]) fout << ((est[g].alpha < 0.5) ? est[g].alpha : (1.f - est[g].alpha)) << "\t" << -est[g].llk1 << "\t" << -est[g].llk0;
-        else fout << "NA\tNA\tNA";
-        fout << "\t" << "NA\tNA\t" << "NA\tNA\tNA\tNA\tNA\t" << "NA\tNA\tNA" << std::endl;
-    }
-    fout.close();
-    if (!fout) return io_error("Errors detected when writing to file " + name + " !");
-    return VB2_OK;
+    return write_text_file(prefix + ".selfRG", [&](std::ostream& fout) {
+        fout << "#SEQ_ID\tRG\tCHIP_ID\t#SNPS\t#READS\tAVG_DP\tFREEMIX\tFREELK1\tFREELK0\tFREE_RH\tFREE_RA\t"
+                "CHIPMIX\tCHIPLK1\tCHIPLK0\tCHIP_RH\tCHIP_RA\tDPREF\tRDPHET\tRDPALT"
+             << std::endl;
+        for (size_t g = 0; g < groups.flat.size(); ++g) {
+            const vb2_flat& f = *groups.flat[g];
+            fout << f.viewer.SEQ_SM << "\t" << groups.info[g].id << "\tNA\t" << f.panel.NumMarker << "\t" << f.viewer.numBases << "\t"
+                 << f.viewer.avgDepth << "\t";
+            if (searched[g]) fout << ((est[g].alpha < 0.5) ? est[g].alpha : (1.f - est[g].alpha)) << "\t" << -est[g].llk1 << "\t" << -est[g].llk0;
+            else fout << "NA\tNA\tNA";
+            fout << "\t" << "NA\tNA\t" << "NA\tNA\tNA\tNA\tNA\t" << "NA\tNA\tNA" << std::endl;
+        }
+    });
 }
 
 // main.cpp:336-369: sites with depth > 0 in bed order.
 int write_pileup(const std::string& prefix, const vb2_flat& f)
 {
-    const std::string name(prefix + ".Pileup");
-    std::ofstream fout(name);
-    if (!fout.is_open()) return io_error("Open file " + name + " failed!");
-    for (size_t i = 0; i < f.panel.PosVec.size(); ++i) {
-        const auto& item = f.panel.PosVec[i];
-        const int32_t slot = f.panel.rowSlot[i], site = f.viewer.site_of(slot);
-        if (site < 0) continue;
-        const uint32_t n = f.viewer.depth(site);
-        if (n == 0) continue;
-        fout << item.first << "\t" << item.second << "\t" << f.panel.slotRef[slot] << "\t" << n << "\t";
-        fout.write(f.viewer.bases(site), n);
-        fout << "\t";
-        fout.write(f.viewer.quals(site), n);
-        fout << std::endl;
-    }
-    fout.close();
-    if (!fout) return io_error("Errors detected when writing to file " + name + " !");
-    return VB2_OK;
+    return write_text_file(prefix + ".Pileup", [&](std::ostream& fout) {
+        for (size_t i = 0; i < f.panel.PosVec.size(); ++i) {
+            const auto& item = f.panel.PosVec[i];
+            const int32_t slot = f.panel.rowSlot[i], site = f.viewer.site_of(slot);
+            if (site < 0) continue;
+            const uint32_t n = f.viewer.depth(site);
+            if (n == 0) continue;
+            fout << item.first << "\t" << item.second << "\t" << f.panel.slotRef[slot] << "\t" << n << "\t";
+            fout.write(f.viewer.bases(site), n);
+            fout << "\t";
+            fout.write(f.viewer.quals(site), n);
+            fout << std::endl;
+        }
+    });
 }
 
 // stdout block of ContaminationEstimator.cpp:100-166.

@@ -11,7 +11,9 @@
 #define VB2_HOSTIO_H_
 
 #include <cstdint>
+#include <functional>
 #include <memory>
+#include <ostream>
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
@@ -199,9 +201,9 @@ int write_pair_ci(const std::string& prefix, int num_pair, const char* const* na
                   const int32_t* ci_status);
 // VB2_ERR_INVALID with a message for an index out of range, a sample paired with itself or a tumour listed twice
 int check_pairs(const char* who, int num_sample, int num_pair, const int32_t* tumour, const int32_t* normal);
-// The panel files of a run (abi.cpp): .UD and .mu parsed on helper threads while the caller's
-// thread reads the .bed (and the AF file); errors in the reference's reading order.
-int load_panel(const vb2_run_args* a, Panel* panel);
+// The tables' one way to a file: opens `name`, lets body write, closes; VB2_ERR_IO with the reference's message for a
+// file that cannot be opened or for one whose stream failed by the time it is closed.
+int write_text_file(const std::string& name, const std::function<void(std::ostream&)>& body);
 }  // namespace vb2
 
 #endif

@@ -15,7 +15,10 @@
 
 #include "batch.h"
 #include "context.h"
+#include "guard.h"
+#include "host_clock.h"
 #include "interval.h"
+#include "run.h"
 
 namespace vb2 {
 namespace {
@@ -527,4 +530,45 @@ int write_ci(const std::string& prefix, const vb2_interval& ci)
     return VB2_OK;
 }
 
+namespace {
+// --ConfidenceInterval as a stage of the run: the interval on the run's context once the search is done; <prefix>.CI and its
+// NOTICE after .selfSM
+RunStage interval_stage(vb2_interval* ci)
+{
+    RunStage stage;
+    stage.on_context = [ci](vb2_ctx* ctx, const vb2_flat&, const vb2_model& model, const vb2_estimate& est) -> int {
+        const bool notices = model.notices != 0;
+        const double t0 = now_s();
+        if (notices) std::fprintf(stderr, "NOTICE - Starting phase: Confidence interval\n");
+        const int rc = ctx_interval(ctx->impl, model, est, ci);
+        if (notices)
+            std::fprintf(stderr, "NOTICE - Finished phase: Confidence interval  [%.3f seconds, %lld derivative launches]\n", now_s() - t0,
+                         (long long)ci->num_launch);
+        return rc;
+    };
+    stage.after_writers = [ci](const vb2_run_args& args) -> int {
+        if (args.output_prefix)
+            if (const int rc = write_ci(args.output_prefix, *ci)) return rc;
+        std::fprintf(stderr, "NOTICE - FREEMIX 95%% CI (profile likelihood): [%g, %g]\n", ci->lo, ci->hi);
+        return VB2_OK;
+    };
+    return stage;
+}
+}  // namespace
+
 }  // namespace vb2
+
+extern "C" int vb2_run_interval(const vb2_run_args* a, vb2_run_result* out, vb2_interval* ci)
+{
+    return vb2::guarded([&]() -> int {
+        if (!ci) {
+            vb2::set_error("vb2_run_interval: invalid argument");
+            return VB2_ERR_INVALID;
+        }
+        if (a && out && a->devices && a->num_device > 1) {
+            vb2::set_error("--ConfidenceInterval takes one device: it cannot be combined with marker shards over several --Devices");
+            return VB2_ERR_INVALID;
+        }
+        return vb2::run_sample(a, out, vb2::interval_stage(ci));
+    });
+}

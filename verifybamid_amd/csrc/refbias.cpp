@@ -10,7 +10,6 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
-#include <fstream>
 #include <memory>
 #include <string>
 #include <vector>
@@ -19,7 +18,7 @@
 #include "guard.h"
 #include "hostio.h"
 #include "refbias_kernels.h"
-#include "replicates.h"
+#include "run.h"
 
 namespace vb2 {
 
@@ -353,29 +352,22 @@ int vb2_run_refbias(const vb2_run_args* args, vb2_run_result* out, vb2_refbias_f
     }
     vb2_refbias_fit f;
     std::memset(&f, 0, sizeof(f));
-    const vb2::RunHook hook = [&](vb2_ctx* ctx, const vb2_flat& flat, const vb2_model& model, const vb2_estimate& whole) -> int {
+    vb2::RunStage stage;
+    stage.on_context = [&](vb2_ctx* ctx, const vb2_flat& flat, const vb2_model& model, const vb2_estimate& whole) -> int {
         const auto t0 = std::chrono::steady_clock::now();
         if (const int rc = vb2::refbias_fit_ctx(ctx->impl, model, &f)) return rc;
         const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         const double freemix = whole.alpha < 0.5 ? whole.alpha : 1 - whole.alpha;
         const double freemix_bias = f.alpha_bias < 0.5 ? f.alpha_bias : 1 - f.alpha_bias;
         if (args->output_prefix) {
-            const std::string name(std::string(args->output_prefix) + ".RefBias");
-            std::ofstream fout(name);
-            if (!fout.is_open()) {
-                set_error("Open file " + name + " failed!");
-                return VB2_ERR_IO;
-            }
-            fout << "#SEQ_ID\tFREEMIX\tFREEMIX_BIAS\tREF_BIAS\tREF_BIAS_SE\tLRT\tFREELK1_BIAS\tFREELK1_HALF\tAT_BOUND\n";
-            fout << flat.viewer.SEQ_SM << "\t" << freemix << "\t" << freemix_bias << "\t" << f.beta << "\t";
-            if (f.beta_se == f.beta_se) fout << f.beta_se;
-            else fout << "NA";
-            fout << "\t" << f.lrt << "\t" << f.llk1_bias << "\t" << f.llk1_at_half << "\t" << f.at_bound << "\n";
-            fout.close();
-            if (!fout) {
-                set_error("Errors detected when writing to file " + name + " !");
-                return VB2_ERR_IO;
-            }
+            const int rc = vb2::write_text_file(std::string(args->output_prefix) + ".RefBias", [&](std::ostream& fout) {
+                fout << "#SEQ_ID\tFREEMIX\tFREEMIX_BIAS\tREF_BIAS\tREF_BIAS_SE\tLRT\tFREELK1_BIAS\tFREELK1_HALF\tAT_BOUND\n";
+                fout << flat.viewer.SEQ_SM << "\t" << freemix << "\t" << freemix_bias << "\t" << f.beta << "\t";
+                if (f.beta_se == f.beta_se) fout << f.beta_se;
+                else fout << "NA";
+                fout << "\t" << f.lrt << "\t" << f.llk1_bias << "\t" << f.llk1_at_half << "\t" << f.at_bound << "\n";
+            });
+            if (rc) return rc;
         }
         std::fprintf(stderr, "NOTICE - REF_BIAS %g (SE %g), LRT %g against 0.5; FREEMIX %g with the bias fitted, %g at 0.5%s  [%d searches, "
                              "%lld lock-step steps, %.3f seconds]\n", f.beta, f.beta_se, f.lrt, freemix_bias, freemix,
@@ -383,7 +375,7 @@ int vb2_run_refbias(const vb2_run_args* args, vb2_run_result* out, vb2_refbias_f
         return VB2_OK;
     };
     return guarded([&] {
-        const int rc = vb2::run_with_hook(args, out, hook);
+        const int rc = vb2::run_sample(args, out, stage);
         if (fit) *fit = f;
         return rc;
     });

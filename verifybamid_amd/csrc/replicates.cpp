@@ -10,7 +10,6 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <fstream>
 #include <memory>
 #include <string>
 #include <vector>
@@ -20,6 +19,7 @@
 #include "host_clock.h"
 #include "hostio.h"
 #include "marker_sum_kernels.h"
+#include "run.h"
 
 namespace vb2 {
 
@@ -338,7 +338,8 @@ int vb2_run_replicates(const vb2_run_args* args, int32_t per_chromosome, int32_t
     std::memset(&sum, 0, sizeof(sum));
     sum.jack_estimate = sum.jack_se = sum.jack_lo = sum.jack_hi = NAN;
     sum.boot_mean = sum.boot_sd = sum.boot_p025 = sum.boot_p975 = NAN;
-    const vb2::RunHook hook = [&](vb2_ctx* ctx, const vb2_flat& flat, const vb2_model& model, const vb2_estimate& whole) -> int {
+    vb2::RunStage stage;
+    stage.on_context = [&](vb2_ctx* ctx, const vb2_flat& flat, const vb2_model& model, const vb2_estimate& whole) -> int {
         const double t0 = vb2::now_s();
         vb2::Context* c = ctx->impl;
         const size_t M = (size_t)c->num_marker;
@@ -387,29 +388,21 @@ int vb2_run_replicates(const vb2_run_args* args, int32_t per_chromosome, int32_t
             }
             sum.num_chrom = C;
             if (args->output_prefix) {
-                const std::string name(std::string(args->output_prefix) + ".Chrom");
-                std::ofstream fout(name);
-                if (!fout.is_open()) {
-                    set_error("Open file " + name + " failed!");
-                    return VB2_ERR_IO;
-                }
-                fout << "#CHROM\tMARKERS\tFREEMIX_ONLY\tFREELK1_ONLY\tFREELK0_ONLY\tFREEMIX_WITHOUT\tDELTA\n";
-                for (int j = 0; j < C; ++j) {
-                    fout << b.names[j] << "\t" << rep->counted[j];
-                    if (m[j] > 0) {
-                        fout << "\t" << vb2::freemix_of(est[j]) << "\t" << -est[j].llk1 << "\t" << -est[j].llk0 << "\t" << without[j]
-                             << "\t" << without[j] - theta << "\n";
-                    } else {
-                        fout << "\tNA\tNA\tNA\tNA\tNA\n";
+                const int rc = vb2::write_text_file(std::string(args->output_prefix) + ".Chrom", [&](std::ostream& fout) {
+                    fout << "#CHROM\tMARKERS\tFREEMIX_ONLY\tFREELK1_ONLY\tFREELK0_ONLY\tFREEMIX_WITHOUT\tDELTA\n";
+                    for (int j = 0; j < C; ++j) {
+                        fout << b.names[j] << "\t" << rep->counted[j];
+                        if (m[j] > 0) {
+                            fout << "\t" << vb2::freemix_of(est[j]) << "\t" << -est[j].llk1 << "\t" << -est[j].llk0 << "\t" << without[j]
+                                 << "\t" << without[j] - theta << "\n";
+                        } else {
+                            fout << "\tNA\tNA\tNA\tNA\tNA\n";
+                        }
                     }
-                }
-                fout << "#JACKKNIFE\tFREEMIX\t" << sum.jack_estimate << "\tSE\t" << sum.jack_se << "\tLO\t" << sum.jack_lo << "\tHI\t"
-                     << sum.jack_hi << "\n";
-                fout.close();
-                if (!fout) {
-                    set_error("Errors detected when writing to file " + name + " !");
-                    return VB2_ERR_IO;
-                }
+                    fout << "#JACKKNIFE\tFREEMIX\t" << sum.jack_estimate << "\tSE\t" << sum.jack_se << "\tLO\t" << sum.jack_lo << "\tHI\t"
+                         << sum.jack_hi << "\n";
+                });
+                if (rc) return rc;
             }
         }
         if (N > 0) {
@@ -431,25 +424,17 @@ int vb2_run_replicates(const vb2_run_args* args, int32_t per_chromosome, int32_t
                 sum.boot_p975 = sorted[(size_t)std::floor(0.975 * last + 0.5)];
             }
             if (args->output_prefix) {
-                const std::string name(std::string(args->output_prefix) + ".Boot");
-                std::ofstream fout(name);
-                if (!fout.is_open()) {
-                    set_error("Open file " + name + " failed!");
-                    return VB2_ERR_IO;
-                }
-                fout << "#REPLICATE\tFREEMIX\tFREELK1\n";
-                for (int q = 0; q < N; ++q) {
-                    const vb2_estimate& e = est[2 * C + q];
-                    if (status[2 * C + q] == VB2_OK) fout << q + 1 << "\t" << vb2::freemix_of(e) << "\t" << -e.llk1 << "\n";
-                    else fout << q + 1 << "\tNA\tNA\n";
-                }
-                fout << "#BOOTSTRAP\tMEAN\t" << sum.boot_mean << "\tSD\t" << sum.boot_sd << "\tP2.5\t" << sum.boot_p025 << "\tP97.5\t"
-                     << sum.boot_p975 << "\n";
-                fout.close();
-                if (!fout) {
-                    set_error("Errors detected when writing to file " + name + " !");
-                    return VB2_ERR_IO;
-                }
+                const int rc = vb2::write_text_file(std::string(args->output_prefix) + ".Boot", [&](std::ostream& fout) {
+                    fout << "#REPLICATE\tFREEMIX\tFREELK1\n";
+                    for (int q = 0; q < N; ++q) {
+                        const vb2_estimate& e = est[2 * C + q];
+                        if (status[2 * C + q] == VB2_OK) fout << q + 1 << "\t" << vb2::freemix_of(e) << "\t" << -e.llk1 << "\n";
+                        else fout << q + 1 << "\tNA\tNA\n";
+                    }
+                    fout << "#BOOTSTRAP\tMEAN\t" << sum.boot_mean << "\tSD\t" << sum.boot_sd << "\tP2.5\t" << sum.boot_p025 << "\tP97.5\t"
+                         << sum.boot_p975 << "\n";
+                });
+                if (rc) return rc;
             }
         }
         sum.seconds = vb2::now_s() - t0;
@@ -465,7 +450,7 @@ int vb2_run_replicates(const vb2_run_args* args, int32_t per_chromosome, int32_t
         return VB2_OK;
     };
     return guarded([&] {
-        const int rc = vb2::run_with_hook(args, out, hook);
+        const int rc = vb2::run_sample(args, out, stage);
         if (summary) *summary = sum;
         return rc;
     });

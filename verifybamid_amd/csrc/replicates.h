@@ -4,13 +4,10 @@
 #define VB2_REPLICATES_H_
 
 #include <cstdint>
-#include <functional>
 #include <vector>
 
 #include "../../include/vb2_abi.h"
 #include "row_set.h"
-
-struct vb2_flat;
 
 namespace vb2 {
 
@@ -38,11 +35,6 @@ private:
 // others go on.  The return value: a failure of fn (it ends every search).
 int replicates_lockstep(vb2_replicates_eval_fn fn, void* user, int num_rep, int num_pc, bool data_has_known_af,
                         const vb2_model& model, vb2_estimate* est, int32_t* status, int64_t* num_step);
-
-// vb2_run with a stage between the search and the writers: hook(ctx, flat, model, estimate) runs on the run's context (one
-// device) after a successful search; a non-zero return fails the run.  Defined in abi.cpp.
-typedef std::function<int(vb2_ctx* ctx, const vb2_flat& flat, const vb2_model& model, const vb2_estimate& est)> RunHook;
-int run_with_hook(const vb2_run_args* args, vb2_run_result* out, const RunHook& hook);
 
 }  // namespace vb2
 

@@ -6,7 +6,8 @@ The item loop is found in the disassembly, not assumed: the innermost span betwe
 both `s_setprio 1` (a wave enters its read loop) and `s_setprio 0` (it leaves it); blocks the compiler placed behind the loop --
 the branch of the tiny likelihoods, the refills of a long list -- lie outside the span and are not counted.  Counts are STATIC:
 an instruction of the walk's unrolled row body counts once however many rows a tile has.  Classes: v_mul_f64 between the two
-s_setprio (the walk's multiplies), every other FP64 arithmetic instruction (v_*_f64 but compares), DPP moves (v_mov_b32_dpp),
+s_setprio (the walk's multiplies), v_fmac_f64_dpp (the projection's FMAs whose coefficient is a lane of the DPP row: eval_body,
+COEF_DPP), every other FP64 arithmetic instruction (v_*_f64 but compares), DPP moves (v_mov_b32_dpp),
 v_permlane16_swap, ds_read_b128, other LDS instructions (ds_*), v_cndmask, v_lshl_add_u64 (a 64-bit address made per lane), other
 vector ALU (v_*), vector memory by the form of its address -- a scalar base or a buffer descriptor with a 32-bit vector offset
 (global_* with an SGPR pair, buffer_*) against a 64-bit vector address (global_* ... off, flat_*) --, s_nop, scalar and the rest
@@ -19,7 +20,7 @@ import tempfile
 
 import isa_diff
 
-CLASSES = ("v_mul_f64 in the walk", "other FP64", "DPP moves", "v_permlane16_swap", "ds_read_b128", "other LDS", "v_cndmask",
+CLASSES = ("v_mul_f64 in the walk", "v_fmac_f64_dpp", "other FP64", "DPP moves", "v_permlane16_swap", "ds_read_b128", "other LDS", "v_cndmask",
            "v_lshl_add_u64", "other VALU", "vector memory, scalar base", "vector memory, vector address", "s_nop", "scalar and the rest")
 
 
@@ -65,6 +66,8 @@ def classify(text, in_walk):
     op = text.split()[0]
     if op.startswith("v_permlane16_swap"):
         return "v_permlane16_swap"
+    if op.startswith("v_fmac_f64_dpp"):      # (FP64 arithmetic with a DPP operand: neither a move nor "other FP64")
+        return "v_fmac_f64_dpp"
     if "_dpp" in op or " row_" in text or " quad_perm" in text:
         return "DPP moves"
     if op.startswith("v_cndmask"):
@@ -88,25 +91,31 @@ def classify(text, in_walk):
     return "scalar and the rest"
 
 
-def main():
-    args = [a for a in sys.argv[1:] if a != "--list"]
-    lib, want = args[0], (args[1] if len(args) > 1 else "llk_eval_split6_kernel<4>")
+def census(lib, want):
+    """(kernel name, its code, (first, last) of the item loop, {class: count}) of the one kernel of lib whose name holds `want`"""
     with tempfile.TemporaryDirectory() as tmp:
         found = [(k, v) for co in isa_diff.code_object(lib, tmp) for k, v in disassemble(co).items() if want in k]
     if len(found) != 1:
         raise SystemExit("%d kernels match %r" % (len(found), want))
     name, code = found[0]
     lo, hi = item_loop(code)
-    span = code[lo:hi + 1]
     counts, walk = dict.fromkeys(CLASSES, 0), False
-    for _, t in span:
+    for _, t in code[lo:hi + 1]:
         if t.startswith("s_setprio"):
             walk = t.startswith("s_setprio 1")
         counts[classify(t, walk)] += 1
+    return name, code, (lo, hi), counts
+
+
+def main():
+    args = [a for a in sys.argv[1:] if a != "--list"]
+    lib, want = args[0], (args[1] if len(args) > 1 else "llk_eval_split6_kernel<4>")
+    name, code, (lo, hi), counts = census(lib, want)
+    span = code[lo:hi + 1]
     print("%s\n  %d instructions in the kernel, item loop: instructions %d..%d (%d)" % (name.split("(")[0], len(code), lo, hi, len(span)))
     for c in CLASSES:
         print("  %-30s %5d" % (c, counts[c]))
-    valu = sum(counts[c] for c in ("v_mul_f64 in the walk", "other FP64", "DPP moves", "v_permlane16_swap", "v_cndmask", "v_lshl_add_u64",
+    valu = sum(counts[c] for c in ("v_mul_f64 in the walk", "v_fmac_f64_dpp", "other FP64", "DPP moves", "v_permlane16_swap", "v_cndmask", "v_lshl_add_u64",
                                    "other VALU"))
     print("  %-30s %5d\n  %-30s %5d" % ("all vector ALU", valu, "all LDS", counts["ds_read_b128"] + counts["other LDS"]))
     if "--list" in sys.argv[1:]:

@@ -471,6 +471,35 @@ __device__ __forceinline__ void lane_scatter8_u32(unsigned p0, unsigned p1, unsi
     other = r[1];
 }
 
+// Component KK of the projection with its coefficients from a DPP row's lanes (eval_body, COEF_DPP; the hardware's conditions are
+// listed where marker_lk calls this): a1[t] += uu * coefficient [KK][t], a2[t] += uu * coefficient [K + KK][t] of the lane's own slot,
+// t = point 0, 1.  ca: lane i of the row holds coefficient i of the slot of the row's quads 0 and 3; cb: the same for the slot of its
+// quads 1 and 2, from lane HI on (K = 4: HI = 0, a register pair of its own; K = 2: HI = 8, the upper half of ca's pair).  KK = 0
+// opens with the wait states of a vector write of EXEC.
+template <int K, int KK>
+__device__ __forceinline__ void project_dpp(double& a10, double& a11, double& a20, double& a21, const double ca, const double cb, const double uu)
+{
+    static_assert((K == 4 || K == 2) && KK >= 0 && KK < K, "sixteen coefficients a slot, or eight");
+    constexpr int kHi = K == 2 ? 8 : 0;
+    constexpr int j10 = 2 * KK, j11 = 2 * KK + 1, j20 = 2 * (K + KK), j21 = 2 * (K + KK) + 1;
+#define VB2_COEF_FMAS \
+    "v_fmac_f64_dpp %0, %4, %6 row_newbcast:%7 row_mask:0xf bank_mask:0x9\n\t" \
+    "v_fmac_f64_dpp %1, %4, %6 row_newbcast:%8 row_mask:0xf bank_mask:0x9\n\t" \
+    "v_fmac_f64_dpp %2, %4, %6 row_newbcast:%9 row_mask:0xf bank_mask:0x9\n\t" \
+    "v_fmac_f64_dpp %3, %4, %6 row_newbcast:%10 row_mask:0xf bank_mask:0x9\n\t" \
+    "v_fmac_f64_dpp %0, %5, %6 row_newbcast:%11 row_mask:0xf bank_mask:0x6\n\t" \
+    "v_fmac_f64_dpp %1, %5, %6 row_newbcast:%12 row_mask:0xf bank_mask:0x6\n\t" \
+    "v_fmac_f64_dpp %2, %5, %6 row_newbcast:%13 row_mask:0xf bank_mask:0x6\n\t" \
+    "v_fmac_f64_dpp %3, %5, %6 row_newbcast:%14 row_mask:0xf bank_mask:0x6"
+#define VB2_COEF_OPERANDS \
+    : "+v"(a10), "+v"(a11), "+v"(a20), "+v"(a21) \
+    : "v"(ca), "v"(cb), "v"(uu), "n"(j10), "n"(j11), "n"(j20), "n"(j21), "n"(kHi + j10), "n"(kHi + j11), "n"(kHi + j20), "n"(kHi + j21)
+    if constexpr (KK == 0) asm volatile("s_nop 4\n\t" VB2_COEF_FMAS VB2_COEF_OPERANDS);
+    else asm volatile(VB2_COEF_FMAS VB2_COEF_OPERANDS);
+#undef VB2_COEF_FMAS
+#undef VB2_COEF_OPERANDS
+}
+
 // Occupancy target: one 1024-thread workgroup per CU (4 waves/SIMD, <=128 VGPRs).  Two
 // smaller workgroups per CU were measured slower: the per-alpha table is built once per
 // workgroup, and that redundant work is 9 % of a launch's transcendentals at one
@@ -584,6 +613,14 @@ __host__ __device__ __forceinline__ bool eval_is_dynamic(const DeviceLayout& L, 
 // one bit, where the compiler's wave-aggregated atomic counts lanes for an add that only ever has one.  The same addresses, no
 // arithmetic on a likelihood: the same bits.  44 vector instructions fewer in the item loop of llk_eval_split6_kernel<4>
 // (tools/item_census.py: 511 -> 467; HISTORY.md, profiles/r14).
+// COEF_DPP (the split launch six ways at --NumPC 4 and 2): a workgroup of such a launch has ONE point group, so a lane's slot and
+// its two points never change, and the epilogue's 2 k ds_read_b128 of projection coefficients fetched the same bytes into the same
+// lane for every item.  The coefficients are loaded once, behind the prologue's last barrier, into the lanes of the 16-lane DPP rows
+// -- lane i of a row holds coefficient i of a slot, ptq's own order [2 k][2 points] --, and each FMA of the projection takes its
+// coefficient from its lane of the reader's row: v_fmac_f64_dpp with row_newbcast, the one DPP control FP64 instructions take.  A
+// row holds the lanes of TWO slots (see the load in front of the item loop), so each FMA exists twice, under complementary bank
+// masks.  The same two factors into the same addend in the same order: the same bits.  Four resident registers (two at --NumPC 2)
+// for the 32 that the reads landed in; 2 k LDS instructions fewer and 4 k vector instructions more per item (HISTORY.md, profiles/r15).
 // PD: a probability-domain context (DeviceLayout::pd; llk_kernels.h, kMaxPow): the table holds P^n rows of class ref only,
 // a marker's list is one 16-bit row offset per step, ref steps first and alt steps behind them; the six sums are PRODUCTS,
 // class alt multiplies them with the row read the other way round (g -> 2 - g, h:164-177: T[alt][q][g1][g2] is T[ref][q][2-g1][2-g2]),
@@ -609,6 +646,7 @@ struct EvalConfig {
     static constexpr bool W16 = false, STREAM = false, LCACHE = false, PD = false;
     static constexpr int QUEUE = -1, KSEL = 0, ESH = 8, SPLIT = 0;
     static constexpr bool READS_AHEAD = false, ITEM_AHEAD = false, EPI_X8 = false, EPI_SCATTER = false, ADDR_SCALAR = false;
+    static constexpr bool COEF_DPP = false;
 };
 template <class Config, class Hook = NoHook>
 __device__ __forceinline__ void
@@ -650,6 +688,8 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
     constexpr bool kEpiScatter = Config::EPI_SCATTER && kEpiX8;      // (one point per lane behind the exchange over marker bit 3)
     static_assert(!Config::ADDR_SCALAR || Config::ITEM_AHEAD, "scalar row offsets: the record's words are taken where the rows ahead are requested");
     constexpr bool kAddrScalar = Config::ADDR_SCALAR && kAhead;      // (the item loop's uniform address arithmetic on the scalar unit)
+    // (the projection's coefficients resident in a DPP row's lanes: one group for the whole launch, two points per lane, --NumPC 4 or 2)
+    constexpr bool kCoefDpp = Config::COEF_DPP && ONEGRP && PD && MODE == 2 && BTL == 2 && (KSEL == 4 || KSEL == 2) && (kAblate & kAblNoEpi) == 0;
     // (items ahead: every row but a tile's first is walked from its two table ADDRESSES, taken from the ring's word before that
     // register is refilled -- row_step and walk_pd, kAt)
     constexpr bool kFixedRing = kAhead && kReadsAhead && (kAblate & kAblNoMul) == 0;
@@ -1120,6 +1160,29 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
     uint32_t etab_lane = (uint32_t)(lane & (kEtabCopies - 1)) * 8u;     // etab is at LDS address 0 (no static LDS in this file)
     const uint32_t tab_addr = lds_byte_addr(tab);
     const uint32_t ptq_addr = lds_byte_addr(ptq);
+    // COEF_DPP: the projection's coefficients, resident in the lanes of the DPP rows for the whole launch -- loaded here, behind the
+    // barrier after which ptq is complete, and never written again (no vector write of them anywhere near a DPP read: there is none
+    // in the item loop).  Which slots a 16-lane row r = lane >> 4 holds, from lane_map: the quads of the rows 0 and 2 have slot
+    // parity 0, 1, 1, 0, those of the rows 1 and 3 parity 1, 0, 0, 1 (nib & 1 of the quads 0..3 and 4..7), and the slot is the
+    // parity + 2 * (lane >> 5) -- the row's quads {0, 3} belong to slot r, its quads {1, 2} to slot r ^ 1: the LDS pass groups
+    // straddle the rows.  --NumPC 4 (sixteen coefficients a slot, ptq's order [2 k][2 points]): lane i of the row holds ptq[slot r][i]
+    // in coef_a and ptq[slot r ^ 1][i] in coef_b.  --NumPC 2 (eight a slot): one pair is enough -- the lanes 0..7 hold slot r's,
+    // the lanes 8..15 slot r ^ 1's, in coef_a.  The values the epilogue's reads brought, the copies of a padded group's last
+    // valid point among them: they come from the same ptq.
+    double coef_a = 0.0, coef_b = 0.0;
+    if constexpr (kCoefDpp) {
+        static_assert(SLOTS == 4 && 2 * KSEL * BTL <= 16, "a row's sixteen lanes hold a slot's coefficients, or two slots'");
+        const uint32_t row_ = (uint32_t)lane >> 4, i_ = (uint32_t)lane & 15u;
+        // (kept as they are loaded: opaque, so that nothing reads them again from LDS inside the loop)
+        if constexpr (KSEL == 4) {
+            coef_a = *reinterpret_cast<lds_cdouble*>(ptq_addr + (row_ * 16u + i_) * 8u);
+            coef_b = *reinterpret_cast<lds_cdouble*>(ptq_addr + ((row_ ^ 1u) * 16u + i_) * 8u);
+            asm volatile("" : "+v"(coef_a), "+v"(coef_b));
+        } else {
+            coef_a = *reinterpret_cast<lds_cdouble*>(ptq_addr + ((i_ < 8u ? row_ : row_ ^ 1u) * 8u + (i_ & 7u)) * 8u);
+            asm volatile("" : "+v"(coef_a));
+        }
+    }
     if (L.stagger > 0 && wave >= (nwave >> 1))
         for (int i = 0; i < L.stagger; ++i) __builtin_amdgcn_s_sleep(1);
     // static mode: the host-built schedule (LPT over the waves), or items dealt in snake order
@@ -1366,8 +1429,40 @@ eval_body(const DeviceLayout& L, const double* ip_v, const int ip_count, const d
             if (z == 12345.678) lk_m[0] = 0.75;
             return;
         }
+        // COEF_DPP: the projection with its coefficients from the resident registers coef_a / coef_b, lane j of the reader's own
+        // 16-lane row -- v_fmac_f64_dpp under row_newbcast:j, written as assembly: the compiler does not fold a 64-bit DPP move into
+        // the FMA.  Per FMA of the old projection TWO: from coef_a under bank mask 0x9 (the row's quads 0 and 3: slot r) and from coef_b
+        // -- --NumPC 2: the same pair's upper eight lanes -- under 0x6 (quads 1 and 2: slot r ^ 1); under a bank mask the other quads
+        // keep their accumulator, so every lane ends with its own slot's sum.  Per accumulator the components come in the old order
+        // kk = 0, 1, ..., each a fused multiply-add of the same two factors into the same addend: the same bits.  One statement per
+        // component, the four accumulators interleaved: a chain's dependent FMAs are four instructions apart.
+        // What the compiler does not check for inline assembly:
+        //   * EXEC must be all ones here -- a source lane that is switched off leaves its readers with their old value (bound_ctrl
+        //     is 0), silently.  So the projection stands IN FRONT of the branch on `live`, which diverges in a partly filled last
+        //     tile, and runs for all 64 lanes: the branches around the epilogue are wave-uniform, every workgroup is whole waves.
+        //     A dead lane's udr was loaded from position 0 and is finite; its sums are not used.
+        //   * no vector instruction writes coef_a / coef_b in the item loop (a VALU write of a DPP source needs two wait states);
+        //   * a vector instruction that writes EXEC needs five wait states before a DPP instruction: the s_nop 4 at the head of the
+        //     first statement covers them (the statements are volatile and keep their order).
+        double afd1[2] = {0., 0.}, afd2[2] = {0., 0.};
+        if constexpr (kCoefDpp) {
+            const double cb_ = KSEL == 2 ? coef_a : coef_b;
+            project_dpp<KSEL, 0>(afd1[0], afd1[1], afd2[0], afd2[1], coef_a, cb_, udr[0]);
+            project_dpp<KSEL, 1>(afd1[0], afd1[1], afd2[0], afd2[1], coef_a, cb_, udr[1]);
+            if constexpr (KSEL == 4) {
+                project_dpp<KSEL, 2>(afd1[0], afd1[1], afd2[0], afd2[1], coef_a, cb_, udr[2]);
+                project_dpp<KSEL, 3>(afd1[0], afd1[1], afd2[0], afd2[1], coef_a, cb_, udr[3]);
+            }
+        }
         if (live) {
             double af1[BTL], af2[BTL];
+            if constexpr (kCoefDpp) {
+#pragma unroll
+                for (int t = 0; t < BTL; ++t) {
+                    af1[t] = afd1[t] + mur; af1[t] /= 2.0;
+                    af2[t] = afd2[t] + mur; af2[t] /= 2.0;
+                }
+            } else
             if (kaf_item) {
                 const double a = g_kaf[pos];
 #pragma unroll

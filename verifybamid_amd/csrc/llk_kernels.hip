@@ -27,11 +27,13 @@ struct PlainEval : EvalConfig {
 };
 // ... the split launch: the 8-point probability-domain shape on the queue with everything that shape has; its tile butterfly
 // is a reduce-scatter, one point per lane (EPI_SCATTER), and its item loop's uniform address arithmetic is the scalar unit's
-// (ADDR_SCALAR)
+// (ADDR_SCALAR); six ways, where a workgroup has one point group for the whole launch, the projection's coefficients stay in the
+// lanes of the DPP rows (COEF_DPP: --NumPC 4 and 2)
 template <int KSEL_, int S>
 struct SplitEval : EvalConfig {
     static constexpr int MODE = 2, QUEUE = 1, KSEL = KSEL_, SPLIT = S;
     static constexpr bool PD = true, READS_AHEAD = true, ITEM_AHEAD = true, EPI_X8 = true, EPI_SCATTER = true, ADDR_SCALAR = true;
+    static constexpr bool COEF_DPP = S == kMaxGroups;
 };
 
 template <int MODE, int QUEUE, int KSEL = 0, bool PD = false>

@@ -974,6 +974,101 @@ int vb2_refbias_lockstep(vb2_refbias_eval_fn fn, void *user, int32_t num_pc, con
  * device and a searched alpha only: VB2_ERR_INVALID otherwise, before any file is read. */
 int vb2_run_refbias(const vb2_run_args *args, vb2_run_result *out, vb2_refbias_fit *fit);
 
+/* ------------------------------------------------------------------------- *
+ * 3h. Empirical base-error rates (--FitError).  Not in the reference: its model with an error rate
+ *     eps[q] per clamped quality q = 0..93 in place of pErr(q) = 10^(-q/10) (ContaminationEstimator.h:65-74), the nominal
+ *     table eps0[q] = pow(10.0, q / -10.0):
+ *         p(read | g1, g2) = (alpha E[g1][c] + (1 - alpha) E[g2][c]) eps_q + (alpha N[g1][c] + (1 - alpha) N[g2][c]) (1 - eps_q)
+ *     (h:223-225; E, N = COND_LK[1], COND_LK[0], c = ref, alt, other).  W, GF1, GF2, L = sum GF1[g1] GF2[g2] W[g1][g2], "a
+ *     marker counts where L > 0" and LLK = sum log L stay as they are.  Every llk of this section is a LOG-LIKELIHOOD.
+ * ------------------------------------------------------------------------- */
+#define VB2_ERR_NUM_QUAL 94
+#define VB2_ERRFIT_MAX_ITER 24
+
+/* vb2_ctx_create under an error table: err_table [VB2_ERR_NUM_QUAL] replaces pErr(q) in every table the context builds and
+ * nothing else; NULL is vb2_ctx_create, and so are the nominal values, byte for byte.  An entry outside [0, 1] or a NaN is
+ * VB2_ERR_INVALID. */
+int vb2_ctx_create_ex(const vb2_input *in, const vb2_options *opt, const double *err_table, vb2_ctx **out);
+
+/* The E-step.  A set holds a device copy of the RAW input (bases, qualities, offsets, alt alleles, panel rows or known
+ * allele frequencies, the depth filter's constants): `in` is not referenced after the call returns.  opt: the device (and
+ * stream) as for vb2_ctx_create; flags are ignored. */
+typedef struct vb2_errstat vb2_errstat;
+int vb2_errstat_create(const vb2_input *in, const vb2_options *opt, vb2_errstat **out);
+void vb2_errstat_destroy(vb2_errstat *set);
+/* At (pc1, pc2, alpha) under err_table, over the markers that count there (the context's rules: a non-empty range, the
+ * +-3 sd depth filter unless disabled, L > 0 as the reference forms it): per quality n_out = their reads, all three classes,
+ * and s_out = the sum of P(the read is an error | all reads of its marker) -- a class-other read counts 1 --; *llk_out =
+ * sum log L (vb2_llk_eval_batch on a context of the same table, to rounding).  Any of the three may be NULL.  All are the
+ * same bits from call to call and whatever the launch's grid: s is summed in 64-bit fixed point (what a read loses is below
+ * 2^-64) and rounded once.  alpha outside [0, 1] (or NaN) and a bad table are VB2_ERR_INVALID.  Synchronous; host pointers. */
+int vb2_errstat_eval(vb2_errstat *set, const double *err_table, const double *pc1, const double *pc2, double alpha,
+                     int64_t *n_out, double *s_out, double *llk_out);
+typedef struct vb2_errstat_info {
+    int32_t num_marker;
+    int32_t num_pc;
+    int64_t num_read;
+    int64_t device_bytes;      /* device memory the set holds                                        */
+    int64_t num_launch;        /* kernel launches so far (two per evaluation)                        */
+} vb2_errstat_info;
+int vb2_errstat_info_get(const vb2_errstat *set, vb2_errstat_info *info);
+
+/* The fit: alternating maximisation of the likelihood penalised by a Beta prior of prior_reads pseudo-reads centred on
+ * the nominal rate of every quality.
+ *   start      eps_0 = eps0, est_0 = `nominal` (the run's own estimate);
+ *   iteration  (n, s) at (est_t, eps_t); eps_{t+1}[q] = (s[q] + kappa eps0[q]) / (n[q] + kappa) where n[q] > 0, eps0[q]
+ *              elsewhere, ROUNDED TO THE NEAREST float32 and stored as that double; then the reference-exact OptimizeLLK
+ *              under the caller's model from the reference's start, every evaluation under eps_{t+1} -> est_{t+1};
+ *   stop       after the iteration in which max over n[q] > 0 of |eps_{t+1}[q] - eps_t[q]| / eps_t[q] <= tol (a bin whose
+ *              eps_t is 0 counts as changed unless eps_{t+1} is 0 too), else after max_iter iterations with converged = 0;
+ *   report     one more (n, s) at the final (est, eps); lrt = 2 (llk_fit - llk_nominal), num_bin = qualities with reads.
+ * The points handed to the statistics are the search's own: the reported PCs with the reference's swap of indices 0 and 1
+ * for alpha >= 0.5 (ContaminationEstimator.cpp:146-149) undone.  is_alpha_fixed is VB2_ERR_INVALID.  A search that fails
+ * puts its code into status and ends the fit with that code. */
+typedef struct vb2_errfit_opts {
+    double prior_reads;        /* kappa; 0 = 100; negative or NaN: VB2_ERR_INVALID                    */
+    double tol;                /* 0 = 1e-4                                                            */
+    int32_t max_iter;          /* 0 = 24; at most VB2_ERRFIT_MAX_ITER                                 */
+    int32_t reserved;
+} vb2_errfit_opts;
+typedef struct vb2_errfit {
+    double err[VB2_ERR_NUM_QUAL];
+    int64_t n[VB2_ERR_NUM_QUAL];
+    double s[VB2_ERR_NUM_QUAL];
+    vb2_estimate est;          /* the final search under err                                          */
+    double llk_fit, llk_nominal, alpha_nominal, lrt;
+    double iter_llk[VB2_ERRFIT_MAX_ITER];      /* the iteration's search: its log-likelihood,       */
+    double iter_change[VB2_ERRFIT_MAX_ITER];   /* the stop rule's maximum,                           */
+    double iter_alpha[VB2_ERRFIT_MAX_ITER];    /* and alpha as fitted                                */
+    float iter_err[VB2_ERRFIT_MAX_ITER][VB2_ERR_NUM_QUAL];      /* eps_{t+1}: every entry is a float32 */
+    int64_t num_step;          /* likelihood evaluations of all searches (the reference's count)      */
+    int32_t num_bin, num_iter, converged;
+    int32_t status;            /* VB2_OK, or the code of the search that failed                       */
+} vb2_errfit;
+/* the procedure on the device: one vb2_errstat, one fresh context per iteration (vb2_ctx_create_ex, vb2_ctx_optimize_llk) */
+int vb2_errfit_input(const vb2_input *in, const vb2_options *opt, const vb2_model *model, const vb2_estimate *nominal,
+                     const vb2_errfit_opts *fit_opts, vb2_errfit *out);
+/* The same procedure over a caller's two callbacks: no device needed.  eval answers the searches (the seam of
+ * vb2_optimize_llk with the table in front); stats is the E-step.  Non-zero from either ends the fit and is returned. */
+typedef struct vb2_errfit_fns {
+    int (*eval)(void *user, const double *err_table, int32_t num_point, const double *pc1, const double *pc2,
+                const double *alpha, double *llk_out);
+    int (*stats)(void *user, const double *err_table, const double *pc1, const double *pc2, double alpha, int64_t *n_out,
+                 double *s_out);
+} vb2_errfit_fns;
+int vb2_errfit_lockstep(const vb2_errfit_fns *fns, void *user, int32_t num_pc, const vb2_model *model, int32_t data_has_known_af,
+                        const vb2_estimate *nominal, const vb2_errfit_opts *fit_opts, vb2_errfit *out);
+/* vb2_run, then the fit on the run's input under the run's model, the run's estimate the nominal one; then
+ * <output_prefix>.ErrorFit (tab-separated, default ostream formatting):
+ *     #SEQ_ID FREEMIX FREEMIX_FIT LRT NUM_BIN FREELK1_FIT FREELK1_NOMINAL ITERATIONS CONVERGED
+ * and <output_prefix>.ErrorRates, one row per quality with reads:
+ *     #Q_REPORTED READS EXPECTED_ERRORS ERROR_RATE Q_EMPIRICAL SE_BINOM
+ * Q_EMPIRICAL = -10 log10 ERROR_RATE; SE_BINOM = sqrt(eps (1 - eps) / READS), a LOWER bound of the rate's standard error:
+ * it takes every read's error indicator as observed.  One NOTICE line on stderr.  stdout, .selfSM and .Ancestry are what
+ * vb2_run writes, byte for byte.  VB2_ERR_INVALID before any file is read: more than one device, is_alpha_fixed, --NumStart /
+ * --LineSearch. */
+int vb2_run_errfit(const vb2_run_args *args, const vb2_errfit_opts *fit_opts, vb2_run_result *out, vb2_errfit *fit);
+
 /* Host-side flattening only (no device): reads panel + pileup, resolves markers
  * and returns the arrays of vb2_input in library-owned memory; free with
  * vb2_flat_free.  Lets callers (tests, shard planners) inspect or slice them. */

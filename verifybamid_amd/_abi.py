@@ -260,6 +260,37 @@ class RefBiasFit(C.Structure):
                [(n, C.c_int32) for n in ("at_bound", "num_round", "num_refit", "num_pair", "status", "reserved")]
 
 
+VB2_ERR_NUM_QUAL, VB2_ERRFIT_MAX_ITER = 94, 24
+# vb2_errfit_fns.eval: (user, err_table, num_point, pc1, pc2, alpha, llk); .stats: (user, err_table, pc1, pc2, alpha, n, s)
+ERRFIT_EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                             C.POINTER(C.c_double), C.POINTER(C.c_double))
+ERRFIT_STATS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
+                              C.POINTER(C.c_int64), C.POINTER(C.c_double))
+
+
+class ErrFitFns(C.Structure):
+    _fields_ = [("eval", ERRFIT_EVAL_FN), ("stats", ERRFIT_STATS_FN)]
+
+
+class ErrStatInfo(C.Structure):
+    _fields_ = [("num_marker", C.c_int32), ("num_pc", C.c_int32), ("num_read", C.c_int64), ("device_bytes", C.c_int64),
+                ("num_launch", C.c_int64)]
+
+
+class ErrFitOpts(C.Structure):
+    _fields_ = [("prior_reads", C.c_double), ("tol", C.c_double), ("max_iter", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ErrFit(C.Structure):
+    """vb2_errfit: every llk is a log-likelihood (.selfSM's FREELK1)."""
+    _fields_ = [("err", C.c_double * VB2_ERR_NUM_QUAL), ("n", C.c_int64 * VB2_ERR_NUM_QUAL), ("s", C.c_double * VB2_ERR_NUM_QUAL),
+                ("est", Estimate)] + \
+               [(n, C.c_double) for n in ("llk_fit", "llk_nominal", "alpha_nominal", "lrt")] + \
+               [(n, C.c_double * VB2_ERRFIT_MAX_ITER) for n in ("iter_llk", "iter_change", "iter_alpha")] + \
+               [("iter_err", (C.c_float * VB2_ERR_NUM_QUAL) * VB2_ERRFIT_MAX_ITER), ("num_step", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("num_bin", "num_iter", "converged", "status")]
+
+
 class ReplicateSummary(C.Structure):
     _fields_ = [("num_chrom", C.c_int32), ("num_boot", C.c_int32)] + \
                [(n, C.c_double) for n in ("jack_estimate", "jack_se", "jack_lo", "jack_hi", "boot_mean", "boot_sd",
@@ -299,6 +330,8 @@ SYMBOLS = [
     "vb2_refbias_create", "vb2_refbias_destroy", "vb2_refbias_eval", "vb2_refbias_optimize_llk", "vb2_refbias_info_get",
     "vb2_refbias_fit_ctx", "vb2_refbias_lockstep", "vb2_run_refbias",
     "vb2_bgzf_inflate", "vb2_bgzf_inflate_stats", "vb2_cohort_bam_stats",
+    "vb2_ctx_create_ex", "vb2_errstat_create", "vb2_errstat_destroy", "vb2_errstat_eval", "vb2_errstat_info_get",
+    "vb2_errfit_input", "vb2_errfit_lockstep", "vb2_run_errfit",
 ]
 
 _lib = None
@@ -516,6 +549,17 @@ def lib():
     L.vb2_refbias_lockstep.argtypes = [REFBIAS_EVAL_FN, C.c_void_p, C.c_int32, C.POINTER(Model), C.c_int32, C.POINTER(RefBiasFit)]
     L.vb2_run_refbias.argtypes = [C.POINTER(RunArgs), C.POINTER(RunResult), C.POINTER(RefBiasFit)]
     L.vb2_debug_refbias_time.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+    L.vb2_ctx_create_ex.argtypes = [C.POINTER(Input), C.POINTER(Options), C.c_void_p, C.POINTER(C.c_void_p)]
+    L.vb2_errstat_create.argtypes = [C.POINTER(Input), C.POINTER(Options), C.POINTER(C.c_void_p)]
+    L.vb2_errstat_destroy.argtypes = [C.c_void_p]
+    L.vb2_errstat_destroy.restype = None
+    L.vb2_errstat_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.vb2_errstat_info_get.argtypes = [C.c_void_p, C.POINTER(ErrStatInfo)]
+    L.vb2_errfit_input.argtypes = [C.POINTER(Input), C.POINTER(Options), C.POINTER(Model), C.POINTER(Estimate), C.POINTER(ErrFitOpts),
+                                   C.POINTER(ErrFit)]
+    L.vb2_errfit_lockstep.argtypes = [C.POINTER(ErrFitFns), C.c_void_p, C.c_int32, C.POINTER(Model), C.c_int32, C.POINTER(Estimate),
+                                      C.POINTER(ErrFitOpts), C.POINTER(ErrFit)]
+    L.vb2_run_errfit.argtypes = [C.POINTER(RunArgs), C.POINTER(ErrFitOpts), C.POINTER(RunResult), C.POINTER(ErrFit)]
     L.vb2_debug_paired_time.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     L.vb2_debug_paired_derivs_time.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     L.vb2_debug_replicates_time.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]

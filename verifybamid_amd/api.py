@@ -162,6 +162,19 @@ def _estimate_dict(est, k):
                 converged=bool(est.converged))
 
 
+def _err_table(err_table):
+    e = np.ascontiguousarray(np.asarray(err_table, dtype=np.float64).reshape(-1))
+    if e.shape != (_abi.VB2_ERR_NUM_QUAL,):
+        raise ValueError("an error table has %d entries, one per clamped quality" % _abi.VB2_ERR_NUM_QUAL)
+    return e
+
+
+def nominal_err_table():
+    """The reference's pErr per clamped quality 0..93, pow(10.0, q / -10.0) (ContaminationEstimator.h:65-74)."""
+    import math
+    return np.array([math.pow(10.0, q / -10.0) for q in range(_abi.VB2_ERR_NUM_QUAL)])
+
+
 class _TraceBuf:
     def __init__(self, capacity, k):
         self.bufs = dict(alpha=np.zeros(capacity), pc1=np.zeros((capacity, k)),
@@ -178,7 +191,8 @@ class _TraceBuf:
 class LikelihoodContext:
     """vb2_ctx: the pileup + panel resident in HBM, ready for batched evaluation."""
 
-    def __init__(self, data: PileupData, device=-1, stream=None, cohort_layout=False):
+    def __init__(self, data: PileupData, device=-1, stream=None, cohort_layout=False, err_table=None):
+        """err_table: [94] error rates per clamped quality in place of 10^(-q/10) (vb2_ctx_create_ex)."""
         self._lib = _abi.lib()
         self.data = data
         self.num_pc = data.num_pc
@@ -186,7 +200,11 @@ class LikelihoodContext:
         opt = _abi.Options(int(device), 1 if cohort_layout else 0,      # VB2_OPT_COHORT_LAYOUT
                            C.c_void_p(stream) if stream else None)
         h = C.c_void_p()
-        _abi.check(self._lib.vb2_ctx_create(C.byref(inp), C.byref(opt), C.byref(h)), "vb2_ctx_create")
+        if err_table is None:
+            _abi.check(self._lib.vb2_ctx_create(C.byref(inp), C.byref(opt), C.byref(h)), "vb2_ctx_create")
+        else:
+            e = _err_table(err_table)
+            _abi.check(self._lib.vb2_ctx_create_ex(C.byref(inp), C.byref(opt), _p(e), C.byref(h)), "vb2_ctx_create_ex")
         self._h = h
 
     def close(self):
@@ -838,6 +856,128 @@ def refbias_with_evaluator(evaluate, num_pc, known_af=False, **model_kw):
     return _refbias_fit_dict(f, k)
 
 
+class ErrStat:
+    """vb2_errstat: the E-step of the error-rate fit on a device copy of the raw sample -- per clamped quality the reads of
+    the counted markers and the expected number of error reads among them, at one point under one error table."""
+
+    def __init__(self, data: PileupData, device=-1, stream=None):
+        self._lib = _abi.lib()
+        self.data = data
+        self.num_pc = data.num_pc
+        inp = data.as_input()
+        opt = _abi.Options(int(device), 0, C.c_void_p(stream) if stream else None)
+        h = C.c_void_p()
+        _abi.check(self._lib.vb2_errstat_create(C.byref(inp), C.byref(opt), C.byref(h)), "vb2_errstat_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.vb2_errstat_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def info(self):
+        i = _abi.ErrStatInfo()
+        _abi.check(self._lib.vb2_errstat_info_get(self._h, C.byref(i)), "vb2_errstat_info_get")
+        return dict(num_marker=i.num_marker, num_pc=i.num_pc, num_read=int(i.num_read), device_bytes=int(i.device_bytes),
+                    num_launch=int(i.num_launch))
+
+    def eval(self, err_table, pc1, pc2, alpha):
+        """vb2_errstat_eval: (n [94] int64, s [94], llk) at (pc1 [k], pc2 [k], alpha) under err_table [94]."""
+        e = _err_table(err_table)
+        pc1 = np.ascontiguousarray(np.asarray(pc1, dtype=np.float64).reshape(-1))
+        pc2 = np.ascontiguousarray(np.asarray(pc2, dtype=np.float64).reshape(-1))
+        assert pc1.shape == (self.num_pc,) and pc2.shape == (self.num_pc,)
+        n, s, llk = np.zeros(_abi.VB2_ERR_NUM_QUAL, dtype=np.int64), np.zeros(_abi.VB2_ERR_NUM_QUAL), C.c_double(0.0)
+        _abi.check(self._lib.vb2_errstat_eval(self._h, _p(e), _p(pc1), _p(pc2), float(alpha), _p(n), _p(s), C.byref(llk)),
+                   "vb2_errstat_eval")
+        return n, s, llk.value
+
+
+def _errfit_opts(prior_reads=0.0, tol=0.0, max_iter=0):
+    return _abi.ErrFitOpts(float(prior_reads), float(tol), int(max_iter), 0)
+
+
+def _errfit_dict(f, k):
+    t = int(f.num_iter)
+    return dict(err=np.array(f.err[:]), n=np.array(f.n[:], dtype=np.int64), s=np.array(f.s[:]),
+                estimate=_estimate_dict(f.est, k), alpha_fit=f.est.alpha, freemix_fit=min(f.est.alpha, 1 - f.est.alpha),
+                llk_fit=f.llk_fit, llk_nominal=f.llk_nominal, alpha_nominal=f.alpha_nominal, lrt=f.lrt,
+                num_bin=int(f.num_bin), num_iter=t, converged=bool(f.converged), num_step=int(f.num_step), status=int(f.status),
+                iter_llk=np.array(f.iter_llk[:t]), iter_change=np.array(f.iter_change[:t]), iter_alpha=np.array(f.iter_alpha[:t]),
+                iter_err=np.array([list(f.iter_err[i]) for i in range(t)], dtype=np.float32).reshape(t, _abi.VB2_ERR_NUM_QUAL))
+
+
+def errfit(data: PileupData, nominal, device=-1, prior_reads=0.0, tol=0.0, max_iter=0, **model_kw):
+    """vb2_errfit_input: the error rates per quality fitted jointly with the model's parameters on the device, starting
+    from `nominal`, the estimate of optimize(**model_kw) on a context of `data`.  Returns err, n, s [94], estimate (the final
+    search), llk_fit, llk_nominal, lrt, num_bin, num_iter, converged and the per-iteration iter_llk, iter_change, iter_alpha,
+    iter_err."""
+    m, keep = _model(known_af=data.known_af is not None, **model_kw)
+    inp = data.as_input()
+    opt = _abi.Options(int(device), 0, None)
+    est = _estimate_struct(nominal, data.num_pc)
+    o = _errfit_opts(prior_reads, tol, max_iter)
+    f = _abi.ErrFit()
+    _abi.check(_abi.lib().vb2_errfit_input(C.byref(inp), C.byref(opt), C.byref(m), C.byref(est), C.byref(o), C.byref(f)),
+               "vb2_errfit_input")
+    del keep
+    return _errfit_dict(f, data.num_pc)
+
+
+def errfit_with_evaluator(evaluate, stats, num_pc, nominal, known_af=False, prior_reads=0.0, tol=0.0, max_iter=0, **model_kw):
+    """The same fit over two Python callbacks (vb2_errfit_lockstep): no device.
+    evaluate(err [94], pc1 [B, k], pc2 [B, k], alpha [B]) -> llk [B] answers the searches;
+    stats(err [94], pc1 [k], pc2 [k], alpha) -> (n [94], s [94]) is the E-step.  Returns the dict of errfit."""
+    k = int(num_pc)
+    Q = _abi.VB2_ERR_NUM_QUAL
+    err = []
+
+    def cb_eval(_user, e, n, p1, p2, a, out):
+        try:
+            table = np.ctypeslib.as_array(e, (Q,)).copy()
+            pc1 = np.ctypeslib.as_array(p1, (n, k)).copy()
+            pc2 = np.ctypeslib.as_array(p2, (n, k)).copy()
+            al = np.ctypeslib.as_array(a, (n,)).copy()
+            np.ctypeslib.as_array(out, (n,))[:] = np.asarray(evaluate(table, pc1, pc2, al), dtype=np.float64).reshape(n)
+            return 0
+        except Exception as exc:   # never let an exception cross the C boundary
+            err.append(exc)
+            return _abi.VB2_ERR_INVALID
+
+    def cb_stats(_user, e, p1, p2, a, n_out, s_out):
+        try:
+            table = np.ctypeslib.as_array(e, (Q,)).copy()
+            pc1 = np.ctypeslib.as_array(p1, (k,)).copy()
+            pc2 = np.ctypeslib.as_array(p2, (k,)).copy()
+            n, s = stats(table, pc1, pc2, float(a))
+            np.ctypeslib.as_array(n_out, (Q,))[:] = np.asarray(n, dtype=np.int64).reshape(Q)
+            np.ctypeslib.as_array(s_out, (Q,))[:] = np.asarray(s, dtype=np.float64).reshape(Q)
+            return 0
+        except Exception as exc:
+            err.append(exc)
+            return _abi.VB2_ERR_INVALID
+    fns = _abi.ErrFitFns(_abi.ERRFIT_EVAL_FN(cb_eval), _abi.ERRFIT_STATS_FN(cb_stats))
+    m, keep = _model(known_af=known_af, **model_kw)
+    est = _estimate_struct(nominal, k)
+    o = _errfit_opts(prior_reads, tol, max_iter)
+    f = _abi.ErrFit()
+    rc = _abi.lib().vb2_errfit_lockstep(C.byref(fns), None, k, C.byref(m), int(bool(known_af)), C.byref(est), C.byref(o),
+                                        C.byref(f))
+    del keep
+    if err:
+        raise err[0]
+    _abi.check(rc, "vb2_errfit_lockstep")
+    return _errfit_dict(f, k)
+
+
 class Paired(_RowSet):
     """vb2_paired: the likelihood of the ONE resident sample given genotype priors on BOTH components -- per hypothesis two
     float32 triples per panel marker, pi1 for the contaminant and pi2 for the intended sample; an all-zero triple falls back
@@ -1215,7 +1355,7 @@ def _set_bam(args, bam_path, mpileup, apply_baq=False, reference_path=None):
 def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_sanity=False,
               known_af_path=None, device=-1, output_pileup=False, devices=None, confidence_interval=False,
               per_chromosome=False, bootstrap=0, bam_path=None, mpileup=None, per_read_group=False, ref_bias=False,
-              apply_baq=False, reference_path=None, **model_kw):
+              apply_baq=False, reference_path=None, fit_error=False, error_prior=0.0, **model_kw):
     """The --SVDPrefix/--PileupFile flow of execute() (vb2_run); devices=[a, b, ...] shards the
     sample's markers over those GPUs.  confidence_interval: vb2_run_interval (<output_prefix>.CI, and an
     `interval` entry in the result).  per_chromosome / bootstrap=N (seeded by seed=): vb2_run_replicates
@@ -1227,7 +1367,9 @@ def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_san
     the estimate's entries (zero when not searched) and num_site, num_bases, avg_depth.
     ref_bias: vb2_run_refbias (<output_prefix>.RefBias, and a `ref_bias` entry in the result: the dict of RefBias.fit).
     apply_baq (with bam_path and reference_path, the FASTA with its .fai): --ApplyBAQ -- the Illumina shift, base alignment
-    quality and the mapping-quality cap the pileup options ask for are applied to the records before the pileup."""
+    quality and the mapping-quality cap the pileup options ask for are applied to the records before the pileup.
+    fit_error: vb2_run_errfit (<output_prefix>.ErrorFit and .ErrorRates, and an `error_fit` entry in the result: the dict of
+    errfit); error_prior: the nominal rate's weight in pseudo-reads per quality, 0 = 100."""
     args, keep = _run_args(svd_prefix, pileup_path, num_pc, disable_sanity, known_af_path,
                            output_prefix, device, output_pileup, devices=devices, **model_kw)
     _set_bam(args, bam_path, mpileup, apply_baq, reference_path)
@@ -1236,7 +1378,15 @@ def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_san
     summary = None
     groups = None
     bias = None
-    if ref_bias:
+    efit = None
+    if fit_error:
+        if confidence_interval or per_chromosome or bootstrap or per_read_group or ref_bias:
+            raise ValueError("fit_error cannot be combined with confidence_interval, per_chromosome, bootstrap, per_read_group "
+                             "or ref_bias")
+        efit = _abi.ErrFit()
+        o = _errfit_opts(prior_reads=error_prior)
+        _abi.check(_abi.lib().vb2_run_errfit(C.byref(args), C.byref(o), C.byref(res), C.byref(efit)), "vb2_run_errfit")
+    elif ref_bias:
         if confidence_interval or per_chromosome or bootstrap or per_read_group:
             raise ValueError("ref_bias cannot be combined with confidence_interval, per_chromosome, bootstrap or per_read_group")
         bias = _abi.RefBiasFit()
@@ -1279,6 +1429,8 @@ def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_san
         out["read_groups"] = groups
     if bias is not None:
         out["ref_bias"] = _refbias_fit_dict(bias, num_pc)
+    if efit is not None:
+        out["error_fit"] = _errfit_dict(efit, num_pc)
     out.update(num_marker=res.num_marker, num_site=res.num_site, num_bases=int(res.num_bases),
                avg_depth=res.avg_depth, sd_depth=res.sd_depth, seconds_load=res.seconds_load,
                seconds_optimize=res.seconds_optimize)

@@ -36,6 +36,11 @@
 // --RefBias estimates the reference bias beta -- the share of REF among the error-free reads of a heterozygous genotype,
 // 0.5 in the model -- jointly with FREEMIX and writes <Output>.RefBias (vb2_run_refbias; one sample,
 // one device, a searched alpha).
+// --FitError [--ErrorPrior k] fits the error rate of every reported base quality jointly with FREEMIX, in place of the
+// model's 10^(-q/10), and writes <Output>.ErrorFit and <Output>.ErrorRates (vb2_run_errfit); k is the
+// weight of the nominal rate in pseudo-reads per quality (default 100).  With --PileupFile or --BamFile; one sample, one
+// device, a searched alpha, the reference's own search: not with --PileupList, --PerReadGroup, --FixAlpha,
+// --ConfidenceInterval, --PerChromosome, --Bootstrap, --RefBias, --NumStart, --LineSearch or several --Devices.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -122,6 +127,8 @@ int main(int argc, char** argv)
     bool perReadGroup = false;
     bool applyBAQ = false;
     bool refBias = false;
+    bool fitError = false;
+    double errorPrior = 100.0;
     // "Pileup Options" (main.cpp:176-187), defaults main.cpp:81-96 (MPLP_REALN | MPLP_SMART_OVERLAPS; UNMAP | SECONDARY |
     // QCFAIL | DUP): they shape what --BamFile input becomes and, as in the reference, do nothing to --PileupFile input
     int minBQ = 13, minMQ = 2, adjustMQ = 40, maxDepth = 8000, inclFlags = (1 << 4) | (1 << 10), exclFlags = 0x4 | 0x100 | 0x200 | 0x400;
@@ -209,6 +216,10 @@ int main(int argc, char** argv)
         // not in the reference (VerifyBamID 1 had --free-refBias): the reference bias of the read model estimated jointly with
         // FREEMIX by profile likelihood, 28 refits of the one resident sample in lock-step (vb2_run_refbias), to <Output>.RefBias
         {"RefBias", {Flag::kBool, &refBias, false}},
+        // not in the reference: the error rate per reported base quality fitted jointly with FREEMIX (vb2_run_errfit), to
+        // <Output>.ErrorFit and <Output>.ErrorRates; --ErrorPrior: pseudo-reads at the nominal rate per quality
+        {"FitError", {Flag::kBool, &fitError, false}},
+        {"ErrorPrior", {Flag::kDouble, &errorPrior, false}},
     };
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
@@ -239,6 +250,24 @@ int main(int argc, char** argv)
         if (f.kind == Flag::kInt) *static_cast<int*>(f.dst) = std::atoi(v);
         else if (f.kind == Flag::kDouble) *static_cast<double*>(f.dst) = std::atof(v);
         else *static_cast<std::string*>(f.dst) = v;
+    }
+    if (fitError) {                                                     // one sample, one device, a searched alpha, the plain search
+        if (PileupList != "Empty")
+            fatal("--FitError cannot be combined with --PileupList: the error rates are fitted for one sample per run");
+        if (perReadGroup) fatal("--FitError cannot be combined with --PerReadGroup: run them separately");
+        if (flags["FixAlpha"].seen)
+            fatal("--FitError cannot be combined with --FixAlpha: a fixed alpha leaves the fit nothing to tell errors from");
+        if (confidenceInterval) fatal("--FitError cannot be combined with --ConfidenceInterval: run them separately");
+        if (perChromosome) fatal("--FitError cannot be combined with --PerChromosome: run them separately");
+        if (flags["Bootstrap"].seen) fatal("--FitError cannot be combined with --Bootstrap: run them separately");
+        if (refBias) fatal("--FitError cannot be combined with --RefBias: the two fits are not estimated jointly; run them separately");
+        if (flags["NumStart"].seen) fatal("--FitError cannot be combined with --NumStart: every iteration's search is the reference's own");
+        if (lineSearch) fatal("--FitError cannot be combined with --LineSearch: every iteration's search is the reference's own");
+        if (Devices != "Empty" && Devices.find(',') != std::string::npos)
+            fatal("--FitError cannot be combined with more than one --Devices: the fit reads one resident sample on one device");
+        if (!(errorPrior > 0.0)) fatal("--ErrorPrior takes a positive number of pseudo-reads");
+    } else if (flags["ErrorPrior"].seen) {
+        fatal("--ErrorPrior needs --FitError");
     }
     if (refBias) {                                                      // one sample, one device, a searched alpha
         if (PileupList != "Empty")
@@ -547,7 +576,11 @@ int main(int argc, char** argv)
     vb2_run_result res;
     vb2_interval ci;
     int32_t numGroup = 0;
-    const int rc = refBias                          ? vb2_run_refbias(&args, &res, nullptr)
+    vb2_errfit_opts fitOpts;
+    std::memset(&fitOpts, 0, sizeof(fitOpts));
+    fitOpts.prior_reads = errorPrior;
+    const int rc = fitError                         ? vb2_run_errfit(&args, &fitOpts, &res, nullptr)
+                   : refBias                        ? vb2_run_refbias(&args, &res, nullptr)
                    : perReadGroup                   ? vb2_run_read_groups(&args, &res, 0, nullptr, &numGroup)
                    : (perChromosome || bootstrap > 0) ? vb2_run_replicates(&args, perChromosome ? 1 : 0, bootstrap, &res, nullptr)
                    : confidenceInterval             ? vb2_run_interval(&args, &res, &ci)

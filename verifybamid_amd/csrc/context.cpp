@@ -465,11 +465,12 @@ struct FlattenTables {
     // (max_bound): see settle_modes.
     double lhet[kNumQual];                   // [rank]
 };
-std::unique_ptr<FlattenTables> make_tables(const vb2_input* in, const Reads& rd)
+// err_table: the caller's error rate per quality (vb2_ctx_create_ex) in place of the reference's; everything below reads phred
+std::unique_ptr<FlattenTables> make_tables(const vb2_input* in, const Reads& rd, const double* err_table)
 {
     std::unique_ptr<FlattenTables> tp(new FlattenTables);
     FlattenTables& T = *tp;
-    for (int i = 0; i < kNumQual; ++i) T.phred[i] = std::pow(10.0, i / -10.0);
+    for (int i = 0; i < kNumQual; ++i) T.phred[i] = err_table ? err_table[i] : std::pow(10.0, i / -10.0);
     // log c[class][q][g], c = E[g][class]*pErr + N[g][class]*pOk: the alpha-free
     // value of the table entry for g1 == g2 (and for class "other", any g1,g2).
     std::vector<double> logc(3 * kNumQual * 3);
@@ -1902,17 +1903,23 @@ int flatten_dry_run(const vb2_input* in, double* ms)
     return rc;
 }
 
-int Context::create(const vb2_input* in, const vb2_options* opt, Context** out)
+int Context::create(const vb2_input* in, const vb2_options* opt, Context** out, const double* err_table)
 {
-    return create_impl(in, opt, out, nullptr);
+    return create_impl(in, opt, out, nullptr, err_table);
 }
 
 // dry_run: the host half only (classification, dictionary, run packing into plain memory) -- no HIP
 // call, nothing returned but, if asked for, the digest; tools/ubench/host_pipeline.cpp times it where there is no GPU
-int Context::create_impl(const vb2_input* in, const vb2_options* opt, Context** out, const DryRun* dry_run)
+int Context::create_impl(const vb2_input* in, const vb2_options* opt, Context** out, const DryRun* dry_run, const double* err_table)
 {
     *out = nullptr;
     if (const int rc = check_input(in)) return rc;
+    if (err_table)
+        for (int q = 0; q < kNumQual; ++q)
+            if (!(err_table[q] >= 0.0 && err_table[q] <= 1.0)) {      // (false for a NaN)
+                set_error("vb2_ctx_create_ex: the error rate of quality " + std::to_string(q) + " lies outside [0, 1]");
+                return VB2_ERR_INVALID;
+            }
     std::unique_ptr<Context> c(new Context());
     Device dv;
     if (const int rc = open_device(opt, dry_run != nullptr, c.get(), &dv)) return rc;
@@ -1927,7 +1934,7 @@ int Context::create_impl(const vb2_input* in, const vb2_options* opt, Context** 
     // what does not depend on the reads, or on a sample of them only
     if (const int rc = check_read_offsets(in)) return rc;
     const Reads rd = read_span(in);
-    const std::unique_ptr<FlattenTables> tables = make_tables(in, rd);
+    const std::unique_ptr<FlattenTables> tables = make_tables(in, rd, err_table);
     Modes md = plan_modes(in, rd.total, tn, dry_run != nullptr);
     int nthr = flatten_thread_count(rd.total, tn);
     if (md.device_flatten) nthr = 1;     // (what is left for the host -- three words per sorted marker -- is not worth a thread's start)

@@ -96,8 +96,10 @@ public:
     std::mutex cohort_mu_;
     std::vector<uint32_t> h_mt_rows;         // rows per micro-tile (host copy: the schedules are built from it)
     std::vector<uint32_t> h_mt_rec_y;        // probability domain: a tile's {ref steps | all steps << 16} (ensure_codes16: the 8-bit lists)
-    static int create(const vb2_input* in, const vb2_options* opt, Context** out);
-    static int create_impl(const vb2_input* in, const vb2_options* opt, Context** out, const DryRun* dry_run);   // null: a real create
+    // err_table (vb2_ctx_create_ex): [kNumQual] error rates per clamped quality in place of 10^(-q/10), or null
+    static int create(const vb2_input* in, const vb2_options* opt, Context** out, const double* err_table = nullptr);
+    static int create_impl(const vb2_input* in, const vb2_options* opt, Context** out, const DryRun* dry_run,   // null: a real create
+                           const double* err_table = nullptr);
     // device pointers, asynchronous on s (nullptr = own stream)
     int eval_device(int num_point, const double* d_points, double* d_llk, hipStream_t s,
                     unsigned long long* done_flag = nullptr, unsigned long long done_seq = 0,

@@ -73,7 +73,9 @@ namespace vb2 {
     X(bam_threads, 0)      /* host threads that inflate and walk: 0 = min(cpus, 16); --NumThread above 4 sets it */   \
     X(bam_inflate, 0)      /* the planned BGZF blocks of a load: 0 zlib on the host pool, 1 bgzf_inflate_kernel (zlib for what it refuses) */ \
     X(baq_lds_kb, 64)      /* --ApplyBAQ: KiB of LDS per workgroup of baq_kernel (four records share them), at most 80: two workgroups a CU */ \
-    X(cohort_bam_inflight, 4) /* .bam lines of a cohort between "file opened" and "context created" at once, per device */
+    X(cohort_bam_inflight, 4) /* .bam lines of a cohort between "file opened" and "context created" at once, per device */ \
+    /* ---- the error-rate fit (errstat.cpp) ---- */                                                                    \
+    X(errstat_groups, 0)   /* workgroups of errstat_marker_kernel: 0 = four per CU; the results are the same bits */
 
 struct Tunables {
 #define VB2_X(name, dflt) int name = dflt;

@@ -1013,6 +1013,37 @@ typedef struct vb2_errstat_info {
 } vb2_errstat_info;
 int vb2_errstat_info_get(const vb2_errstat *set, vb2_errstat_info *info);
 
+/* The E-step of up to VB2_ERRSTAT_BATCH_MAX samples in one launch pair: a set holds the RAW inputs
+ * of all of them on one device.  in [num_sample]; a NULL in[s] is a sample that holds nothing (one that failed its own run).
+ * Inputs whose ud and means pointers -- or known_af pointers -- are equal, with equal num_marker and num_pc, share one
+ * device copy: the samples of a cohort share the panel.  The inputs are not referenced after the call returns. */
+#define VB2_ERRSTAT_BATCH_MAX 64
+typedef struct vb2_errstat_batch vb2_errstat_batch;
+int vb2_errstat_batch_create(const vb2_input *const *in, int32_t num_sample, const vb2_options *opt, vb2_errstat_batch **out);
+void vb2_errstat_batch_destroy(vb2_errstat_batch *set);
+/* Every live sample at its own point under its own table: live [S] (NULL: all), err_tables [S][94] (a pooled fit passes the
+ * same table S times), pc1 / pc2 [S][num_pc] with num_pc the set's (vb2_errstat_batch_info: the largest of the samples'; a
+ * sample reads its own first entries; NULL where every live sample has known allele frequencies), alpha [S]; n_out [S][94],
+ * s_out [S][94], llk_out [S], any of which may be NULL.  For every live sample the three are BIT FOR BIT what
+ * vb2_errstat_eval returns for that sample alone at the same point and table, whatever the other samples of the call.  A
+ * sample that is not live, was NULL, or has num_marker == 0 takes no workgroup and reads zeros and llk 0.  A bad table, or
+ * an alpha outside [0, 1], of a live sample is VB2_ERR_INVALID; what belongs to a sample that is not live is not read.
+ * Synchronous; host pointers. */
+int vb2_errstat_batch_eval(vb2_errstat_batch *set, const int32_t *live, const double *err_tables, const double *pc1,
+                           const double *pc2, const double *alpha, int64_t *n_out, double *s_out, double *llk_out);
+typedef struct vb2_errstat_batch_info {
+    int32_t num_sample;
+    int32_t num_pc;            /* the largest num_pc of the samples: the row stride of pc1 / pc2        */
+    int32_t num_panel;         /* device copies of (ud, means) or known_af the samples share            */
+    int32_t last_grid;         /* workgroups of the last evaluation's marker kernel                     */
+    int64_t num_marker;        /* summed over the samples                                               */
+    int64_t num_read;
+    int64_t device_bytes;      /* device memory the set holds                                           */
+    int64_t num_launch;        /* kernel launches so far (two per evaluation with a live sample)        */
+    int64_t num_eval;          /* evaluations so far                                                    */
+} vb2_errstat_batch_info;
+int vb2_errstat_batch_info_get(const vb2_errstat_batch *set, vb2_errstat_batch_info *info);
+
 /* The fit: alternating maximisation of the likelihood penalised by a Beta prior of prior_reads pseudo-reads centred on
  * the nominal rate of every quality.
  *   start      eps_0 = eps0, est_0 = `nominal` (the run's own estimate);
@@ -1058,6 +1089,87 @@ typedef struct vb2_errfit_fns {
 } vb2_errfit_fns;
 int vb2_errfit_lockstep(const vb2_errfit_fns *fns, void *user, int32_t num_pc, const vb2_model *model, int32_t data_has_known_af,
                         const vb2_estimate *nominal, const vb2_errfit_opts *fit_opts, vb2_errfit *out);
+/* The fit of a cohort: the procedure above for up to VB2_ERRSTAT_BATCH_MAX samples in lock-step.
+ * Each step is one batched E-step of the samples still fitting (vb2_errstat_batch_eval), fresh contexts under the new tables
+ * (vb2_ctx_create_ex) and one vb2_batch_optimize_llk over them.
+ *   per sample (pooled = 0)  every sample runs the procedure unchanged on its own table and leaves when it converges or
+ *              reaches max_iter: fits[s] is what vb2_errfit_input gives on the sample alone (tables, n, iterations and
+ *              convergence equal; what comes out of a search to the searches' own agreement);
+ *   pooled     ONE table for all.  start: eps_0 = eps0, every sample at its own nominal estimate; iteration: (n_s, s_s)
+ *              of every sample still in at (est_s,t, eps_t); N[q] = sum n_s[q] in integers, SUM[q] = the s_s[q] added in
+ *              list order; eps_{t+1}[q] = (float)((SUM[q] + kappa eps0[q]) / (N[q] + kappa)) where N[q] > 0, eps0[q]
+ *              elsewhere -- kappa is NOT scaled by the number of samples --; then the search of every sample under
+ *              eps_{t+1}; stop: the rule above on the pooled table; report: one more E-step.  fits[s]: err the pooled
+ *              table, n / s the sample's own at the end, iter_err / iter_change the pool's, iter_alpha / iter_llk its own.
+ * A sample whose enter_status is not VB2_OK (its own run failed) never enters and keeps that code as fits[s].status, the
+ * rest of fits[s] zeros and NaNs.  A sample whose context or search fails under a table gets that code as its status, is in
+ * no later sum, and the others go on.  With one sample, pooled is the single-sample fit exactly. */
+typedef struct vb2_errfit_pool {
+    double err[VB2_ERR_NUM_QUAL];      /* pooled: the fitted table; per sample: the nominal one                         */
+    int64_t n[VB2_ERR_NUM_QUAL];       /* the reported samples' final n summed,                                         */
+    double s[VB2_ERR_NUM_QUAL];        /* ... and their s, added in list order                                          */
+    double iter_change[VB2_ERRFIT_MAX_ITER];                     /* pooled only: the stop rule's maximum, and           */
+    float iter_err[VB2_ERRFIT_MAX_ITER][VB2_ERR_NUM_QUAL];       /* eps_{t+1}                                            */
+    double lrt_sum;                    /* the reported samples' lrt summed                                              */
+    double seconds_stats, seconds_context, seconds_search;       /* vb2_errfit_cohort_inputs: where the time went       */
+    int64_t num_step;                  /* likelihood evaluations of all searches                                        */
+    int64_t device_bytes;              /* vb2_errfit_cohort_inputs: what the batched E-step's set held                  */
+    int32_t num_bin;                   /* qualities with reads in n                                                     */
+    int32_t num_iter;                  /* iterations run (per sample: the longest fit's)                                */
+    int32_t converged;                 /* pooled: the pooled table's; per sample: every reported sample converged       */
+    int32_t pooled;
+    int32_t num_sample, num_entered, num_fitted;                 /* given; enter_status VB2_OK; reported                 */
+    int32_t num_estep;                 /* batched E-steps                                                               */
+} vb2_errfit_pool;
+/* on the device `opt` names; the samples that enter have one num_pc and known allele frequencies all or none; nominal,
+ * enter_status (or NULL: all enter), fits: [num_sample] */
+int vb2_errfit_cohort_inputs(const vb2_input *const *in, int32_t num_sample, const vb2_options *opt, const vb2_model *model,
+                             const vb2_estimate *nominal, const int32_t *enter_status, const vb2_errfit_opts *fit_opts,
+                             int32_t pooled, vb2_errfit *fits, vb2_errfit_pool *pool);
+/* The same procedure over a caller's two callbacks: no device needed.  eval answers the searches of sample `sample` (the
+ * seam of vb2_optimize_llk with the sample and its table in front; non-zero fails that sample's search); stats is the
+ * batched E-step with vb2_errstat_batch_eval's arrays (pc1 / pc2 [num_sample][num_pc]); non-zero from it ends the fit. */
+typedef struct vb2_errfit_cohort_fns {
+    int (*eval)(void *user, int32_t sample, const double *err_table, int32_t num_point, const double *pc1, const double *pc2,
+                const double *alpha, double *llk_out);
+    int (*stats)(void *user, int32_t num_sample, const int32_t *live, const double *err_tables, const double *pc1,
+                 const double *pc2, const double *alpha, int64_t *n_out, double *s_out);
+} vb2_errfit_cohort_fns;
+int vb2_errfit_cohort_lockstep(const vb2_errfit_cohort_fns *fns, void *user, int32_t num_sample, int32_t num_pc,
+                               const vb2_model *model, int32_t data_has_known_af, const vb2_estimate *nominal,
+                               const int32_t *enter_status, const vb2_errfit_opts *fit_opts, int32_t pooled, vb2_errfit *fits,
+                               vb2_errfit_pool *pool);
+
+/* vb2_cohort_run, then the fit of the cohort (--PileupList L --CohortFitError [--PooledError]): an after-run stage that takes
+ * every searched sample's flattened input as it retires (the readers leave the raw arrays in it) and then runs
+ * vb2_errfit_cohort_inputs in chunks of at most VB2_ERRSTAT_BATCH_MAX samples, the run's own estimates the nominal ones, a
+ * sample's own status its enter_status.  Per sample (pooled = 0): <prefix>.ErrorFit and <prefix>.ErrorRates of every fitted
+ * sample, in vb2_run_errfit's formats.  Pooled: <output_prefix>.ErrorRates in the same format (READS = N, SE_BINOM from N)
+ * and <output_prefix>.PooledFit, a header and one row per sample of the list:
+ *     #SEQ_ID FREEMIX FREEMIX_FIT LRT FREELK1_FIT FREELK1_NOMINAL STATUS
+ * ("NA" where a sample was not fitted; STATUS: the code it left with; SEQ_ID of a sample that failed its own run: its pileup
+ * path).  One NOTICE line on stderr.  stdout, .selfSM and .Ancestry are what vb2_cohort_run writes, byte for byte; out and
+ * status are its own.  fits [num_sample] and pooled_out may be NULL (pooled_out: the last chunk's).  VB2_ERR_INVALID before
+ * any file is read: more than one device, is_alpha_fixed, --NumStart / --LineSearch, bad fit options, pooled with more than
+ * VB2_ERRSTAT_BATCH_MAX samples.  Raw inputs that do not fit the device fail the stage (VB2_ERR_NOMEM, the byte counts in
+ * the message) before any of them goes up. */
+int vb2_cohort_run_errfit(const vb2_cohort_args *args, const vb2_errfit_opts *fit_opts, int32_t pooled, vb2_run_result *out,
+                          int32_t *status, vb2_errfit *fits, vb2_errfit_pool *pooled_out);
+
+/* --ErrorTable F: a fitted table applied to other runs.  vb2_err_table_read reads a file in the format of .ErrorRates --
+ * a tab-separated header that names at least the columns #Q_REPORTED and ERROR_RATE, then a row per quality -- into
+ * err_table [VB2_ERR_NUM_QUAL]: the file's rate of every quality it lists (*num_taken of them; may be NULL), the nominal
+ * pow(10.0, q / -10.0) of the others.  VB2_ERR_INVALID, the message naming the line (1 = the header): a file that cannot be
+ * opened, a missing column, too few fields, a quality that is no whole number within 0..93 or listed twice, a rate that
+ * is no number, a NaN or outside [0, 1].  No device is touched.
+ * vb2_run_under_table is vb2_run, and vb2_cohort_run_under_table is vb2_cohort_run, with every context made by
+ * vb2_ctx_create_ex under err_table and nothing else changed: the same files, the same stdout; with the nominal table the
+ * same bytes.  A bad table is VB2_ERR_INVALID before any file is read; vb2_run_under_table takes one device (no marker
+ * shards). */
+int vb2_err_table_read(const char *path, double *err_table, int32_t *num_taken);
+int vb2_run_under_table(const vb2_run_args *args, const double *err_table, vb2_run_result *out);
+int vb2_cohort_run_under_table(const vb2_cohort_args *args, const double *err_table, vb2_run_result *out, int32_t *status);
+
 /* vb2_run, then the fit on the run's input under the run's model, the run's estimate the nominal one; then
  * <output_prefix>.ErrorFit (tab-separated, default ostream formatting):
  *     #SEQ_ID FREEMIX FREEMIX_FIT LRT NUM_BIN FREELK1_FIT FREELK1_NOMINAL ITERATIONS CONVERGED

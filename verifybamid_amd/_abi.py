@@ -277,6 +277,14 @@ class ErrStatInfo(C.Structure):
                 ("num_launch", C.c_int64)]
 
 
+class ErrStatBatchInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("num_sample", "num_pc", "num_panel", "last_grid")] + \
+               [(n, C.c_int64) for n in ("num_marker", "num_read", "device_bytes", "num_launch", "num_eval")]
+
+
+VB2_ERRSTAT_BATCH_MAX = 64
+
+
 class ErrFitOpts(C.Structure):
     _fields_ = [("prior_reads", C.c_double), ("tol", C.c_double), ("max_iter", C.c_int32), ("reserved", C.c_int32)]
 
@@ -289,6 +297,29 @@ class ErrFit(C.Structure):
                [(n, C.c_double * VB2_ERRFIT_MAX_ITER) for n in ("iter_llk", "iter_change", "iter_alpha")] + \
                [("iter_err", (C.c_float * VB2_ERR_NUM_QUAL) * VB2_ERRFIT_MAX_ITER), ("num_step", C.c_int64)] + \
                [(n, C.c_int32) for n in ("num_bin", "num_iter", "converged", "status")]
+
+
+class ErrFitPool(C.Structure):
+    """vb2_errfit_pool: the pooled summary of a cohort's error-rate fit."""
+    _fields_ = [("err", C.c_double * VB2_ERR_NUM_QUAL), ("n", C.c_int64 * VB2_ERR_NUM_QUAL), ("s", C.c_double * VB2_ERR_NUM_QUAL),
+                ("iter_change", C.c_double * VB2_ERRFIT_MAX_ITER), ("iter_err", (C.c_float * VB2_ERR_NUM_QUAL) * VB2_ERRFIT_MAX_ITER)] + \
+               [(n, C.c_double) for n in ("lrt_sum", "seconds_stats", "seconds_context", "seconds_search")] + \
+               [("num_step", C.c_int64), ("device_bytes", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("num_bin", "num_iter", "converged", "pooled", "num_sample", "num_entered", "num_fitted",
+                                         "num_estep")]
+
+
+# vb2_errfit_cohort_fns.eval: (user, sample, err_table, num_point, pc1, pc2, alpha, llk);
+# .stats: (user, num_sample, live, err_tables, pc1, pc2, alpha, n, s)
+ERRFIT_COHORT_EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double),
+                                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double))
+ERRFIT_COHORT_STATS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                     C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_double))
+
+
+class ErrFitCohortFns(C.Structure):
+    _fields_ = [("eval", ERRFIT_COHORT_EVAL_FN), ("stats", ERRFIT_COHORT_STATS_FN)]
 
 
 class ReplicateSummary(C.Structure):
@@ -332,6 +363,9 @@ SYMBOLS = [
     "vb2_bgzf_inflate", "vb2_bgzf_inflate_stats", "vb2_cohort_bam_stats",
     "vb2_ctx_create_ex", "vb2_errstat_create", "vb2_errstat_destroy", "vb2_errstat_eval", "vb2_errstat_info_get",
     "vb2_errfit_input", "vb2_errfit_lockstep", "vb2_run_errfit",
+    "vb2_errstat_batch_create", "vb2_errstat_batch_destroy", "vb2_errstat_batch_eval", "vb2_errstat_batch_info_get",
+    "vb2_errfit_cohort_inputs", "vb2_errfit_cohort_lockstep", "vb2_cohort_run_errfit",
+    "vb2_err_table_read", "vb2_run_under_table", "vb2_cohort_run_under_table",
 ]
 
 _lib = None
@@ -555,6 +589,21 @@ def lib():
     L.vb2_errstat_destroy.restype = None
     L.vb2_errstat_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
     L.vb2_errstat_info_get.argtypes = [C.c_void_p, C.POINTER(ErrStatInfo)]
+    L.vb2_errstat_batch_create.argtypes = [C.POINTER(C.POINTER(Input)), C.c_int32, C.POINTER(Options), C.POINTER(C.c_void_p)]
+    L.vb2_errstat_batch_destroy.argtypes = [C.c_void_p]
+    L.vb2_errstat_batch_destroy.restype = None
+    L.vb2_errstat_batch_eval.argtypes = [C.c_void_p] * 9
+    L.vb2_errstat_batch_info_get.argtypes = [C.c_void_p, C.POINTER(ErrStatBatchInfo)]
+    L.vb2_err_table_read.argtypes = [C.c_char_p, C.c_void_p, C.POINTER(C.c_int32)]
+    L.vb2_run_under_table.argtypes = [C.POINTER(RunArgs), C.c_void_p, C.POINTER(RunResult)]
+    L.vb2_cohort_run_under_table.argtypes = [C.POINTER(CohortArgs), C.c_void_p, C.POINTER(RunResult), C.POINTER(C.c_int32)]
+    L.vb2_cohort_run_errfit.argtypes = [C.POINTER(CohortArgs), C.POINTER(ErrFitOpts), C.c_int32, C.POINTER(RunResult),
+                                        C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]
+    L.vb2_errfit_cohort_inputs.argtypes = [C.POINTER(C.POINTER(Input)), C.c_int32, C.POINTER(Options), C.POINTER(Model), C.c_void_p,
+                                           C.c_void_p, C.POINTER(ErrFitOpts), C.c_int32, C.c_void_p, C.POINTER(ErrFitPool)]
+    L.vb2_errfit_cohort_lockstep.argtypes = [C.POINTER(ErrFitCohortFns), C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Model), C.c_int32,
+                                             C.c_void_p, C.c_void_p, C.POINTER(ErrFitOpts), C.c_int32, C.c_void_p,
+                                             C.POINTER(ErrFitPool)]
     L.vb2_errfit_input.argtypes = [C.POINTER(Input), C.POINTER(Options), C.POINTER(Model), C.POINTER(Estimate), C.POINTER(ErrFitOpts),
                                    C.POINTER(ErrFit)]
     L.vb2_errfit_lockstep.argtypes = [C.POINTER(ErrFitFns), C.c_void_p, C.c_int32, C.POINTER(Model), C.c_int32, C.POINTER(Estimate),

@@ -169,6 +169,21 @@ def _err_table(err_table):
     return e
 
 
+def read_err_table(path):
+    """vb2_err_table_read: (table [94], the number of qualities the file lists) of a file in .ErrorRates format; the
+    qualities it does not list are nominal.  No device."""
+    table, taken = np.zeros(_abi.VB2_ERR_NUM_QUAL), C.c_int32(0)
+    _abi.check(_abi.lib().vb2_err_table_read(str(path).encode(), _p(table), C.byref(taken)), "vb2_err_table_read")
+    return table, int(taken.value)
+
+
+def _table_of(error_table):
+    """error_table= of run_files / run_cohort_files: a path in .ErrorRates format, or the 94 rates."""
+    if isinstance(error_table, (str, bytes)) or hasattr(error_table, "__fspath__"):
+        return read_err_table(error_table)[0]
+    return _err_table(error_table)
+
+
 def nominal_err_table():
     """The reference's pErr per clamped quality 0..93, pow(10.0, q / -10.0) (ContaminationEstimator.h:65-74)."""
     import math
@@ -901,6 +916,66 @@ class ErrStat:
         return n, s, llk.value
 
 
+class ErrStatBatch:
+    """vb2_errstat_batch: the E-steps of up to 64 samples in one launch pair, every sample at its own point under its own
+    error table.  `samples` is a list of PileupData; None stands for a sample that holds nothing.  Samples whose ud and
+    means (or known_af) are the same arrays share one device copy.  What a sample gets is ErrStat.eval's bits."""
+
+    def __init__(self, samples, device=-1, stream=None):
+        self._lib = _abi.lib()
+        self.samples = list(samples)
+        S = self.num_sample = len(self.samples)
+        self._inputs = [None if d is None else d.as_input() for d in self.samples]
+        ptrs = (C.POINTER(_abi.Input) * max(S, 1))(*[C.POINTER(_abi.Input)() if i is None else C.pointer(i) for i in self._inputs])
+        opt = _abi.Options(int(device), 0, C.c_void_p(stream) if stream else None)
+        h = C.c_void_p()
+        _abi.check(self._lib.vb2_errstat_batch_create(ptrs, S, C.byref(opt), C.byref(h)), "vb2_errstat_batch_create")
+        self._h = h
+        self.num_pc = self.info()["num_pc"]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.vb2_errstat_batch_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def info(self):
+        i = _abi.ErrStatBatchInfo()
+        _abi.check(self._lib.vb2_errstat_batch_info_get(self._h, C.byref(i)), "vb2_errstat_batch_info_get")
+        return {n: int(getattr(i, n)) for n, _ in _abi.ErrStatBatchInfo._fields_}
+
+    def eval(self, err_tables, pc1, pc2, alpha, live=None):
+        """vb2_errstat_batch_eval: (n [S, 94] int64, s [S, 94], llk [S]).  err_tables [S, 94], or [94] for one table shared
+        by all; pc1 / pc2: per sample a vector of its own num_pc entries (a list, or an array [S, num_pc]; None with known
+        allele frequencies throughout); alpha [S]; live [S] or None (all)."""
+        S, Q, k = self.num_sample, _abi.VB2_ERR_NUM_QUAL, self.num_pc
+        e = np.asarray(err_tables, dtype=np.float64)
+        e = np.ascontiguousarray(np.broadcast_to(e, (S, Q)) if e.ndim == 1 else e.reshape(S, Q))
+
+        def rows(pc):
+            if pc is None:
+                return None
+            out = np.zeros((S, k))
+            for i in range(S):
+                v = np.asarray(pc[i], dtype=np.float64).reshape(-1)
+                out[i, :min(k, v.shape[0])] = v[:k]
+            return out
+        p1, p2 = rows(pc1), rows(pc2)
+        a = np.ascontiguousarray(np.asarray(alpha, dtype=np.float64).reshape(S))
+        lv = None if live is None else np.ascontiguousarray(np.asarray(live).reshape(S), dtype=np.int32)
+        n, s, llk = np.zeros((S, Q), dtype=np.int64), np.zeros((S, Q)), np.zeros(S)
+        _abi.check(self._lib.vb2_errstat_batch_eval(self._h, _p(lv), _p(e), _p(p1), _p(p2), _p(a), _p(n), _p(s), _p(llk)),
+                   "vb2_errstat_batch_eval")
+        return n, s, llk
+
+
 def _errfit_opts(prior_reads=0.0, tol=0.0, max_iter=0):
     return _abi.ErrFitOpts(float(prior_reads), float(tol), int(max_iter), 0)
 
@@ -976,6 +1051,106 @@ def errfit_with_evaluator(evaluate, stats, num_pc, nominal, known_af=False, prio
         raise err[0]
     _abi.check(rc, "vb2_errfit_lockstep")
     return _errfit_dict(f, k)
+
+
+def _errfit_pool_dict(p):
+    t = int(p.num_iter) if p.pooled else 0
+    out = {n: int(getattr(p, n)) for n in ("num_step", "device_bytes", "num_bin", "num_iter", "num_sample", "num_entered",
+                                           "num_fitted", "num_estep")}
+    out.update(err=np.array(p.err[:]), n=np.array(p.n[:], dtype=np.int64), s=np.array(p.s[:]), lrt_sum=p.lrt_sum,
+               converged=bool(p.converged), pooled=bool(p.pooled), seconds_stats=p.seconds_stats,
+               seconds_context=p.seconds_context, seconds_search=p.seconds_search, iter_change=np.array(p.iter_change[:t]),
+               iter_err=np.array([list(p.iter_err[i]) for i in range(t)], dtype=np.float32).reshape(t, _abi.VB2_ERR_NUM_QUAL))
+    return out
+
+
+def _cohort_fit_args(nominals, enter_status, k):
+    S = len(nominals)
+    ests = (_abi.Estimate * S)()
+    enter = np.zeros(S, dtype=np.int32) if enter_status is None else np.ascontiguousarray(enter_status, dtype=np.int32).reshape(S)
+    for i, nom in enumerate(nominals):
+        if nom is not None and enter[i] == 0:
+            ests[i] = _estimate_struct(nom, k)
+        elif enter[i] == 0:
+            raise ValueError("sample %d enters the fit and has no nominal estimate" % i)
+    return ests, enter, (_abi.ErrFit * S)(), _abi.ErrFitPool()
+
+
+def errfit_cohort(samples, nominals, pooled=False, enter_status=None, device=-1, prior_reads=0.0, tol=0.0, max_iter=0, **model_kw):
+    """vb2_errfit_cohort_inputs: the error-rate fits of up to 64 samples in lock-step on the device -- every sample on its own
+    table, or (pooled=True) all of them on one.  samples: PileupData of one num_pc (None where enter_status is non-zero);
+    nominals: each sample's own estimate; enter_status [S]: non-zero for a sample whose own run failed -- it never enters.
+    Returns (fits, pool): per sample the dict of errfit (its "status" the code it left with), and the pooled summary."""
+    S = len(samples)
+    held = [d for i, d in enumerate(samples) if d is not None and (enter_status is None or enter_status[i] == 0)]
+    k = held[0].num_pc if held else 1
+    m, keep = _model(known_af=bool(held) and held[0].known_af is not None, **model_kw)
+    inputs = [None if d is None else d.as_input() for d in samples]
+    ptrs = (C.POINTER(_abi.Input) * max(S, 1))(*[C.POINTER(_abi.Input)() if i is None else C.pointer(i) for i in inputs])
+    ests, enter, fits, pool = _cohort_fit_args(nominals, enter_status, k)
+    opt = _abi.Options(int(device), 0, None)
+    o = _errfit_opts(prior_reads, tol, max_iter)
+    _abi.check(_abi.lib().vb2_errfit_cohort_inputs(ptrs, S, C.byref(opt), C.byref(m), C.addressof(ests), _p(enter), C.byref(o),
+                                                   int(bool(pooled)), C.addressof(fits), C.byref(pool)),
+               "vb2_errfit_cohort_inputs")
+    del keep
+    return [_errfit_dict(f, k) for f in fits], _errfit_pool_dict(pool)
+
+
+class SearchFailed(Exception):
+    """Raised by the evaluate callback of errfit_cohort_with_evaluator: the search of that sample fails with `code`."""
+
+    def __init__(self, code):
+        super().__init__("search failed (%d)" % code)
+        self.code = int(code)
+
+
+def errfit_cohort_with_evaluator(evaluate, stats, num_pc, nominals, pooled=False, enter_status=None, known_af=False,
+                                 prior_reads=0.0, tol=0.0, max_iter=0, **model_kw):
+    """The same fit over two Python callbacks (vb2_errfit_cohort_lockstep): no device.
+    evaluate(sample, err [94], pc1 [B, k], pc2 [B, k], alpha [B]) -> llk [B] answers the searches of `sample`;
+    stats(live [S], err [S, 94], pc1 [S, k], pc2 [S, k], alpha [S]) -> (n [S, 94], s [S, 94]) is the batched E-step (the rows
+    of samples that are not live are ignored).  An evaluate that raises SearchFailed(code) fails that sample's search with
+    the code: the sample leaves, the others go on.  Returns (fits, pool) as errfit_cohort."""
+    k, S, Q = int(num_pc), len(nominals), _abi.VB2_ERR_NUM_QUAL
+    err = []
+
+    def cb_eval(_user, sample, e, n, p1, p2, a, out):
+        try:
+            table = np.ctypeslib.as_array(e, (Q,)).copy()
+            pc1 = np.ctypeslib.as_array(p1, (n, k)).copy()
+            pc2 = np.ctypeslib.as_array(p2, (n, k)).copy()
+            al = np.ctypeslib.as_array(a, (n,)).copy()
+            np.ctypeslib.as_array(out, (n,))[:] = np.asarray(evaluate(int(sample), table, pc1, pc2, al), dtype=np.float64).reshape(n)
+            return 0
+        except SearchFailed as exc:
+            return exc.code
+        except Exception as exc:   # never let an exception cross the C boundary
+            err.append(exc)
+            return _abi.VB2_ERR_INVALID
+
+    def cb_stats(_user, num, live, e, p1, p2, a, n_out, s_out):
+        try:
+            lv = np.ctypeslib.as_array(live, (num,)).copy()
+            n, s = stats(lv, np.ctypeslib.as_array(e, (num, Q)).copy(), np.ctypeslib.as_array(p1, (num, k)).copy(),
+                         np.ctypeslib.as_array(p2, (num, k)).copy(), np.ctypeslib.as_array(a, (num,)).copy())
+            np.ctypeslib.as_array(n_out, (num, Q))[:] = np.asarray(n, dtype=np.int64).reshape(num, Q)
+            np.ctypeslib.as_array(s_out, (num, Q))[:] = np.asarray(s, dtype=np.float64).reshape(num, Q)
+            return 0
+        except Exception as exc:
+            err.append(exc)
+            return _abi.VB2_ERR_INVALID
+    fns = _abi.ErrFitCohortFns(_abi.ERRFIT_COHORT_EVAL_FN(cb_eval), _abi.ERRFIT_COHORT_STATS_FN(cb_stats))
+    m, keep = _model(known_af=known_af, **model_kw)
+    ests, enter, fits, pool = _cohort_fit_args(nominals, enter_status, k)
+    o = _errfit_opts(prior_reads, tol, max_iter)
+    rc = _abi.lib().vb2_errfit_cohort_lockstep(C.byref(fns), None, S, k, C.byref(m), int(bool(known_af)), C.addressof(ests),
+                                               _p(enter), C.byref(o), int(bool(pooled)), C.addressof(fits), C.byref(pool))
+    del keep
+    if err:
+        raise err[0]
+    _abi.check(rc, "vb2_errfit_cohort_lockstep")
+    return [_errfit_dict(f, k) for f in fits], _errfit_pool_dict(pool)
 
 
 class Paired(_RowSet):
@@ -1355,7 +1530,7 @@ def _set_bam(args, bam_path, mpileup, apply_baq=False, reference_path=None):
 def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_sanity=False,
               known_af_path=None, device=-1, output_pileup=False, devices=None, confidence_interval=False,
               per_chromosome=False, bootstrap=0, bam_path=None, mpileup=None, per_read_group=False, ref_bias=False,
-              apply_baq=False, reference_path=None, fit_error=False, error_prior=0.0, **model_kw):
+              apply_baq=False, reference_path=None, fit_error=False, error_prior=0.0, error_table=None, **model_kw):
     """The --SVDPrefix/--PileupFile flow of execute() (vb2_run); devices=[a, b, ...] shards the
     sample's markers over those GPUs.  confidence_interval: vb2_run_interval (<output_prefix>.CI, and an
     `interval` entry in the result).  per_chromosome / bootstrap=N (seeded by seed=): vb2_run_replicates
@@ -1379,7 +1554,13 @@ def run_files(svd_prefix, pileup_path, output_prefix=None, num_pc=2, disable_san
     groups = None
     bias = None
     efit = None
-    if fit_error:
+    if error_table is not None:
+        if fit_error or confidence_interval or per_chromosome or bootstrap or per_read_group or ref_bias:
+            raise ValueError("error_table runs a plain run: it cannot be combined with fit_error, confidence_interval, per_chromosome, "
+                             "bootstrap, per_read_group or ref_bias")
+        table = _table_of(error_table)
+        _abi.check(_abi.lib().vb2_run_under_table(C.byref(args), _p(table), C.byref(res)), "vb2_run_under_table")
+    elif fit_error:
         if confidence_interval or per_chromosome or bootstrap or per_read_group or ref_bias:
             raise ValueError("fit_error cannot be combined with confidence_interval, per_chromosome, bootstrap, per_read_group "
                              "or ref_bias")
@@ -1626,7 +1807,8 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
                      known_af_path=None, device=-1, output_pileup=False, group_size=0, num_host_thread=0,
                      devices=None, find_source=False, source_top=3, sources_prefix=None, confidence_interval=False,
                      refit_source=False, find_related=False, related_top=3, matched_normal=None, normal_hom_min=0.99,
-                     pair_interval=False, mpileup=None, apply_baq=False, reference_path=None, **model_kw):
+                     pair_interval=False, mpileup=None, apply_baq=False, reference_path=None, cohort_fit_error=False,
+                     pooled_error=False, error_prior=0.0, error_table=None, **model_kw):
     """Many pileups against one panel (vb2_cohort_run): the panel is read once, the pileups are read
     and flattened by host threads while the device searches the previous group in lock-step.
     Returns one dict per sample (with its own "status" code).
@@ -1651,8 +1833,23 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
     failed its own run, < 0: the refit's error), normal_freemix, freemix, freelk1, alpha_paired, lk1_paired, lk0_paired --
     and with output_prefixes and sources_prefix <sources_prefix>.PairFit is written.  normal_hom_min: --NormalHomMin.
     pair_interval (with matched_normal; vb2_cohort_run_paired_intervals): every refitted pair's dict also has `interval` --
-    alpha_paired unfolded in "freemix", its interval within [0, 1] -- and <sources_prefix>.PairCI is written."""
+    alpha_paired unfolded in "freemix", its interval within [0, 1] -- and <sources_prefix>.PairCI is written.
+    cohort_fit_error (vb2_cohort_run_errfit; one device; with none of the above): the error rates of every sample fitted in
+    lock-step after the run, each on its own table or, with pooled_error, all on one; error_prior: --ErrorPrior.  Returns
+    (samples, dict(fits=[the dict of errfit per sample], pool=the pooled summary)); with output_prefixes the per-sample
+    <prefix>.ErrorFit / .ErrorRates, pooled with sources_prefix <sources_prefix>.ErrorRates / .PooledFit are written.
+    error_table (vb2_cohort_run_under_table; with none of the above): a path in .ErrorRates format, or 94 rates -- the plain
+    run with every sample's context under that table."""
     S = len(pileup_paths)
+    if error_table is not None and (cohort_fit_error or find_source or find_related or confidence_interval or refit_source or
+                                    matched_normal is not None):
+        raise ValueError("error_table runs a plain cohort run: it cannot be combined with cohort_fit_error, find_source, find_related, "
+                         "confidence_interval, refit_source or matched_normal")
+    if pooled_error and not cohort_fit_error:
+        raise ValueError("pooled_error needs cohort_fit_error")
+    if cohort_fit_error and (find_source or find_related or confidence_interval or refit_source or matched_normal is not None):
+        raise ValueError("cohort_fit_error cannot be combined with find_source, find_related, confidence_interval, refit_source or "
+                         "matched_normal")
     if pair_interval and matched_normal is None:
         raise ValueError("pair_interval needs matched_normal")
     if matched_normal is not None and (find_source or find_related or confidence_interval or refit_source):
@@ -1662,7 +1859,7 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
     if refit_source and (not find_source or confidence_interval):
         raise ValueError("refit_source needs find_source and cannot be combined with confidence_interval")
     args, keep = _run_args(svd_prefix, pileup_paths[0], num_pc, disable_sanity, known_af_path,
-                           sources_prefix if find_source or find_related or matched_normal is not None else None,
+                           sources_prefix if find_source or find_related or matched_normal is not None or cohort_fit_error else None,
                            device, output_pileup, devices=devices, **model_kw)
     args.mpileup = _mpileup_opts(mpileup)
     args.bam_adjust = int(apply_baq)      # --ApplyBAQ for the list's .bam lines (reference_path: the FASTA)
@@ -1683,7 +1880,15 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
     status = (C.c_int32 * S)()
     score = shared = None
     civ = None
-    if matched_normal is not None:
+    if error_table is not None:
+        table = _table_of(error_table)
+        _abi.check(_abi.lib().vb2_cohort_run_under_table(C.byref(ca), _p(table), res, status), "vb2_cohort_run_under_table")
+    elif cohort_fit_error:
+        efits, epool = (_abi.ErrFit * S)(), _abi.ErrFitPool()
+        eo = _errfit_opts(error_prior)
+        _abi.check(_abi.lib().vb2_cohort_run_errfit(C.byref(ca), C.byref(eo), int(bool(pooled_error)), res, status,
+                                                    C.addressof(efits), C.addressof(epool)), "vb2_cohort_run_errfit")
+    elif matched_normal is not None:
         pairs = np.ascontiguousarray(np.asarray(matched_normal, dtype=np.int32).reshape(-1, 2))
         tum, nrm = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
         pfits = (_abi.PairFit * max(len(pairs), 1))()
@@ -1726,6 +1931,8 @@ def run_cohort_files(svd_prefix, pileup_paths, output_prefixes=None, num_pc=2, d
             if _abi.lib().vb2_cohort_bam_stats(s, C.byref(st)) == _abi.VB2_OK:
                 d["bam"] = {name: getattr(st, name) for name, _ in _abi.BamStats._fields_}
         out.append(d)
+    if cohort_fit_error:
+        return out, dict(fits=[_errfit_dict(f, num_pc) for f in efits], pool=_errfit_pool_dict(epool))
     if matched_normal is not None:
         fits = [{name: getattr(pfits[p], name) for name, _ in _abi.PairFit._fields_} for p in range(len(pairs))]
         for p, f in enumerate(fits):

@@ -41,6 +41,13 @@
 // weight of the nominal rate in pseudo-reads per quality (default 100).  With --PileupFile or --BamFile; one sample, one
 // device, a searched alpha, the reference's own search: not with --PileupList, --PerReadGroup, --FixAlpha,
 // --ConfidenceInterval, --PerChromosome, --Bootstrap, --RefBias, --NumStart, --LineSearch or several --Devices.
+// --PileupList F --CohortFitError [--PooledError] [--ErrorPrior k] fits them for every sample of a cohort in lock-step after
+// the run (vb2_cohort_run_errfit): each sample on its own table, to <prefix>.ErrorFit / .ErrorRates, or
+// with --PooledError all on one, to <Output>.ErrorRates and <Output>.PooledFit.  One device, a searched alpha, the
+// reference's own search, no other after-run stage (--FindSource, --FindRelated, --MatchedNormal, --CohortInterval).
+// --ErrorTable F runs a plain --PileupFile / --BamFile / --PileupList run under the rates of F, a file in .ErrorRates format
+// (columns #Q_REPORTED and ERROR_RATE; a quality it does not list stays nominal): what makes a pooled fit usable elsewhere.
+// Not with any flag above that adds a stage, nor with --FitError / --CohortFitError.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -128,7 +135,9 @@ int main(int argc, char** argv)
     bool applyBAQ = false;
     bool refBias = false;
     bool fitError = false;
+    bool cohortFitError = false, pooledError = false;
     double errorPrior = 100.0;
+    std::string ErrorTable("Empty");
     // "Pileup Options" (main.cpp:176-187), defaults main.cpp:81-96 (MPLP_REALN | MPLP_SMART_OVERLAPS; UNMAP | SECONDARY |
     // QCFAIL | DUP): they shape what --BamFile input becomes and, as in the reference, do nothing to --PileupFile input
     int minBQ = 13, minMQ = 2, adjustMQ = 40, maxDepth = 8000, inclFlags = (1 << 4) | (1 << 10), exclFlags = 0x4 | 0x100 | 0x200 | 0x400;
@@ -220,6 +229,13 @@ int main(int argc, char** argv)
         // <Output>.ErrorFit and <Output>.ErrorRates; --ErrorPrior: pseudo-reads at the nominal rate per quality
         {"FitError", {Flag::kBool, &fitError, false}},
         {"ErrorPrior", {Flag::kDouble, &errorPrior, false}},
+        // ... of every sample of a --PileupList cohort in lock-step (vb2_cohort_run_errfit): each on its own table, or with
+        // --PooledError all on one, to <Output>.ErrorRates and <Output>.PooledFit
+        {"CohortFitError", {Flag::kBool, &cohortFitError, false}},
+        {"PooledError", {Flag::kBool, &pooledError, false}},
+        // a plain --PileupFile / --BamFile / --PileupList run under the error rates of a file in .ErrorRates format
+        // (vb2_err_table_read, vb2_run_under_table, vb2_cohort_run_under_table)
+        {"ErrorTable", {Flag::kString, &ErrorTable, false}},
     };
     for (int i = 1; i < argc; ++i) {
         const char* a = argv[i];
@@ -251,6 +267,24 @@ int main(int argc, char** argv)
         else if (f.kind == Flag::kDouble) *static_cast<double*>(f.dst) = std::atof(v);
         else *static_cast<std::string*>(f.dst) = v;
     }
+    if (ErrorTable != "Empty") {                                        // a plain run, every context under the file's table
+        if (fitError) fatal("--ErrorTable cannot be combined with --FitError: a run either fits the error rates or is given them");
+        if (cohortFitError) fatal("--ErrorTable cannot be combined with --CohortFitError: a run either fits the error rates or is given them");
+        if (confidenceInterval) fatal("--ErrorTable cannot be combined with --ConfidenceInterval: the interval is computed under the nominal rates");
+        if (cohortInterval) fatal("--ErrorTable cannot be combined with --CohortInterval: the intervals are computed under the nominal rates");
+        if (findSource) fatal("--ErrorTable cannot be combined with --FindSource: the source scores are computed under the nominal rates");
+        if (findRelated) fatal("--ErrorTable cannot be combined with --FindRelated: the relatedness is computed under the nominal rates");
+        if (MatchedNormal != "Empty") fatal("--ErrorTable cannot be combined with --MatchedNormal: the paired refits are computed under the nominal rates");
+        if (perReadGroup) fatal("--ErrorTable cannot be combined with --PerReadGroup: the groups are searched under the nominal rates");
+        if (perChromosome) fatal("--ErrorTable cannot be combined with --PerChromosome: the replicates are searched under the nominal rates");
+        if (flags["Bootstrap"].seen) fatal("--ErrorTable cannot be combined with --Bootstrap: the replicates are searched under the nominal rates");
+        if (refBias) fatal("--ErrorTable cannot be combined with --RefBias: the bias is fitted under the nominal rates");
+        if (PileupList == "Empty" && Devices != "Empty" && Devices.find(',') != std::string::npos)
+            fatal("--ErrorTable cannot be combined with more than one --Devices for one sample: marker shards are built under the nominal rates");
+    }
+    double errTable[VB2_ERR_NUM_QUAL];                                  // (read before any other file of the run)
+    int32_t errTableTaken = 0;
+    if (ErrorTable != "Empty" && vb2_err_table_read(ErrorTable.c_str(), errTable, &errTableTaken) != VB2_OK) fatal(vb2_last_error());
     if (fitError) {                                                     // one sample, one device, a searched alpha, the plain search
         if (PileupList != "Empty")
             fatal("--FitError cannot be combined with --PileupList: the error rates are fitted for one sample per run");
@@ -266,8 +300,25 @@ int main(int argc, char** argv)
         if (Devices != "Empty" && Devices.find(',') != std::string::npos)
             fatal("--FitError cannot be combined with more than one --Devices: the fit reads one resident sample on one device");
         if (!(errorPrior > 0.0)) fatal("--ErrorPrior takes a positive number of pseudo-reads");
+    } else if (cohortFitError) {                                        // a cohort on one device, the plain searches, no other stage
+        if (PileupList == "Empty")
+            fatal("--CohortFitError needs --PileupList: it fits the error rates of every sample of a cohort run (--FitError is the "
+                  "flag for one sample)");
+        if (flags["FixAlpha"].seen)
+            fatal("--CohortFitError cannot be combined with --FixAlpha: a fixed alpha leaves the fit nothing to tell errors from");
+        if (flags["NumStart"].seen) fatal("--CohortFitError cannot be combined with --NumStart: every iteration's search is the reference's own");
+        if (lineSearch) fatal("--CohortFitError cannot be combined with --LineSearch: every iteration's search is the reference's own");
+        if (Devices != "Empty" && Devices.find(',') != std::string::npos)
+            fatal("--CohortFitError cannot be combined with more than one --Devices: the samples' raw inputs are fitted together on one device");
+        if (findSource) fatal("--CohortFitError cannot be combined with --FindSource: run the source scores and the fits separately");
+        if (findRelated) fatal("--CohortFitError cannot be combined with --FindRelated: run the relatedness and the fits separately");
+        if (MatchedNormal != "Empty") fatal("--CohortFitError cannot be combined with --MatchedNormal: run the paired refits and the fits separately");
+        if (cohortInterval) fatal("--CohortFitError cannot be combined with --CohortInterval: run the intervals and the fits separately");
+        if (!(errorPrior > 0.0)) fatal("--ErrorPrior takes a positive number of pseudo-reads");
+    } else if (pooledError) {
+        fatal("--PooledError needs --CohortFitError");
     } else if (flags["ErrorPrior"].seen) {
-        fatal("--ErrorPrior needs --FitError");
+        fatal("--ErrorPrior needs --FitError or --CohortFitError");
     }
     if (refBias) {                                                      // one sample, one device, a searched alpha
         if (PileupList != "Empty")
@@ -529,6 +580,9 @@ int main(int argc, char** argv)
     }
     if (args.known_af_path) args.model.is_af_known = 1;               // main.cpp:314-319
 
+    if (ErrorTable != "Empty")
+        std::fprintf(stderr, "NOTICE - --ErrorTable: the error rates of %d qualities taken from %s, the others nominal\n",
+                     (int)errTableTaken, ErrorTable.c_str());
     if (PileupList != "Empty") {
         std::vector<const char*> cpile, cpref;
         for (size_t i = 0; i < pile.size(); ++i) { cpile.push_back(pile[i].c_str()); cpref.push_back(pref[i].c_str()); }
@@ -546,7 +600,12 @@ int main(int argc, char** argv)
         if (MatchedNormal != "Empty" &&         // (before the panel is read and any device is touched)
             vb2_matched_normal_read(MatchedNormal.c_str(), ca.num_sample, cpile.data(), &numPair, tumour.data(), normal.data()) != VB2_OK)
             fatal(vb2_last_error());
-        const int rcc = numPair > 0 && pairInterval
+        vb2_errfit_opts cohortFitOpts;
+        std::memset(&cohortFitOpts, 0, sizeof(cohortFitOpts));
+        cohortFitOpts.prior_reads = errorPrior;
+        const int rcc = ErrorTable != "Empty" ? vb2_cohort_run_under_table(&ca, errTable, cres.data(), cst.data())
+                        : cohortFitError ? vb2_cohort_run_errfit(&ca, &cohortFitOpts, pooledError ? 1 : 0, cres.data(), cst.data(), nullptr, nullptr)
+                        : numPair > 0 && pairInterval
                             ? vb2_cohort_run_paired_intervals(&ca, numPair, tumour.data(), normal.data(), normalHomMin, cres.data(),
                                                               cst.data(), nullptr, nullptr)
                         : numPair > 0 ? vb2_cohort_run_paired(&ca, numPair, tumour.data(), normal.data(), normalHomMin, cres.data(), cst.data(), nullptr)
@@ -579,7 +638,8 @@ int main(int argc, char** argv)
     vb2_errfit_opts fitOpts;
     std::memset(&fitOpts, 0, sizeof(fitOpts));
     fitOpts.prior_reads = errorPrior;
-    const int rc = fitError                         ? vb2_run_errfit(&args, &fitOpts, &res, nullptr)
+    const int rc = ErrorTable != "Empty"            ? vb2_run_under_table(&args, errTable, &res)
+                   : fitError                       ? vb2_run_errfit(&args, &fitOpts, &res, nullptr)
                    : refBias                        ? vb2_run_refbias(&args, &res, nullptr)
                    : perReadGroup                   ? vb2_run_read_groups(&args, &res, 0, nullptr, &numGroup)
                    : (perChromosome || bootstrap > 0) ? vb2_run_replicates(&args, perChromosome ? 1 : 0, bootstrap, &res, nullptr)

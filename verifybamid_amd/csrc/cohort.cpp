@@ -65,10 +65,14 @@ public:
     // stages.after: what the run does after its last sample (cohort_stages.h); stages.intervals: every searched sample's
     // vb2_interval as well (one device) -- <prefix>.CI, and ci[s] when ci is not null -- before the sample goes to the releaser
     CohortRunner(const vb2_cohort_args* a, vb2_run_result* out, int32_t* status, const vb2::CohortStages& stages)
-        : a_(a), out_(out), status_(status), S_(a->num_sample), intervals_(stages.intervals), ci_(stages.ci)
+        : a_(a), out_(out), status_(status), S_(a->num_sample), intervals_(stages.intervals), ci_(stages.ci),
+          err_table_(stages.err_table)
     {
         for (vb2::CohortStage* st : stages.after)
-            if (st) after_.push_back(st);
+            if (st) {
+                after_.push_back(st);
+                keep_raw_ = keep_raw_ || st->takes_flat();
+            }
         if (a->base.devices && a->base.num_device > 0) devices_.assign(a->base.devices, a->base.devices + a->base.num_device);
         else devices_.push_back(a->base.device);
         ndev_ = (int)devices_.size();
@@ -248,12 +252,14 @@ private:
     std::deque<Done> done_queue_;          // (rel_mu_)
     // the stages after the run (none: a plain run), their set (null without planes), the contexts they keep (releaser thread)
     std::vector<vb2::CohortStage*> after_;
+    bool keep_raw_ = false;                 // a stage takes the samples' flattened inputs: the readers leave the raw arrays
     std::unique_ptr<vb2::SourceSet> set_;
     std::vector<vb2_ctx*> parked_;
     int64_t parked_bytes_ = 0;
     // --CohortInterval (false without it: nothing below then differs from a plain run).  Streaming: a searched sample waits
     // in iv_queue_ for a fiber of the interval stage (interval_loop), which has a thread and a stream of its own.
     bool intervals_ = false;
+    const double* err_table_ = nullptr;    // every context under this error table (--ErrorTable), or null
     vb2_interval* ci_ = nullptr;
     struct IvItem { int s = -1; vb2_estimate est{}; };
     std::mutex iv_mu_;
@@ -434,7 +440,7 @@ private:
         opt.flags = VB2_OPT_COHORT_LAYOUT;       // the lock-step search streams the 16-bit run lists
         if (!own_streams_.empty())               // (one of the device's two creation streams: see run())
             opt.stream = own_streams_[(size_t)device_of_sample(s) * 4 + 2 + (size_t)(s / ndev_) % 2];
-        sl.rc = vb2_ctx_create(&f.input, &opt, &sl.ctx);
+        sl.rc = err_table_ ? vb2_ctx_create_ex(&f.input, &opt, err_table_, &sl.ctx) : vb2_ctx_create(&f.input, &opt, &sl.ctx);
         if (sl.rc == VB2_OK && sl.ctx && sl.ctx->impl) {
             // the static schedules of the sample's group (and of the batches its lane is regrouped into): here, on one of many
             // reader threads, not on the one thread that feeds the device (a failure only means they are built there)
@@ -445,12 +451,15 @@ private:
         // the context holds its own (flattened) copy: the sample's text-sized arrays go back now, on
         // this reader thread, instead of piling up in front of the single releaser (the writers need
         // only the viewer's counters and the panel)
-        std::string().swap(f.bases);
-        std::string().swap(f.quals);
+        // (unless a stage takes the flattened input: CohortStage::takes_flat)
         std::string().swap(f.viewer.basePool);
         std::string().swap(f.viewer.qualPool);
-        std::vector<int64_t>().swap(f.read_off);
-        f.input = vb2_input{};
+        if (!keep_raw_) {
+            std::string().swap(f.bases);
+            std::string().swap(f.quals);
+            std::vector<int64_t>().swap(f.read_off);
+            f.input = vb2_input{};
+        }
         const double t_end = now_s();
         out_[s].seconds_load = t_end - t0;
         {
@@ -733,6 +742,12 @@ private:
                     d.ctx = nullptr;
                 }
             }
+            if (keep_raw_ && d.row && d.flat && status_[d.s] == VB2_OK)
+                for (vb2::CohortStage* st : after_)
+                    if (st->takes_flat()) {
+                        st->take_flat(d.s, std::move(d.flat), d.est);
+                        break;
+                    }
             const double t0 = now_s();
             if (d.ctx) vb2_ctx_destroy(d.ctx);
             const double t1 = now_s();

@@ -12,8 +12,13 @@
 #include <string>
 #include <vector>
 
+#include <hip/hip_runtime_api.h>
+
 #include "cohort_stages.h"
 #include "conditioned.h"
+#include "errfit.h"
+#include "errfit_cohort.h"
+#include "errstat.h"
 #include "guard.h"
 #include "hostio.h"
 #include "paired.h"
@@ -356,6 +361,119 @@ struct PairedStage : vb2::CohortStage {
 
 // ---- the entry points' checks, in the order every one of them makes them ----
 
+// --CohortFitError: the error-rate fit of the cohort's samples (errfit_cohort.h).  The stage takes the
+// retiring samples' flattened inputs, with the raw arrays in them, and in finish() fits them in lock-step -- per sample, or
+// pooled into one table -- through one ErrStatBatch per chunk of at most 64 samples.
+struct ErrFitStage : vb2::CohortStage {
+    const vb2_errfit_opts* opts;
+    const bool pooled;
+    vb2_errfit* fits_out;
+    vb2_errfit_pool* pool_out;
+    std::vector<std::unique_ptr<vb2_flat>> flats;
+    std::vector<vb2_estimate> est;
+    ErrFitStage(int S, const vb2_errfit_opts* o, bool pool_them, vb2_errfit* fits, vb2_errfit_pool* pool)
+        : CohortStage("--CohortFitError", 0), opts(o), pooled(pool_them), fits_out(fits), pool_out(pool), flats((size_t)S), est((size_t)S)
+    {
+    }
+    bool takes_flat() const override { return true; }
+    void take_flat(int s, std::unique_ptr<vb2_flat> f, const vb2_estimate& e) override
+    {
+        flats[(size_t)s] = std::move(f);
+        est[(size_t)s] = e;
+    }
+
+    int finish(const CohortEnd& e) override
+    {
+        const int S = e.a->num_sample, kMax = VB2_ERRSTAT_BATCH_MAX;
+        if (pooled && S > kMax) {
+            set_error("--PooledError: one pool holds at most " + std::to_string(kMax) + " samples, the list has " + std::to_string(S));
+            return VB2_ERR_INVALID;
+        }
+        vb2_options opt{};
+        opt.device = e.a->base.num_device > 0 && e.a->base.devices ? e.a->base.devices[0] : e.a->base.device;
+        // the raw inputs stay on the device for the whole fit: all of a chunk or nothing
+        for (int c0 = 0; c0 < S; c0 += kMax) {
+            const int n = std::min(kMax, S - c0);
+            long long need = 0;
+            bool panel_counted = false;
+            for (int i = c0; i < c0 + n; ++i)
+                if (e.status[i] == VB2_OK && flats[(size_t)i]) {
+                    const vb2_input& in = flats[(size_t)i]->input;
+                    const long long M = in.num_marker, R = M > 0 ? in.read_off[M] - in.read_off[0] : 0;
+                    need += 2 * R + 9 * (M + 1);                     // bases, qualities; offsets and alleles
+                    if (!panel_counted) need += M * 8LL * (in.num_pc + 1);          // (the samples share the panel's arrays)
+                    panel_counted = true;
+                }
+            size_t free_b = 0, total_b = 0;
+            if (opt.device >= 0) (void)hipSetDevice(opt.device);
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (unsigned long long)need > free_b) {
+                set_error("--CohortFitError: the raw inputs of samples " + std::to_string(c0) + ".." + std::to_string(c0 + n - 1) + " take " +
+                          std::to_string(need) + " bytes on the device, " + std::to_string(free_b) + " of " + std::to_string(total_b) +
+                          " are free");
+                return VB2_ERR_NOMEM;
+            }
+        }
+        std::vector<vb2_errfit> fits((size_t)S);
+        vb2_errfit_pool pool{};
+        int iters = 0, fitted = 0, bins = 0;
+        double lrt_sum = 0.0;
+        const double t0 = vb2::now_s();
+        for (int c0 = 0; c0 < S; c0 += kMax) {
+            const int n = std::min(kMax, S - c0);
+            std::vector<const vb2_input*> in((size_t)n, nullptr);
+            std::vector<int32_t> enter((size_t)n);
+            for (int i = 0; i < n; ++i) {
+                const size_t s = (size_t)(c0 + i);
+                enter[(size_t)i] = e.status[s] != VB2_OK ? e.status[s] : flats[s] ? VB2_OK : VB2_ERR_INVALID;
+                if (enter[(size_t)i] == VB2_OK) in[(size_t)i] = &flats[s]->input;
+            }
+            if (const int rc = vb2::errfit_cohort_inputs(in.data(), n, &opt, e.model, est.data() + c0, enter.data(), opts, pooled,
+                                                         fits.data() + c0, &pool))
+                return rc;
+            iters = std::max(iters, (int)pool.num_iter);
+            fitted += pool.num_fitted;
+            bins = std::max(bins, (int)pool.num_bin);
+            lrt_sum += pool.lrt_sum;
+        }
+        const auto folded = [](double a) { return a < 0.5 ? a : 1 - a; };
+        const char* const* prefixes = e.a->output_prefixes;
+        if (!pooled && prefixes)
+            for (int s = 0; s < S; ++s)
+                if (e.status[s] == VB2_OK && fits[(size_t)s].status == VB2_OK && flats[(size_t)s] && prefixes[s])
+                    if (const int rc = vb2::write_errfit_files(prefixes[s], flats[(size_t)s]->viewer.SEQ_SM, folded(est[(size_t)s].alpha),
+                                                               fits[(size_t)s]))
+                        return rc;
+        if (pooled && e.a->base.output_prefix) {
+            const std::string prefix = e.a->base.output_prefix;
+            if (const int rc = vb2::write_error_rates(prefix, pool.err, pool.n, pool.s)) return rc;
+            const int rc = vb2::write_text_file(prefix + ".PooledFit", [&](std::ostream& fout) {
+                fout << "#SEQ_ID\tFREEMIX\tFREEMIX_FIT\tLRT\tFREELK1_FIT\tFREELK1_NOMINAL\tSTATUS\n";
+                for (int s = 0; s < S; ++s) {
+                    const vb2_errfit& f = fits[(size_t)s];
+                    fout << (flats[(size_t)s] ? flats[(size_t)s]->viewer.SEQ_SM : std::string(e.a->pileup_paths[s])) << "\t";
+                    if (e.status[s] == VB2_OK) fout << folded(est[(size_t)s].alpha);
+                    else fout << "NA";
+                    if (f.status == VB2_OK) fout << "\t" << folded(f.est.alpha) << "\t" << f.lrt << "\t" << f.llk_fit << "\t" << f.llk_nominal;
+                    else fout << "\tNA\tNA\tNA\tNA";
+                    fout << "\t" << f.status << "\n";
+                }
+            });
+            if (rc) return rc;
+        }
+        if (pooled)
+            std::fprintf(stderr, "NOTICE - --PooledError: one error table for %d of %d samples, %d qualities fitted in %d iterations%s; "
+                                 "summed LRT %g  [%.3f seconds]\n", fitted, S, bins, iters, pool.converged ? "" : ", not converged", lrt_sum,
+                         vb2::now_s() - t0);
+        else
+            std::fprintf(stderr, "NOTICE - --CohortFitError: the error rates of %d of %d samples fitted, each on its own table, at most %d "
+                                 "iterations; summed LRT %g  [%.3f seconds]\n", fitted, S, iters, lrt_sum, vb2::now_s() - t0);
+        if (fits_out) std::memcpy(fits_out, fits.data(), sizeof(vb2_errfit) * (size_t)S);
+        if (pool_out) *pool_out = pool;
+        flats.clear();
+        return VB2_OK;
+    }
+};
+
 int check_args(const char* fn, const vb2_cohort_args* a, const vb2_run_result* out, const int32_t* status, bool rest_ok = true)
 {
     if (a && out && status && a->num_sample >= 1 && a->pileup_paths && a->base.ud_path && a->base.mean_path && a->base.bed_path &&
@@ -447,6 +565,39 @@ extern "C" int vb2_cohort_run_intervals(const vb2_cohort_args* a, int32_t source
         return rc;
     SourcesStage sources(source_top, nullptr, nullptr);
     return vb2::cohort_run_with(a, out, status, {{source_top > 0 ? &sources : nullptr}, true, ci});
+}
+
+extern "C" int vb2_cohort_run_errfit(const vb2_cohort_args* a, const vb2_errfit_opts* fit_opts, int32_t pooled, vb2_run_result* out,
+                                     int32_t* status, vb2_errfit* fits, vb2_errfit_pool* pooled_out)
+{
+    if (const int rc = check_args("vb2_cohort_run_errfit", a, out, status)) return rc;
+    if (const int rc = one_device(a, "--CohortFitError takes one device: the samples' raw inputs are fitted together on one device, not "
+                                     "over several --Devices"))
+        return rc;
+    if (const int rc = refuse(a->base.model.is_alpha_fixed,
+                              "--CohortFitError cannot be combined with --FixAlpha: a fixed alpha leaves the fit nothing to tell errors from"))
+        return rc;
+    if (const int rc = refuse(a->base.search.num_start > 1 || a->base.search.line_search,
+                              "--CohortFitError cannot be combined with --NumStart / --LineSearch: every iteration's search is the "
+                              "reference's own"))
+        return rc;
+    {   // the fit's options, before any file is read
+        double kappa = 0.0, tol = 0.0;
+        int max_iter = 0;
+        if (const int rc = vb2::errfit_options(a->base.model, fit_opts, "vb2_cohort_run_errfit", &kappa, &tol, &max_iter)) return rc;
+    }
+    if (const int rc = refuse(pooled && a->num_sample > VB2_ERRSTAT_BATCH_MAX, "--PooledError: one pool holds at most 64 samples"))
+        return rc;
+    ErrFitStage fit(a->num_sample, fit_opts, pooled != 0, fits, pooled_out);
+    return vb2::cohort_run_with(a, out, status, {{&fit}});
+}
+
+extern "C" int vb2_cohort_run_under_table(const vb2_cohort_args* a, const double* err_table, vb2_run_result* out, int32_t* status)
+{
+    if (const int rc = check_args("vb2_cohort_run_under_table", a, out, status, a && a->base.num_device >= 0 && a->base.num_device <= 64))
+        return rc;
+    if (!vb2::err_table_ok(err_table, "vb2_cohort_run_under_table")) return VB2_ERR_INVALID;
+    return vb2::cohort_run_with(a, out, status, {{}, false, nullptr, err_table});
 }
 
 extern "C" int vb2_cohort_run_paired(const vb2_cohort_args* a, int32_t num_pair, const int32_t* tumour, const int32_t* normal,

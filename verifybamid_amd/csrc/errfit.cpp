@@ -10,6 +10,7 @@
 #include <string>
 
 #include "context.h"
+#include "err_table.h"
 #include "errstat.h"
 #include "estimator.h"
 #include "guard.h"
@@ -22,8 +23,9 @@ namespace {
 
 constexpr int kQ = VB2_ERR_NUM_QUAL;
 
-// the search's own point of an estimate: the reported PCs with the reference's swap of indices 0, 1 undone (source.cpp)
-void search_point(const vb2_estimate& est, int k, bool heter, double* p1, double* p2)
+}  // namespace
+
+void errfit_search_point(const vb2_estimate& est, int k, bool heter, double* p1, double* p2)
 {
     std::memcpy(p1, est.pc, sizeof(double) * (size_t)k);
     std::memcpy(p2, est.pc2, sizeof(double) * (size_t)k);
@@ -33,13 +35,9 @@ void search_point(const vb2_estimate& est, int k, bool heter, double* p1, double
     }
 }
 
-}  // namespace
-
-int errfit(const ErrFitSteps& steps, int num_pc, const vb2_model& model, bool data_has_known_af, const vb2_estimate& nominal,
-           const vb2_errfit_opts* opts, const char* who, vb2_errfit* out)
+int errfit_options(const vb2_model& model, const vb2_errfit_opts* opts, const char* who, double* kappa_out, double* tol_out,
+                   int* max_iter_out)
 {
-    std::memset(out, 0, sizeof(*out));
-    out->llk_fit = out->llk_nominal = out->alpha_nominal = out->lrt = NAN;
     const std::string w(who);
     if (model.is_alpha_fixed) {
         set_error(w + ": a fixed alpha leaves the fit nothing to tell errors from (--FixAlpha)");
@@ -53,9 +51,44 @@ int errfit(const ErrFitSteps& steps, int num_pc, const vb2_model& model, bool da
                   std::to_string(VB2_ERRFIT_MAX_ITER) + " (0 = " + std::to_string(VB2_ERRFIT_MAX_ITER) + ")");
         return VB2_ERR_INVALID;
     }
+    *kappa_out = kappa;
+    *tol_out = tol;
+    *max_iter_out = max_iter;
+    return VB2_OK;
+}
+
+void errfit_nominal_table(double* eps0)
+{
+    for (int q = 0; q < kQ; ++q) eps0[q] = std::pow(10.0, q / -10.0);
+}
+
+double errfit_mstep(const int64_t* n, const double* s, const double* eps0, const double* eps, double kappa, double* next)
+{
+    double change = 0.0;
+    for (int q = 0; q < kQ; ++q) {
+        next[q] = eps0[q];
+        if (n[q] <= 0) continue;
+        // the posterior mode's share of error reads among n + kappa, kept as the nearest float32: the device fit and the
+        // restatement continue from the same bits
+        next[q] = (double)(float)((s[q] + kappa * eps0[q]) / ((double)n[q] + kappa));
+        const double d = eps[q] > 0.0 ? std::fabs(next[q] - eps[q]) / eps[q] : (next[q] == 0.0 ? 0.0 : INFINITY);
+        change = d > change ? d : change;
+    }
+    return change;
+}
+
+int errfit(const ErrFitSteps& steps, int num_pc, const vb2_model& model, bool data_has_known_af, const vb2_estimate& nominal,
+           const vb2_errfit_opts* opts, const char* who, vb2_errfit* out)
+{
+    std::memset(out, 0, sizeof(*out));
+    out->llk_fit = out->llk_nominal = out->alpha_nominal = out->lrt = NAN;
+    double kappa = 0.0, tol = 0.0;
+    int max_iter = 0;
+    if (const int rc = errfit_options(model, opts, who, &kappa, &tol, &max_iter)) return rc;
     const bool heter = model.is_heter && !model.is_af_known && !data_has_known_af;
     double eps0[kQ], eps[kQ], next[kQ], p1[VB2_MAX_PC], p2[VB2_MAX_PC];
-    for (int q = 0; q < kQ; ++q) eps[q] = eps0[q] = std::pow(10.0, q / -10.0);
+    errfit_nominal_table(eps0);
+    std::memcpy(eps, eps0, sizeof(eps));
     vb2_estimate est = nominal;
     out->llk_nominal = -nominal.llk1;
     out->alpha_nominal = nominal.alpha;
@@ -63,18 +96,9 @@ int errfit(const ErrFitSteps& steps, int num_pc, const vb2_model& model, bool da
     quiet.notices = 0;
     quiet.verbose = 0;
     for (int t = 0; t < max_iter; ++t) {
-        search_point(est, num_pc, heter, p1, p2);
+        errfit_search_point(est, num_pc, heter, p1, p2);
         if (const int rc = steps.stats(eps, p1, p2, est.alpha, out->n, out->s)) return rc;
-        double change = 0.0;
-        for (int q = 0; q < kQ; ++q) {
-            next[q] = eps0[q];
-            if (out->n[q] <= 0) continue;
-            // the posterior mode's share of error reads among n + kappa, kept as the nearest float32: the device fit and the
-            // restatement continue from the same bits
-            next[q] = (double)(float)((out->s[q] + kappa * eps0[q]) / ((double)out->n[q] + kappa));
-            const double d = eps[q] > 0.0 ? std::fabs(next[q] - eps[q]) / eps[q] : (next[q] == 0.0 ? 0.0 : INFINITY);
-            change = d > change ? d : change;
-        }
+        const double change = errfit_mstep(out->n, out->s, eps0, eps, kappa, next);
         if (const int rc = steps.search(next, &est)) {
             out->status = rc;
             return rc;
@@ -91,7 +115,7 @@ int errfit(const ErrFitSteps& steps, int num_pc, const vb2_model& model, bool da
             break;
         }
     }
-    search_point(est, num_pc, heter, p1, p2);
+    errfit_search_point(est, num_pc, heter, p1, p2);
     if (const int rc = steps.stats(eps, p1, p2, est.alpha, out->n, out->s)) return rc;
     std::memcpy(out->err, eps, sizeof(eps));
     out->est = est;
@@ -99,6 +123,30 @@ int errfit(const ErrFitSteps& steps, int num_pc, const vb2_model& model, bool da
     out->lrt = 2.0 * (out->llk_fit - out->llk_nominal);
     for (int q = 0; q < kQ; ++q) out->num_bin += out->n[q] > 0 ? 1 : 0;
     return VB2_OK;
+}
+
+int write_error_rates(const std::string& prefix, const double* err, const int64_t* n, const double* s)
+{
+    return write_text_file(prefix + ".ErrorRates", [&](std::ostream& fout) {
+        fout << "#Q_REPORTED\tREADS\tEXPECTED_ERRORS\tERROR_RATE\tQ_EMPIRICAL\tSE_BINOM\n";
+        for (int q = 0; q < VB2_ERR_NUM_QUAL; ++q) {
+            if (n[q] <= 0) continue;
+            const double e = err[q];
+            fout << q << "\t" << (long long)n[q] << "\t" << s[q] << "\t" << e << "\t" << -10.0 * std::log10(e) << "\t"
+                 << std::sqrt(e * (1.0 - e) / (double)n[q]) << "\n";
+        }
+    });
+}
+
+int write_errfit_files(const std::string& prefix, const std::string& seq_id, double freemix, const vb2_errfit& f)
+{
+    const double freemix_fit = f.est.alpha < 0.5 ? f.est.alpha : 1 - f.est.alpha;
+    const int rc = write_text_file(prefix + ".ErrorFit", [&](std::ostream& fout) {
+        fout << "#SEQ_ID\tFREEMIX\tFREEMIX_FIT\tLRT\tNUM_BIN\tFREELK1_FIT\tFREELK1_NOMINAL\tITERATIONS\tCONVERGED\n";
+        fout << seq_id << "\t" << freemix << "\t" << freemix_fit << "\t" << f.lrt << "\t" << f.num_bin << "\t" << f.llk_fit << "\t"
+             << f.llk_nominal << "\t" << f.num_iter << "\t" << f.converged << "\n";
+    });
+    return rc ? rc : write_error_rates(prefix, f.err, f.n, f.s);
 }
 
 namespace {
@@ -206,6 +254,41 @@ int vb2_errfit_lockstep(const vb2_errfit_fns* fns, void* user, int32_t num_pc, c
     });
 }
 
+int vb2_err_table_read(const char* path, double* err_table, int32_t* num_taken)
+{
+    if (num_taken) *num_taken = 0;
+    if (!path || !err_table) {
+        set_error("vb2_err_table_read: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    return guarded([&]() -> int {
+        std::string error;
+        int taken = 0;
+        if (!vb2::read_err_table(path, err_table, &taken, &error)) {
+            set_error(error);
+            return VB2_ERR_INVALID;
+        }
+        if (num_taken) *num_taken = taken;
+        return VB2_OK;
+    });
+}
+
+int vb2_run_under_table(const vb2_run_args* args, const double* err_table, vb2_run_result* out)
+{
+    if (!args || !out) {
+        set_error("vb2_run_under_table: invalid argument");
+        return VB2_ERR_INVALID;
+    }
+    if (!vb2::err_table_ok(err_table, "vb2_run_under_table")) return VB2_ERR_INVALID;
+    if (args->devices && args->num_device > 1) {
+        set_error("--ErrorTable takes one device: it cannot be combined with marker shards over several --Devices");
+        return VB2_ERR_INVALID;
+    }
+    vb2::RunStage stage;
+    stage.err_table = err_table;
+    return guarded([&] { return vb2::run_sample(args, out, stage); });
+}
+
 int vb2_run_errfit(const vb2_run_args* args, const vb2_errfit_opts* fit_opts, vb2_run_result* out, vb2_errfit* fit)
 {
     if (!args || !out) {
@@ -235,24 +318,8 @@ int vb2_run_errfit(const vb2_run_args* args, const vb2_errfit_opts* fit_opts, vb
         const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         const double freemix = whole.alpha < 0.5 ? whole.alpha : 1 - whole.alpha;
         const double freemix_fit = f->est.alpha < 0.5 ? f->est.alpha : 1 - f->est.alpha;
-        if (args->output_prefix) {
-            int rc = vb2::write_text_file(std::string(args->output_prefix) + ".ErrorFit", [&](std::ostream& fout) {
-                fout << "#SEQ_ID\tFREEMIX\tFREEMIX_FIT\tLRT\tNUM_BIN\tFREELK1_FIT\tFREELK1_NOMINAL\tITERATIONS\tCONVERGED\n";
-                fout << flat.viewer.SEQ_SM << "\t" << freemix << "\t" << freemix_fit << "\t" << f->lrt << "\t" << f->num_bin << "\t"
-                     << f->llk_fit << "\t" << f->llk_nominal << "\t" << f->num_iter << "\t" << f->converged << "\n";
-            });
-            if (rc) return rc;
-            rc = vb2::write_text_file(std::string(args->output_prefix) + ".ErrorRates", [&](std::ostream& fout) {
-                fout << "#Q_REPORTED\tREADS\tEXPECTED_ERRORS\tERROR_RATE\tQ_EMPIRICAL\tSE_BINOM\n";
-                for (int q = 0; q < VB2_ERR_NUM_QUAL; ++q) {
-                    if (f->n[q] <= 0) continue;
-                    const double e = f->err[q];
-                    fout << q << "\t" << (long long)f->n[q] << "\t" << f->s[q] << "\t" << e << "\t" << -10.0 * std::log10(e) << "\t"
-                         << std::sqrt(e * (1.0 - e) / (double)f->n[q]) << "\n";
-                }
-            });
-            if (rc) return rc;
-        }
+        if (args->output_prefix)
+            if (const int rc = vb2::write_errfit_files(args->output_prefix, flat.viewer.SEQ_SM, freemix, *f)) return rc;
         std::fprintf(stderr, "NOTICE - FREEMIX %g with the error rates of %d qualities fitted, %g at 10^(-q/10); LRT %g; %d iterations%s  "
                              "[%lld likelihood evaluations, %.3f seconds]\n", freemix_fit, (int)f->num_bin, freemix, f->lrt,
                      (int)f->num_iter, f->converged ? "" : ", not converged", (long long)f->num_step, seconds);

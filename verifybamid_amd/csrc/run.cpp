@@ -177,7 +177,9 @@ int search_on_context(const vb2_run_args* a, const vb2_flat& flat, const vb2_mod
     vb2_options opt{};
     opt.device = (a->devices && a->num_device == 1) ? a->devices[0] : a->device;
     vb2_ctx* created = nullptr;
-    if (const int rc = vb2_ctx_create(&flat.input, &opt, &created)) return rc;
+    if (const int rc = stage.err_table ? vb2_ctx_create_ex(&flat.input, &opt, stage.err_table, &created)
+                                       : vb2_ctx_create(&flat.input, &opt, &created))
+        return rc;
     std::unique_ptr<vb2_ctx, CtxDestroy> ctx(created);
     out->seconds_load = now_s() - clock.t0;
     if (notices)

@@ -32,6 +32,8 @@ struct RunStage {
     std::function<int(vb2_ctx* ctx, const vb2_flat& flat, const vb2_model& model, const vb2_estimate& est)> on_context;
     // after the run's own writers
     std::function<int(const vb2_run_args& args)> after_writers;
+    // [VB2_ERR_NUM_QUAL] or null: the run's context is made under this error table (vb2_ctx_create_ex; one device)
+    const double* err_table = nullptr;
 };
 
 // vb2_run with a stage; groups (may be null): loaded beside the whole sample (vb2_run_read_groups searches them afterwards).

@@ -75,7 +75,8 @@ namespace vb2 {
     X(baq_lds_kb, 64)      /* --ApplyBAQ: KiB of LDS per workgroup of baq_kernel (four records share them), at most 80: two workgroups a CU */ \
     X(cohort_bam_inflight, 4) /* .bam lines of a cohort between "file opened" and "context created" at once, per device */ \
     /* ---- the error-rate fit (errstat.cpp) ---- */                                                                    \
-    X(errstat_groups, 0)   /* workgroups of errstat_marker_kernel: 0 = four per CU; the results are the same bits */
+    X(errstat_groups, 0)   /* workgroups of errstat_marker_kernel: 0 = four per CU; the results are the same bits */     \
+    X(errstat_multi_groups, 0) /* workgroups PER SAMPLE of errstat_multi_marker_kernel (at most 64): 0 = dealt by marker groups; the same bits */
 
 struct Tunables {
 #define VB2_X(name, dflt) int name = dflt;
